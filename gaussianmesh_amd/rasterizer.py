@@ -187,7 +187,7 @@ _QUEUE_WARNED = [False]
 def _note_stream(stream):
     """Frames pipelined over three or more HIP streams only overlap if the runtime has a hardware queue for each: HIP multiplexes
     streams onto FOUR queues by default and streams that share one serialise (four streams: 4160 frames/s on 4 queues, 5010 on 8,
-    DESIGN.md section 5).  gaussianmesh_amd.configure_runtime() exports GPU_MAX_HW_QUEUES=8 when the integrator calls it before the
+    DESIGN.md section 5).  gaussianmesh_amd.configure_runtime() exports the queue count (at most 2) when the integrator calls it before the
     first HIP call (the package itself never touches the environment).  Warn, once, when the third stream shows up and the variable is
     not set (or was set too late to be read)."""
     if _QUEUE_WARNED[0]:
@@ -203,7 +203,7 @@ def _note_stream(stream):
             warnings.warn("gaussianmesh_amd: frames are being issued on %d HIP streams, but GPU_MAX_HW_QUEUES was not set before the HIP "
                           "runtime started; the runtime multiplexes streams onto 4 hardware queues by default and streams sharing a queue "
                           "serialise (-17 %% on the four-stream loop). Call gaussianmesh_amd.configure_runtime() (or export "
-                          "GPU_MAX_HW_QUEUES=8) before the first torch.cuda call." % len(_STREAMS_SEEN), RuntimeWarning, stacklevel=3)
+                          "GPU_MAX_HW_QUEUES, at most 2) before the first torch.cuda call." % len(_STREAMS_SEEN), RuntimeWarning, stacklevel=3)
 
 
 

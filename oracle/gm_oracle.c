@@ -8,8 +8,8 @@
  * The reference's implementation of that core is CUDA (+cub, +Jittor JIT); it cannot be
  * imported (no jittor) nor built in this image without writing stand-in CUDA headers, which
  * the build rules forbid, and the reference ships no tests / golden vectors.
- * What IS pinned against reference code executed in the dev container (tests/golden/, made by
- * tests/golden/make_golden.py importing /root/reference python modules):
+ * What IS pinned against reference code executed where the reference tree is available (tests/golden/, made by
+ * tests/golden/make_golden.py importing the reference python modules):
  *   - the SH polynomial (orc_sh_to_rgb)      vs  utils/sh_utils.py:eval_sh, edittool/sh_utils.py:eval_sh
  *   - barycentric weights (orc_bary_weights)  vs  edittool/general_utils.py:get_barycentric_coordinate
  *   - camera matrices (python side)           vs  utils/graphics_utils.py:getWorld2View2
@@ -17,7 +17,7 @@
  * (oracle/torch_dense.py: float64, gradients from autograd), by central finite differences of its own forward, and by structural
  * invariants (tests/test_oracle_*.py).
  *
- * Every function cites the reference file:line it restates (paths relative to /root/reference,
+ * Every function cites the reference file:line it restates (paths relative to the reference checkout,
  * RAST = gaussian_renderer/diff_gaussian_rasterizater/cuda_rasterizer).
  *
  * ARITHMETIC CONTRACT (shared with the HIP kernels, see DESIGN.md "arithmetic contract"):

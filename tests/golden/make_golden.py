@@ -1,6 +1,6 @@
-"""Generates tests/golden/*.npz by EXECUTING reference python functions in the dev container.
+"""Generates tests/golden/*.npz by EXECUTING reference python functions.
 
-Runs only where /root/reference exists (never on the GPU box; the fixtures are committed).
+Runs only where the reference tree is available, GM_REFERENCE_TREE=<its path> (the fixtures are committed; the tests never read it).
 The reference modules `import jittor` at module top although the functions used here are pure
 python/numpy arithmetic (eval_sh: "Works with torch/np/jnp").  jittor is not installed in this
 image, so an INERT placeholder module is registered for the import statement only: any attribute
@@ -23,7 +23,7 @@ import types
 
 import numpy as np
 
-REF = "/root/reference"
+REF = os.environ.get("GM_REFERENCE_TREE", "")          # path to the reference checkout
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -42,7 +42,7 @@ def _load(relpath, name):
 
 
 def main():
-    assert os.path.isdir(REF), "reference tree not present; fixtures can only be regenerated in the dev container"
+    assert os.path.isdir(REF), "set GM_REFERENCE_TREE to the reference checkout; the fixtures can only be regenerated there"
     sys.modules.setdefault("jittor", _Inert("jittor"))
     sh_train = _load("utils/sh_utils.py", "ref_utils_sh_utils")
     sh_edit = _load("edittool/sh_utils.py", "ref_edittool_sh_utils")

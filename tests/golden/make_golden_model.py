@@ -1,7 +1,7 @@
 """Generates tests/golden/{cameras.json, cameras_expected.npz, mesh_ply.npz, densify.npz} by EXECUTING the reference's
-own python - model class, camera serialiser, PLY writer / reader logic, optimizer surgery - in the dev container.
+own python - model class, camera serialiser, PLY writer / reader logic, optimizer surgery -.
 
-Runs only where /root/reference exists (never on the GPU box; the fixtures are committed).  Unlike make_golden.py
+Runs only where the reference tree is available, GM_REFERENCE_TREE=<its path> (the fixtures are committed; the tests never read it).  Unlike make_golden.py
 (pure-numpy functions behind an inert jittor placeholder) these functions use tensors, so they run on this package's
 torch-backed `jittor` subset (gaussianmesh_amd.compat): the ARITHMETIC is trivial (indexing, repeat, concat, (a+b)/2, log)
 - what the fixtures pin is the reference's ORDER of rows, attributes and optimizer-state edits, which no formula of ours
@@ -27,7 +27,7 @@ import types
 
 import numpy as np
 
-REF = "/root/reference"
+REF = os.environ.get("GM_REFERENCE_TREE", "")          # path to the reference checkout
 OUT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
 
@@ -128,7 +128,7 @@ def snapshot(g, prefix, out):
 
 
 def main():
-    assert os.path.isdir(REF), "reference tree not present; fixtures can only be regenerated in the dev container"
+    assert os.path.isdir(REF), "set GM_REFERENCE_TREE to the reference checkout; the fixtures can only be regenerated there"
     import gaussianmesh_amd.compat as compat
     jt = compat.install(force=True, operators=True)
     for name in ("plyfile", "igl"):

@@ -14,6 +14,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# ranks sharing the one GPU of the test box: at most six processes may hold a GPU at once, and the test process is one of them
+RANKS = 4
 
 
 def _free_port():
@@ -36,40 +38,44 @@ def _launch(tmp_path, nproc, env_extra, P, W, H, F, steps, warm, batch=None, ext
     return json.loads(lines[0])
 
 
-def test_bench_eight_ranks_walk_the_c4_view_split(tmp_path):
-    """BASELINE config C4's split - 64-camera trajectory, 8 views per rank - as bench.py shards it: `--gpus 8 --cameras 64`, eight
-    ranks on the one GPU of the test box (gloo; a dry run of the launch, the exchange and the sharding, not a measurement): over
-    eight loop steps rank r renders cameras 8r .. 8r+7 and nothing else; one broadcast carries eight steps of vertex positions."""
-    P, W, H, F, steps, warm = 2000, 96, 64, 64, 8, 0
-    out = _launch(tmp_path, 8, dict(GM_BENCH_SHARE_DEVICE="1", GM_BENCH_BACKEND="gloo"), P, W, H, F, steps, warm)
-    assert out["n_gpus"] == 8 and out["config"]["parallelism"] == "views x8" and out["value"] > 0
+def test_bench_four_ranks_walk_the_c4_view_split(tmp_path):
+    """BASELINE config C4's 64-camera trajectory as bench.py shards it over ranks: `--gpus 4 --cameras 64`, four ranks on the one
+    GPU of the test box (gloo; a dry run of the launch, the exchange and the sharding, not a measurement): over sixteen loop steps
+    rank r renders cameras 16r .. 16r+15 and nothing else; one broadcast carries eight steps of vertex positions."""
+    P, W, H, F, warm = 2000, 96, 64, 64, 0
+    per = F // RANKS
+    steps = per
+    out = _launch(tmp_path, RANKS, dict(GM_BENCH_SHARE_DEVICE="1", GM_BENCH_BACKEND="gloo"), P, W, H, F, steps, warm)
+    assert out["n_gpus"] == RANKS and out["config"]["parallelism"] == "views x%d" % RANKS and out["value"] > 0
     assert out["config"]["exchange"]["steps_per_broadcast"] == 8 and out["config"]["exchange"]["bytes_per_step"] == 7500 * 12
     seen = set()
-    for r in range(8):
+    for r in range(RANKS):
         d = np.load(os.path.join(str(tmp_path), "rank%d.npz" % r))
-        assert d["views"].tolist() == list(range(8 * r, 8 * r + 8)), (r, d["views"].tolist())
+        assert d["views"].tolist() == list(range(per * r, per * r + per)), (r, d["views"].tolist())
         assert int(d["overflows"]) == 0 and np.isfinite(d["image"]).all()
         seen.update(d["views"].tolist())
     assert seen == set(range(64))
 
 
-def test_c4_at_full_size_eight_ranks_on_one_gpu(tmp_path):
-    """BASELINE config C4 AT ITS SIZE - the 1 M-Gaussian deformed scene, 1920x1080, 64-camera trajectory, 8 views per rank - with
-    the eight ranks of `bench.py --gpus 8 --cameras 64` sharing the one GPU of the test box (gloo for the exchange; the images do
+def test_c4_at_full_size_four_ranks_on_one_gpu(tmp_path):
+    """BASELINE config C4 AT ITS SIZE - the 1 M-Gaussian deformed scene, 1920x1080, 64-camera trajectory - with the four ranks of
+    `bench.py --gpus 4 --cameras 64` (16 views per rank) sharing the one GPU of the test box (gloo for the exchange; the images do
     not depend on the transport).  Not a measurement: what it shows is that the full-size multi-rank configuration runs end to end
     (one-time broadcast of the 0.3-GB cloud, batched vertex-position broadcasts, every rank deriving (R, S) itself, sync-free
-    four-stream loop) and that a rank renders exactly what a single process renders for its view: rank r walks cameras 8r .. 8r+7,
+    four-stream loop) and that a rank renders exactly what a single process renders for its view: rank r walks cameras 16r .. 16r+15,
     the 64 views are covered once, no frame is lost to an overflow, and the last images of two ranks are bit-identical to
     single-process renders of those (frame, camera) pairs."""
-    P, W, H, F, steps, warm = 1_000_000, 1920, 1080, 64, 8, 0
-    out = _launch(tmp_path, 8, dict(GM_BENCH_SHARE_DEVICE="1", GM_BENCH_BACKEND="gloo"), P, W, H, F, steps, warm)
-    assert out["n_gpus"] == 8 and out["config"]["gaussians"] == P and out["config"]["width"] == W and out["value"] > 0
+    P, W, H, F, warm = 1_000_000, 1920, 1080, 64, 0
+    per = F // RANKS
+    steps = per
+    out = _launch(tmp_path, RANKS, dict(GM_BENCH_SHARE_DEVICE="1", GM_BENCH_BACKEND="gloo"), P, W, H, F, steps, warm)
+    assert out["n_gpus"] == RANKS and out["config"]["gaussians"] == P and out["config"]["width"] == W and out["value"] > 0
     ex = out["config"]["exchange"]
-    assert ex["steps_per_broadcast"] == 8 and ex["bytes_per_step"] == 7500 * 12 and len(ex["ms_per_step_by_rank"]) == 8
+    assert ex["steps_per_broadcast"] == 8 and ex["bytes_per_step"] == 7500 * 12 and len(ex["ms_per_step_by_rank"]) == RANKS
     seen = set()
-    for r in range(8):
+    for r in range(RANKS):
         d = np.load(os.path.join(str(tmp_path), "rank%d.npz" % r))
-        assert d["views"].tolist() == list(range(8 * r, 8 * r + 8)) and int(d["overflows"]) == 0 and np.isfinite(d["image"]).all()
+        assert d["views"].tolist() == list(range(per * r, per * r + per)) and int(d["overflows"]) == 0 and np.isfinite(d["image"]).all()
         seen.update(d["views"].tolist())
     assert seen == set(range(64))
     sys.path.insert(0, ROOT)
@@ -81,10 +87,10 @@ def test_c4_at_full_size_eight_ranks_on_one_gpu(tmp_path):
     g = {k: T(host[k]) for k in ("weights", "pos", "cov", "opac", "shs", "verts")}
     g["tri"] = T(host["tri"], dtype=torch.int32)
     last = warm + 2 * steps - 1                  # (bench.py runs one discarded region of `steps` in front of the timed one)
-    for r in (0, 5):
+    for r in (0, RANKS - 1):
         d = np.load(os.path.join(str(tmp_path), "rank%d.npz" % r))
-        v = multiview.view_for_step(last, F, r, 8)
-        assert int(d["view"]) == v == 8 * r + 7 and int(d["frame"]) == last % F
+        v = multiview.view_for_step(last, F, r, RANKS)
+        assert int(d["view"]) == v == per * r + per - 1 and int(d["frame"]) == last % F
         cam = scenes.orbit_camera(v, F, W, H)
         ct = {n: T(cam[n]) for n in ("view", "proj", "campos")}
         state = mesh_rs(g["verts"], T(host["mesh"][last % F][:, 0:3]), T(host["faces"], dtype=torch.int32), want_state=True)[2]

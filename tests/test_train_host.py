@@ -13,7 +13,7 @@ def test_lr_schedule_matches_the_reference_formula():
 
 def test_schedule_and_defaults_match_values_computed_by_the_reference():
     """tests/golden/schedule.npz: utils/general_utils.py get_expon_lr_func and arguments/__init__.py OptimizationParams
-    executed in the dev container (tests/golden/make_golden.py)."""
+    executed where the reference tree is available (tests/golden/make_golden.py)."""
     import os
     from gaussianmesh_amd.train import DEFAULT_OPT, get_expon_lr_func
     f = np.load(os.path.join(os.path.dirname(__file__), "golden", "schedule.npz"))
