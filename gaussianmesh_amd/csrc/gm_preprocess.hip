@@ -138,6 +138,7 @@ __global__ __launch_bounds__(TH) void preprocess_fwd_kernel(const PreArgs a) {
 #pragma unroll
         for (int c = 0; c < 12; c++) { const float4 v = row[c]; sh[4 * c] = v.x; sh[4 * c + 1] = v.y; sh[4 * c + 2] = v.z; sh[4 * c + 3] = v.w; }
       } else {
+        if (DMA) __builtin_assume((reinterpret_cast<uintptr_t>(a.shs) & 15) == 0);   // launch_preprocess sends only aligned rows here
         load_sh(a.shs, idx, a.M, ncoef, sh);
       }
 #pragma unroll
@@ -179,10 +180,10 @@ int launch_preprocess(const RasterArgs& r, GeomState& g, int* radii) {
     if (a.shs && a.M == 16 && aligned16(a.shs)) {
       hipLaunchKernelGGL((preprocess_fwd_kernel<true, 64, true>), dim3((r.P + 63) / 64), dim3(64), sizeof(float4) * 64 * 12, r.stream, a);
     }
-    else if (a.shs && (a.M == 1 || a.M == 4 || a.M == 12))
+    else if (a.shs && (a.M == 1 || a.M == 4 || a.M == 12) && aligned16(a.shs))
       // a dense [P,1,3] / [P,4,3] / [P,12,3] tensor of the ACTIVE coefficients (the trainer's phases below the full SH degree,
       // train.Trainer(dense_dc)): nothing to stage - 12 / 48 / 144 contiguous bytes per Gaussian, 16-byte loads - but every
-      // per-Gaussian input requested up front, as on the row path
+      // per-Gaussian input requested up front, as on the row path.  Only aligned operands come here (the kernel tells load_sh so)
       hipLaunchKernelGGL((preprocess_fwd_kernel<false, 64, true>), dim3((r.P + 63) / 64), dim3(64), 0, r.stream, a);
     else
       hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3((r.P + 255) / 256), dim3(256), 0, r.stream, a);

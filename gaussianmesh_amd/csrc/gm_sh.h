@@ -37,11 +37,12 @@ __device__ __forceinline__ float sh_channel(int deg, F S, float x, float y, floa
   return r;
 }
 
-// loads the first ncoef SH coefficients (x3 channels) of Gaussian idx into sh[48] with 16-byte loads
+// loads the first ncoef SH coefficients (x3 channels) of Gaussian idx into sh[48]: with 16-byte loads when every row starts on a
+// 16-byte boundary (a row stride of whole granules AND a 16-byte aligned base), else one float at a time
 __device__ __forceinline__ void load_sh(const float* __restrict__ shs, size_t idx, int M, int ncoef, float* sh) {
   const float* base = shs + idx * (size_t)M * 3;
   const int nf = ncoef * 3;
-  if ((((size_t)M * 3) & 3) == 0) {            // rows are 16-byte aligned (M = 16 -> 192 B rows)
+  if ((((size_t)M * 3) & 3) == 0 && (reinterpret_cast<uintptr_t>(shs) & 15) == 0) {   // e.g. M = 16 -> 192 B rows
     const float4* b4 = reinterpret_cast<const float4*>(base);
 #pragma unroll
     for (int k = 0; k < 12; k++) {

@@ -357,8 +357,8 @@ class MeshBoundGaussians(torch.nn.Module):
             owner.begin_dense_active()           # ... and trains the (D+1)^2 active coefficients of the NEW degree densely (below the full degree)
 
     def begin_dense_dc(self, K=None):
-        """K (default (active_sh_degree + 1)^2; round 6: 1, 4 or 9 - round 5 knew K = 1 only): the leading K coefficients of every row as
-        a dense [N,K,3] leaf; the text below is round 5's for K = 1.
+        """K (default (active_sh_degree + 1)^2; 1 or 4, the widths train.Trainer.dense_width gives at degrees 0 and 1 - other K raise
+        ValueError): the leading K coefficients of every row as a dense [N,K,3] leaf; the text below is for K = 1.
         While the model renders at SH degree 0 (the first 1000 iterations of train_mesh_gaussian.py:70-71) only coefficient 0 of every
         192-byte SH row is read, differentiated and stepped - 12 bytes in whole memory sectors of four strided arrays (parameter, gradient,
         both Adam moments).  This moves coefficient 0 into a dense [N,1,3] leaf that the rasterizer takes as `shs` with M = 1
@@ -366,6 +366,8 @@ class MeshBoundGaussians(torch.nn.Module):
         group 0.353 -> 0.026).  Coefficient 0 of `_features` is stale until end_dense_dc() / oneupSHdegree() folds the leaf back;
         get_features / _features_dc always show the current values."""
         K = (self.active_sh_degree + 1) ** 2 if K is None else int(K)
+        if K not in (1, 4):
+            raise ValueError("begin_dense_dc: K = %d; the dense leaf carries 1 or 4 coefficients (SH degree 0 or 1)" % K)
         if K < (self.active_sh_degree + 1) ** 2 or K >= self._features.shape[1]:
             raise ValueError("begin_dense_dc: K = %d coefficients cannot carry SH degree %d of %d-coefficient rows densely" % (
                 K, self.active_sh_degree, self._features.shape[1]))

@@ -400,7 +400,7 @@ class Trainer:
 
     def begin_dense_active(self):
         """After oneupSHdegree() folded the dense leaf into the rows: while the NEW degree is still below the model's full one, the
-        (D+1)^2 active coefficients become the dense leaf again - [N,4,3] at degree 1, [N,9,3] at degree 2 - with both Adam moments of those
+        (D+1)^2 active coefficients become the dense leaf again - [N,4,3] at degree 1 (dense_width) - with both Adam moments of those
         coefficients carried over from the rows' (the new coefficients' are zero: they have never had a gradient).  The rasterizer takes the
         leaf as `shs` with M = (D+1)^2; at the full degree the rows themselves are trained (and stepped inside the backward, fused_sh_step)."""
         g = self.g

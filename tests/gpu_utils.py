@@ -39,15 +39,17 @@ def _view(buf, ptr, count, dtype):
     return buf[off:off + nbytes].view(dtype).cpu().numpy()
 
 
-def forward_state(scene, cam, bg, D=3, use_precomp_cov=False, use_precomp_color=False, mod=1.0, debug=False, tile_cull=False):
+def forward_state(scene, cam, bg, D=3, use_precomp_cov=False, use_precomp_color=False, mod=1.0, debug=False, tile_cull=False, shs=None):
     """Low-level forward returning colour + every intermediate the oracle also exposes.
     tile_cull=False: emit every tile of the rectangle like the reference (lists comparable 1:1 with the oracle);
-    tile_cull=True: the product default (instances the Gaussian cannot reach are not emitted)."""
+    tile_cull=True: the product default (instances the Gaussian cannot reach are not emitted).
+    shs (optional): the [P,M,3] device tensor to pass as the SH operand instead of a fresh copy of scene["shs"] (its layout and
+    alignment pick the preprocess kernel); out["radii_t"] keeps the radii tensor for a following backward."""
     lib = _lib.lib()
     mode = int(tile_cull)
     P = scene["means"].shape[0]
     W, H = cam["W"], cam["H"]
-    sh = None if use_precomp_color else T(scene["shs"])
+    sh = None if use_precomp_color else (T(scene["shs"]) if shs is None else shs)
     col = T(scene["colors_precomp"]) if use_precomp_color else None
     sc = None if use_precomp_cov else T(scene["scales"])
     rot = None if use_precomp_cov else T(scene["rots"])
@@ -59,7 +61,7 @@ def forward_state(scene, cam, bg, D=3, use_precomp_cov=False, use_precomp_color=
     sh_ = max(mode - 1, 0)
     gx, gy = (W + 15) // 16, (H + 15) // 16
     tiles = ((gx + (1 << sh_) - 1) >> sh_) * ((gy + (1 << sh_) - 1) >> sh_)       # lists are per parent tile
-    out = dict(R=nr, color=color.cpu().numpy(), radii=radii.cpu().numpy(), geom=geom, binning=binning, img=img)
+    out = dict(R=nr, color=color.cpu().numpy(), radii=radii.cpu().numpy(), radii_t=radii, geom=geom, binning=binning, img=img)
     if P > 0:
         gp = lambda n: lib.gm_geom_field(geom.data_ptr(), P, n.encode())
         SF = lib.gm_splat_floats()                       # 9: x, y, conic xyz.., opacity, rgb (helpers below index it by name)

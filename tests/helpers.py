@@ -201,3 +201,27 @@ def assert_forward_gate(fw, color, W, H, tol=1e-4, what="", plain_tol=None, bg=N
         assert n_mid_bad == 0, "%s: %d pixel(s) without a threshold flip are off by more than %g" % (what, n_mid_bad, plain_tol)
         assert n_mid <= max(4, 2e-4 * W * H), "%s: %d pixels above %g" % (what, n_mid, plain_tol)
     return n_out
+
+
+def _check_geometry(orc, st, fw, scene, use_precomp_color):
+    """gpu_utils.forward_state against oracle.forward_full: radii, tiles, instance lists and ranges bit-exact, and the per-Gaussian
+    geometry (means2D, conic, opacity, depth key, rgb, clamp bits) of every visible Gaussian bit-identical under the arithmetic contract."""
+    g = fw["geo"]
+    vis = g["radii"] > 0
+    assert np.array_equal(st["radii"], g["radii"])
+    assert np.array_equal(st["tiles"], g["tiles"])
+    assert st["R"] == fw["bins"]["R"]
+    sp = st["splat"]
+    assert np.array_equal(sp[vis, 0:2].view(np.uint32), g["xy"][vis].view(np.uint32))
+    con = np.concatenate([sp[:, 2:4], sp[:, 4:5]], 1)
+    assert np.array_equal(con[vis].view(np.uint32), g["conic_op"][vis, :3].view(np.uint32))
+    assert np.array_equal(sp[vis, 5], g["conic_op"][vis, 3])
+    assert np.array_equal(st["depth_key"][vis], g["depths"][vis].view(np.uint32)) and (st["depth_key"][~vis] == 0xFFFFFFFF).all()
+    rgb = np.concatenate([sp[:, 6:8], sp[:, 8:9]], 1)
+    assert np.array_equal(rgb[vis].view(np.uint32), g["rgb"][vis].view(np.uint32))
+    if not use_precomp_color:
+        cl = np.stack([(st["clamped"] >> c) & 1 for c in range(3)], 1)
+        assert np.array_equal(cl[vis], g["clamped"][vis])
+    assert np.array_equal(st["point_list"], fw["bins"]["point_list"])
+    assert np.array_equal(st["tile_keys"], (fw["bins"]["keys"] >> np.uint64(32)).astype(np.uint32))
+    assert np.array_equal(st["ranges"], fw["bins"]["ranges"])

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import assert_contributor_counts, assert_forward_gate, assert_grads_elementwise, small_scene
+from helpers import _check_geometry, assert_contributor_counts, assert_forward_gate, assert_grads_elementwise, small_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -24,28 +24,6 @@ def _default_emission_policy():
     rasterizer.set_default_emission_policy(2)
 
 MODES = [(False, False), (True, False), (False, True), (True, True)]
-
-
-def _check_geometry(orc, st, fw, scene, use_precomp_color):
-    g = fw["geo"]
-    vis = g["radii"] > 0
-    assert np.array_equal(st["radii"], g["radii"])
-    assert np.array_equal(st["tiles"], g["tiles"])
-    assert st["R"] == fw["bins"]["R"]
-    sp = st["splat"]
-    assert np.array_equal(sp[vis, 0:2].view(np.uint32), g["xy"][vis].view(np.uint32))
-    con = np.concatenate([sp[:, 2:4], sp[:, 4:5]], 1)
-    assert np.array_equal(con[vis].view(np.uint32), g["conic_op"][vis, :3].view(np.uint32))
-    assert np.array_equal(sp[vis, 5], g["conic_op"][vis, 3])
-    assert np.array_equal(st["depth_key"][vis], g["depths"][vis].view(np.uint32)) and (st["depth_key"][~vis] == 0xFFFFFFFF).all()
-    rgb = np.concatenate([sp[:, 6:8], sp[:, 8:9]], 1)
-    assert np.array_equal(rgb[vis].view(np.uint32), g["rgb"][vis].view(np.uint32))
-    if not use_precomp_color:
-        cl = np.stack([(st["clamped"] >> c) & 1 for c in range(3)], 1)
-        assert np.array_equal(cl[vis], g["clamped"][vis])
-    assert np.array_equal(st["point_list"], fw["bins"]["point_list"])
-    assert np.array_equal(st["tile_keys"], (fw["bins"]["keys"] >> np.uint64(32)).astype(np.uint32))
-    assert np.array_equal(st["ranges"], fw["bins"]["ranges"])
 
 
 @pytest.mark.parametrize("use_precomp_cov,use_precomp_color", MODES)

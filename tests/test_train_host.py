@@ -120,3 +120,27 @@ def test_a_rows_trainer_folds_a_model_left_in_dense_mode():
     with pytest.raises(ValueError, match="densify_stats=True"):
         tr.train_iteration(None, None, None)
     assert tr.iteration == 599
+
+
+def test_begin_dense_dc_takes_exactly_the_widths_the_trainer_uses():
+    """begin_dense_dc(K) accepts the K that Trainer.dense_width produces (1 and 4, at SH degrees 0 and 1) and refuses every other K with a
+    ValueError before the model changes: K = 9 at degree 2 included, which would put the rasterizer on the generic [N,9,3] route."""
+    import pytest
+    import torch
+    from gaussianmesh_amd.train import Trainer
+    widths = {Trainer.dense_width(d) for d in range(4)} - {None}
+    assert widths == {1, 4}
+    for deg in range(4):
+        for K in (None, 1, 2, 4, 9, 12, 16):
+            m = _tiny_model()
+            m.active_sh_degree = deg
+            want = (deg + 1) ** 2 if K is None else K
+            if want in widths and want >= (deg + 1) ** 2:
+                leaf = m.begin_dense_dc(K)
+                assert tuple(leaf.shape) == (m._features.shape[0], want, 3)
+                assert torch.equal(leaf.detach(), m._features.detach()[:, :want])
+                m.end_dense_dc()
+            else:
+                with pytest.raises(ValueError, match="begin_dense_dc"):
+                    m.begin_dense_dc(K)
+                assert m._features_dc0 is None
