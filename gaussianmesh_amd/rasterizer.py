@@ -34,7 +34,6 @@ class GaussianRasterizationSettings(NamedTuple):
     work_hint: Optional[torch.Tensor] = None     # extension (new_work_hint()): per-tile cost memory of this camera / view stream
 
 
-
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
@@ -140,7 +139,6 @@ class RasterWorkspace:
         self._bufs = {}
         self._pinned = None
         self._status = None
-        self._event = None
         self.in_flight = None
         self.capacity = 0            # instances the binning buffer holds (sync-free mode)
 
@@ -150,17 +148,12 @@ class RasterWorkspace:
             self._pinned = torch.zeros((1,), dtype=torch.int32).pin_memory()
         return self._pinned
 
-    def pinned_status(self):
+    def status(self):
+        """page-locked int32[4] status words of a sync-free frame and the event recorded behind them: one pair per workspace (a
+        workspace carries one frame at a time, and its event is only recorded again after that frame has been checked and released it)"""
         if self._status is None:
-            self._status = torch.zeros((4,), dtype=torch.int32).pin_memory()
+            self._status = (torch.zeros((4,), dtype=torch.int32).pin_memory(), torch.cuda.Event())
         return self._status
-
-    def status_event(self):
-        """the event recorded behind a sync-free frame's status words: one per workspace (a workspace carries one frame at a
-        time, and its event is only recorded again after that frame has been checked and released it)"""
-        if self._event is None:
-            self._event = torch.cuda.Event()
-        return self._event
 
     def get(self, name, nbytes, device):
         b = self._bufs.get(name)
@@ -195,7 +188,6 @@ def _note_stream(stream):
     _STREAMS_SEEN.add(stream.cuda_stream)
     if len(_STREAMS_SEEN) >= 3:
         _QUEUE_WARNED[0] = True
-        import os
         import warnings
         import gaussianmesh_amd as _pkg
         cfg = _pkg.RUNTIME_CONFIG
@@ -204,9 +196,6 @@ def _note_stream(stream):
                           "runtime started; the runtime multiplexes streams onto 4 hardware queues by default and streams sharing a queue "
                           "serialise (-17 %% on the four-stream loop). Call gaussianmesh_amd.configure_runtime() (or export "
                           "GPU_MAX_HW_QUEUES, at most 2) before the first torch.cuda call." % len(_STREAMS_SEEN), RuntimeWarning, stacklevel=3)
-
-
-
 
 
 def new_work_hint(width, height, device):
@@ -238,17 +227,17 @@ class PendingForward:
     buffer of the workspace is used at its current capacity and the kernels read the count on the device; check()
     later tells whether the frame fitted (False: call finish() again - it then takes the exact path)."""
 
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-        self.status_event = None
+    def __init__(self, policy, workspace, stream, args, geom, img, color, radii, count_host, event, deformed=None, binning=None,
+                 rebegin=None):
+        self.policy, self.workspace, self.stream, self.args = policy, workspace, stream, args
+        self.geom, self.img, self.color, self.radii, self.deformed, self.binning = geom, img, color, radii, deformed, binning
+        self.count_host, self.event = count_host, event      # the instance count's pinned copy and the event behind it (None: not enqueued)
+        self.status_event = self.result = self.known_count = self.work_hint = None
+        self.status_host = None          # pinned status words: sync-free without a workspace (a pooled block, until check()) and _status()
         self.checked = None              # (fitted, num_rendered) once check() has consumed the status
-        self.result = None
-        self.known_count = None
-        self.image_only = False
-        self.exact_exponent = False
-        self.work_hint = None
-        self.direct = False              # begun with direct depth placement (DepthPlan); rebegin re-issues the first half on the partition path
-        self.rebegin = None
+        self.image_only = self.exact_exponent = False
+        self.direct = rebegin is not None    # begun with direct depth placement (DepthPlan); rebegin re-issues the first half on the partition path
+        self.rebegin = rebegin
         self.refusal = 0                 # status word 3 of the checked frame: 1 capacity / policy, 2 direct placement
 
     def _geom(self, binning, num_rendered, capacity, status=None):
@@ -259,6 +248,24 @@ class PendingForward:
                                          None if status is None else status.data_ptr(),
                                          (1 if self.image_only else 0) | (2 if self.exact_exponent else 0),
                                          None if self.work_hint is None else self.work_hint.data_ptr()))
+
+    def _status(self):
+        """The frame's four status words, read now: enqueued into a pinned block, then a wait for the frame's stream."""
+        if self.status_host is None:
+            self.status_host = torch.zeros((4,), dtype=torch.int32).pin_memory()
+        _lib.check(_lib.lib().gm_forward_status_async(_ptr(self.geom), self.args["P"], self.status_host.data_ptr(), self.stream.cuda_stream))
+        self.stream.synchronize()
+        return self.status_host.tolist()
+
+    def _partition_again(self):
+        """The direct depth placement refused the frame (no table yet / stale table / piles of equal depths): the first half again, on
+        the partition path, into the same buffers (rebegin counts the refusal in the DepthPlan); the count is to be read anew."""
+        self.rebegin()
+        self.direct, self.refusal, self.known_count, self.count_host = False, 0, None, None
+
+    def _release(self):
+        if self.workspace is not None:
+            self.workspace.release(self)
 
     def finish(self, sync_free=False, capacity=0, image_only=False, work_hint=None, exact_exponent=False):
         """See _finish().  A failure anywhere in here (allocation, a C-side error) releases the workspace: one failed frame must
@@ -272,8 +279,7 @@ class PendingForward:
         try:
             return self._finish(sync_free, capacity, image_only, work_hint)
         except Exception:
-            if self.workspace is not None:
-                self.workspace.release(self)
+            self._release()
             raise
 
     def _finish(self, sync_free=False, capacity=0, image_only=False, work_hint=None):
@@ -298,52 +304,34 @@ class PendingForward:
         a = self.args
         device = a["device"]
         ws = self.workspace
-        if sync_free and ws is not None and ws.capacity > 0 and a["P"] > 0 and self.status_event is None and self.checked is None:
-            nbytes = lib.gm_binning_bytes(ws.capacity)
-            binning = ws._bufs.get("binning")
-            if binning is not None and binning.device == device and binning.numel() >= nbytes:
-                # steady state of a pipelined render loop: the buffer exists, nothing is allocated, so nothing here depends on
-                # torch's current stream - the launches take the frame's stream explicitly
-                with _on(device):
-                    self._geom(binning, -1, ws.capacity, ws.pinned_status())
-                    self.status_event = ws.status_event()
-                    self.status_event.record(self.stream)
-                self.binning = binning
-                self.result = (-1, self.color, self.radii, self.geom, binning, self.img)
-                return self.result
-        if self.direct and self.refusal == 2 and self.rebegin is not None:
-            # the direct depth placement refused the frame (no table yet / stale table / piles of equal depths): the first half again,
-            # on the partition path, into the same buffers; the exact path below completes it
-            self.rebegin()
-            self.direct, self.refusal, self.known_count, self.count_host = False, 0, None, None
+        cap = capacity if ws is None else ws.capacity
+        if sync_free and cap > 0 and a["P"] > 0 and self.status_event is None and self.checked is None:
+            nbytes = lib.gm_binning_bytes(cap)
+            binning = None if ws is None else ws._bufs.get("binning")
+            with _on(device):
+                if binning is None or binning.device != device or binning.numel() < nbytes:
+                    # (allocating: on the frame's stream.  The steady state of a pipelined loop, the workspace's buffer exists, allocates
+                    # nothing, so nothing in it depends on torch's current stream - the launches take the frame's stream explicitly)
+                    with torch.cuda.stream(self.stream):
+                        binning = torch.empty((nbytes,), dtype=torch.uint8, device=device) if ws is None else ws.get("binning", nbytes, device)
+                if ws is None:
+                    self.status_host = _PINNED_STATUS.pop() if _PINNED_STATUS else torch.zeros((4,), dtype=torch.int32).pin_memory()
+                status, event = (self.status_host, torch.cuda.Event()) if ws is None else ws.status()
+                self._geom(binning, -1, cap, status)          # the blend kernel writes the status words itself
+                event.record(self.stream)
+            self.status_event, self.binning = event, binning
+            self.result = (-1, self.color, self.radii, self.geom, binning, self.img)
+            return self.result
         with _on(device), torch.cuda.stream(self.stream):
-            if sync_free and ws is None and capacity > 0 and a["P"] > 0 and self.status_event is None and self.checked is None:
-                binning = torch.empty((lib.gm_binning_bytes(capacity),), dtype=torch.uint8, device=device)
-                self.status_host = _PINNED_STATUS.pop() if _PINNED_STATUS else torch.zeros((4,), dtype=torch.int32).pin_memory()
-                self._geom(binning, -1, capacity, self.status_host)      # the blend kernel writes the status words itself
-                self.status_event = torch.cuda.Event()
-                self.status_event.record(self.stream)
-                self.capacity = capacity
-                self.result = (-1, self.color, self.radii, self.geom, binning, self.img)
-                return self.result
-            if sync_free and ws is not None and ws.capacity > 0 and a["P"] > 0 and self.status_event is None and self.checked is None:
-                binning = ws.get("binning", lib.gm_binning_bytes(ws.capacity), device)
-                self._geom(binning, -1, ws.capacity, ws.pinned_status())
-                self.status_event = torch.cuda.Event()
-                self.status_event.record(self.stream)
-                self.binning = binning
-                self.result = (-1, self.color, self.radii, self.geom, binning, self.img)
-                return self.result
+            if self.direct and self.refusal == 2:          # check() saw the direct placement refuse the frame; the exact path completes it
+                self._partition_again()
             if self.count_host is not None:
                 self.event.synchronize()
                 num_rendered = int(self.count_host[0])
             elif self.known_count is not None:                       # begun without the count copy; check() has read the status
                 num_rendered = self.known_count
             else:                                                    # begun without the count copy and never checked: fetch it now
-                st = torch.zeros((4,), dtype=torch.int32).pin_memory()
-                _lib.check(lib.gm_forward_status_async(_ptr(self.geom), a["P"], st.data_ptr(), self.stream.cuda_stream))
-                self.stream.synchronize()
-                num_rendered = int(st[0])
+                num_rendered = self._status()[0]
             if ws is not None:
                 ws.capacity = max(ws.capacity, int(num_rendered * ws.growth) + 1024)
                 binning = ws.get("binning", lib.gm_binning_bytes(ws.capacity), device)
@@ -352,28 +340,18 @@ class PendingForward:
                 if self.count_host is not None and len(_PINNED_POOL) < 64:
                     _PINNED_POOL.append(self.count_host)
             self._geom(binning, num_rendered, 0)
-            if self.direct and self.rebegin is not None:
-                # a direct-placement frame completed without the sync-free status protocol: look at its status here (one more
-                # host wait on a path that waits for the count anyway) and take the partition path if it was refused
-                st = torch.zeros((4,), dtype=torch.int32).pin_memory()
-                _lib.check(lib.gm_forward_status_async(_ptr(self.geom), a["P"], st.data_ptr(), self.stream.cuda_stream))
-                self.stream.synchronize()
-                if int(st[3]) == 2:
-                    self.rebegin()
-                    _lib.check(lib.gm_forward_status_async(_ptr(self.geom), a["P"], st.data_ptr(), self.stream.cuda_stream))
-                    self.stream.synchronize()
-                    num_rendered = int(st[0])
-                    self._geom(binning, num_rendered, 0)          # (the instance total does not depend on the depth path)
-                self.direct = False
+            # a direct-placement frame completed without the sync-free status protocol: look at its status here (one more host wait
+            # on a path that waits for the count anyway) and take the partition path if it was refused
+            if self.direct and self._status()[3] == 2:
+                self._partition_again()
+                num_rendered = self._status()[0]
+                self._geom(binning, num_rendered, 0)          # (the instance total does not depend on the depth path)
+            self.direct = False
             self.status_event = None
-            if a.get("prefiltered") and a["P"] > 0:         # the reference traps the kernel (auxiliary.h:155-159); here: an error
-                st = torch.zeros((4,), dtype=torch.int32).pin_memory()
-                _lib.check(lib.gm_forward_status_async(_ptr(self.geom), a["P"], st.data_ptr(), self.stream.cuda_stream))
-                self.stream.synchronize()
-                if int(st[1]):
-                    raise _lib.GmeshError(_PREFILTER_MESSAGE)
-        if ws is not None:
-            ws.release(self)
+            if a.get("prefiltered") and a["P"] > 0 and self._status()[1]:   # the reference traps the kernel (auxiliary.h:155-159); here: an error
+                raise _lib.GmeshError(_PREFILTER_MESSAGE)
+        self._release()
+        self.binning = binning
         self.result = (num_rendered, self.color, self.radii, self.geom, binning, self.img)
         return self.result
 
@@ -384,38 +362,25 @@ class PendingForward:
         pass through it, so a second look through an old handle must not read what a later frame left there - it returns the
         answer the first call recorded."""
         if self.status_event is None:
-            if self.checked is not None:
-                return self.checked
-            return True, (self.result[0] if self.result else 0)
+            return self.checked or (True, (self.result[0] if self.result else 0))
         ws = self.workspace
         if ws is not None and ws.in_flight is not self:
             raise _lib.GmeshError("PendingForward.check(): the workspace of this frame has been released and reacquired; its status "
                                   "words now belong to a later frame")
         self.status_event.synchronize()
         self.status_event = None
-        if ws is None:
-            st = self.status_host
-            nr, refused, violated = int(st[0]), int(st[3]), int(st[1])
-            self.refusal = refused
-            self.known_count = nr
-            if len(_PINNED_STATUS) < 64:
-                _PINNED_STATUS.append(st)
-            self.status_host = None
-            self.checked = ((not refused), nr)
-            if violated and self.args.get("prefiltered"):
-                raise _lib.GmeshError(_PREFILTER_MESSAGE)
-            return self.checked
-        st = ws.pinned_status()
-        nr, refused = int(st[0]), int(st[3])
-        self.refusal = refused
-        self.known_count = nr
+        st = self.status_host if ws is None else ws.status()[0]
+        nr, violated, _, refused = st.tolist()
+        self.refusal, self.known_count = refused, nr
         self.checked = ((not refused), nr)
-        if int(st[1]) and self.args.get("prefiltered"):
-            ws.release(self)
+        if ws is None and len(_PINNED_STATUS) < 64:
+            _PINNED_STATUS.append(st)
+        self.status_host = None
+        if violated and self.args.get("prefiltered"):
+            self._release()
             raise _lib.GmeshError(_PREFILTER_MESSAGE)
-        if refused:                      # still holds the workspace: finish() renders the frame again on the exact path
-            return self.checked
-        ws.release(self)
+        if not refused:                  # a refused frame still holds the workspace: finish() renders it again on the exact path
+            self._release()
         return self.checked
 
 
@@ -425,21 +390,48 @@ _PINNED_POOL = []          # page-locked int32[1] counters of workspace-less for
 _PINNED_STATUS = []        # page-locked int32[4] status words of sync-free forwards without a workspace
 
 
-def _scratch(workspace, P, W, H, device):
+def _scratch(workspace, P, W, H, device, count_stream=None):
+    """A frame's outputs (colour [3,H,W], radii [P]) and geometry / image buffers (the workspace's, or fresh ones); with count_stream
+    also a page-locked int32[1] for the instance count and an event recorded on that stream, which the library re-records right
+    behind the count's copy (it needs a live hipEvent_t handle)."""
     lib = _lib.lib()
+    color = torch.empty((3, H, W), dtype=torch.float32, device=device)
+    radii = torch.empty((P,), dtype=torch.int32, device=device)
     if workspace is not None:
-        return (workspace.get("geom", lib.gm_geom_bytes(P), device), workspace.get("img", lib.gm_image_bytes(W, H), device),
-                workspace.pinned_counter())
-    count = _PINNED_POOL.pop() if _PINNED_POOL else torch.zeros((1,), dtype=torch.int32).pin_memory()
-    return (torch.empty((lib.gm_geom_bytes(P),), dtype=torch.uint8, device=device),
-            torch.empty((lib.gm_image_bytes(W, H),), dtype=torch.uint8, device=device), count)
+        geom, img = workspace.get("geom", lib.gm_geom_bytes(P), device), workspace.get("img", lib.gm_image_bytes(W, H), device)
+    else:
+        geom, img = (torch.empty((n,), dtype=torch.uint8, device=device) for n in (lib.gm_geom_bytes(P), lib.gm_image_bytes(W, H)))
+    count = event = None
+    if count_stream is not None:
+        if workspace is not None:
+            count = workspace.pinned_counter()
+        else:
+            count = _PINNED_POOL.pop() if _PINNED_POOL else torch.zeros((1,), dtype=torch.int32).pin_memory()
+        event = torch.cuda.Event()
+        event.record(count_stream)
+    return color, radii, geom, img, count, event
 
 
-def _count_event(stream):
-    """an event the library re-records right behind the instance-count copy (needs a live hipEvent_t handle)"""
-    ev = torch.cuda.Event()
-    ev.record(stream)
-    return ev
+def _begin(device, workspaces, issue):
+    """The preamble of the three begin functions: the device check, the frame's stream (torch's current one), and the workspaces,
+    held by this call (owner: `issue`) while issue(stream) enqueues the frames and returns their handles, one per workspace, then
+    handed over to them.  A failure releases every workspace this call acquired."""
+    if device.type != "cuda":
+        raise _lib.GmeshError("gaussianmesh_amd rasterizer needs tensors on a HIP (cuda) device; there is no CPU path")
+    stream = _current_stream(device)
+    _note_stream(stream)
+    try:
+        for ws in workspaces:
+            ws.acquire(issue)
+        with _on(device):
+            handles = issue(stream)
+    except Exception:
+        for ws in workspaces:
+            ws.release(issue)
+        raise
+    for ws, h in zip(workspaces, handles):
+        ws.in_flight = h
+    return handles
 
 
 def rasterize_forward_begin(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -449,8 +441,6 @@ def rasterize_forward_begin(bg, means3D, colors, opacity, scales, rotations, sca
     Typical loop: h_next = begin(frame i+1, workspace=ws[(i+1) % 2]); outputs = h_cur.finish()."""
     lib = _lib.lib()
     device = means3D.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("gaussianmesh_amd rasterizer needs tensors on a HIP (cuda) device; there is no CPU path")
     policy = _pol(emission_policy, image_width, image_height)
     means3D = _prep(means3D, device)
     P = 0 if means3D is None else means3D.shape[0]
@@ -463,30 +453,18 @@ def rasterize_forward_begin(bg, means3D, colors, opacity, scales, rotations, sca
         M = sh.shape[1] if sh.dim() == 3 else sh.numel() // (3 * max(P, 1))
     if force_M is not None and sh is not None and M != force_M:
         raise ValueError("NewGaussianRasterizer expects shs of shape [P,%d,3]" % force_M)
-    stream = _current_stream(device)
-    _note_stream(stream)
-    h = PendingForward(policy=policy, workspace=workspace, stream=stream)
-    if workspace is not None:
-        workspace.acquire(h)
-    try:
-        with _on(device):
-            color = torch.empty((3, H, W), dtype=torch.float32, device=device)
-            radii = torch.empty((P,), dtype=torch.int32, device=device)
-            geom, img, count_host = _scratch(workspace, P, W, H, device)
-            event = _count_event(stream)
-            _lib.check(lib.gm_forward_0_async(policy, _ptr(geom), P, int(degree), M, _ptr(bg), W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
-                                              _ptr(opacity), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                                              _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy),
-                                              int(bool(prefiltered)), _ptr(radii), int(bool(debug)), stream.cuda_stream,
-                                              count_host.data_ptr(), event.cuda_event))
-    except Exception:
-        if workspace is not None:
-            workspace.release(h)
-        raise
-    h.args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)), prefiltered=bool(prefiltered),
-                  keep=(means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos))
-    h.geom, h.img, h.color, h.radii, h.count_host, h.event = geom, img, color, radii, count_host, event
-    return h
+
+    def issue(stream):
+        color, radii, geom, img, count_host, event = _scratch(workspace, P, W, H, device, stream)
+        _lib.check(lib.gm_forward_0_async(policy, _ptr(geom), P, int(degree), M, _ptr(bg), W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
+                                          _ptr(opacity), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
+                                          _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy),
+                                          int(bool(prefiltered)), _ptr(radii), int(bool(debug)), stream.cuda_stream,
+                                          count_host.data_ptr(), event.cuda_event))
+        args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)), prefiltered=bool(prefiltered),
+                    keep=(means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos))
+        return [PendingForward(policy, workspace, stream, args, geom, img, color, radii, count_host, event)]
+    return _begin(device, () if workspace is None else (workspace,), issue)[0]
 
 
 def rasterize_forward(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -515,8 +493,6 @@ def forward_deformed_begin(bg, tri, weights, packed, cov, pos, shs, opacity, vie
     check() them, or the status of a refused frame goes unseen."""
     lib = _lib.lib()
     device = pos.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("gaussianmesh_amd rasterizer needs tensors on a HIP (cuda) device; there is no CPU path")
     policy = _pol(emission_policy, image_width, image_height)
     P, M = pos.shape[0], shs.shape[1]
     if tri.dtype is not torch.int32 or not tri.is_contiguous():
@@ -524,55 +500,37 @@ def forward_deformed_begin(bg, tri, weights, packed, cov, pos, shs, opacity, vie
     weights, packed, cov, pos, shs, opacity = (_prep(t, device) for t in (weights, packed, cov, pos, shs, opacity))   # None when empty
     bg, viewmatrix, projmatrix, campos = (_prep(t, device) for t in (bg, viewmatrix, projmatrix, campos))
     H, W = int(image_height), int(image_width)
-    stream = _current_stream(device)
-    _note_stream(stream)
-    h = PendingForward(policy=policy, workspace=workspace, stream=stream)
-    if workspace is not None:
-        workspace.acquire(h)
-    try:
-        with _on(device):
-            f = dict(dtype=torch.float32, device=device)
-            color = torch.empty((3, H, W), **f)
-            radii = torch.empty((P,), dtype=torch.int32, device=device)
-            deformed = (torch.empty((P, 3), **f), torch.empty((P, 6), **f), torch.empty((P, 3), **f)) if want_deformed else None
-            geom, img, count_host = _scratch(workspace, P, W, H, device)
-            dp = [None, None, None] if deformed is None else [t.data_ptr() for t in deformed]
-            event = _count_event(stream) if want_count else None
-            if not want_count:
-                count_host = None
-            cov6 = cov is not None and cov.dim() == 2 and cov.shape[1] == 6       # deform.pack_cov6(): GM_STREAM_COV6
-            direct = depth_plan is not None and depth_plan.primed and P > 0
-            slab = None
-            if direct:
-                nbytes = lib.gm_depth_slab_bytes(P)
-                slab = workspace.get("slab", nbytes, device) if workspace is not None else torch.empty((nbytes,), dtype=torch.uint8, device=device)
 
-            def begin(direct_now, count_ptr, event_ptr):
-                _lib.check(lib.gm_forward_0_deformed_stream_async(
-                    policy, _ptr(geom), P, int(degree), M, W, H, _ptr(tri), _ptr(weights), _ptr(packed), _ptr(cov), _ptr(pos), _ptr(shs),
-                    _ptr(opacity), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), dp[0], dp[1], dp[2],
-                    _ptr(radii), int(bool(debug)), stream.cuda_stream, count_ptr, event_ptr, _ptr(slab) if direct_now else None,
-                    None if depth_plan is None else depth_plan.buf.data_ptr(), (1 if direct_now else 0) | (2 if cov6 else 0)))
+    def issue(stream):
+        color, radii, geom, img, count_host, event = _scratch(workspace, P, W, H, device, stream if want_count else None)
+        deformed = tuple(torch.empty((P, n), dtype=torch.float32, device=device) for n in (3, 6, 3)) if want_deformed else None
+        dp = [None, None, None] if deformed is None else [t.data_ptr() for t in deformed]
+        cov6 = cov is not None and cov.dim() == 2 and cov.shape[1] == 6       # deform.pack_cov6(): GM_STREAM_COV6
+        direct = depth_plan is not None and depth_plan.primed and P > 0
+        slab = None
+        if direct:
+            nbytes = lib.gm_depth_slab_bytes(P)
+            slab = workspace.get("slab", nbytes, device) if workspace is not None else torch.empty((nbytes,), dtype=torch.uint8, device=device)
 
-            begin(direct, None if count_host is None else count_host.data_ptr(), None if event is None else event.cuda_event)
-            if depth_plan is not None and P > 0:
-                depth_plan.primed = True               # (this frame, whichever path it took, leaves a table behind)
-    except Exception:
-        if workspace is not None:
-            workspace.release(h)
-        raise
-    h.args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)),
-                  keep=(tri, weights, packed, cov, pos, shs, opacity, viewmatrix, projmatrix, campos))
-    h.geom, h.img, h.color, h.radii, h.count_host, h.event, h.deformed = geom, img, color, radii, count_host, event, deformed
-    if direct:
-        h.direct = True
+        def begin(direct_now, count_ptr, event_ptr):
+            _lib.check(lib.gm_forward_0_deformed_stream_async(
+                policy, _ptr(geom), P, int(degree), M, W, H, _ptr(tri), _ptr(weights), _ptr(packed), _ptr(cov), _ptr(pos), _ptr(shs),
+                _ptr(opacity), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), dp[0], dp[1], dp[2],
+                _ptr(radii), int(bool(debug)), stream.cuda_stream, count_ptr, event_ptr, _ptr(slab) if direct_now else None,
+                None if depth_plan is None else depth_plan.buf.data_ptr(), (1 if direct_now else 0) | (2 if cov6 else 0)))
 
-        def rebegin():
+        def rebegin():                             # (PendingForward._partition_again, under the frame's device)
             depth_plan.refused += 1
-            with _on(device):
-                begin(False, None, None)
-        h.rebegin = rebegin
-    return h
+            begin(False, None, None)
+
+        begin(direct, None if count_host is None else count_host.data_ptr(), None if event is None else event.cuda_event)
+        if depth_plan is not None and P > 0:
+            depth_plan.primed = True               # (this frame, whichever path it took, leaves a table behind)
+        args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)),
+                    keep=(tri, weights, packed, cov, pos, shs, opacity, viewmatrix, projmatrix, campos))
+        return [PendingForward(policy, workspace, stream, args, geom, img, color, radii, count_host, event, deformed=deformed,
+                               rebegin=rebegin if direct else None)]
+    return _begin(device, () if workspace is None else (workspace,), issue)[0]
 
 
 def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity, cameras, image_height, image_width, degree, workspaces,
@@ -586,8 +544,6 @@ def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity
     through the single-frame second half.  Each frame comes out bit for bit as from forward_deformed_begin(...).finish(sync_free=True)."""
     lib = _lib.lib()
     device = pos.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("gaussianmesh_amd rasterizer needs tensors on a HIP (cuda) device; there is no CPU path")
     K = len(packed_list)
     if not (1 <= K <= _lib.GM_BATCH_MAX) or len(cameras) != K or len(workspaces) != K:
         raise ValueError("forward_deformed_batch: 1..%d frames, one camera and one workspace each" % _lib.GM_BATCH_MAX)
@@ -599,50 +555,37 @@ def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity
         tri = tri.detach().contiguous().to(torch.int32)
     weights, cov, pos, shs, opacity, bg = (_prep(t, device) for t in (weights, cov, pos, shs, opacity, bg))
     H, W = int(image_height), int(image_width)
-    stream = _current_stream(device)
-    _note_stream(stream)
     cap = max(ws.capacity for ws in workspaces)
     if cap <= 0:
         raise _lib.GmeshError("forward_deformed_batch: the workspaces have no capacity yet - complete one frame of the stream through "
                               "forward_deformed_begin(...).finish() first (the batch is sync-free: it cannot size the binning buffers)")
     cov6 = cov is not None and cov.dim() == 2 and cov.shape[1] == 6
     get = lambda c, k: c[k] if isinstance(c, dict) else getattr(c, k)
-    handles, frames, keep = [], (_lib.BatchFrame * K)(), []
-    try:
-        with _on(device), torch.cuda.stream(stream):
-            nbin = lib.gm_binning_bytes(cap)
-            for k in range(K):
-                ws, c = workspaces[k], cameras[k]
-                h = PendingForward(policy=policy, workspace=ws, stream=stream)
-                ws.acquire(h)
-                handles.append(h)
-                ws.capacity = cap
-                color = torch.empty((3, H, W), dtype=torch.float32, device=device)
-                radii = torch.empty((P,), dtype=torch.int32, device=device)
-                geom, img, _ = _scratch(ws, P, W, H, device)
-                binning = ws.get("binning", nbin, device)
-                view, proj, campos, packed = (_prep(t, device) for t in (get(c, "view"), get(c, "proj"), get(c, "campos"), packed_list[k]))
-                keep.append((view, proj, campos, packed))
-                f = frames[k]
-                f.packed, f.viewmatrix, f.projmatrix, f.cam_pos = packed.data_ptr(), view.data_ptr(), proj.data_ptr(), campos.data_ptr()
-                f.tan_fovx, f.tan_fovy = float(get(c, "tanx")), float(get(c, "tany"))
-                f.geom_buffer, f.binning_buffer, f.image_buffer = geom.data_ptr(), binning.data_ptr(), img.data_ptr()
-                f.out_color, f.radii, f.status_host = color.data_ptr(), radii.data_ptr(), ws.pinned_status().data_ptr()
-                h.args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)), keep=(tri, weights, cov, pos, shs, opacity, keep[-1]))
-                h.geom, h.img, h.color, h.radii, h.count_host, h.event, h.deformed, h.binning = geom, img, color, radii, None, None, None, binning
-                h.image_only, h.work_hint = bool(image_only), work_hint
-            _lib.check(lib.gm_forward_deformed_batch_async(policy, K, frames, P, int(degree), M, W, H, _ptr(tri), _ptr(weights), _ptr(cov), _ptr(pos), _ptr(shs),
-                                                           _ptr(opacity), _ptr(bg), cap, (1 if image_only else 0) | (2 if cov6 else 0),
-                                                           None if work_hint is None else work_hint.data_ptr(), int(bool(debug)), stream.cuda_stream))
-            for h in handles:
-                h.status_event = h.workspace.status_event()
-                h.status_event.record(stream)
-                h.result = (-1, h.color, h.radii, h.geom, h.binning, h.img)
-    except Exception:
+
+    def issue(stream):
+        handles, frames = [], (_lib.BatchFrame * K)()
+        nbin = lib.gm_binning_bytes(cap)
+        for k, (ws, c) in enumerate(zip(workspaces, cameras)):
+            ws.capacity = cap
+            color, radii, geom, img, _, _ = _scratch(ws, P, W, H, device)
+            binning = ws.get("binning", nbin, device)
+            view, proj, campos, packed = (_prep(t, device) for t in (get(c, "view"), get(c, "proj"), get(c, "campos"), packed_list[k]))
+            f = frames[k]
+            f.packed, f.viewmatrix, f.projmatrix, f.cam_pos = packed.data_ptr(), view.data_ptr(), proj.data_ptr(), campos.data_ptr()
+            f.tan_fovx, f.tan_fovy = float(get(c, "tanx")), float(get(c, "tany"))
+            f.geom_buffer, f.binning_buffer, f.image_buffer = geom.data_ptr(), binning.data_ptr(), img.data_ptr()
+            f.out_color, f.radii, f.status_host = color.data_ptr(), radii.data_ptr(), ws.status()[0].data_ptr()
+            args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)), keep=(tri, weights, cov, pos, shs, opacity, (view, proj, campos, packed)))
+            handles.append(PendingForward(policy, ws, stream, args, geom, img, color, radii, None, None, binning=binning))
+        _lib.check(lib.gm_forward_deformed_batch_async(policy, K, frames, P, int(degree), M, W, H, _ptr(tri), _ptr(weights), _ptr(cov), _ptr(pos), _ptr(shs),
+                                                       _ptr(opacity), _ptr(bg), cap, (1 if image_only else 0) | (2 if cov6 else 0),
+                                                       None if work_hint is None else work_hint.data_ptr(), int(bool(debug)), stream.cuda_stream))
         for h in handles:
-            h.workspace.release(h)
-        raise
-    return handles
+            h.status_event = h.workspace.status()[1]
+            h.status_event.record(stream)
+            h.result = (-1, h.color, h.radii, h.geom, h.binning, h.img)
+        return handles
+    return _begin(device, workspaces, issue)
 
 
 def rasterize_backward(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,

@@ -36,7 +36,7 @@ def _state(h, P, W, H, policy, nr):
     from gpu_utils import _view
     from gaussianmesh_amd import _lib
     lib = _lib.lib()
-    geom, binning, img = h.geom, h.binning if getattr(h, "binning", None) is not None else h.result[4], h.img
+    geom, binning, img = h.geom, h.binning, h.img
     gp = lambda n: lib.gm_geom_field(geom.data_ptr(), P, n.encode())
     out = {"radii": h.radii.cpu().numpy(), "color": h.color.cpu().numpy()}
     SF = lib.gm_splat_floats()

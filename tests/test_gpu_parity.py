@@ -685,6 +685,37 @@ def test_sync_free_forward_matches_exact_and_reports_overflow():
     h1.finish()
 
 
+def test_sync_free_finish_on_a_sized_workspace_allocates_nothing():
+    """The steady state of a pipelined render loop: finish(sync_free=True) on a workspace whose binning buffer already holds its
+    capacity allocates no device memory (begin allocates the frame's image and radii; finish only enqueues) and does not depend on
+    torch's current stream - the frame is begun on a side stream and finished under another one."""
+    from gpu_utils import T
+    from gaussianmesh_amd import rasterizer as Rz, scenes
+    sc = scenes.make_cloud(20000, seed=6, scale_lo=0.01, scale_hi=0.15)
+    cams = [scenes.orbit_camera(k, 8, 320, 200, radius=7.5) for k in range(3)]
+    bg = T(np.array([0.1, 0.2, 0.3], np.float32))
+    def args(k):
+        ct = {n: T(cams[k][n]) for n in ("view", "proj", "campos")}
+        return (bg, T(sc["means"]), None, T(sc["opac"]), T(sc["scales"]), T(sc["rots"]), 1.0, None, ct["view"], ct["proj"], cams[k]["tanx"],
+                cams[k]["tany"], 200, 320, T(sc["shs"]), 3, ct["campos"])
+    ref = [Rz.rasterize_forward(*args(k), False, False) for k in range(3)]
+    ws = Rz.RasterWorkspace()
+    Rz.rasterize_forward_begin(*args(0), workspace=ws).finish()          # sizes the capacity and the binning buffer
+    side = torch.cuda.Stream()
+    for k in (1, 2):
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            h = Rz.rasterize_forward_begin(*args(k), workspace=ws)
+        torch.cuda.synchronize()
+        before = torch.cuda.memory_stats()["allocation.all.allocated"]
+        nr, color, radii, *_ = h.finish(sync_free=True)
+        after = torch.cuda.memory_stats()["allocation.all.allocated"]
+        assert nr == -1 and after == before
+        ok, count = h.check()
+        assert ok and count == ref[k][0] and torch.equal(color, ref[k][1]) and torch.equal(radii, ref[k][2])
+        assert ws.in_flight is None and h.binning is not None
+
+
 def test_fused_frame_edge_cases():
     """Edit-loop fast path on an empty cloud, a one-Gaussian cloud and a cloud entirely behind the camera."""
     from gpu_utils import T
