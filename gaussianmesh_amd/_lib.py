@@ -43,6 +43,8 @@ SIGNATURES = {
                           vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "gm_backward_p": (i32, [i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp,
                             vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "gm_backward_aux": (i32, [i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp,
+                              vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "gm_backward_sh_step": (i32, [i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                   vp, i32, vp, vp, f32, f32, f64, f64, f64, i32, i32, vp]),
     "gm_mark_visible": (i32, [i32, vp, vp, vp, vp, vp]),
@@ -63,6 +65,7 @@ SIGNATURES = {
     "gm_depth_plan_bytes": (sz, []),
     "gm_depth_slab_bytes": (sz, [i32]),
     "gm_forward_1_geom": (i32, [i32, vp, vp, vp, i32, i32, i64, vp, i32, i32, vp, i32, vp, vp, i32, vp]),
+    "gm_forward_1_aux": (i32, [i32, vp, vp, vp, i32, i32, i64, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp]),
     "gm_forward_status_async": (i32, [vp, i32, vp, vp]),
     "gm_forward_deformed_batch_async": (i32, [i32, i32, C.POINTER(BatchFrame), i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, i32, vp]),
     "gm_mesh_rs_packed_batch": (i32, [i32, i32, i32, vp, C.POINTER(vp), vp, vp, vp, C.POINTER(vp), vp]),

@@ -208,6 +208,7 @@ int gm_forward_0_deformed_stream_async(int emission_policy, void* geom_buffer, i
   if (direct) {
     DepthSlab d = DepthSlab::from(depth_slab, (size_t)P);
     if (int rc = launch_arm_direct(g, d, depth_plan, a.stream)) return rc;
+    GM_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g.counters + GM_CNT_DEPTH_STALE), 1, 1, a.stream));   // no depth_key: gm_forward_1_aux refuses the frame
     if (int rc = launch_deform_shade_pre(a, g, radii, deg, tri, w, packed, cov, pos, shs, pos_out, cov6_out, rgb_out, &d, cov6)) return rc;
     if (debug_stop_after() == 1) return GM_OK;
     return launch_depth_order_direct(g, d, depth_plan, P, debug, a.stream, num_rendered_host, reinterpret_cast<hipEvent_t>(count_event));
@@ -219,9 +220,9 @@ int gm_forward_0_deformed_stream_async(int emission_policy, void* geom_buffer, i
   return GM_OK;
 }
 
-int gm_forward_1_geom(int emission_policy, void* geom_buffer, void* binning_buffer, void* image_buffer, int P, int num_rendered,
-                      int64_t binning_capacity, const float* background, int width, int height, float* out_color, int debug, void* stream,
-                      int* status_host, int flags, unsigned int* work_hint) {
+static int forward_1_impl(int emission_policy, void* geom_buffer, void* binning_buffer, void* image_buffer, int P, int num_rendered,
+                          int64_t binning_capacity, const float* background, int width, int height, float* out_color, int debug, void* stream,
+                          int* status_host, int flags, unsigned int* work_hint, bool aux, float* out_depth, float* out_alpha) {
   if (int rc = check_policy(emission_policy)) return rc;
   if (flags & ~(GM_FWD_IMAGE_ONLY | GM_FWD_EXACT_EXPONENT)) { set_error("unknown flags 0x%x", flags); return GM_ERR_INVALID_ARG; }
   if ((flags & GM_FWD_IMAGE_ONLY) && (flags & GM_FWD_EXACT_EXPONENT)) {
@@ -262,7 +263,33 @@ int gm_forward_1_geom(int emission_policy, void* geom_buffer, void* binning_buff
   }
   if (debug_stop_after() == 4) return GM_OK;
   return launch_render_fwd(g, b.pairs[slot], img, width, height, mode, background, out_color, status_host, (flags & GM_FWD_IMAGE_ONLY) != 0,
-                           work_hint, debug, st, (flags & GM_FWD_EXACT_EXPONENT) != 0);
+                           work_hint, debug, st, (flags & GM_FWD_EXACT_EXPONENT) != 0, nullptr, out_depth, out_alpha, aux,
+                           P > 0 ? g.counters : nullptr);
+}
+
+int gm_forward_1_geom(int emission_policy, void* geom_buffer, void* binning_buffer, void* image_buffer, int P, int num_rendered,
+                      int64_t binning_capacity, const float* background, int width, int height, float* out_color, int debug, void* stream,
+                      int* status_host, int flags, unsigned int* work_hint) {
+  return forward_1_impl(emission_policy, geom_buffer, binning_buffer, image_buffer, P, num_rendered, binning_capacity, background, width, height,
+                        out_color, debug, stream, status_host, flags, work_hint, false, nullptr, nullptr);
+}
+
+// [a, a + na) and [b, b + nb) (floats) share memory
+static bool overlaps(const float* a, size_t na, const float* b, size_t nb) {
+  return a && b && a < b + nb && b < a + na;
+}
+
+int gm_forward_1_aux(int emission_policy, void* geom_buffer, void* binning_buffer, void* image_buffer, int P, int num_rendered,
+                     int64_t binning_capacity, const float* background, int width, int height, float* out_color, int debug, void* stream,
+                     int* status_host, int flags, unsigned int* work_hint, float* out_depth, float* out_alpha) {
+  if (width > 0 && height > 0) {
+    const size_t HW = (size_t)width * height;
+    if (overlaps(out_depth, HW, out_color, 3 * HW) || overlaps(out_alpha, HW, out_color, 3 * HW) || overlaps(out_depth, HW, out_alpha, HW)) {
+      set_error("gm_forward_1_aux: out_depth / out_alpha overlap out_color or each other"); return GM_ERR_INVALID_ARG;
+    }
+  }
+  return forward_1_impl(emission_policy, geom_buffer, binning_buffer, image_buffer, P, num_rendered, binning_capacity, background, width, height,
+                        out_color, debug, stream, status_host, flags, work_hint, true, out_depth, out_alpha);
 }
 
 int gm_forward_deformed_batch_async(int emission_policy, int K, const gm_batch_frame* frames, int P, int deg, int M, int width, int height,
@@ -381,7 +408,8 @@ static int backward_impl(int emission_policy, int P, int D, int M, int R, const 
                          const float* campos, float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
                          void* binning_buffer, void* image_buffer, const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
                          float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                         float* dL_dscale, float* dL_drot, int debug, void* stream, const ShAdamArgs* sh_adam) {
+                         float* dL_dscale, float* dL_drot, int debug, void* stream, const ShAdamArgs* sh_adam,
+                         const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr, float* dL_dz = nullptr) {
   if (int rc = check_policy(emission_policy)) return rc;
   const float* opacities = reinterpret_cast<const float*>(1);   // not used by backward; satisfies the shared check
   const float* cam_pos = campos;
@@ -402,10 +430,31 @@ static int backward_impl(int emission_policy, int P, int D, int M, int R, const 
   GM_HIP(hipMemsetAsync(g.grad_acc, 0, sizeof(float) * 12 * (size_t)P, a.stream));   // the only zero-fill of a backward
   if (R > 0) {
     if (!binning_buffer) { set_error("gm_backward: null binning buffer"); return GM_ERR_INVALID_ARG; }
-    if (int rc = launch_render_bwd(g, b.pairs[slot], img, width, height, a.tile_cull, background, dL_dpix, debug, a.stream)) return rc;
+    if (int rc = launch_render_bwd(g, b.pairs[slot], img, width, height, a.tile_cull, background, dL_dpix, debug, a.stream,
+                                   dL_ddepth || dL_dalpha, dL_ddepth, dL_dalpha)) return rc;
   }
-  return launch_preprocess_bwd(a, g, radii, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                               dL_dscale, dL_drot, sh_adam);
+  if (int rc = launch_preprocess_bwd(a, g, radii, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                     dL_dscale, dL_drot, sh_adam)) return rc;
+  if (dL_ddepth || dL_dz) return launch_depth_grad(P, g, viewmatrix, dL_dmean3D, dL_dz, a.stream);
+  return GM_OK;
+}
+
+int gm_backward_aux(int emission_policy, int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
+                    const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+                    const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                    const float* campos, float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
+                    void* binning_buffer, void* image_buffer, const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
+                    float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                    float* dL_dscale, float* dL_drot, const float* dL_ddepth, const float* dL_dalpha, float* dL_dz, int debug, void* stream) {
+  if (P > 0) {
+    const size_t n = (size_t)P;
+    if (overlaps(dL_dz, n, dL_dmean3D, 3 * n) || overlaps(dL_dz, n, dL_dmean2D, 3 * n) || overlaps(dL_dz, n, dL_dopacity, n)) {
+      set_error("gm_backward_aux: dL_dz overlaps another gradient output"); return GM_ERR_INVALID_ARG;
+    }
+  }
+  return backward_impl(emission_policy, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                       viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D, dL_dconic,
+                       dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream, nullptr, dL_ddepth, dL_dalpha, dL_dz);
 }
 
 int gm_backward_p(int emission_policy, int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,

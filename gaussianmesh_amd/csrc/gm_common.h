@@ -113,6 +113,7 @@ __host__ __device__ __forceinline__ uint32_t coarse_index(uint32_t bin, uint32_t
 #define GM_CNT_CMIN 6                // first / last coarse bin that holds a visible key
 #define GM_CNT_CMAX 7
 #define GM_CNT_DIRECT_FAIL 8         // direct depth placement (DepthSlab below) could not order this frame: emission is refused with status 2
+#define GM_CNT_DEPTH_STALE 9         // set by a direct-placement first half, which does not write depth_key: an AUX blend (depth / alpha maps) refuses the frame
 #define GM_CNT_COUNT 32
 #define GM_SLOTS 256                 // atomic slots {instance sum, visible count, 2047 - first coarse bin, last coarse bin} filled by the preprocess kernel
 #define GM_SLOT_STRIDE 32            // words between slots: one 128-byte line each (atomics on one line serialise in the memory-side atomic unit)
@@ -175,7 +176,7 @@ struct GeomState {              // per-Gaussian state (P-sized)
   uint32_t* coarse;             // [GM_COARSE_COPIES][GM_COARSE_BINS] coarse histogram of the visible depth keys
   uint32_t* counters;           // [GM_CNT_COUNT] device scalars
   uint32_t* acc;                // [bk_acc_words(P)] accumulators of the partition pass
-  float* grad_acc;              // [P][12] backward accumulators: dcolor rgb | dmean2D xy | dconic x,y,w | dopacity | pad
+  float* grad_acc;              // [P][12] backward accumulators (render_bwd_kernel: dcolor rgb | moments of h (3-8) | dL/dz of the AUX backward (9) | pad)
   static GeomState from(void* buf, size_t P) {
     char* p = reinterpret_cast<char*>(buf);
     GeomState g;
@@ -376,9 +377,14 @@ int launch_tile_ranges(const GeomState& g, BinningState& b, int slot, ImageState
 int launch_tile_order(ImageState& img, int tiles, uint32_t* work_hint, int debug, hipStream_t s);          // ranges -> tile_order
 int launch_render_fwd(const GeomState& g, const uint2* pairs, ImageState& img, int W, int H, int mode,
                       const float* background, float* out_color, int* status_host, bool image_only, uint32_t* work_hint, int debug,
-                      hipStream_t s, bool exact_exponent = false, const BatchOfs* bt = nullptr);
+                      hipStream_t s, bool exact_exponent = false, const BatchOfs* bt = nullptr,
+                      float* out_depth = nullptr, float* out_alpha = nullptr, bool aux = false,    // aux: the AUX blend (single frames)
+                      uint32_t* aux_latch = nullptr);                                              // (g.counters; NULL for P = 0)
 int launch_render_bwd(const GeomState& g, const uint2* pairs, ImageState& img, int W, int H, int mode,
-                      const float* background, const float* dL_dpix, int debug, hipStream_t s);   // accumulates into g.grad_acc
+                      const float* background, const float* dL_dpix, int debug, hipStream_t s,
+                      bool aux = false, const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr);   // accumulates into g.grad_acc
+// gm_backward_aux: dL/dmean3D += dL/dz (view[2], view[6], view[10]); dL/dz = grad_acc[12 i + 9] (written to dL_dz too when given)
+int launch_depth_grad(int P, const GeomState& g, const float* viewmatrix, float* dL_dmean3D, float* dL_dz, hipStream_t s);
 
 int launch_deform(int N, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
                   const float* cov, const float* pos, float* pos_out, float* cov_out, float* rot_out, float* cov6_out,

@@ -616,4 +616,26 @@ int launch_preprocess_bwd(const RasterArgs& r, GeomState& g, const int* radii, f
   return 0;
 }
 
+// gm_backward_aux: the depth map's gradient reaches the means through z = p_view.z = view[2] x + view[6] y + view[10] z + view[14]
+// (transposed view matrix): dL/dmean3D += dL/dz (view[2], view[6], view[10]), dL/dz = grad_acc[12 i + 9] (render_bwd_aux_kernel).
+__global__ __launch_bounds__(256) void depth_grad_kernel(int P, const float* __restrict__ grad_acc, const float* __restrict__ view,
+                                                         float* __restrict__ dL_dmean3D, float* __restrict__ dL_dz) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  const float dz = grad_acc[12 * (size_t)i + 9];
+  if (dL_dz) dL_dz[i] = dz;
+  if (dz != 0.0f) {
+    dL_dmean3D[3 * (size_t)i] += dz * view[2];
+    dL_dmean3D[3 * (size_t)i + 1] += dz * view[6];
+    dL_dmean3D[3 * (size_t)i + 2] += dz * view[10];
+  }
+}
+
+int launch_depth_grad(int P, const GeomState& g, const float* viewmatrix, float* dL_dmean3D, float* dL_dz, hipStream_t s) {
+  StageScope sc(ST_PREPROCESS_BWD, s);
+  if (P > 0) hipLaunchKernelGGL(depth_grad_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, g.grad_acc, viewmatrix, dL_dmean3D, dL_dz);
+  GM_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace gm

@@ -228,7 +228,7 @@ class PendingForward:
     later tells whether the frame fitted (False: call finish() again - it then takes the exact path)."""
 
     def __init__(self, policy, workspace, stream, args, geom, img, color, radii, count_host, event, deformed=None, binning=None,
-                 rebegin=None):
+                 rebegin=None, maps=None):
         self.policy, self.workspace, self.stream, self.args = policy, workspace, stream, args
         self.geom, self.img, self.color, self.radii, self.deformed, self.binning = geom, img, color, radii, deformed, binning
         self.count_host, self.event = count_host, event      # the instance count's pinned copy and the event behind it (None: not enqueued)
@@ -239,15 +239,22 @@ class PendingForward:
         self.direct = rebegin is not None    # begun with direct depth placement (DepthPlan); rebegin re-issues the first half on the partition path
         self.rebegin = rebegin
         self.refusal = 0                 # status word 3 of the checked frame: 1 capacity / policy, 2 direct placement
+        self.maps = maps                 # (depth [1,H,W], alpha [1,H,W]) of a frame begun with aux=True (gm_forward_1_aux), else None
 
     def _geom(self, binning, num_rendered, capacity, status=None):
         lib = _lib.lib()
         a = self.args
-        _lib.check(lib.gm_forward_1_geom(self.policy, _ptr(self.geom), _ptr(binning), _ptr(self.img), a["P"], num_rendered, capacity,
-                                         _ptr(a["bg"]), a["W"], a["H"], _ptr(self.color), a["debug"], self.stream.cuda_stream,
-                                         None if status is None else status.data_ptr(),
-                                         (1 if self.image_only else 0) | (2 if self.exact_exponent else 0),
-                                         None if self.work_hint is None else self.work_hint.data_ptr()))
+        call = (self.policy, _ptr(self.geom), _ptr(binning), _ptr(self.img), a["P"], num_rendered, capacity, _ptr(a["bg"]), a["W"], a["H"],
+                _ptr(self.color), a["debug"], self.stream.cuda_stream, None if status is None else status.data_ptr(),
+                (1 if self.image_only else 0) | (2 if self.exact_exponent else 0), None if self.work_hint is None else self.work_hint.data_ptr())
+        if self.maps is None:
+            _lib.check(lib.gm_forward_1_geom(*call))
+        else:
+            _lib.check(lib.gm_forward_1_aux(*call, _ptr(self.maps[0]), _ptr(self.maps[1])))
+
+    def _outputs(self, num_rendered, binning):
+        out = (num_rendered, self.color, self.radii, self.geom, binning, self.img)
+        return out if self.maps is None else out + self.maps
 
     def _status(self):
         """The frame's four status words, read now: enqueued into a pinned block, then a wait for the frame's stream."""
@@ -288,7 +295,8 @@ class PendingForward:
         per-pixel final transmittance / contributor count of the image state alone; the returned img must not be handed
         to rasterize_backward.
         work_hint (new_work_hint()): per-tile cost memory shared by the consecutive frames of one view stream; the blend's
-        dispatch order then follows what tiles cost in recent frames.  Never changes an image."""
+        dispatch order then follows what tiles cost in recent frames.  Never changes an image.
+        Returns (num_rendered, color, radii, geom, binning, img), followed by (depth, alpha) for a frame begun with aux=True."""
         self.image_only = bool(image_only)
         if work_hint is not None:
             key = (work_hint.data_ptr(), work_hint.numel(), self.args["W"], self.args["H"], self.args["device"])
@@ -320,7 +328,7 @@ class PendingForward:
                 self._geom(binning, -1, cap, status)          # the blend kernel writes the status words itself
                 event.record(self.stream)
             self.status_event, self.binning = event, binning
-            self.result = (-1, self.color, self.radii, self.geom, binning, self.img)
+            self.result = self._outputs(-1, binning)
             return self.result
         with _on(device), torch.cuda.stream(self.stream):
             if self.direct and self.refusal == 2:          # check() saw the direct placement refuse the frame; the exact path completes it
@@ -352,7 +360,7 @@ class PendingForward:
                 raise _lib.GmeshError(_PREFILTER_MESSAGE)
         self._release()
         self.binning = binning
-        self.result = (num_rendered, self.color, self.radii, self.geom, binning, self.img)
+        self.result = self._outputs(num_rendered, binning)
         return self.result
 
     def check(self):
@@ -390,12 +398,13 @@ _PINNED_POOL = []          # page-locked int32[1] counters of workspace-less for
 _PINNED_STATUS = []        # page-locked int32[4] status words of sync-free forwards without a workspace
 
 
-def _scratch(workspace, P, W, H, device, count_stream=None):
-    """A frame's outputs (colour [3,H,W], radii [P]) and geometry / image buffers (the workspace's, or fresh ones); with count_stream
-    also a page-locked int32[1] for the instance count and an event recorded on that stream, which the library re-records right
-    behind the count's copy (it needs a live hipEvent_t handle)."""
+def _scratch(workspace, P, W, H, device, count_stream=None, aux=False):
+    """A frame's outputs (colour [3,H,W], radii [P]; with aux the maps (depth [1,H,W], alpha [1,H,W]), else None) and geometry / image
+    buffers (the workspace's, or fresh ones); with count_stream also a page-locked int32[1] for the instance count and an event recorded
+    on that stream, which the library re-records right behind the count's copy (it needs a live hipEvent_t handle)."""
     lib = _lib.lib()
     color = torch.empty((3, H, W), dtype=torch.float32, device=device)
+    maps = tuple(torch.empty((1, H, W), dtype=torch.float32, device=device) for _ in range(2)) if aux else None
     radii = torch.empty((P,), dtype=torch.int32, device=device)
     if workspace is not None:
         geom, img = workspace.get("geom", lib.gm_geom_bytes(P), device), workspace.get("img", lib.gm_image_bytes(W, H), device)
@@ -409,7 +418,7 @@ def _scratch(workspace, P, W, H, device, count_stream=None):
             count = _PINNED_POOL.pop() if _PINNED_POOL else torch.zeros((1,), dtype=torch.int32).pin_memory()
         event = torch.cuda.Event()
         event.record(count_stream)
-    return color, radii, geom, img, count, event
+    return color, radii, geom, img, count, event, maps
 
 
 def _begin(device, workspaces, issue):
@@ -436,9 +445,11 @@ def _begin(device, workspaces, issue):
 
 def rasterize_forward_begin(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered=False,
-                            debug=False, workspace=None, emission_policy=None, force_M=None):
+                            debug=False, workspace=None, emission_policy=None, force_M=None, aux=False):
     """First half of a forward without host synchronisation (gm_forward_0_async); returns a PendingForward.
-    Typical loop: h_next = begin(frame i+1, workspace=ws[(i+1) % 2]); outputs = h_cur.finish()."""
+    Typical loop: h_next = begin(frame i+1, workspace=ws[(i+1) % 2]); outputs = h_cur.finish().
+    aux: the frame also renders its depth and opacity maps (gm_forward_1_aux): finish() appends (depth, alpha), each [1,H,W] -
+    alpha = 1 - T_final, depth = sum alpha_i T_i z_i (view-space z, not normalised, background 0: divide by alpha for the surface depth)."""
     lib = _lib.lib()
     device = means3D.device
     policy = _pol(emission_policy, image_width, image_height)
@@ -455,7 +466,7 @@ def rasterize_forward_begin(bg, means3D, colors, opacity, scales, rotations, sca
         raise ValueError("NewGaussianRasterizer expects shs of shape [P,%d,3]" % force_M)
 
     def issue(stream):
-        color, radii, geom, img, count_host, event = _scratch(workspace, P, W, H, device, stream)
+        color, radii, geom, img, count_host, event, maps = _scratch(workspace, P, W, H, device, stream, aux)
         _lib.check(lib.gm_forward_0_async(policy, _ptr(geom), P, int(degree), M, _ptr(bg), W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
                                           _ptr(opacity), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
                                           _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy),
@@ -463,7 +474,7 @@ def rasterize_forward_begin(bg, means3D, colors, opacity, scales, rotations, sca
                                           count_host.data_ptr(), event.cuda_event))
         args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)), prefiltered=bool(prefiltered),
                     keep=(means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos))
-        return [PendingForward(policy, workspace, stream, args, geom, img, color, radii, count_host, event)]
+        return [PendingForward(policy, workspace, stream, args, geom, img, color, radii, count_host, event, maps=maps)]
     return _begin(device, () if workspace is None else (workspace,), issue)[0]
 
 
@@ -480,7 +491,7 @@ def rasterize_forward(bg, means3D, colors, opacity, scales, rotations, scale_mod
 
 def forward_deformed_begin(bg, tri, weights, packed, cov, pos, shs, opacity, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                            image_height, image_width, degree, campos, debug=False, workspace=None, want_deformed=False,
-                           emission_policy=None, want_count=True, depth_plan=None):
+                           emission_policy=None, want_count=True, depth_plan=None, aux=False):
     """Edit-loop frame, first half (gm_forward_0_deformed_async): mesh-driven deformation + rotated-direction SH colour +
     forward preprocess + depth order + instance count in one enqueue, no host synchronisation.  `packed` is
     deform.pack_mesh_state() of the frame.  Returns a PendingForward; .finish() completes the frame
@@ -490,7 +501,9 @@ def forward_deformed_begin(bg, tri, weights, packed, cov, pos, shs, opacity, vie
     cov: the rest covariances [N,3,3] / [N,9], or [N,6] from deform.pack_cov6() (bit-symmetric matrices: 12 bytes per Gaussian
     less to read, identical results).
     depth_plan (new_depth_plan(), one per view stream): see DepthPlan; complete such frames with finish(sync_free=True) and
-    check() them, or the status of a refused frame goes unseen."""
+    check() them, or the status of a refused frame goes unseen.
+    aux: depth and opacity maps as in rasterize_forward_begin (forward only).  Direct depth placement does not write the depth keys the
+    maps are made of, so an aux frame always takes the partition path (it still leaves its table in depth_plan)."""
     lib = _lib.lib()
     device = pos.device
     policy = _pol(emission_policy, image_width, image_height)
@@ -502,11 +515,11 @@ def forward_deformed_begin(bg, tri, weights, packed, cov, pos, shs, opacity, vie
     H, W = int(image_height), int(image_width)
 
     def issue(stream):
-        color, radii, geom, img, count_host, event = _scratch(workspace, P, W, H, device, stream if want_count else None)
+        color, radii, geom, img, count_host, event, maps = _scratch(workspace, P, W, H, device, stream if want_count else None, aux)
         deformed = tuple(torch.empty((P, n), dtype=torch.float32, device=device) for n in (3, 6, 3)) if want_deformed else None
         dp = [None, None, None] if deformed is None else [t.data_ptr() for t in deformed]
         cov6 = cov is not None and cov.dim() == 2 and cov.shape[1] == 6       # deform.pack_cov6(): GM_STREAM_COV6
-        direct = depth_plan is not None and depth_plan.primed and P > 0
+        direct = depth_plan is not None and depth_plan.primed and P > 0 and not aux
         slab = None
         if direct:
             nbytes = lib.gm_depth_slab_bytes(P)
@@ -529,12 +542,12 @@ def forward_deformed_begin(bg, tri, weights, packed, cov, pos, shs, opacity, vie
         args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)),
                     keep=(tri, weights, packed, cov, pos, shs, opacity, viewmatrix, projmatrix, campos))
         return [PendingForward(policy, workspace, stream, args, geom, img, color, radii, count_host, event, deformed=deformed,
-                               rebegin=rebegin if direct else None)]
+                               rebegin=rebegin if direct else None, maps=maps)]
     return _begin(device, () if workspace is None else (workspace,), issue)[0]
 
 
 def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity, cameras, image_height, image_width, degree, workspaces,
-                           image_only=True, work_hint=None, emission_policy=None, debug=False):
+                           image_only=True, work_hint=None, emission_policy=None, debug=False, aux=False):
     """K frames of one view stream in ONE launch chain (gm_forward_deformed_batch_async): the static cloud is read from HBM once for the
     batch and every stage is one launch over the K frames.  packed_list: the K gather tables (deform.mesh_rs_packed_batch);
     cameras: K dicts / objects with view, proj, campos (device tensors), tanx, tany; workspaces: K RasterWorkspace, one per frame, each with
@@ -542,6 +555,8 @@ def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity
     handles in the state finish(sync_free=True) leaves them in: .result = (-1, color, radii, geom, binning, img); check() each of them -
     a frame whose instance count outgrew the batch's capacity is refused (image = background) and finish() renders it again, exactly,
     through the single-frame second half.  Each frame comes out bit for bit as from forward_deformed_begin(...).finish(sync_free=True)."""
+    if aux:
+        raise _lib.GmeshError("forward_deformed_batch: the batch renders no depth / alpha maps; use forward_deformed_begin(aux=True)")
     lib = _lib.lib()
     device = pos.device
     K = len(packed_list)
@@ -567,7 +582,7 @@ def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity
         nbin = lib.gm_binning_bytes(cap)
         for k, (ws, c) in enumerate(zip(workspaces, cameras)):
             ws.capacity = cap
-            color, radii, geom, img, _, _ = _scratch(ws, P, W, H, device)
+            color, radii, geom, img, _, _, _ = _scratch(ws, P, W, H, device)
             binning = ws.get("binning", nbin, device)
             view, proj, campos, packed = (_prep(t, device) for t in (get(c, "view"), get(c, "proj"), get(c, "campos"), packed_list[k]))
             f = frames[k]
@@ -590,7 +605,7 @@ def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity
 
 def rasterize_backward(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
                        tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geom, num_rendered, binning, img, debug,
-                       emission_policy=None, skip_intermediates=False, want_conic=False, sh_step=None):
+                       emission_policy=None, skip_intermediates=False, want_conic=False, sh_step=None, dL_ddepth=None, dL_dalpha=None):
     """RasterizeGaussiansBackwardCUDA of the reference bridge (rasterize_points.py:276-401): returns
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
     emission_policy: the policy the forward that filled geom / binning / img ran under.
@@ -599,7 +614,9 @@ def rasterize_backward(bg, means3D, radii, colors, scales, rotations, scale_modi
     sh_step (an ShStep, see below): the Adam step of the SH rows happens inside the backward (gm_backward_sh_step); dL_dsh, dL_dcolors and
     dL_dcov3D (with scales) come back as None.
     want_conic (tests): a ninth return value, dL_dconic [P,2,2] (slots [0,0], [0,1], [1,1] used: the blend stage's output that the
-    reference keeps internal, rasterize_points.py:305)."""
+    reference keeps internal, rasterize_points.py:305).
+    dL_ddepth / dL_dalpha ([1,H,W] or [H,W], either may be None): gradients of the depth / alpha maps of a forward begun with aux=True
+    (gm_backward_aux); with both None the pass is gm_backward_p's.  Not together with sh_step."""
     lib = _lib.lib()
     device = means3D.device
     P = means3D.shape[0]
@@ -614,6 +631,14 @@ def rasterize_backward(bg, means3D, radii, colors, scales, rotations, scale_modi
     dpix = _prep(dL_dout_color, device)
     H, W = dpix.shape[1], dpix.shape[2]
     M = sh.shape[1] if sh is not None else 0
+    dL_ddepth, dL_dalpha = (None if t is None else _prep(t, device) for t in (dL_ddepth, dL_dalpha))
+    for t in (dL_ddepth, dL_dalpha):
+        if t is not None and t.numel() != H * W:
+            raise ValueError("rasterize_backward: depth / alpha gradients must hold H x W = %d x %d values" % (H, W))
+    aux = dL_ddepth is not None or dL_dalpha is not None
+    if sh_step is not None and aux:
+        raise _lib.GmeshError("rasterize_backward: the fused SH step (ShStep) does not take depth / alpha gradients; render the maps "
+                              "outside the ShStep block or leave them out of the loss")
     if sh_step is not None:
         if sh is None or M != 16 or colors is not None or sh.data_ptr() != sh_step.param.data_ptr():
             raise _lib.GmeshError("rasterize_backward(sh_step=...): the step's parameter must be the [P,16,3] shs operand of this pass")
@@ -640,12 +665,15 @@ def rasterize_backward(bg, means3D, radii, colors, scales, rotations, scale_modi
         dsh = torch.empty((P, M, 3), **f) if sh is not None else None
         dscales = torch.empty((P, 3), **f) if scales is not None else None
         drots = torch.empty((P, 4), **f) if scales is not None else None
-        _lib.check(lib.gm_backward_p(_pol(emission_policy, W, H), P, int(degree), M, int(num_rendered), _ptr(bg), W, H, _ptr(means3D), _ptr(sh),
-                                     _ptr(colors), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix),
-                                     _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geom),
-                                     _ptr(binning), _ptr(img), _ptr(dpix), _ptr(dmeans2D), _ptr(dconic), _ptr(dopac),
-                                     _ptr(dcolors), _ptr(dmeans3D), _ptr(dcov3D), _ptr(dsh), _ptr(dscales), _ptr(drots),
-                                     int(bool(debug)), _stream(device)))
+        call = (_pol(emission_policy, W, H), P, int(degree), M, int(num_rendered), _ptr(bg), W, H, _ptr(means3D), _ptr(sh),
+                _ptr(colors), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix),
+                _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geom),
+                _ptr(binning), _ptr(img), _ptr(dpix), _ptr(dmeans2D), _ptr(dconic), _ptr(dopac),
+                _ptr(dcolors), _ptr(dmeans3D), _ptr(dcov3D), _ptr(dsh), _ptr(dscales), _ptr(drots))
+        if aux:
+            _lib.check(lib.gm_backward_aux(*call, _ptr(dL_ddepth), _ptr(dL_dalpha), None, int(bool(debug)), _stream(device)))
+        else:
+            _lib.check(lib.gm_backward_p(*call, int(bool(debug)), _stream(device)))
     if want_conic:
         return dmeans2D, dcolors, dopac, dmeans3D, dcov3D, dsh, dscales, drots, dconic
     return dmeans2D, dcolors, dopac, dmeans3D, dcov3D, dsh, dscales, drots
@@ -809,7 +837,7 @@ def current_sync_free():
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                force_M):
+                force_M, return_aux=False):
         rs = raster_settings
         if means3D.device.type != "cuda":
             raise _lib.GmeshError("gaussianmesh_amd rasterizer needs tensors on a HIP (cuda) device; there is no CPU path")
@@ -822,9 +850,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             h = rasterize_forward_begin(rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                                         rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
                                         rs.sh_degree, rs.campos, rs.prefiltered, rs.debug, workspace=ws, emission_policy=policy,
-                                        force_M=force_M)
+                                        force_M=force_M, aux=return_aux)
             if cap > 0:
-                num_rendered, color, radii, geom, binning, img = h.finish(sync_free=True, capacity=cap, work_hint=rs.work_hint, exact_exponent=True)
+                num_rendered, color, radii, geom, binning, img = h.finish(sync_free=True, capacity=cap, work_hint=rs.work_hint, exact_exponent=True)[:6]
                 num_rendered = cap                        # the binning layout is that of the capacity
                 if len(sf.unchecked) >= _SYNC_FREE_MAX_UNCHECKED:
                     raise _lib.GmeshError("sync-free training: %d forwards were issued without SyncFreeState.verify(); every "
@@ -833,7 +861,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 sf.unchecked.append(h)
             else:
                 # image_only: no backward will follow; exact_exponent: one will, and takes the decisions this forward took
-                num_rendered, color, radii, geom, binning, img = h.finish(image_only=not needs_grad, work_hint=rs.work_hint, exact_exponent=needs_grad)
+                num_rendered, color, radii, geom, binning, img = h.finish(image_only=not needs_grad, work_hint=rs.work_hint, exact_exponent=needs_grad)[:6]
                 if sf is not None:
                     sf.note_count(means3D.device, num_rendered)
         except Exception:
@@ -858,20 +886,26 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.opacity_shape = opacities.shape
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img)
         ctx.mark_non_differentiable(radii)
-        return color, radii
+        ctx.return_aux = return_aux
+        if not return_aux:
+            return color, radii
+        ctx.set_materialize_grads(False)        # a map no loss term uses arrives as None: the backward then takes the ordinary route
+        return color, radii, h.maps[0], h.maps[1]
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii):
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
         ss = ctx.sh_step
         if ss is not None and ss.applied:
             ss = None                            # one step per ShStep: a second backward takes the ordinary route
+        if grad_out_color is None:               # (return_aux: only the maps reach the loss)
+            grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
         try:
             g2d, gcol, gop, g3d, gcov, gsh, gsc, grot = rasterize_backward(
                 rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geom, ctx.num_rendered,
-                binning, img, rs.debug, ctx.emission_policy, skip_intermediates=True, sh_step=ss)
+                binning, img, rs.debug, ctx.emission_policy, skip_intermediates=True, sh_step=ss, dL_ddepth=grad_depth, dL_dalpha=grad_alpha)
         except Exception:
             if rs.debug:       # diff_gaussian_rasterizater/__init__.py:102-108
                 _snapshot("snapshot_bw.dump", dict(bg=rs.bg, means3D=means3D, radii=radii, colors_precomp=colors_precomp, scales=scales,
@@ -884,7 +918,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         has = lambda t: t is not None and t.numel() > 0
         return (g3d, g2d, gsh if (has(sh) and gsh is not None) else None, gcol if has(colors_precomp) else None, gop.reshape(ctx.opacity_shape),
                 gsc if has(scales) else None, grot if has(rotations) else None, gcov if has(cov3Ds_precomp) else None,
-                None, None)
+                None, None) + ((None,) if ctx.return_aux else ())
 
 
 class GaussianRasterizer(nn.Module):
@@ -900,7 +934,10 @@ class GaussianRasterizer(nn.Module):
             return mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, return_aux=False):
+        """(image [3,H,W], radii [P]); with return_aux also the depth and opacity maps of the same blend, (image, radii, depth [1,H,W],
+        alpha [1,H,W]), all differentiable: alpha = 1 - T_final, depth = sum alpha_i T_i z_i with z_i the view-space depth - not
+        normalised and without a background term (divide by alpha for the surface depth)."""
         raster_settings = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -913,6 +950,9 @@ class GaussianRasterizer(nn.Module):
         scales = e() if scales is None else scales
         rotations = e() if rotations is None else rotations
         cov3D_precomp = e() if cov3D_precomp is None else cov3D_precomp
+        if return_aux:
+            return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                             raster_settings, self._force_M, True)
         return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                          raster_settings, self._force_M)
 

@@ -172,9 +172,10 @@ def _joint_buffers(pc, bg_gaussian):
     return jb
 
 
-def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, bg_gaussian=None):
+def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, bg_gaussian=None, return_aux=False):
     """gaussian_renderer/__init__.py:26-143.  Returns {"render", "viewspace_points", "visibility_filter", "radii",
-    "vertex1", "vertex2", "vertex3", "scale"}.
+    "vertex1", "vertex2", "vertex3", "scale"}; with return_aux also "depth" and "alpha" ([1,H,W], differentiable; see
+    GaussianRasterizer.forward: depth is the alpha-weighted view-space depth, not normalised, background 0).
     With bg_gaussian on the fused route (a MeshBoundGaussians on the GPU, pipe.compute_cov3D_python off) the activations and the screen-space
     probe live in PERSISTENT joint [fg; bg] buffers (_joint_buffers; `pc.joint_buffers = False` opts out and concatenates per call):
     one forward per backward - the next render() of the same model rewrites the storage the previous call's graph saved (its backward
@@ -231,18 +232,26 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         else:
             bgc = sh_colors(bg_gaussian.get_xyz, viewpoint_camera.camera_center, bg_gaussian.get_features, rot=None, deg=3)
             colors_precomp = torch.cat([colors_precomp, bgc], dim=0)
-    rendered_image, radii = rasterizer(means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
-                                       scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+    maps = None
+    if return_aux:
+        rendered_image, radii, *maps = rasterizer(means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+                                                  scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, return_aux=True)
+    else:
+        rendered_image, radii = rasterizer(means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+                                           scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
     out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
            "vertex1": getattr(pc, "vertex1", None), "vertex2": getattr(pc, "vertex2", None),
            "vertex3": getattr(pc, "vertex3", None), "scale": scales if (bg_gaussian is None or scales is None) else scales[:pc.screenspace_points.shape[0]]}  # None on the compute_cov3D_python route (:143)
     if mrloss is not None:                       # extra key (pipe.mesh_restrict_weight set): the loss term of train_mesh_gaussian.py:93
         out["mesh_restrict_loss"] = mrloss
+    if maps is not None:
+        out["depth"], out["alpha"] = maps
     return out
 
 
-def bg_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, mesh_gaussians=None):
-    """gaussian_renderer/__init__.py:146-260: background model trained with the (frozen) mesh Gaussians composited in."""
+def bg_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, mesh_gaussians=None, return_aux=False):
+    """gaussian_renderer/__init__.py:146-260: background model trained with the (frozen) mesh Gaussians composited in.
+    return_aux: "depth" and "alpha" as in render()."""
     screenspace_points = pc.screenspace_points
     if mesh_gaussians is not None:
         screenspace_points = torch.cat([screenspace_points, mesh_gaussians.screenspace_points], dim=0)
@@ -276,15 +285,21 @@ def bg_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, overri
         rotations = torch.cat([rotations, mesh_gaussians.get_rotation.detach()], dim=0)
         shs = torch.cat([shs, mesh_gaussians.get_features.detach()], dim=0)
         opacity = torch.cat([opacity, mesh_gaussians.get_opacity.detach()], dim=0)
+    if return_aux:
+        rendered_image, radii, depth, alpha = rasterizer(means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+                                                         scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, return_aux=True)
+        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
+                "depth": depth, "alpha": alpha}
     rendered_image, radii = rasterizer(means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
                                        scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
 
 
-def render_deformed(viewpoint_camera, objects, bg_color=None):
+def render_deformed(viewpoint_camera, objects, bg_color=None, return_aux=False):
     """ObjectVisualTool.render_gaussian (edittool/__init__.py:400-475): concatenate the deformed objects
     (SingleObjectDeform instances after .deform()), colours from SH with the deformation-rotated view direction,
-    NewGaussianRasterizer with colors_precomp + cov3D_precomp on a white background."""
+    NewGaussianRasterizer with colors_precomp + cov3D_precomp on a white background.  return_aux: (image, depth, alpha), the maps
+    [1,H,W] as in render() - for compositing the frame or resolving occlusion against a mesh render."""
     dev = objects[0].gaussian_deform_pos.device
     bg = torch.ones(3, device=dev) if bg_color is None else bg_color
     cat = (lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs, dim=0))
@@ -295,6 +310,10 @@ def render_deformed(viewpoint_camera, objects, bg_color=None):
     opacity = cat([o.gaussian_o for o in objects])
     colors_precomp = sh_colors(means3D, viewpoint_camera.camera_center, shs, rot=rot, deg=3)
     rasterizer = NewGaussianRasterizer(_settings(viewpoint_camera, bg, 1, 3, False))
+    if return_aux:
+        image, _, depth, alpha = rasterizer(means3D=means3D, means2D=torch.zeros_like(means3D), shs=None, colors_precomp=colors_precomp,
+                                            opacities=opacity, scales=None, rotations=None, cov3D_precomp=strip_symmetric(cov), return_aux=True)
+        return image, depth, alpha
     image, _ = rasterizer(means3D=means3D, means2D=torch.zeros_like(means3D), shs=None, colors_precomp=colors_precomp,
                           opacities=opacity, scales=None, rotations=None, cov3D_precomp=strip_symmetric(cov))
     return image

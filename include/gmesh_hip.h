@@ -130,6 +130,20 @@ int gm_backward_p(int emission_policy, int P, int D, int M, int R, const float* 
                   float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                   float* dL_dscale, float* dL_drot, int debug, void* stream);
 
+/* gm_backward_p with the gradients of gm_forward_1_aux's maps (backward.cu:399-557 with two more colour channels: depth, of
+ * colour z_i, and alpha, of colour 1, both with background 0).  dL_ddepth / dL_dalpha: [H,W], either may be NULL; with both NULL
+ * this is gm_backward_p.  Their terms enter dL/dalpha of every (entry, pixel) and so the opacity, conic and mean2D chain;
+ * dL/dz_i = sum over pixels of dL/ddepth alpha_i T_i becomes dL_dmean3D += dL/dz_i (viewmatrix[2], viewmatrix[6], viewmatrix[10]).
+ * dL_dz ([P], may be NULL) receives dL/dz_i itself; it may not overlap dL_dmean3D, dL_dmean2D or dL_dopacity.  The forward must
+ * have kept its state (not GM_FWD_IMAGE_ONLY), as for gm_backward_p. */
+int gm_backward_aux(int emission_policy, int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
+                    const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+                    const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                    const float* campos, float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
+                    void* binning_buffer, void* image_buffer, const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
+                    float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                    float* dL_dscale, float* dL_drot, const float* dL_ddepth, const float* dL_dalpha, float* dL_dz, int debug, void* stream);
+
 /* gm_backward_p for a TRAINING step whose SH rows are the optimizer's parameter (scene/mesh_based_gaussian_model.py:242-263: the "f_dc" and
  * "f_rest" groups of training_setup; jittor.nn.Adam): the Adam step of those rows is applied inside the backward pass instead of by
  * gm_adam_step afterwards.  dL/dSH of a Gaussian is produced whole by the thread that owns it (RAST/backward.cu:20-139), so the 192-byte
@@ -294,6 +308,26 @@ int gm_forward_1_geom(int emission_policy, void* geom_buffer, void* binning_buff
                       int* status_host, int flags, unsigned int* work_hint);
 int gm_forward_status_async(void* geom_buffer, int P, int* status_host, void* stream);
 
+/* Depth and opacity maps of the same blend (the reference renders the colour image only; the maps are the convention of the
+ * common 3DGS rasterizer forks).  Over the entries the colour blend accepts (forward.cu:330-365: same order, same alpha >= 1/255
+ * skips, same T < 1e-4 stop), per pixel:
+ *   out_alpha = 1 - T_final, from the float T the colour output uses: a frame that keeps its state has out_alpha == 1 - final_T
+ *               bit for bit;
+ *   out_depth = sum_i alpha_i T_i z_i, z_i = the view-space depth p_view.z of the Gaussian (the float of "depth_key").  NOT
+ *               normalised and without a background term (the background contributes 0): divide by out_alpha for the
+ *               surface depth.
+ * Both float32 [H,W]; either may be NULL.  Neither may overlap out_color or the other (GM_ERR_INVALID_ARG before any GPU work).
+ * A refused frame (sync-free overflow, policy mismatch, direct-placement refusal) has out_alpha = out_depth = 0.
+ *
+ * gm_forward_1_aux: gm_forward_1_geom (same arguments, same image, radii, lists and status words bit for bit) that also writes the
+ * maps.  It completes every single-frame first half (gm_forward_0_async, gm_forward_0_deformed_async, and
+ * gm_forward_0_deformed_stream_async without GM_STREAM_DIRECT).  A GM_STREAM_DIRECT first half does not write depth_key; it
+ * latches that in the geometry buffer, and gm_forward_1_aux REFUSES such a frame: background, both maps 0, status word 3 = 3
+ * (begin it again without the flag).  gm_forward_deformed_batch_async has no maps. */
+int gm_forward_1_aux(int emission_policy, void* geom_buffer, void* binning_buffer, void* image_buffer, int P, int num_rendered,
+                     int64_t binning_capacity, const float* background, int width, int height, float* out_color, int debug, void* stream,
+                     int* status_host, int flags, unsigned int* work_hint, float* out_depth, float* out_alpha);
+
 /* K frames of ONE view stream per launch chain (the edit tool replaying a deformation sequence, a camera path: the frames the render
  * loop would otherwise keep in flight on K HIP streams).  Equivalent, frame by frame and bit for bit (radii, lists, image, status words), to
  *   gm_forward_0_deformed_stream_async(policy, frame.geom_buffer, ..., frame.packed, ..., frame.viewmatrix, ..., flags & GM_BATCH_COV6)
@@ -307,7 +341,7 @@ int gm_forward_status_async(void* geom_buffer, int P, int* status_host, void* st
  * Sync-free second half only (the instance counts stay on the device; binning_capacity instances per frame; a frame that outgrows it is
  * refused in its own status words and rendered again by the caller through the single-frame calls).  1 <= K <= GM_BATCH_MAX; M == 16;
  * emission policies with at most 2048 list tiles (the one-pass tile sort); every scratch buffer base 256-byte aligned; the frames'
- * buffers distinct.  Like every deformed frame: forward only. */
+ * buffers distinct.  Like every deformed frame: forward only.  The batch renders no depth / alpha maps (gm_forward_1_aux). */
 #define GM_BATCH_MAX 8
 #define GM_BATCH_IMAGE_ONLY 1    /* as GM_FWD_IMAGE_ONLY */
 #define GM_BATCH_COV6 2          /* as GM_STREAM_COV6 */
