@@ -54,6 +54,8 @@ SIGNATURES = {
     "gm_binning_field": (vp, [vp, i64, i32, i32, i32, C.c_char_p]),
     "gm_knn_workspace_bytes": (sz, [i32]),
     "gm_knn": (i32, [i32, vp, vp, vp, sz, vp]),
+    "gm_knn_nearest_workspace_bytes": (sz, [i32, i32]),
+    "gm_knn_nearest": (i32, [i32, vp, i32, vp, vp, vp, vp, sz, vp]),
     "gm_deform": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gm_sh_colors": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "gm_deform_shade": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -75,6 +77,8 @@ SIGNATURES = {
     "gm_mesh_rs_packed": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "gm_mesh_activate_fwd": (i32, [i32, f32] + [vp] * 10 + [vp] * 4 + [f32, vp] + [vp]),
     "gm_mesh_activate_bwd": (i32, [i32, f32] + [vp] * 10 + [vp] * 4 + [vp] * 5 + [f32, vp] + [vp]),
+    "gm_plain_activate_fwd": (i32, [i32] + [vp] * 4 + [vp] * 4 + [i32, i32, vp]),
+    "gm_plain_activate_bwd": (i32, [i32] + [vp] * 3 + [vp] * 4 + [i32, i32] + [vp] * 4 + [vp]),
     "gm_adam_step": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, f64, f64, i32, vp]),
     "gm_adam_step_active": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, f64, f64, i32, vp]),
     "gm_densify_stats": (i32, [i32, vp, vp, vp, vp, vp, vp]),

@@ -541,6 +541,15 @@ int gm_knn(int P, const float* points, float* meanDists, void* workspace, size_t
   return launch_knn(P, points, meanDists, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t gm_knn_nearest_workspace_bytes(int Pq, int Pr) { return knn_nearest_workspace_bytes(Pq, Pr); }
+int gm_knn_nearest(int Pq, const float* query, int Pr, const float* ref, float* out_d2, int* out_idx, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+  if (Pq < 0 || Pr < 0) { set_error("gm_knn_nearest: negative size"); return GM_ERR_INVALID_ARG; }
+  if (Pr == 0) { set_error("gm_knn_nearest: empty reference set (Pr == 0)"); return GM_ERR_INVALID_ARG; }
+  if (Pq > 0 && (!query || !ref || !out_d2 || !out_idx || !workspace)) { set_error("gm_knn_nearest: null pointer"); return GM_ERR_INVALID_ARG; }
+  return launch_knn_nearest(Pq, query, Pr, ref, out_d2, out_idx, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
 int gm_deform(int N, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
               const float* cov, const float* pos, float* pos_out, float* cov_out, float* rot_out, float* cov6_out,
               void* stream) {
@@ -678,6 +687,40 @@ int gm_mesh_activate_bwd(int N, float alpha, const float* bc, const float* dist,
   }
   return launch_mesh_activate_bwd(a, d_xyz, d_scales, d_rots, d_opac, d_bc, d_dist, d_scaling, d_rotation, d_opacity, mr_weight, d_mr,
                                   reinterpret_cast<hipStream_t>(stream));
+}
+
+int gm_plain_activate_fwd(int N, const float* xyz, const float* scaling, const float* rotation, const float* opacity, float* out_xyz,
+                          float* out_scales, float* out_rots, float* out_opac, int row0, int capacity, void* stream) {
+  if (N < 0 || row0 < 0 || capacity < 0 || (long long)row0 + N > capacity) {
+    set_error("gm_plain_activate_fwd: rows [%d, %d + %d) do not fit a capacity of %d", row0, row0, N, capacity); return GM_ERR_INVALID_ARG;
+  }
+  if (N > 0 && (!xyz || !scaling || !rotation || !opacity || !out_xyz || !out_scales || !out_rots || !out_opac)) {
+    set_error("gm_plain_activate_fwd: null pointer"); return GM_ERR_INVALID_ARG;
+  }
+  if (N > 0 && ((reinterpret_cast<uintptr_t>(rotation) | reinterpret_cast<uintptr_t>(out_rots)) & 15)) {
+    set_error("gm_plain_activate_fwd: rotation / out_rots must be 16-byte aligned"); return GM_ERR_INVALID_ARG;
+  }
+  const size_t r = (size_t)row0;
+  return launch_plain_activate_fwd(N, xyz, scaling, rotation, opacity, out_xyz + 3 * r, out_scales + 3 * r, out_rots + 4 * r, out_opac + r,
+                                   reinterpret_cast<hipStream_t>(stream));
+}
+
+int gm_plain_activate_bwd(int N, const float* scaling, const float* rotation, const float* opacity, const float* g_xyz, const float* g_scales,
+                          const float* g_rots, const float* g_opac, int row0, int capacity, float* d_xyz, float* d_scaling, float* d_rotation,
+                          float* d_opacity, void* stream) {
+  if (N < 0 || row0 < 0 || capacity < 0 || (long long)row0 + N > capacity) {
+    set_error("gm_plain_activate_bwd: rows [%d, %d + %d) do not fit a capacity of %d", row0, row0, N, capacity); return GM_ERR_INVALID_ARG;
+  }
+  if (N > 0 && (!scaling || !rotation || !opacity || !d_xyz || !d_scaling || !d_rotation || !d_opacity)) {
+    set_error("gm_plain_activate_bwd: null pointer"); return GM_ERR_INVALID_ARG;
+  }
+  if (N > 0 && ((reinterpret_cast<uintptr_t>(rotation) | reinterpret_cast<uintptr_t>(d_rotation) | reinterpret_cast<uintptr_t>(g_rots)) & 15)) {
+    set_error("gm_plain_activate_bwd: rotation / g_rots / d_rotation must be 16-byte aligned"); return GM_ERR_INVALID_ARG;
+  }
+  const size_t r = (size_t)row0;
+  return launch_plain_activate_bwd(N, scaling, rotation, opacity, g_xyz ? g_xyz + 3 * r : nullptr, g_scales ? g_scales + 3 * r : nullptr,
+                                   g_rots ? g_rots + 4 * r : nullptr, g_opac ? g_opac + r : nullptr, d_xyz, d_scaling, d_rotation, d_opacity,
+                                   reinterpret_cast<hipStream_t>(stream));
 }
 
 int gm_adam_step(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,

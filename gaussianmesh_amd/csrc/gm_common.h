@@ -452,10 +452,18 @@ int launch_mesh_activate_fwd(const ActArgs& a, float* xyz, float* scales, float*
 int launch_mesh_activate_bwd(const ActArgs& a, const float* d_xyz, const float* d_scales, const float* d_rots, const float* d_opac,
                              float* d_bc, float* d_dist, float* d_scaling, float* d_rotation, float* d_opacity, float mr_weight,
                              const float* d_mr, hipStream_t s);
+int launch_plain_activate_fwd(int N, const float* xyz_in, const float* scaling, const float* rotation, const float* opacity, float* xyz,
+                              float* scales, float* rots, float* opac, hipStream_t s);
+int launch_plain_activate_bwd(int N, const float* scaling, const float* rotation, const float* opacity, const float* g_xyz,
+                              const float* g_scales, const float* g_rots, const float* g_opac, float* d_xyz, float* d_scaling,
+                              float* d_rotation, float* d_opacity, hipStream_t s);
 int launch_adam(const AdamTable& tab, hipStream_t s);
 int launch_densify_stats(int N, const int* radii, const float* grad2d, float* max_radii2D, float* grad_accum, float* denom, hipStream_t s);
 int launch_knn(int P, const float* points, float* meanDists, void* ws, size_t ws_bytes, hipStream_t s);
 size_t knn_workspace_bytes(int P);
+int launch_knn_nearest(int Pq, const float* query, int Pr, const float* ref, float* out_d2, int* out_idx, void* ws, size_t ws_bytes,
+                       hipStream_t s);
+size_t knn_nearest_workspace_bytes(int Pq, int Pr);
 
 // number of set bits of a wave-wide 64-bit mask (a ballot) at positions BELOW the calling lane: v_mbcnt_lo + v_mbcnt_hi, two
 // vector instructions and no per-lane mask registers (popcount(mask & lanes_lt) costs four and two registers)

@@ -1,4 +1,5 @@
-// gm_knn.hip -- mean squared distance to the 3 nearest neighbours (model initialisation helper).
+// gm_knn.hip -- mean squared distance to the 3 nearest neighbours (model initialisation helper), and the nearest point of a
+// second cloud (knn_nearest, below: the neighbour pruning of train_bg_gaussian.py:129-137).
 //
 // Replaces SimpleKNN::knn (scene/simple_knn/cuda_headers/simple_knn.cu:185-221; python entry
 // scene/simple_knn/__init__.py:15-28 distCUDA2).  Same algorithm family: Morton order, 1024-point boxes,
@@ -197,6 +198,166 @@ int launch_knn(int P, const float* points, float* meanDists, void* ws, size_t ws
   const int nboxes = (P + KNN_BOX - 1) / KNN_BOX;
   hipLaunchKernelGGL(knn_box_minmax, dim3(nboxes), dim3(256), 0, s, P, points, sorted_idx, k.boxes);
   hipLaunchKernelGGL(knn_box_mean_dist, dim3((P + 255) / 256), dim3(256), 0, s, P, points, sorted_idx, k.boxes, meanDists);
+  GM_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// knn_nearest: for every query point the nearest reference point (k = 1), squared distance and index.
+//   d2 = (dx*dx + dy*dy) + dz*dz in float32, no contraction (file pragma), ties -> lowest reference index: the result is that of
+//   a float32 brute force bit for bit, whatever the search structure.
+// Structure: the reference points in Morton order (bbox and radix sort as gm_knn) cut into boxes of NN_BOX points with their
+// bounding boxes; the queries in Morton order too, so that the 64 queries of a wave are neighbours and visit the same boxes.
+// A query starts from the NN_WIN sorted reference points around its own Morton code, then visits every box whose distance
+// to it is <= the best so far.  The float distance to a box never exceeds the float distance to a point inside it (rounding
+// is monotonic), so no box holding the answer - or a tie with a lower index - is skipped.
+#define NN_BOX 256
+#define NN_WIN 8
+
+struct NnWs {
+  float* bbox_partial;   // [1024][6]
+  float* bbox;           // [8]
+  uint32_t* rkeys[2];
+  uint32_t* ridx[2];
+  uint32_t* qkeys[2];
+  uint32_t* qidx[2];
+  uint32_t* hist;
+  uint32_t* digit_total;
+  float4* rsorted;       // [Pr] x, y, z, original index (bits)
+  float4* boxes;         // [nboxes][2] min xyz, max xyz
+  char* end;
+  static NnWs from(void* ws, size_t Pq, size_t Pr) {
+    char* p = reinterpret_cast<char*>(ws);
+    // (the sort's tile size grows with n, so its block count is not monotonic in n: size for both sorts)
+    const size_t hb = sort_blocks(Pq) > sort_blocks(Pr) ? sort_blocks(Pq) : sort_blocks(Pr);
+    const size_t dc = sort_chunk_counters(Pq) > sort_chunk_counters(Pr) ? sort_chunk_counters(Pq) : sort_chunk_counters(Pr);
+    NnWs k;
+    k.bbox_partial = carve<float>(p, 1024 * 6);
+    k.bbox = carve<float>(p, 8);
+    k.rkeys[0] = carve<uint32_t>(p, Pr); k.rkeys[1] = carve<uint32_t>(p, Pr);
+    k.ridx[0] = carve<uint32_t>(p, Pr); k.ridx[1] = carve<uint32_t>(p, Pr);
+    k.qkeys[0] = carve<uint32_t>(p, Pq); k.qkeys[1] = carve<uint32_t>(p, Pq);
+    k.qidx[0] = carve<uint32_t>(p, Pq); k.qidx[1] = carve<uint32_t>(p, Pq);
+    k.hist = carve<uint32_t>(p, 256 * hb);
+    k.digit_total = carve<uint32_t>(p, dc);
+    k.rsorted = carve<float4>(p, Pr);
+    k.boxes = carve<float4>(p, 2 * ((Pr + NN_BOX - 1) / NN_BOX));
+    k.end = p;
+    return k;
+  }
+};
+
+size_t knn_nearest_workspace_bytes(int Pq, int Pr) {
+  NnWs k = NnWs::from(nullptr, (size_t)(Pq > 0 ? Pq : 1), (size_t)(Pr > 0 ? Pr : 1));
+  return (size_t)k.end + 256;
+}
+
+// Morton code against the reference bbox; queries outside it are clamped onto it (and a flat axis maps to 0)
+__device__ __forceinline__ uint32_t nn_morton_code(float x, float y, float z, const float* bb) {
+  const float v[3] = {x, y, z};
+  uint32_t c[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float ext = bb[3 + k] - bb[k];
+    float t = ext > 0.f ? (v[k] - bb[k]) / ext : 0.f;
+    t = fminf(fmaxf(t, 0.f), 1.f);               // (NaN -> 0)
+    c[k] = prep_morton((uint32_t)(t * ((1 << 10) - 1)));
+  }
+  return c[0] | (c[1] << 1) | (c[2] << 2);
+}
+
+__global__ __launch_bounds__(256) void nn_morton(int P, const float* __restrict__ pts, const float* __restrict__ bbox, uint32_t* __restrict__ codes) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  codes[i] = nn_morton_code(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2], bbox);
+}
+
+// sorted reference points as float4 (w = original index) and the bounding box of every NN_BOX of them (one workgroup per box)
+__global__ __launch_bounds__(NN_BOX) void nn_gather_boxes(int Pr, const float* __restrict__ ref, const uint32_t* __restrict__ idx,
+                                                          float4* __restrict__ rsorted, float4* __restrict__ boxes) {
+  __shared__ float sm[NN_BOX / 64][6];
+  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  const int i = blockIdx.x * NN_BOX + threadIdx.x;
+  if (i < Pr) {
+    const uint32_t g = idx[i];
+    const float x = ref[3 * (size_t)g], y = ref[3 * (size_t)g + 1], z = ref[3 * (size_t)g + 2];
+    rsorted[i] = make_float4(x, y, z, __uint_as_float(g));
+    mn[0] = mx[0] = x; mn[1] = mx[1] = y; mn[2] = mx[2] = z;
+  }
+  block_minmax(mn, mx, sm);
+  if (threadIdx.x == 0) {
+    boxes[2 * blockIdx.x] = make_float4(mn[0], mn[1], mn[2], 0.f);
+    boxes[2 * blockIdx.x + 1] = make_float4(mx[0], mx[1], mx[2], 0.f);
+  }
+}
+
+__device__ __forceinline__ float nn_d2(float px, float py, float pz, const float4 r) {
+  const float dx = px - r.x, dy = py - r.y, dz = pz - r.z;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+__device__ __forceinline__ void nn_take(float d, uint32_t id, float& best, uint32_t& bid) {
+  if (d < best || (d == best && id < bid)) { best = d; bid = id; }
+}
+__device__ __forceinline__ float nn_axis(float p, float lo, float hi) { return p < lo ? lo - p : (p > hi ? p - hi : 0.f); }
+
+// one thread per Morton-sorted query
+__global__ __launch_bounds__(256) void nn_query(int Pq, const float* __restrict__ query, const uint32_t* __restrict__ qidx, int Pr,
+                                                const uint32_t* __restrict__ rkeys, const float4* __restrict__ rsorted,
+                                                const float4* __restrict__ boxes, int nboxes, const float* __restrict__ bbox,
+                                                float* __restrict__ out_d2, int* __restrict__ out_idx) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Pq) return;
+  const uint32_t q = qidx[i];
+  const float px = query[3 * (size_t)q], py = query[3 * (size_t)q + 1], pz = query[3 * (size_t)q + 2];
+  // start: the sorted reference points around the query's own Morton code
+  const uint32_t code = nn_morton_code(px, py, pz, bbox);
+  int lo = 0, hi = Pr;                           // lower_bound
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (rkeys[mid] < code) lo = mid + 1; else hi = mid;
+  }
+  float best = INFINITY;                         // (an infinite distance is still taken, lowest index first)
+  uint32_t bid = 0xFFFFFFFFu;
+  const int j0 = max(0, lo - NN_WIN), j1 = min(Pr, lo + NN_WIN);
+  for (int j = j0; j < j1; j++) {
+    const float4 r = rsorted[j];
+    nn_take(nn_d2(px, py, pz, r), __float_as_uint(r.w), best, bid);
+  }
+  for (int b = 0; b < nboxes; b++) {
+    const float4 bmn = boxes[2 * b], bmx = boxes[2 * b + 1];
+    const float d0 = nn_axis(px, bmn.x, bmx.x), d1 = nn_axis(py, bmn.y, bmx.y), d2 = nn_axis(pz, bmn.z, bmx.z);
+    if ((d0 * d0 + d1 * d1) + d2 * d2 > best) continue;
+    const int e = min(Pr, (b + 1) * NN_BOX);
+    for (int j = b * NN_BOX; j < e; j++) {
+      const float4 r = rsorted[j];
+      nn_take(nn_d2(px, py, pz, r), __float_as_uint(r.w), best, bid);
+    }
+  }
+  out_d2[q] = best;
+  out_idx[q] = (int)bid;
+}
+
+int launch_knn_nearest(int Pq, const float* query, int Pr, const float* ref, float* out_d2, int* out_idx, void* ws, size_t ws_bytes,
+                       hipStream_t s) {
+  if (Pq <= 0) return 0;
+  const size_t need = knn_nearest_workspace_bytes(Pq, Pr);
+  if (ws_bytes < need) { set_error("gm_knn_nearest: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
+  NnWs k = NnWs::from(ws, (size_t)Pq, (size_t)Pr);
+  const int nb = min(1024, (Pr + 255) / 256);
+  hipLaunchKernelGGL(knn_bbox_partial, dim3(nb), dim3(256), 0, s, Pr, ref, k.bbox_partial);
+  hipLaunchKernelGGL(knn_bbox_final, dim3(1), dim3(256), 0, s, nb, k.bbox_partial, k.bbox);
+  hipLaunchKernelGGL(nn_morton, dim3((Pr + 255) / 256), dim3(256), 0, s, Pr, ref, k.bbox, k.rkeys[0]);
+  hipLaunchKernelGGL(nn_morton, dim3((Pq + 255) / 256), dim3(256), 0, s, Pq, query, k.bbox, k.qkeys[0]);
+  GM_HIP(hipGetLastError());
+  // 30-bit keys: 4 passes of 8 bits, the result lands back in slot 0
+  int rc = radix_sort_pairs(k.rkeys, k.ridx, k.hist, k.digit_total, (size_t)Pr, 30, true, 0, s);
+  if (rc) return rc;
+  rc = radix_sort_pairs(k.qkeys, k.qidx, k.hist, k.digit_total, (size_t)Pq, 30, true, 0, s);
+  if (rc) return rc;
+  const int nboxes = (Pr + NN_BOX - 1) / NN_BOX;
+  hipLaunchKernelGGL(nn_gather_boxes, dim3(nboxes), dim3(NN_BOX), 0, s, Pr, ref, k.ridx[0], k.rsorted, k.boxes);
+  hipLaunchKernelGGL(nn_query, dim3((Pq + 255) / 256), dim3(256), 0, s, Pq, query, k.qidx[0], Pr, k.rkeys[0], k.rsorted, k.boxes, nboxes,
+                     k.bbox, out_d2, out_idx);
   GM_HIP(hipGetLastError());
   return 0;
 }

@@ -6,6 +6,7 @@
 //       get_opacity  = sigmoid(_opacity)                                                              :172-174
 //     In the reference these are ~15 Jittor elementwise ops forward and ~25 in the autograd pass, each a pass over P;
 //     here one kernel each way (60 B in, 44 B out per Gaussian forward).
+//   plain_activate_fwd / _bwd : the same for the plain 3DGS model (scene/gaussian_model.py), xyz being a parameter itself.
 //   adam_kernel : jittor.nn.Adam's update for all parameter groups of the model in ONE launch (table of tensors,
 //     per-group learning rate; the SH tensor [P,16,3] takes two rates - coefficient 0 is the reference's "f_dc" group,
 //     the rest "f_rest" - so no concatenation / split of the 192-byte SH rows is needed per iteration):
@@ -132,6 +133,78 @@ int launch_mesh_activate_bwd(const ActArgs& a, const float* d_xyz, const float* 
   hipLaunchKernelGGL(mesh_activate_bwd_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a, d_xyz, d_scales,
                      reinterpret_cast<const float4*>(d_rots), d_opac, d_bc, d_dist, d_scaling, reinterpret_cast<float4*>(d_rotation), d_opacity,
                      mr_weight, d_mr);
+  GM_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// plain_activate_fwd / _bwd : GaussianModel's raw parameters -> rasterizer inputs and the adjoint (scene/gaussian_model.py:26-43,
+// 96-117): xyz copied, scales = exp(_scaling), rots = _rotation / max(|_rotation|, 1e-12), opac = sigmoid(_opacity).  The outputs
+// (forward) and the incoming gradients (backward) are rows [row0, row0 + N) of buffers that may hold more rows (the joint
+// [background; object] buffers of renderer.bg_render).  expf, not __expf, and the forward in torch's own formulas (sigmoid =
+// 1 / (1 + exp(-x)), q / max(|q|, eps) by division) and the opacity adjoint as torch / Jittor form it, g (1 - s) s in float32: 0 where
+// s rounds to 1 (x > ~17).  A more accurate e / (1 + e)^2 there would hand Adam ~1e-13 gradients that it turns into full-rate steps
+// the reference never takes.
+__global__ __launch_bounds__(256) void plain_activate_fwd_kernel(int N, const float* __restrict__ xyz_in, const float* __restrict__ scaling,
+                                                                  const float4* __restrict__ rotation, const float* __restrict__ opacity,
+                                                                  float* __restrict__ xyz, float* __restrict__ scales,
+                                                                  float4* __restrict__ rots, float* __restrict__ opac) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const size_t i3 = 3 * (size_t)i;
+#pragma unroll
+  for (int c = 0; c < 3; c++) { xyz[i3 + c] = xyz_in[i3 + c]; scales[i3 + c] = expf(scaling[i3 + c]); }
+  const float4 q = rotation[i];
+  const float n = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-12f);   // F.normalize eps
+  rots[i] = make_float4(q.x / n, q.y / n, q.z / n, q.w / n);
+  opac[i] = 1.0f / (1.0f + expf(-opacity[i]));
+}
+
+__global__ __launch_bounds__(256) void plain_activate_bwd_kernel(int N, const float* __restrict__ scaling, const float4* __restrict__ rotation,
+                                                                  const float* __restrict__ opacity, const float* __restrict__ g_xyz,
+                                                                  const float* __restrict__ g_scales, const float4* __restrict__ g_rots,
+                                                                  const float* __restrict__ g_opac, float* __restrict__ d_xyz,
+                                                                  float* __restrict__ d_scaling, float4* __restrict__ d_rotation,
+                                                                  float* __restrict__ d_opacity) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const size_t i3 = 3 * (size_t)i;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    d_xyz[i3 + c] = g_xyz ? g_xyz[i3 + c] : 0.f;
+    d_scaling[i3 + c] = g_scales ? g_scales[i3 + c] * expf(scaling[i3 + c]) : 0.f;
+  }
+  const float4 q = rotation[i];
+  const float4 g = g_rots ? g_rots[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float len = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+  const float qn = 1.0f / fmaxf(len, 1e-12f);
+  if (len > 1e-12f) {                            // d(q/|q|) = (g - y (y.g)) / |q|
+    const float4 y = make_float4(q.x * qn, q.y * qn, q.z * qn, q.w * qn);
+    const float yd = y.x * g.x + y.y * g.y + y.z * g.z + y.w * g.w;
+    d_rotation[i] = make_float4((g.x - y.x * yd) * qn, (g.y - y.y * yd) * qn, (g.z - y.z * yd) * qn, (g.w - y.w * yd) * qn);
+  } else {                                       // the clamp is active: q / eps
+    d_rotation[i] = make_float4(g.x * qn, g.y * qn, g.z * qn, g.w * qn);
+  }
+  const float o = 1.0f / (1.0f + expf(-opacity[i]));
+  d_opacity[i] = g_opac ? (g_opac[i] * (1.0f - o)) * o : 0.f;
+}
+
+int launch_plain_activate_fwd(int N, const float* xyz_in, const float* scaling, const float* rotation, const float* opacity, float* xyz,
+                              float* scales, float* rots, float* opac, hipStream_t s) {
+  if (N <= 0) return 0;
+  hipLaunchKernelGGL(plain_activate_fwd_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, xyz_in, scaling,
+                     reinterpret_cast<const float4*>(rotation), opacity, xyz, scales, reinterpret_cast<float4*>(rots), opac);
+  GM_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_plain_activate_bwd(int N, const float* scaling, const float* rotation, const float* opacity, const float* g_xyz,
+                              const float* g_scales, const float* g_rots, const float* g_opac, float* d_xyz, float* d_scaling,
+                              float* d_rotation, float* d_opacity, hipStream_t s) {
+  if (N <= 0) return 0;
+  hipLaunchKernelGGL(plain_activate_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, scaling, reinterpret_cast<const float4*>(rotation),
+                     opacity, g_xyz, g_scales, reinterpret_cast<const float4*>(g_rots), g_opac, d_xyz, d_scaling,
+                     reinterpret_cast<float4*>(d_rotation), d_opacity);
   GM_HIP(hipGetLastError());
   return 0;
 }

@@ -3,6 +3,9 @@
   mesh_activate(bc, distance, scaling, rotation, opacity, v1, v2, v3, normal, r, alpha=4)
       -> (xyz, scales, rotations, opacities): MeshBasedGaussianModel.get_xyz / get_scaling / get_rotation / get_opacity
          (scene/mesh_based_gaussian_model.py:122-152, 172-174) in one kernel, differentiable (one kernel backward).
+  plain_activate(xyz, scaling, rotation, opacity, joint=None)
+      -> (xyz, scales, rotations, opacities): GaussianModel.get_xyz / get_scaling / get_rotation / get_opacity
+         (scene/gaussian_model.py:26-43, 96-117) in one kernel each way.
   FusedAdam(groups, eps, betas)
       jittor.nn.Adam's update rule for all groups in one launch per step (scene/mesh_based_gaussian_model.py:242-263).
 """
@@ -76,6 +79,56 @@ def mesh_activate(bc, distance, scaling, rotation, opacity, v1, v2, v3, normal, 
     whole buffers (the gradient of the tail rows is dropped)."""
     out = _MeshActivate.apply(bc, distance, scaling, rotation, opacity, v1, v2, v3, normal, r, alpha, mr_weight, joint)
     return out if mr_weight is not None else out[:4]
+
+
+class _PlainActivate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, scaling, rotation, opacity, joint=None):
+        lib = _lib.lib()
+        dev = xyz.device
+        if dev.type != "cuda":
+            raise _lib.GmeshError("plain_activate needs tensors on a HIP (cuda) device; there is no CPU path")
+        ins = [_c(t) for t in (xyz, scaling, rotation, opacity)]
+        N = ins[0].shape[0]
+        f = dict(dtype=torch.float32, device=dev)
+        if joint is None:
+            outs = (torch.empty((N, 3), **f), torch.empty((N, 3), **f), torch.empty((N, 4), **f), torch.empty((N, 1), **f))
+        else:
+            # the heads of persistent joint [N + Nm, .] buffers (renderer.bg_render): same contract as _MeshActivate's joint - one
+            # forward per backward; the version bump makes a backward of an earlier forward raise instead of reading new values
+            outs = tuple(joint[k].view_as(joint[k]) for k in ("xyz", "scales", "rots", "opac"))
+            for t in outs:
+                torch.autograd.graph.increment_version(t)
+        cap = outs[0].shape[0]
+        with torch.cuda.device(dev):
+            _lib.check(lib.gm_plain_activate_fwd(N, *[t.data_ptr() for t in ins], *[t.data_ptr() for t in outs], 0, cap,
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+        ctx.save_for_backward(ins[1], ins[2], ins[3])
+        ctx.N, ctx.cap = N, cap
+        ctx.shapes = [tuple(t.shape) for t in (xyz, scaling, rotation, opacity)]
+        return outs
+
+    @staticmethod
+    def backward(ctx, d_xyz, d_scales, d_rots, d_opac):
+        lib = _lib.lib()
+        scaling, rotation, opacity = ctx.saved_tensors
+        dev = scaling.device
+        N = ctx.N
+        f = dict(dtype=torch.float32, device=dev)
+        outs = (torch.empty((N, 3), **f), torch.empty((N, 3), **f), torch.empty((N, 4), **f), torch.empty((N,), **f))
+        g = [None if t is None else _c(t) for t in (d_xyz, d_scales, d_rots, d_opac)]
+        with torch.cuda.device(dev):
+            _lib.check(lib.gm_plain_activate_bwd(N, scaling.data_ptr(), rotation.data_ptr(), opacity.data_ptr(),
+                                                 *[None if t is None else t.data_ptr() for t in g], 0, ctx.cap, *[t.data_ptr() for t in outs],
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+        return tuple(o.reshape(s) for o, s in zip(outs, ctx.shapes)) + (None,)
+
+
+def plain_activate(xyz, scaling, rotation, opacity, joint=None):
+    """(xyz, exp(scaling), rotation / max(|rotation|, 1e-12), sigmoid(opacity)) from one fused kernel (gm_plain_activate_fwd / _bwd),
+    differentiable.  joint: dict of persistent [N + Nm, .] buffers "xyz", "scales", "rots", "opac" whose tails hold a frozen cloud; the
+    kernel writes their leading N rows and the outputs are the whole buffers (the gradient of the tail rows is dropped)."""
+    return _PlainActivate.apply(xyz, scaling, rotation, opacity, joint)
 
 
 class FusedAdam:

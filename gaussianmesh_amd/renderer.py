@@ -249,9 +249,82 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     return out
 
 
+def plain_joint_buffers(pc, mesh_gaussians):
+    """Persistent [N + Nm, .] buffers of bg_render's fused route for a bg_model.PlainGaussians `pc`: rows in the reference's order,
+    the N background rows first, then the Nm rows of the frozen `mesh_gaussians` (None: Nm = 0).  The tails - positions, scales,
+    rotations, opacities and SH rows of the object - are written once per (model, mesh model, row count); gm_plain_activate_fwd
+    writes the heads every iteration; "shs" is the joint SH buffer whose head the model's `_features` is a view of after
+    PlainGaussians.share_feature_storage; "ss" is the screen-space probe of all N + Nm rows (a leaf; its hook hands the first N rows
+    of its .grad to pc.screenspace_points.grad, as _joint_buffers does)."""
+    N, K = pc._xyz.shape[0], pc._features.shape[1]
+    dev = pc._xyz.device
+    Nm = 0 if mesh_gaussians is None else int(mesh_gaussians.get_xyz.shape[0])
+    jb = getattr(pc, "_plain_joint", None)
+    if jb is not None and jb["N"] == N and jb["Nm"] == Nm and jb["mesh"] is mesh_gaussians and jb["K"] == K and jb["xyz"].device == dev:
+        return jb
+    f = dict(dtype=torch.float32, device=dev)
+    jb = {"N": N, "Nm": Nm, "K": K, "mesh": mesh_gaussians, "xyz": torch.empty((N + Nm, 3), **f), "scales": torch.empty((N + Nm, 3), **f),
+          "rots": torch.empty((N + Nm, 4), **f), "opac": torch.empty((N + Nm, 1), **f), "shs": torch.empty((N + Nm, K, 3), **f),
+          "ss": torch.zeros((N + Nm, 3), requires_grad=True, **f)}
+    if Nm:
+        m = mesh_gaussians
+        with torch.no_grad():
+            jb["xyz"][N:].copy_(m.get_xyz); jb["scales"][N:].copy_(m.get_scaling); jb["rots"][N:].copy_(m.get_rotation)
+            jb["opac"][N:].copy_(m.get_opacity.reshape(-1, 1)); jb["shs"][N:].copy_(m.get_features[:, :K])
+    import weakref
+    ref = weakref.ref(pc)
+
+    def to_model(grad, n=N):
+        p = ref()
+        if p is not None and p.screenspace_points.shape[0] == n:
+            p.screenspace_points.grad = grad[:n]
+        return grad
+    jb["ss"].register_hook(to_model)
+    pc._plain_joint = jb
+    return jb
+
+
+def _bg_render_plain(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, mesh_gaussians, return_aux):
+    """bg_render's fused route (see bg_render): one activation kernel into the heads of the joint buffers, no concatenation."""
+    from .model_ops import plain_activate
+    jb = plain_joint_buffers(pc, mesh_gaussians)
+    N = jb["N"]
+    screenspace_points = jb["ss"]
+    screenspace_points.grad = None
+    if pc.screenspace_points.grad is not None:
+        pc.screenspace_points.grad = None
+    means3D, scales, rotations, opacity = plain_activate(pc._xyz, pc._scaling, pc._rotation, pc._opacity, jb)
+    feats = pc._features
+    if feats.data_ptr() == jb["shs"].data_ptr() and feats.shape == jb["shs"][:N].shape:
+        shs = _SharedRows.apply(feats, jb["shs"])
+    else:                                        # (rows not shared - share_feature_storage not called: one copy per call)
+        shs = torch.cat([feats, jb["shs"][N:]], dim=0)
+    rasterizer = GaussianRasterizer(_settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree, pipe.debug))
+    if return_aux:
+        rendered_image, radii, depth, alpha = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=None,
+                                                         opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=None,
+                                                         return_aux=True)
+        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
+                "depth": depth, "alpha": alpha}
+    rendered_image, radii = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=None, opacities=opacity,
+                                       scales=scales, rotations=rotations, cov3D_precomp=None)
+    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+
+
+def _plain_fused(pc, pipe, override_color):
+    from .bg_model import PlainGaussians
+    return (isinstance(pc, PlainGaussians) and getattr(pc, "fused", True) and pc._xyz.is_cuda and not pipe.compute_cov3D_python and
+            override_color is None and not pipe.convert_SHs_python)
+
+
 def bg_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, mesh_gaussians=None, return_aux=False):
     """gaussian_renderer/__init__.py:146-260: background model trained with the (frozen) mesh Gaussians composited in.
     return_aux: "depth" and "alpha" as in render()."""
+    if _plain_fused(pc, pipe, override_color):
+        # a bg_model.PlainGaussians on the GPU (rasterizer covariances, rasterizer SH): persistent joint [background; object] buffers
+        # (plain_joint_buffers), one fused activation kernel, the SH rows shared instead of concatenated.  Same CONTRACT as render()'s
+        # joint buffers: one forward per backward; "viewspace_points" is the joint probe, pc.screenspace_points.grad its first N rows.
+        return _bg_render_plain(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, mesh_gaussians, return_aux)
     screenspace_points = pc.screenspace_points
     if mesh_gaussians is not None:
         screenspace_points = torch.cat([screenspace_points, mesh_gaussians.screenspace_points], dim=0)

@@ -197,6 +197,16 @@ void* gm_binning_field(void* binning_buffer, int64_t R, int W, int H, int emissi
 size_t gm_knn_workspace_bytes(int P);
 int gm_knn(int P, const float* points, float* meanDists, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Nearest reference point of every query point (k = 1): the neighbour pruning of train_bg_gaussian.py:129-137, which removes
+ * background Gaussians close to the object's.  query float [Pq,3], ref float [Pr,3]; out_d2 float [Pq] = the SQUARED distance
+ * (dx*dx + dy*dy) + dz*dz with d = query - ref, evaluated in float32 without contraction; out_idx int32 [Pq] = the reference
+ * index, the lowest one on ties.  The result is bit-identical to a float32 brute force.  Pr == 0 is an error (refused before
+ * any GPU work); Pq == 0 does nothing.  Caller workspace of gm_knn_nearest_workspace_bytes(Pq, Pr) (O(Pq + Pr)); no host
+ * synchronisation. */
+size_t gm_knn_nearest_workspace_bytes(int Pq, int Pr);
+int gm_knn_nearest(int Pq, const float* query, int Pr, const float* ref, float* out_d2, int* out_idx, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 /* Mesh-driven deformation of bound Gaussians; replaces the Jittor tensor algebra of
  * SingleObjectDeform.deform_gaussian (edittool/__init__.py:116-131), tensor-in form:
  *   tri int32 [N,3] vertex ids of the bound face, w float [N,3] barycentric weights,
@@ -423,6 +433,19 @@ int gm_mesh_activate_bwd(int N, float alpha, const float* bc, const float* dist,
                          const float* opacity, const float* v1, const float* v2, const float* v3, const float* normal, const float* r,
                          const float* d_xyz, const float* d_scales, const float* d_rots, const float* d_opac, float* d_bc, float* d_dist,
                          float* d_scaling, float* d_rotation, float* d_opacity, float mr_weight, const float* d_mr, void* stream);
+
+/* gm_plain_activate_fwd: the plain 3DGS model's raw parameters -> rasterizer inputs (scene/gaussian_model.py:26-43, 96-117) in one pass:
+ *   out_xyz = xyz, out_scales = exp(scaling), out_rots = rotation / max(|rotation|, 1e-12), out_opac = sigmoid(opacity).
+ *   Inputs xyz/scaling float [N,3], rotation float [N,4] (16-byte aligned), opacity float [N].  The outputs are rows
+ *   [row0, row0 + N) of buffers of `capacity` rows (out_rots 16-byte aligned): the head of joint [background; object] buffers.
+ * gm_plain_activate_bwd: the adjoint.  g_xyz / g_scales / g_rots / g_opac (rows [row0, row0 + N) of `capacity`-row buffers; each
+ *   may be NULL = zero) -> d_xyz = g_xyz, d_scaling = g_scales * exp(scaling), d_rotation = the normalisation's Jacobian applied to
+ *   g_rots, d_opacity = g_opac * s (1 - s); outputs [N] rows. */
+int gm_plain_activate_fwd(int N, const float* xyz, const float* scaling, const float* rotation, const float* opacity, float* out_xyz,
+                          float* out_scales, float* out_rots, float* out_opac, int row0, int capacity, void* stream);
+int gm_plain_activate_bwd(int N, const float* scaling, const float* rotation, const float* opacity, const float* g_xyz, const float* g_scales,
+                          const float* g_rots, const float* g_opac, int row0, int capacity, float* d_xyz, float* d_scaling, float* d_rotation,
+                          float* d_opacity, void* stream);
 
 /* jittor.nn.Adam's update (the optimizer of training_setup, scene/mesh_based_gaussian_model.py:242-263) for up to 8
  * parameter tensors in one launch:  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
