@@ -70,6 +70,8 @@ SIGNATURES = {
     "gm_forward_1_aux": (i32, [i32, vp, vp, vp, i32, i32, i64, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp]),
     "gm_forward_status_async": (i32, [vp, i32, vp, vp]),
     "gm_forward_deformed_batch_async": (i32, [i32, i32, C.POINTER(BatchFrame), i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, i32, vp]),
+    "gm_forward_deformed_batch_aux_async": (i32, [i32, i32, C.POINTER(BatchFrame), i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp,
+                                                  i32, vp, C.POINTER(vp), C.POINTER(vp)]),
     "gm_mesh_rs_packed_batch": (i32, [i32, i32, i32, vp, C.POINTER(vp), vp, vp, vp, C.POINTER(vp), vp]),
     "gm_deform_shade_packed": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gm_cov_to_scale_rot": (i32, [i32, vp, vp, vp, vp]),

@@ -292,19 +292,21 @@ int gm_forward_1_aux(int emission_policy, void* geom_buffer, void* binning_buffe
                         out_color, debug, stream, status_host, flags, work_hint, true, out_depth, out_alpha);
 }
 
-int gm_forward_deformed_batch_async(int emission_policy, int K, const gm_batch_frame* frames, int P, int deg, int M, int width, int height,
-                                    const int* tri, const float* w, const float* cov, const float* pos, const float* shs, const float* opacities,
-                                    const float* background, int64_t binning_capacity, int flags, unsigned int* work_hint, int debug, void* stream) {
+// The batch entry points (gm_forward_deformed_batch_async; with aux, gm_forward_deformed_batch_aux_async): validation, then the launch chain.
+static int forward_batch_impl(const char* who, int emission_policy, int K, const gm_batch_frame* frames, int P, int deg, int M, int width, int height,
+                              const int* tri, const float* w, const float* cov, const float* pos, const float* shs, const float* opacities,
+                              const float* background, int64_t binning_capacity, int flags, unsigned int* work_hint, int debug, void* stream,
+                              bool aux, float* const* out_depth, float* const* out_alpha) {
   if (int rc = check_policy(emission_policy)) return rc;
-  if (K < 1 || K > GM_BATCH_MAX || !frames) { set_error("gm_forward_deformed_batch: 1..%d frames", GM_BATCH_MAX); return GM_ERR_INVALID_ARG; }
-  if (flags & ~(GM_BATCH_IMAGE_ONLY | GM_BATCH_COV6)) { set_error("gm_forward_deformed_batch: unknown flags 0x%x", flags); return GM_ERR_INVALID_ARG; }
-  if (P <= 0 || width <= 0 || height <= 0) { set_error("gm_forward_deformed_batch: invalid sizes P=%d W=%d H=%d (an empty cloud goes through the single-frame calls)", P, width, height); return GM_ERR_INVALID_ARG; }
-  if (deg < 0 || deg > 3 || M != 16) { set_error("gm_forward_deformed_batch: needs SH rows of M == 16 coefficients, degree 0..3"); return GM_ERR_INVALID_ARG; }
-  if (!tri || !w || !cov || !pos || !shs || !opacities || !background) { set_error("gm_forward_deformed_batch: null required input"); return GM_ERR_INVALID_ARG; }
-  if (binning_capacity <= 0) { set_error("gm_forward_deformed_batch: binning_capacity must be positive (sync-free second half)"); return GM_ERR_INVALID_ARG; }
+  if (K < 1 || K > GM_BATCH_MAX || !frames) { set_error("%s: 1..%d frames", who, GM_BATCH_MAX); return GM_ERR_INVALID_ARG; }
+  if (flags & ~(GM_BATCH_IMAGE_ONLY | GM_BATCH_COV6)) { set_error("%s: unknown flags 0x%x", who, flags); return GM_ERR_INVALID_ARG; }
+  if (P <= 0 || width <= 0 || height <= 0) { set_error("%s: invalid sizes P=%d W=%d H=%d (an empty cloud goes through the single-frame calls)", who, P, width, height); return GM_ERR_INVALID_ARG; }
+  if (deg < 0 || deg > 3 || M != 16) { set_error("%s: needs SH rows of M == 16 coefficients, degree 0..3", who); return GM_ERR_INVALID_ARG; }
+  if (!tri || !w || !cov || !pos || !shs || !opacities || !background) { set_error("%s: null required input", who); return GM_ERR_INVALID_ARG; }
+  if (binning_capacity <= 0) { set_error("%s: binning_capacity must be positive (sync-free second half)", who); return GM_ERR_INVALID_ARG; }
   const TileGrid tg(width, height, emission_policy);
   if (tg.ptiles > (1 << GM_BUCKET_BITS)) {
-    set_error("gm_forward_deformed_batch: %dx%d has %d list tiles under policy %d; a batch needs the one-pass tile sort (<= 2048)", width, height, tg.ptiles, emission_policy);
+    set_error("%s: %dx%d has %d list tiles under policy %d; a batch needs the one-pass tile sort (<= 2048)", who, width, height, tg.ptiles, emission_policy);
     return GM_ERR_INVALID_ARG;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -314,14 +316,14 @@ int gm_forward_deformed_batch_async(int emission_policy, int K, const gm_batch_f
   for (int k = 0; k < K; k++) {
     const gm_batch_frame& f = frames[k];
     if (!f.packed || !f.viewmatrix || !f.projmatrix || !f.cam_pos || !f.geom_buffer || !f.binning_buffer || !f.image_buffer || !f.out_color) {
-      set_error("gm_forward_deformed_batch: frame %d has a null pointer", k); return GM_ERR_INVALID_ARG;
+      set_error("%s: frame %d has a null pointer", who, k); return GM_ERR_INVALID_ARG;
     }
     if ((reinterpret_cast<uintptr_t>(f.geom_buffer) | reinterpret_cast<uintptr_t>(f.binning_buffer) | reinterpret_cast<uintptr_t>(f.image_buffer)) & 255) {
-      set_error("gm_forward_deformed_batch: frame %d: scratch buffers must be 256-byte aligned", k); return GM_ERR_INVALID_ARG;
+      set_error("%s: frame %d: scratch buffers must be 256-byte aligned", who, k); return GM_ERR_INVALID_ARG;
     }
     for (int j = 0; j < k; j++)
       if (frames[j].geom_buffer == f.geom_buffer || frames[j].binning_buffer == f.binning_buffer || frames[j].image_buffer == f.image_buffer || frames[j].out_color == f.out_color) {
-        set_error("gm_forward_deformed_batch: frames %d and %d share a buffer", j, k); return GM_ERR_INVALID_ARG;
+        set_error("%s: frames %d and %d share a buffer", who, j, k); return GM_ERR_INVALID_ARG;
       }
     fr[k].packed = f.packed; fr[k].viewmatrix = f.viewmatrix; fr[k].projmatrix = f.projmatrix; fr[k].cam_pos = f.cam_pos;
     fr[k].tan_fovx = f.tan_fovx; fr[k].tan_fovy = f.tan_fovy; fr[k].radii = f.radii;
@@ -332,6 +334,25 @@ int gm_forward_deformed_batch_async(int emission_policy, int K, const gm_batch_f
     B.color.d[k] = (long long)(reinterpret_cast<intptr_t>(f.out_color) - reinterpret_cast<intptr_t>(frames[0].out_color));
     B.status[k] = f.status_host;
   }
+  if (aux) {                          // the maps: each array NULL or K non-null pointers; no map range shares memory with a colour image or another map
+    const size_t HW = (size_t)width * height;
+    const float* r[3 * GM_BATCH_MAX];                  // [0, K): the colour images (3 HW floats), then the maps (HW floats): K depth, K alpha
+    for (int k = 0; k < K; k++) {
+      if ((out_depth && !out_depth[k]) || (out_alpha && !out_alpha[k])) { set_error("%s: frame %d: null map pointer in a non-null array", who, k); return GM_ERR_INVALID_ARG; }
+      r[k] = frames[k].out_color; r[K + k] = out_depth ? out_depth[k] : nullptr; r[2 * K + k] = out_alpha ? out_alpha[k] : nullptr;
+    }
+    for (int i = K; i < 3 * K; i++) {
+      if (!r[i]) continue;
+      const int k = i % K;
+      if (reinterpret_cast<uintptr_t>(r[i]) & 3) { set_error("%s: frame %d: unaligned map pointer", who, k); return GM_ERR_INVALID_ARG; }
+      for (int j = 0; j < 3 * K; j++)
+        if (j != i && overlaps(r[i], HW, r[j], j < K ? 3 * HW : HW)) {
+          set_error("%s: frame %d's %s map overlaps a colour image or another map of the batch", who, k, i < 2 * K ? "depth" : "alpha");
+          return GM_ERR_INVALID_ARG;
+        }
+      (i < 2 * K ? B.depth : B.alpha).d[k] = (long long)(reinterpret_cast<intptr_t>(r[i]) - reinterpret_cast<intptr_t>(r[i - k]));
+    }
+  }
   GeomState g = fr[0].g;
   ImageState img = ImageState::from(frames[0].image_buffer, width, height);
   BinningState b = BinningState::from(frames[0].binning_buffer, (size_t)binning_capacity);
@@ -341,10 +362,27 @@ int gm_forward_deformed_batch_async(int emission_policy, int K, const gm_batch_f
   if (int rc = launch_duplicate(g, b, P, width, height, emission_policy, (size_t)binning_capacity, debug, st, &B)) return rc;
   bool order_done = false;
   if (int rc = launch_tile_sort(g, b, img, (size_t)binning_capacity, g.counters + GM_CNT_RENDERED, tg.ptiles, &order_done, work_hint, debug, st, &B)) return rc;
-  if (!order_done) { set_error("gm_forward_deformed_batch: internal: the tile pass did not produce the dispatch order"); return GM_ERR_INVALID_ARG; }
+  if (!order_done) { set_error("%s: internal: the tile pass did not produce the dispatch order", who); return GM_ERR_INVALID_ARG; }
   return launch_render_fwd(g, b.pairs[sort_final_slot(tg.ptiles)], img, width, height, emission_policy, background, frames[0].out_color, frames[0].status_host,
-                           (flags & GM_BATCH_IMAGE_ONLY) != 0, work_hint, debug, st, false, &B);
+                           (flags & GM_BATCH_IMAGE_ONLY) != 0, work_hint, debug, st, false, &B,
+                           aux && out_depth ? out_depth[0] : nullptr, aux && out_alpha ? out_alpha[0] : nullptr, aux, aux ? g.counters : nullptr);
 }
+
+int gm_forward_deformed_batch_async(int emission_policy, int K, const gm_batch_frame* frames, int P, int deg, int M, int width, int height,
+                                    const int* tri, const float* w, const float* cov, const float* pos, const float* shs, const float* opacities,
+                                    const float* background, int64_t binning_capacity, int flags, unsigned int* work_hint, int debug, void* stream) {
+  return forward_batch_impl("gm_forward_deformed_batch", emission_policy, K, frames, P, deg, M, width, height, tri, w, cov, pos, shs, opacities,
+                            background, binning_capacity, flags, work_hint, debug, stream, false, nullptr, nullptr);
+}
+
+int gm_forward_deformed_batch_aux_async(int emission_policy, int K, const gm_batch_frame* frames, int P, int deg, int M, int width, int height,
+                                        const int* tri, const float* w, const float* cov, const float* pos, const float* shs, const float* opacities,
+                                        const float* background, int64_t binning_capacity, int flags, unsigned int* work_hint, int debug, void* stream,
+                                        float* const* out_depth, float* const* out_alpha) {
+  return forward_batch_impl("gm_forward_deformed_batch_aux", emission_policy, K, frames, P, deg, M, width, height, tri, w, cov, pos, shs, opacities,
+                            background, binning_capacity, flags, work_hint, debug, stream, true, out_depth, out_alpha);
+}
+
 
 int gm_mesh_rs_packed_batch(int K, int Vm, int nfaces, const float* V0, const float* const* V1, const int* faces, const int* adj_offsets,
                             const int* adj_faces, float* const* packed, void* stream) {

@@ -306,6 +306,7 @@ struct BatchOfs {                 // host side: the distances of a batch (all ze
   int frames;
   FrameOfs geom, binning, image, color;
   int* status[GM_BATCH_MAX];
+  FrameOfs depth, alpha;          // the maps of an AUX batch (gm_forward_deformed_batch_aux_async): read by its blend only
 };
 static inline BatchOfs single_frame() { BatchOfs b{}; b.frames = 1; return b; }
 
@@ -378,7 +379,7 @@ int launch_tile_order(ImageState& img, int tiles, uint32_t* work_hint, int debug
 int launch_render_fwd(const GeomState& g, const uint2* pairs, ImageState& img, int W, int H, int mode,
                       const float* background, float* out_color, int* status_host, bool image_only, uint32_t* work_hint, int debug,
                       hipStream_t s, bool exact_exponent = false, const BatchOfs* bt = nullptr,
-                      float* out_depth = nullptr, float* out_alpha = nullptr, bool aux = false,    // aux: the AUX blend (single frames)
+                      float* out_depth = nullptr, float* out_alpha = nullptr, bool aux = false,    // aux: the AUX blend (a batch: maps at bt->depth / alpha)
                       uint32_t* aux_latch = nullptr);                                              // (g.counters; NULL for P = 0)
 int launch_render_bwd(const GeomState& g, const uint2* pairs, ImageState& img, int W, int H, int mode,
                       const float* background, const float* dL_dpix, int debug, hipStream_t s,

@@ -237,7 +237,7 @@ struct FwdLds {                  // per wave: 5.1 KiB
 // pixel-relative form of round 2 / of the backward kernel (staged_exponent: |e - e_exact| ~ 5e-7) instead of the matrix core's
 // polynomial (~1e-5).  Everything else - lists, cull, decisions, recurrence - is the same code, so the two builds may differ only
 // where an entry's alpha or a pixel's T sits within the polynomial's error of a threshold (tests/test_gpu_parity.py).
-// AUX (gm_forward_1_aux; single frames only): the blend also writes the per-pixel maps out_alpha = 1 - T_final (the float T of the colour
+// AUX (gm_forward_1_aux; a batch: render_fwd_aux_batch_kernel): the blend also writes the per-pixel maps out_alpha = 1 - T_final (the float T of the colour
 // output) and out_depth = sum alpha_i T_i z_i over the accepted entries, z_i = the view-space depth the preprocess left in depth_key
 // (not normalised, no background term; either map may be NULL).  The survivors' z is gathered from depth_key when a batch is staged -
 // 4 bytes per survivor, the 36-byte record stays as it is.  A frame whose depth_key is stale (aux_latch[GM_CNT_DEPTH_STALE], set by a
@@ -277,6 +277,28 @@ __global__ __launch_bounds__(64) void render_fwd_aux_kernel(const uint2* __restr
 #include "gm_render_fwd_body.inc"
 #undef GM_BLEND_AUX
 }
+// The AUX blend of a batch (gm_forward_deformed_batch_aux_async): render_fwd_aux_kernel whose frame blockIdx.z also reads depth_key and
+// the latch of its own geometry buffer (rf.go) and writes its maps at its own distances (dofs, aofs: not part of RenderFrames, which the
+// plain kernels take).  A kernel of its own rather than a template parameter: the single-frame AUX kernels keep their names, argument
+// lists and instructions.
+template <bool STATE, bool EXACT>
+__global__ __launch_bounds__(64) void render_fwd_aux_batch_kernel(const uint2* __restrict__ ranges, const uint2* __restrict__ pairs,
+                                                                  const float4* __restrict__ splat, int W, int H, TileMap tm,
+                                                                  const float* __restrict__ bg, float* __restrict__ out_color,
+                                                                  float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,
+                                                                  const uint32_t* __restrict__ counters, int* __restrict__ status_host,
+                                                                  uint32_t* __restrict__ hint, const uint32_t* __restrict__ epoch, const RenderFrames rf,
+                                                                  const uint32_t* __restrict__ depth_key, float* __restrict__ out_depth,
+                                                                  float* __restrict__ out_alpha, uint32_t* __restrict__ aux_latch,
+                                                                  const FrameOfs dofs, const FrameOfs aofs) {
+  constexpr bool AUX = true, TRACE = false;
+  unsigned long long* const trace = nullptr;
+  depth_key = frame_ptr(depth_key, rf.go); aux_latch = frame_ptr(aux_latch, rf.go);
+  out_depth = frame_ptr(out_depth, dofs); out_alpha = frame_ptr(out_alpha, aofs);
+#define GM_BLEND_AUX 1
+#include "gm_render_fwd_body.inc"
+#undef GM_BLEND_AUX
+}
 
 static unsigned long long* g_render_trace = nullptr;      // debugging aid (tools/wave_trace.py), never set by the package
 extern "C" void gm_debug_render_trace(void* buffer) { g_render_trace = reinterpret_cast<unsigned long long*>(buffer); }
@@ -299,11 +321,17 @@ int launch_render_fwd(const GeomState& g, const uint2* pairs, ImageState& img, i
     for (int f = 0; f < GM_BATCH_MAX; f++) rf.status[f] = bt->status[f];
   }
   if (rf.frames > 1 && tg.ptiles <= 0) { set_error("batched blend: empty tile grid"); return 1; }
-  if (aux && bt) { set_error("the batched blend has no depth / alpha maps"); return 1; }
   if (tg.ptiles > 0) {
     const dim3 grid(tm.blocks() * 4, 1, (uint32_t)rf.frames), block(64);     // one wave (8x8 quadrant) per workgroup
     const bool exact = g_fwd_exact || exact_exponent;
-    if (aux) {
+    if (aux && bt) {
+#define GM_AUX_ARGS grid, block, 0, s, img.ranges, pairs, g.splat, W, H, tm, background, out_color, img.final_T, img.n_contrib, g.counters, status_host, \
+                    work_hint, img.epoch, rf, g.depth_key, out_depth, out_alpha, aux_latch, bt->depth, bt->alpha
+      if (exact) hipLaunchKernelGGL((render_fwd_aux_batch_kernel<true, true>), GM_AUX_ARGS);
+      else if (image_only) hipLaunchKernelGGL((render_fwd_aux_batch_kernel<false, false>), GM_AUX_ARGS);
+      else hipLaunchKernelGGL((render_fwd_aux_batch_kernel<true, false>), GM_AUX_ARGS);
+#undef GM_AUX_ARGS
+    } else if (aux) {
 #define GM_AUX_ARGS grid, block, 0, s, img.ranges, pairs, g.splat, W, H, tm, background, out_color, img.final_T, img.n_contrib, g.counters, status_host, \
                     work_hint, img.epoch, rf, g.depth_key, out_depth, out_alpha, aux_latch
       if (exact) hipLaunchKernelGGL((render_fwd_aux_kernel<true, true>), GM_AUX_ARGS);   // (as below: the EXACT build keeps the state)

@@ -186,8 +186,9 @@ def mesh_rs_packed(rest_vertices, deformed_vertices, faces, adjacency, out=None)
 
 def mesh_rs_packed_batch(rest_vertices, deformed_vertices_list, faces, adjacency, out=None):
     """gm_mesh_rs_packed_batch: the gather tables of up to GM_BATCH_MAX deformed meshes in ONE launch (the frames of a
-    rasterizer.forward_deformed_batch); deformed_vertices_list: K tensors [Vm,3]; out: optional [K,Vm,24] tensor.  Returns the K tables
-    (views of one [K,Vm,24] tensor), each bit for bit what mesh_rs_packed makes of its mesh."""
+    rasterizer.forward_deformed_batch); deformed_vertices_list: K tensors [Vm,3]; out: optional [K,Vm,24] tensor, or a list of K
+    contiguous [Vm,24] tensors (e.g. one object's rows of combined tables).  Returns the K tables (views of one [K,Vm,24] tensor, or
+    the list), each bit for bit what mesh_rs_packed makes of its mesh."""
     lib = _lib.lib()
     device = rest_vertices.device
     if device.type != "cuda":
@@ -202,6 +203,8 @@ def mesh_rs_packed_batch(rest_vertices, deformed_vertices_list, faces, adjacency
         faces = faces.detach().contiguous().to(torch.int32)
     off, adj = adjacency
     packed = out if out is not None else torch.empty((K, Vm, 24), dtype=torch.float32, device=device)
+    if isinstance(packed, (list, tuple)) and (len(packed) != K or any(t.shape != (Vm, 24) or not t.is_contiguous() for t in packed)):
+        raise ValueError("mesh_rs_packed_batch: out must hold K contiguous [Vm,24] tables")
     import ctypes as C
     from .rasterizer import _on, _stream
     pv = (C.c_void_p * K)(*[v.data_ptr() for v in V1])
@@ -210,6 +213,48 @@ def mesh_rs_packed_batch(rest_vertices, deformed_vertices_list, faces, adjacency
         _lib.check(lib.gm_mesh_rs_packed_batch(K, Vm, faces.shape[0], V0.data_ptr(), pv, faces.data_ptr(), off.data_ptr(), adj.data_ptr(), pp,
                                                _stream(device)))
     return [packed[k] for k in range(K)]
+
+
+def rest_mesh_state(vertex):
+    """The [Vm,21] frame state (V1 | R | S) of a mesh at rest: its own vertices, R = S = identity (pack_mesh_state's input)."""
+    Vm = vertex.shape[0]
+    eye = torch.eye(3, dtype=torch.float32, device=vertex.device).reshape(1, 9).expand(Vm, 9)
+    return torch.cat([_f(vertex), eye, eye], dim=1)
+
+
+def plan_sequence(sizes, frames_per_launch=4, emission_policy=None, batchable=True):
+    """Route of an edit sequence (edittool.ObjectVisualTool.render_sequence), host only: sizes = the frames' (W, H) in order.  Returns
+    [(kind, [frame indices])] in frame order:
+      "learn"  - the first frame of a resolution: forward_deformed_begin(...).finish(), which teaches the workspaces their capacity;
+      "batch"  - up to frames_per_launch consecutive frames of one resolution: rasterizer.forward_deformed_batch (a change of
+                 resolution ends a batch);
+      "single" - a frame whose resolution the batch refuses (more than 2048 list tiles under its emission policy, or batchable False,
+                 e.g. an empty cloud): the single-frame path, forward_deformed_begin / finish."""
+    from .rasterizer import _pol
+    K = int(frames_per_launch)
+    if not 1 <= K <= _lib.GM_BATCH_MAX:
+        raise ValueError("frames_per_launch: 1..%d, got %r" % (_lib.GM_BATCH_MAX, frames_per_launch))
+    plan, learned, run, run_size = [], set(), [], None
+
+    def fits(W, H):                                        # gm_forward_deformed_batch_async: the one-pass tile sort (TileGrid in gm_common.h)
+        s = max(_pol(emission_policy, W, H) - 1, 0)
+        gx, gy = (W + 15) // 16, (H + 15) // 16
+        return ((gx + (1 << s) - 1) >> s) * ((gy + (1 << s) - 1) >> s) <= 2048
+
+    for i, (W, H) in enumerate(sizes):
+        size = (int(W), int(H))
+        if run and (size != run_size or len(run) == K):
+            plan.append(("batch", run)); run = []
+        if not batchable or not fits(*size):
+            plan.append(("single", [i]))
+        elif size not in learned:
+            learned.add(size)
+            plan.append(("learn", [i]))
+        else:
+            run.append(i); run_size = size
+    if run:
+        plan.append(("batch", run))
+    return plan
 
 
 def mesh_rs(rest_vertices, deformed_vertices, faces, adjacency=None, want_state=False):
@@ -264,6 +309,7 @@ class SingleObjectDeform:
         self.gaussian_deform_cov = self.gaussian_cov
         self.gaussian_deform_rot = torch.eye(3, device=self.gaussian_pos.device).expand(self.number_gaussian, 3, 3).contiguous()
         self.gaussian_deform_cov6 = None
+        self.deform_state = None         # (V1, R, S) of the last deform(); None: the rest pose (edittool render_sequence renders it)
 
     def get_name(self):
         return self.name
@@ -274,6 +320,7 @@ class SingleObjectDeform:
                                              cur_shear.reshape(-1, 3, 3), self.gaussian_cov, self.gaussian_pos)
         self.gaussian_deform_pos, self.gaussian_deform_cov, self.gaussian_deform_rot = pos, cov, rot
         self.gaussian_deform_cov6 = cov6
+        self.deform_state = (_f(deform_vertex), cur_rot, cur_shear)
         return pos, cov, rot
 
     def deform_and_shade(self, deform_vertex, cur_rot, cur_shear, campos, deg=3):

@@ -1,0 +1,63 @@
+"""Animate an edited object: the animation loop of the reference's edit.py (its commented-out part, edit.py:46-54), batched.
+
+    python -m gaussianmesh_amd.edit_sequence --object_gaussian fg.ply --object_origin_mesh mesh.obj --mesh_sequence DIR \
+        --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N] [--frames_per_launch 4] [--save_maps]
+
+--mesh_sequence: a folder of OBJ files in numeric order (1.obj, 2.obj, ...: the reference's `mesh_sequnce`), one frame each.
+--camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
+cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
+{i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
+files are written on the host while the device renders the next batch (the generator issues batch b + 1 before it yields batch b).
+"""
+import os
+import re
+from argparse import ArgumentParser
+
+
+def mesh_sequence(folder):
+    """The OBJ files of a folder in numeric order of their names (1.obj, 2.obj, ..., 10.obj)."""
+    names = [n for n in os.listdir(folder) if n.lower().endswith(".obj")]
+    key = lambda n: (int(re.sub(r"\D", "", n) or -1), n)
+    return [os.path.join(folder, n) for n in sorted(names, key=key)]
+
+
+def main(argv=None):
+    parser = ArgumentParser(description="Render a mesh-driven animation of a mesh-bound Gaussian object")
+    parser.add_argument("--object_gaussian", type=str, required=True)
+    parser.add_argument("--object_origin_mesh", type=str, required=True)
+    parser.add_argument("--object_name", type=str, default="Object")
+    parser.add_argument("--camera_path", type=str, required=True)
+    parser.add_argument("--render_path", type=str, required=True)
+    parser.add_argument("--mesh_sequence", type=str, required=True)
+    parser.add_argument("--camera_id", type=int, default=None)
+    parser.add_argument("--frames_per_launch", type=int, default=4)
+    parser.add_argument("--save_maps", action="store_true", default=False)
+    args = parser.parse_args(argv)
+
+    import numpy as np
+    import torch
+    from .edittool import ObjectVisualTool
+    from .io import save_image
+
+    meshes = mesh_sequence(args.mesh_sequence)
+    if not meshes:
+        raise SystemExit("edit_sequence: no .obj files in %s" % args.mesh_sequence)
+    tool = ObjectVisualTool()
+    cams = tool.get_camera(args.camera_path)
+    tool.add_gaussian(args.object_gaussian, args.object_origin_mesh, args.object_name)
+    frames = [(cams[args.camera_id] if args.camera_id is not None else cams[i % len(cams)], {args.object_name: m})
+              for i, m in enumerate(meshes)]
+    os.makedirs(args.render_path, exist_ok=True)
+    with torch.no_grad():
+        for i, out in enumerate(tool.render_sequence(frames, frames_per_launch=args.frames_per_launch, aux=args.save_maps)):
+            stem = os.path.join(args.render_path, "{0:05d}".format(i))
+            image = out[0] if args.save_maps else out
+            save_image(image, stem + ".png")
+            if args.save_maps:
+                np.save(stem + "_depth.npy", out[1][0].cpu().numpy())
+                np.save(stem + "_alpha.npy", out[2][0].cpu().numpy())
+    return len(frames)
+
+
+if __name__ == "__main__":
+    main()

@@ -17,7 +17,9 @@ import torch
 
 from . import io as gio
 from .deform import SingleObjectDeform as _TensorObject
-from .deform import barycentric_weights, cov_to_scale_rot, mesh_rs, vertex_face_adjacency
+from . import _lib
+from .deform import (barycentric_weights, cov_to_scale_rot, mesh_rs, mesh_rs_packed_batch, pack_cov6, pack_mesh_state, plan_sequence,
+                     rest_mesh_state, vertex_face_adjacency)
 from .rasterizer import GaussianRasterizationSettings, NewGaussianRasterizer
 from .renderer import Camera, camera_work_hint, render_deformed
 
@@ -164,6 +166,157 @@ class ObjectVisualTool:
     def render_gaussian(self, viewpoint_camera):
         return render_deformed(viewpoint_camera, self.gaussians_list)
 
+    # ---- edit sequences: K frames per launch chain (rasterizer.forward_deformed_batch) ----
+    def _deformations(self, deformation):
+        """A frame's {object name: [Vm,3] vertices / OBJ path} -> {object index: [Vm,3] float32 device tensor}."""
+        out = {}
+        for name, v in (deformation or {}).items():
+            idx = [i for i, o in enumerate(self.gaussians_list) if o.get_name() == name]
+            if not idx:
+                raise ValueError("render_sequence: no object named %r" % (name,))
+            if isinstance(v, (str, os.PathLike)):
+                v = gio.read_obj(v)[0]
+            v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v, dtype=torch.float32, device=self.device).contiguous()
+            for i in idx:
+                if v.shape != self.gaussians_list[i].vertex.shape:
+                    raise ValueError("render_sequence: object %r: deformed vertices must be [%d,3]" % (name, self.gaussians_list[i].vertex.shape[0]))
+                out[i] = v
+        return out
+
+    def _sequence_cloud(self):
+        """All objects as ONE static cloud (face ids offset by the preceding objects' vertex counts); rebuilt when gaussians_list changes."""
+        objs = tuple(self.gaussians_list)
+        c = getattr(self, "_seq_cloud", None)
+        if c is not None and len(c["objs"]) == len(objs) and all(a is b for a, b in zip(c["objs"], objs)):
+            return c
+        cat = lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs, dim=0)
+        voff = np.cumsum([0] + [o.vertex.shape[0] for o in objs])
+        cov = cat([o.gaussian_cov for o in objs])
+        c = dict(objs=objs, voff=[int(v) for v in voff], tables={},
+                 tri=cat([o.gaussian_triangles + int(voff[i]) for i, o in enumerate(objs)]).to(torch.int32).contiguous(),
+                 weights=cat([o.coord for o in objs]).contiguous(), pos=cat([o.gaussian_pos for o in objs]).contiguous(),
+                 shs=cat([o.gaussian_feature for o in objs]).contiguous(), opac=cat([o.gaussian_o for o in objs]).contiguous())
+        cov6 = pack_cov6(cov)
+        c["cov"] = cov.contiguous() if cov6 is None else cov6
+        self._seq_cloud = c
+        return c
+
+    def _current_table(self, cloud, i):
+        """pack_mesh_state of object i's current state (its last deform(), or its rest pose), cached while that state stands."""
+        o = cloud["objs"][i]
+        st = o.deform_state
+        hit = cloud["tables"].get(i)
+        if hit is not None and hit[0] is st:
+            return hit[1]
+        state = rest_mesh_state(o.vertex) if st is None else torch.cat([st[0], st[1].reshape(-1, 9), st[2].reshape(-1, 9)], dim=1)
+        table = pack_mesh_state(state, o.vertex)
+        cloud["tables"][i] = (st, table)
+        return table
+
+    def gather_tables(self, deformations, cloud=None):
+        """The combined gather tables [K, sum Vm, 24] of K frames: per frame, the per-object tables concatenated along the vertex axis -
+        deform.mesh_rs_packed_batch of the objects a frame names (one launch per object over the frames), the cached pack_mesh_state of
+        the current state for the others.  deformations: K dicts as render_sequence takes them (or None)."""
+        cloud = self._sequence_cloud() if cloud is None else cloud
+        defs = [self._deformations(d) for d in deformations]
+        K, voff = len(defs), cloud["voff"]
+        tables = torch.empty((K, voff[-1], 24), dtype=torch.float32, device=self.device)
+        for i, o in enumerate(cloud["objs"]):
+            rows = tables[:, voff[i]:voff[i + 1]]
+            named = [k for k in range(K) if i in defs[k]]
+            if named:
+                mesh_rs_packed_batch(o.vertex, [defs[k][i] for k in named], o.faces, o._adjacency, out=[rows[k] for k in named])
+            if len(named) < K:
+                cur = self._current_table(cloud, i)
+                for k in range(K):
+                    if k not in named:
+                        rows[k].copy_(cur)
+        return tables
+
+    def render_sequence(self, frames, *, frames_per_launch=4, aux=False, bg_color=None):
+        """Render an edit sequence: frames = iterable of (camera, deformation); camera a renderer.Camera or any object with the reference's
+        camera attributes, deformation None or {object name: [Vm,3] deformed vertices (tensor / array) or an OBJ path}.  An object a frame
+        does not name is rendered in its current state (its last deform_gaussian / deform_vertices / deform, or its rest pose).
+        A generator: yields, in input order, image [3,H,W] - with aux (image, depth [1,H,W], alpha [1,H,W]) - on a white background
+        by default, as render_gaussian(return_aux=...) would; the tensors belong to the caller.  No object attribute changes.
+        Route (deform.plan_sequence): every object in one combined static cloud, frames of one resolution in batches of
+        frames_per_launch (1..GM_BATCH_MAX) through rasterizer.forward_deformed_batch - the cloud read once per batch, no host wait per
+        frame; batch b + 1 is issued before batch b is checked and yielded.  The first frame of a resolution teaches the workspaces
+        their capacity (forward_deformed_begin(...).finish()); a frame that outgrows it is rendered again, exactly; a resolution the
+        batch refuses (more than 2048 list tiles) takes the single-frame path.  Forward only."""
+        if not 1 <= int(frames_per_launch) <= _lib.GM_BATCH_MAX:
+            raise ValueError("frames_per_launch: 1..%d, got %r" % (_lib.GM_BATCH_MAX, frames_per_launch))
+        return self._render_sequence(list(frames), int(frames_per_launch), bool(aux), bg_color)
+
+    def _render_sequence(self, frames, K, aux, bg_color):
+        import math
+        from . import rasterizer as Rz
+        dev = self.device
+        cloud = self._sequence_cloud()
+        P = cloud["pos"].shape[0]
+        bg = torch.ones(3, device=dev) if bg_color is None else torch.as_tensor(bg_color, dtype=torch.float32, device=dev)
+        sizes = [(int(c.image_width), int(c.image_height)) for c, _ in frames]
+        plan = plan_sequence(sizes, K, batchable=P > 0)
+        streams = {}                                   # (W, H) -> workspaces (two batches in flight) + one work hint
+
+        def stream_of(size):
+            st = streams.get(size)
+            if st is None:
+                st = streams[size] = dict(ws=[Rz.RasterWorkspace() for _ in range(2 * K)], hint=Rz.new_work_hint(size[0], size[1], dev), next=0)
+            return st
+
+        def cam(c):
+            return dict(view=c.world_view_transform, proj=c.full_proj_transform, campos=c.camera_center,
+                        tanx=math.tan(c.FoVx * 0.5), tany=math.tan(c.FoVy * 0.5))
+
+        def share_capacity(st):
+            cap = max(w.capacity for w in st["ws"])
+            for w in st["ws"]:
+                w.capacity = cap
+
+        def issue(kind, idx):
+            st = stream_of(sizes[idx[0]])
+            W, H = sizes[idx[0]]
+            tables = self.gather_tables([frames[i][1] for i in idx], cloud)
+            cams = [cam(frames[i][0]) for i in idx]
+            if kind == "batch":
+                ws = st["ws"][st["next"]:st["next"] + len(idx)]
+                st["next"] = K - st["next"]                     # the other half of the workspaces for the next batch
+                hs = Rz.forward_deformed_batch(bg, cloud["tri"], cloud["weights"], list(tables), cloud["cov"], cloud["pos"], cloud["shs"],
+                                               cloud["opac"], cams, H, W, 3, ws, image_only=True, work_hint=st["hint"], aux=aux)
+                return hs, st
+            c = cams[0]
+            h = Rz.forward_deformed_begin(bg, cloud["tri"], cloud["weights"], tables[0], cloud["cov"], cloud["pos"], cloud["shs"], cloud["opac"],
+                                          c["view"], c["proj"], c["tanx"], c["tany"], H, W, 3, c["campos"],
+                                          workspace=st["ws"][st["next"]] if kind == "learn" else None, aux=aux)
+            return [h], st
+
+        def complete(kind, hs, st):
+            for h in hs:
+                if kind == "batch":
+                    ok, _ = h.check()
+                    out = h.result if ok else h.finish(image_only=True, work_hint=st["hint"])   # outgrew the capacity: again, exactly
+                else:
+                    out = h.finish(image_only=True, work_hint=st["hint"])
+                if kind != "single":
+                    share_capacity(st)
+                yield (out[1], out[6], out[7]) if aux else out[1]
+
+        pending = None
+        for kind, idx in plan:
+            issued = (kind,) + issue(kind, idx)
+            if kind == "learn":                             # complete it now: the next batch needs the capacity it learns
+                if pending is not None:
+                    yield from complete(*pending)
+                    pending = None
+                yield from complete(*issued)
+                continue
+            if pending is not None:
+                yield from complete(*pending)
+            pending = issued
+        if pending is not None:
+            yield from complete(*pending)
+
 
 class SceneVisualTool(ObjectVisualTool):
     """edittool.SceneVisualTool (:133-231): a free-standing background cloud plus deformed objects.  As in the reference
@@ -185,7 +338,32 @@ class SceneVisualTool(ObjectVisualTool):
         self.bg_opacity = torch.sigmoid(t(m["opacity"]))
         self.bg_deform_rot = torch.eye(3, device=self.device).repeat(self.bg_scale.shape[0], 1, 1)
 
-    def render_gaussian(self, viewpoint_camera):
+    def render_sequence(self, frames, *, frames_per_launch=4, aux=False, bg_color=None):
+        """ObjectVisualTool.render_sequence for a scene: render_gaussian per frame, in order (the objects are shaded through the
+        rasterizer's own SH with the unrotated direction, which the batch's fused pass does not compute; no batched route).  Each frame's
+        named objects are deformed for that frame and restored after it.  No depth / alpha maps (aux=True raises GmeshError)."""
+        if aux:
+            raise _lib.GmeshError("SceneVisualTool.render_sequence renders no depth / alpha maps")
+        if not 1 <= int(frames_per_launch) <= _lib.GM_BATCH_MAX:
+            raise ValueError("frames_per_launch: 1..%d, got %r" % (_lib.GM_BATCH_MAX, frames_per_launch))
+        return self._scene_sequence(frames, bg_color)
+
+    def _scene_sequence(self, frames, bg_color):
+        keys = ("gaussian_deform_pos", "gaussian_deform_cov", "gaussian_deform_rot", "gaussian_deform_cov6", "deform_state")
+        for camera, deformation in frames:
+            defs = self._deformations(deformation)
+            saved = {i: tuple(getattr(self.gaussians_list[i], k) for k in keys) for i in defs}
+            try:
+                for i, v in defs.items():
+                    self.gaussians_list[i].deform_vertices(v)
+                image = self.render_gaussian(camera, bg_color=bg_color)
+            finally:
+                for i, vals in saved.items():
+                    for k, v in zip(keys, vals):
+                        setattr(self.gaussians_list[i], k, v)
+            yield image
+
+    def render_gaussian(self, viewpoint_camera, bg_color=None):
         import math
         c = viewpoint_camera
         objs = self.gaussians_list
@@ -195,7 +373,8 @@ class SceneVisualTool(ObjectVisualTool):
         opacity = torch.cat([self.bg_opacity] + [o.gaussian_o for o in objs], dim=0)
         new_s, new_q = cov_to_scale_rot(cov)
         rs = GaussianRasterizationSettings(int(c.image_height), int(c.image_width), math.tan(c.FoVx * 0.5), math.tan(c.FoVy * 0.5),
-                                           torch.ones(3, device=self.device), 1, c.world_view_transform, c.full_proj_transform, 3,
+                                           torch.ones(3, device=self.device) if bg_color is None else bg_color, 1, c.world_view_transform,
+                                           c.full_proj_transform, 3,
                                            c.camera_center, False, False, camera_work_hint(c, self.device))
         image, _ = NewGaussianRasterizer(rs)(means3D=means3D, means2D=torch.zeros_like(means3D), shs=shs, colors_precomp=None,
                                              opacities=opacity, scales=new_s, rotations=new_q, cov3D_precomp=None)

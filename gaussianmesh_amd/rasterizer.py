@@ -554,9 +554,10 @@ def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity
     a learned capacity (frames of this stream completed through finish() before: the batch is sync-free only).  Returns K PendingForward
     handles in the state finish(sync_free=True) leaves them in: .result = (-1, color, radii, geom, binning, img); check() each of them -
     a frame whose instance count outgrew the batch's capacity is refused (image = background) and finish() renders it again, exactly,
-    through the single-frame second half.  Each frame comes out bit for bit as from forward_deformed_begin(...).finish(sync_free=True)."""
-    if aux:
-        raise _lib.GmeshError("forward_deformed_batch: the batch renders no depth / alpha maps; use forward_deformed_begin(aux=True)")
+    through the single-frame second half.  Each frame comes out bit for bit as from forward_deformed_begin(...).finish(sync_free=True).
+    aux (gm_forward_deformed_batch_aux_async): each frame also renders its depth and opacity maps; .result and finish() then end in
+    (depth [1,H,W], alpha [1,H,W]) as for forward_deformed_begin(..., aux=True), and a refused frame is rendered again through
+    gm_forward_1_aux, so its maps are exact too."""
     lib = _lib.lib()
     device = pos.device
     K = len(packed_list)
@@ -579,10 +580,13 @@ def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity
 
     def issue(stream):
         handles, frames = [], (_lib.BatchFrame * K)()
+        depth_ptrs, alpha_ptrs = (C.c_void_p * K)(), (C.c_void_p * K)()
         nbin = lib.gm_binning_bytes(cap)
         for k, (ws, c) in enumerate(zip(workspaces, cameras)):
             ws.capacity = cap
-            color, radii, geom, img, _, _, _ = _scratch(ws, P, W, H, device)
+            color, radii, geom, img, _, _, maps = _scratch(ws, P, W, H, device, aux=aux)
+            if maps is not None:
+                depth_ptrs[k], alpha_ptrs[k] = maps[0].data_ptr(), maps[1].data_ptr()
             binning = ws.get("binning", nbin, device)
             view, proj, campos, packed = (_prep(t, device) for t in (get(c, "view"), get(c, "proj"), get(c, "campos"), packed_list[k]))
             f = frames[k]
@@ -591,14 +595,17 @@ def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity
             f.geom_buffer, f.binning_buffer, f.image_buffer = geom.data_ptr(), binning.data_ptr(), img.data_ptr()
             f.out_color, f.radii, f.status_host = color.data_ptr(), radii.data_ptr(), ws.status()[0].data_ptr()
             args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)), keep=(tri, weights, cov, pos, shs, opacity, (view, proj, campos, packed)))
-            handles.append(PendingForward(policy, ws, stream, args, geom, img, color, radii, None, None, binning=binning))
-        _lib.check(lib.gm_forward_deformed_batch_async(policy, K, frames, P, int(degree), M, W, H, _ptr(tri), _ptr(weights), _ptr(cov), _ptr(pos), _ptr(shs),
-                                                       _ptr(opacity), _ptr(bg), cap, (1 if image_only else 0) | (2 if cov6 else 0),
-                                                       None if work_hint is None else work_hint.data_ptr(), int(bool(debug)), stream.cuda_stream))
+            handles.append(PendingForward(policy, ws, stream, args, geom, img, color, radii, None, None, binning=binning, maps=maps))
+        call = (policy, K, frames, P, int(degree), M, W, H, _ptr(tri), _ptr(weights), _ptr(cov), _ptr(pos), _ptr(shs), _ptr(opacity), _ptr(bg), cap,
+                (1 if image_only else 0) | (2 if cov6 else 0), None if work_hint is None else work_hint.data_ptr(), int(bool(debug)), stream.cuda_stream)
+        if aux:
+            _lib.check(lib.gm_forward_deformed_batch_aux_async(*call, depth_ptrs, alpha_ptrs))
+        else:
+            _lib.check(lib.gm_forward_deformed_batch_async(*call))
         for h in handles:
             h.status_event = h.workspace.status()[1]
             h.status_event.record(stream)
-            h.result = (-1, h.color, h.radii, h.geom, h.binning, h.img)
+            h.result = h._outputs(-1, h.binning)
         return handles
     return _begin(device, workspaces, issue)
 

@@ -333,7 +333,7 @@ int gm_forward_status_async(void* geom_buffer, int P, int* status_host, void* st
  * maps.  It completes every single-frame first half (gm_forward_0_async, gm_forward_0_deformed_async, and
  * gm_forward_0_deformed_stream_async without GM_STREAM_DIRECT).  A GM_STREAM_DIRECT first half does not write depth_key; it
  * latches that in the geometry buffer, and gm_forward_1_aux REFUSES such a frame: background, both maps 0, status word 3 = 3
- * (begin it again without the flag).  gm_forward_deformed_batch_async has no maps. */
+ * (begin it again without the flag).  The maps of a batch: gm_forward_deformed_batch_aux_async (below, next to the batch). */
 int gm_forward_1_aux(int emission_policy, void* geom_buffer, void* binning_buffer, void* image_buffer, int P, int num_rendered,
                      int64_t binning_capacity, const float* background, int width, int height, float* out_color, int debug, void* stream,
                      int* status_host, int flags, unsigned int* work_hint, float* out_depth, float* out_alpha);
@@ -351,7 +351,7 @@ int gm_forward_1_aux(int emission_policy, void* geom_buffer, void* binning_buffe
  * Sync-free second half only (the instance counts stay on the device; binning_capacity instances per frame; a frame that outgrows it is
  * refused in its own status words and rendered again by the caller through the single-frame calls).  1 <= K <= GM_BATCH_MAX; M == 16;
  * emission policies with at most 2048 list tiles (the one-pass tile sort); every scratch buffer base 256-byte aligned; the frames'
- * buffers distinct.  Like every deformed frame: forward only.  The batch renders no depth / alpha maps (gm_forward_1_aux). */
+ * buffers distinct.  Like every deformed frame: forward only.  Depth / alpha maps: gm_forward_deformed_batch_aux_async below. */
 #define GM_BATCH_MAX 8
 #define GM_BATCH_IMAGE_ONLY 1    /* as GM_FWD_IMAGE_ONLY */
 #define GM_BATCH_COV6 2          /* as GM_STREAM_COV6 */
@@ -367,6 +367,17 @@ typedef struct gm_batch_frame {
 int gm_forward_deformed_batch_async(int emission_policy, int K, const gm_batch_frame* frames, int P, int deg, int M, int width, int height,
                                     const int* tri, const float* w, const float* cov, const float* pos, const float* shs, const float* opacities,
                                     const float* background, int64_t binning_capacity, int flags, unsigned int* work_hint, int debug, void* stream);
+/* gm_forward_deformed_batch_async that also renders each frame's depth and opacity maps, as gm_forward_1_aux defines them (above).
+ * out_depth / out_alpha: host arrays of K device pointers, one float32 [H,W] map per frame (the convention of gm_mesh_rs_packed_batch);
+ * each array is NULL (no such map) or holds K non-null pointers.  Frame by frame and bit for bit: colour, radii, lists, status words and
+ * per-pixel state equal those of gm_forward_deformed_batch_async, and the maps equal those of gm_forward_0_deformed_stream_async (without
+ * GM_STREAM_DIRECT) + gm_forward_1_aux in sync-free mode; a refused frame has both maps 0 (rendered again through those two calls, its
+ * maps come out exact).  Refused with GM_ERR_INVALID_ARG before any GPU work: everything gm_forward_deformed_batch_async refuses, a NULL
+ * inside a non-null array, a map (H*W floats) that shares memory with any frame's out_color (3*H*W floats) or with any other map. */
+int gm_forward_deformed_batch_aux_async(int emission_policy, int K, const gm_batch_frame* frames, int P, int deg, int M, int width, int height,
+                                        const int* tri, const float* w, const float* cov, const float* pos, const float* shs, const float* opacities,
+                                        const float* background, int64_t binning_capacity, int flags, unsigned int* work_hint, int debug, void* stream,
+                                        float* const* out_depth, float* const* out_alpha);
 /* gm_mesh_rs_packed for the K deformed meshes of such a batch in one launch: V1[k] -> packed[k] (host arrays of K device pointers). */
 int gm_mesh_rs_packed_batch(int K, int Vm, int nfaces, const float* V0, const float* const* V1, const int* faces, const int* adj_offsets,
                             const int* adj_faces, float* const* packed, void* stream);
