@@ -12,7 +12,10 @@ All inputs are resident in HBM before the timed region.  With --gpus N every ran
 time (90 KB per step) over RCCL, one batch ahead of their use, every rank derives the per-vertex (R, S) itself (gm_mesh_rs); the
 static cloud is broadcast once before timing.  value = frames of all ranks per second (weak scaling).
 
-One JSON line on stdout (rank 0).  Extra objects: "roofline" (dominant kernel of the frame, HIP-event timing from gm_profile_*),
+One JSON line on stdout (rank 0): the headline ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", ...) and
+"config".  A plain run sets up, warms up, runs one discarded region and the timed one, writes --dump-outputs and prints the line;
+everything else runs only with --full, which first checks the fused frame against the unfused chain and adds the extra objects
+"stage_ms", "stage_roofline", "variants", "roofline" (dominant kernel of the frame, HIP-event timing from gm_profile_*),
 "frame_roofline" (whole frame), "cpu_baseline" (oracle port on the host cores, N=1 only), "fwd_bwd" (ms/iter of forward + backward
 on the same cloud through the autograd operator, with its stage times, "roofline" of the backward blend and "iteration_roofline";
 also the iteration with the L1 + SSIM loss, a whole training iteration and BASELINE config C2; N=1 only), "c5" (a bounded leg of
@@ -513,8 +516,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 300; --config c5: 1000 iterations)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=4, help="extra timed regions of the same length after the one that defines `value` "
-                    "(N=1 only): their frame rates and the median are reported beside it")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure and check everything else: the fused frame against the "
+                    "unfused chain (before timing), repeats of the timed region, the loop's variants, single-stream latency, per-stage times and "
+                    "rooflines, forward + backward, the training iteration, C2, the C5 legs and the CPU baseline (the --no-* options leave "
+                    "parts out).  Without it the run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--repeats", type=int, default=None, help="--full: extra timed regions of the same length after the one that defines "
+                    "`value` (N=1 only, default 4): their frame rates and the median are reported beside it")
     ap.add_argument("--gaussians", type=int, default=1_000_000)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -555,13 +562,13 @@ def main():
                     "with GM_FWD_IMAGE_ONLY by default")
     ap.add_argument("--no-discard-region", action="store_true", help="time the FIRST region of K steps behind the W warm-up steps (rounds 1-4) "
                     "instead of running one discarded region of K steps in front of the timed one")
-    ap.add_argument("--no-variants", dest="variants", action="store_false", help="N = 1: leave out the two extra regions that time the loop with "
+    ap.add_argument("--no-variants", dest="variants", action="store_false", help="--full, N = 1: leave out the two extra regions that time the loop with "
                     "the backward state written / with [N,3,3] rest covariances (`variants` of the bench line)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fwd-bwd", action="store_true")
-    ap.add_argument("--no-c5", action="store_true", help="leave out the C5 legs (the 3 M-Gaussian 4K training loop: the reference's first 1000 "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline (the oracle port on the host cores)")
+    ap.add_argument("--no-fwd-bwd", action="store_true", help="--full: leave out forward + backward, the training iteration, C2 and the C5 legs")
+    ap.add_argument("--no-c5", action="store_true", help="--full: leave out the C5 legs (the 3 M-Gaussian 4K training loop: the reference's first 1000 "
                     "iterations with their schedule, and --c5-iters iterations at a fixed topology)")
-    ap.add_argument("--c5-iters", type=int, default=200)
+    ap.add_argument("--c5-iters", type=int, default=200, help="--full: iterations of the fixed-topology C5 leg and of each SH degree's phase")
     ap.add_argument("--c5-scene", default="r05", choices=["r05", "r04"], help="--config c5: r05 = the teacher has features the student misplaced (densify_and_prune "
                     "splits ~1000 rows at 600 / 800 / 1000), r04 = the scene of rounds 1-4 (one row)")
     ap.add_argument("--c5-fixed", action="store_true", help="--config c5: time the fixed-topology SH-degree-3 leg of rounds 1-3 instead of the "
@@ -572,6 +579,10 @@ def main():
     args = ap.parse_args()
     if args.steps is not None and args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.repeats is not None and not args.full:
+        ap.error("--repeats times extra regions of a --full run")
+    if args.repeats is None:
+        args.repeats = 4
     if args.config == "c5":
         if args.dump_outputs:
             ap.error("--dump-outputs covers the C3 frame loop (the default --config)")
@@ -596,6 +607,7 @@ def main():
     if pinned is not None:
         torch.set_num_threads(max(1, min(4, len(pinned))))
     image_only = not args.backward_state
+    full = args.full                             # everything beyond the headline (see --full)
     # GM_BENCH_SHARE_DEVICE=1 + GM_BENCH_BACKEND=gloo: functional smoke test of the N>1 path on a one-GPU box
     # (RCCL refuses two ranks on one device); never used for measurements.
     if os.environ.get("GM_BENCH_SHARE_DEVICE") == "1":
@@ -849,8 +861,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    if rank == 0 and not args.unfused and not os.environ.get("GM_DEBUG_STOP_AFTER"):   # (tools/stage_marginal.sh: truncated frames)
-        # the timed path (fused deform + colour + preprocess, async halves) must render what the unfused chain
+    if full and rank == 0 and not args.unfused and not os.environ.get("GM_DEBUG_STOP_AFTER"):   # (tools/stage_marginal.sh: truncated frames)
+        # --full: the timed path (fused deform + colour + preprocess, async halves) must render what the unfused chain
         # (gm_deform_shade_packed -> gm_forward_0/1) renders for the same frame: bit-identical image and radii
         c = cam_t[multiview.view_for_step(0, F, rank, world)]
         pk = pack_mesh_state(g["mesh"][0], g["verts"])
@@ -926,7 +938,7 @@ def main():
     repeats = []
     variants = {}
     single_stream_ms = single_stream_sf_ms = None
-    if world == 1:
+    if world == 1 and full:
         nxt = first + args.steps
         for _ in range(max(0, args.repeats)):    # the same region again: run-to-run spread of the pipelined loop
             repeats.append(args.steps / timed_region(nxt))
@@ -1018,7 +1030,7 @@ def main():
             out["single_stream"]["sync_free_note"] = ("the same frames enqueued in one go each (binning capacity known from the frames before, instance count left on "
                                                       "the device, status words read after the image), stream drained after every frame")
 
-    if rank == 0:
+    if rank == 0 and full:
         # ---- per-stage HIP-event timing over a second pass of the same steps (events perturb the pipelining a
         # little, so they are kept out of the region that defines `value`)
         # ... and on ONE stream, so a stage's events bracket only its own kernels
@@ -1126,7 +1138,7 @@ def main():
             out["frame_roofline"]["valu_issue_ms"] = sum(frame_valu) * 4.2 / (1024 * 2.4e9) * 1e3
             out["frame_roofline"]["valu_issue_frac"] = out["frame_roofline"]["valu_issue_ms"] / (1e3 * elapsed / args.steps)
 
-    if rank == 0 and world == 1 and not args.no_fwd_bwd:
+    if full and rank == 0 and world == 1 and not args.no_fwd_bwd:
         # ---- forward + backward through the autograd operator (train-time input mode: SH + scale/rot)
         from gaussianmesh_amd import GaussianRasterizer, GaussianRasterizationSettings
         c = cam_t[0]
@@ -1274,7 +1286,7 @@ def main():
         torch.cuda.synchronize()
         out["fwd_bwd"]["c2_500k_ms_per_iter"] = 1e3 * (time.perf_counter() - t1) / nit
 
-    if rank == 0 and world == 1 and not args.no_fwd_bwd and not args.no_c5:
+    if full and rank == 0 and world == 1 and not args.no_fwd_bwd and not args.no_c5:
         # ---- bounded C5 leg: BASELINE config C5 (3 M Gaussians, 3840x2160, the train_mesh_gaussian.py iteration) on the same box,
         # --c5-iters iterations of Trainer.step; `python bench.py --config c5` runs the 1000 iterations of the config as a line of its own
         host_keep = {k: g[k].cpu() for k in ("tri", "weights", "pos", "cov", "opac", "shs", "verts")} if not args.no_cpu_baseline else None
@@ -1296,7 +1308,7 @@ def main():
     else:
         host_keep = mesh_keep = None
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # ---- CPU baseline: the oracle port (plain C + OpenMP) on the host cores, bounded sample of the same workload
         from oracle import oracle as orc
         nfr_max, budget_s = 24, 10.0                # bounded sample: at least 2 frames, then until ~10 s of host work

@@ -1,4 +1,5 @@
 #!/bin/bash
 cd ${GRAFT_REPO_ROOT:-.}
-python bench.py --steps 100 --warmup 10 --repeats 2 --no-cpu-baseline --no-fwd-bwd > gpurun_out/fwd_$1.json 2> gpurun_out/fwd_$1.err || tail -3 gpurun_out/fwd_$1.err
-python tools/show.py gpurun_out/fwd_$1.json
+outdir=${GM_TOOLS_OUT:-tools_out}; mkdir -p $outdir
+python bench.py --full --steps 100 --warmup 10 --repeats 2 --no-cpu-baseline --no-fwd-bwd > $outdir/fwd_$1.json 2> $outdir/fwd_$1.err || tail -3 $outdir/fwd_$1.err
+python tools/show.py $outdir/fwd_$1.json

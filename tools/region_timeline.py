@@ -8,6 +8,6 @@ regions = int(sys.argv[1]) if len(sys.argv) > 1 else 6
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 warm = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 os.environ["GM_BENCH_TIMELINE"] = str(regions)
-sys.argv = ["bench.py", "--steps", str(steps), "--warmup", str(warm), "--repeats", str(regions - 1), "--no-cpu-baseline", "--no-fwd-bwd", "--no-c5"]
+sys.argv = ["bench.py", "--full", "--steps", str(steps), "--warmup", str(warm), "--repeats", str(regions - 1), "--no-cpu-baseline", "--no-fwd-bwd", "--no-c5"]
 import bench
 bench.main()
