@@ -17,6 +17,7 @@ _lib = None
 vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 
 GM_BATCH_MAX = 8
+GM_SCENE_OBJECTS_MAX = 32
 
 
 class BatchFrame(C.Structure):
@@ -72,6 +73,8 @@ SIGNATURES = {
     "gm_forward_deformed_batch_async": (i32, [i32, i32, C.POINTER(BatchFrame), i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, i32, vp]),
     "gm_forward_deformed_batch_aux_async": (i32, [i32, i32, C.POINTER(BatchFrame), i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp,
                                                   i32, vp, C.POINTER(vp), C.POINTER(vp)]),
+    "gm_forward_scene_batch_async": (i32, [i32, i32, C.POINTER(BatchFrame), i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_uint),
+                                           vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, i32, vp]),
     "gm_mesh_rs_packed_batch": (i32, [i32, i32, i32, vp, C.POINTER(vp), vp, vp, vp, C.POINTER(vp), vp]),
     "gm_deform_shade_packed": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gm_cov_to_scale_rot": (i32, [i32, vp, vp, vp, vp]),

@@ -292,17 +292,69 @@ int gm_forward_1_aux(int emission_policy, void* geom_buffer, void* binning_buffe
                         out_color, debug, stream, status_host, flags, work_hint, true, out_depth, out_alpha);
 }
 
-// The batch entry points (gm_forward_deformed_batch_async; with aux, gm_forward_deformed_batch_aux_async): validation, then the launch chain.
+// The scene batch (gm_forward_scene_batch_async): its row layout, per-frame deformation masks and static (scale, rotation) rows
+struct SceneRows {
+  int n_objects;
+  const int* object_rows;
+  const unsigned int* deformed;
+  const float *scales, *rots;
+};
+
+// gm_forward_scene_batch_async's own refusals: the row layout, the masks, and buffers of the batch that overlap as ranges
+static int check_scene_batch(const char* who, const SceneRows& sc, int K, const gm_batch_frame* frames, int P, int width, int height,
+                             int64_t binning_capacity, const int* tri, const float* w, const float* cov) {
+  const int n = sc.n_objects;
+  if (n < 0 || n > GM_SCENE_OBJECTS_MAX) { set_error("%s: n_objects = %d, not in 0..GM_SCENE_OBJECTS_MAX (%d)", who, n, GM_SCENE_OBJECTS_MAX); return GM_ERR_INVALID_ARG; }
+  for (int j = 0; j <= n; j++) {
+    const int r = sc.object_rows[j];
+    if (r < 0 || r > P || (j > 0 && r < sc.object_rows[j - 1])) {
+      set_error("%s: object_rows must ascend within [0, P = %d]: object_rows[%d] = %d", who, P, j, r); return GM_ERR_INVALID_ARG;
+    }
+  }
+  for (int k = 0; k < K; k++) {
+    const unsigned int m = sc.deformed[k];
+    if (n < 32 && (m >> n)) { set_error("%s: frame %d: deformed mask 0x%x has a bit at or above n_objects = %d", who, k, m, n); return GM_ERR_INVALID_ARG; }
+    if (m && !frames[k].packed) { set_error("%s: frame %d deforms objects (mask 0x%x) but packed is NULL", who, k, m); return GM_ERR_INVALID_ARG; }
+    if (m && (!tri || !w || !cov)) { set_error("%s: frame %d deforms objects: tri / w / cov are required", who, k); return GM_ERR_INVALID_ARG; }
+  }
+  // every buffer a frame writes, as a byte range: no two may share memory (within a frame or between frames)
+  struct Range { uintptr_t a; size_t n; int k; const char* what; };
+  Range rg[6 * GM_BATCH_MAX];
+  int nr = 0;
+  const size_t HW = (size_t)width * height;
+  for (int k = 0; k < K; k++) {
+    const gm_batch_frame& f = frames[k];
+    rg[nr++] = {reinterpret_cast<uintptr_t>(f.geom_buffer), gm_geom_bytes(P), k, "geometry"};
+    rg[nr++] = {reinterpret_cast<uintptr_t>(f.binning_buffer), gm_binning_bytes(binning_capacity), k, "binning"};
+    rg[nr++] = {reinterpret_cast<uintptr_t>(f.image_buffer), gm_image_bytes(width, height), k, "image"};
+    rg[nr++] = {reinterpret_cast<uintptr_t>(f.out_color), 3 * HW * sizeof(float), k, "out_color"};
+    if (f.radii) rg[nr++] = {reinterpret_cast<uintptr_t>(f.radii), (size_t)P * sizeof(int), k, "radii"};
+    if (f.status_host) rg[nr++] = {reinterpret_cast<uintptr_t>(f.status_host), 4 * sizeof(int), k, "status_host"};
+  }
+  for (int x = 0; x < nr; x++)
+    for (int y = x + 1; y < nr; y++)
+      if (rg[x].a < rg[y].a + rg[y].n && rg[y].a < rg[x].a + rg[x].n) {
+        set_error("%s: frame %d's %s buffer overlaps frame %d's %s buffer", who, rg[x].k, rg[x].what, rg[y].k, rg[y].what);
+        return GM_ERR_INVALID_ARG;
+      }
+  return GM_OK;
+}
+
+// The batch entry points (gm_forward_deformed_batch_async; with aux, gm_forward_deformed_batch_aux_async; with scene,
+// gm_forward_scene_batch_async): validation, then the launch chain.
 static int forward_batch_impl(const char* who, int emission_policy, int K, const gm_batch_frame* frames, int P, int deg, int M, int width, int height,
                               const int* tri, const float* w, const float* cov, const float* pos, const float* shs, const float* opacities,
                               const float* background, int64_t binning_capacity, int flags, unsigned int* work_hint, int debug, void* stream,
-                              bool aux, float* const* out_depth, float* const* out_alpha) {
+                              bool aux, float* const* out_depth, float* const* out_alpha, const SceneRows* scene = nullptr) {
   if (int rc = check_policy(emission_policy)) return rc;
   if (K < 1 || K > GM_BATCH_MAX || !frames) { set_error("%s: 1..%d frames", who, GM_BATCH_MAX); return GM_ERR_INVALID_ARG; }
-  if (flags & ~(GM_BATCH_IMAGE_ONLY | GM_BATCH_COV6)) { set_error("%s: unknown flags 0x%x", who, flags); return GM_ERR_INVALID_ARG; }
+  if (flags & ~(scene ? GM_BATCH_IMAGE_ONLY : (GM_BATCH_IMAGE_ONLY | GM_BATCH_COV6))) { set_error("%s: unknown flags 0x%x", who, flags); return GM_ERR_INVALID_ARG; }
   if (P <= 0 || width <= 0 || height <= 0) { set_error("%s: invalid sizes P=%d W=%d H=%d (an empty cloud goes through the single-frame calls)", who, P, width, height); return GM_ERR_INVALID_ARG; }
   if (deg < 0 || deg > 3 || M != 16) { set_error("%s: needs SH rows of M == 16 coefficients, degree 0..3", who); return GM_ERR_INVALID_ARG; }
-  if (!tri || !w || !cov || !pos || !shs || !opacities || !background) { set_error("%s: null required input", who); return GM_ERR_INVALID_ARG; }
+  if (scene ? (!pos || !scene->scales || !scene->rots || !shs || !opacities || !background || !scene->object_rows || !scene->deformed)
+            : (!tri || !w || !cov || !pos || !shs || !opacities || !background)) {
+    set_error("%s: null required input", who); return GM_ERR_INVALID_ARG;
+  }
   if (binning_capacity <= 0) { set_error("%s: binning_capacity must be positive (sync-free second half)", who); return GM_ERR_INVALID_ARG; }
   const TileGrid tg(width, height, emission_policy);
   if (tg.ptiles > (1 << GM_BUCKET_BITS)) {
@@ -315,7 +367,7 @@ static int forward_batch_impl(const char* who, int emission_policy, int K, const
   B.frames = K;
   for (int k = 0; k < K; k++) {
     const gm_batch_frame& f = frames[k];
-    if (!f.packed || !f.viewmatrix || !f.projmatrix || !f.cam_pos || !f.geom_buffer || !f.binning_buffer || !f.image_buffer || !f.out_color) {
+    if ((!scene && !f.packed) || !f.viewmatrix || !f.projmatrix || !f.cam_pos || !f.geom_buffer || !f.binning_buffer || !f.image_buffer || !f.out_color) {
       set_error("%s: frame %d has a null pointer", who, k); return GM_ERR_INVALID_ARG;
     }
     if ((reinterpret_cast<uintptr_t>(f.geom_buffer) | reinterpret_cast<uintptr_t>(f.binning_buffer) | reinterpret_cast<uintptr_t>(f.image_buffer)) & 255) {
@@ -334,6 +386,8 @@ static int forward_batch_impl(const char* who, int emission_policy, int K, const
     B.color.d[k] = (long long)(reinterpret_cast<intptr_t>(f.out_color) - reinterpret_cast<intptr_t>(frames[0].out_color));
     B.status[k] = f.status_host;
   }
+  if (scene)
+    if (int rc = check_scene_batch(who, *scene, K, frames, P, width, height, binning_capacity, tri, w, cov)) return rc;
   if (aux) {                          // the maps: each array NULL or K non-null pointers; no map range shares memory with a colour image or another map
     const size_t HW = (size_t)width * height;
     const float* r[3 * GM_BATCH_MAX];                  // [0, K): the colour images (3 HW floats), then the maps (HW floats): K depth, K alpha
@@ -357,7 +411,12 @@ static int forward_batch_impl(const char* who, int emission_policy, int K, const
   ImageState img = ImageState::from(frames[0].image_buffer, width, height);
   BinningState b = BinningState::from(frames[0].binning_buffer, (size_t)binning_capacity);
   if (int rc = launch_arm_counters(g, st, &B)) return rc;
-  if (int rc = launch_deform_shade_pre_batch(K, fr, P, deg, width, height, emission_policy, tri, w, cov, pos, shs, opacities, (flags & GM_BATCH_COV6) != 0, debug, st)) return rc;
+  if (scene) {
+    if (int rc = launch_scene_shade_pre_batch(K, fr, scene->deformed, scene->n_objects, scene->object_rows, P, deg, width, height, emission_policy, pos,
+                                              scene->scales, scene->rots, shs, opacities, tri, w, cov, debug, st)) return rc;
+  } else if (int rc = launch_deform_shade_pre_batch(K, fr, P, deg, width, height, emission_policy, tri, w, cov, pos, shs, opacities, (flags & GM_BATCH_COV6) != 0, debug, st)) {
+    return rc;
+  }
   if (int rc = launch_depth_order(g, P, debug, st, nullptr, nullptr, &B)) return rc;
   if (int rc = launch_duplicate(g, b, P, width, height, emission_policy, (size_t)binning_capacity, debug, st, &B)) return rc;
   bool order_done = false;
@@ -381,6 +440,15 @@ int gm_forward_deformed_batch_aux_async(int emission_policy, int K, const gm_bat
                                         float* const* out_depth, float* const* out_alpha) {
   return forward_batch_impl("gm_forward_deformed_batch_aux", emission_policy, K, frames, P, deg, M, width, height, tri, w, cov, pos, shs, opacities,
                             background, binning_capacity, flags, work_hint, debug, stream, true, out_depth, out_alpha);
+}
+
+int gm_forward_scene_batch_async(int emission_policy, int K, const gm_batch_frame* frames, int P, int deg, int M, int width, int height,
+                                 int n_objects, const int* object_rows, const unsigned int* deformed, const float* pos, const float* scales,
+                                 const float* rots, const float* shs, const float* opacities, const int* tri, const float* w, const float* cov,
+                                 const float* background, int64_t binning_capacity, int flags, unsigned int* work_hint, int debug, void* stream) {
+  const SceneRows scene{n_objects, object_rows, deformed, scales, rots};
+  return forward_batch_impl("gm_forward_scene_batch", emission_policy, K, frames, P, deg, M, width, height, tri, w, cov, pos, shs, opacities,
+                            background, binning_capacity, flags, work_hint, debug, stream, false, nullptr, nullptr, &scene);
 }
 
 

@@ -296,6 +296,7 @@ struct BinningState {           // per-instance state (R-sized)
 // depend only on (base address mod 256, sizes), and the batch entry point insists on 256-byte aligned bases, so a field of frame f is the
 // same field of frame 0 moved by that distance.  A single-frame launch passes zeros and gridDim.z == 1.
 #define GM_BATCH_MAX 8
+#define GM_SCENE_OBJECTS_MAX 32   // objects of a scene batch (gm_forward_scene_batch_async): the width of its per-frame masks
 struct FrameOfs { long long d[GM_BATCH_MAX]; };
 template <class T>
 __device__ __forceinline__ T* frame_ptr(T* p, const FrameOfs& o) {       // (pointer arithmetic on p itself: the result keeps p's __restrict__ provenance)
@@ -417,6 +418,11 @@ struct BatchFrameArgs {
 };
 int launch_deform_shade_pre_batch(int frames, const BatchFrameArgs* fr, int P, int deg, int W, int H, int tile_cull, const int* tri, const float* w,
                                   const float* cov, const float* pos, const float* shs, const float* opacities, bool cov6, int debug, hipStream_t s);
+// the scene batch's fused pass (gm_forward_scene_batch_async): deformed[k] bit j = frame k deforms object j (rows object_rows[j] ..
+// object_rows[j + 1] - 1; tri / w / cov indexed by row - object_rows[0]); every other row is static (pos, scales, rots)
+int launch_scene_shade_pre_batch(int frames, const BatchFrameArgs* fr, const uint32_t* deformed, int n_obj, const int* object_rows, int P, int deg,
+                                 int W, int H, int tile_cull, const float* pos, const float* scales, const float* rots, const float* shs,
+                                 const float* opacities, const int* tri, const float* w, const float* cov, int debug, hipStream_t s);
 int launch_ssim_fwd(const float* img1, const float* img2, int planes, int H, int W, float* d_mu1, float* d_e11, float* d_e12,
                     float* partial, hipStream_t s);
 int launch_loss_combine(const float* partial, long long n, double c_ssim, double c_l1, double offset, float* out, hipStream_t s);

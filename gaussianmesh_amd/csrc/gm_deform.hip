@@ -491,6 +491,20 @@ __global__ __launch_bounds__(64) void deform_shade_pre_batch_kernel(int N, int d
   }
 }
 
+// one frame of a batched fused pass: camera constants and the frame's geometry buffer (shared by the object and the scene batch)
+static FusedFrame fused_frame(const BatchFrameArgs& a, int W, int H, int tile_cull) {
+  FusedFrame F{};
+  F.cam.W = W; F.cam.H = H; F.cam.gx = (W + GM_TILE - 1) / GM_TILE; F.cam.gy = (H + GM_TILE - 1) / GM_TILE;
+  F.cam.tile_cull = tile_cull; F.cam.view = a.viewmatrix; F.cam.proj = a.projmatrix;
+  F.cam.tanx = a.tan_fovx; F.cam.tany = a.tan_fovy;
+  F.cam.fy = H / (2.0f * a.tan_fovy); F.cam.fx = W / (2.0f * a.tan_fovx);      // rasterizer_impl.cu:359-360
+  F.tab = reinterpret_cast<const float4*>(a.packed); F.campos = a.cam_pos;
+  const GeomState& g = a.g;
+  F.splat = g.splat; F.radii_int = g.radii; F.radii_out = a.radii; F.tiles = g.tiles_touched; F.bin = g.bin; F.counters = g.counters; F.slots = g.slots;
+  F.coarse = g.coarse; F.depth_key = g.depth_key;
+  return F;
+}
+
 int launch_deform_shade_pre_batch(int frames, const BatchFrameArgs* fr, int P, int deg, int W, int H, int tile_cull, const int* tri, const float* w,
                                   const float* cov, const float* pos, const float* shs, const float* opacities, bool cov6, int debug, hipStream_t s) {
   if (P <= 0) return 0;
@@ -500,17 +514,8 @@ int launch_deform_shade_pre_batch(int frames, const BatchFrameArgs* fr, int P, i
   FusedBatch fb{};
   fb.frames = frames; fb.cov6 = cov6 ? 1 : 0; fb.opac = opacities;
   for (int k = 0; k < frames; k++) {
-    const BatchFrameArgs& a = fr[k];
-    if (!aligned16(a.packed)) { set_error("gm_forward_deformed_batch: packed tables must be 16-byte aligned"); return 1; }
-    FusedFrame& F = fb.f[k];
-    F.cam.W = W; F.cam.H = H; F.cam.gx = (W + GM_TILE - 1) / GM_TILE; F.cam.gy = (H + GM_TILE - 1) / GM_TILE;
-    F.cam.tile_cull = tile_cull; F.cam.view = a.viewmatrix; F.cam.proj = a.projmatrix;
-    F.cam.tanx = a.tan_fovx; F.cam.tany = a.tan_fovy;
-    F.cam.fy = H / (2.0f * a.tan_fovy); F.cam.fx = W / (2.0f * a.tan_fovx);      // rasterizer_impl.cu:359-360
-    F.tab = reinterpret_cast<const float4*>(a.packed); F.campos = a.cam_pos;
-    const GeomState& g = a.g;
-    F.splat = g.splat; F.radii_int = g.radii; F.radii_out = a.radii; F.tiles = g.tiles_touched; F.bin = g.bin; F.counters = g.counters; F.slots = g.slots;
-    F.coarse = g.coarse; F.depth_key = g.depth_key;
+    if (!aligned16(fr[k].packed)) { set_error("gm_forward_deformed_batch: packed tables must be 16-byte aligned"); return 1; }
+    fb.f[k] = fused_frame(fr[k], W, H, tile_cull);
   }
   hipLaunchKernelGGL(deform_shade_pre_batch_kernel, dim3((P + 63) / 64), dim3(64), sizeof(float) * 64 * 48, s, P, deg, tri, w, cov, pos, shs, fb);
   GM_LAUNCH_CHECK(debug, s);
@@ -618,84 +623,184 @@ int launch_deform_shade(int N, int deg, int M, const int* tri, const float* w, c
 // eigenvector matrix multiplied by sign(det) as the reference does, quaternion (w,x,y,z) by the branch-safe
 // largest-component form (the reference's w = sqrt(1+trace)/2 divides by zero for trace <= -1), normalised.
 // Eigenvector signs are not unique, so parity is on the reconstructed covariance R diag(s^2) R^T, not on (s, q).
+// cov_to_scale_rot_row: the same for row i of cov -> rots[i], scales[3 i .. 3 i + 2] (gm_cov_to_scale_rot_body.inc, the kernel's own body);
+// the scene batch's fused pass runs it on a deformed row's covariance in registers (i = 0 on local arrays).
+__device__ __forceinline__ void cov_to_scale_rot_row(const float* cov, float4* rots, float* scales, int i) {
+#include "gm_cov_to_scale_rot_body.inc"
+}
+
 __global__ __launch_bounds__(256) void cov_to_scale_rot_kernel(int N, const float* __restrict__ cov, float* __restrict__ scales,
                                                                float* __restrict__ rots) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
-  double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  const float* c = cov + 9 * (size_t)i;
-  // symmetrise (the deformed covariance RS C RS^T is symmetric up to rounding)
-  A[0][0] = c[0]; A[1][1] = c[4]; A[2][2] = c[8];
-  A[0][1] = A[1][0] = 0.5 * ((double)c[1] + c[3]);
-  A[0][2] = A[2][0] = 0.5 * ((double)c[2] + c[6]);
-  A[1][2] = A[2][1] = 0.5 * ((double)c[5] + c[7]);
-  const double scale = fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]) + 1e-300;
-  for (int sweep = 0; sweep < 8; sweep++) {
-    const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-    if (off <= 1e-15 * scale) break;
-#pragma unroll
-    for (int pq = 0; pq < 3; pq++) {
-      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-      const double apq = A[p][q];
-      if (fabs(apq) <= 1e-300) continue;
-      const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-      const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-      const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-      const int r = 3 - p - q;
-      const double arp = A[r][p], arq = A[r][q];
-      A[p][p] -= t * apq; A[q][q] += t * apq; A[p][q] = A[q][p] = 0.0;
-      A[r][p] = A[p][r] = cs * arp - sn * arq;
-      A[r][q] = A[q][r] = sn * arp + cs * arq;
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        const double vp = V[k][p], vq = V[k][q];
-        V[k][p] = cs * vp - sn * vq; V[k][q] = sn * vp + cs * vq;
-      }
-    }
-  }
-  // ascending order of eigenvalues (columns of V follow)
-  double ev[3] = {A[0][0], A[1][1], A[2][2]};
-  int idx[3] = {0, 1, 2};
-#define CSWAP(a_, b_) if (ev[idx[a_]] > ev[idx[b_]]) { const int t_ = idx[a_]; idx[a_] = idx[b_]; idx[b_] = t_; }
-  CSWAP(0, 1) CSWAP(1, 2) CSWAP(0, 1)
-#undef CSWAP
-  double U[3][3];
-#pragma unroll
-  for (int k = 0; k < 3; k++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) U[k][j] = V[k][idx[j]];
-  const double det = U[0][0] * (U[1][1] * U[2][2] - U[1][2] * U[2][1]) - U[0][1] * (U[1][0] * U[2][2] - U[1][2] * U[2][0]) +
-                     U[0][2] * (U[1][0] * U[2][1] - U[1][1] * U[2][0]);
-  const double sg = det < 0 ? -1.0 : 1.0;
-#pragma unroll
-  for (int k = 0; k < 3; k++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) U[k][j] *= sg;
-  // rotation matrix -> quaternion, largest-component branch
-  const double tr = U[0][0] + U[1][1] + U[2][2];
-  double qw, qx, qy, qz;
-  if (tr > 0) {
-    const double s4 = 2.0 * sqrt(1.0 + tr);
-    qw = 0.25 * s4; qx = (U[2][1] - U[1][2]) / s4; qy = (U[0][2] - U[2][0]) / s4; qz = (U[1][0] - U[0][1]) / s4;
-  } else if (U[0][0] > U[1][1] && U[0][0] > U[2][2]) {
-    const double s4 = 2.0 * sqrt(1.0 + U[0][0] - U[1][1] - U[2][2]);
-    qw = (U[2][1] - U[1][2]) / s4; qx = 0.25 * s4; qy = (U[0][1] + U[1][0]) / s4; qz = (U[0][2] + U[2][0]) / s4;
-  } else if (U[1][1] > U[2][2]) {
-    const double s4 = 2.0 * sqrt(1.0 + U[1][1] - U[0][0] - U[2][2]);
-    qw = (U[0][2] - U[2][0]) / s4; qx = (U[0][1] + U[1][0]) / s4; qy = 0.25 * s4; qz = (U[1][2] + U[2][1]) / s4;
-  } else {
-    const double s4 = 2.0 * sqrt(1.0 + U[2][2] - U[0][0] - U[1][1]);
-    qw = (U[1][0] - U[0][1]) / s4; qx = (U[0][2] + U[2][0]) / s4; qy = (U[1][2] + U[2][1]) / s4; qz = 0.25 * s4;
-  }
-  const double qn = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-  reinterpret_cast<float4*>(rots)[i] = make_float4((float)(qw * qn), (float)(qx * qn), (float)(qy * qn), (float)(qz * qn));
-#pragma unroll
-  for (int j = 0; j < 3; j++) scales[3 * (size_t)i + j] = (float)sqrt(fmax(ev[idx[j]], 0.0));
+#include "gm_cov_to_scale_rot_body.inc"
 }
 
 int launch_cov_to_scale_rot(int N, const float* cov, float* scales, float* rots, hipStream_t s) {
   if (N > 0) hipLaunchKernelGGL(cov_to_scale_rot_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, cov, scales, rots);
   GM_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// K frames of a SCENE from ONE pass over its cloud (gm_forward_scene_batch_async): a free-standing background plus mesh-bound objects,
+// the rows in the order SceneVisualTool.render_gaussian concatenates them (background, then each object).  One frame of that route is
+// gm_cov_to_scale_rot of every row's covariance, then preprocess_fwd_kernel on (means, shs, scales, rotations): the colour from the
+// rasterizer's own SH with the UNROTATED direction p - campos (edittool/__init__.py:196-223).  Here each row is, in each frame, one of:
+//   static    a background row, or a row of an object at rest in this frame: its position and (s, q) = gm_cov_to_scale_rot of its covariance,
+//             computed once per state by the caller (the Jacobi is deterministic: once equals every frame);
+//   deformed  a row of an object the frame's gather table moves: the expressions of deform_kernel, in the order deform_shade_kernel evaluates
+//             them, then the Jacobi of cov_to_scale_rot_kernel on the 3x3 result - skipped for a row behind the near plane, whose (s, q)
+//             reach no output.
+// Both kinds then run preprocess_fwd_kernel's computeCov3D, SH colour, projection and emission (gm_pre_body.h, scale modifier 1 as in
+// render_gaussian): each frame's geometry buffer comes out as the single-frame route writes it, bit for bit (tests/test_gpu_scene_batch.py).
+// As deform_shade_pre_batch_kernel: one 64-lane wave per workgroup, the block's SH rows in LDS by LDS-DMA, the static inputs in registers,
+// a loop over the frames.  A wave may straddle the background / object boundary or two objects: the kind is chosen per lane.
+struct SceneBatch {
+  int frames, n_obj;
+  uint32_t moving;                                 // objects some frame of the batch deforms (the OR of mask[])
+  int rows[GM_SCENE_OBJECTS_MAX + 1];              // object j: rows [rows[j], rows[j + 1]); tri / w / cov are indexed by row - rows[0]
+  uint32_t mask[GM_BATCH_MAX];                     // bit j of mask[f]: frame f deforms object j through f[f].tab
+  const float* opac;
+  FusedFrame f[GM_BATCH_MAX];
+};
+
+__global__ __launch_bounds__(64) void scene_shade_pre_batch_kernel(int N, int deg, const float* __restrict__ pos, const float* __restrict__ scales,
+                                                                   const float* __restrict__ rots, const float* __restrict__ shs,
+                                                                   const int* __restrict__ tri, const float* __restrict__ w,
+                                                                   const float* __restrict__ cov, const SceneBatch sb) {
+  constexpr int DS_THREADS = 64;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float4* l_sh = reinterpret_cast<float4*>(lds);   // [64][12] granules: linear image of the block's SH rows (12 KiB)
+  const size_t row0 = (size_t)blockIdx.x * DS_THREADS;
+  const int nrows = min(DS_THREADS, N - (int)row0);
+  const int t = threadIdx.x;
+  const size_t i = row0 + t;
+  const bool live = t < nrows;
+  int obj = -1;                                    // the row's object; -1: static in every frame (background, or behind the last object)
+  if (live && (int)i >= sb.rows[0] && (int)i < sb.rows[sb.n_obj]) {
+    obj = 0;
+    for (int j = 1; j < sb.n_obj; j++) obj = (int)i >= sb.rows[j] ? j : obj;      // (an empty object shares its start with the next)
+  }
+  const bool moving = obj >= 0 && ((sb.moving >> obj) & 1u);
+  float p0 = 0.f, p1 = 0.f, p2 = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, opac = 0.f;
+  float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f);
+  int t0 = 0, t1 = 0, t2 = 0; float w0 = 0.f, w1 = 0.f, w2 = 0.f;
+  if (live) {
+    p0 = pos[3 * i]; p1 = pos[3 * i + 1]; p2 = pos[3 * i + 2];
+    s0 = scales[3 * i]; s1 = scales[3 * i + 1]; s2 = scales[3 * i + 2];
+    q0 = reinterpret_cast<const float4*>(rots)[i];
+    opac = sb.opac[i];
+  }
+  const size_t r = moving ? i - (size_t)sb.rows[0] : 0;
+  if (moving) {
+    t0 = tri[3 * r]; t1 = tri[3 * r + 1]; t2 = tri[3 * r + 2];
+    w0 = w[3 * r]; w1 = w[3 * r + 1]; w2 = w[3 * r + 2];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if (nrows == DS_THREADS) {
+    const char* gsh = reinterpret_cast<const char*>(shs + row0 * 48) + t * 16;
+#pragma unroll
+    for (int q = 0; q < 12; q++) dma16(gsh + q * 1024, reinterpret_cast<char*>(l_sh) + q * 1024);
+  } else if (live) {
+#pragma unroll
+    for (int c = 0; c < 12; c++) l_sh[t * 12 + c] = reinterpret_cast<const float4*>(shs)[i * 12 + c];
+  }
+  float C[9];                                      // the rest covariance of a movable row
+#pragma unroll
+  for (int k = 0; k < 9; k++) C[k] = moving ? cov[r * 9 + k] : 0.f;
+  __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): the DMA has landed
+  __syncthreads();
+#pragma unroll 1
+  for (int f = 0; f < sb.frames; f++) {
+    const FusedFrame& F = sb.f[f];
+    V3 p = {p0, p1, p2};
+    float4 q = q0;
+    float sc[3] = {s0, s1, s2};
+    if (moving && ((sb.mask[f] >> obj) & 1u)) {
+      const float4* tab = F.tab;
+      float va[24], vb[24], vc[24];
+#pragma unroll
+      for (int u = 0; u < 6; u++) {
+        const float4 a = tab[6 * (size_t)t0 + u], b = tab[6 * (size_t)t1 + u], c = tab[6 * (size_t)t2 + u];
+        va[4 * u] = a.x; va[4 * u + 1] = a.y; va[4 * u + 2] = a.z; va[4 * u + 3] = a.w;
+        vb[4 * u] = b.x; vb[4 * u + 1] = b.y; vb[4 * u + 2] = b.z; vb[4 * u + 3] = b.w;
+        vc[4 * u] = c.x; vc[4 * u + 1] = c.y; vc[4 * u + 2] = c.z; vc[4 * u + 3] = c.w;
+      }
+      float d[3], Rb[9], Sb[9], Rt[9], RS[9], A[9], O[9];
+#pragma unroll
+      for (int k = 0; k < 3; k++) d[k] = (w0 * va[k] + w1 * vb[k]) + w2 * vc[k];
+#pragma unroll
+      for (int k = 0; k < 9; k++) {
+        Rb[k] = (w0 * va[4 + k] + w1 * vb[4 + k]) + w2 * vc[4 + k];
+        Sb[k] = (w0 * va[13 + k] + w1 * vb[13 + k]) + w2 * vc[13 + k];
+      }
+#pragma unroll
+      for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) Rt[3 * a + b] = Rb[3 * b + a];
+#pragma unroll
+      for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) RS[3 * a + b] = (Rt[3 * a] * Sb[b] + Rt[3 * a + 1] * Sb[3 + b]) + Rt[3 * a + 2] * Sb[6 + b];
+#pragma unroll
+      for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) A[3 * a + b] = (RS[3 * a] * C[b] + RS[3 * a + 1] * C[3 + b]) + RS[3 * a + 2] * C[6 + b];
+#pragma unroll
+      for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) O[3 * a + b] = (A[3 * a] * RS[3 * b] + A[3 * a + 1] * RS[3 * b + 1]) + A[3 * a + 2] * RS[3 * b + 2];
+      p = V3{p0 + d[0], p1 + d[1], p2 + d[2]};
+      if (!(xform4x3(p, F.cam.view).z <= 0.2f)) cov_to_scale_rot_row(O, &q, sc, 0);     // (not culled by pre_project's near-plane test)
+    }
+    uint32_t tiles = 0, dkey = 0xFFFFFFFFu;
+    uint4 dbin = make_uint4(0u, 0u, 0u, 0u);
+    if (live) {
+      float c3[6];
+      cov3d_from_scale_rot(q, sc, c3);
+      PreGeom pg;
+      const bool vis = pre_project(F.cam, p, c3, pg);
+      int radius_i = 0;
+      if (vis) {
+        float col[3];
+        sh_color(deg, p, F.campos, l_sh + t * 12, col);
+        dkey = __float_as_uint(pg.depth);
+        splat_store(F.splat, i, pg.pix, pg.piy, pg.conx, pg.cony, pg.conz, opac, col[0], col[1], col[2], pg.depth);
+        radius_i = (int)pg.radius;
+        pre_emit(F.cam, pg, opac, tiles, dbin);
+      }
+      if (F.radii_out) F.radii_out[i] = radius_i; else F.radii_int[i] = radius_i;
+      if (tiles >= GM_BIN_COUNT_SAT) F.tiles[i] = tiles;
+      F.bin[i] = dbin;
+      F.depth_key[i] = dkey;
+      if (i == 0) F.counters[GM_CNT_POLICY] = (uint32_t)F.cam.tile_cull;
+    }
+    slot_accumulate(F.slots, F.coarse, tiles, dkey);
+  }
+}
+
+int launch_scene_shade_pre_batch(int frames, const BatchFrameArgs* fr, const uint32_t* deformed, int n_obj, const int* object_rows, int P, int deg,
+                                 int W, int H, int tile_cull, const float* pos, const float* scales, const float* rots, const float* shs,
+                                 const float* opacities, const int* tri, const float* w, const float* cov, int debug, hipStream_t s) {
+  if (P <= 0) return 0;
+  if (frames < 1 || frames > GM_BATCH_MAX || n_obj < 0 || n_obj > GM_SCENE_OBJECTS_MAX) {
+    set_error("scene fused pass: 1..%d frames, 0..%d objects", GM_BATCH_MAX, GM_SCENE_OBJECTS_MAX); return 1;
+  }
+  if (!aligned16(shs) || !aligned16(rots)) { set_error("gm_forward_scene_batch: shs / rots must be 16-byte aligned"); return 1; }
+  StageScope sc(ST_DEFORM, s);
+  SceneBatch sb{};
+  sb.frames = frames; sb.n_obj = n_obj; sb.opac = opacities;
+  for (int j = 0; j <= n_obj; j++) sb.rows[j] = object_rows[j];
+  for (int k = 0; k < frames; k++) {
+    sb.mask[k] = deformed[k];
+    sb.moving |= deformed[k];
+    if (deformed[k] && !aligned16(fr[k].packed)) { set_error("gm_forward_scene_batch: packed tables must be 16-byte aligned"); return 1; }
+    sb.f[k] = fused_frame(fr[k], W, H, tile_cull);
+  }
+  hipLaunchKernelGGL(scene_shade_pre_batch_kernel, dim3((P + 63) / 64), dim3(64), sizeof(float) * 64 * 48, s, P, deg, pos, scales, rots, shs, tri, w,
+                     cov, sb);
+  GM_LAUNCH_CHECK(debug, s);
   return 0;
 }
 

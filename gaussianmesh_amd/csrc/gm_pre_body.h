@@ -1,11 +1,12 @@
 // gm_pre_body.h -- the per-Gaussian forward geometry of preprocessCUDA (RAST/forward.cu:155-256) as inline device
-// functions, shared by preprocess_fwd_kernel (gm_preprocess.hip) and the fused deform+shade+preprocess kernel of the edit
+// functions, shared by preprocess_fwd_kernel (gm_preprocess.hip) and the fused deform+shade+preprocess kernels of the edit
 // loop (gm_deform.hip).  ARITHMETIC CONTRACT: every function body here switches FMA contraction off and keeps the
 // reference's association order, whatever the including translation unit's default is, so both users (and the CPU
 // oracle) produce bit-identical radii, rectangles, conics, depth keys and instance counts.
 #pragma once
 #include "gm_common.h"
 #include "gm_cull.h"
+#include "gm_sh.h"
 
 namespace gm {
 
@@ -74,6 +75,33 @@ __device__ __forceinline__ void cov2d_from_T(const float* T0, const float* T1, c
   a = (A0[0] * T0[0] + A0[1] * T0[1]) + A0[2] * T0[2];
   b = (A1[0] * T0[0] + A1[1] * T0[1]) + A1[2] * T0[2];
   cc = (A1[0] * T1[0] + A1[1] * T1[1]) + A1[2] * T1[2];
+}
+
+// computeCov3D, forward.cu:118-152: the six distinct entries of (S R)^T (S R) for the quaternion (r, x, y, z) = (q.x, q.y, q.z, q.w) and
+// the scales s[3] (the scale modifier applied).  The statements are those preprocess_fwd_kernel includes in place (gm_cov3d_body.inc).
+__device__ __forceinline__ void cov3d_from_scale_rot(const float4 q, const float* scale, float* c3) {
+#pragma clang fp contract(off)
+#define GM_COV3D_SCALE(k) scale[k]
+#include "gm_cov3d_body.inc"
+#undef GM_COV3D_SCALE
+}
+
+// computeColorFromSH, forward.cu:20-71: col = max(SH_D(dir) + 0.5, 0) per channel with the UNROTATED direction dir = (p - campos) / |p - campos|,
+// the coefficients from a row of 12 float4 granules (an LDS row).  Returns the clamp bits (bit ch: channel ch was clamped).  The statements are
+// those preprocess_fwd_kernel includes in place (gm_sh_color_body.inc).
+__device__ __forceinline__ uint8_t sh_color(int D, const V3 p, const float* campos, const float4* row, float* col) {
+#pragma clang fp contract(off)
+  uint8_t clampbits = 0;
+#define GM_SH_DEG D
+#define GM_SH_CAMPOS campos
+#define GM_SH_LOAD(sh)                                                                                                                  \
+  _Pragma("unroll")                                                                                                                     \
+  for (int c = 0; c < 12; c++) { const float4 v = row[c]; sh[4 * c] = v.x; sh[4 * c + 1] = v.y; sh[4 * c + 2] = v.z; sh[4 * c + 3] = v.w; }
+#include "gm_sh_color_body.inc"
+#undef GM_SH_LOAD
+#undef GM_SH_CAMPOS
+#undef GM_SH_DEG
+  return clampbits;
 }
 
 

@@ -106,17 +106,9 @@ __global__ __launch_bounds__(TH) void preprocess_fwd_kernel(const PreArgs a) {
       for (int k = 0; k < 6; k++) c3[k] = a.cov3D_pre[6 * (size_t)idx + k];
     } else {                                        // computeCov3D, forward.cu:118-152
       const float4 q = DMA ? in_q : reinterpret_cast<const float4*>(a.rots)[idx];
-      float Rg[9], Mc[9];
-      quat_cols(q.x, q.y, q.z, q.w, Rg);
-      const float s[3] = {a.mod * (DMA ? in_s[0] : a.scales[3 * (size_t)idx]), a.mod * (DMA ? in_s[1] : a.scales[3 * (size_t)idx + 1]),
-                          a.mod * (DMA ? in_s[2] : a.scales[3 * (size_t)idx + 2])};
-#pragma unroll
-      for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) Mc[3 * c + k] = s[k] * Rg[3 * c + k];
-#define SIG(u, w) (Mc[3 * u + 0] * Mc[3 * w + 0] + Mc[3 * u + 1] * Mc[3 * w + 1] + Mc[3 * u + 2] * Mc[3 * w + 2])
-      c3[0] = SIG(0, 0); c3[1] = SIG(0, 1); c3[2] = SIG(0, 2); c3[3] = SIG(1, 1); c3[4] = SIG(1, 2); c3[5] = SIG(2, 2);
-#undef SIG
+#define GM_COV3D_SCALE(k) a.mod * (DMA ? in_s[k] : a.scales[3 * (size_t)idx + k])
+#include "gm_cov3d_body.inc"
+#undef GM_COV3D_SCALE
 #pragma unroll
       for (int k = 0; k < 6; k++) a.cov3D[6 * (size_t)idx + k] = c3[k];
     }
@@ -128,26 +120,22 @@ __global__ __launch_bounds__(TH) void preprocess_fwd_kernel(const PreArgs a) {
     if (a.colors_pre) {
       col[0] = a.colors_pre[3 * (size_t)idx]; col[1] = a.colors_pre[3 * (size_t)idx + 1]; col[2] = a.colors_pre[3 * (size_t)idx + 2];
     } else {                                        // computeColorFromSH, forward.cu:20-71
-      float dx = p.x - a.campos[0], dy = p.y - a.campos[1], dz = p.z - a.campos[2];
-      const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-      dx = dx / len; dy = dy / len; dz = dz / len;
-      float sh[48];
-      const int ncoef = (a.D + 1) * (a.D + 1);
-      if (STAGE_SH) {
-        const float4* row = reinterpret_cast<const float4*>(lds_pre) + threadIdx.x * LROW;
-#pragma unroll
-        for (int c = 0; c < 12; c++) { const float4 v = row[c]; sh[4 * c] = v.x; sh[4 * c + 1] = v.y; sh[4 * c + 2] = v.z; sh[4 * c + 3] = v.w; }
-      } else {
-        if (DMA) __builtin_assume((reinterpret_cast<uintptr_t>(a.shs) & 15) == 0);   // launch_preprocess sends only aligned rows here
-        load_sh(a.shs, idx, a.M, ncoef, sh);
+#define GM_SH_DEG a.D
+#define GM_SH_CAMPOS a.campos
+#define GM_SH_LOAD(sh)                                                                                                                  \
+      const int ncoef = (a.D + 1) * (a.D + 1);                                                                                          \
+      if (STAGE_SH) {                                                                                                                   \
+        const float4* row = reinterpret_cast<const float4*>(lds_pre) + threadIdx.x * LROW;                                              \
+        _Pragma("unroll")                                                                                                               \
+        for (int c = 0; c < 12; c++) { const float4 v = row[c]; sh[4 * c] = v.x; sh[4 * c + 1] = v.y; sh[4 * c + 2] = v.z; sh[4 * c + 3] = v.w; } \
+      } else {                                                                                                                          \
+        if (DMA) __builtin_assume((reinterpret_cast<uintptr_t>(a.shs) & 15) == 0);   /* launch_preprocess sends only aligned rows here */ \
+        load_sh(a.shs, idx, a.M, ncoef, sh);                                                                                            \
       }
-#pragma unroll
-      for (int ch = 0; ch < 3; ch++) {
-        float r = sh_channel(a.D, [&](int i) { return sh[3 * i + ch]; }, dx, dy, dz);
-        r += 0.5f;
-        if (r < 0) clampbits |= (uint8_t)(1u << ch);
-        col[ch] = fmaxf(r, 0.0f);
-      }
+#include "gm_sh_color_body.inc"
+#undef GM_SH_LOAD
+#undef GM_SH_CAMPOS
+#undef GM_SH_DEG
     }
     a.clamped[idx] = clampbits;
     const float opac = DMA ? in_op : a.opac[idx];

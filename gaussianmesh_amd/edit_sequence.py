@@ -2,12 +2,16 @@
 
     python -m gaussianmesh_amd.edit_sequence --object_gaussian fg.ply --object_origin_mesh mesh.obj --mesh_sequence DIR \
         --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N] [--frames_per_launch 4] [--save_maps]
+        [--background_gaussian BG.ply [--is_exist_bg]]
 
 --mesh_sequence: a folder of OBJ files in numeric order (1.obj, 2.obj, ...: the reference's `mesh_sequnce`), one frame each.
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
 files are written on the host while the device renders the next batch (the generator issues batch b + 1 before it yields batch b).
+--background_gaussian BG.ply: the object in front of a free-standing background cloud (edit.py's --is_exist_bg mode, SceneVisualTool;
+--is_exist_bg is accepted and needs the background): frames through SceneVisualTool.render_sequence.  A scene renders no maps, so
+--save_maps with a background is refused.
 """
 import os
 import re
@@ -32,17 +36,23 @@ def main(argv=None):
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
     parser.add_argument("--save_maps", action="store_true", default=False)
+    parser.add_argument("--background_gaussian", type=str, default=None)
+    parser.add_argument("--is_exist_bg", action="store_true", default=False)
     args = parser.parse_args(argv)
+    if args.is_exist_bg and args.background_gaussian is None:
+        parser.error("--is_exist_bg needs --background_gaussian (the background cloud's PLY)")
+    if args.background_gaussian is not None and args.save_maps:
+        parser.error("--save_maps: a scene with a background renders no depth / alpha maps; drop --save_maps or the background")
 
     import numpy as np
     import torch
-    from .edittool import ObjectVisualTool
+    from .edittool import ObjectVisualTool, SceneVisualTool
     from .io import save_image
 
     meshes = mesh_sequence(args.mesh_sequence)
     if not meshes:
         raise SystemExit("edit_sequence: no .obj files in %s" % args.mesh_sequence)
-    tool = ObjectVisualTool()
+    tool = ObjectVisualTool() if args.background_gaussian is None else SceneVisualTool(args.background_gaussian)
     cams = tool.get_camera(args.camera_path)
     tool.add_gaussian(args.object_gaussian, args.object_origin_mesh, args.object_name)
     frames = [(cams[args.camera_id] if args.camera_id is not None else cams[i % len(cams)], {args.object_name: m})

@@ -249,73 +249,91 @@ class ObjectVisualTool:
         return self._render_sequence(list(frames), int(frames_per_launch), bool(aux), bg_color)
 
     def _render_sequence(self, frames, K, aux, bg_color):
-        import math
         from . import rasterizer as Rz
-        dev = self.device
         cloud = self._sequence_cloud()
-        P = cloud["pos"].shape[0]
-        bg = torch.ones(3, device=dev) if bg_color is None else torch.as_tensor(bg_color, dtype=torch.float32, device=dev)
-        sizes = [(int(c.image_width), int(c.image_height)) for c, _ in frames]
-        plan = plan_sequence(sizes, K, batchable=P > 0)
-        streams = {}                                   # (W, H) -> workspaces (two batches in flight) + one work hint
+        bg = self._bg(bg_color)
 
-        def stream_of(size):
-            st = streams.get(size)
-            if st is None:
-                st = streams[size] = dict(ws=[Rz.RasterWorkspace() for _ in range(2 * K)], hint=Rz.new_work_hint(size[0], size[1], dev), next=0)
-            return st
-
-        def cam(c):
-            return dict(view=c.world_view_transform, proj=c.full_proj_transform, campos=c.camera_center,
-                        tanx=math.tan(c.FoVx * 0.5), tany=math.tan(c.FoVy * 0.5))
-
-        def share_capacity(st):
-            cap = max(w.capacity for w in st["ws"])
-            for w in st["ws"]:
-                w.capacity = cap
-
-        def issue(kind, idx):
-            st = stream_of(sizes[idx[0]])
-            W, H = sizes[idx[0]]
+        def issue_batch(idx, cams, ws, hint):
+            W, H = _size(frames[idx[0]][0])
             tables = self.gather_tables([frames[i][1] for i in idx], cloud)
-            cams = [cam(frames[i][0]) for i in idx]
+            return Rz.forward_deformed_batch(bg, cloud["tri"], cloud["weights"], list(tables), cloud["cov"], cloud["pos"], cloud["shs"],
+                                             cloud["opac"], cams, H, W, 3, ws, image_only=True, work_hint=hint, aux=aux)
+
+        def issue_frame(i, c, workspace):
+            W, H = _size(frames[i][0])
+            table = self.gather_tables([frames[i][1]], cloud)[0]
+            return Rz.forward_deformed_begin(bg, cloud["tri"], cloud["weights"], table, cloud["cov"], cloud["pos"], cloud["shs"], cloud["opac"],
+                                             c["view"], c["proj"], c["tanx"], c["tany"], H, W, 3, c["campos"], workspace=workspace, aux=aux)
+        yield from _run_plan(frames, K, cloud["pos"].shape[0] > 0, issue_batch, issue_frame, aux, self.device)
+
+    def _bg(self, bg_color):
+        return torch.ones(3, device=self.device) if bg_color is None else torch.as_tensor(bg_color, dtype=torch.float32, device=self.device)
+
+
+def _size(c):
+    return int(c.image_width), int(c.image_height)
+
+
+def _run_plan(frames, K, batchable, issue_batch, issue_frame, aux, dev):
+    """The route both tools' render_sequence take (deform.plan_sequence): frames of one resolution in batches of K through
+    issue_batch(frame indices, cameras, workspaces, work hint) -> K PendingForward, the first frame of a resolution (which teaches the
+    workspaces their capacity) and frames the batch refuses through issue_frame(frame index, camera, workspace or None) -> PendingForward.
+    Batch b + 1 is issued before batch b is checked and yielded; a frame that outgrew the capacity is rendered again, exactly."""
+    import math
+    from . import rasterizer as Rz
+    sizes = [_size(c) for c, _ in frames]
+    plan = plan_sequence(sizes, K, batchable=batchable)
+    streams = {}                                   # (W, H) -> workspaces (two batches in flight) + one work hint
+
+    def stream_of(size):
+        st = streams.get(size)
+        if st is None:
+            st = streams[size] = dict(ws=[Rz.RasterWorkspace() for _ in range(2 * K)], hint=Rz.new_work_hint(size[0], size[1], dev), next=0)
+        return st
+
+    def cam(c):
+        return dict(view=c.world_view_transform, proj=c.full_proj_transform, campos=c.camera_center,
+                    tanx=math.tan(c.FoVx * 0.5), tany=math.tan(c.FoVy * 0.5))
+
+    def share_capacity(st):
+        cap = max(w.capacity for w in st["ws"])
+        for w in st["ws"]:
+            w.capacity = cap
+
+    def issue(kind, idx):
+        st = stream_of(sizes[idx[0]])
+        cams = [cam(frames[i][0]) for i in idx]
+        if kind == "batch":
+            ws = st["ws"][st["next"]:st["next"] + len(idx)]
+            st["next"] = K - st["next"]                     # the other half of the workspaces for the next batch
+            return issue_batch(idx, cams, ws, st["hint"]), st
+        return [issue_frame(idx[0], cams[0], st["ws"][st["next"]] if kind == "learn" else None)], st
+
+    def complete(kind, hs, st):
+        for h in hs:
             if kind == "batch":
-                ws = st["ws"][st["next"]:st["next"] + len(idx)]
-                st["next"] = K - st["next"]                     # the other half of the workspaces for the next batch
-                hs = Rz.forward_deformed_batch(bg, cloud["tri"], cloud["weights"], list(tables), cloud["cov"], cloud["pos"], cloud["shs"],
-                                               cloud["opac"], cams, H, W, 3, ws, image_only=True, work_hint=st["hint"], aux=aux)
-                return hs, st
-            c = cams[0]
-            h = Rz.forward_deformed_begin(bg, cloud["tri"], cloud["weights"], tables[0], cloud["cov"], cloud["pos"], cloud["shs"], cloud["opac"],
-                                          c["view"], c["proj"], c["tanx"], c["tany"], H, W, 3, c["campos"],
-                                          workspace=st["ws"][st["next"]] if kind == "learn" else None, aux=aux)
-            return [h], st
+                ok, _ = h.check()
+                out = h.result if ok else h.finish(image_only=True, work_hint=st["hint"])   # outgrew the capacity: again, exactly
+            else:
+                out = h.finish(image_only=True, work_hint=st["hint"])
+            if kind != "single":
+                share_capacity(st)
+            yield (out[1], out[6], out[7]) if aux else out[1]
 
-        def complete(kind, hs, st):
-            for h in hs:
-                if kind == "batch":
-                    ok, _ = h.check()
-                    out = h.result if ok else h.finish(image_only=True, work_hint=st["hint"])   # outgrew the capacity: again, exactly
-                else:
-                    out = h.finish(image_only=True, work_hint=st["hint"])
-                if kind != "single":
-                    share_capacity(st)
-                yield (out[1], out[6], out[7]) if aux else out[1]
-
-        pending = None
-        for kind, idx in plan:
-            issued = (kind,) + issue(kind, idx)
-            if kind == "learn":                             # complete it now: the next batch needs the capacity it learns
-                if pending is not None:
-                    yield from complete(*pending)
-                    pending = None
-                yield from complete(*issued)
-                continue
+    pending = None
+    for kind, idx in plan:
+        issued = (kind,) + issue(kind, idx)
+        if kind == "learn":                             # complete it now: the next batch needs the capacity it learns
             if pending is not None:
                 yield from complete(*pending)
-            pending = issued
+                pending = None
+            yield from complete(*issued)
+            continue
         if pending is not None:
             yield from complete(*pending)
+        pending = issued
+    if pending is not None:
+        yield from complete(*pending)
 
 
 class SceneVisualTool(ObjectVisualTool):
@@ -337,31 +355,87 @@ class SceneVisualTool(ObjectVisualTool):
         self.bg_shs = torch.cat([t(m["features_dc"]), t(m["features_rest"])], dim=1).contiguous()
         self.bg_opacity = torch.sigmoid(t(m["opacity"]))
         self.bg_deform_rot = torch.eye(3, device=self.device).repeat(self.bg_scale.shape[0], 1, 1)
+        self._scene_seq = None                       # the static scene cloud of render_sequence: rebuilt from the new background
 
     def render_sequence(self, frames, *, frames_per_launch=4, aux=False, bg_color=None):
-        """ObjectVisualTool.render_sequence for a scene: render_gaussian per frame, in order (the objects are shaded through the
-        rasterizer's own SH with the unrotated direction, which the batch's fused pass does not compute; no batched route).  Each frame's
-        named objects are deformed for that frame and restored after it.  No depth / alpha maps (aux=True raises GmeshError)."""
+        """ObjectVisualTool.render_sequence for a scene: each frame equals, bit for bit, render_gaussian with the objects the frame names
+        deformed for that frame (the others in their current state).  Route: the background and every object as ONE static cloud in
+        render_gaussian's row order, with the (scale, rotation) of each row's resting covariance computed once; frames of one resolution in
+        batches of frames_per_launch through rasterizer.forward_scene_batch, which deforms (and decomposes) only the rows of the objects a
+        frame moves - the objects it names and those in a deformed current state.  The first frame of a resolution goes through the
+        single-frame path (render_gaussian's arithmetic) and teaches the workspaces their capacity.  No object attribute changes.  No depth
+        / alpha maps (aux=True raises GmeshError)."""
         if aux:
             raise _lib.GmeshError("SceneVisualTool.render_sequence renders no depth / alpha maps")
         if not 1 <= int(frames_per_launch) <= _lib.GM_BATCH_MAX:
             raise ValueError("frames_per_launch: 1..%d, got %r" % (_lib.GM_BATCH_MAX, frames_per_launch))
-        return self._scene_sequence(frames, bg_color)
+        return self._scene_sequence(list(frames), int(frames_per_launch), bg_color)
 
-    def _scene_sequence(self, frames, bg_color):
-        keys = ("gaussian_deform_pos", "gaussian_deform_cov", "gaussian_deform_rot", "gaussian_deform_cov6", "deform_state")
-        for camera, deformation in frames:
-            defs = self._deformations(deformation)
-            saved = {i: tuple(getattr(self.gaussians_list[i], k) for k in keys) for i in defs}
-            try:
-                for i, v in defs.items():
-                    self.gaussians_list[i].deform_vertices(v)
-                image = self.render_gaussian(camera, bg_color=bg_color)
-            finally:
-                for i, vals in saved.items():
-                    for k, v in zip(keys, vals):
-                        setattr(self.gaussians_list[i], k, v)
-            yield image
+    def _scene_cloud(self):
+        """The static scene cloud: background rows then each object's rows (render_gaussian's order), every row's position (the objects'
+        rest positions), SH row, opacity and the (scale, rotation) of its resting covariance; the objects' face ids (offset into the
+        combined gather table), weights and rest covariances.  Rebuilt when gaussians_list changes or load_bg_gaussian runs."""
+        objs = tuple(self.gaussians_list)
+        c = getattr(self, "_scene_seq", None)
+        if c is not None and len(c["objs"]) == len(objs) and all(a is b for a, b in zip(c["objs"], objs)):
+            return c
+        if len(objs) > _lib.GM_SCENE_OBJECTS_MAX:
+            raise _lib.GmeshError("SceneVisualTool.render_sequence: at most %d objects" % _lib.GM_SCENE_OBJECTS_MAX)
+        cat = lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs, dim=0)
+        voff = np.cumsum([0] + [o.vertex.shape[0] for o in objs])
+        rows = np.cumsum([self.bg_mean3D.shape[0]] + [o.gaussian_pos.shape[0] for o in objs])
+        scales, rots = cov_to_scale_rot(cat([self.bg_cov3D] + [o.gaussian_cov for o in objs]))
+        c = dict(objs=objs, voff=[int(v) for v in voff], rows=[int(r) for r in rows], tables={}, scales=scales, rots=rots,
+                 pos=cat([self.bg_mean3D] + [o.gaussian_pos for o in objs]).contiguous(),
+                 shs=cat([self.bg_shs] + [o.gaussian_feature for o in objs]).contiguous(),
+                 opac=cat([self.bg_opacity] + [o.gaussian_o for o in objs]).reshape(-1).contiguous(),
+                 tri=None, weights=None, cov=None)
+        if objs:
+            c["tri"] = cat([o.gaussian_triangles + int(voff[i]) for i, o in enumerate(objs)]).to(torch.int32).contiguous()
+            c["weights"] = cat([o.coord for o in objs]).contiguous()
+            c["cov"] = cat([o.gaussian_cov.reshape(-1, 9) for o in objs]).contiguous()
+        self._scene_seq = c
+        return c
+
+    def _frame_rows(self, defs):
+        """means3D, scales, rotations of one frame as render_gaussian computes them, the objects in defs deformed by mesh_rs + deform
+        (SingleObjectDeform.deform_vertices) without touching the objects: the single-frame path of render_sequence."""
+        from .deform import deform_tensors
+        pos, cov = [self.bg_mean3D], [self.bg_cov3D]
+        for i, o in enumerate(self.gaussians_list):
+            if i in defs:
+                R, S = mesh_rs(o.vertex, defs[i], o.faces, adjacency=o._adjacency)
+                p, c, _, _ = deform_tensors(o.gaussian_triangles, o.coord, defs[i] - o.vertex, R.reshape(-1, 3, 3), S.reshape(-1, 3, 3),
+                                            o.gaussian_cov, o.gaussian_pos)
+            else:
+                p, c = o.gaussian_deform_pos, o.gaussian_deform_cov
+            pos.append(p); cov.append(c)
+        s, q = cov_to_scale_rot(torch.cat(cov, dim=0))
+        return torch.cat(pos, dim=0), s, q
+
+    def _scene_sequence(self, frames, K, bg_color):
+        from . import rasterizer as Rz
+        cloud = self._scene_cloud()
+        bg = self._bg(bg_color)
+        objs = cloud["objs"]
+
+        def issue_batch(idx, cams, ws, hint):
+            W, H = _size(frames[idx[0]][0])
+            defs = [self._deformations(frames[i][1]) for i in idx]
+            masks = [sum(1 << j for j, o in enumerate(objs) if j in d or o.deform_state is not None) for d in defs]
+            tables = [None] * len(idx)
+            if any(masks):
+                tables = list(self.gather_tables([frames[i][1] for i in idx], cloud))
+            return Rz.forward_scene_batch(bg, cloud["rows"], masks, cloud["pos"], cloud["scales"], cloud["rots"], cloud["shs"], cloud["opac"],
+                                          cloud["tri"], cloud["weights"], cloud["cov"], [t if m else None for t, m in zip(tables, masks)], cams,
+                                          H, W, 3, ws, image_only=True, work_hint=hint)
+
+        def issue_frame(i, c, workspace):
+            W, H = _size(frames[i][0])
+            means3D, s, q = self._frame_rows(self._deformations(frames[i][1]))
+            return Rz.rasterize_forward_begin(bg, means3D, None, cloud["opac"], s, q, 1, None, c["view"], c["proj"], c["tanx"], c["tany"], H, W,
+                                              cloud["shs"], 3, c["campos"], False, False, workspace=workspace, force_M=16)
+        yield from _run_plan(frames, K, cloud["pos"].shape[0] > 0, issue_batch, issue_frame, False, self.device)
 
     def render_gaussian(self, viewpoint_camera, bg_color=None):
         import math

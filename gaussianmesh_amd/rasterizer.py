@@ -610,6 +610,67 @@ def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity
     return _begin(device, workspaces, issue)
 
 
+def forward_scene_batch(bg, object_rows, deformed, pos, scales, rotations, shs, opacity, tri, weights, cov, packed_list, cameras, image_height,
+                        image_width, degree, workspaces, image_only=True, work_hint=None, emission_policy=None, debug=False):
+    """K frames of a SCENE in ONE launch chain (gm_forward_scene_batch_async): a background cloud plus mesh-bound objects, the rows in
+    SceneVisualTool.render_gaussian's order (background, then each object).  object_rows: n_objects + 1 ascending row indices (object j
+    = rows [object_rows[j], object_rows[j + 1]), rows before object_rows[0] are background); deformed: K masks, bit j = frame k deforms
+    object j through packed_list[k] (its combined gather table; None in a frame whose mask is 0).  pos [P,3], scales [P,3], rotations [P,4]:
+    every row's position and static (scale, rotation) - deform.cov_to_scale_rot of its covariance; tri / weights / cov ([*,3] / [*,3] /
+    [*,3,3]): the object rows' bindings and rest covariances (None when no mask is set).  cameras and workspaces as for
+    forward_deformed_batch; returns K PendingForward handles in the same state.  Each frame comes out bit for bit as cov_to_scale_rot +
+    NewGaussianRasterizer on its rows (deformed objects through SingleObjectDeform.deform); a frame refused for capacity is rendered again,
+    exactly, by finish()."""
+    lib = _lib.lib()
+    device = pos.device
+    K = len(cameras)
+    if not (1 <= K <= _lib.GM_BATCH_MAX) or len(deformed) != K or len(packed_list) != K or len(workspaces) != K:
+        raise ValueError("forward_scene_batch: 1..%d frames, one mask, gather table, camera and workspace each" % _lib.GM_BATCH_MAX)
+    if len({id(w_) for w_ in workspaces}) != K:
+        raise ValueError("forward_scene_batch: the frames of a batch need distinct workspaces")
+    policy = _pol(emission_policy, image_width, image_height)
+    P, M = pos.shape[0], shs.shape[1]
+    if tri is not None and (tri.dtype is not torch.int32 or not tri.is_contiguous()):
+        tri = tri.detach().contiguous().to(torch.int32)
+    weights, cov, pos, scales, rotations, shs, opacity, bg = (_prep(t, device) for t in (weights, cov, pos, scales, rotations, shs, opacity, bg))
+    H, W = int(image_height), int(image_width)
+    cap = max(ws.capacity for ws in workspaces)
+    if cap <= 0:
+        raise _lib.GmeshError("forward_scene_batch: the workspaces have no capacity yet - complete one frame of the stream through the "
+                              "single-frame path first (the batch is sync-free: it cannot size the binning buffers)")
+    rows = (C.c_int * len(object_rows))(*[int(r) for r in object_rows])
+    masks = (C.c_uint * K)(*[int(m) for m in deformed])
+    get = lambda c, k: c[k] if isinstance(c, dict) else getattr(c, k)
+
+    def issue(stream):
+        handles, frames = [], (_lib.BatchFrame * K)()
+        nbin = lib.gm_binning_bytes(cap)
+        for k, (ws, c) in enumerate(zip(workspaces, cameras)):
+            ws.capacity = cap
+            color, radii, geom, img, _, _, _ = _scratch(ws, P, W, H, device)
+            binning = ws.get("binning", nbin, device)
+            view, proj, campos = (_prep(t, device) for t in (get(c, "view"), get(c, "proj"), get(c, "campos")))
+            packed = None if packed_list[k] is None else _prep(packed_list[k], device)
+            f = frames[k]
+            f.packed, f.viewmatrix, f.projmatrix, f.cam_pos = _ptr(packed), view.data_ptr(), proj.data_ptr(), campos.data_ptr()
+            f.tan_fovx, f.tan_fovy = float(get(c, "tanx")), float(get(c, "tany"))
+            f.geom_buffer, f.binning_buffer, f.image_buffer = geom.data_ptr(), binning.data_ptr(), img.data_ptr()
+            f.out_color, f.radii, f.status_host = color.data_ptr(), radii.data_ptr(), ws.status()[0].data_ptr()
+            args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)),
+                        keep=(tri, weights, cov, pos, scales, rotations, shs, opacity, (view, proj, campos, packed)))
+            handles.append(PendingForward(policy, ws, stream, args, geom, img, color, radii, None, None, binning=binning))
+        _lib.check(lib.gm_forward_scene_batch_async(policy, K, frames, P, int(degree), M, W, H, len(object_rows) - 1, rows, masks, _ptr(pos),
+                                                    _ptr(scales), _ptr(rotations), _ptr(shs), _ptr(opacity), _ptr(tri), _ptr(weights), _ptr(cov),
+                                                    _ptr(bg), cap, 1 if image_only else 0, None if work_hint is None else work_hint.data_ptr(),
+                                                    int(bool(debug)), stream.cuda_stream))
+        for h in handles:
+            h.status_event = h.workspace.status()[1]
+            h.status_event.record(stream)
+            h.result = h._outputs(-1, h.binning)
+        return handles
+    return _begin(device, workspaces, issue)
+
+
 def rasterize_backward(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
                        tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geom, num_rendered, binning, img, debug,
                        emission_policy=None, skip_intermediates=False, want_conic=False, sh_step=None, dL_ddepth=None, dL_dalpha=None):

@@ -378,6 +378,29 @@ int gm_forward_deformed_batch_aux_async(int emission_policy, int K, const gm_bat
                                         const int* tri, const float* w, const float* cov, const float* pos, const float* shs, const float* opacities,
                                         const float* background, int64_t binning_capacity, int flags, unsigned int* work_hint, int debug, void* stream,
                                         float* const* out_depth, float* const* out_alpha);
+/* K frames of a SCENE per launch chain: a free-standing background cloud plus mesh-bound objects (SceneVisualTool,
+ * edittool/__init__.py:133-231).  The P rows are in the order SceneVisualTool.render_gaussian concatenates them: the background
+ * (rows before object_rows[0]), then object j = rows [object_rows[j], object_rows[j+1]) for j < n_objects (host array of n_objects + 1
+ * ascending entries in [0, P]).  Equivalent, frame by frame and bit for bit (radii, lists, image, status words), to
+ *   gm_cov_to_scale_rot(the rows' covariances) + gm_forward_0_async(policy, ..., means = the rows' positions, shs, opacities, scales, 1.0,
+ *   rotations, ...) + gm_forward_1_geom(..., -1, binning_capacity, ...) as gm_forward_deformed_batch_async states it,
+ * where a row is, in frame k, one of
+ *   static    a background row, or a row of object j with bit j of deformed[k] clear: position pos, (scale, rotation) = (scales, rots),
+ *             which the caller computes once per state as gm_cov_to_scale_rot of the row's covariance;
+ *   deformed  a row of object j with bit j of deformed[k] set: gm_deform of its rest position pos and rest covariance cov[row - object_rows[0]]
+ *             by frame k's gather table (frames[k].packed; tri / w as for gm_forward_deformed_batch_async, face ids into that table),
+ *             then gm_cov_to_scale_rot of the result.
+ * Colours from the SH rows with the unrotated view direction (the rasterizer's own).  deformed: host array of K masks; frames[k].packed
+ * may be NULL in a frame whose mask is 0; tri / w / cov ([*,3] int32, [*,3], [*,9]: the object rows only) may be NULL when every mask is 0.
+ * pos [P,3], scales [P,3], rots [P,4] (16-byte aligned), shs [P,16,3] (16-byte aligned), opacities [P].  flags: GM_BATCH_IMAGE_ONLY or 0.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: everything gm_forward_deformed_batch_async refuses (a NULL packed aside),
+ * n_objects outside 0..GM_SCENE_OBJECTS_MAX, object_rows that do not ascend or leave [0, P], a mask bit at or above n_objects, a set bit
+ * with packed == NULL, and frames whose buffers overlap as ranges (geometry, binning, image, out_color, non-null radii and status_host). */
+#define GM_SCENE_OBJECTS_MAX 32   /* objects of a scene batch (gm_forward_scene_batch_async): the width of its per-frame masks */
+int gm_forward_scene_batch_async(int emission_policy, int K, const gm_batch_frame* frames, int P, int deg, int M, int width, int height,
+                                 int n_objects, const int* object_rows, const unsigned int* deformed, const float* pos, const float* scales,
+                                 const float* rots, const float* shs, const float* opacities, const int* tri, const float* w, const float* cov,
+                                 const float* background, int64_t binning_capacity, int flags, unsigned int* work_hint, int debug, void* stream);
 /* gm_mesh_rs_packed for the K deformed meshes of such a batch in one launch: V1[k] -> packed[k] (host arrays of K device pointers). */
 int gm_mesh_rs_packed_batch(int K, int Vm, int nfaces, const float* V0, const float* const* V1, const int* faces, const int* adj_offsets,
                             const int* adj_faces, float* const* packed, void* stream);
