@@ -372,6 +372,64 @@ void orc_render_fwd(int W, int H, const uint32_t* ranges, const uint32_t* point_
 }
 
 /* ---------------------------------------------------------------------------------------------
+ * Census of the `power > 0` skip of RAST/forward.cu:336 (the blend kernels of the product clamp the exponent to 0 instead): the
+ * (pixel, entry) pairs where orc_render_fwd's walk, with its own float arithmetic, skips an entry because power > 0 although the
+ * entry would count with power clamped to 0 (co[3] >= 1/255, i.e. min(0.99, co[3] * exp(0)) >= 1/255), before the pixel's stop.
+ * Returns the number of such pairs; with pixel / pos given, the first `cap` of them in (tile, pixel of the tile, list position)
+ * order: pixel = y W + x, pos = the entry's index into point_list.
+ */
+static int64_t census_tile(int W, int H, int gx, int tile, const uint32_t* ranges, const uint32_t* point_list, const float* xy,
+                           const float* conic_op, int64_t cap, int64_t at, uint32_t* pixel, uint32_t* pos) {
+  const int tx = tile % gx, ty = tile / gx;
+  const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
+  int64_t n = 0;
+  for (int ly = 0; ly < TILE; ly++)
+    for (int lx = 0; lx < TILE; lx++) {
+      const int px = tx * TILE + lx, py = ty * TILE + ly;
+      if (px >= W || py >= H) continue;
+      const float pfx = (float)px, pfy = (float)py;
+      float T = 1.0f;
+      for (uint32_t e = r0; e < r1; e++) {
+        const uint32_t g = point_list[e];
+        const float dx = xy[2 * (size_t)g] - pfx, dy = xy[2 * (size_t)g + 1] - pfy;
+        const float* co = conic_op + 4 * (size_t)g;
+        const float power = -0.5f * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
+        if (power > 0.0f) {
+          if (co[3] >= 1.0f / 255.0f) {
+            if (pixel && at + n < cap) { pixel[at + n] = (uint32_t)((size_t)W * py + px); pos[at + n] = e; }
+            n++;
+          }
+          continue;
+        }
+        const float alpha = fminf(0.99f, co[3] * expf(power));
+        if (alpha < 1.0f / 255.0f) continue;
+        const float test_T = T * (1 - alpha);
+        if (test_T < 0.0001f) break;
+        T = test_T;
+      }
+    }
+  return n;
+}
+
+int64_t orc_power_census(int W, int H, const uint32_t* ranges, const uint32_t* point_list, const float* xy, const float* conic_op,
+                         int64_t cap, uint32_t* pixel, uint32_t* pos) {
+  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, nt = gx * gy;
+  int64_t* cnt = (int64_t*)calloc((size_t)nt + 1, sizeof(int64_t));
+  if (!cnt) return -1;
+#pragma omp parallel for schedule(dynamic, 4)
+  for (int tile = 0; tile < nt; tile++) cnt[tile + 1] = census_tile(W, H, gx, tile, ranges, point_list, xy, conic_op, 0, 0, NULL, NULL);
+  for (int tile = 0; tile < nt; tile++) cnt[tile + 1] += cnt[tile];
+  const int64_t total = cnt[nt];
+  if (pixel && pos && total > 0) {
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int tile = 0; tile < nt; tile++)
+      if (cnt[tile + 1] > cnt[tile] && cnt[tile] < cap) census_tile(W, H, gx, tile, ranges, point_list, xy, conic_op, cap, cnt[tile], pixel, pos);
+  }
+  free(cnt);
+  return total;
+}
+
+/* ---------------------------------------------------------------------------------------------
  * For every (Gaussian, tile) instance of a binned list: does ANY pixel of the tile accept the entry, i.e. pass both
  * skips of RAST/forward.cu:336-345 (power <= 0 and alpha >= 1/255) with the float arithmetic of orc_render_fwd?
  * Checker for the product's emission-time tile culling: every instance with needed == 1 must be emitted.

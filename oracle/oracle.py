@@ -38,6 +38,7 @@ def lib():
         _LIB = C.CDLL(so)
         _LIB.orc_bin.restype = C.c_int64
         _LIB.orc_forward.restype = C.c_int64
+        _LIB.orc_power_census.restype = C.c_int64
         _LIB.orc_higher_msb.restype = C.c_uint32
         _LIB.orc_num_threads.restype = C.c_int
     return _LIB
@@ -134,6 +135,20 @@ def render_fwd(W, H, bins, geo, bg):
     lib().orc_render_fwd(W, H, _ptr(bins["ranges"]), _ptr(pl), _ptr(geo["xy"]), _ptr(geo["rgb"]),
                          _ptr(geo["conic_op"]), _ptr(_f(bg).reshape(-1)), _ptr(out), _ptr(fT), _ptr(nc))
     return out, fT, nc
+
+
+def power_census(W, H, bins, geo):
+    """(pixel [n] = y W + x, pos [n] = index into the point list) of every pair where render_fwd's walk skips an entry for `power > 0`
+    that would count with power clamped to 0 (opacity >= 1/255), before the pixel's stop (orc_power_census), in tile order."""
+    pl = np.ascontiguousarray(bins["point_list"] if bins["R"] > 0 else np.zeros(1), np.uint32)
+    ranges, xy, co = np.ascontiguousarray(bins["ranges"], np.uint32), _f(geo["xy"]), _f(geo["conic_op"])
+    args = (W, H, _ptr(ranges), _ptr(pl), _ptr(xy), _ptr(co))
+    n = int(lib().orc_power_census(*args, C.c_int64(0), None, None))
+    assert n >= 0, "orc_power_census: out of memory"
+    pixel = np.zeros(max(n, 1), np.uint32); pos = np.zeros(max(n, 1), np.uint32)
+    if n:
+        assert lib().orc_power_census(*args, C.c_int64(n), _ptr(pixel), _ptr(pos)) == n
+    return pixel[:n], pos[:n]
 
 
 def render_bwd(W, H, bins, geo, bg, final_T, n_contrib, dL_dpix):

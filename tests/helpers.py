@@ -225,3 +225,32 @@ def _check_geometry(orc, st, fw, scene, use_precomp_color):
     assert np.array_equal(st["point_list"], fw["bins"]["point_list"])
     assert np.array_equal(st["tile_keys"], (fw["bins"]["keys"] >> np.uint64(32)).astype(np.uint32))
     assert np.array_equal(st["ranges"], fw["bins"]["ranges"])
+
+
+def assert_power_census(orc, fw, images, W, H, what=""):
+    """The reference skips an entry where power > 0 (forward.cu:336); both blend kernels clamp the exponent to 0 instead (gm_render.hip),
+    so on such a pair the product blends alpha = min(0.99, opacity) where the reference blends nothing.  Counts, with the oracle's own
+    float arithmetic (oracle.power_census), the pairs where that can matter - opacity >= 1/255, before the pixel's stop - and holds
+    every pixel that has one to the strict forward gate: within plain_tol of the oracle, or explained by an entry at a decision threshold
+    (a pair whose |power| lies within its rounding distance is such an entry; one beyond it would leave the pixel unexplained).
+    images: [(image, plain_tol, label)].  Returns the number of pairs."""
+    pixel, pos = orc.power_census(W, H, fw["bins"], fw["geo"])
+    pix = np.unique(pixel)
+    g = fw["bins"]["point_list"][pos]
+    xy, co = fw["geo"]["xy"].astype(np.float64)[g], fw["geo"]["conic_op"].astype(np.float64)[g]
+    dx, dy = xy[:, 0] - (pixel % W), xy[:, 1] - (pixel // W)
+    t1, t2, t3 = 0.5 * co[:, 0] * dx * dx, 0.5 * co[:, 2] * dy * dy, co[:, 1] * dx * dy
+    beyond = int((np.abs(-(t1 + t2) - t3) > 8 * 2.0 ** -23 * (np.abs(t1) + np.abs(t2) + np.abs(t3) + 1.0)).sum())
+    for image, plain_tol, label in images:
+        err = np.abs(np.asarray(image, np.float64) - fw["color"]).max(axis=0).reshape(-1)
+        mask = np.zeros(H * W, bool)
+        mask[pix[err[pix] > plain_tol]] = True
+        n, bad, worst = account_outlier_pixels(fw, image, W, H, mask=mask.reshape(H, W))
+        print("power > 0 census %-24s %dx%d: %d pairs on %d pixels (%d beyond their rounding distance); %d of the pixels off by more "
+              "than %g, %d of them unexplained, worst %.3g; largest error on the others %.3g" % (
+                  "%s %s" % (what, label), W, H, len(pixel), len(pix), beyond, n, plain_tol, bad, worst,
+                  float(err[pix][err[pix] <= plain_tol].max()) if (err[pix] <= plain_tol).any() else 0.0))
+        assert bad == 0, "%s %s: %d pixels with a power > 0 pair are off by more than %g without a decision at a threshold" % (
+            what, label, bad, plain_tol)
+        assert worst <= 2.0 / 255.0 + 1e-3, (what, label, worst)
+    return len(pixel)

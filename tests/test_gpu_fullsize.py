@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import assert_forward_gate, assert_grads_elementwise
+from helpers import assert_forward_gate, assert_grads_elementwise, assert_power_census
 
 pytestmark = pytest.mark.gpu
 
@@ -218,6 +218,7 @@ def test_c2_full_size_gradients_vs_oracle(oracle):
     assert np.array_equal(color, ex_exact["color"])
     assert_forward_gate(fw, color, W, H, 1e-4, "C2 (training forward)", plain_tol=2.5e-5)
     assert_forward_gate(fw, ex["color"], W, H, 1e-4, "C2", plain_tol=5e-5)
+    assert_power_census(oracle, fw, [(ex["color"], 5e-5, "policy 0"), (color, 2.5e-5, "training forward")], W, H, "C2")
     _check_all_grads(g, bw, 1e-3)
 
 
@@ -227,10 +228,13 @@ def test_c3_bench_path_full_size_vs_oracle(oracle):
     gm_forward_1_geom, two frames / cameras.  Deformed cloud and colours vs the oracle's
     deform -> rotated SH colour (<= 1e-5 relative); then the oracle rasterizes the SAME deformed cloud: radii equal,
     num_rendered under the reference emission policy equal, sorted lists equal, strict image gate; the default policy's
-    image is bit-identical to the reference policy's."""
+    image is bit-identical to the reference policy's.  The census of the reference's `power > 0` skip on each frame.  Then both frames
+    once more as ONE launch chain of the object batch (gm_forward_deformed_batch_async) against the same oracle forwards: radii equal,
+    strict image gate.  (The batch takes at most 2048 list tiles - the one-pass tile sort - so at 1080p it runs under policy 2, 2040
+    tiles of 32 px; the reference policy's 8160 16-px tiles are refused.  Its lists are the single-frame policy-2 path's.)"""
     import bench
-    from gpu_utils import T, set_policy
-    from gaussianmesh_amd import rasterizer as Rz, scenes
+    from gpu_utils import T, _view, set_policy
+    from gaussianmesh_amd import _lib, rasterizer as Rz, scenes
     from gaussianmesh_amd.deform import mesh_rs, pack_mesh_state
     from oracle import mesh_oracle
     P, W, H, F = 1_000_000, 1920, 1080, 64
@@ -239,6 +243,7 @@ def test_c3_bench_path_full_size_vs_oracle(oracle):
     g = {k: T(host[k]) for k in ("weights", "pos", "cov", "opac", "shs", "verts")}
     g["tri"] = T(host["tri"], dtype=torch.int32)
     bg = np.ones(3, np.float32)
+    frames = []
     for t, k in ((3, 3), (40, 17)):
         cam = scenes.orbit_camera(k, F, W, H)
         ct = {n: T(cam[n]) for n in ("view", "proj", "campos")}
@@ -257,8 +262,6 @@ def test_c3_bench_path_full_size_vs_oracle(oracle):
             torch.cuda.synchronize()
             out[mode] = (nr, color.cpu().numpy(), radii.cpu().numpy(), [x.cpu().numpy() for x in h.deformed])
             if mode == 0:
-                from gpu_utils import _view
-                from gaussianmesh_amd import _lib
                 plist = _view(binning, _lib.lib().gm_binning_field(binning.data_ptr(), nr, W, H, 0, b"pairs"), 2 * nr, torch.int32).astype(np.uint32)[1::2]
         set_policy(2)
         assert np.array_equal(out[0][1], out[2][1]) and np.array_equal(out[0][2], out[2][2]) and out[2][0] < out[0][0]
@@ -277,6 +280,20 @@ def test_c3_bench_path_full_size_vs_oracle(oracle):
         assert np.array_equal(out[0][2], fw["geo"]["radii"])
         assert out[0][0] == fw["bins"]["R"] and np.array_equal(plist, fw["bins"]["point_list"])
         assert_forward_gate(fw, out[2][1], W, H, 1e-4, "C3 frame %d" % t, plain_tol=5e-5)
+        assert_power_census(oracle, fw, [(out[2][1], 5e-5, "policy 2")], W, H, "C3 frame %d" % t)
+        frames.append((packed, dict(ct, tanx=cam["tanx"], tany=cam["tany"]), fw, out[2]))
+    # the object batch: both frames in one chain
+    ws = [Rz.RasterWorkspace() for _ in frames]
+    for w_ in ws:
+        w_.capacity = int(1.05 * max(f[3][0] for f in frames))
+    hs = Rz.forward_deformed_batch(T(bg), g["tri"], g["weights"], [f[0] for f in frames], g["cov"], g["pos"], g["shs"], g["opac"],
+                                   [f[1] for f in frames], H, W, 3, ws, image_only=True, emission_policy=2)
+    for (_, _, fw, single), h, (t, _) in zip(frames, hs, ((3, 3), (40, 17))):
+        ok, nr = h.check()
+        assert ok and nr == single[0], (t, ok, nr, single[0])
+        color = h.color.cpu().numpy()
+        assert np.array_equal(h.radii.cpu().numpy(), fw["geo"]["radii"]) and np.array_equal(color, single[1]), t
+        assert_forward_gate(fw, color, W, H, 1e-4, "C3 batch frame %d" % t, plain_tol=5e-5)
 
 
 def test_c3_batch_of_four_full_size_equals_the_single_frame_path():
@@ -369,6 +386,7 @@ def test_4k_policy3_lists_image_and_gradients_vs_oracle(oracle):
     print("4K policy 3: %d instances for %d reference instances (%d of them needed by some pixel); %d (tile, Gaussian) pairs covered" % (
         cu["R"], ex["R"], int(needed.sum()), len(got)))
     assert_forward_gate(fw, cu["color"], W, H, 1e-4, "4K policy 3", plain_tol=5e-5)
+    assert_power_census(oracle, fw, [(cu["color"], 5e-5, "policy 3")], W, H, "4K")
     dpix = np.random.default_rng(1).normal(size=(3, H, W)).astype(np.float32)
     bw = oracle.backward_full(sc, cam, bg, fw, dpix, D=3)
     color, radii, g = _grads_gpu(sc, cam, bg, dpix, 3, False, False)            # the operator: auto policy = 3 at this size

@@ -439,6 +439,159 @@ def test_cov_to_scale_rot(oracle):
     assert np.abs(a["color"] - b["color"]).max() <= 2e-3
 
 
+# Row-relative bars of gm_cov_to_scale_rot, in float32 ulps (2^-23) of the row's own largest |eigenvalue| (its norm).  The Jacobi runs in
+# double on the float32 row, so what is left is the rounding of the float32 outputs: s^2 is within 1 ulp of the eigenvalue, a component of q
+# within half an ulp, R(q) within ~2 ulp of an exact rotation.
+C2SR_EIG_ULP = 4          # |s_j^2 - w_j|             <= 4 ulp x max|w|
+C2SR_REC_ULP = 8          # |R diag(s^2) R^T - sym(c)| <= 8 ulp x max|w|
+C2SR_NORM_ULP = 2         # ||q| - 1|                  <= 2 ulp
+C2SR_DET_ULP = 8          # |det R(q) - 1|             <= 8 ulp
+C2SR_VEC_ULP = 16         # ||U^T V| - I|              <= 16 ulp where every eigenvalue gap is >= C2SR_GAP x max|w|
+C2SR_GAP = 1e-3
+_ULP = 2.0 ** -23
+
+
+def _rot(axis, angle):
+    """rotation matrices [n,3,3] (float64) about unit axes [n,3] by angles [n] (Rodrigues)"""
+    a = axis / np.linalg.norm(axis, axis=1, keepdims=True)
+    K = np.zeros((len(a), 3, 3))
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 2] = -a[:, 2], a[:, 1], -a[:, 0]
+    K -= K.transpose(0, 2, 1)
+    s, c = np.sin(angle)[:, None, None], np.cos(angle)[:, None, None]
+    return np.eye(3) + s * K + (1 - c) * (K @ K)
+
+
+def _random_rot(rng, n):
+    q = rng.normal(size=(n, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    r, x, y, z = q.T
+    return np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y), 2 * (x * y + r * z), 1 - 2 * (x * x + z * z),
+                     2 * (y * z - r * x), 2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], 1).reshape(n, 3, 3)
+
+
+def _cov_to_scale_rot_rows(seed=11):
+    """float32 covariance rows [N,3,3] (N = 21 514, not a multiple of 256) in labelled families, the regimes where a 3x3 Jacobi goes wrong"""
+    rng = np.random.default_rng(seed)
+    fams = []
+
+    def add(name, R, ev):                                  # R diag(ev) R^T in float64, rounded once to float32
+        fams.append((name, (R @ (ev[:, :, None] * R.transpose(0, 2, 1))).astype(np.float32)))
+
+    def perm3(ev):
+        return np.take_along_axis(ev, np.argsort(rng.random(ev.shape), axis=1), axis=1)
+    # scales 1e-4 .. 1e2 in one batch (eigenvalues 1e-8 .. 1e4), moderate anisotropy
+    n = 6013
+    s = 10.0 ** rng.uniform(-4, 2, (n, 1)) * 10.0 ** rng.uniform(-0.5, 0.5, (n, 3))
+    add("span 1e-4..1e2", _random_rot(rng, n), s ** 2)
+    # needles (1, 1, r) and flat discs (r, r, 1), r up to 1e4, overall scale 1e-3 .. 10
+    for name, shape in (("needle to 1e4:1", lambda r: np.stack([np.ones_like(r), np.ones_like(r), r], 1)),
+                        ("disc to 1e4:1", lambda r: np.stack([r, r, np.ones_like(r)], 1))):
+        n = 2000
+        r = 10.0 ** rng.uniform(1, 4, n)
+        add(name, _random_rot(rng, n), perm3((10.0 ** rng.uniform(-3, 1, (n, 1)) * shape(r)) ** 2))
+    # one exact zero eigenvalue: a v v^T + b w w^T with small integer vectors and power-of-two weights (every entry exact in float32)
+    n = 1000
+    v, w = rng.integers(-3, 4, (n, 3)), rng.integers(-3, 4, (n, 3))
+    bad = np.linalg.norm(np.cross(v, w), axis=1) == 0
+    v[bad], w[bad] = [1, 2, -1], [0, 1, 3]
+    a, b = 2.0 ** rng.integers(-12, 4, (n, 1, 1)), 2.0 ** rng.integers(-12, 4, (n, 1, 1))
+    fams.append(("exact zero", (a * v[:, :, None] * v[:, None, :] + b * w[:, :, None] * w[:, None, :]).astype(np.float32)))
+    # two eigenvalues equal to within 1 + 1e-6 and 1 + 1e-3 (the third 0.1 .. 10 times away)
+    for name, rel in (("pair 1+1e-6", 1e-6), ("pair 1+1e-3", 1e-3)):
+        n = 1500
+        lam = 10.0 ** rng.uniform(-4, 2, (n, 1))
+        add(name, _random_rot(rng, n), perm3(lam * np.concatenate([np.ones((n, 1)), 1 + rel * np.ones((n, 1)),
+                                                                   10.0 ** rng.choice([-1, -0.5, 0.5, 1], (n, 1))], 1)))
+    # all three equal: exactly (lam I) and after rounding a rotated lam I
+    n = 1000
+    lam = 10.0 ** rng.uniform(-6, 3, (n, 1, 1))
+    fams.append(("triple exact", (lam * np.eye(3)).astype(np.float32)))
+    add("triple rounded", _random_rot(rng, n), np.repeat(lam[:, :, 0], 3, axis=1))
+    # rotations of exactly and nearly 180 degrees about random axes, and axis-aligned rows (diagonal in every order, exact and slightly
+    # rotated): the Jacobi starts from the identity, so a diagonal row in descending order comes back as a half-turn (trace -1)
+    n = 2000
+    ang = np.pi - rng.choice([0.0, 1e-7, 1e-4, 1e-2], n)
+    add("half-turn", _rot(rng.normal(size=(n, 3)), ang), 10.0 ** rng.uniform(-2, 1, (n, 3)))
+    n = 1500
+    ev = -np.sort(-(10.0 ** rng.uniform(-2, 1, (n, 3))), axis=1)
+    ev[n // 2:] = perm3(ev[n // 2:])
+    add("axis-aligned", _rot(rng.normal(size=(n, 3)), rng.choice([0.0, 1e-6, 1e-3], n)), ev)
+    # non-symmetric at rounding level, as deform_tensors makes it: O = (RS C) RS^T in float32, each sum associated as the kernel's
+    n = 2001
+    R0 = _random_rot(rng, n)
+    C = (R0 @ ((10.0 ** rng.uniform(-3, 0, (n, 3)))[:, :, None] ** 2 * R0.transpose(0, 2, 1))).astype(np.float32)
+    C = 0.5 * (C + C.transpose(0, 2, 1))                                 # the rest covariance: symmetric
+    RS = (_random_rot(rng, n) @ (np.eye(3) + 0.3 * rng.normal(size=(n, 3, 3)))).astype(np.float32)
+    mm = lambda X, Y: ((X[:, :, 0, None] * Y[:, None, 0, :] + X[:, :, 1, None] * Y[:, None, 1, :]) + X[:, :, 2, None] * Y[:, None, 2, :])
+    fams.append(("non-symmetric", mm(mm(RS, C), RS.transpose(0, 2, 1).copy())))
+    cov = np.concatenate([c for _, c in fams]).astype(np.float32)
+    label = np.concatenate([np.full(len(c), k) for k, (_, c) in enumerate(fams)])
+    return cov, label, [f for f, _ in fams]
+
+
+def _quat_mat(q):
+    r, x, y, z = (np.asarray(q, np.float64)[:, k] for k in range(4))
+    return np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y), 2 * (x * y + r * z), 1 - 2 * (x * x + z * z),
+                     2 * (y * z - r * x), 2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
+
+
+def _scale_rot_row_errors(cov, s, q):
+    """Per-row errors of (s, q) against numpy.linalg.eigh (float64) of the symmetrised float32 rows, each in ulps of the row's norm:
+    dict(eig, rec, norm, det, vec [NaN where an eigenvalue gap is below C2SR_GAP], branch [the quaternion branch R(q) selects], trace)"""
+    c = np.asarray(cov, np.float64).reshape(-1, 3, 3)
+    A = 0.5 * (c + c.transpose(0, 2, 1))
+    w, V = np.linalg.eigh(A)
+    s, q = np.asarray(s, np.float64), np.asarray(q, np.float64)
+    norm = np.maximum(np.abs(w).max(axis=1), 1e-300)
+    R = _quat_mat(q)
+    rec = R @ (s[:, :, None] ** 2 * R.transpose(0, 2, 1))
+    vec = np.abs(np.abs(R.transpose(0, 2, 1) @ V) - np.eye(3)).max(axis=(1, 2)) / _ULP
+    vec[np.diff(w, axis=1).min(axis=1) < C2SR_GAP * norm] = np.nan
+    tr = np.trace(R, axis1=1, axis2=2)
+    d = np.diagonal(R, axis1=1, axis2=2)
+    branch = np.where(tr > 0, 0, np.where((d[:, 0] > d[:, 1]) & (d[:, 0] > d[:, 2]), 1, np.where(d[:, 1] > d[:, 2], 2, 3)))
+    return dict(eig=np.abs(s ** 2 - w).max(axis=1) / norm / _ULP, rec=np.abs(rec - A).max(axis=(1, 2)) / norm / _ULP,
+                norm=np.abs(np.linalg.norm(q, axis=1) - 1) / _ULP, det=np.abs(np.linalg.det(R) - 1) / _ULP, vec=vec, branch=branch, trace=tr)
+
+
+def _assert_scale_rot_rows(cov, label, names, s, q):
+    """every row within the C2SR_* bars, scales ascending; prints the largest error of each family; returns the per-row errors"""
+    e = _scale_rot_row_errors(cov, s, q)
+    for k, name in enumerate(names):
+        m = label == k
+        v = e["vec"][m]
+        print("cov_to_scale_rot %-16s %5d rows: max ulp of the row's norm: eigenvalues %6.2f  reconstruction %6.2f  |q| %5.2f  det %5.2f  "
+              "eigenvectors %s" % (name, m.sum(), e["eig"][m].max(), e["rec"][m].max(), e["norm"][m].max(), e["det"][m].max(),
+                                   "%6.2f (%d rows)" % (np.nanmax(v), np.isfinite(v).sum()) if np.isfinite(v).any() else "-"))
+    for key, bar in (("eig", C2SR_EIG_ULP), ("rec", C2SR_REC_ULP), ("norm", C2SR_NORM_ULP), ("det", C2SR_DET_ULP)):
+        bad = np.nonzero(~(e[key] <= bar))[0]
+        assert len(bad) == 0, "%s: %d rows above %d ulp, e.g. row %d (%s): %.3g ulp" % (key, len(bad), bar, bad[0], names[label[bad[0]]],
+                                                                                      e[key][bad[0]])
+    bad = np.nonzero(e["vec"] > C2SR_VEC_ULP)[0]
+    assert len(bad) == 0, "eigenvectors: %d rows above %d ulp, e.g. row %d (%s)" % (len(bad), C2SR_VEC_ULP, bad[0], names[label[bad[0]]])
+    assert (np.diff(np.asarray(s), axis=1) >= 0).all()        # ascending, like eigh (exactly: sqrt and the rounding are monotone)
+    return e
+
+
+def test_cov_to_scale_rot_rows_against_float64_eigh():
+    """gm_cov_to_scale_rot row by row against numpy.linalg.eigh in float64, every bar relative to the row itself (test_cov_to_scale_rot's bars
+    are relative to the batch's largest row: a row at scale 1e-2 would be allowed 0.5 % there).  Families: scales 1e-4 .. 1e2, needles and
+    discs to 1e4:1, an exact zero eigenvalue, pairs equal to 1 + 1e-6 / 1 + 1e-3, all three equal, half-turns and axis-aligned rows
+    (trace -1), rows made non-symmetric at rounding level as deform_tensors makes them.  Each of the four quaternion branches runs >= 100x."""
+    from gpu_utils import T
+    from gaussianmesh_amd.deform import cov_to_scale_rot
+    cov, label, names = _cov_to_scale_rot_rows()
+    assert len(cov) >= 20000 and len(cov) % 256 != 0
+    ns = cov[label == names.index("non-symmetric")]
+    assert (ns[:, [0, 0, 1], [1, 2, 2]] != ns[:, [1, 2, 2], [0, 0, 1]]).any(axis=1).mean() > 0.5         # c[1] != c[3] etc. at rounding level
+    s, q = (x.cpu().numpy() for x in cov_to_scale_rot(T(cov)))
+    e = _assert_scale_rot_rows(cov, label, names, s, q)
+    counts = np.bincount(e["branch"], minlength=4)
+    near = int((e["trace"] < -1 + 1e-3).sum())
+    print("cov_to_scale_rot: quaternion branches (trace > 0, x, y, z) taken %s times; %d rows with trace < -1 + 1e-3" % (counts.tolist(), near))
+    assert counts.min() >= 100 and near >= 100, (counts, near)
+
+
 def test_render_glue_contract(oracle):
     """8f-1: render() dict contract, mesh-bound get_xyz, gradients reaching the barycentric parameters."""
     from types import SimpleNamespace

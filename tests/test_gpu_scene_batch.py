@@ -50,41 +50,50 @@ def _layout(tool, name):
             "no_bg": (0, [(A, every), (B, every)]), "bg_only": (800, [])}[name]
 
 
-def _batch_inputs(tool, nbg, objs):
+def _batch_inputs(tool, nbg, objs, ntail=0):
+    """the scene's rows: background rows [0, nbg), the objects' slices, then ntail more background rows (static rows behind the last
+    object: object_rows[n_objects] < P).  Each (object, slice) entry is an object of the batch with its own copy of its mesh's vertices in
+    the combined gather table (voff)."""
     cat = lambda xs: torch.cat(xs, dim=0).contiguous()
     rows = [nbg]
     for o, sl in objs:
         rows.append(rows[-1] + o.gaussian_pos[sl].shape[0])
     voff = np.cumsum([0] + [o.vertex.shape[0] for o, _ in objs])
+    bgr = lambda t: (t[:nbg], t[nbg:nbg + ntail])
+    assert nbg + ntail <= tool.bg_mean3D.shape[0]
     g = dict(rows=rows, voff=voff,
-             pos=cat([tool.bg_mean3D[:nbg]] + [o.gaussian_pos[sl] for o, sl in objs]),
-             cov=cat([tool.bg_cov3D[:nbg]] + [o.gaussian_cov[sl] for o, sl in objs]),
-             shs=cat([tool.bg_shs[:nbg]] + [o.gaussian_feature[sl] for o, sl in objs]),
-             opac=cat([tool.bg_opacity[:nbg].reshape(-1)] + [o.gaussian_o[sl].reshape(-1) for o, sl in objs]))
+             pos=cat([bgr(tool.bg_mean3D)[0]] + [o.gaussian_pos[sl] for o, sl in objs] + [bgr(tool.bg_mean3D)[1]]),
+             cov=cat([bgr(tool.bg_cov3D)[0]] + [o.gaussian_cov[sl] for o, sl in objs] + [bgr(tool.bg_cov3D)[1]]),
+             shs=cat([bgr(tool.bg_shs)[0]] + [o.gaussian_feature[sl] for o, sl in objs] + [bgr(tool.bg_shs)[1]]),
+             opac=cat([bgr(tool.bg_opacity)[0].reshape(-1)] + [o.gaussian_o[sl].reshape(-1) for o, sl in objs] +
+                      [bgr(tool.bg_opacity)[1].reshape(-1)]))
     g["tri"] = cat([o.gaussian_triangles[sl] + int(voff[j]) for j, (o, sl) in enumerate(objs)]).to(torch.int32) if objs else None
     g["w"] = cat([o.coord[sl] for o, sl in objs]) if objs else None
     g["ocov"] = cat([o.gaussian_cov[sl].reshape(-1, 9) for o, sl in objs]) if objs else None
     return g
 
 
-def _reference(tool, nbg, objs, defs, cam, H, W, bg):
+def _reference(tool, nbg, objs, defs, cam, H, W, bg, ntail=0, policy=None):
     """The contract: the rows concatenated in render_gaussian's order (deformed objects through mesh_rs + deform), gm_cov_to_scale_rot of
-    every row, the rasterizer's forward with scales / rotations / SH rows -> (num_rendered, image, radii)"""
+    every row, the rasterizer's forward with scales / rotations / SH rows -> (num_rendered, image, radii, dict(the frame's rows: pos,
+    scales, rots; its binning buffer, laid out for num_rendered instances))"""
     from gaussianmesh_amd import rasterizer as Rz
     from gaussianmesh_amd.deform import cov_to_scale_rot, deform_tensors, mesh_rs
     pos, cov = [tool.bg_mean3D[:nbg]], [tool.bg_cov3D[:nbg]]
     for j, (o, sl) in enumerate(objs):
-        if j in defs:
+        if j in defs and o.gaussian_pos[sl].shape[0]:
             R, S = mesh_rs(o.vertex, defs[j], o.faces, adjacency=o._adjacency)
             p, c, _, _ = deform_tensors(o.gaussian_triangles[sl], o.coord[sl], defs[j] - o.vertex, R, S, o.gaussian_cov[sl], o.gaussian_pos[sl])
         else:
             p, c = o.gaussian_pos[sl], o.gaussian_cov[sl]
         pos.append(p); cov.append(c)
-    g = _batch_inputs(tool, nbg, objs)
+    pos.append(tool.bg_mean3D[nbg:nbg + ntail]); cov.append(tool.bg_cov3D[nbg:nbg + ntail])
+    g = _batch_inputs(tool, nbg, objs, ntail)
     s, q = cov_to_scale_rot(torch.cat(cov, dim=0))
-    out = Rz.rasterize_forward_begin(bg, torch.cat(pos, dim=0), None, g["opac"], s, q, 1, None, cam["view"], cam["proj"], cam["tanx"], cam["tany"],
-                                     H, W, g["shs"], 3, cam["campos"], False, False, force_M=16).finish(image_only=True)
-    return out[0], out[1].clone(), out[2].clone()
+    pos = torch.cat(pos, dim=0)
+    out = Rz.rasterize_forward_begin(bg, pos, None, g["opac"], s, q, 1, None, cam["view"], cam["proj"], cam["tanx"], cam["tany"],
+                                     H, W, g["shs"], 3, cam["campos"], False, False, emission_policy=policy, force_M=16).finish(image_only=True)
+    return out[0], out[1].clone(), out[2].clone(), dict(pos=pos, scales=s, rots=q, binning=out[4])
 
 
 def _tables(objs, defs_list):
@@ -101,17 +110,17 @@ def _tables(objs, defs_list):
     return out
 
 
-def _run_batch(tool, nbg, objs, defs_list, cams, H, W, bg, cap):
+def _run_batch(tool, nbg, objs, defs_list, cams, H, W, bg, cap, ntail=0, policy=None):
     from gaussianmesh_amd import rasterizer as Rz
     from gaussianmesh_amd.deform import cov_to_scale_rot
-    g = _batch_inputs(tool, nbg, objs)
+    g = _batch_inputs(tool, nbg, objs, ntail)
     s, q = cov_to_scale_rot(g["cov"])                                  # the static rows: every row's resting (scale, rotation)
     masks = [sum(1 << j for j in defs) for defs in defs_list]
     ws = [Rz.RasterWorkspace() for _ in defs_list]
     for w_ in ws:
         w_.capacity = cap
     hs = Rz.forward_scene_batch(bg, g["rows"], masks, g["pos"], s, q, g["shs"], g["opac"], g["tri"], g["w"], g["ocov"], _tables(objs, defs_list),
-                                cams, H, W, 3, ws, image_only=True)
+                                cams, H, W, 3, ws, image_only=True, emission_policy=policy)
     return hs
 
 
@@ -265,3 +274,163 @@ def test_cli_with_a_background_writes_what_the_api_renders(tmp_path):
         assert np.array_equal(png, exp), i
         n += 1
     assert n == 7 and not os.path.exists(os.path.join(out, "%05d.png" % 7))
+
+
+# ---------------------------------------------------------------------------------------------
+# The batch at the edges of its ABI: every emission policy at ragged sizes and at the 2048-list-tile limit of a batch, 32 objects, empty
+# objects, static rows behind the last object, object boundaries on wave boundaries, deformed rows on both sides of the near plane, full
+# batches; each frame bit for bit against the contract above (images, radii, instance count, status words; lists under policy 0).
+
+def _edge_layout(tool, name):
+    """(background rows before the objects, [(object, row slice)], background rows after them)
+    "split32": A and B cut into 16 slices each - 32 objects (GM_SCENE_OBJECTS_MAX), each with its own copy of its mesh in the table;
+    "empty": empty objects first, in the middle and last; "tail": static rows behind the last object (object_rows[n] < P);
+    "tail_only": object_rows[0] == 0 and trailing rows; "waves": P = 3110 (not a multiple of 64), object boundaries at rows = 63, 0, 1
+    (mod 64)"""
+    A, B = tool.gaussians_list
+    if name == "split32":
+        objs = []
+        for o in (A, B):
+            cut = np.linspace(0, o.gaussian_pos.shape[0], 17).astype(int)
+            objs += [(o, slice(int(a), int(b))) for a, b in zip(cut[:-1], cut[1:])]
+        return 100, objs, 0
+    return {"empty": (200, [(A, slice(0, 0)), (A, slice(0, 1500)), (B, slice(7, 7)), (A, slice(1500, None)), (B, slice(None)), (B, slice(5, 5))], 0),
+            "tail": (300, [(A, slice(None)), (B, slice(0, 1000))], 400),
+            "tail_only": (0, [(A, slice(None))], 500),
+            "waves": (63, [(A, slice(0, 65)), (B, slice(0, 1)), (A, slice(65, 127)), (B, slice(1, 66)), (A, slice(127, 2944))], 37)}[name]
+
+
+def _pairs(binning, laid_out_for, nr, W, H, policy):
+    """the sorted (key, id) instance list of a frame from its binning buffer (laid out for `laid_out_for` instances)"""
+    from gpu_utils import _view
+    from gaussianmesh_amd import _lib
+    return _view(binning, _lib.lib().gm_binning_field(binning.data_ptr(), laid_out_for, W, H, policy, b"pairs"), 2 * nr, torch.int32)
+
+
+def _frames_equal_the_contract(tool, nbg, objs, ntail, masks, cams, H, W, bg, policy=None, lists=False, t0=3):
+    """frame k deforms object j (its own twist of the object's mesh) when bit j of masks[k] is set; the batch of the K frames against
+    the contract frame by frame: instance count, status words, radii, image, with lists=True the instance list.  Returns (ref, handles)."""
+    from gaussianmesh_amd import rasterizer as Rz
+    defs_list = [{j: _mesh(o, t0 + 2 * k + 5 * (j % 7)) for j, (o, _) in enumerate(objs) if (m >> j) & 1} for k, m in enumerate(masks)]
+    ref = [_reference(tool, nbg, objs, defs, c, H, W, bg, ntail, policy) for defs, c in zip(defs_list, cams)]
+    assert all(r[0] > 0 for r in ref), [r[0] for r in ref]
+    cap = int(max(r[0] for r in ref) * 1.25) + 1024
+    hs = _run_batch(tool, nbg, objs, defs_list, cams, H, W, bg, cap, ntail, policy)
+    pol = Rz.get_default_emission_policy(W, H) if policy is None else policy
+    what = "%dx%d policy %d, %d objects" % (W, H, pol, len(objs))
+    for k, h in enumerate(hs):
+        ok, nr = h.check()
+        assert ok and nr == ref[k][0], (what, k, ok, nr, ref[k][0])
+        assert h.workspace.status()[0].tolist() == [nr, 0, pol, 0], (what, k)
+        assert torch.equal(h.radii, ref[k][2]), "%s, frame %d (mask %#x): radii" % (what, k, masks[k])
+        assert torch.equal(h.color, ref[k][1]), "%s, frame %d (mask %#x): image" % (what, k, masks[k])
+        if lists:
+            assert np.array_equal(_pairs(h.binning, h.workspace.capacity, nr, W, H, pol), _pairs(ref[k][3]["binning"], nr, nr, W, H, pol)), (
+                "%s, frame %d: instance list" % (what, k))
+    return ref, hs
+
+
+def _list_tiles(W, H, policy):
+    sh = max(policy - 1, 0)
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    return ((gx + (1 << sh) - 1) >> sh) * ((gy + (1 << sh) - 1) >> sh)
+
+
+# per policy a ragged size with exactly 2048 list tiles (16-px tiles under 0 and 1, 32-px parents under 2, 64-px under 3): the most a
+# batch takes (the one-pass tile sort)
+_AT_THE_LIMIT = {0: (1017, 509), 1: (2041, 241), 2: (2033, 1009), 3: (4065, 2017)}
+
+
+@pytest.mark.parametrize("policy", [0, 1, 2, 3])
+def test_scene_batch_under_every_emission_policy(tmp_path, policy):
+    tool, d1, _ = _tool(tmp_path)
+    nbg, objs = _layout(tool, "scene")
+    cams = [_cam(c) for c in tool.get_camera(d1)]
+    bg = torch.tensor([0.3, 0.1, 0.6], device="cuda")
+    assert _list_tiles(*_AT_THE_LIMIT[policy], policy) == 2048
+    for W, H in [(161, 97), (333, 211), _AT_THE_LIMIT[policy]]:
+        _frames_equal_the_contract(tool, nbg, objs, 0, [0b01, 0b11, 0b00], cams, H, W, bg, policy=policy, lists=policy == 0)
+
+
+def test_scene_batch_of_32_objects_full_batch(tmp_path):
+    """GM_SCENE_OBJECTS_MAX objects and GM_BATCH_MAX frames: only object 31, all 32, none, alternating both ways, the first and the last,
+    each half"""
+    from gaussianmesh_amd import _lib
+    tool, d1, _ = _tool(tmp_path)
+    nbg, objs, ntail = _edge_layout(tool, "split32")
+    assert len(objs) == _lib.GM_SCENE_OBJECTS_MAX
+    masks = [1 << 31, 0xFFFFFFFF, 0, 0x55555555, 0xAAAAAAAA, (1 << 31) | 1, 0xFFFF0000, 0x0000FFFF]
+    assert len(masks) == _lib.GM_BATCH_MAX
+    cams = [_cam(c) for c in tool.get_camera(d1)]
+    _frames_equal_the_contract(tool, nbg, objs, ntail, masks, [cams[k % len(cams)] for k in range(len(masks))], 120, 200,
+                               torch.tensor([0.2, 0.5, 0.7], device="cuda"))
+
+
+@pytest.mark.parametrize("layout", ["empty", "tail", "tail_only", "waves"])
+def test_scene_batch_row_layout_edges(tmp_path, layout):
+    tool, d1, _ = _tool(tmp_path)
+    nbg, objs, ntail = _edge_layout(tool, layout)
+    g = _batch_inputs(tool, nbg, objs, ntail)
+    P, rows = g["pos"].shape[0], g["rows"]
+    if layout == "empty":
+        assert rows[0] == rows[1] and rows[2] == rows[3] and rows[-2] == rows[-1] == P
+    elif layout in ("tail", "tail_only"):
+        assert rows[-1] < P and (rows[0] == 0) == (layout == "tail_only")
+    else:
+        assert P == 3110 and rows == [63, 128, 129, 191, 256, 3073]                # boundaries at 63, 0, 1, 63, 0, 1 (mod 64)
+    n = len(objs)
+    full, even = (1 << n) - 1, sum(1 << j for j in range(0, n, 2))
+    masks = [full, even, 0, full ^ even, full]
+    cams = [_cam(c) for c in tool.get_camera(d1)]
+    _frames_equal_the_contract(tool, nbg, objs, ntail, masks, [cams[k % len(cams)] for k in range(len(masks))], 97, 161,
+                               torch.tensor([0.6, 0.2, 0.1], device="cuda"), policy=0, lists=True)
+
+
+def test_scene_batch_deformed_rows_at_the_near_plane(tmp_path):
+    """a camera inside the tori's tube: deformed rows on both sides of view-space z = 0.2, where the fused pass skips the Jacobi of a row
+    (pre_project culls it) and the contract does not"""
+    from gaussianmesh_amd import scenes
+    from gaussianmesh_amd.renderer import Camera
+    tool, _, _ = _tool(tmp_path)
+    nbg, objs = _layout(tool, "scene")
+    H, W = 120, 200
+    cams = [_cam(Camera(scenes.orbit_camera(k, 7, W, H, radius=2.0, height=0.0), "cuda")) for k in (1, 4, 6)]
+    masks = [0b01, 0b11, 0b10]
+    ref, _ = _frames_equal_the_contract(tool, nbg, objs, 0, masks, cams, H, W, torch.tensor([0.1, 0.1, 0.1], device="cuda"))
+    rows = _batch_inputs(tool, nbg, objs)["rows"]
+    for k, (r, c) in enumerate(zip(ref, cams)):
+        z = r[3]["pos"] @ c["view"][:3, 2] + c["view"][3, 2]                    # view-space depth (the row-vector view matrix)
+        moved = torch.zeros_like(z, dtype=torch.bool)
+        for j in range(len(objs)):
+            if (masks[k] >> j) & 1:
+                moved[rows[j]:rows[j + 1]] = True
+        near, front = int(((z <= 0.2) & moved).sum()), int(((z > 0.2) & (z < 0.4) & moved).sum())
+        assert near >= 50 and front >= 50, (k, near, front)
+
+
+@pytest.mark.parametrize("policy", [0, 2])
+def test_scene_frames_against_the_oracle(tmp_path, oracle, policy):
+    """each frame of a scene batch against the CPU oracle directly (not only against the HIP single-frame route): the frame's rows as the
+    contract builds them (positions, (scale, rotation) from cov_to_scale_rot) through oracle.forward_full - radii equal, under policy 0
+    the instance count and sorted list equal, and the strict forward gate on the image"""
+    from helpers import assert_forward_gate
+    tool, d1, _ = _tool(tmp_path)
+    nbg, objs, ntail = _edge_layout(tool, "waves")
+    H, W = 120, 200
+    cams = [_cam(c) for c in tool.get_camera(d1)]
+    bg = torch.tensor([0.2, 0.5, 0.7], device="cuda")
+    n = len(objs)
+    masks = [(1 << n) - 1, 0b10101, 0]
+    ref, hs = _frames_equal_the_contract(tool, nbg, objs, ntail, masks, cams, H, W, bg, policy=policy)
+    g = _batch_inputs(tool, nbg, objs, ntail)
+    host = lambda t: t.detach().cpu().numpy()
+    for k, (r, h, c) in enumerate(zip(ref, hs, cams)):
+        sc = dict(means=host(r[3]["pos"]), opac=host(g["opac"]), shs=host(g["shs"]), scales=host(r[3]["scales"]), rots=host(r[3]["rots"]))
+        cam = dict(view=host(c["view"]), proj=host(c["proj"]), campos=host(c["campos"]), W=W, H=H, tanx=c["tanx"], tany=c["tany"])
+        fw = oracle.forward_full(sc, cam, host(bg), D=3)
+        assert np.array_equal(host(h.radii), fw["geo"]["radii"]), (policy, k)
+        if policy == 0:
+            nr = h.check()[1]
+            assert nr == fw["bins"]["R"], (k, nr, fw["bins"]["R"])
+            assert np.array_equal(_pairs(h.binning, h.workspace.capacity, nr, W, H, 0)[1::2].astype(np.uint32), fw["bins"]["point_list"]), k
+        assert_forward_gate(fw, host(h.color), W, H, 1e-4, "scene frame %d policy %d" % (k, policy), plain_tol=5e-5)

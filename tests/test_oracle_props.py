@@ -115,3 +115,71 @@ def test_mesh_rs_oracle_invariants():
     R, S = mesh_oracle.mesh_rs(verts, verts @ A.T, faces)
     assert np.abs(np.einsum("nji,njk->nik", R, S) - A).max() <= 1e-6      # (the 1e-9 normal regulariser)
     assert np.abs(np.linalg.det(R) - 1).max() <= 1e-10 and np.abs(S - S.transpose(0, 2, 1)).max() <= 1e-12
+
+
+def _census_walk(W, H, bins, geo):
+    """orc_power_census restated in numpy float32 (the same expression, evaluation order and stop): the list of (pixel, list position)"""
+    f = np.float32
+    xy, co = geo["xy"].astype(f), geo["conic_op"].astype(f)
+    gx = (W + 15) // 16
+    out = []
+    for t, (r0, r1) in enumerate(bins["ranges"]):
+        for y in range(16 * (t // gx), min(16 * (t // gx) + 16, H)):
+            for x in range(16 * (t % gx), min(16 * (t % gx) + 16, W)):
+                T = f(1)
+                for e in range(r0, r1):
+                    g = bins["point_list"][e]
+                    dx, dy = xy[g, 0] - f(x), xy[g, 1] - f(y)
+                    power = f(-0.5) * (co[g, 0] * dx * dx + co[g, 2] * dy * dy) - co[g, 1] * dx * dy
+                    if power > 0:
+                        if co[g, 3] >= f(1) / f(255):
+                            out.append((y * W + x, e))
+                        continue
+                    alpha = min(f(0.99), co[g, 3] * f(np.exp(power)))
+                    if alpha < f(1) / f(255):
+                        continue
+                    if T * (f(1) - alpha) < f(1e-4):
+                        break
+                    T = T * (f(1) - alpha)
+    return out
+
+
+def test_power_census_counts_a_constructed_scene(oracle):
+    """orc_power_census on hand-made lists (20x18 pixels, four tiles; only tile 0 has a list) with a known answer.  Entry 3 has the
+    indefinite conic (1, 0, -1) centred on (7.5, 7.5): power = (dy^2 - dx^2) / 2, exact in float32, > 0 on the 4 x 28 = 112 pixels of the
+    tile with |dy| > |dx|.  Entry 0 takes alpha = 0.99 everywhere (T = 0.01); entry 1 stops column 3 (alpha = 0.99 at dx = 0, < 1/255
+    elsewhere), whose 6 pixels with |dy| > 4.5 therefore never reach entry 3: 106 pairs.  Entry 2 is entry 3's twin below 1/255 opacity
+    (skipped by every pixel with power clamped to 0 as well): no pair.  Then a random scene against a numpy restatement of the walk."""
+    W, H = 20, 18
+    xy = np.array([[7.5, 7.5], [3.0, 7.5], [7.5, 7.5], [7.5, 7.5]], np.float32)
+    co = np.array([[1e-6, 0, 1e-6, 1.0], [100.0, 0, 1e-6, 1.0], [1, 0, -1, 1 / 300], [1, 0, -1, 0.5]], np.float32)
+    ranges = np.zeros((4, 2), np.uint32); ranges[0] = [0, 4]
+    bins = dict(R=4, point_list=np.arange(4, dtype=np.uint32), ranges=ranges)
+    geo = dict(xy=xy, conic_op=co)
+    pixel, pos = oracle.power_census(W, H, bins, geo)
+    assert len(pixel) == 106 and (pos == 3).all()
+    y, x = pixel // W, pixel % W
+    assert (np.abs(y - 7.5) > np.abs(x - 7.5)).all() and not ((x == 3) & (np.abs(y - 7.5) > 4.5)).any()
+    assert len(np.unique(pixel)) == 106 and (x < 16).all() and (y < 16).all()
+    assert sorted(zip(pixel.tolist(), pos.tolist())) == sorted(_census_walk(W, H, bins, geo))
+    # without the stopper every pixel of the tile reaches entry 3: 112
+    keep = np.array([0, 2, 3], np.uint32)
+    ranges[0] = [0, 3]
+    assert len(oracle.power_census(W, H, dict(R=3, point_list=keep, ranges=ranges), geo)[0]) == 112
+    # opacity exactly 1/255 counts, just below does not
+    co2 = co.copy(); co2[3, 3] = np.float32(1) / np.float32(255)
+    assert len(oracle.power_census(W, H, dict(R=3, point_list=keep, ranges=ranges), dict(xy=xy, conic_op=co2))[0]) == 112
+    co2[3, 3] = np.nextafter(co2[3, 3], np.float32(0))
+    assert len(oracle.power_census(W, H, dict(R=3, point_list=keep, ranges=ranges), dict(xy=xy, conic_op=co2))[0]) == 0
+    # random lists over a ragged 37 x 29 image, conics of both signs, against the numpy walk (order: tile, pixel, list position)
+    rng = np.random.default_rng(4)
+    W, H, P = 37, 29, 60
+    xy = rng.uniform(-4, 40, (P, 2)).astype(np.float32)
+    co = np.stack([rng.uniform(0.01, 0.5, P), rng.uniform(-0.6, 0.6, P), rng.uniform(0.01, 0.5, P), rng.uniform(0, 1, P)], 1).astype(np.float32)
+    gx, gy = 3, 2
+    lists = [rng.choice(P, int(rng.integers(0, 30)), replace=False) for _ in range(gx * gy)]
+    ranges = np.cumsum([0] + [len(l) for l in lists]).astype(np.uint32)
+    bins = dict(R=int(ranges[-1]), point_list=np.concatenate(lists).astype(np.uint32), ranges=np.stack([ranges[:-1], ranges[1:]], 1).copy())
+    pixel, pos = oracle.power_census(W, H, bins, dict(xy=xy, conic_op=co))
+    ref = _census_walk(W, H, bins, dict(xy=xy, conic_op=co))
+    assert len(ref) > 50 and list(zip(pixel.tolist(), pos.tolist())) == ref
