@@ -752,6 +752,41 @@ int gm_ssim_bwd(const float* img1, const float* img2, const float* dS_dmu1, cons
   return launch_ssim_bwd(img1, img2, dS_dmu1, dS_dE11, dS_dE12, planes, H, W, g_ssim, g_l1, dL_dimg1, reinterpret_cast<hipStream_t>(stream));
 }
 
+static int check_u8_target(const char* who, const unsigned char* rgb, const unsigned char* mask, int64_t mask_plane_stride,
+                           const float* background, int planes, int H, int W) {
+  char msg[160];
+  if (planes != 3) { snprintf(msg, sizeof msg, "%s: an 8-bit target has 3 planes", who); set_error(msg); return GM_ERR_INVALID_ARG; }
+  if (!rgb) { snprintf(msg, sizeof msg, "%s: null rgb", who); set_error(msg); return GM_ERR_INVALID_ARG; }
+  if (mask && !background) { snprintf(msg, sizeof msg, "%s: a mask needs the background colour (device float[3])", who); set_error(msg); return GM_ERR_INVALID_ARG; }
+  if (mask && mask_plane_stride != 0 && mask_plane_stride < (int64_t)H * W) {
+    snprintf(msg, sizeof msg, "%s: mask_plane_stride is 0 (one shared plane) or at least H*W", who); set_error(msg); return GM_ERR_INVALID_ARG;
+  }
+  return GM_OK;
+}
+
+int gm_ssim_fwd_u8(const float* img1, const uint8_t* rgb, const uint8_t* mask, int64_t mask_plane_stride, const float* background,
+                   int planes, int H, int W, float* dS_dmu1, float* dS_dE11, float* dS_dE12, float* partial, void* stream) {
+  if (planes < 0 || H < 0 || W < 0) { set_error("gm_ssim_fwd_u8: negative size"); return GM_ERR_INVALID_ARG; }
+  if (planes == 0 || H == 0 || W == 0) return GM_OK;
+  if (!img1 || !partial) { set_error("gm_ssim_fwd_u8: null image or partial buffer"); return GM_ERR_INVALID_ARG; }
+  const int nmaps = (dS_dmu1 != nullptr) + (dS_dE11 != nullptr) + (dS_dE12 != nullptr);
+  if (nmaps != 0 && nmaps != 3) { set_error("gm_ssim_fwd_u8: pass all three derivative maps or none"); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_u8_target("gm_ssim_fwd_u8", rgb, mask, mask_plane_stride, background, planes, H, W)) return rc;
+  return launch_ssim_fwd_u8(img1, rgb, mask, (size_t)mask_plane_stride, background, H, W, dS_dmu1, dS_dE11, dS_dE12, partial,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int gm_ssim_bwd_u8(const float* img1, const uint8_t* rgb, const uint8_t* mask, int64_t mask_plane_stride, const float* background,
+                   const float* dS_dmu1, const float* dS_dE11, const float* dS_dE12, int planes, int H, int W, const float* g_ssim,
+                   const float* g_l1, float* dL_dimg1, void* stream) {
+  if (planes < 0 || H < 0 || W < 0) { set_error("gm_ssim_bwd_u8: negative size"); return GM_ERR_INVALID_ARG; }
+  if (planes == 0 || H == 0 || W == 0) return GM_OK;
+  if (!img1 || !dS_dmu1 || !dS_dE11 || !dS_dE12 || !g_ssim || !dL_dimg1) { set_error("gm_ssim_bwd_u8: null argument"); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_u8_target("gm_ssim_bwd_u8", rgb, mask, mask_plane_stride, background, planes, H, W)) return rc;
+  return launch_ssim_bwd_u8(img1, rgb, mask, (size_t)mask_plane_stride, background, dS_dmu1, dS_dE11, dS_dE12, H, W, g_ssim, g_l1,
+                            dL_dimg1, reinterpret_cast<hipStream_t>(stream));
+}
+
 int gm_loss_combine(const float* partial, int64_t n_partials, double c_ssim, double c_l1, double offset, float* out, void* stream) {
   if (n_partials < 0) { set_error("gm_loss_combine: negative count"); return GM_ERR_INVALID_ARG; }
   if (!out || (n_partials > 0 && !partial)) { set_error("gm_loss_combine: null partial / out"); return GM_ERR_INVALID_ARG; }

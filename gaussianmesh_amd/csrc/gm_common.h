@@ -428,6 +428,12 @@ int launch_ssim_fwd(const float* img1, const float* img2, int planes, int H, int
 int launch_loss_combine(const float* partial, long long n, double c_ssim, double c_l1, double offset, float* out, hipStream_t s);
 int launch_ssim_bwd(const float* img1, const float* img2, const float* d_mu1, const float* d_e11, const float* d_e12, int planes,
                     int H, int W, const float* g_ssim, const float* g_l1, float* dL_dimg1, hipStream_t s);
+// the same two kernels' bodies with an 8-bit target composited on load (three planes; gm_loss.hip U8Target)
+int launch_ssim_fwd_u8(const float* img1, const unsigned char* rgb, const unsigned char* mask, size_t mask_stride, const float* bg, int H,
+                       int W, float* d_mu1, float* d_e11, float* d_e12, float* partial, hipStream_t s);
+int launch_ssim_bwd_u8(const float* img1, const unsigned char* rgb, const unsigned char* mask, size_t mask_stride, const float* bg,
+                       const float* d_mu1, const float* d_e11, const float* d_e12, int H, int W, const float* g_ssim, const float* g_l1,
+                       float* dL_dimg1, hipStream_t s);
 struct ActArgs {                 // mesh-bound parameter -> rasterizer-input map (gm_train.hip)
   int N;
   float alpha;

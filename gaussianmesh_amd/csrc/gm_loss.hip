@@ -12,6 +12,9 @@
 //   backward: dL/dx = conv(g dS/dmu1) + 2 x conv(g dS/dE[xx]) + y conv(g dS/dE[xy]) + g_l1 sign(x - y)
 //             (the window is symmetric, so the adjoint of the correlation is the same correlation).
 // HBM traffic per pixel-channel: forward 8 B in + 12 B out, backward 20 B in + 4 B out.
+// ssim_fwd_u8_kernel / ssim_bwd_u8_kernel: the same two bodies (gm_ssim_fwd_body.inc / gm_ssim_bwd_body.inc) with the target read as the
+// 8-bit planes of a dataset and composited over a background on load: 2 B (rgb + one mask plane) instead of 4 B of target per
+// pixel-channel, and no composite pass in front of the loss.
 #include "gm_common.h"
 
 namespace gm {
@@ -43,141 +46,63 @@ __device__ __forceinline__ float block_sum(float v, float* red /*[4]*/) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// The target image y of the two kernel bodies (gm_ssim_fwd_body.inc, gm_ssim_bwd_body.inc): the staging loop of the forward and the per-pixel
+// read of the backward get it through LS_TARGET.  The float kernels read a float [planes,H,W] image.  The u8 kernels read the 8-bit planes
+// a dataset file holds and composite them on load, as the reference's training loop composites its target every iteration
+// (train_mesh_gaussian.py:89-91: gt * mask + bg * (1 - mask) on images that PILtoJittor divided by 255): g = rgb/255, m = mask/255,
+// y = g*m + bg[c]*(1 - m), each operation rounded to float32 on its own and in this order, so that y has the bits the tensor expression
+// gives; without a mask y = g.
+template <bool HAS_MASK>
+struct U8Target {
+  const unsigned char* __restrict__ rgb;     // [3,H,W]
+  const unsigned char* __restrict__ mask;    // [Cm,H,W] (HAS_MASK)
+  size_t mask_stride;                        // elements between the mask planes of two channels (0: one shared plane)
+  float bgc;                                 // background[channel]
+  __device__ __forceinline__ float load(size_t p, size_t off, int z) const {
+#pragma clang fp contract(off)
+    // u / 255.0f is a true (correctly rounded) division: multiplying by 1/255.0f differs from it for 126 of the 256 values.
+    // Bytes are fetched one per lane (global_load_ubyte): a row segment of the 42-wide halo tile starts at any byte address, and
+    // consecutive lanes read consecutive bytes of it.
+    float y = (float)rgb[p] / 255.0f;
+    if (HAS_MASK) {
+      const float m = (float)mask[(size_t)z * mask_stride + off] / 255.0f;
+      const float t1 = y * m;
+      const float t2 = 1.0f - m;
+      const float t3 = bgc * t2;
+      y = t1 + t3;
+    }
+    // The value leaves as an opaque register, as a loaded float is: which products of the body the compiler fuses or packs must not
+    // depend on how the target was made (the float kernels leave that to the compiler, and bit-identity with them is the contract).
+    asm volatile("" : "+v"(y));
+    return y;
+  }
+};
+#define LS_U8_BEGIN const U8Target<HAS_MASK> tgt{rgb, mask, mask_stride, HAS_MASK ? bg[blockIdx.z] : 0.f};
+#define LS_U8(p) tgt.load(p, (p) - plane, blockIdx.z)
+
 template <bool WRITE_MAPS>
 __global__ __launch_bounds__(LS_THREADS) void ssim_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
                                                               int H, int W, LossWindow win, float* __restrict__ d_mu1,
                                                               float* __restrict__ d_e11, float* __restrict__ d_e12,
                                                               float* __restrict__ partial) {
-  // Quantities travel in PAIRS - (x, y), (xx, yy), then xy alone - so that the 11-tap sums run on the packed-f32 pipe (v_pk_fma_f32:
-  // two of them per issue slot): three instructions per tap and output instead of five, and one 8-byte LDS access per pair.  Every sum
-  // keeps its own order of additions: results are bit-identical to the one-quantity-at-a-time form.
-  // LDS: the staged inputs and the horizontal sums share their memory (27.1 KiB per workgroup, five workgroups per CU instead of the
-  // three that 41 KiB allowed): the horizontal pass keeps its results in registers until every thread has read its inputs.
-  struct Horiz { float2 hb01[LS_SPAN][LS_TILE + 1], hb23[LS_SPAN][LS_TILE + 1]; float hb4[LS_SPAN][LS_TILE + 1]; };
-  __shared__ __attribute__((aligned(16))) char lds_raw[sizeof(Horiz)];
-  static_assert(sizeof(float2) * LS_SPAN * (LS_SPAN + 1) <= sizeof(Horiz), "the staged inputs fit the horizontal sums' memory");
-  float2 (*sxy)[LS_SPAN + 1] = reinterpret_cast<float2 (*)[LS_SPAN + 1]>(lds_raw);          // staged (image, target) with the halo
-  Horiz& hz = *reinterpret_cast<Horiz*>(lds_raw);                  // horizontal sums of (x, y), (xx, yy) and xy
-  __shared__ float red[4];
-  const int tid = threadIdx.x;
-  const int ox = blockIdx.x * LS_TILE, oy = blockIdx.y * LS_TILE;
-  const size_t plane = (size_t)blockIdx.z * H * W;
-  for (int i = tid; i < LS_SPAN * LS_SPAN; i += LS_THREADS) {
-    const int r = i / LS_SPAN, c = i - r * LS_SPAN;
-    const int gx = ox + c - LS_HALO, gy = oy + r - LS_HALO;
-    const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;          // zero padding (conv2d padding = 5)
-    const size_t p = plane + (size_t)(in ? gy : 0) * W + (in ? gx : 0);
-    sxy[r][c] = make_float2(in ? img1[p] : 0.f, in ? img2[p] : 0.f);
-  }
-  __syncthreads();
-  // horizontal taps: one work item = 4 adjacent output columns of one row (14 staged values feed 4 x 11 taps);
-  // consecutive lanes take consecutive rows (row stride 43 pairs: conflict-free)
-  constexpr int HITEMS = LS_SPAN * (LS_TILE / 4), HPASS = (HITEMS + LS_THREADS - 1) / LS_THREADS;     // 336 items, 2 passes
-  lv2f h01[HPASS][4], h23[HPASS][4];
-  float h4[HPASS][4];
-#pragma unroll
-  for (int ps = 0; ps < HPASS; ps++) {
-    const int i = tid + ps * LS_THREADS;
-    if (i < HITEMS) {
-      const int r = i % LS_SPAN, c0 = (i / LS_SPAN) * 4;
-      lv2f p0[14], p1[14];
-      float xy[14];
-#pragma unroll
-      for (int k = 0; k < 14; k++) {
-        const float2 v = sxy[r][c0 + k];
-        p0[k] = lv2f{v.x, v.y};
-        p1[k] = p0[k] * p0[k];
-        xy[k] = v.x * v.y;
-      }
-#pragma unroll
-      for (int o = 0; o < 4; o++) {
-        lv2f a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
-        float a4 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-          const float w = win.w[k];
-          const lv2f ww = {w, w};
-          a01 = ww * p0[o + k] + a01; a23 = ww * p1[o + k] + a23; a4 += w * xy[o + k];
-        }
-        h01[ps][o] = a01; h23[ps][o] = a23; h4[ps][o] = a4;
-      }
-    }
-  }
-  // the thread's own four pixels (L1 term) before the staged inputs are overwritten
-  float2 own[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) own[j] = sxy[(tid >> 5) * 4 + j + LS_HALO][(tid & 31) + LS_HALO];
-  __syncthreads();
-#pragma unroll
-  for (int ps = 0; ps < HPASS; ps++) {
-    const int i = tid + ps * LS_THREADS;
-    if (i < HITEMS) {
-      const int r = i % LS_SPAN, c0 = (i / LS_SPAN) * 4;
-#pragma unroll
-      for (int o = 0; o < 4; o++) {
-        hz.hb01[r][c0 + o] = make_float2(h01[ps][o].x, h01[ps][o].y); hz.hb23[r][c0 + o] = make_float2(h23[ps][o].x, h23[ps][o].y);
-        hz.hb4[r][c0 + o] = h4[ps][o];
-      }
-    }
-  }
-  __syncthreads();
-  const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-  const int c = tid & 31;
-  float s_sum = 0.f, l1_sum = 0.f;
-  // vertical taps: a thread owns 4 adjacent rows of one column (14 values per quantity feed 4 x 11 taps)
-  float vq[5][4];
-  {
-    lv2f c01[14], c23[14];
-    float c4[14];
-#pragma unroll
-    for (int k = 0; k < 14; k++) {
-      const float2 u = hz.hb01[(tid >> 5) * 4 + k][c], v = hz.hb23[(tid >> 5) * 4 + k][c];
-      c01[k] = lv2f{u.x, u.y}; c23[k] = lv2f{v.x, v.y}; c4[k] = hz.hb4[(tid >> 5) * 4 + k][c];
-    }
-#pragma unroll
-    for (int o = 0; o < 4; o++) {
-      lv2f a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
-      float a4 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 11; k++) {
-        const float w = win.w[k];
-        const lv2f ww = {w, w};
-        a01 = ww * c01[o + k] + a01; a23 = ww * c23[o + k] + a23; a4 += w * c4[o + k];
-      }
-      vq[0][o] = a01.x; vq[1][o] = a01.y; vq[2][o] = a23.x; vq[3][o] = a23.y; vq[4][o] = a4;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const int r = (tid >> 5) * 4 + j;
-    const float mu1 = vq[0][j], mu2 = vq[1][j], e11 = vq[2][j], e22 = vq[3][j], e12 = vq[4][j];
-    const int gx = ox + c, gy = oy + r;
-    if (gx < W && gy < H) {
-      const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-      const float s1 = e11 - mu1_sq, s2 = e22 - mu2_sq, s12 = e12 - mu12;
-      const float A1 = 2.f * mu12 + C1, A2 = 2.f * s12 + C2, B1 = mu1_sq + mu2_sq + C1, B2 = s1 + s2 + C2;
-      const float inv_b1 = 1.0f / B1, inv_b2 = 1.0f / B2;
-      const float S = (A1 * A2) * (inv_b1 * inv_b2);
-      s_sum += S;
-      l1_sum += fabsf(own[j].x - own[j].y);
-      if (WRITE_MAPS) {
-        const size_t p = plane + (size_t)gy * W + gx;
-        // S as a function of (mu1, E[xx], E[xy]) with sigma1^2 = E[xx] - mu1^2, sigma12 = E[xy] - mu1 mu2
-        const float dS_ds1 = -S * inv_b2;                       // = dS/dE[xx]
-        const float dS_ds12 = 2.f * A1 * (inv_b1 * inv_b2);     // = dS/dE[xy]
-        d_mu1[p] = 2.f * mu2 * A2 * (inv_b1 * inv_b2) - 2.f * mu1 * S * inv_b1 - 2.f * mu1 * dS_ds1 - mu2 * dS_ds12;
-        d_e11[p] = dS_ds1;
-        d_e12[p] = dS_ds12;
-      }
-    }
-  }
-  const float ts = block_sum(s_sum, red);
-  const float tl = block_sum(l1_sum, red);
-  if (tid == 0) {
-    const size_t b = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partial[2 * b] = ts;
-    partial[2 * b + 1] = tl;
-  }
+#define LS_TARGET_BEGIN
+#define LS_TARGET(p) img2[p]
+#include "gm_ssim_fwd_body.inc"
+#undef LS_TARGET_BEGIN
+#undef LS_TARGET
+}
+
+template <bool WRITE_MAPS, bool HAS_MASK>
+__global__ __launch_bounds__(LS_THREADS) void ssim_fwd_u8_kernel(const float* __restrict__ img1, const unsigned char* __restrict__ rgb,
+                                                                 const unsigned char* __restrict__ mask, size_t mask_stride,
+                                                                 const float* __restrict__ bg, int H, int W, LossWindow win,
+                                                                 float* __restrict__ d_mu1, float* __restrict__ d_e11,
+                                                                 float* __restrict__ d_e12, float* __restrict__ partial) {
+#define LS_TARGET_BEGIN LS_U8_BEGIN
+#define LS_TARGET(p) LS_U8(p)
+#include "gm_ssim_fwd_body.inc"
+#undef LS_TARGET_BEGIN
+#undef LS_TARGET
 }
 
 __global__ __launch_bounds__(LS_THREADS) void ssim_bwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
@@ -186,77 +111,33 @@ __global__ __launch_bounds__(LS_THREADS) void ssim_bwd_kernel(const float* __res
                                                               const float* __restrict__ g_ssim /*[planes]*/,
                                                               const float* __restrict__ g_l1 /*[1] or null*/,
                                                               float* __restrict__ dL_dimg1) {
-  // (dS/dmu1, dS/dE[xx]) travel as a pair, dS/dE[xy] alone: packed-f32 sums as in ssim_fwd_kernel
-  __shared__ float2 sm01[LS_SPAN][LS_SPAN + 1];
-  __shared__ float sm2[LS_SPAN][LS_SPAN + 1];
-  __shared__ float2 hb01[LS_SPAN][LS_TILE + 1];
-  __shared__ float hb2[LS_SPAN][LS_TILE + 1];
-  const int tid = threadIdx.x;
-  const int ox = blockIdx.x * LS_TILE, oy = blockIdx.y * LS_TILE;
-  const size_t plane = (size_t)blockIdx.z * H * W;
-  for (int i = tid; i < LS_SPAN * LS_SPAN; i += LS_THREADS) {
-    const int r = i / LS_SPAN, c = i - r * LS_SPAN;
-    const int gx = ox + c - LS_HALO, gy = oy + r - LS_HALO;
-    const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;          // no ssim-map pixel outside the image
-    const size_t p = plane + (size_t)(in ? gy : 0) * W + (in ? gx : 0);
-    sm01[r][c] = make_float2(in ? d_mu1[p] : 0.f, in ? d_e11[p] : 0.f);
-    sm2[r][c] = in ? d_e12[p] : 0.f;
+#define LS_TARGET_BEGIN
+#define LS_TARGET_PIXEL(p, j) img2[p]
+#include "gm_ssim_bwd_body.inc"
+#undef LS_TARGET_BEGIN
+#undef LS_TARGET_PIXEL
+}
+
+template <bool HAS_MASK>
+__global__ __launch_bounds__(LS_THREADS) void ssim_bwd_u8_kernel(const float* __restrict__ img1, const unsigned char* __restrict__ rgb,
+                                                                 const unsigned char* __restrict__ mask, size_t mask_stride,
+                                                                 const float* __restrict__ bg, const float* __restrict__ d_mu1,
+                                                                 const float* __restrict__ d_e11, const float* __restrict__ d_e12, int H,
+                                                                 int W, LossWindow win, const float* __restrict__ g_ssim,
+                                                                 const float* __restrict__ g_l1, float* __restrict__ dL_dimg1) {
+  // the thread's four target pixels are made before the vertical taps and enter the final sum as plain registers
+#define LS_TARGET_BEGIN                                                                          \
+  LS_U8_BEGIN                                                                                    \
+  float yv[4];                                                                                   \
+  _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                \
+    const int gx = ox + (tid & 31), gy = oy + (tid >> 5) * 4 + j;                                \
+    const size_t p = plane + (size_t)(gy < H ? gy : 0) * W + (gx < W ? gx : 0);                  \
+    yv[j] = LS_U8(p);                                                                            \
   }
-  __syncthreads();
-  for (int i = tid; i < LS_SPAN * (LS_TILE / 4); i += LS_THREADS) {      // see ssim_fwd_kernel
-    const int r = i % LS_SPAN, c0 = (i / LS_SPAN) * 4;
-    lv2f v01[14];
-    float v2[14];
-#pragma unroll
-    for (int k = 0; k < 14; k++) { const float2 u = sm01[r][c0 + k]; v01[k] = lv2f{u.x, u.y}; v2[k] = sm2[r][c0 + k]; }
-#pragma unroll
-    for (int o = 0; o < 4; o++) {
-      lv2f a01 = {0.f, 0.f};
-      float a2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 11; k++) {
-        const float w = win.w[k];
-        const lv2f ww = {w, w};
-        a01 = ww * v01[o + k] + a01; a2 += w * v2[o + k];
-      }
-      hb01[r][c0 + o] = make_float2(a01.x, a01.y); hb2[r][c0 + o] = a2;
-    }
-  }
-  __syncthreads();
-  const float gs = g_ssim[blockIdx.z];
-  const float gl = g_l1 ? g_l1[0] : 0.f;
-  const int c = tid & 31;
-  float vq[3][4];
-  {
-    lv2f c01[14];
-    float c2[14];
-#pragma unroll
-    for (int k = 0; k < 14; k++) { const float2 u = hb01[(tid >> 5) * 4 + k][c]; c01[k] = lv2f{u.x, u.y}; c2[k] = hb2[(tid >> 5) * 4 + k][c]; }
-#pragma unroll
-    for (int o = 0; o < 4; o++) {
-      lv2f a01 = {0.f, 0.f};
-      float a2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 11; k++) {
-        const float w = win.w[k];
-        const lv2f ww = {w, w};
-        a01 = ww * c01[o + k] + a01; a2 += w * c2[o + k];
-      }
-      vq[0][o] = a01.x; vq[1][o] = a01.y; vq[2][o] = a2;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const int r = (tid >> 5) * 4 + j;
-    const float A = vq[0][j], B = vq[1][j], Cc = vq[2][j];
-    const int gx = ox + c, gy = oy + r;
-    if (gx < W && gy < H) {
-      const size_t p = plane + (size_t)gy * W + gx;
-      const float x = img1[p], y = img2[p], d = x - y;
-      const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-      dL_dimg1[p] = gs * (A + 2.f * x * B + y * Cc) + gl * sgn;
-    }
-  }
+#define LS_TARGET_PIXEL(p, j) yv[j]
+#include "gm_ssim_bwd_body.inc"
+#undef LS_TARGET_BEGIN
+#undef LS_TARGET_PIXEL
 }
 
 // value = offset + c_ssim * sum partial[.][0] + c_l1 * sum partial[.][1], summed in double by one workgroup: the fused loss's scalar
@@ -303,6 +184,35 @@ int launch_ssim_bwd(const float* img1, const float* img2, const float* d_mu1, co
   const dim3 grid((W + LS_TILE - 1) / LS_TILE, (H + LS_TILE - 1) / LS_TILE, planes);
   hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(LS_THREADS), 0, s, img1, img2, d_mu1, d_e11, d_e12, H, W, make_window(), g_ssim, g_l1,
                      dL_dimg1);
+  GM_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_ssim_fwd_u8(const float* img1, const unsigned char* rgb, const unsigned char* mask, size_t mask_stride, const float* bg, int H,
+                       int W, float* d_mu1, float* d_e11, float* d_e12, float* partial, hipStream_t s) {
+  StageScope sc(ST_LOSS, s);
+  const dim3 grid((W + LS_TILE - 1) / LS_TILE, (H + LS_TILE - 1) / LS_TILE, 3);
+  const LossWindow win = make_window();
+#define LS_FWD_U8(MAPS, MASK) \
+  hipLaunchKernelGGL((ssim_fwd_u8_kernel<MAPS, MASK>), grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, bg, H, W, win, d_mu1, d_e11, d_e12, partial)
+  if (d_mu1) { if (mask) LS_FWD_U8(true, true); else LS_FWD_U8(true, false); }
+  else { if (mask) LS_FWD_U8(false, true); else LS_FWD_U8(false, false); }
+#undef LS_FWD_U8
+  GM_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_ssim_bwd_u8(const float* img1, const unsigned char* rgb, const unsigned char* mask, size_t mask_stride, const float* bg,
+                       const float* d_mu1, const float* d_e11, const float* d_e12, int H, int W, const float* g_ssim, const float* g_l1,
+                       float* dL_dimg1, hipStream_t s) {
+  StageScope sc(ST_LOSS_BWD, s);
+  const dim3 grid((W + LS_TILE - 1) / LS_TILE, (H + LS_TILE - 1) / LS_TILE, 3);
+  if (mask)
+    hipLaunchKernelGGL(ssim_bwd_u8_kernel<true>, grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, bg, d_mu1, d_e11, d_e12, H, W,
+                       make_window(), g_ssim, g_l1, dL_dimg1);
+  else
+    hipLaunchKernelGGL(ssim_bwd_u8_kernel<false>, grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, bg, d_mu1, d_e11, d_e12, H, W,
+                       make_window(), g_ssim, g_l1, dL_dimg1);
   GM_HIP(hipGetLastError());
   return 0;
 }

@@ -7,6 +7,10 @@
   photometric_loss(image, gt, lambda_dssim)         train_mesh_gaussian.py:92-94:
                                                     (1 - l) * l1_loss + l * (1 - ssim), one fused pass
 
+  photometric_loss_u8(image, gt, background, lambda_dssim)   the same loss against a dataset.GroundTruth: the 8-bit planes of the
+                                                    file, composited gt * mask + bg * (1 - mask) (train_mesh_gaussian.py:89-91) inside
+                                                    the kernels' own load (gm_ssim_fwd_u8 / gm_ssim_bwd_u8)
+
 ssim and photometric_loss run csrc/gm_loss.hip (gm_ssim_fwd / gm_ssim_bwd) and are differentiable with respect to
 the first image (the rendered one); the ground truth gets no gradient, as in the training loop.  There is no CPU path.
 """
@@ -142,6 +146,80 @@ class _Photometric(torch.autograd.Function):
 def photometric_loss(image, gt, lambda_dssim=0.2):
     """(1 - lambda) * l1_loss(image, gt) + lambda * (1 - ssim(image, gt)) in one forward and one backward kernel."""
     return _Photometric.apply(image, gt, float(lambda_dssim))
+
+
+def _u8_args(a, gt, background):
+    """pointers of a dataset.GroundTruth for gm_ssim_*_u8: (rgb, mask or None, mask plane stride, background or None, keep-alive list)"""
+    rgb, mask = gt.rgb, gt.mask
+    if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[0] != 3 or not rgb.is_contiguous():
+        raise ValueError("photometric_loss_u8: gt.rgb must be a contiguous uint8 [3,H,W] tensor")
+    if a.dim() != 3 or tuple(a.shape) != tuple(rgb.shape):
+        raise ValueError("photometric_loss_u8: image %s and ground truth %s differ in shape" % (tuple(a.shape), tuple(rgb.shape)))
+    if rgb.device != a.device:
+        raise ValueError("photometric_loss_u8: the ground truth is on %s, the image on %s" % (rgb.device, a.device))
+    if mask is None:
+        return rgb.data_ptr(), None, 0, None, [rgb]
+    if mask.dtype != torch.uint8 or mask.dim() != 3 or mask.shape[0] not in (1, 3) or tuple(mask.shape[1:]) != tuple(rgb.shape[1:]) or \
+            not mask.is_contiguous() or mask.device != a.device:
+        raise ValueError("photometric_loss_u8: gt.mask must be a contiguous uint8 [1,H,W] or [3,H,W] tensor on the image's device")
+    if background is None:
+        raise ValueError("photometric_loss_u8: a masked ground truth needs the background colour")
+    bg = background.detach().to(device=a.device, dtype=torch.float32).reshape(3).contiguous()      # (no copy for a device float32 [3])
+    stride = 0 if mask.shape[0] == 1 else mask.shape[1] * mask.shape[2]
+    return rgb.data_ptr(), mask.data_ptr(), stride, bg.data_ptr(), [rgb, mask, bg]
+
+
+class _PhotometricU8(torch.autograd.Function):
+    """_Photometric with the target read through gm_ssim_fwd_u8 / gm_ssim_bwd_u8: same partial sums, same derivative maps, same
+    combine - bit for bit _Photometric on gt.float_target(background)."""
+
+    @staticmethod
+    def forward(ctx, image, gt, background, lambda_dssim):
+        lib = _lib.lib()
+        if image.device.type != "cuda":
+            raise _lib.GmeshError("photometric_loss_u8 needs tensors on a HIP (cuda) device; there is no CPU path")
+        a = image.detach().contiguous().float()
+        rgb, mask, stride, bg, keep = _u8_args(a, gt, background)
+        H, W = a.shape[-2], a.shape[-1]
+        dev = a.device
+        want_grad = ctx.needs_input_grad[0]
+        n_part = int(lib.gm_ssim_partials(3, H, W))
+        partial = torch.empty((n_part, 2), dtype=torch.float32, device=dev)
+        maps = torch.empty((3,) + tuple(a.shape), dtype=torch.float32, device=dev) if want_grad else None
+        mp = [maps[i].data_ptr() for i in range(3)] if want_grad else [None, None, None]
+        lam, n = float(lambda_dssim), a.numel()
+        _, grad = _coefs(lam, n, 3, dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.gm_ssim_fwd_u8(a.data_ptr(), rgb, mask, stride, bg, 3, H, W, mp[0], mp[1], mp[2], partial.data_ptr(), stream))
+            _lib.check(lib.gm_loss_combine(partial.data_ptr(), n_part, -lam / n, (1.0 - lam) / n, lam, out.data_ptr(), stream))
+        ctx.shape, ctx.u8 = image.shape, (rgb, mask, stride, bg, keep)
+        ctx.partial = partial                    # (tests read the partial sums; a small tensor)
+        if maps is not None:
+            ctx.save_for_backward(a, maps, grad)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, maps, grad = ctx.saved_tensors
+        rgb, mask, stride, bg, _keep = ctx.u8
+        gv = grad * g.reshape(1)
+        g_ssim, g_l1 = gv[:3].contiguous(), gv[3:].contiguous()
+        out = torch.empty_like(a)
+        H, W = a.shape[-2], a.shape[-1]
+        with torch.cuda.device(a.device):
+            _lib.check(_lib.lib().gm_ssim_bwd_u8(a.data_ptr(), rgb, mask, stride, bg, maps[0].data_ptr(), maps[1].data_ptr(), maps[2].data_ptr(),
+                                                 3, H, W, g_ssim.data_ptr(), g_l1.data_ptr(), out.data_ptr(),
+                                                 torch.cuda.current_stream(a.device).cuda_stream))
+        return out.view(ctx.shape), None, None, None
+
+
+def photometric_loss_u8(image, gt, background=None, lambda_dssim=0.2):
+    """photometric_loss(image, gt.float_target(background), lambda_dssim), bit for bit, without the float target: `gt` is a
+    dataset.GroundTruth (uint8 rgb [3,H,W] and an optional uint8 mask [1 or 3,H,W] on the device), `background` a float [3] tensor
+    (on the device it stays there: a colour drawn per iteration costs no synchronisation).  Gradient to `image` only."""
+    return _PhotometricU8.apply(image, gt, background, float(lambda_dssim))
 
 
 def distance(point1, point2):

@@ -431,6 +431,69 @@ class MeshBoundGaussians(torch.nn.Module):
         self.max_sh_degree = self.active_sh_degree = sh_degree
         self.screenspace_points = torch.zeros_like(vertex1, requires_grad=True)
 
+    @staticmethod
+    def mesh_init_tensors(vertices, faces, sh_degree=3, generator=None):
+        """Host side of create_from_pcd (scene/mesh_based_gaussian_model.py:183-240): every tensor of the first model except the
+        scales, as CPU tensors - one Gaussian per face at barycentrics (1/3, 1/3, 1/3) and normal offset 0; r = mean edge length;
+        unit face normals with igl.per_face_normals' fallback (1, 0, 0) for a degenerate face; identity rotation; opacity
+        inverse_sigmoid(0.1); SH coefficient 0 = RGB2SH(u), u uniform in [0, 1) - `generator`: None for numpy's global stream (what the
+        reference draws from), or anything with .random(shape) (np.random.Generator / RandomState) - the other coefficients 0.
+        "centres" are the face centres whose distCUDA2 gives the scales."""
+        import numpy as np
+        from .compat.igl_subset import per_face_normals
+        vertices = np.asarray(vertices, np.float64)
+        faces = np.asarray(faces)
+        n = faces.shape[0]
+        f32 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32)
+        normal = f32(per_face_normals(vertices, faces, np.array([1.0, 0.0, 0.0])))
+        draw = np.random.random((n, 3)) if generator is None else generator.random((n, 3))
+        K = (sh_degree + 1) ** 2
+        features = torch.zeros((n, K, 3), dtype=torch.float32)
+        features[:, 0] = (f32(draw) - 0.5) / _SH_C0                               # RGB2SH, utils/sh_utils.py:114-115
+        v1, v2, v3 = (f32(vertices[faces[:, k]]) for k in range(3))
+        edge = lambda a, b: torch.linalg.vector_norm(a - b, dim=1).unsqueeze(1)
+        x = 0.1 * torch.ones((n, 1), dtype=torch.float32)
+        rots = torch.zeros((n, 4), dtype=torch.float32)
+        rots[:, 0] = 1
+        return dict(bc=torch.ones((n, 3), dtype=torch.float32) / 3, distance=torch.zeros((n, 1), dtype=torch.float32),
+                    features_dc=features[:, :1].contiguous(), features_rest=features[:, 1:].contiguous(), rotation=rots,
+                    opacity=torch.log(x / (1 - x)), vertex1=v1, vertex2=v2, vertex3=v3, normal=normal,
+                    r=(edge(v1, v2) + edge(v2, v3) + edge(v3, v1)) / 3, fid=torch.arange(n, dtype=torch.int32).unsqueeze(1),
+                    vertex_index=torch.as_tensor(faces.astype(np.int32)), v=f32(vertices), centres=(v1 + v2 + v3) / 3)
+
+    @classmethod
+    def create_from_mesh(cls, vertices, faces, sh_degree=3, generator=None, device="cuda"):
+        """The first model of a training run from the proxy mesh (io.read_obj): create_from_pcd (:183-240) - mesh_init_tensors on the
+        host, the scales log(sqrt(clamp(distCUDA2(face centres), 1e-7))) on all three axes on the device (there is no CPU path).  As
+        in the reference the model starts at SH degree 0 of `sh_degree`."""
+        from .simple_knn import distCUDA2
+        t = {k: v.to(device) for k, v in cls.mesh_init_tensors(vertices, faces, sh_degree, generator).items()}
+        dist2 = torch.clamp(distCUDA2(t["centres"]), min=0.0000001)
+        scaling = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)
+        m = cls(t["bc"], t["distance"], t["features_dc"], t["features_rest"], scaling, t["rotation"], t["opacity"], t["vertex1"], t["vertex2"],
+                t["vertex3"], t["normal"], t["r"], sh_degree=sh_degree, fid=t["fid"], vertex_index=t["vertex_index"], v=t["v"])
+        m.active_sh_degree = 0
+        return m
+
+    def ply_columns(self):
+        """The tensors save_ply (:305-330) writes, under io.save_mesh_gaussians' keys: x,y,z = get_xyz (the ACTIVATED position),
+        ca,cb,cc = the raw `_bc`, everything else raw (pre-activation) as well."""
+        a = lambda t: t.detach().cpu().numpy()
+        n = self._bc.shape[0]
+        feats = self.get_features.detach()
+        vi = self.vertex_index if self.vertex_index is not None else torch.zeros((n, 3))
+        return dict(xyz=a(self.get_xyz), normal=a(self.normal), bc=a(self._bc), v1=a(self.vertex1), v2=a(self.vertex2), v3=a(self.vertex3),
+                    distance=a(self._distance), vertex_index=a(vi).astype("float32"), radius=a(self.r).reshape(n, 1),
+                    fid=a(self.fid).reshape(n, 1).astype("float32"), features_dc=a(feats[:, :1]), features_rest=a(feats[:, 1:]),
+                    opacity=a(self._opacity), scaling=a(self._scaling), rotation=a(self._rotation))
+
+    def save_ply(self, path):
+        """save_ply (:304-330): point_cloud.ply in the reference's column layout (io.save_mesh_gaussians); folders are created."""
+        import os
+        from . import io as gio
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        gio.save_mesh_gaussians(path, self.ply_columns())
+
     @property
     def get_number(self):
         return self._bc.shape[0]

@@ -16,7 +16,8 @@ from types import SimpleNamespace
 
 import torch
 
-from .loss import mesh_restrict_loss, photometric_loss
+from .dataset import GroundTruth
+from .loss import mesh_restrict_loss, photometric_loss, photometric_loss_u8
 from .renderer import render
 
 
@@ -326,7 +327,10 @@ class Trainer:
         import contextlib
         with (ss if ss is not None else contextlib.nullcontext()):
             pkg = render(camera, g, self.pipe, background, bg_gaussian=self.bg_gaussian)
-            loss = photometric_loss(pkg["render"], gt_image, self.opt.lambda_dssim)
+            if isinstance(gt_image, GroundTruth):    # the view's 8-bit planes, composited over `background` inside the loss kernels
+                loss = photometric_loss_u8(pkg["render"], gt_image, background, self.opt.lambda_dssim)
+            else:
+                loss = photometric_loss(pkg["render"], gt_image, self.opt.lambda_dssim)
             if self.opt.alpha_mrloss:
                 mr = pkg.get("mesh_restrict_loss")
                 loss = loss + (mr if mr is not None else
@@ -424,7 +428,8 @@ class Trainer:
         self.g.oneupSHdegree()
 
     def step(self, camera, gt_image, background, stats=True, densify=None, optimizer_step=True):
-        """One iteration; returns (loss tensor, render package).  Host synchronisation: the rasterizer's instance-count
+        """One iteration; returns (loss tensor, render package).  gt_image: a float [3,H,W] tensor, or a dataset.GroundTruth - then the
+        target is gt * mask + background * (1 - mask) (train_mesh_gaussian.py:89-91), composited in the loss kernels' own load.  Host synchronisation: the rasterizer's instance-count
         read-back, or with sync_free only the (long completed) status words of the forward.
         stats=False: leave the densification statistics alone (iterations past densify_until_iter).
         densify: None, or the argument tuple of densify_and_prune, applied after this iteration's statistics.

@@ -448,6 +448,21 @@ int gm_ssim_bwd(const float* img1, const float* img2, const float* dS_dmu1, cons
                 int H, int W, const float* g_ssim, const float* g_l1, float* dL_dimg1, void* stream);
 int gm_loss_combine(const float* partial, int64_t n_partials, double c_ssim, double c_l1, double offset, float* out, void* stream);
 
+/* The same two kernels with the ground truth as the 8-bit planes a dataset holds, composited while it is loaded
+ * (train_mesh_gaussian.py:89-91: gt * mask + bg * (1 - mask), every iteration, with a fresh random bg in the --is_exist_bg mode).
+ * rgb: uint8 [3,H,W] planar (planes must be 3).  mask: uint8 [Cm,H,W] or NULL; mask_plane_stride = elements between the mask
+ * planes of two channels: 0 for one shared plane (Cm = 1), H*W (or more) for Cm = 3.  background: DEVICE float[3] (needed with a
+ * mask): a colour drawn on the device never crosses the host.
+ * Target of plane c at a pixel, float32, every operation rounded on its own, in this order - the bits the tensor expression gives:
+ *   g = rgb/255, m = mask/255 (correctly rounded quotients), t1 = g*m, t2 = 1 - m, t3 = background[c]*t2, y = t1 + t3;  no mask: y = g.
+ * Everything else - partial layout, derivative maps, g_ssim / g_l1 - as gm_ssim_fwd / gm_ssim_bwd, whose results on the float
+ * image y these reproduce bit for bit. */
+int gm_ssim_fwd_u8(const float* img1, const uint8_t* rgb, const uint8_t* mask, int64_t mask_plane_stride, const float* background,
+                   int planes, int H, int W, float* dS_dmu1, float* dS_dE11, float* dS_dE12, float* partial, void* stream);
+int gm_ssim_bwd_u8(const float* img1, const uint8_t* rgb, const uint8_t* mask, int64_t mask_plane_stride, const float* background,
+                   const float* dS_dmu1, const float* dS_dE11, const float* dS_dE12, int planes, int H, int W, const float* g_ssim,
+                   const float* g_l1, float* dL_dimg1, void* stream);
+
 /* Training-loop fusions around the rasterizer ("MeshBasedGaussianModel.get_xyz ... fused into the op").
  * gm_mesh_activate_fwd: raw parameters -> rasterizer inputs in one pass, replacing the Jittor elementwise chains of
  *   get_xyz = softmax(bc).(v1,v2,v3) + alpha r (sigmoid(dist) - 0.5) normal   (scene/mesh_based_gaussian_model.py:138-152)
