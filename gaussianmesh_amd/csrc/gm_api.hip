@@ -67,12 +67,23 @@ static void drain_profile() {
   g_pending.clear();
 }
 
+// the emission record keeps a tile rectangle in 12 bits per field (gm_common.h, bin_pack): a wider or taller grid would spill into the count
+static int check_tile_grid(int W, int H) {
+  const TileGrid tg(W, H, 0);
+  if (tg.gx > 4095 || tg.gy > 4095) {
+    set_error("%dx%d is a grid of %d x %d 16-px tiles; the limit is 4095 x 4095 tiles (65520 pixels a side)", W, H, tg.gx, tg.gy);
+    return GM_ERR_INVALID_ARG;
+  }
+  return 0;
+}
+
 static int check_raster_args(const RasterArgs& a) {
   if (a.P < 0 || a.W <= 0 || a.H <= 0) { set_error("invalid sizes P=%d W=%d H=%d", a.P, a.W, a.H); return GM_ERR_INVALID_ARG; }
   if (TileGrid(a.W, a.H, a.tile_cull).ptiles > 65536) {
     set_error("%dx%d has more than 65536 list tiles under emission policy %d; use policy 2 or 3", a.W, a.H, a.tile_cull);
     return GM_ERR_INVALID_ARG;
   }
+  if (int rc = check_tile_grid(a.W, a.H)) return rc;
   if (a.P == 0) return 0;                       // empty cloud: every per-Gaussian pointer may be null
   if ((a.shs == nullptr) == (a.colors_precomp == nullptr)) {
     set_error("provide exactly one of shs / colors_precomp"); return GM_ERR_INVALID_ARG;
@@ -192,6 +203,7 @@ int gm_forward_0_deformed_stream_async(int emission_policy, void* geom_buffer, i
   const bool cov6 = (flags & GM_STREAM_COV6) != 0;
   if (direct && (!depth_slab || !depth_plan)) { set_error("gm_forward_0_deformed_stream: direct placement needs depth_slab and depth_plan"); return GM_ERR_INVALID_ARG; }
   if (P < 0 || width <= 0 || height <= 0) { set_error("invalid sizes P=%d W=%d H=%d", P, width, height); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_tile_grid(width, height)) return rc;
   if (P == 0) { if (num_rendered_host) *num_rendered_host = 0; return GM_OK; }
   if (deg < 0 || deg > 3 || M != 16) { set_error("gm_forward_0_deformed: needs SH rows of M == 16 coefficients, degree 0..3"); return GM_ERR_INVALID_ARG; }
   if (!geom_buffer || !tri || !w || !packed || !cov || !pos || !shs || !opacities || !viewmatrix || !projmatrix || !cam_pos) {
@@ -229,6 +241,7 @@ static int forward_1_impl(int emission_policy, void* geom_buffer, void* binning_
     set_error("GM_FWD_EXACT_EXPONENT is for a forward a backward pass follows: not together with GM_FWD_IMAGE_ONLY"); return GM_ERR_INVALID_ARG;
   }
   if (P < 0 || width <= 0 || height <= 0) { set_error("invalid sizes P=%d W=%d H=%d", P, width, height); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_tile_grid(width, height)) return rc;
   if (!image_buffer || !out_color || !background) { set_error("null image_buffer / out_color / background"); return GM_ERR_INVALID_ARG; }
   const bool device_count = num_rendered < 0;          // sync-free: the count stays on the device, bounded by the capacity
   const int64_t cap = device_count ? binning_capacity : (int64_t)num_rendered;
@@ -356,6 +369,7 @@ static int forward_batch_impl(const char* who, int emission_policy, int K, const
     set_error("%s: null required input", who); return GM_ERR_INVALID_ARG;
   }
   if (binning_capacity <= 0) { set_error("%s: binning_capacity must be positive (sync-free second half)", who); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_tile_grid(width, height)) return rc;
   const TileGrid tg(width, height, emission_policy);
   if (tg.ptiles > (1 << GM_BUCKET_BITS)) {
     set_error("%s: %dx%d has %d list tiles under policy %d; a batch needs the one-pass tile sort (<= 2048)", who, width, height, tg.ptiles, emission_policy);
@@ -624,6 +638,8 @@ void* gm_geom_field(void* geom_buffer, int P, const char* name) {
   if (!strcmp(name, "order")) return g.order;
   if (!strcmp(name, "bucket_start")) return g.bucket_start;
   if (!strcmp(name, "counters")) return g.counters;
+  if (!strcmp(name, "bmap")) return g.bmap;
+  if (!strcmp(name, "dmap")) return g.dmap;
   return nullptr;
 }
 void* gm_image_field(void* image_buffer, int W, int H, const char* name) {

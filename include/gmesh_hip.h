@@ -75,7 +75,10 @@ size_t gm_binning_bytes(int64_t num_rendered);
  * per-Gaussian preprocess (cull, cov3D, EWA cov2D, conic, radius, tile rect, SH->RGB) and the
  * count of (Gaussian, tile) instances.  Performs the ONE host synchronisation of a forward pass
  * (reference: cudaMemcpy D2H at rasterizer_impl.cu:411) and stores the count in *num_rendered.
- * radii (int32 [P], may be NULL) receives the screen radius (0 = culled). */
+ * radii (int32 [P], may be NULL) receives the screen radius (0 = culled).
+ * Frame sizes (every forward entry point, the batched ones included; refused on the arguments alone): at most 65536 list tiles under
+ * the emission policy (2048 for a batch), and under EVERY policy a grid of at most 4095 x 4095 16-px tiles (65520 pixels a side) - a
+ * Gaussian's tile rectangle travels in 12 bits per field. */
 int gm_forward_0(void* geom_buffer, int P, int D, int M, const float* background, int width, int height,
                  const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
                  const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
@@ -177,7 +180,9 @@ int gm_mark_visible(int P, const float* means3D, const float* viewmatrix, const 
  *            is given none either - pass the forward's array otherwise), "tiles_touched" uint32[P] (gm_forward_0_deformed_async
  *            fills it only for rectangles of 65535 instances or more: the count rides in the emission record), "cov3D" float[P][6],
  *            "clamped" uint8[P] (bit ch set = channel ch clamped), "order" uint32[V] (ids of the V visible Gaussians
- *            in (depth, id) order; V = "bucket_start"[2048]), "bucket_start" uint32[2049]
+ *            in (depth, id) order; V = "bucket_start"[2048]), "bucket_start" uint32[2049], "counters" uint32[32], and the depth-bucket
+ *            table of the frame, for tests that ask which route the ordering took: "dmap" uint32[2048] (coarse bin key >> 20 ->
+ *            first bucket << 16 | buckets), "bmap" uint32[2048][2] (bucket -> first key, bits of the key range; partition path only)
  *   image:   "final_T" float[H*W], "n_contrib" uint32[H*W], "ranges" uint32[T][2], "tile_order" uint32[T] (the forward blend's
  *            dispatch order: a permutation of the list tiles)
  *   binning: "pairs" uint32[R][2] = (list tile id | child mask << 16, Gaussian id) per instance, sorted by tile then

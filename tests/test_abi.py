@@ -51,6 +51,52 @@ def test_argument_validation_happens_before_any_gpu_work():
     assert l.gm_sh_colors(5, 4, 16, one, one, None, one, one, None) == 1
 
 
+def test_grids_wider_than_the_emission_record_are_refused():
+    """The emission record keeps a Gaussian's tile rectangle in 12 bits per field (gm_common.h, bin_pack): 4095 x 4095 tiles of 16 px.  A
+    65536 x 16 frame has 4096 list tiles - far below the 65536 the tile sort takes - but a splat across its width would carry a width of
+    0x1000 into the record's count.  Every entry point that refuses too many list tiles refuses such a grid, on the arguments alone:
+    65520 pixels (4095 tiles) pass the check - the call fails on the NEXT rule - and 65521 do not."""
+    from gaussianmesh_amd import _lib
+    l = _lib.lib()
+    R = C.c_int(-1)
+    one = 1
+    f0 = lambda W, H, pol=0: l.gm_forward_0_async(pol, one, 10, 3, 16, one, W, H, one, one, one, one, one, 1.0, one, None, one, one, one, 0.5, 0.5, 0,
+                                                  None, 0, None, None, None)              # (shs AND colors_precomp: the rule after the grid's)
+    for pol in (0, 1, 2, 3):
+        for W, H in ((65520, 16), (16, 65520)):
+            assert f0(W, H, pol) == 1 and b"exactly one of shs / colors_precomp" in l.gm_last_error(), (pol, W, H)
+        for W, H in ((65521, 16), (16, 65521), (65536, 16)):
+            assert f0(W, H, pol) == 1 and b"4095 x 4095 tiles" in l.gm_last_error(), (pol, W, H, l.gm_last_error())
+    rc = l.gm_forward_0(one, 10, 3, 16, one, 65521, 16, one, one, None, one, one, 1.0, one, None, one, one, one, 0.5, 0.5, 0, None, 0, None, C.byref(R))
+    assert rc == 1 and b"4095 x 4095 tiles" in l.gm_last_error()
+    # the deformed first half and the second half
+    fd = lambda W, H: l.gm_forward_0_deformed_stream_async(0, None, 10, 3, 16, W, H, one, one, one, one, one, one, one, one, one, one, 0.5, 0.5, None, None, None,
+                                                           None, 0, None, None, None, None, None, 0)
+    assert fd(65520, 16) == 1 and b"null required input" in l.gm_last_error()
+    assert fd(65521, 16) == 1 and b"4095 x 4095 tiles" in l.gm_last_error()
+    assert fd(16, 65521) == 1 and b"4095 x 4095 tiles" in l.gm_last_error()
+    f1 = lambda W, H: l.gm_forward_1_geom(0, None, one, one, 10, 5, 0, one, W, H, one, 0, None, None, 0, None)
+    assert f1(65520, 16) == 1 and b"null scratch buffer" in l.gm_last_error()
+    assert f1(65521, 16) == 1 and b"4095 x 4095 tiles" in l.gm_last_error()
+    assert f1(16, 65521) == 1 and b"4095 x 4095 tiles" in l.gm_last_error()
+    # the batch entry points take at most 2048 list tiles UNDER THE EMISSION POLICY: with 32- and 64-px parent tiles a 65536 x 16 frame
+    # (policy 2: 2048 parents) or a 131072 x 16 one (policy 3) has few enough, on a grid the record cannot hold
+    K = 2
+    frames = (_lib.BatchFrame * K)()
+    rows, masks = (C.c_int * 3)(0, 5, 10), (C.c_uint * K)(0, 0)
+    batch = lambda W, H, pol: l.gm_forward_deformed_batch_async(pol, K, frames, 10, 3, 16, W, H, one, one, one, one, one, one, one, 1000, 1, None, 0, None)
+    aux = lambda W, H, pol: l.gm_forward_deformed_batch_aux_async(pol, K, frames, 10, 3, 16, W, H, one, one, one, one, one, one, one, 1000, 1, None, 0, None,
+                                                                  (C.c_void_p * K)(4096, 8192), (C.c_void_p * K)(12288, 16384))
+    scene = lambda W, H, pol: l.gm_forward_scene_batch_async(pol, K, frames, 10, 3, 16, W, H, 2, rows, masks, one, one, one, one, one, one, one, one, one, 1000, 1,
+                                                             None, 0, None)
+    for fn in (batch, aux, scene):
+        for W, H, pol in ((65520, 16, 2), (16, 65520, 2), (65520, 16, 3)):
+            assert fn(W, H, pol) == 1 and b"4095 x 4095 tiles" not in l.gm_last_error() and b"list tiles" not in l.gm_last_error(), l.gm_last_error()
+        for W, H, pol in ((65536, 16, 2), (16, 65536, 2), (65521, 16, 2), (131072, 16, 3), (65521, 16, 3)):
+            assert fn(W, H, pol) == 1 and b"4095 x 4095 tiles" in l.gm_last_error(), (W, H, pol, l.gm_last_error())
+    assert batch(65520, 16, 2) == 1 and b"null pointer" in l.gm_last_error()          # (the rule after the frame size's: frames of nulls)
+
+
 def test_round6_entry_points_validate_before_any_gpu_work():
     """gm_forward_deformed_batch_async / gm_mesh_rs_packed_batch / gm_backward_sh_step (ABI 3): every refusal below is decided on the
     arguments alone - no device is touched, so it holds on a box without one."""

@@ -923,18 +923,11 @@ def test_emission_policies_agree_on_random_scenes(seed):
         assert np.array_equal(cu["color"], ref["color"]), mode
 
 
-@pytest.mark.parametrize("case", ["equal_depths", "depth_pileup", "many_tiles", "tiny", "twenty_octaves", "object_and_background"])
-def test_ordering_paths(oracle, case):
-    """gm_bucket.hip's special paths against the oracle's (tile, depth, id) stable sort, lists bit-exact:
-    equal_depths: every Gaussian at the same view depth (one bucket, no low bits: order by id, bucket larger than the LDS);
-    depth_pileup: 12k Gaussians inside a few ulps of one depth plus a sparse spread (one overfull bucket WITH low bits: the
-                  global-memory slow path of bucket_sort_kernel, several passes);
-    many_tiles:   more than 2048 list tiles (two 8-bit tile passes + tile_ranges_kernel), reference and default policy;
-    tiny:         3 Gaussians;
-    twenty_octaves: depths from 0.3 to 3e5 around the optical axis - 160 sparsely filled coarse depth bins;
-    object_and_background: a dense cluster in a tenth of a depth unit in front of a sparse background and behind a few
-                  floaters (the proportional bucket table: most buckets go to the cluster)."""
-    from gpu_utils import forward_state
+ORDERING_CASES = ["equal_depths", "depth_pileup", "many_tiles", "tiny", "twenty_octaves", "object_and_background"]
+
+
+def ordering_scene(case):
+    """the scene of test_ordering_paths[case] -> (scene, camera, emission policies, W, H)"""
     from gaussianmesh_amd import scenes
     rng = np.random.default_rng(5)
     W, H = 320, 200
@@ -973,6 +966,27 @@ def test_ordering_paths(oracle, case):
         sc = scenes.make_cloud(3, seed=1, scale_lo=0.05, scale_hi=0.3)
         cam = scenes.orbit_camera(0, 4, W, H, radius=5.0)
         modes = (0, 2)
+    return sc, cam, modes, W, H
+
+
+@pytest.mark.parametrize("case", ORDERING_CASES)
+def test_ordering_paths(oracle, case):
+    """gm_bucket.hip's special paths against the oracle's (tile, depth, id) stable sort, lists bit-exact:
+    equal_depths: every Gaussian at the same view depth: the visible ones (about 13 400) land in ONE bucket, larger than the LDS - the
+                  global-memory slow path of bucket_sort_kernel.  The bucket is one of the 1792 sub-ranges of its coarse bin and has 10 low
+                  bits (two passes over all-equal digits), not none; the order comes out by id;
+    depth_pileup: 12k Gaussians inside a few ulps of one depth plus a sparse spread (one overfull bucket of about 11 500 entries, 10 low
+                  bits: the slow path again, two passes; the spread's buckets take the counting split with 10 to 20 low bits);
+    many_tiles:   more than 2048 list tiles (two 8-bit tile passes + tile_ranges_kernel), reference and default policy;
+    tiny:         3 Gaussians;
+    twenty_octaves: depths from 0.3 to 3e5 around the optical axis - about 160 sparsely filled coarse depth bins (some 1700 buckets:
+                  the proportional table, not its one-bucket-per-bin fallback);
+    object_and_background: a dense cluster in a tenth of a depth unit in front of a sparse background and behind a few
+                  floaters (the proportional bucket table: most buckets go to the cluster).
+    The routes named here are asserted by test_gpu_ordering_paths.test_witness_over_the_older_ordering_scenes from the device's bucket
+    table (the figures are printed there); none of these scenes reaches the stable LSD passes of the in-LDS sort or the table's fallback - that file's cases do."""
+    from gpu_utils import forward_state
+    sc, cam, modes, W, H = ordering_scene(case)
     bg = np.array([0.2, 0.3, 0.4], np.float32)
     fw = oracle.forward_full(sc, cam, bg, D=3)
     if case in ("twenty_octaves", "object_and_background"):
