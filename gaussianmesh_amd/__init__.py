@@ -3,6 +3,7 @@
   rasterizer.GaussianRasterizationSettings / GaussianRasterizer / NewGaussianRasterizer
   simple_knn.distCUDA2
   deform.SingleObjectDeform (tensor-in deform + the reference attribute names)
+  mesh_bind.closest_faces / bind_points (a plain cloud bound to a proxy mesh)
 All compute runs in csrc/libgmesh_hip.so (hand-written HIP for gfx950) through include/gmesh_hip.h.
 """
 import os as _os

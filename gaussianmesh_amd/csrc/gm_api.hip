@@ -672,6 +672,17 @@ int gm_knn_nearest(int Pq, const float* query, int Pr, const float* ref, float* 
   return launch_knn_nearest(Pq, query, Pr, ref, out_d2, out_idx, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t gm_closest_face_workspace_bytes(int N, int F) { return closest_face_workspace_bytes(N, F); }
+int gm_closest_face(int N, const float* points, int Vm, const float* vertices, int F, const int* faces, float* out_d2, int* out_face,
+                    float* out_closest, void* workspace, size_t workspace_bytes, void* stream) {
+  if (N < 0 || Vm < 0 || F < 0) { set_error("gm_closest_face: negative size N=%d Vm=%d F=%d", N, Vm, F); return GM_ERR_INVALID_ARG; }
+  if (N == 0) return GM_OK;
+  if (F == 0 || Vm == 0) { set_error("gm_closest_face: empty mesh (F == %d, Vm == %d)", F, Vm); return GM_ERR_INVALID_ARG; }
+  if (!points || !vertices || !faces || !out_d2 || !out_face || !workspace) { set_error("gm_closest_face: null pointer"); return GM_ERR_INVALID_ARG; }
+  return launch_closest_face(N, points, Vm, vertices, F, faces, out_d2, out_face, out_closest, workspace, workspace_bytes,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
 int gm_deform(int N, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
               const float* cov, const float* pos, float* pos_out, float* cov_out, float* rot_out, float* cov6_out,
               void* stream) {

@@ -1,9 +1,11 @@
 """Animate an edited object: the animation loop of the reference's edit.py (its commented-out part, edit.py:46-54), batched.
 
-    python -m gaussianmesh_amd.edit_sequence --object_gaussian fg.ply --object_origin_mesh mesh.obj --mesh_sequence DIR \
+    python -m gaussianmesh_amd.edit_sequence (--object_gaussian fg.ply | --object_plain_gaussian cloud.ply) --object_origin_mesh mesh.obj --mesh_sequence DIR \
         --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N] [--frames_per_launch 4] [--save_maps]
         [--background_gaussian BG.ply [--is_exist_bg]]
 
+--object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
+faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of the two.
 --mesh_sequence: a folder of OBJ files in numeric order (1.obj, 2.obj, ...: the reference's `mesh_sequnce`), one frame each.
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
@@ -27,7 +29,9 @@ def mesh_sequence(folder):
 
 def main(argv=None):
     parser = ArgumentParser(description="Render a mesh-driven animation of a mesh-bound Gaussian object")
-    parser.add_argument("--object_gaussian", type=str, required=True)
+    which = parser.add_mutually_exclusive_group(required=True)
+    which.add_argument("--object_gaussian", type=str, default=None)
+    which.add_argument("--object_plain_gaussian", type=str, default=None)
     parser.add_argument("--object_origin_mesh", type=str, required=True)
     parser.add_argument("--object_name", type=str, default="Object")
     parser.add_argument("--camera_path", type=str, required=True)
@@ -54,7 +58,10 @@ def main(argv=None):
         raise SystemExit("edit_sequence: no .obj files in %s" % args.mesh_sequence)
     tool = ObjectVisualTool() if args.background_gaussian is None else SceneVisualTool(args.background_gaussian)
     cams = tool.get_camera(args.camera_path)
-    tool.add_gaussian(args.object_gaussian, args.object_origin_mesh, args.object_name)
+    if args.object_plain_gaussian is not None:
+        tool.add_plain_gaussian(args.object_plain_gaussian, args.object_origin_mesh, args.object_name)
+    else:
+        tool.add_gaussian(args.object_gaussian, args.object_origin_mesh, args.object_name)
     frames = [(cams[args.camera_id] if args.camera_id is not None else cams[i % len(cams)], {args.object_name: m})
               for i, m in enumerate(meshes)]
     os.makedirs(args.render_path, exist_ok=True)

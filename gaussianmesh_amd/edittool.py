@@ -86,6 +86,38 @@ class SingleObjectDeform(_TensorObject):
         self.load_mesh(mesh_path)
         self.name = mesh_path if name is None else name
 
+    @classmethod
+    def from_plain(cls, gaussian_path, mesh_path, name=None, device="cuda"):
+        """A PLAIN Gaussian PLY (x y z, f_dc / f_rest, opacity, scale, rot: any 3DGS trainer's point_cloud.ply, bg_model.PlainGaussians.save_ply)
+        attached to a proxy mesh (OBJ): every Gaussian is bound to the closest face of the mesh - mesh_bind.bind_points, the search on the
+        device (gm_closest_face) - with the weights of the foot of its perpendicular on that face's plane, as load_mesh's no-face-id branch
+        forms them.  Positions, covariances, opacities and SH rows as load_gaussian forms them.  The object is then like any other
+        (deform_gaussian / deform_vertices, the tools' render_gaussian and render_sequence); it keeps bind_sqr_distance [N] (float32, host),
+        the squared distance of every Gaussian to its face: how far off the surface the cloud lies."""
+        from .mesh_bind import bind_points
+        self = cls.__new__(cls)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.GmeshError("SingleObjectDeform.from_plain binds on a HIP (cuda) device; there is no CPU path")
+        t = lambda a, dt=torch.float32: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=self.device)
+        m = gio.load_plain_gaussians(gaussian_path)
+        vertex, triangles = gio.read_obj(mesh_path)
+        pos = t(m["xyz"])
+        cov = _covariance(t(m["scaling"]), t(m["rotation"]))
+        opacity = torch.sigmoid(t(m["opacity"]))
+        feats = torch.cat([t(m["features_dc"]), t(m["features_rest"])], dim=1).contiguous()
+        b = bind_points(pos, vertex, triangles)
+        self._loaded = m
+        self.gaussian_proj_pos = pos
+        self.index_tri = b["face_id"][:, None]
+        self.bind_sqr_distance = b["sqr_distance"]
+        _TensorObject.__init__(self, pos, cov, opacity, feats, t(b["tri"], torch.int32), t(b["weights"]), t(vertex), name=None)
+        self.faces = t(triangles, torch.int32)
+        off, adj = vertex_face_adjacency(triangles, vertex.shape[0])
+        self._adjacency = (t(off, torch.int32), t(adj, torch.int32))
+        self.name = mesh_path if name is None else name
+        return self
+
     def load_gaussian(self, gaussian_path):
         """:48-64.  The edit tool's loader fills _bc from the saved x, y, z (edittool/mesh_based_gaussian.py:183-184), so
         get_proj_xyz = softmax(xyz) . (v1, v2, v3); positions are the SAVED x, y, z (get_load_xyz)."""
@@ -150,6 +182,10 @@ class ObjectVisualTool:
 
     def add_gaussian(self, gaussian_path, mesh_path, name=None):
         self.gaussians_list.append(SingleObjectDeform(gaussian_path, mesh_path, name, device=self.device))
+
+    def add_plain_gaussian(self, gaussian_path, mesh_path, name=None):
+        """add_gaussian for a plain Gaussian PLY: bound to the mesh's closest faces on load (SingleObjectDeform.from_plain)."""
+        self.gaussians_list.append(SingleObjectDeform.from_plain(gaussian_path, mesh_path, name, device=self.device))
 
     def deform_one_gaussian(self, name, deform_mesh_path):
         for g in self.gaussians_list:

@@ -212,6 +212,32 @@ size_t gm_knn_nearest_workspace_bytes(int Pq, int Pr);
 int gm_knn_nearest(int Pq, const float* query, int Pr, const float* ref, float* out_d2, int* out_idx, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* Closest triangle of a mesh for every point: what binds a plain Gaussian cloud to a proxy mesh (the branch of
+ * SingleObjectDeform.load_mesh that runs without face ids, edittool/__init__.py:68-85, igl.point_mesh_squared_distance there).
+ * points float [N,3], vertices float [Vm,3], faces int32 [F,3] vertex ids.  out_d2 float [N] = squared distance to the closest face,
+ * out_face int32 [N] = its index, out_closest float [N,3] (may be NULL) = the closest point q on it.
+ * The result is defined by arithmetic, not by the search structure: per (point p, face (a, b, c)) in float32, no contraction, correctly
+ * rounded divisions, dot(u, w) = (u.x*w.x + u.y*w.y) + u.z*w.z (Ericson 5.1.5 as edittool.point_mesh_squared_distance evaluates it):
+ *   ab = b - a, ac = c - a, cb = c - b;  d1 = dot(ab, p - a), d2 = dot(ac, p - a), d3 = dot(ab, p - b), d4 = dot(ac, p - b),
+ *   d5 = dot(ab, p - c), d6 = dot(ac, p - c);  vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4;
+ *   denom = 1 / ((va + vb) + vc), v = vb*denom, w = vc*denom;  x = d4 - d3, y = d5 - d6;
+ *   q = (a + ab*v) + ac*w, replaced by the LAST of these that holds (the precedence vertex a, b, c, edge ab, ac, bc, interior):
+ *     b + cb*(x / (x + y))      if va <= 0, x >= 0, y >= 0        a + ac*(d2 / (d2 - d6))   if vb <= 0, d2 >= 0, d6 <= 0
+ *     a + ab*(d1 / (d1 - d3))   if vc <= 0, d1 >= 0, d3 <= 0      c   if d6 >= 0, d5 <= d6
+ *     b   if d3 >= 0, d4 <= d3                                    a   if d1 <= 0, d2 <= 0
+ *   e = p - q, d2(p, face) = (e.x*e.x + e.y*e.y) + e.z*e.z.
+ * Winner: the smallest d2, ties to the LOWEST face index; a NaN d2 (a degenerate face: 0 / 0) never wins; if every face gives NaN the
+ * point gets out_face = -1, out_d2 = +inf, out_closest = NaN.  So (out_d2, out_face, out_closest) equal a float32 brute force over all
+ * F faces bit for bit, for every finite input (csrc/gm_closest.hip: the search structure and why no box that matters is skipped).
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: a negative size, F == 0 or Vm == 0 with N > 0, a NULL among points, vertices,
+ * faces, out_d2, out_face, workspace; with GM_ERR_BUFFER: a workspace below gm_closest_face_workspace_bytes(N, F) (O(N + F), monotonic
+ * in both).  N == 0 succeeds and launches nothing.  Face indices outside [0, Vm) CANNOT be checked here without a read-back: they are
+ * forced into range, so such a face reads some other vertex - no fault, no meaningful result; a caller that holds the faces on the
+ * host checks them there (mesh_bind.closest_faces does).  Stream-ordered, no device allocation, no host synchronisation. */
+size_t gm_closest_face_workspace_bytes(int N, int F);
+int gm_closest_face(int N, const float* points, int Vm, const float* vertices, int F, const int* faces, float* out_d2, int* out_face,
+                    float* out_closest, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Mesh-driven deformation of bound Gaussians; replaces the Jittor tensor algebra of
  * SingleObjectDeform.deform_gaussian (edittool/__init__.py:116-131), tensor-in form:
  *   tri int32 [N,3] vertex ids of the bound face, w float [N,3] barycentric weights,

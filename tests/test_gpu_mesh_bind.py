@@ -1,0 +1,348 @@
+"""-m gpu: gm_closest_face (mesh_bind.closest_faces) against its definition - the float32 brute force of tests/closest_ref.py, bit for
+bit - on inputs made to hurt and at product size; then a plain Gaussian cloud bound to a mesh end to end: SingleObjectDeform.from_plain
+against the float64 host search, the binding's coherence under rigid motions, ObjectVisualTool / SceneVisualTool.render_sequence on a
+plain-bound object, and the CLI's --object_plain_gaussian."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import closest_ref as cr
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, f32).view(np.uint32)
+
+
+def _device_search(P, V, F):
+    from gaussianmesh_amd.mesh_bind import closest_faces
+    d2, face, close = closest_faces(torch.tensor(P, device="cuda"), V, F, want_closest=True)
+    torch.cuda.synchronize()
+    return d2.cpu().numpy(), face.cpu().numpy(), close.cpu().numpy()
+
+
+def _same(got, ref, what):
+    (d2, face, close), (rd2, rface, rclose) = got, ref
+    bad = np.nonzero(face != rface)[0]
+    assert len(bad) == 0, "%s: %d faces differ, first row %d: device %d (d2 %r) brute force %d (d2 %r)" % (
+        what, len(bad), bad[0], face[bad[0]], d2[bad[0]], rface[bad[0]], rd2[bad[0]])
+    assert np.array_equal(_bits(d2), _bits(rd2)), "%s: d2 bits differ" % what
+    hit = rface >= 0
+    assert np.array_equal(_bits(close[hit]), _bits(rclose[hit])), "%s: closest-point bits differ" % what
+    assert np.isnan(close[~hit]).all()
+
+
+def _fit(faces, F):
+    """F faces out of a list: a prefix, or the list repeated (then faces are present more than once)"""
+    return np.resize(faces, (F, 3)).astype(np.int32)
+
+
+def _grid(F):
+    """A regular grid in the plane z = 0 (flat in one axis), vertex coordinates multiples of 1/4, EVERY FACE PRESENT TWICE (the second copy
+    behind the first), with queries exactly on vertices, on edge midpoints, on face centres, above them, and outside the bounding box:
+    exact ties by the dozen - the lowest index has to win each."""
+    n = int(np.ceil(np.sqrt(max(F, 2) / 4.0))) + 1
+    g = np.stack(np.meshgrid(np.arange(n), np.arange(n), indexing="ij"), -1).reshape(-1, 2) * 0.25
+    V = np.concatenate([g, np.zeros((n * n, 1))], 1).astype(f32)
+    idx = np.arange(n * n).reshape(n, n)
+    base = np.concatenate([np.stack([idx[:-1, :-1], idx[1:, :-1], idx[1:, 1:]], -1).reshape(-1, 3),
+                           np.stack([idx[:-1, :-1], idx[1:, 1:], idx[:-1, 1:]], -1).reshape(-1, 3)], 0)
+    half = max(1, F // 2)
+    faces = _fit(np.concatenate([base[:half], base[:half]], 0), F)
+    return V, faces
+
+
+def _grid_queries(V, N, rng):
+    n = int(round(np.sqrt(len(V))))
+    i = rng.integers(n - 1, size=(N, 2)).astype(np.float64)
+    kind = rng.integers(6, size=N)
+    off = np.array([[0, 0], [0.5, 0], [0, 0.5], [0.5, 0.5], [1 / 3, 1 / 3], [0, 0]])[kind]      # vertex, edge midpoints (three directions), inside
+    P = np.concatenate([(i + off) * 0.25, np.zeros((N, 1))], 1)
+    P[kind == 4, 2] = rng.choice([0.0, 0.5, -2.0], size=int((kind == 4).sum()))                  # above / below the plane
+    out = kind == 5                                                                              # outside the bounding box, in the plane and off it
+    P[out, :2] = P[out, :2] + rng.choice([-3.0, 40.0], size=(int(out.sum()), 2))
+    P[out, 2] = rng.choice([0.0, 1.0], size=int(out.sum()))
+    return P.astype(f32)
+
+
+def _torus(F):
+    from gaussianmesh_amd import scenes
+    nu = max(3, int(np.ceil(np.sqrt(F / 2.0 * 4 / 3))))
+    nv = max(3, int(np.ceil(F / 2.0 / nu)))
+    if F == 70000:
+        nu, nv = 200, 175
+    if F == 2400:
+        nu, nv = 40, 30
+    V, faces = scenes.torus_mesh(nu, nv)
+    return V.astype(f32), faces
+
+
+def _degenerate(V, faces, F):
+    """the torus's faces with a face without area (three distinct collinear vertices), one with two equal vertices and one with three equal
+    vertices put among them"""
+    V = np.concatenate([V, np.array([[0.5, 0.25, 0.0], [1.0, 0.5, 0.0], [1.5, 0.75, 0.0]], f32)], 0)
+    faces = _fit(faces, F).copy()
+    n = len(V)
+    extra = np.array([[n - 3, n - 2, n - 1], [5 % n, 5 % n, 5 % n], [n - 3, n - 3, n - 1]], np.int32)
+    where = np.unique(np.array([0, F // 2, F - 1]))
+    faces[where] = extra[:len(where)]
+    return V, faces
+
+
+def _case(kind, N, F, seed):
+    from gaussianmesh_amd import scenes                                    # noqa: F401
+    rng = np.random.default_rng(seed)
+    if kind == "grid_ties":
+        V, faces = _grid(F)
+        return V, faces, _grid_queries(V, N, rng)
+    V, base = _torus(F)
+    near = cr.near_surface(V, base, N, rng)
+    if kind == "shifted":                                                  # +1000: eight bits of every coordinate gone
+        return (V + f32(1000)).astype(f32), _fit(base, F), (near + f32(1000)).astype(f32)
+    assert kind == "degenerate_far"
+    V2, faces = _degenerate(V, base, F)
+    P = near.copy()
+    third = N // 3
+    P[:third] = (rng.normal(0, 2.0, size=(third, 3)) * 150).astype(f32)                          # far away
+    P[third:2 * third] = rng.uniform(-1, 1, size=(third, 3)).astype(f32) * f32(0.5) + np.array([6.0, -4.0, 7.5], f32)   # outside the box
+    if N >= 8:
+        P[-3:] = V2[-3:]                                                   # on the face without area
+        P[-4] = np.array([1.25, 0.625, 0.0], f32)
+    return V2, faces, P
+
+
+SIZES = [(1, 1), (1, 50), (50, 1), (300, 2400), (777, 333), (4097, 1025), (300, 70000)]
+
+
+@pytest.mark.parametrize("kind", ["grid_ties", "degenerate_far", "shifted"])
+@pytest.mark.parametrize("N, F", SIZES)
+def test_bit_identical_to_the_float32_brute_force(N, F, kind):
+    V, faces, P = _case(kind, N, F, seed=N + F)
+    assert faces.shape == (F, 3) and P.shape == (N, 3) and np.isfinite(P).all() and np.isfinite(V).all()
+    ref = cr.closest_face_ref(P, V, faces)
+    got = _device_search(P, V, faces)
+    _same(got, ref, "%s N=%d F=%d" % (kind, N, F))
+    if kind == "grid_ties" and N >= 300 and F >= 300:
+        # the input does hold ties: many queries are as close to a second face, and the copy with the lower index won
+        assert (ref[1] < max(1, F // 2)).all()
+
+
+def test_only_degenerate_faces():
+    """every face gives NaN for a point -> (-1, +inf, NaN); a face with three equal vertices is a point and does bind"""
+    from gaussianmesh_amd.mesh_bind import bind_points
+    V = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [2, 2, 2]], f32)
+    P = np.array([[0.25, 0.25, 1.0], [5, 5, 5]], f32)
+    F = np.array([[0, 0, 1]], np.int32)
+    ref = cr.closest_face_ref(P, V, F)
+    assert ref[1][0] == -1
+    _same(_device_search(P, V, F), ref, "a = b")
+    with pytest.raises(ValueError, match="point 0 has no closest face"):
+        bind_points(torch.tensor(P, device="cuda"), V, F)
+    F = np.array([[3, 3, 3]], np.int32)
+    _same(_device_search(P, V, F), cr.closest_face_ref(P, V, F), "a = b = c")
+    d2, face = __import__("gaussianmesh_amd.mesh_bind", fromlist=["x"]).closest_faces(torch.zeros((0, 3), device="cuda"), V, F)
+    assert d2.shape == (0,) and face.shape == (0,) and face.dtype == torch.int64
+
+
+@pytest.mark.parametrize("name, N, nu, nv, sampled", [("C3 mesh", 1000000, 100, 75, 512), ("300 k faces", 200000, 400, 375, 64)])
+def test_product_size(name, N, nu, nv, sampled):
+    """For ALL queries: out_d2 is, bit for bit, the definition's distance to out_face (an O(N) evaluation); for a sample: the full brute
+    force agrees bit for bit."""
+    from gaussianmesh_amd import scenes
+    rng = np.random.default_rng(11)
+    V, faces = scenes.torus_mesh(nu, nv)
+    V = V.astype(f32)
+    P = cr.near_surface(V, faces, N, rng)
+    d2, face, close = _device_search(P, V, faces)
+    assert (face >= 0).all() and (face < len(faces)).all()
+    assert np.array_equal(_bits(cr.distance_to_face(P, V, faces, face)), _bits(d2))
+    rows = rng.choice(N, size=sampled, replace=False)
+    _same((d2[rows], face[rows], close[rows]), cr.closest_face_ref(P[rows], V, faces), name)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# end to end
+def _write_plain_scene(d, N=2000, seed=4):
+    """A PLAIN Gaussian PLY whose Gaussians lie within N(0, 0.05) of scenes.torus_mesh(40, 30), the mesh as OBJ, cameras.json, a background
+    PLY.  The vertices are put on the grid of 2^-16 (float32-representable, and so are their sums with a grid translation below 8 and their
+    images under a quarter turn: see the rigid motions of test_from_plain_...)"""
+    from gaussianmesh_amd import io as gio, scenes
+    rng = np.random.default_rng(seed)
+    verts, faces = scenes.torus_mesh(40, 30)
+    verts = np.round(verts * 65536.0) / 65536.0
+    assert np.array_equal(verts.astype(f32).astype(np.float64), verts)
+    cl = scenes.make_cloud(N, seed=seed + 1, scale_lo=0.01, scale_hi=0.06)
+    xyz = cr.near_surface(verts, faces, N, rng)
+    m = dict(xyz=xyz, features_dc=cl["shs"][:, :1], features_rest=cl["shs"][:, 1:], opacity=np.log(cl["opac"] / (1 - cl["opac"])).reshape(N, 1),
+             scaling=np.log(cl["scales"]), rotation=cl["rots"] * rng.uniform(0.5, 2.0, (N, 1)))
+    gio.save_plain_gaussians(os.path.join(d, "cloud.ply"), m)
+    gio.write_obj(os.path.join(d, "rest.obj"), verts, faces)
+    cams = []
+    for k in range(3):
+        c = scenes.orbit_camera(k, 7, 200, 120, radius=6.5)
+        view = c["view"].reshape(4, 4).T.astype(np.float64)
+        cams.append(gio.camera_to_json(k, view[:3, :3].T, view[:3, 3], 200, 120, c["fovx"], c["fovy"], "img_%d" % k))
+    with open(os.path.join(d, "cameras.json"), "w") as f:
+        json.dump(cams, f)
+    bgc = scenes.make_cloud(800, seed=seed + 5, scale_lo=0.02, scale_hi=0.1)
+    nb = np.linalg.norm(bgc["means"], axis=1, keepdims=True) + 1e-6
+    gio.save_plain_gaussians(os.path.join(d, "background.ply"),
+                             dict(xyz=bgc["means"] / nb * (4.5 + nb), features_dc=bgc["shs"][:, :1], features_rest=bgc["shs"][:, 1:],
+                                  opacity=np.log(bgc["opac"] / (1 - bgc["opac"])).reshape(-1, 1), scaling=np.log(bgc["scales"]), rotation=bgc["rots"]))
+    return m, verts, faces
+
+
+def _rot(axis, ang):
+    axis = np.asarray(axis, float) / np.linalg.norm(axis)
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    return np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * K @ K
+
+
+def test_from_plain_binds_like_the_float64_host_search_and_moves_coherently(tmp_path):
+    """(i) the binding against the float64 host search, (ii) its coherence, then rigid motions of the mesh at 1e-5 x the magnitude of the
+    quantity (largest |entry| of the expected tensor) - the 1e-5 test_gpu_mesh_rs grants (R, S) under a rigid motion.
+    The motions are EXACT in float32: the mesh's vertices lie on the grid of 2^-16, the translation too (sums below 8: 19 bits), and the
+    rotation is a third of a turn about (1, 1, 1) - a cyclic permutation of the coordinates - so the vertices handed to deform_vertices ARE
+    the moved mesh.  A generic motion is not: its vertices are rounded to float32 on the way in, ~1.2e-7 against edges of 0.06-0.4, and
+    that rounding alone - the per-vertex (R, S) of oracle/mesh_oracle.py in float64 on the rounded vertices - changes a covariance by
+    5.4e-5 of its size for t = (0.3, -2, 5), 2.9e-5 for t = (0.25, -0.5, 1) and 2.9e-5 for a rotation by 0.9 about (1, 2, -0.5): several
+    times the tolerance before any arithmetic of the code under test.  Those two generic motions are printed, not asserted."""
+    from gaussianmesh_amd import edittool
+    from gaussianmesh_amd.mesh_bind import bind_points
+    d = str(tmp_path)
+    m, verts, faces = _write_plain_scene(d)
+    o = edittool.SingleObjectDeform.from_plain(os.path.join(d, "cloud.ply"), os.path.join(d, "rest.obj"), "Object")
+    N = len(m["xyz"])
+    x = o.gaussian_pos.cpu().numpy()
+    assert np.array_equal(x, m["xyz"].astype(f32)) and o.get_name() == "Object"
+    tri, w = o.gaussian_triangles.cpu().numpy(), o.coord.cpu().numpy()
+    # (i) the float64 host search of the parent on the same inputs
+    k64 = edittool.closest_triangles(x.astype(np.float64), verts, faces)
+    host = bind_points(x, verts, faces, face_id=k64)
+    same = o.index_tri.reshape(-1) == k64
+    print("from_plain: %d of %d faces differ from the float64 host search" % (int((~same).sum()), N))
+    assert (~same).sum() <= 0.005 * N
+    assert np.array_equal(tri[same], host["tri"][same]) and np.array_equal(_bits(w[same]), _bits(host["weights"][same]))
+    # (ii) coherent whatever face a row got
+    assert np.array_equal(tri, faces[o.index_tri.reshape(-1)])
+    assert (w >= 0).all() and np.abs(w.astype(np.float64).sum(axis=1) - 1).max() <= 4 * 2.0 ** -24
+    assert o.bind_sqr_distance.shape == (N,) and o.bind_sqr_distance.dtype == f32
+    assert np.array_equal(_bits(o.bind_sqr_distance), _bits(cr.distance_to_face(x, verts, faces, o.index_tri.reshape(-1))))
+    assert np.sqrt(o.bind_sqr_distance.max()) < 0.4                       # N(0, 0.05) off the surface
+    cov = o.gaussian_cov.cpu().numpy().astype(np.float64)
+    foot = np.einsum("nk,nkj->nj", w.astype(np.float64), verts[tri])      # a Gaussian travels with its weighted foot point (gm_deform.hip),
+    tol = 1e-5                                                            # the offset from the surface is not rotated
+
+    def moved(Q, t):
+        """(position error, covariance error) of the object under v -> Q v + t, each over the largest |entry| of what is expected"""
+        V1 = verts @ Q.T + t
+        o.deform_vertices(torch.tensor(V1, dtype=torch.float32, device="cuda"))
+        pos, c = o.gaussian_deform_pos.cpu().numpy().astype(np.float64), o.gaussian_deform_cov.cpu().numpy().astype(np.float64)
+        exp_pos, exp_cov = x + foot @ (Q - np.eye(3)).T + t, Q @ cov @ Q.T
+        exact = np.array_equal(V1.astype(f32).astype(np.float64), V1)
+        return np.abs(pos - exp_pos).max() / np.abs(exp_pos).max(), np.abs(c - exp_cov).max() / np.abs(exp_cov).max(), exact
+
+    I3 = np.eye(3)
+    for name, Q, t in (("generic translation (0.3, -2, 5)", I3, np.array([0.3, -2.0, 5.0])), ("generic rotation 0.9 about (1, 2, -0.5)", _rot([1, 2, -0.5], 0.9), np.zeros(3))):
+        print("%s, vertices rounded on the way in (not asserted): position %.3g, covariance %.3g of their size" % ((name,) + moved(Q, t)[:2]))
+    t = np.array([0.3125, -2.0, 4.75])                                    # on the grid of 2^-16, every sum below 8
+    cyc = np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])   # (x, y, z) -> (z, x, y): 120 degrees about (1, 1, 1); not symmetric
+    assert np.allclose(cyc, _rot([1, 1, 1], 2 * np.pi / 3)) and not np.array_equal(cyc, cyc.T)
+    for name, Q, tt in (("translation", I3, t), ("rotation", cyc, np.zeros(3)), ("rotation and translation", cyc, t)):
+        e_pos, e_cov, exact = moved(Q, tt)
+        print("%s, exact in float32: position %.3g, covariance %.3g of their size" % (name, e_pos, e_cov))
+        assert exact, name
+        assert e_pos <= tol, (name, e_pos)
+        assert e_cov <= tol, (name, e_cov)
+
+
+def _twist(verts, t):
+    from gaussianmesh_amd import scenes
+    return torch.tensor(scenes.twist_bend_frame(verts, t=t)[0].astype(f32), device="cuda")
+
+
+@pytest.mark.parametrize("aux", [False, True])
+def test_render_sequence_of_a_plain_bound_object(tmp_path, aux):
+    from test_gpu_edit_sequence import _fused
+    from gaussianmesh_amd.deform import mesh_rs_packed
+    from gaussianmesh_amd.edittool import ObjectVisualTool
+    from gaussianmesh_amd.renderer import render_deformed
+    d = str(tmp_path)
+    _, verts, _ = _write_plain_scene(d)
+    tool, ref = ObjectVisualTool(), ObjectVisualTool()
+    for t_ in (tool, ref):
+        t_.add_plain_gaussian(os.path.join(d, "cloud.ply"), os.path.join(d, "rest.obj"), "Object")
+    cams = tool.get_camera(d)
+    meshes = [_twist(verts, t) for t in (3, 7, 11, 14)]
+    frames = [(cams[i % len(cams)], {"Object": meshes[i]}) for i in range(4)]
+    got = list(tool.render_sequence(frames, frames_per_launch=4, aux=aux))
+    torch.cuda.synchronize()
+    assert len(got) == 4
+    o = tool.gaussians_list[0]
+    cloud = dict(tri=o.gaussian_triangles, weights=o.coord, cov=o.gaussian_cov, pos=o.gaussian_pos, shs=o.gaussian_feature, opac=o.gaussian_o)
+    for i, (cam, _) in enumerate(frames):
+        outs = got[i] if aux else (got[i],)
+        # what the sequences of a mesh-bound object give (test_gpu_edit_sequence): bit for bit the fused single-frame path
+        exact = _fused(cloud, mesh_rs_packed(o.vertex, meshes[i], o.faces, o._adjacency), cam, torch.ones(3, device="cuda"), aux)
+        for g_, e_, name in zip(outs, exact if aux else (exact,), ("image", "depth", "alpha")):
+            assert torch.equal(g_, e_), "frame %d: %s differs from the fused single-frame path" % (i, name)
+        ref.gaussians_list[0].deform_vertices(meshes[i])
+        exp = render_deformed(cam, ref.gaussians_list, return_aux=True) if aux else (ref.render_gaussian(cam),)
+        for g_, e_, name in zip(outs, exp, ("image", "depth", "alpha")):
+            print("frame %d %s vs deform_vertices + render_gaussian: %d values differ, max abs %.3g" % (
+                i, name, int((g_ != e_).sum()), float((g_ - e_).abs().max())))
+        for g_, e_, name in zip(outs, exp, ("image", "depth", "alpha")):
+            assert torch.equal(g_, e_), "frame %d: %s differs from deform_vertices + render_gaussian" % (i, name)
+    assert float((got[0][0] if aux else got[0]).min()) < 0.9              # the object is in the picture
+
+
+def test_scene_sequence_with_a_plain_bound_object(tmp_path):
+    from gaussianmesh_amd.edittool import SceneVisualTool
+    d = str(tmp_path)
+    _, verts, _ = _write_plain_scene(d)
+    tool, ref = (SceneVisualTool(os.path.join(d, "background.ply")) for _ in range(2))
+    for t_ in (tool, ref):
+        t_.add_plain_gaussian(os.path.join(d, "cloud.ply"), os.path.join(d, "rest.obj"), "Object")
+    cams = tool.get_camera(d)
+    meshes = [_twist(verts, t) for t in (3, 7, 11, 14)]
+    frames = [(cams[i % len(cams)], {"Object": meshes[i]}) for i in range(4)]
+    got = list(tool.render_sequence(frames, frames_per_launch=4))
+    torch.cuda.synchronize()
+    for i, (cam, _) in enumerate(frames):
+        ref.gaussians_list[0].deform_vertices(meshes[i])
+        assert torch.equal(got[i], ref.render_gaussian(cam)), "frame %d differs from deform_vertices + render_gaussian" % i
+
+
+def test_cli_renders_a_plain_gaussian_file(tmp_path):
+    from PIL import Image
+    from gaussianmesh_amd import io as gio, scenes
+    from gaussianmesh_amd.edittool import ObjectVisualTool
+    d = str(tmp_path)
+    _, verts, faces = _write_plain_scene(d)
+    seq = os.path.join(d, "seq")
+    os.makedirs(seq)
+    for i in range(1, 6):
+        gio.write_obj(os.path.join(seq, "%d.obj" % i), scenes.twist_bend_frame(verts, t=2 * i)[0], faces)
+    out = os.path.join(d, "renders")
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, "-m", "gaussianmesh_amd.edit_sequence", "--object_plain_gaussian", os.path.join(d, "cloud.ply"),
+                        "--object_origin_mesh", os.path.join(d, "rest.obj"), "--camera_path", d, "--render_path", out, "--mesh_sequence", seq,
+                        "--frames_per_launch", "4"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:]
+    tool = ObjectVisualTool()
+    tool.add_plain_gaussian(os.path.join(d, "cloud.ply"), os.path.join(d, "rest.obj"), "Object")
+    cams = tool.get_camera(d)
+    frames = [(cams[(i - 1) % len(cams)], {"Object": os.path.join(seq, "%d.obj" % i)}) for i in range(1, 6)]
+    for i, image in enumerate(tool.render_sequence(frames)):
+        png = np.asarray(Image.open(os.path.join(out, "%05d.png" % i)))
+        exp = (np.clip(image.cpu().numpy(), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8).transpose(1, 2, 0)
+        assert np.array_equal(png, exp), i
+    assert not os.path.exists(os.path.join(out, "%05d.png" % 5))
