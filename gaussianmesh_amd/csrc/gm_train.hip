@@ -22,6 +22,12 @@ namespace gm {
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
+// __expf(x) for the softmax's x = b - max b <= 0.  The exponential instruction behind __expf returns 0 where the result would be subnormal
+// (x < -87.34), and w_i = 0 then zeroes w_i v_i and d_bc_i = w_i (dw_i - dot), which are up to ~10 w_i and may well be normal numbers.
+// Below -87 the exponential is taken 44 higher - x + 44 is exact there - and scaled back by e^-44, a product that rounds to the
+// subnormal it should be; above, the bits are __expf's as before.
+__device__ __forceinline__ float softmax_exp(float x) { return x < -87.0f ? __expf(x + 44.0f) * 7.78113225e-20f : __expf(x); }
+
 // sqrt(|AB x AC|) of the bound face: the reference's circumradius() (utils/loss_utils.py:86-101)
 __device__ __forceinline__ float face_radius(const ActArgs& a, size_t i3) {
   const float ax = a.v2[i3] - a.v1[i3], ay = a.v2[i3 + 1] - a.v1[i3 + 1], az = a.v2[i3 + 2] - a.v1[i3 + 2];
@@ -42,7 +48,7 @@ __global__ __launch_bounds__(256) void mesh_activate_fwd_kernel(const ActArgs a,
   const size_t i3 = 3 * (size_t)i;
   const float b0 = a.bc[i3], b1 = a.bc[i3 + 1], b2 = a.bc[i3 + 2];
   const float mx = fmaxf(b0, fmaxf(b1, b2));
-  const float e0 = __expf(b0 - mx), e1 = __expf(b1 - mx), e2 = __expf(b2 - mx);
+  const float e0 = softmax_exp(b0 - mx), e1 = softmax_exp(b1 - mx), e2 = softmax_exp(b2 - mx);
   const float inv = 1.0f / (e0 + e1 + e2);
   const float w0 = e0 * inv, w1 = e1 * inv, w2 = e2 * inv;
   const float k = a.alpha * a.r[i] * (sigmoidf(a.dist[i]) - 0.5f);
@@ -80,7 +86,7 @@ __global__ __launch_bounds__(256) void mesh_activate_bwd_kernel(const ActArgs a,
   {  // softmax-barycentric position and normal offset
     const float b0 = a.bc[i3], b1 = a.bc[i3 + 1], b2 = a.bc[i3 + 2];
     const float mx = fmaxf(b0, fmaxf(b1, b2));
-    const float e0 = __expf(b0 - mx), e1 = __expf(b1 - mx), e2 = __expf(b2 - mx);
+    const float e0 = softmax_exp(b0 - mx), e1 = softmax_exp(b1 - mx), e2 = softmax_exp(b2 - mx);
     const float inv = 1.0f / (e0 + e1 + e2);
     const float w0 = e0 * inv, w1 = e1 * inv, w2 = e2 * inv;
     const float dw0 = gx * a.v1[i3] + gy * a.v1[i3 + 1] + gz * a.v1[i3 + 2];
@@ -105,11 +111,16 @@ __global__ __launch_bounds__(256) void mesh_activate_bwd_kernel(const ActArgs a,
   }
   {
     const float4 q = reinterpret_cast<const float4*>(a.rotation)[i];
-    const float nrm = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-12f), qn = 1.0f / nrm;
-    const float4 y = make_float4(q.x * qn, q.y * qn, q.z * qn, q.w * qn);
+    const float len = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+    const float qn = 1.0f / fmaxf(len, 1e-12f);
     const float4 g = d_rots ? d_rots[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float yd = y.x * g.x + y.y * g.y + y.z * g.z + y.w * g.w;
-    d_rotation[i] = make_float4((g.x - y.x * yd) * qn, (g.y - y.y * yd) * qn, (g.z - y.z * yd) * qn, (g.w - y.w * yd) * qn);
+    if (len > 1e-12f) {                          // d(q/|q|) = (g - y (y.g)) / |q|
+      const float4 y = make_float4(q.x * qn, q.y * qn, q.z * qn, q.w * qn);
+      const float yd = y.x * g.x + y.y * g.y + y.z * g.z + y.w * g.w;
+      d_rotation[i] = make_float4((g.x - y.x * yd) * qn, (g.y - y.y * yd) * qn, (g.z - y.z * yd) * qn, (g.w - y.w * yd) * qn);
+    } else {                                     // the clamp is active: q / eps, as jt.normalize's x / maximum(|x|, eps) differentiates
+      d_rotation[i] = make_float4(g.x * qn, g.y * qn, g.z * qn, g.w * qn);
+    }
   }
   {
     const float o = sigmoidf(a.opacity[i]);

@@ -458,3 +458,89 @@ def test_backward_after_a_matrix_core_forward_c2_size():
     assert float(dev[dev <= 1e-3].max()) <= 1e-3 and float(dev[dev <= 1e-3].median()) <= 2e-5         # rounding of the reciprocals only
     assert off <= 64, off                                  # pixels with an entry on the threshold (measured: 6 of 1.3 M covered pixels), each a 0.4 % weight
     assert float(dev.max()) <= 0.05                        # never more than a handful of threshold entries on one pixel
+
+
+# ---------------------------------------------------------------------------------------------------------------- FusedAdam at scale
+def _adam32_torch(p, m, v, g, st, eps):
+    """Adam's rule with float32 rounding after every operation, in the order adam_update (csrc/gm_common.h) spells it, as eager torch
+    ops on the device (tests/train_ops_ref.adam_ref32 is the numpy original): m' = fma(b1, m, c1 g), v' = fma(b2, v, (c2 g) g), the
+    fma as an exact float64 product and sum rounded once to float32"""
+    b1, b2 = torch.tensor(0.9, dtype=torch.float32, device=p.device), torch.tensor(0.999, dtype=torch.float32, device=p.device)
+    c1, c2 = float(np.float32(1.0 - 0.9)), float(np.float32(1.0 - 0.999))
+    m1 = (b1.double() * m.double() + (g * c1).double()).float()
+    v1 = (b2.double() * v.double() + ((g * c2) * g).double()).float()
+    return m1, v1
+
+
+def _ulp32_torch(x):
+    """spacing of float32 at |x| (float64 tensor), never below the subnormal spacing"""
+    e = torch.floor(torch.log2(torch.clamp(x.abs(), min=2.0 ** -126)))
+    return torch.pow(torch.tensor(2.0, dtype=torch.float64, device=x.device), e - 23)
+
+
+@pytest.mark.parametrize("active", [0, 12])
+def test_fused_adam_sh_group_above_the_grid_stride_threshold(active):
+    """FusedAdam on an SH group [P,16,3], P = 400,003: 19.2 M elements, above the 16,777,216 that 16384 workgroups of 256 float4 lanes
+    cover, so adam_kernel's grid-stride loop makes a second pass (every full-size model is there: P > 349,525); a second group [P,3]
+    rides in the same launch.  Two steps.  active = 12: the gradients are zero and the moments at rest above coefficient 4, as training
+    has them, and that region keeps its bits.  Every element, against float64 torch on the device, with the gates of
+    tests/test_gpu_model_ops.py: m', v' within 1 ulp (+ float32's smallest normal) of the float32-rounded rule, p' within
+    2e-6 |step| + 1.3e-7 |p| + 1e-12 of the float64 rule on the moments written, and the rate every element received recovered from
+    dp (sqrt(v') + eps) / m' (lr and lr_rest are a factor of 20 apart)."""
+    from gaussianmesh_amd.model_ops import FusedAdam
+    P, eps, lr, lr_rest, lr_o = 400_003, 1e-15, 0.02, 0.001, 0.005
+    gen = torch.Generator(device="cuda").manual_seed(active + 1)
+    rnd = lambda *s: torch.rand(s, device="cuda", generator=gen)
+    sign = torch.where(rnd(P, 16, 3) < 0.5, -1.0, 1.0)
+    p = (0.01 * torch.randn((P, 16, 3), device="cuda", generator=gen)).requires_grad_(True)
+    o = torch.randn((P, 3), device="cuda", generator=gen).requires_grad_(True)
+    opt = FusedAdam([{"params": [p], "lr": lr, "lr_rest": lr_rest, "period": 48, "split": 3, "active": active, "name": "f"},
+                     {"params": [o], "lr": lr_o, "name": "o"}], eps=eps)
+    m, v = opt.param_groups[0]["m"][0], opt.param_groups[0]["values"][0]
+    m.copy_(sign * (0.2 + 1.8 * rnd(P, 16, 3))); v.copy_((0.3 + 1.7 * rnd(P, 16, 3)) ** 2)          # m != 0 of the gradient's sign, v > 0
+    opt.param_groups[1]["m"][0].copy_(torch.randn((P, 3), device="cuda", generator=gen))
+    opt.param_groups[1]["values"][0].copy_(rnd(P, 3) + 0.1)
+    nc = 16 if not active else active // 3
+    if active:
+        m[:, nc:] = 0.0; v[:, nc:] = 0.0
+    opt.n_step = 5
+    rate = torch.full((1, 16, 1), lr_rest, dtype=torch.float64, device="cuda"); rate[:, 0] = lr
+    for it in range(2):
+        t = opt.n_step + 1
+        g = sign * (0.2 + 1.8 * rnd(P, 16, 3))
+        if active:
+            g[:, nc:] = 0.0
+        go = torch.randn((P, 3), device="cuda", generator=gen)
+        p.grad, o.grad = g, go
+        p0, m0, v0, g0 = p.detach().clone(), m.clone(), v.clone(), g.clone()
+        o0, om0, ov0 = o.detach().clone(), opt.param_groups[1]["m"][0].clone(), opt.param_groups[1]["values"][0].clone()
+        opt.step()
+        torch.cuda.synchronize()
+        assert opt.n_step == t and torch.equal(g, g0)
+        corr = float(np.sqrt(1.0 - 0.999 ** t) / (1.0 - 0.9 ** t))
+        for name, (q0, qm0, qv0, qg, q1, qm1, qv1, rt) in dict(
+                sh=(p0, m0, v0, g0, p.detach(), m, v, rate),
+                other=(o0, om0, ov0, go, o.detach(), opt.param_groups[1]["m"][0], opt.param_groups[1]["values"][0], lr_o)).items():
+            live = slice(0, nc) if name == "sh" else slice(None)
+            mr, vr = _adam32_torch(q0, qm0, qv0, qg, None, eps)
+            for what, got, ref in (("m'", qm1, mr), ("v'", qv1, vr)):
+                err = (got[:, live].double() - ref[:, live].double()).abs()
+                bad = err > _ulp32_torch(ref[:, live].double()) + 1.1754944e-38
+                assert not bad.any(), "%s %s step %d: %d elements beyond 1 ulp, first %s" % (name, what, t, int(bad.sum()), bad.nonzero()[0].tolist())
+            step = rt * corr * qm1.double() / (qv1.double().sqrt() + eps)
+            want = q0.double() - step
+            err = (q1.double() - want).abs()[:, live]
+            bad = err > (2e-6 * step.abs() + 1.3e-7 * q0.double().abs() + 1e-12)[:, live]
+            assert not bad.any(), "%s p' step %d: %d elements outside the bound, first %s" % (name, t, int(bad.sum()), bad.nonzero()[0].tolist())
+        # which rate did every SH element receive?
+        dp = (p0.double() - p.detach().double())[:, :nc]
+        got_rate = dp * (v.double().sqrt() + eps)[:, :nc] / m.double()[:, :nc] / corr
+        took = torch.where(got_rate > float(np.sqrt(lr * lr_rest)), torch.tensor(lr, dtype=torch.float64, device="cuda"), torch.tensor(lr_rest, dtype=torch.float64, device="cuda"))
+        wrong = took != rate.expand(P, 16, 3)[:, :nc]
+        assert not wrong.any(), "step %d: %d elements took the other rate, first %s" % (t, int(wrong.sum()), wrong.nonzero()[0].tolist())
+        assert ((got_rate / rate.expand(P, 16, 3)[:, :nc] - 1).abs() < 0.02).all()
+        if active:                                                 # the untouched region: bit-unchanged
+            for a, b in ((p.detach(), p0), (m, m0), (v, v0)):
+                assert torch.equal(a[:, nc:].view(torch.int32), b[:, nc:].view(torch.int32))
+        else:
+            assert float(dp.abs().min()) > 0
