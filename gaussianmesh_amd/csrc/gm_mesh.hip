@@ -13,6 +13,13 @@
 // one-ring still yields a full-rank map (its normal direction then follows the deformed normal, scaled like a length).
 // For any affine deformation of a non-planar neighbourhood T_i is that affine map exactly: identity -> (I, I), rigid motion
 // -> (rotation, I), uniform scale s -> (I, s I).
+// Polar decomposition, by the shape of T: a proper, well-conditioned map takes Newton's iteration; a reflection, a strongly
+// anisotropic or a (nearly) singular one takes the eigen-decomposition of T^T T, which supplies the principal directions e_k
+// only - the stretches are the lengths |T e_k|, never square roots of eigenvalues (T^T T squares the condition number), and the
+// weakest column of Q is the cross product of the other two.  So a neighbourhood squashed onto a plane (an ordinary edit)
+// gets the rotation that is the limit of the thin one's, orthonormal to rounding, with Q S = T; the smallest stretch carries
+// the sign of a reflection.  A neighbourhood collapsed onto a line or a point (second stretch at most 1e-12 of the first)
+// singles out no rotation: Q = I by convention, S = the symmetric factor of T^T T (S = 0 for a point).
 // Outputs, per vertex, row-major 3x3: S, and R = Q^T - the transpose is pyACAP's row-vector convention as the call site uses
 // it: deform_gaussian takes gaussian_deform_rot = blend(R)^T and transforms covariances by (R^T S) C (R^T S)^T
 // (edittool/__init__.py:118-129), which is T C T^T exactly when R^T S = T.
@@ -217,58 +224,64 @@ __global__ __launch_bounds__(GM_MESH_THREADS) void mesh_rs_kernel(int Vm, const 
     }
   }
   if (have) {
+    // Eigen-decomposition route: F^T F = E diag(lambda) E^T gives the principal directions only.  The stretches are NOT
+    // sqrt(lambda): F^T F squares the condition number, so an eigenvalue below ~1e-16 of the largest is rounding noise and its
+    // square root (1e-8) would scale a column of Q by garbage.  They are the lengths |F e_k| instead (absolute error ~1e-16 of the
+    // largest, since the eigenvectors are accurate where the gap is), and only the two strongest columns F e_k / |F e_k| enter
+    // Q; the weakest is their cross product, which stays a unit vector however small its stretch is - a neighbourhood squashed
+    // flat is the continuous limit of a thin one.  The weakest stretch carries the sign (negative for a reflection).
     double C[3][3], E[3][3];
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
       for (int j = 0; j < 3; j++) C[i][j] = F[0][i] * F[0][j] + F[1][i] * F[1][j] + F[2][i] * F[2][j];   // F^T F
     jacobi3(C, E);
-    double sig[3] = {sqrt(fmax(C[0][0], 0.0)), sqrt(fmax(C[1][1], 0.0)), sqrt(fmax(C[2][2], 0.0))};
-    const double det = F[0][0] * (F[1][1] * F[2][2] - F[1][2] * F[2][1]) - F[0][1] * (F[1][0] * F[2][2] - F[1][2] * F[2][0]) +
-                       F[0][2] * (F[1][0] * F[2][1] - F[1][1] * F[2][0]);
-    if (det < 0.0) {                                               // reflection: the smallest stretch takes the sign
-      const int m = (sig[0] <= sig[1] && sig[0] <= sig[2]) ? 0 : (sig[1] <= sig[2] ? 1 : 2);
-      sig[m] = -sig[m];
-    }
-    const double big = fmax(fabs(sig[0]), fmax(fabs(sig[1]), fabs(sig[2])));
-    double inv[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) inv[k] = fabs(sig[k]) > 1e-12 * big && big > 0.0 ? 1.0 / sig[k] : 0.0;
-    double FE[3][3];                                                // F E
+    double FE[3][3], sig[3];                                        // F E, column lengths
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
       for (int k = 0; k < 3; k++) FE[i][k] = F[i][0] * E[0][k] + F[i][1] * E[1][k] + F[i][2] * E[2][k];
 #pragma unroll
-    for (int i = 0; i < 3; i++)
+    for (int k = 0; k < 3; k++) sig[k] = sqrt(FE[0][k] * FE[0][k] + FE[1][k] * FE[1][k] + FE[2][k] * FE[2][k]);
+    // order the directions sig[0] >= sig[1] >= sig[2] (three compare-exchanges, compile-time indices)
 #pragma unroll
-      for (int j = 0; j < 3; j++) {
-        S[i][j] = E[i][0] * sig[0] * E[j][0] + E[i][1] * sig[1] * E[j][1] + E[i][2] * sig[2] * E[j][2];
-        Q[i][j] = FE[i][0] * inv[0] * E[j][0] + FE[i][1] * inv[1] * E[j][1] + FE[i][2] * inv[2] * E[j][2];
-      }
-    if (inv[0] == 0.0 || inv[1] == 0.0 || inv[2] == 0.0) {       // a collapsed direction: complete Q on it by a cross product
-      // columns of Q E for the non-collapsed directions are orthonormal; rebuild the missing one(s) only in the
-      // single-collapse case (a flattened neighbourhood), otherwise fall back to the identity rotation
-      int zc = (inv[0] == 0.0) + (inv[1] == 0.0) + (inv[2] == 0.0);
-      if (zc == 1) {
-        const int m = inv[0] == 0.0 ? 0 : (inv[1] == 0.0 ? 1 : 2), p = (m + 1) % 3, q = (m + 2) % 3;
-        double up[3], uq[3], um[3];
+    for (int pass = 0; pass < 3; pass++) {
+      const int a = pass == 1 ? 1 : 0, b = a + 1;
+      if (sig[a] < sig[b]) {
+        double t = sig[a]; sig[a] = sig[b]; sig[b] = t;
 #pragma unroll
-        for (int i = 0; i < 3; i++) { up[i] = FE[i][p] * inv[p]; uq[i] = FE[i][q] * inv[q]; }
-        cross3(up, uq, um);
-        double ep[3] = {E[0][p], E[1][p], E[2][p]}, eq[3] = {E[0][q], E[1][q], E[2][q]}, em[3];
-        cross3(ep, eq, em);                                        // = +-E[:, m]; using the same handedness keeps det Q = +1
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-          for (int j = 0; j < 3; j++) Q[i][j] = up[i] * ep[j] + uq[i] * eq[j] + um[i] * em[j];
-      } else {
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-          for (int j = 0; j < 3; j++) Q[i][j] = i == j ? 1.0 : 0.0;
+        for (int i = 0; i < 3; i++) {
+          t = FE[i][a]; FE[i][a] = FE[i][b]; FE[i][b] = t;
+          t = E[i][a]; E[i][a] = E[i][b]; E[i][b] = t;
+        }
       }
     }
+    const double ep[3] = {E[0][0], E[1][0], E[2][0]}, eq[3] = {E[0][1], E[1][1], E[2][1]};
+    double em[3];
+    cross3(ep, eq, em);                                             // = +-E[:, 2]; the handedness of (ep, eq, em) keeps det Q = +1
+    double up[3] = {0, 0, 0}, uq[3] = {0, 0, 0}, um[3] = {0, 0, 0};
+    if (sig[1] > 1e-12 * sig[0]) {                                  // rank >= 2 (false for F = 0 as well)
+      double dpq = 0.0, lq = 0.0;
+#pragma unroll
+      for (int i = 0; i < 3; i++) { up[i] = FE[i][0] / sig[0]; dpq += up[i] * FE[i][1]; }
+#pragma unroll
+      for (int i = 0; i < 3; i++) { uq[i] = FE[i][1] - dpq * up[i]; lq += uq[i] * uq[i]; }       // dpq = e_p^T F^T F e_q / sig_p: rounding only
+      lq = sqrt(lq);
+#pragma unroll
+      for (int i = 0; i < 3; i++) uq[i] /= lq;
+      cross3(up, uq, um);
+      sig[2] = 0.0;                                                 // signed: um . (F em)
+#pragma unroll
+      for (int i = 0; i < 3; i++) sig[2] += um[i] * (F[i][0] * em[0] + F[i][1] * em[1] + F[i][2] * em[2]);
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) Q[i][j] = up[i] * ep[j] + uq[i] * eq[j] + um[i] * em[j];
+    }                                                               // else: collapsed to a line or a point - no rotation is singled out, Q stays the identity
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) S[i][j] = sig[0] * ep[i] * ep[j] + sig[1] * eq[i] * eq[j] + sig[2] * em[i] * em[j];
   }
 #pragma unroll
   for (int i = 0; i < 3; i++)

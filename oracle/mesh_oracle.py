@@ -7,11 +7,17 @@ PARITY STATUS: "parity unpinned".  The reference obtains the per-vertex (R, S) p
 T_i = argmin sum_j c_ij |e'_ij - T e_ij|^2, then the polar decomposition T = Q S) and anchored on the call site
 (deform_gaussian transposes the blended R and transforms covariances by R^T S, :118-129, so R = Q^T).
 Written independently of the HIP kernel's algebra (per-edge scatter + numpy solve + SVD instead of the per-vertex CSR loop,
-adjugate inverse and Jacobi eigen-solver); conditioning constants as documented in gm_mesh.hip."""
+adjugate inverse, Newton iteration and Jacobi eigen-solver); conditioning constants as documented in gm_mesh.hip.
+Conditioning of the polar step: the SVD of T itself, so a collapsed direction costs no accuracy in the others (the sensitivity of
+the proper polar factor goes with 1 / (sigma_2 + sigma_3)); the reflection sign is det(U V^T), exactly +-1, not det(T), which is
+rounding noise at rank 2.  At rank 2 the rotation is still unique and the kernel must match it; at rank <= 1 it is not (the SVD's
+choice here, the identity in the kernel), and only S is comparable."""
 import numpy as np
 
 
-def mesh_rs(V0, V1, faces):
+def mesh_rs(V0, V1, faces, return_fit=False):
+    """(R, S) per vertex, float64 [Vm,3,3]; with return_fit also the fitted map F [Vm,3,3] (R^T S = F wherever F has rank >= 2)
+    and its singular values [Vm,3], descending and unsigned (identity / ones for a vertex without a usable one-ring)."""
     V0 = np.asarray(V0, np.float64); V1 = np.asarray(V1, np.float64); faces = np.asarray(faces, np.int64)
     Vm = V0.shape[0]
     M0 = np.zeros((Vm, 3, 3)); M1 = np.zeros((Vm, 3, 3)); nr = np.zeros((Vm, 3)); nd = np.zeros((Vm, 3)); wsum = np.zeros(Vm)
@@ -41,9 +47,13 @@ def mesh_rs(V0, V1, faces):
     has = (wsum > 0) & (np.abs(np.linalg.det(M0)) > 1e-300)
     F = M1[has] @ np.linalg.inv(M0[has])
     U, sig, Vt = np.linalg.svd(F)
-    neg = np.linalg.det(F) < 0
+    neg = np.linalg.det(U @ Vt) < 0                              # not det(F): at rank 2 that is rounding noise, this is exactly +-1
     sig = sig.copy(); sig[neg, 2] *= -1.0                         # the smallest stretch takes the sign of a reflection
     Q = np.einsum("nik,nk,nkj->nij", U, np.where(neg[:, None], np.array([1.0, 1.0, -1.0]), 1.0), Vt)
     S[has] = np.einsum("nki,nk,nkj->nij", Vt, sig, Vt)
     R[has] = Q.transpose(0, 2, 1)
+    if return_fit:
+        Ff = np.tile(np.eye(3), (Vm, 1, 1)); sv = np.ones((Vm, 3))
+        Ff[has] = F; sv[has] = np.abs(sig)
+        return R, S, Ff, sv
     return R, S
