@@ -107,6 +107,145 @@ int launch_sh_colors(int N, int deg, int M, const float* pos, const float* campo
 }
 
 // ---------------------------------------------------------------------------------------------
+// The row body of the three fused kernels below (deform_shade_kernel, deform_shade_pre_batch_kernel, scene_shade_pre_batch_kernel).
+// Their frames must come out bit for bit equal (tests/test_gpu_batch.py, test_gpu_scene_batch.py, test_gpu_parity.py), so every
+// expression they share is written once, here, with its parenthesisation; arrays are plain pointers and stay in registers after inlining.
+constexpr int DS_THREADS = 64;                     // one-wave workgroups of 64 Gaussians
+
+// The block's SH rows -> LDS ([64][12] granules, the linear image of the rows).  A full block goes by LDS-DMA; the last, partial block by
+// plain copies of each thread's own row.  The caller places this behind a sched_barrier(0) and waits (vmcnt(0) + __syncthreads) where it
+// wants the rows: what it issues in between is in flight together with the DMA.
+__device__ __forceinline__ void stage_sh_rows(float4* l_sh, const float* __restrict__ shs, size_t row0, int nrows, int t, size_t i) {
+  if (nrows == DS_THREADS) {
+    const char* gsh = reinterpret_cast<const char*>(shs + row0 * 48) + t * 16;
+#pragma unroll
+    for (int q = 0; q < 12; q++) dma16(gsh + q * 1024, reinterpret_cast<char*>(l_sh) + q * 1024);
+  } else if (t < nrows) {
+#pragma unroll
+    for (int c = 0; c < 12; c++) l_sh[t * 12 + c] = reinterpret_cast<const float4*>(shs)[i * 12 + c];
+  }
+}
+
+// The rest covariance of row i goes straight to registers (36 B per lane, the wave's 2304 B are contiguous): staging it as well
+// would cost 2.25 KiB of LDS per wave, i.e. two resident waves per CU.  cov6 (wave-uniform): the row is its six distinct entries
+// xx xy xz yy yz zz, 24 B per lane.
+__device__ __forceinline__ void load_rest_cov(float* C, const float* __restrict__ cov, size_t i, bool live, bool cov6) {
+  if (!live) {                                     // (decided once for the row, not per entry)
+#pragma unroll
+    for (int k = 0; k < 9; k++) C[k] = 0.f;
+    return;
+  }
+  if (cov6) {
+    float c6[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) c6[k] = cov[i * 6 + k];
+    C[0] = c6[0]; C[1] = c6[1]; C[2] = c6[2]; C[3] = c6[1]; C[4] = c6[3]; C[5] = c6[4]; C[6] = c6[2]; C[7] = c6[4]; C[8] = c6[5];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; k++) C[k] = cov[i * 9 + k];
+  }
+}
+
+// The three vertices of a Gaussian's face from the packed per-vertex table (pack_mesh_state_kernel: 6 float4 per vertex, 18 16-byte loads)
+// and their barycentric blend: displacement d, rotation Rb, stretch Sb.
+__device__ __forceinline__ void gather_blend(const float4* __restrict__ tab, int t0, int t1, int t2, float w0, float w1, float w2, float* d,
+                                             float* Rb, float* Sb) {
+  float va[24], vb[24], vc[24];
+#pragma unroll
+  for (int q = 0; q < 6; q++) {
+    const float4 a = tab[6 * (size_t)t0 + q], b = tab[6 * (size_t)t1 + q], c = tab[6 * (size_t)t2 + q];
+    va[4 * q] = a.x; va[4 * q + 1] = a.y; va[4 * q + 2] = a.z; va[4 * q + 3] = a.w;
+    vb[4 * q] = b.x; vb[4 * q + 1] = b.y; vb[4 * q + 2] = b.z; vb[4 * q + 3] = b.w;
+    vc[4 * q] = c.x; vc[4 * q + 1] = c.y; vc[4 * q + 2] = c.z; vc[4 * q + 3] = c.w;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) d[k] = (w0 * va[k] + w1 * vb[k]) + w2 * vc[k];
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    Rb[k] = (w0 * va[4 + k] + w1 * vb[4 + k]) + w2 * vc[4 + k];
+    Sb[k] = (w0 * va[13 + k] + w1 * vb[13 + k]) + w2 * vc[13 + k];
+  }
+}
+
+// Rt = Rb^T (the rotation the colour's view direction is turned by), O = (Rt Sb) C (Rt Sb)^T: deform_kernel's chain
+__device__ __forceinline__ void deform_cov(const float* Rb, const float* Sb, const float* C, float* Rt, float* O) {
+  float RS[9], A[9];
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = 0; b < 3; b++) Rt[3 * a + b] = Rb[3 * b + a];
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = 0; b < 3; b++) RS[3 * a + b] = (Rt[3 * a] * Sb[b] + Rt[3 * a + 1] * Sb[3 + b]) + Rt[3 * a + 2] * Sb[6 + b];
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = 0; b < 3; b++) A[3 * a + b] = (RS[3 * a] * C[b] + RS[3 * a + 1] * C[3 + b]) + RS[3 * a + 2] * C[6 + b];
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = 0; b < 3; b++) O[3 * a + b] = (A[3 * a] * RS[3 * b] + A[3 * a + 1] * RS[3 * b + 1]) + A[3 * a + 2] * RS[3 * b + 2];
+}
+
+// The edit tool's colour: SH of the view direction turned back into the rest frame (sh_colors_kernel with rot = Rt), from the
+// thread's staged row
+__device__ __forceinline__ void shade_rotated(int deg, const float* Rt, const float* npos, const float* __restrict__ campos, const float4* row,
+                                              float* col) {
+  float dx = npos[0] - campos[0], dy = npos[1] - campos[1], dz = npos[2] - campos[2];
+  const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+  dx = dx / len; dy = dy / len; dz = dz / len;
+  // dir_rot = rot^T dir with rot = Rt
+  const float x = (Rt[0] * dx + Rt[3] * dy) + Rt[6] * dz;
+  const float y = (Rt[1] * dx + Rt[4] * dy) + Rt[7] * dz;
+  const float z = (Rt[2] * dx + Rt[5] * dy) + Rt[8] * dz;
+  float sh[48];
+#pragma unroll
+  for (int c = 0; c < 12; c++) {
+    const float4 v = row[c];
+    sh[4 * c] = v.x; sh[4 * c + 1] = v.y; sh[4 * c + 2] = v.z; sh[4 * c + 3] = v.w;
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) {
+    const float r = sh_channel(deg, [&](int k) { return sh[3 * k + ch]; }, x, y, z);
+    col[ch] = fmaxf(r + 0.5f, 0.0f);
+  }
+}
+
+// Where a fused pass leaves a row's preprocess results: the frame's geometry buffer and the caller's radii
+struct PreSinks { float4* splat; int* radii_int; int* radii_out; uint32_t* tiles; uint4* bin; uint32_t* counters; uint32_t* slots; uint32_t* coarse; uint32_t* depth_key; };
+
+static PreSinks pre_sinks(const GeomState& g, int* radii) {
+  return PreSinks{g.splat, g.radii, radii, g.tiles_touched, g.bin, g.counters, g.slots, g.coarse, g.depth_key};
+}
+
+// Written once, where it is read: the radius goes to the caller's array (the internal copy exists for callers that pass none);
+// the clamp flags and the per-Gaussian instance count are read by the backward pass and by the emission of a rectangle with
+// 65535 instances or more only - a frame of this path has no backward, and the count rides in the emission record otherwise
+// (9 of 349 bytes per Gaussian in a kernel that runs at the HBM's pace).  DIRECT: the record and the depth key go to the
+// bucket's slab instead (direct_store).
+template <bool DIRECT>
+__device__ __forceinline__ void pre_write_row(const PreSinks& o, size_t i, int radius_i, uint32_t tiles, const uint4& dbin, uint32_t dkey,
+                                              int tile_cull) {
+  if (o.radii_out) o.radii_out[i] = radius_i; else o.radii_int[i] = radius_i;
+  if (tiles >= GM_BIN_COUNT_SAT) o.tiles[i] = tiles;
+  if (!DIRECT) {
+    o.bin[i] = dbin;
+    o.depth_key[i] = dkey;
+  }
+  if (i == 0) o.counters[GM_CNT_POLICY] = (uint32_t)tile_cull;
+}
+
+static PreCam pre_cam(int W, int H, int tile_cull, const float* view, const float* proj, float tanx, float tany) {
+  PreCam c;
+  c.W = W; c.H = H; c.gx = (W + GM_TILE - 1) / GM_TILE; c.gy = (H + GM_TILE - 1) / GM_TILE;
+  c.tile_cull = tile_cull; c.view = view; c.proj = proj;
+  c.tanx = tanx; c.tany = tany;
+  c.fy = H / (2.0f * tany); c.fx = W / (2.0f * tanx);      // rasterizer_impl.cu:359-360
+  return c;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Fused edit-loop kernel: deform + view-dependent colour in one pass (what ObjectVisualTool.render_gaussian needs per
 // frame: means3D = x', colors_precomp, cov3D_precomp = strip_symmetric(Sigma'); edittool/__init__.py:421-472), and with PRE
 // also the forward preprocess of the Gaussian it just produced.
@@ -128,7 +267,7 @@ int launch_sh_colors(int N, int deg, int M, const float* pos, const float* campo
 struct FusedPre {
   PreCam cam;
   const float* opac;
-  float4* splat; int* radii_int; int* radii_out; uint32_t* tiles; uint4* bin; uint32_t* counters; uint32_t* slots; uint32_t* coarse; uint8_t* clamped; uint32_t* depth_key;
+  PreSinks out;
   // DIRECT (gm_common.h, DepthSlab): the frame's snapshot of the stream's depth table and the bucket slabs the records are appended to
   const uint32_t* dmap; uint32_t* slab_cnt; uint2* slab_pairs; uint4* slab_recs; uint32_t slab_cap;
   int cov6;                     // the rest covariances come as [N][6] (a caller whose matrices are bit-symmetric: deform.pack_cov6)
@@ -188,7 +327,6 @@ __global__ __launch_bounds__(64) void deform_shade_kernel(int N, int deg, const 
                                                           const float* __restrict__ campos, float* __restrict__ pos_out,
                                                           float* __restrict__ cov6_out, float* __restrict__ rgb_out,
                                                           float* __restrict__ cov_out, float* __restrict__ rot_out, const FusedPre fp) {
-  constexpr int DS_THREADS = 64;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float4* l_sh = reinterpret_cast<float4*>(lds);   // [64][12] granules: linear image of the block's SH rows (12 KiB)
   const size_t row0 = (size_t)blockIdx.x * DS_THREADS;
@@ -205,44 +343,12 @@ __global__ __launch_bounds__(64) void deform_shade_kernel(int N, int deg, const 
   }
   // ids are in (first use below waits for them); now start the row DMA, then the vertex gathers behind it
   __builtin_amdgcn_sched_barrier(0);
-  if (nrows == DS_THREADS) {
-    const char* gsh = reinterpret_cast<const char*>(shs + row0 * 48) + t * 16;
-#pragma unroll
-    for (int q = 0; q < 12; q++) dma16(gsh + q * 1024, reinterpret_cast<char*>(l_sh) + q * 1024);
-  } else if (live) {                               // last, partial block: plain copies of the thread's own rows
-#pragma unroll
-    for (int c = 0; c < 12; c++) l_sh[t * 12 + c] = reinterpret_cast<const float4*>(shs)[i * 12 + c];
-  }
-  // the covariance row goes straight to registers (36 B per lane, the wave's 2304 B are contiguous): staging it as well
-  // would cost 2.25 KiB of LDS per wave, i.e. two resident waves per CU
+  stage_sh_rows(l_sh, shs, row0, nrows, t, i);
   float C[9];
-  if (PRE && fp.cov6) {                            // (wave-uniform) rest covariance as its six distinct entries xx xy xz yy yz zz: 24 B per lane
-    float c6[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) c6[k] = live ? cov[i * 6 + k] : 0.f;
-    C[0] = c6[0]; C[1] = c6[1]; C[2] = c6[2]; C[3] = c6[1]; C[4] = c6[3]; C[5] = c6[4]; C[6] = c6[2]; C[7] = c6[4]; C[8] = c6[5];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 9; k++) C[k] = live ? cov[i * 9 + k] : 0.f;
-  }
+  load_rest_cov(C, cov, i, live, PRE && fp.cov6);
   float d[3], Rb[9], Sb[9];
   if (PACKED) {
-    const float4* tab = reinterpret_cast<const float4*>(dV);
-    float va[24], vb[24], vc[24];
-#pragma unroll
-    for (int q = 0; q < 6; q++) {
-      const float4 a = tab[6 * (size_t)t0 + q], b = tab[6 * (size_t)t1 + q], c = tab[6 * (size_t)t2 + q];
-      va[4 * q] = a.x; va[4 * q + 1] = a.y; va[4 * q + 2] = a.z; va[4 * q + 3] = a.w;
-      vb[4 * q] = b.x; vb[4 * q + 1] = b.y; vb[4 * q + 2] = b.z; vb[4 * q + 3] = b.w;
-      vc[4 * q] = c.x; vc[4 * q + 1] = c.y; vc[4 * q + 2] = c.z; vc[4 * q + 3] = c.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) d[k] = (w0 * va[k] + w1 * vb[k]) + w2 * vc[k];
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-      Rb[k] = (w0 * va[4 + k] + w1 * vb[4 + k]) + w2 * vc[4 + k];
-      Sb[k] = (w0 * va[13 + k] + w1 * vb[13 + k]) + w2 * vc[13 + k];
-    }
+    gather_blend(reinterpret_cast<const float4*>(dV), t0, t1, t2, w0, w1, w2, d, Rb, Sb);
   } else {
 #pragma unroll
     for (int k = 0; k < 3; k++) d[k] = (w0 * dV[3 * (size_t)t0 + k] + w1 * dV[3 * (size_t)t1 + k]) + w2 * dV[3 * (size_t)t2 + k];
@@ -254,44 +360,9 @@ __global__ __launch_bounds__(64) void deform_shade_kernel(int N, int deg, const 
   }
   __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): the DMA has landed
   __syncthreads();
-  {
-    float RS[9], A[9];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-      for (int b = 0; b < 3; b++) Rt[3 * a + b] = Rb[3 * b + a];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-      for (int b = 0; b < 3; b++) RS[3 * a + b] = (Rt[3 * a] * Sb[b] + Rt[3 * a + 1] * Sb[3 + b]) + Rt[3 * a + 2] * Sb[6 + b];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-      for (int b = 0; b < 3; b++) A[3 * a + b] = (RS[3 * a] * C[b] + RS[3 * a + 1] * C[3 + b]) + RS[3 * a + 2] * C[6 + b];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-      for (int b = 0; b < 3; b++) O[3 * a + b] = (A[3 * a] * RS[3 * b] + A[3 * a + 1] * RS[3 * b + 1]) + A[3 * a + 2] * RS[3 * b + 2];
-    npos[0] = p0 + d[0]; npos[1] = p1 + d[1]; npos[2] = p2 + d[2];
-    float dx = npos[0] - campos[0], dy = npos[1] - campos[1], dz = npos[2] - campos[2];
-    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-    dx = dx / len; dy = dy / len; dz = dz / len;
-    // dir_rot = rot^T dir with rot = Rt
-    const float x = (Rt[0] * dx + Rt[3] * dy) + Rt[6] * dz;
-    const float y = (Rt[1] * dx + Rt[4] * dy) + Rt[7] * dz;
-    const float z = (Rt[2] * dx + Rt[5] * dy) + Rt[8] * dz;
-    float sh[48];
-#pragma unroll
-    for (int c = 0; c < 12; c++) {
-      const float4 v = l_sh[t * 12 + c];
-      sh[4 * c] = v.x; sh[4 * c + 1] = v.y; sh[4 * c + 2] = v.z; sh[4 * c + 3] = v.w;
-    }
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-      const float r = sh_channel(deg, [&](int k) { return sh[3 * k + ch]; }, x, y, z);
-      col[ch] = fmaxf(r + 0.5f, 0.0f);
-    }
-  }
+  deform_cov(Rb, Sb, C, Rt, O);
+  npos[0] = p0 + d[0]; npos[1] = p1 + d[1]; npos[2] = p2 + d[2];
+  shade_rotated(deg, Rt, npos, campos, l_sh + t * 12, col);
   // ---- forward preprocess of the deformed Gaussian (colors_precomp / cov3D_precomp input mode)
   uint32_t tiles = 0, dkey = 0xFFFFFFFFu;
   uint4 dbin = make_uint4(0u, 0u, 0u, 0u);
@@ -309,24 +380,14 @@ __global__ __launch_bounds__(64) void deform_shade_kernel(int N, int deg, const 
     int radius_i = 0;
     if (vis) {
       const float opac = fp.opac[i];
-      splat_store(fp.splat, i, pg.pix, pg.piy, pg.conx, pg.cony, pg.conz, opac, col[0], col[1], col[2], pg.depth);
+      splat_store(fp.out.splat, i, pg.pix, pg.piy, pg.conx, pg.cony, pg.conz, opac, col[0], col[1], col[2], pg.depth);
       radius_i = (int)pg.radius;
       pre_emit(fp.cam, pg, opac, tiles, dbin);
     }
-    // Written once, where it is read: the radius goes to the caller's array (the internal copy exists for callers that pass none);
-    // the clamp flags and the per-Gaussian instance count are read by the backward pass and by the emission of a rectangle with
-    // 65535 instances or more only - a frame of this path has no backward, and the count rides in the emission record otherwise
-    // (9 of 349 bytes per Gaussian in a kernel that runs at the HBM's pace)
-    if (fp.radii_out) fp.radii_out[i] = radius_i; else fp.radii_int[i] = radius_i;
-    if (tiles >= GM_BIN_COUNT_SAT) fp.tiles[i] = tiles;
-    if (!DIRECT) {
-      fp.bin[i] = dbin;
-      fp.depth_key[i] = dkey;
-    }
-    if (i == 0) fp.counters[GM_CNT_POLICY] = (uint32_t)fp.cam.tile_cull;
+    pre_write_row<DIRECT>(fp.out, i, radius_i, tiles, dbin, dkey, fp.cam.tile_cull);
   }
   if (PRE && DIRECT) direct_store(fp, slot, (uint32_t)i, dkey, dbin);
-  if (PRE) slot_accumulate(fp.slots, fp.coarse, tiles, dkey);
+  if (PRE) slot_accumulate(fp.out.slots, fp.out.coarse, tiles, dkey);
   if (!pos_out) return;                          // wave-uniform
   __syncthreads();                               // everyone is done reading the staged inputs: reuse LDS for the outputs
   float* o_pos = lds;                            // [256][3]
@@ -357,19 +418,18 @@ __global__ __launch_bounds__(64) void deform_shade_kernel(int N, int deg, const 
 // 192, opacity 4 - and a render loop with several frames in flight streamed them from HBM once per frame.  Here a wave loads them once
 // (the SH rows stay in LDS, the rest in ~20 registers) and loops over the batch's frames: gather the frame's per-vertex table (L2
 // resident: 0.7 MB per frame), deform, rotated-direction SH colour, project, emission record -> the frame's own geometry buffer.  Every
-// expression is the one deform_shade_kernel<true, true> evaluates, in the same order, contraction off: each frame's geometry buffer comes
-// out bit for bit as from the single-frame launch (tests/test_gpu_batch.py).
+// expression is the one deform_shade_kernel<true, true> evaluates (the row body above, called in the same order), contraction off: each
+// frame's geometry buffer comes out bit for bit as from the single-frame launch (tests/test_gpu_batch.py).
 struct FusedFrame {
   PreCam cam;
   const float4* tab; const float* campos;
-  float4* splat; int* radii_int; int* radii_out; uint32_t* tiles; uint4* bin; uint32_t* counters; uint32_t* slots; uint32_t* coarse; uint32_t* depth_key;
+  PreSinks out;
 };
 struct FusedBatch { int frames, cov6; const float* opac; FusedFrame f[GM_BATCH_MAX]; };
 
 __global__ __launch_bounds__(64) void deform_shade_pre_batch_kernel(int N, int deg, const int* __restrict__ tri, const float* __restrict__ w,
                                                                      const float* __restrict__ cov, const float* __restrict__ pos,
                                                                      const float* __restrict__ shs, const FusedBatch fb) {
-  constexpr int DS_THREADS = 64;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float4* l_sh = reinterpret_cast<float4*>(lds);   // [64][12] granules: linear image of the block's SH rows (12 KiB)
   const size_t row0 = (size_t)blockIdx.x * DS_THREADS;
@@ -385,87 +445,19 @@ __global__ __launch_bounds__(64) void deform_shade_pre_batch_kernel(int N, int d
     opac = fb.opac[i];
   }
   __builtin_amdgcn_sched_barrier(0);
-  if (nrows == DS_THREADS) {
-    const char* gsh = reinterpret_cast<const char*>(shs + row0 * 48) + t * 16;
-#pragma unroll
-    for (int q = 0; q < 12; q++) dma16(gsh + q * 1024, reinterpret_cast<char*>(l_sh) + q * 1024);
-  } else if (live) {
-#pragma unroll
-    for (int c = 0; c < 12; c++) l_sh[t * 12 + c] = reinterpret_cast<const float4*>(shs)[i * 12 + c];
-  }
+  stage_sh_rows(l_sh, shs, row0, nrows, t, i);
   float C[9];
-  if (fb.cov6) {
-    float c6[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) c6[k] = live ? cov[i * 6 + k] : 0.f;
-    C[0] = c6[0]; C[1] = c6[1]; C[2] = c6[2]; C[3] = c6[1]; C[4] = c6[3]; C[5] = c6[4]; C[6] = c6[2]; C[7] = c6[4]; C[8] = c6[5];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 9; k++) C[k] = live ? cov[i * 9 + k] : 0.f;
-  }
+  load_rest_cov(C, cov, i, live, fb.cov6);
   __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): the DMA has landed
   __syncthreads();
 #pragma unroll 1
   for (int f = 0; f < fb.frames; f++) {
     const FusedFrame& F = fb.f[f];
-    float d[3], Rb[9], Sb[9];
-    {
-      const float4* tab = F.tab;
-      float va[24], vb[24], vc[24];
-#pragma unroll
-      for (int q = 0; q < 6; q++) {
-        const float4 a = tab[6 * (size_t)t0 + q], b = tab[6 * (size_t)t1 + q], c = tab[6 * (size_t)t2 + q];
-        va[4 * q] = a.x; va[4 * q + 1] = a.y; va[4 * q + 2] = a.z; va[4 * q + 3] = a.w;
-        vb[4 * q] = b.x; vb[4 * q + 1] = b.y; vb[4 * q + 2] = b.z; vb[4 * q + 3] = b.w;
-        vc[4 * q] = c.x; vc[4 * q + 1] = c.y; vc[4 * q + 2] = c.z; vc[4 * q + 3] = c.w;
-      }
-#pragma unroll
-      for (int k = 0; k < 3; k++) d[k] = (w0 * va[k] + w1 * vb[k]) + w2 * vc[k];
-#pragma unroll
-      for (int k = 0; k < 9; k++) {
-        Rb[k] = (w0 * va[4 + k] + w1 * vb[4 + k]) + w2 * vc[4 + k];
-        Sb[k] = (w0 * va[13 + k] + w1 * vb[13 + k]) + w2 * vc[13 + k];
-      }
-    }
-    float O[9], Rt[9], npos[3], col[3];
-    {
-      float RS[9], A[9];
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) Rt[3 * a + b] = Rb[3 * b + a];
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) RS[3 * a + b] = (Rt[3 * a] * Sb[b] + Rt[3 * a + 1] * Sb[3 + b]) + Rt[3 * a + 2] * Sb[6 + b];
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) A[3 * a + b] = (RS[3 * a] * C[b] + RS[3 * a + 1] * C[3 + b]) + RS[3 * a + 2] * C[6 + b];
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) O[3 * a + b] = (A[3 * a] * RS[3 * b] + A[3 * a + 1] * RS[3 * b + 1]) + A[3 * a + 2] * RS[3 * b + 2];
-      npos[0] = p0 + d[0]; npos[1] = p1 + d[1]; npos[2] = p2 + d[2];
-      const float* campos = F.campos;
-      float dx = npos[0] - campos[0], dy = npos[1] - campos[1], dz = npos[2] - campos[2];
-      const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-      dx = dx / len; dy = dy / len; dz = dz / len;
-      const float x = (Rt[0] * dx + Rt[3] * dy) + Rt[6] * dz;
-      const float y = (Rt[1] * dx + Rt[4] * dy) + Rt[7] * dz;
-      const float z = (Rt[2] * dx + Rt[5] * dy) + Rt[8] * dz;
-      float sh[48];
-#pragma unroll
-      for (int c = 0; c < 12; c++) {
-        const float4 v = l_sh[t * 12 + c];
-        sh[4 * c] = v.x; sh[4 * c + 1] = v.y; sh[4 * c + 2] = v.z; sh[4 * c + 3] = v.w;
-      }
-#pragma unroll
-      for (int ch = 0; ch < 3; ch++) {
-        const float r = sh_channel(deg, [&](int k) { return sh[3 * k + ch]; }, x, y, z);
-        col[ch] = fmaxf(r + 0.5f, 0.0f);
-      }
-    }
+    float d[3], Rb[9], Sb[9], O[9], Rt[9], npos[3], col[3];
+    gather_blend(F.tab, t0, t1, t2, w0, w1, w2, d, Rb, Sb);
+    deform_cov(Rb, Sb, C, Rt, O);
+    npos[0] = p0 + d[0]; npos[1] = p1 + d[1]; npos[2] = p2 + d[2];
+    shade_rotated(deg, Rt, npos, F.campos, l_sh + t * 12, col);
     uint32_t tiles = 0, dkey = 0xFFFFFFFFu;
     uint4 dbin = make_uint4(0u, 0u, 0u, 0u);
     PreGeom pg;
@@ -477,32 +469,20 @@ __global__ __launch_bounds__(64) void deform_shade_pre_batch_kernel(int N, int d
       if (vis) dkey = __float_as_uint(pg.depth);
       int radius_i = 0;
       if (vis) {
-        splat_store(F.splat, i, pg.pix, pg.piy, pg.conx, pg.cony, pg.conz, opac, col[0], col[1], col[2], pg.depth);
+        splat_store(F.out.splat, i, pg.pix, pg.piy, pg.conx, pg.cony, pg.conz, opac, col[0], col[1], col[2], pg.depth);
         radius_i = (int)pg.radius;
         pre_emit(F.cam, pg, opac, tiles, dbin);
       }
-      if (F.radii_out) F.radii_out[i] = radius_i; else F.radii_int[i] = radius_i;
-      if (tiles >= GM_BIN_COUNT_SAT) F.tiles[i] = tiles;
-      F.bin[i] = dbin;
-      F.depth_key[i] = dkey;
-      if (i == 0) F.counters[GM_CNT_POLICY] = (uint32_t)F.cam.tile_cull;
+      pre_write_row<false>(F.out, i, radius_i, tiles, dbin, dkey, F.cam.tile_cull);
     }
-    slot_accumulate(F.slots, F.coarse, tiles, dkey);
+    slot_accumulate(F.out.slots, F.out.coarse, tiles, dkey);
   }
 }
 
 // one frame of a batched fused pass: camera constants and the frame's geometry buffer (shared by the object and the scene batch)
 static FusedFrame fused_frame(const BatchFrameArgs& a, int W, int H, int tile_cull) {
-  FusedFrame F{};
-  F.cam.W = W; F.cam.H = H; F.cam.gx = (W + GM_TILE - 1) / GM_TILE; F.cam.gy = (H + GM_TILE - 1) / GM_TILE;
-  F.cam.tile_cull = tile_cull; F.cam.view = a.viewmatrix; F.cam.proj = a.projmatrix;
-  F.cam.tanx = a.tan_fovx; F.cam.tany = a.tan_fovy;
-  F.cam.fy = H / (2.0f * a.tan_fovy); F.cam.fx = W / (2.0f * a.tan_fovx);      // rasterizer_impl.cu:359-360
-  F.tab = reinterpret_cast<const float4*>(a.packed); F.campos = a.cam_pos;
-  const GeomState& g = a.g;
-  F.splat = g.splat; F.radii_int = g.radii; F.radii_out = a.radii; F.tiles = g.tiles_touched; F.bin = g.bin; F.counters = g.counters; F.slots = g.slots;
-  F.coarse = g.coarse; F.depth_key = g.depth_key;
-  return F;
+  return FusedFrame{pre_cam(W, H, tile_cull, a.viewmatrix, a.projmatrix, a.tan_fovx, a.tan_fovy), reinterpret_cast<const float4*>(a.packed),
+                    a.cam_pos, pre_sinks(a.g, a.radii)};
 }
 
 int launch_deform_shade_pre_batch(int frames, const BatchFrameArgs* fr, int P, int deg, int W, int H, int tile_cull, const int* tri, const float* w,
@@ -573,13 +553,9 @@ int launch_deform_shade_pre(const RasterArgs& r, GeomState& g, int* radii, int d
   }
   StageScope sc(ST_DEFORM, r.stream);
   FusedPre fp;
-  fp.cam.W = r.W; fp.cam.H = r.H; fp.cam.gx = (r.W + GM_TILE - 1) / GM_TILE; fp.cam.gy = (r.H + GM_TILE - 1) / GM_TILE;
-  fp.cam.tile_cull = r.tile_cull; fp.cam.view = r.viewmatrix; fp.cam.proj = r.projmatrix;
-  fp.cam.tanx = r.tan_fovx; fp.cam.tany = r.tan_fovy;
-  fp.cam.fy = r.H / (2.0f * r.tan_fovy); fp.cam.fx = r.W / (2.0f * r.tan_fovx);   // rasterizer_impl.cu:359-360
+  fp.cam = pre_cam(r.W, r.H, r.tile_cull, r.viewmatrix, r.projmatrix, r.tan_fovx, r.tan_fovy);
   fp.opac = r.opacities;
-  fp.splat = g.splat; fp.radii_int = g.radii; fp.radii_out = radii; fp.tiles = g.tiles_touched; fp.bin = g.bin; fp.counters = g.counters; fp.slots = g.slots; fp.coarse = g.coarse;
-  fp.clamped = g.clamped; fp.depth_key = g.depth_key;
+  fp.out = pre_sinks(g, radii);
   fp.cov6 = cov6 ? 1 : 0;
   fp.dmap = g.dmap; fp.slab_cnt = nullptr; fp.slab_pairs = nullptr; fp.slab_recs = nullptr; fp.slab_cap = 0;
   if (slab) { fp.slab_cnt = slab->cnt; fp.slab_pairs = slab->pairs; fp.slab_recs = slab->recs; fp.slab_cap = slab->cap; }
@@ -669,7 +645,6 @@ __global__ __launch_bounds__(64) void scene_shade_pre_batch_kernel(int N, int de
                                                                    const float* __restrict__ rots, const float* __restrict__ shs,
                                                                    const int* __restrict__ tri, const float* __restrict__ w,
                                                                    const float* __restrict__ cov, const SceneBatch sb) {
-  constexpr int DS_THREADS = 64;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float4* l_sh = reinterpret_cast<float4*>(lds);   // [64][12] granules: linear image of the block's SH rows (12 KiB)
   const size_t row0 = (size_t)blockIdx.x * DS_THREADS;
@@ -698,17 +673,9 @@ __global__ __launch_bounds__(64) void scene_shade_pre_batch_kernel(int N, int de
     w0 = w[3 * r]; w1 = w[3 * r + 1]; w2 = w[3 * r + 2];
   }
   __builtin_amdgcn_sched_barrier(0);
-  if (nrows == DS_THREADS) {
-    const char* gsh = reinterpret_cast<const char*>(shs + row0 * 48) + t * 16;
-#pragma unroll
-    for (int q = 0; q < 12; q++) dma16(gsh + q * 1024, reinterpret_cast<char*>(l_sh) + q * 1024);
-  } else if (live) {
-#pragma unroll
-    for (int c = 0; c < 12; c++) l_sh[t * 12 + c] = reinterpret_cast<const float4*>(shs)[i * 12 + c];
-  }
+  stage_sh_rows(l_sh, shs, row0, nrows, t, i);
   float C[9];                                      // the rest covariance of a movable row
-#pragma unroll
-  for (int k = 0; k < 9; k++) C[k] = moving ? cov[r * 9 + k] : 0.f;
+  load_rest_cov(C, cov, r, moving, false);
   __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): the DMA has landed
   __syncthreads();
 #pragma unroll 1
@@ -718,39 +685,9 @@ __global__ __launch_bounds__(64) void scene_shade_pre_batch_kernel(int N, int de
     float4 q = q0;
     float sc[3] = {s0, s1, s2};
     if (moving && ((sb.mask[f] >> obj) & 1u)) {
-      const float4* tab = F.tab;
-      float va[24], vb[24], vc[24];
-#pragma unroll
-      for (int u = 0; u < 6; u++) {
-        const float4 a = tab[6 * (size_t)t0 + u], b = tab[6 * (size_t)t1 + u], c = tab[6 * (size_t)t2 + u];
-        va[4 * u] = a.x; va[4 * u + 1] = a.y; va[4 * u + 2] = a.z; va[4 * u + 3] = a.w;
-        vb[4 * u] = b.x; vb[4 * u + 1] = b.y; vb[4 * u + 2] = b.z; vb[4 * u + 3] = b.w;
-        vc[4 * u] = c.x; vc[4 * u + 1] = c.y; vc[4 * u + 2] = c.z; vc[4 * u + 3] = c.w;
-      }
-      float d[3], Rb[9], Sb[9], Rt[9], RS[9], A[9], O[9];
-#pragma unroll
-      for (int k = 0; k < 3; k++) d[k] = (w0 * va[k] + w1 * vb[k]) + w2 * vc[k];
-#pragma unroll
-      for (int k = 0; k < 9; k++) {
-        Rb[k] = (w0 * va[4 + k] + w1 * vb[4 + k]) + w2 * vc[4 + k];
-        Sb[k] = (w0 * va[13 + k] + w1 * vb[13 + k]) + w2 * vc[13 + k];
-      }
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) Rt[3 * a + b] = Rb[3 * b + a];
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) RS[3 * a + b] = (Rt[3 * a] * Sb[b] + Rt[3 * a + 1] * Sb[3 + b]) + Rt[3 * a + 2] * Sb[6 + b];
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) A[3 * a + b] = (RS[3 * a] * C[b] + RS[3 * a + 1] * C[3 + b]) + RS[3 * a + 2] * C[6 + b];
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) O[3 * a + b] = (A[3 * a] * RS[3 * b] + A[3 * a + 1] * RS[3 * b + 1]) + A[3 * a + 2] * RS[3 * b + 2];
+      float d[3], Rb[9], Sb[9], Rt[9], O[9];         // (Rt: the scene's colour takes the unrotated direction)
+      gather_blend(F.tab, t0, t1, t2, w0, w1, w2, d, Rb, Sb);
+      deform_cov(Rb, Sb, C, Rt, O);
       p = V3{p0 + d[0], p1 + d[1], p2 + d[2]};
       if (!(xform4x3(p, F.cam.view).z <= 0.2f)) cov_to_scale_rot_row(O, &q, sc, 0);     // (not culled by pre_project's near-plane test)
     }
@@ -766,17 +703,13 @@ __global__ __launch_bounds__(64) void scene_shade_pre_batch_kernel(int N, int de
         float col[3];
         sh_color(deg, p, F.campos, l_sh + t * 12, col);
         dkey = __float_as_uint(pg.depth);
-        splat_store(F.splat, i, pg.pix, pg.piy, pg.conx, pg.cony, pg.conz, opac, col[0], col[1], col[2], pg.depth);
+        splat_store(F.out.splat, i, pg.pix, pg.piy, pg.conx, pg.cony, pg.conz, opac, col[0], col[1], col[2], pg.depth);
         radius_i = (int)pg.radius;
         pre_emit(F.cam, pg, opac, tiles, dbin);
       }
-      if (F.radii_out) F.radii_out[i] = radius_i; else F.radii_int[i] = radius_i;
-      if (tiles >= GM_BIN_COUNT_SAT) F.tiles[i] = tiles;
-      F.bin[i] = dbin;
-      F.depth_key[i] = dkey;
-      if (i == 0) F.counters[GM_CNT_POLICY] = (uint32_t)F.cam.tile_cull;
+      pre_write_row<false>(F.out, i, radius_i, tiles, dbin, dkey, F.cam.tile_cull);
     }
-    slot_accumulate(F.slots, F.coarse, tiles, dkey);
+    slot_accumulate(F.out.slots, F.out.coarse, tiles, dkey);
   }
 }
 

@@ -546,6 +546,51 @@ def forward_deformed_begin(bg, tri, weights, packed, cov, pos, shs, opacity, vie
     return _begin(device, () if workspace is None else (workspace,), issue)[0]
 
 
+def _batch_begin(name, each, first_frame, per_frame, device, bg, P, image_height, image_width, emission_policy, debug, aux, keep, call):
+    """What forward_deformed_batch and forward_scene_batch (`name`) share.  per_frame = (packed_list, cameras, workspaces, ...): the lists
+    with one entry per frame (`each` names them in the refusal; a gather table may be None).  Checks them, then through _begin: per frame
+    the scratch of its workspace, its _lib.BatchFrame and its PendingForward (args["keep"] = keep + the frame's own tensors), then
+    call(policy, K, frames, W, H, cap, stream, handles) - the C entry point - and behind it the status events: the handles come back in
+    the state finish(sync_free=True) leaves them in.  first_frame: how a stream gets its first capacity (for the refusal)."""
+    lib = _lib.lib()
+    packed_list, cameras, workspaces = per_frame[:3]
+    K = len(per_frame[0])
+    if not (1 <= K <= _lib.GM_BATCH_MAX) or any(len(l) != K for l in per_frame):
+        raise ValueError("%s: 1..%d frames, %s each" % (name, _lib.GM_BATCH_MAX, each))
+    if len({id(w_) for w_ in workspaces}) != K:
+        raise ValueError("%s: the frames of a batch need distinct workspaces" % name)
+    policy = _pol(emission_policy, image_width, image_height)
+    H, W = int(image_height), int(image_width)
+    cap = max(ws.capacity for ws in workspaces)
+    if cap <= 0:
+        raise _lib.GmeshError("%s: the workspaces have no capacity yet - complete one frame of the stream through %s first "
+                              "(the batch is sync-free: it cannot size the binning buffers)" % (name, first_frame))
+    get = lambda c, k: c[k] if isinstance(c, dict) else getattr(c, k)
+
+    def issue(stream):
+        handles, frames = [], (_lib.BatchFrame * K)()
+        nbin = lib.gm_binning_bytes(cap)
+        for k, (ws, c) in enumerate(zip(workspaces, cameras)):
+            ws.capacity = cap
+            color, radii, geom, img, _, _, maps = _scratch(ws, P, W, H, device, aux=aux)
+            binning = ws.get("binning", nbin, device)
+            view, proj, campos, packed = (_prep(t, device) for t in (get(c, "view"), get(c, "proj"), get(c, "campos"), packed_list[k]))
+            f = frames[k]
+            f.packed, f.viewmatrix, f.projmatrix, f.cam_pos = _ptr(packed), view.data_ptr(), proj.data_ptr(), campos.data_ptr()
+            f.tan_fovx, f.tan_fovy = float(get(c, "tanx")), float(get(c, "tany"))
+            f.geom_buffer, f.binning_buffer, f.image_buffer = geom.data_ptr(), binning.data_ptr(), img.data_ptr()
+            f.out_color, f.radii, f.status_host = color.data_ptr(), radii.data_ptr(), ws.status()[0].data_ptr()
+            args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)), keep=keep + ((view, proj, campos, packed),))
+            handles.append(PendingForward(policy, ws, stream, args, geom, img, color, radii, None, None, binning=binning, maps=maps))
+        call(policy, K, frames, W, H, cap, stream, handles)
+        for h in handles:
+            h.status_event = h.workspace.status()[1]
+            h.status_event.record(stream)
+            h.result = h._outputs(-1, h.binning)
+        return handles
+    return _begin(device, workspaces, issue)
+
+
 def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity, cameras, image_height, image_width, degree, workspaces,
                            image_only=True, work_hint=None, emission_policy=None, debug=False, aux=False):
     """K frames of one view stream in ONE launch chain (gm_forward_deformed_batch_async): the static cloud is read from HBM once for the
@@ -560,54 +605,23 @@ def forward_deformed_batch(bg, tri, weights, packed_list, cov, pos, shs, opacity
     gm_forward_1_aux, so its maps are exact too."""
     lib = _lib.lib()
     device = pos.device
-    K = len(packed_list)
-    if not (1 <= K <= _lib.GM_BATCH_MAX) or len(cameras) != K or len(workspaces) != K:
-        raise ValueError("forward_deformed_batch: 1..%d frames, one camera and one workspace each" % _lib.GM_BATCH_MAX)
-    if len({id(w_) for w_ in workspaces}) != K:
-        raise ValueError("forward_deformed_batch: the frames of a batch need distinct workspaces")
-    policy = _pol(emission_policy, image_width, image_height)
     P, M = pos.shape[0], shs.shape[1]
     if tri.dtype is not torch.int32 or not tri.is_contiguous():
         tri = tri.detach().contiguous().to(torch.int32)
     weights, cov, pos, shs, opacity, bg = (_prep(t, device) for t in (weights, cov, pos, shs, opacity, bg))
-    H, W = int(image_height), int(image_width)
-    cap = max(ws.capacity for ws in workspaces)
-    if cap <= 0:
-        raise _lib.GmeshError("forward_deformed_batch: the workspaces have no capacity yet - complete one frame of the stream through "
-                              "forward_deformed_begin(...).finish() first (the batch is sync-free: it cannot size the binning buffers)")
     cov6 = cov is not None and cov.dim() == 2 and cov.shape[1] == 6
-    get = lambda c, k: c[k] if isinstance(c, dict) else getattr(c, k)
 
-    def issue(stream):
-        handles, frames = [], (_lib.BatchFrame * K)()
-        depth_ptrs, alpha_ptrs = (C.c_void_p * K)(), (C.c_void_p * K)()
-        nbin = lib.gm_binning_bytes(cap)
-        for k, (ws, c) in enumerate(zip(workspaces, cameras)):
-            ws.capacity = cap
-            color, radii, geom, img, _, _, maps = _scratch(ws, P, W, H, device, aux=aux)
-            if maps is not None:
-                depth_ptrs[k], alpha_ptrs[k] = maps[0].data_ptr(), maps[1].data_ptr()
-            binning = ws.get("binning", nbin, device)
-            view, proj, campos, packed = (_prep(t, device) for t in (get(c, "view"), get(c, "proj"), get(c, "campos"), packed_list[k]))
-            f = frames[k]
-            f.packed, f.viewmatrix, f.projmatrix, f.cam_pos = packed.data_ptr(), view.data_ptr(), proj.data_ptr(), campos.data_ptr()
-            f.tan_fovx, f.tan_fovy = float(get(c, "tanx")), float(get(c, "tany"))
-            f.geom_buffer, f.binning_buffer, f.image_buffer = geom.data_ptr(), binning.data_ptr(), img.data_ptr()
-            f.out_color, f.radii, f.status_host = color.data_ptr(), radii.data_ptr(), ws.status()[0].data_ptr()
-            args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)), keep=(tri, weights, cov, pos, shs, opacity, (view, proj, campos, packed)))
-            handles.append(PendingForward(policy, ws, stream, args, geom, img, color, radii, None, None, binning=binning, maps=maps))
-        call = (policy, K, frames, P, int(degree), M, W, H, _ptr(tri), _ptr(weights), _ptr(cov), _ptr(pos), _ptr(shs), _ptr(opacity), _ptr(bg), cap,
+    def call(policy, K, frames, W, H, cap, stream, handles):
+        args = (policy, K, frames, P, int(degree), M, W, H, _ptr(tri), _ptr(weights), _ptr(cov), _ptr(pos), _ptr(shs), _ptr(opacity), _ptr(bg), cap,
                 (1 if image_only else 0) | (2 if cov6 else 0), None if work_hint is None else work_hint.data_ptr(), int(bool(debug)), stream.cuda_stream)
         if aux:
-            _lib.check(lib.gm_forward_deformed_batch_aux_async(*call, depth_ptrs, alpha_ptrs))
+            depth_ptrs, alpha_ptrs = ((C.c_void_p * K)(*[h.maps[j].data_ptr() for h in handles]) for j in (0, 1))
+            _lib.check(lib.gm_forward_deformed_batch_aux_async(*args, depth_ptrs, alpha_ptrs))
         else:
-            _lib.check(lib.gm_forward_deformed_batch_async(*call))
-        for h in handles:
-            h.status_event = h.workspace.status()[1]
-            h.status_event.record(stream)
-            h.result = h._outputs(-1, h.binning)
-        return handles
-    return _begin(device, workspaces, issue)
+            _lib.check(lib.gm_forward_deformed_batch_async(*args))
+    return _batch_begin("forward_deformed_batch", "one camera and one workspace", "forward_deformed_begin(...).finish()",
+                        (packed_list, cameras, workspaces), device, bg, P, image_height, image_width, emission_policy, debug, aux,
+                        (tri, weights, cov, pos, shs, opacity), call)
 
 
 def forward_scene_batch(bg, object_rows, deformed, pos, scales, rotations, shs, opacity, tri, weights, cov, packed_list, cameras, image_height,
@@ -623,52 +637,21 @@ def forward_scene_batch(bg, object_rows, deformed, pos, scales, rotations, shs, 
     exactly, by finish()."""
     lib = _lib.lib()
     device = pos.device
-    K = len(cameras)
-    if not (1 <= K <= _lib.GM_BATCH_MAX) or len(deformed) != K or len(packed_list) != K or len(workspaces) != K:
-        raise ValueError("forward_scene_batch: 1..%d frames, one mask, gather table, camera and workspace each" % _lib.GM_BATCH_MAX)
-    if len({id(w_) for w_ in workspaces}) != K:
-        raise ValueError("forward_scene_batch: the frames of a batch need distinct workspaces")
-    policy = _pol(emission_policy, image_width, image_height)
     P, M = pos.shape[0], shs.shape[1]
     if tri is not None and (tri.dtype is not torch.int32 or not tri.is_contiguous()):
         tri = tri.detach().contiguous().to(torch.int32)
     weights, cov, pos, scales, rotations, shs, opacity, bg = (_prep(t, device) for t in (weights, cov, pos, scales, rotations, shs, opacity, bg))
-    H, W = int(image_height), int(image_width)
-    cap = max(ws.capacity for ws in workspaces)
-    if cap <= 0:
-        raise _lib.GmeshError("forward_scene_batch: the workspaces have no capacity yet - complete one frame of the stream through the "
-                              "single-frame path first (the batch is sync-free: it cannot size the binning buffers)")
     rows = (C.c_int * len(object_rows))(*[int(r) for r in object_rows])
-    masks = (C.c_uint * K)(*[int(m) for m in deformed])
-    get = lambda c, k: c[k] if isinstance(c, dict) else getattr(c, k)
+    masks = (C.c_uint * len(deformed))(*[int(m) for m in deformed])
 
-    def issue(stream):
-        handles, frames = [], (_lib.BatchFrame * K)()
-        nbin = lib.gm_binning_bytes(cap)
-        for k, (ws, c) in enumerate(zip(workspaces, cameras)):
-            ws.capacity = cap
-            color, radii, geom, img, _, _, _ = _scratch(ws, P, W, H, device)
-            binning = ws.get("binning", nbin, device)
-            view, proj, campos = (_prep(t, device) for t in (get(c, "view"), get(c, "proj"), get(c, "campos")))
-            packed = None if packed_list[k] is None else _prep(packed_list[k], device)
-            f = frames[k]
-            f.packed, f.viewmatrix, f.projmatrix, f.cam_pos = _ptr(packed), view.data_ptr(), proj.data_ptr(), campos.data_ptr()
-            f.tan_fovx, f.tan_fovy = float(get(c, "tanx")), float(get(c, "tany"))
-            f.geom_buffer, f.binning_buffer, f.image_buffer = geom.data_ptr(), binning.data_ptr(), img.data_ptr()
-            f.out_color, f.radii, f.status_host = color.data_ptr(), radii.data_ptr(), ws.status()[0].data_ptr()
-            args = dict(device=device, P=P, W=W, H=H, bg=bg, debug=int(bool(debug)),
-                        keep=(tri, weights, cov, pos, scales, rotations, shs, opacity, (view, proj, campos, packed)))
-            handles.append(PendingForward(policy, ws, stream, args, geom, img, color, radii, None, None, binning=binning))
+    def call(policy, K, frames, W, H, cap, stream, handles):
         _lib.check(lib.gm_forward_scene_batch_async(policy, K, frames, P, int(degree), M, W, H, len(object_rows) - 1, rows, masks, _ptr(pos),
                                                     _ptr(scales), _ptr(rotations), _ptr(shs), _ptr(opacity), _ptr(tri), _ptr(weights), _ptr(cov),
                                                     _ptr(bg), cap, 1 if image_only else 0, None if work_hint is None else work_hint.data_ptr(),
                                                     int(bool(debug)), stream.cuda_stream))
-        for h in handles:
-            h.status_event = h.workspace.status()[1]
-            h.status_event.record(stream)
-            h.result = h._outputs(-1, h.binning)
-        return handles
-    return _begin(device, workspaces, issue)
+    return _batch_begin("forward_scene_batch", "one mask, gather table, camera and workspace", "the single-frame path",
+                        (packed_list, cameras, workspaces, deformed), device, bg, P, image_height, image_width, emission_policy, debug, False,
+                        (tri, weights, cov, pos, scales, rotations, shs, opacity), call)
 
 
 def rasterize_backward(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
