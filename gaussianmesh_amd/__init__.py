@@ -4,6 +4,7 @@
   simple_knn.distCUDA2
   deform.SingleObjectDeform (tensor-in deform + the reference attribute names)
   mesh_bind.closest_faces / bind_points (a plain cloud bound to a proxy mesh)
+  arap.ArapSolver (the proxy mesh deformed from dragged handle vertices, as rigidly as possible)
 All compute runs in csrc/libgmesh_hip.so (hand-written HIP for gfx950) through include/gmesh_hip.h.
 """
 import os as _os

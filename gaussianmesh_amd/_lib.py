@@ -59,6 +59,8 @@ SIGNATURES = {
     "gm_knn_nearest": (i32, [i32, vp, i32, vp, vp, vp, vp, sz, vp]),
     "gm_closest_face_workspace_bytes": (sz, [i32, i32]),
     "gm_closest_face": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "gm_arap_workspace_bytes": (sz, [i32]),
+    "gm_arap_solve": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp, sz, vp]),
     "gm_deform": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gm_sh_colors": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "gm_deform_shade": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1,0 +1,150 @@
+"""Deform a proxy mesh from dragged handle vertices: as-rigid-as-possible (Sorkine & Alexa 2007) on the device (gm_arap_solve,
+csrc/gm_arap.hip).  The stage the reference leaves to an external binary: "move these vertices there; the rest of the mesh follows as
+rigidly as it can".  Its output is what deform.mesh_rs / SingleObjectDeform.deform_vertices / render_sequence take, so a handle drag is
+solve -> gm_mesh_rs -> forward on one stream, with no host wait.  Definition, ABI and rules: INTEGRATION.md section Q."""
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def edge_csr(vertices, faces):
+    """The weighted edge graph of a triangle mesh as a symmetric CSR: (row_offsets int32 [Vm+1], cols int32 [nnz], weights float64
+    [nnz]), columns ascending within each row, no diagonal.  Weights as mesh_rs_kernel forms them (gm_mesh.hip), in float64 from the
+    float32 vertices: every face corner c opposite edge (a, b) adds max(0.5 cot(angle at c), 1e-3) to w_ab, cot = (u . w) / |u x w| with
+    u = a - c, w = b - c; a face with |u x w| <= 1e-30 adds nothing (an edge that only such faces hold does not appear).  Every weight
+    is positive.  Host, numpy only; once per mesh, like deform.vertex_face_adjacency."""
+    v = np.asarray(_host(vertices), np.float32).astype(np.float64)
+    f = np.asarray(_host(faces)).astype(np.int64).reshape(-1, 3)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("edge_csr: vertices must be [Vm,3]; got %s" % (tuple(v.shape),))
+    Vm = v.shape[0]
+    if f.shape[0] and (int(f.min()) < 0 or int(f.max()) >= Vm):
+        raise ValueError("edge_csr: face index outside [0, %d)" % Vm)
+    keys, vals = [], []
+    for c in range(3):
+        ia, ib, ic = f[:, (c + 1) % 3], f[:, (c + 2) % 3], f[:, c]
+        u, w = v[ia] - v[ic], v[ib] - v[ic]
+        area2 = np.linalg.norm(np.cross(u, w), axis=1)
+        ok = (area2 > 1e-30) & (ia != ib)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            wt = np.maximum(0.5 * (u * w).sum(axis=1) / area2, 1e-3)
+        keys += [ia[ok] * Vm + ib[ok], ib[ok] * Vm + ia[ok]]
+        vals += [wt[ok], wt[ok]]
+    keys = np.concatenate(keys) if keys else np.zeros(0, np.int64)
+    vals = np.concatenate(vals) if vals else np.zeros(0, np.float64)
+    uniq, inv = np.unique(keys, return_inverse=True)                   # sorted: rows ascend, columns ascend within a row
+    weights = np.bincount(inv.reshape(-1), weights=vals, minlength=len(uniq)).astype(np.float64)
+    rows, cols = uniq // Vm, uniq % Vm
+    offsets = np.zeros(Vm + 1, np.int64)
+    np.cumsum(np.bincount(rows, minlength=Vm), out=offsets[1:])
+    return offsets.astype(np.int32), cols.astype(np.int32), weights
+
+
+def _components(Vm, rows, cols):
+    """Label of the connected component of every vertex (the smallest vertex id in it): min-label propagation with pointer jumping."""
+    label = np.arange(Vm, dtype=np.int64)
+    while True:
+        new = label.copy()
+        np.minimum.at(new, rows, label[cols])
+        new = new[new]                                                 # a label is a vertex of the same component: jump to its label
+        if np.array_equal(new, label):
+            return label
+        label = new
+
+
+class ArapSolver:
+    """As-rigid-as-possible deformation of one mesh from one set of handle vertices.  Built once: the edge CSR (edge_csr), the mask of
+    held rows (the handles, and PINNED vertices: those whose weights sum to 0 - unreferenced, or every face at them degenerate - which
+    keep their `init` position), the device workspace.
+    rest_vertices [Vm,3], faces [F,3] vertex ids, handles: H distinct vertex ids.  ValueError for a handle id out of range or given
+    twice, an empty handle set, and a connected component of the weighted edge graph that has a free vertex but no handle (its
+    positions would be undetermined: the linear system is singular)."""
+
+    def __init__(self, rest_vertices, faces, handles, device="cuda"):
+        self.device = torch.device(device)
+        v = np.ascontiguousarray(np.asarray(_host(rest_vertices), np.float32))
+        if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] == 0:
+            raise ValueError("ArapSolver: rest_vertices must be [Vm,3] with Vm > 0; got %s" % (tuple(v.shape),))
+        Vm = v.shape[0]
+        h = np.asarray(_host(handles)).reshape(-1)
+        if h.size == 0:
+            raise ValueError("ArapSolver: the handle set is empty")
+        if h.dtype.kind not in "iu":
+            raise ValueError("ArapSolver: handles must be integer vertex ids, got %s" % h.dtype)
+        h = h.astype(np.int64)
+        if int(h.min()) < 0 or int(h.max()) >= Vm:
+            raise ValueError("ArapSolver: handle id outside [0, %d) (min %d, max %d)" % (Vm, int(h.min()), int(h.max())))
+        if len(np.unique(h)) != len(h):
+            raise ValueError("ArapSolver: a handle id is given twice")
+        off, cols, weights = edge_csr(v, faces)
+        rows = np.repeat(np.arange(Vm, dtype=np.int64), np.diff(off.astype(np.int64)))
+        pinned = np.bincount(rows, weights=weights, minlength=Vm) <= 0.0
+        fixed = pinned.copy()
+        fixed[h] = True
+        label = _components(Vm, rows, cols.astype(np.int64))
+        has_handle = np.zeros(Vm, bool)
+        has_handle[label[h]] = True
+        loose = np.nonzero(~fixed & ~has_handle[label])[0]
+        if len(loose):
+            raise ValueError("ArapSolver: vertex %d lies in a connected component without a handle (%d such vertices): the system is singular"
+                             % (int(loose[0]), len(loose)))
+        self.Vm, self.handles, self.pinned = Vm, h, np.nonzero(pinned)[0]
+        self.csr = (off, cols, weights)
+        if self.device.type != "cuda":                                 # the set-up above is host work; solve() needs the device
+            return
+        t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=self.device)
+        self.rest = t(v, torch.float32)
+        self._off, self._cols, self._w = t(off, torch.int32), t(cols, torch.int32), t(weights, torch.float64)
+        self._fixed = t(fixed.astype(np.uint8), torch.uint8)
+        self._handle_idx = t(h, torch.int64)
+        self._nbytes = _lib.lib().gm_arap_workspace_bytes(Vm)
+        self._ws = torch.empty((self._nbytes,), dtype=torch.uint8, device=self.device)
+
+    def solve(self, handle_positions, init=None, outer_iterations=4, cg_iterations=64, cg_tolerance=1e-6, out=None, want_stats=False):
+        """Positions [Vm,3] float32 on the device with the handles at handle_positions [H,3] (in the order of `handles`) and the rest of
+        the mesh following as rigidly as it can.  init: the starting positions (None: the rest pose; the previous frame's solution
+        warm-starts a drag); its handle rows are replaced by handle_positions (index_copy on the device).  out: where to write; it may
+        be `init` itself (then init's handle rows are overwritten too).  With want_stats returns (vertices, stats): stats float64
+        [outer_iterations, 8] on the device = E after the local step, E after the global step, CG steps used for x / y / z, final
+        |r| / |b| for x / y / z.  Stream-ordered; nothing here waits for the device (reading stats does).  Two identical calls give
+        identical bits.
+        The defaults (4 outer iterations, at most 64 CG steps each, relative residual 1e-6) began as unmeasured starting values and
+        were kept after tools/arap_time.py: 7.3 ms at 7.5 k vertices on an MI355X; from the rest pose the
+        64-step cap binds before the tolerance, and four such outer iterations reach a lower energy than four with converged solves."""
+        if self.device.type != "cuda":
+            raise _lib.GmeshError("ArapSolver.solve needs a HIP (cuda) device; there is no CPU path")
+        lib = _lib.lib()
+        Vm, dev = self.Vm, self.device
+        hp = torch.as_tensor(handle_positions, dtype=torch.float32, device=dev) if not torch.is_tensor(handle_positions) else \
+            handle_positions.detach().to(device=dev, dtype=torch.float32)
+        if hp.shape != (len(self.handles), 3):
+            raise ValueError("ArapSolver.solve: handle_positions must be [%d,3]; got %s" % (len(self.handles), tuple(hp.shape)))
+        if init is not None:
+            if not torch.is_tensor(init):
+                init = torch.as_tensor(np.asarray(init), dtype=torch.float32, device=dev)
+            if init.shape != (Vm, 3):
+                raise ValueError("ArapSolver.solve: init must be [%d,3]; got %s" % (Vm, tuple(init.shape)))
+        if out is not None and (not torch.is_tensor(out) or out.shape != (Vm, 3) or out.dtype is not torch.float32 or not out.is_contiguous()
+                                or out.device != self.rest.device):
+            raise ValueError("ArapSolver.solve: out must be a contiguous float32 [%d,3] tensor on the solver's device" % Vm)
+        if out is not None and out is init:
+            guess = out                                                # in place
+        else:
+            guess = (self.rest if init is None else init.detach().to(device=dev, dtype=torch.float32)).clone(memory_format=torch.contiguous_format)
+        guess.index_copy_(0, self._handle_idx, hp)
+        if out is None:
+            out = guess
+        stats = torch.zeros((int(outer_iterations), 8), dtype=torch.float64, device=dev) if want_stats and outer_iterations > 0 else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.gm_arap_solve(Vm, self._off.data_ptr(), self._cols.data_ptr(), self._w.data_ptr(), self.rest.data_ptr(),
+                                         self._fixed.data_ptr(), guess.data_ptr(), int(outer_iterations), int(cg_iterations), float(cg_tolerance),
+                                         out.data_ptr(), None if stats is None else stats.data_ptr(), self._ws.data_ptr(), self._nbytes,
+                                         torch.cuda.current_stream(dev).cuda_stream))
+        if want_stats:
+            return out, (stats if stats is not None else torch.zeros((0, 8), dtype=torch.float64, device=dev))
+        return out

@@ -480,6 +480,10 @@ size_t knn_nearest_workspace_bytes(int Pq, int Pr);
 int launch_closest_face(int N, const float* points, int Vm, const float* vertices, int F, const int* faces, float* out_d2, int* out_face,
                         float* out_closest, void* ws, size_t ws_bytes, hipStream_t s);
 size_t closest_face_workspace_bytes(int N, int F);
+int launch_arap_solve(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
+                      const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
+                      size_t ws_bytes, hipStream_t s);
+size_t arap_workspace_bytes(int Vm);
 
 // number of set bits of a wave-wide 64-bit mask (a ballot) at positions BELOW the calling lane: v_mbcnt_lo + v_mbcnt_hi, two
 // vector instructions and no per-lane mask registers (popcount(mask & lanes_lt) costs four and two registers)

@@ -310,9 +310,45 @@ class SingleObjectDeform:
         self.gaussian_deform_rot = torch.eye(3, device=self.gaussian_pos.device).expand(self.number_gaussian, 3, 3).contiguous()
         self.gaussian_deform_cov6 = None
         self.deform_state = None         # (V1, R, S) of the last deform(); None: the rest pose (edittool render_sequence renders it)
+        self.arap = None                 # the ArapSolver of set_handles()
 
     def get_name(self):
         return self.name
+
+    @property
+    def mesh_vertex_current(self):
+        """The proxy mesh's vertices as last deformed ([Vm,3], the V1 of deform_state); None: the rest pose.  drag() starts from them."""
+        return None if self.deform_state is None else self.deform_state[0]
+
+    def set_handles(self, vertex_ids, faces=None):
+        """Choose the handle vertices of drag(): builds the arap.ArapSolver of this object's rest mesh (its refusals apply).  faces
+        [F,3]: the proxy mesh's triangles, for an object built from tensors alone (the file-based object has them)."""
+        from .arap import ArapSolver
+        if faces is not None:
+            self.faces = torch.as_tensor(faces).detach().to(device=self.vertex.device, dtype=torch.int32).contiguous()
+            off, adj = vertex_face_adjacency(self.faces, self.vertex.shape[0])
+            self._adjacency = (torch.tensor(off, device=self.vertex.device), torch.tensor(adj, device=self.vertex.device))
+        if getattr(self, "faces", None) is None:
+            raise ValueError("set_handles: this object has no faces; pass faces=[F,3]")
+        self.arap = ArapSolver(self.vertex, self.faces, vertex_ids, device=self.vertex.device)
+        return self.arap
+
+    def deform_vertices(self, deform_vertex):
+        """deform() from the deformed vertices alone: their per-vertex (R, S) by gm_mesh_rs first."""
+        if getattr(self, "faces", None) is None:
+            raise ValueError("deform_vertices: this object has no faces; set_handles(..., faces=[F,3]) supplies them")
+        R, S = mesh_rs(self.vertex, deform_vertex, self.faces, adjacency=getattr(self, "_adjacency", None))
+        return self.deform(deform_vertex, R, S)
+
+    def drag(self, handle_positions, **solve_options):
+        """Move the handles of set_handles() to handle_positions [H,3]; the mesh follows as rigidly as it can (ArapSolver.solve, started
+        from mesh_vertex_current - the rest pose the first time - so consecutive drags warm-start), and the Gaussians follow the mesh:
+        exactly deform_vertices(solver.solve(handle_positions, init=mesh_vertex_current, **solve_options)).  No host wait."""
+        if self.arap is None:
+            raise ValueError("drag: call set_handles(vertex_ids) first")
+        if solve_options.get("want_stats"):
+            raise ValueError("drag: want_stats is ArapSolver.solve's; call self.arap.solve for the statistics")
+        return self.deform_vertices(self.arap.solve(handle_positions, init=self.mesh_vertex_current, **solve_options))
 
     def deform(self, deform_vertex, cur_rot, cur_shear):
         dV = _f(deform_vertex) - self.vertex

@@ -164,12 +164,8 @@ class SingleObjectDeform(_TensorObject):
         """:103-131: read the deformed mesh, per-vertex (R, S) of the deformation (pyACAP.GetRS there, gm_mesh_rs here),
         then the Gaussian deformation; sets gaussian_deform_pos / gaussian_deform_cov / gaussian_deform_rot."""
         deform_vertex, _ = gio.read_obj(deform_mesh_path)
+        # (deform_vertices: the same from a [Vm,3] tensor - an animation loop needs no file per frame; the tensor-in class defines it)
         return self.deform_vertices(torch.as_tensor(deform_vertex, dtype=torch.float32, device=self.device))
-
-    def deform_vertices(self, deform_vertex):
-        """the same from a [Vm,3] tensor of deformed vertices (an animation loop needs no file per frame)"""
-        R, S = mesh_rs(self.vertex, deform_vertex, self.faces, adjacency=self._adjacency)
-        return self.deform(deform_vertex, R, S)
 
 
 class ObjectVisualTool:
@@ -191,6 +187,17 @@ class ObjectVisualTool:
         for g in self.gaussians_list:
             if g.get_name() == name:
                 g.deform_gaussian(deform_mesh_path)
+
+    def drag_one_gaussian(self, name, vertex_ids, handle_positions, **solve_options):
+        """deform_one_gaussian without a mesh file: the objects called `name` get their handle vertices vertex_ids dragged to
+        handle_positions [H,3] (SingleObjectDeform.drag: as-rigid-as-possible, warm-started from the object's current mesh).  The
+        solver is built on the first call and kept while vertex_ids stay the same."""
+        ids = np.asarray(vertex_ids.detach().cpu() if torch.is_tensor(vertex_ids) else vertex_ids).reshape(-1)
+        for g in self.gaussians_list:
+            if g.get_name() == name:
+                if g.arap is None or not np.array_equal(g.arap.handles, ids):
+                    g.set_handles(ids)
+                g.drag(handle_positions, **solve_options)
 
     def get_camera(self, path):
         """cameras.json of a model directory -> cameras with the reference's attribute names (:547-584)"""

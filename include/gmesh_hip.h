@@ -238,6 +238,32 @@ size_t gm_closest_face_workspace_bytes(int N, int F);
 int gm_closest_face(int N, const float* points, int Vm, const float* vertices, int F, const int* faces, float* out_d2, int* out_face,
                     float* out_closest, void* workspace, size_t workspace_bytes, void* stream);
 
+/* As-rigid-as-possible deformation of a proxy mesh from dragged handles (Sorkine & Alexa 2007): the deformed mesh itself, which
+ * gm_mesh_rs then reads (R, S) from.  (row_offsets int32 [Vm+1], cols int32 [nnz], weights double [nnz]): the symmetric edge CSR with
+ * positive weights (arap.edge_csr: per face corner opposite edge (a, b) max(0.5 cot, 1e-3), mesh_rs_kernel's weights).  V0 float
+ * [Vm,3] rest vertices; fixed [Vm]: 1 = the row is held (a handle, a pinned vertex), and a row whose weights sum to 0 is held too;
+ * V_init float [Vm,3] the starting positions, whose held rows already carry their targets; V_out float [Vm,3].
+ *   E(P', R) = sum_i sum_j w_ij |(p'_i - p'_j) - R_i (p_i - p_j)|^2.  Per outer iteration, in float64:
+ *   local:  S_i = sum_j w_ij (p'_i - p'_j)(p_i - p_j)^T, R_i = U diag(1, 1, det(U V^T)) V^T (S_i = U Sigma V^T); rank <= 1
+ *           (second singular value <= 1e-12 of the first): R_i = I;
+ *   global: for every free row sum_j w_ij (p'_i - p'_j) = sum_j (w_ij / 2)(R_i + R_j)(p_i - p_j), the three coordinates separately by
+ *           Jacobi-preconditioned conjugate gradients from the current positions, until |r|_2 <= cg_tolerance |b|_2 or cg_iterations
+ *           steps; no number of steps raises E.
+ * stats: NULL, or double [outer_iterations][8] = E after the local step, E after the global step, CG steps used for x / y / z, final
+ * |r| / |b| for x / y / z; with NULL no energy is computed.  outer_iterations == 0 copies V_init to V_out.  V_out == V_init is allowed
+ * (the state lives in the workspace); any other overlap among V0, V_init, V_out, stats and the workspace is refused.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: Vm <= 0, outer_iterations < 0, cg_iterations < 1, a cg_tolerance that is negative
+ * or not finite, a NULL among row_offsets, cols, weights, V0, fixed, V_init, V_out, workspace, an overlap; with GM_ERR_BUFFER a workspace
+ * below gm_arap_workspace_bytes(Vm) (O(Vm), monotonic).  The CSR cannot be checked here without a read-back: column ids are forced into
+ * [0, Vm); row_offsets must ascend within the arrays (arap.ArapSolver builds all three itself).  A component of the edge graph with a
+ * free row and no held one makes the system singular: the caller rules that out (ArapSolver does).
+ * One workgroup per coordinate runs that column's whole solve; sums are taken in a fixed order and there are no atomics, so two calls
+ * on the same input give the same bits.  Stream-ordered, no device allocation, no host synchronisation. */
+size_t gm_arap_workspace_bytes(int Vm);
+int gm_arap_solve(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
+                  const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* Mesh-driven deformation of bound Gaussians; replaces the Jittor tensor algebra of
  * SingleObjectDeform.deform_gaussian (edittool/__init__.py:116-131), tensor-in form:
  *   tri int32 [N,3] vertex ids of the bound face, w float [N,3] barycentric weights,
