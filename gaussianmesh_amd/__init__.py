@@ -5,6 +5,7 @@
   deform.SingleObjectDeform (tensor-in deform + the reference attribute names)
   mesh_bind.closest_faces / bind_points (a plain cloud bound to a proxy mesh)
   arap.ArapSolver (the proxy mesh deformed from dragged handle vertices, as rigidly as possible)
+  mesh_pick.ray_mesh_hits / pick / visible_vertices / screen_offset (from a pixel to a vertex of the current mesh and back)
 All compute runs in csrc/libgmesh_hip.so (hand-written HIP for gfx950) through include/gmesh_hip.h.
 """
 import os as _os

@@ -711,6 +711,21 @@ int gm_arap_solve(int Vm, const int* row_offsets, const int* cols, const double*
                            workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t gm_ray_mesh_workspace_bytes(int R, int F) { return ray_mesh_workspace_bytes(R, F); }
+int gm_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const float* vertices, int F, const int* faces, float t_min, float t_max,
+                float* out_t, int* out_face, float* out_uv, void* workspace, size_t workspace_bytes, void* stream) {
+  if (R < 0 || Vm < 0 || F < 0) { set_error("gm_ray_mesh: negative size R=%d Vm=%d F=%d", R, Vm, F); return GM_ERR_INVALID_ARG; }
+  if (!(t_min >= 0.f) || t_max != t_max) { set_error("gm_ray_mesh: t_min must be >= 0 and neither bound NaN"); return GM_ERR_INVALID_ARG; }
+  if (R == 0) return GM_OK;
+  if (F == 0 || Vm == 0) { set_error("gm_ray_mesh: empty mesh (F == %d, Vm == %d)", F, Vm); return GM_ERR_INVALID_ARG; }
+  if (!origins || !dirs || !vertices || !faces || !out_t || !out_face || !workspace) { set_error("gm_ray_mesh: null pointer"); return GM_ERR_INVALID_ARG; }
+  if (ray_mesh_blocks(R, F) > 0x7FFFFFFFull) {
+    set_error("gm_ray_mesh: R x F too large for one launch (%llu workgroups); split the rays", ray_mesh_blocks(R, F)); return GM_ERR_INVALID_ARG;
+  }
+  return launch_ray_mesh(R, origins, dirs, Vm, vertices, F, faces, t_min, t_max, out_t, out_face, out_uv, workspace, workspace_bytes,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
 int gm_deform(int N, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
               const float* cov, const float* pos, float* pos_out, float* cov_out, float* rot_out, float* cov6_out,
               void* stream) {

@@ -484,6 +484,10 @@ int launch_arap_solve(int Vm, const int* row_offsets, const int* cols, const dou
                       const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
                       size_t ws_bytes, hipStream_t s);
 size_t arap_workspace_bytes(int Vm);
+int launch_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const float* vertices, int F, const int* faces, float t_min,
+                    float t_max, float* out_t, int* out_face, float* out_uv, void* ws, size_t ws_bytes, hipStream_t s);
+size_t ray_mesh_workspace_bytes(int R, int F);
+unsigned long long ray_mesh_blocks(int R, int F);
 
 // number of set bits of a wave-wide 64-bit mask (a ballot) at positions BELOW the calling lane: v_mbcnt_lo + v_mbcnt_hi, two
 // vector instructions and no per-lane mask registers (popcount(mask & lanes_lt) costs four and two registers)

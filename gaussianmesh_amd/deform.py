@@ -350,6 +350,44 @@ class SingleObjectDeform:
             raise ValueError("drag: want_stats is ArapSolver.solve's; call self.arap.solve for the statistics")
         return self.deform_vertices(self.arap.solve(handle_positions, init=self.mesh_vertex_current, **solve_options))
 
+    def _screen_mesh(self, who):
+        """(current vertices, faces, check_faces) for the screen-space methods: the face indices are checked on the host the first
+        time this face tensor is seen (mesh_pick), afterwards nothing waits for the device."""
+        if getattr(self, "faces", None) is None:
+            raise ValueError("%s: this object has no faces; set_handles(..., faces=[F,3]) supplies them" % who)
+        check = getattr(self, "_faces_checked", None) is not self.faces
+        current = self.mesh_vertex_current
+        return (self.vertex if current is None else current), self.faces, check
+
+    def pick(self, camera, pixels):
+        """mesh_pick.pick on this object's mesh as last deformed (mesh_vertex_current; the rest pose if there is none): what lies under
+        pixels [P,2] of the camera, dict(face, vertex, point, depth) on the device.  Its vertex ids are set_handles' ids."""
+        from . import mesh_pick
+        v, f, check = self._screen_mesh("pick")
+        out = mesh_pick.pick(camera, pixels, v, f, check_faces=check)
+        self._faces_checked = f
+        return out
+
+    def select_visible(self, camera, rect=None):
+        """The ids (int64, ascending, on the device) of the vertices of the current mesh that the camera sees
+        (mesh_pick.visible_vertices), inside rect = (x0, y0, x1, y1) in pixels if given."""
+        from . import mesh_pick
+        v, f, check = self._screen_mesh("select_visible")
+        mask = mesh_pick.visible_vertices(camera, v, f, rect=rect, check_faces=check)
+        self._faces_checked = f
+        return torch.nonzero(mask)[:, 0]
+
+    def drag_pixels(self, camera, pixel_offsets, **solve_options):
+        """drag() from the screen: the handles of set_handles() move by pixel_offsets [H,2] in the camera's image, each parallel to the
+        image plane at its own depth: exactly drag(mesh_pick.screen_offset(camera, current handle positions, pixel_offsets)), the
+        current positions being mesh_vertex_current's rows (the rest pose's the first time).  No host wait."""
+        from . import mesh_pick
+        if self.arap is None:
+            raise ValueError("drag_pixels: call set_handles(vertex_ids) first")
+        current = self.mesh_vertex_current
+        at = (self.vertex if current is None else current).index_select(0, self.arap._handle_idx)
+        return self.drag(mesh_pick.screen_offset(camera, at, pixel_offsets), **solve_options)
+
     def deform(self, deform_vertex, cur_rot, cur_shear):
         dV = _f(deform_vertex) - self.vertex
         pos, cov, rot, cov6 = deform_tensors(self.gaussian_triangles, self.coord, dV, cur_rot.reshape(-1, 3, 3),

@@ -1,7 +1,7 @@
 """Animate an edited object: the animation loop of the reference's edit.py (its commented-out part, edit.py:46-54), batched.
 
     python -m gaussianmesh_amd.edit_sequence (--object_gaussian fg.ply | --object_plain_gaussian cloud.ply) --object_origin_mesh mesh.obj \
-        (--mesh_sequence DIR | --handle_sequence FILE.npz) --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N]
+        (--mesh_sequence DIR | --handle_sequence FILE.npz | --pick_sequence FILE.json) --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N]
         [--frames_per_launch 4] [--save_maps] [--save_meshes] [--background_gaussian BG.ply [--is_exist_bg]]
 
 --object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
@@ -9,7 +9,14 @@ faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of
 --mesh_sequence: a folder of OBJ files in numeric order (1.obj, 2.obj, ...: the reference's `mesh_sequnce`), one frame each.
 --handle_sequence: instead of ready-made meshes, an .npz with `handles` (int [H] vertex ids) and `positions` (float [T,H,3]): frame t is the
 as-rigid-as-possible deformation with the handles at positions[t] (arap.ArapSolver), solved from frame t - 1's solution (frame 0 from the
-rest pose).  Exactly one of --mesh_sequence / --handle_sequence.  --save_meshes also writes every frame's mesh as {i:05d}.obj.
+rest pose).
+--pick_sequence: the same from the screen, a JSON file with "camera_id" (the camera of MODEL_DIR/cameras.json in which the pixels are
+meant), "handles" [[x, y], ...] (the pixels whose picked vertices move), optionally "anchors" [[x, y], ...] (picks held at their rest
+position) and "offsets" [T][len(handles)][2] (per frame the pixel offsets from the original pick).  The picks are resolved once, on the
+rest mesh (SingleObjectDeform.pick: the hit face's corner nearest the hit); a pick that misses the mesh, or two picks of one vertex, end
+the run.  Frame t has the handles at their rest positions moved by offsets[t] parallel to the image plane (mesh_pick.screen_offset) and
+the anchors in place, solved from frame t - 1's solution as above.
+Exactly one of --mesh_sequence / --handle_sequence / --pick_sequence.  --save_meshes also writes every frame's mesh as {i:05d}.obj.
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
@@ -30,6 +37,43 @@ def mesh_sequence(folder):
     return [os.path.join(folder, n) for n in sorted(names, key=key)]
 
 
+def read_pick_sequence(path):
+    """A --pick_sequence file -> (camera_id, handles float32 [H,2], anchors float32 [A,2], offsets float32 [T,H,2]); SystemExit naming
+    what is wrong with it.  Host work only."""
+    import json
+    import numpy as np
+    bad = lambda what: SystemExit("edit_sequence: %s: %s" % (path, what))
+    try:
+        with open(path) as fh:
+            doc = json.load(fh)
+    except (OSError, ValueError) as e:
+        raise bad("cannot read it as JSON (%s)" % e)
+    if not isinstance(doc, dict):
+        raise bad("must hold a JSON object")
+    cam = doc.get("camera_id")
+    if not isinstance(cam, int) or isinstance(cam, bool) or cam < 0:
+        raise bad('"camera_id" (the camera in which the pixels are meant) is required: a non-negative integer')
+
+    def pixels(key, required):
+        if key not in doc and not required:
+            return np.zeros((0, 2), np.float32)
+        try:
+            a = np.asarray(doc.get(key), np.float32)
+        except (TypeError, ValueError):
+            a = None
+        if a is None or a.ndim != 2 or a.shape[1] != 2 or (required and a.shape[0] == 0) or not np.isfinite(a).all():
+            raise bad('"%s" must be a list of [x, y] pixels%s' % (key, ", at least one" if required else ""))
+        return a
+    handles, anchors = pixels("handles", True), pixels("anchors", False)
+    try:
+        offsets = np.asarray(doc.get("offsets"), np.float32)
+    except (TypeError, ValueError):
+        offsets = None
+    if offsets is None or offsets.ndim != 3 or offsets.shape[0] == 0 or offsets.shape[1:] != (len(handles), 2) or not np.isfinite(offsets).all():
+        raise bad('"offsets" must be [T][%d][2] pixel offsets, T >= 1; got shape %s' % (len(handles), None if offsets is None else offsets.shape))
+    return cam, handles, anchors, offsets
+
+
 def main(argv=None):
     parser = ArgumentParser(description="Render a mesh-driven animation of a mesh-bound Gaussian object")
     which = parser.add_mutually_exclusive_group(required=True)
@@ -42,6 +86,7 @@ def main(argv=None):
     source = parser.add_mutually_exclusive_group(required=True)
     source.add_argument("--mesh_sequence", type=str, default=None)
     source.add_argument("--handle_sequence", type=str, default=None)
+    source.add_argument("--pick_sequence", type=str, default=None)
     parser.add_argument("--save_meshes", action="store_true", default=False)
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
@@ -53,6 +98,8 @@ def main(argv=None):
         parser.error("--is_exist_bg needs --background_gaussian (the background cloud's PLY)")
     if args.background_gaussian is not None and args.save_maps:
         parser.error("--save_maps: a scene with a background renders no depth / alpha maps; drop --save_maps or the background")
+    if args.pick_sequence is not None:
+        pick_camera, pick_handles, pick_anchors, pick_offsets = read_pick_sequence(args.pick_sequence)
 
     import numpy as np
     import torch
@@ -69,14 +116,32 @@ def main(argv=None):
         tool.add_plain_gaussian(args.object_plain_gaussian, args.object_origin_mesh, args.object_name)
     else:
         tool.add_gaussian(args.object_gaussian, args.object_origin_mesh, args.object_name)
+    handles = None
     if args.handle_sequence is not None:
         with np.load(args.handle_sequence) as z:
             handles, positions = np.asarray(z["handles"]).reshape(-1), np.asarray(z["positions"], np.float32)
         if positions.ndim != 3 or positions.shape[1:] != (len(handles), 3):
             raise SystemExit("edit_sequence: %s: positions must be [T,%d,3], got %s" % (args.handle_sequence, len(handles), positions.shape))
+    if args.pick_sequence is not None:
+        from .mesh_pick import screen_offset
+        if pick_camera >= len(cams):
+            raise SystemExit("edit_sequence: %s: camera_id %d, but %s has %d cameras" % (args.pick_sequence, pick_camera, args.camera_path, len(cams)))
+        obj, cam = tool.gaussians_list[-1], cams[pick_camera]
+        pixels = np.concatenate([pick_handles, pick_anchors], 0)
+        names = ["handle %d" % i for i in range(len(pick_handles))] + ["anchor %d" % i for i in range(len(pick_anchors))]
+        handles = obj.pick(cam, pixels)["vertex"].cpu().numpy()                       # resolved once, on the rest mesh
+        for i, v in enumerate(handles):
+            if v < 0:
+                raise SystemExit("edit_sequence: %s: %s at pixel (%g, %g) misses the mesh" % (args.pick_sequence, names[i], pixels[i, 0], pixels[i, 1]))
+            if v in handles[:i]:
+                raise SystemExit("edit_sequence: %s: %s and %s pick the same vertex %d" % (args.pick_sequence, names[list(handles[:i]).index(v)], names[i], v))
+        rest = obj.vertex[torch.as_tensor(handles, device=obj.vertex.device)]
+        offsets = torch.as_tensor(pick_offsets, device=rest.device)
+        positions = [torch.cat([screen_offset(cam, rest[:len(pick_handles)], offsets[t]), rest[len(pick_handles):]], 0) for t in range(len(offsets))]
+    if handles is not None:
         solver = tool.gaussians_list[-1].set_handles(handles)
         meshes, current = [], None
-        for t in range(positions.shape[0]):                       # enqueued back to back: no host wait between the solves
+        for t in range(len(positions)):                           # enqueued back to back: no host wait between the solves
             current = solver.solve(positions[t], init=current)
             meshes.append(current)
     frames = [(cams[args.camera_id] if args.camera_id is not None else cams[i % len(cams)], {args.object_name: m})

@@ -199,6 +199,14 @@ class ObjectVisualTool:
                     g.set_handles(ids)
                 g.drag(handle_positions, **solve_options)
 
+    def pick_one_gaussian(self, name, camera, pixels):
+        """What lies under pixels [P,2] of the camera on the current proxy mesh of the (first) object called `name`
+        (SingleObjectDeform.pick): dict(face, vertex, point, depth) on the device; the vertex ids are drag_one_gaussian's."""
+        for g in self.gaussians_list:
+            if g.get_name() == name:
+                return g.pick(camera, pixels)
+        raise ValueError("pick_one_gaussian: no object named %r" % (name,))
+
     def get_camera(self, path):
         """cameras.json of a model directory -> cameras with the reference's attribute names (:547-584)"""
         return [Camera(c, self.device) for c in gio.load_cameras_json(os.path.join(path, "cameras.json"))]

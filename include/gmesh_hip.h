@@ -264,6 +264,28 @@ int gm_arap_solve(int Vm, const int* row_offsets, const int* cols, const double*
                   const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* First hit of every ray on a mesh: what takes an editor from a pixel to a vertex of the current, deformed proxy mesh
+ * (mesh_pick.ray_mesh_hits / pick / visible_vertices).  The reference has no such stage: the result is defined by arithmetic.
+ * origins, dirs float [R,3], vertices float [Vm,3], faces int32 [F,3] vertex ids.  out_t float [R], out_face int32 [R], out_uv float
+ * [R,2] (may be NULL).  Per (ray (o, d), face (a, b, c)) in float32, no contraction, correctly rounded division,
+ * dot(x, y) = (x.x*y.x + x.y*y.y) + x.z*y.z, cross products per component as x.y*y.z - x.z*y.y (Moeller & Trumbore, two-sided):
+ *   e1 = b - a, e2 = c - a, p = d x e2, det = dot(e1, p), s = o - a, q = s x e1, inv = 1 / det
+ *   u = dot(s, p) * inv, v = dot(d, q) * inv, t = dot(e2, q) * inv
+ *   hit iff u >= 0 and v >= 0 and (u + v) <= 1 and t >= t_min and t <= t_max (every comparison false on NaN; no epsilon on det:
+ *   det == 0 gives inf or NaN, which fail by themselves).  d is not normalised: t is in units of |d|.
+ * Winner: the smallest t, ties to the LOWEST face index; out_t = t + 0.0f (-0 reported as +0), out_face, out_uv = (u, v) of that face.
+ * No hit: out_face = -1, out_t = +inf, out_uv = NaN.  So the outputs equal a float32 brute force over all F faces bit for bit, for
+ * every finite input, and two calls give the same bits (csrc/gm_raycast.hip: every pair is evaluated, nothing is skipped).
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: a negative size, t_min < 0, a NaN bound, and with R > 0: F == 0 or Vm == 0, a
+ * NULL among origins, dirs, vertices, faces, out_t, out_face, workspace, more than 2^31 - 1 workgroups (ceil(R / 256) * ceil(F / 64):
+ * split the rays); with GM_ERR_BUFFER: a workspace below gm_ray_mesh_workspace_bytes(R, F) (O(R + F), monotonic in both, positive at
+ * (0, 0)).  R == 0 succeeds and launches nothing.  Face indices outside [0, Vm) are forced into range, as in gm_closest_face: no
+ * fault, no meaningful result for that face; mesh_pick.ray_mesh_hits checks them on the host.  Stream-ordered, no device allocation, no
+ * host synchronisation. */
+size_t gm_ray_mesh_workspace_bytes(int R, int F);
+int gm_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const float* vertices, int F, const int* faces, float t_min, float t_max,
+                float* out_t, int* out_face, float* out_uv, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Mesh-driven deformation of bound Gaussians; replaces the Jittor tensor algebra of
  * SingleObjectDeform.deform_gaussian (edittool/__init__.py:116-131), tensor-in form:
  *   tri int32 [N,3] vertex ids of the bound face, w float [N,3] barycentric weights,
