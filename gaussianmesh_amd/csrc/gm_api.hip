@@ -633,6 +633,10 @@ void* gm_geom_field(void* geom_buffer, int P, const char* name) {
   if (!strcmp(name, "depth_key")) return g.depth_key;
   if (!strcmp(name, "radii")) return g.radii;
   if (!strcmp(name, "tiles_touched")) return g.tiles_touched;
+  if (!strcmp(name, "bin")) return g.bin;
+  if (!strcmp(name, "inst16")) return g.inst16;
+  if (!strcmp(name, "bin_sorted")) return g.bin_sorted;
+  if (!strcmp(name, "grad_acc")) return g.grad_acc;
   if (!strcmp(name, "cov3D")) return g.cov3D;
   if (!strcmp(name, "clamped")) return g.clamped;
   if (!strcmp(name, "order")) return g.order;

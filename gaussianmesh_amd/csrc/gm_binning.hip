@@ -63,25 +63,38 @@ __device__ __forceinline__ void get_rect(float px, float py, int r, int gx, int 
   y1 = min(gy, max(0, (int)((py + r + GM_TILE - 1) / GM_TILE)));
 }
 
+// the records of a thread's positions; DIRECT: in depth order already (bin_sorted), else gathered through the order
+template <bool DIRECT, int BN_PER_THREAD>
+__device__ __forceinline__ void load_records(const uint32_t* __restrict__ order, const uint4* __restrict__ recs, uint32_t base, uint32_t P1,
+                                             uint32_t (&gid)[BN_PER_THREAD], uint4 (&rc)[BN_PER_THREAD]) {
+#pragma unroll
+  for (int i = 0; i < BN_PER_THREAD; i++) gid[i] = (!DIRECT && base + i < P1) ? order[base + i] : 0u;
+#pragma unroll
+  for (int i = 0; i < BN_PER_THREAD; i++) rc[i] = base + i < P1 ? recs[DIRECT ? base + i : gid[i]] : make_uint4(0u, 0u, 0u, 0u);
+}
+
 // Instance emission.  Workgroup r owns the run of sorted positions [512 r, 512 r + 512) (gm_bucket.hip leaves the instance
 // total of every run in chunk_inst; the work does not depend on how the depth buckets came out): thread t owns 2 consecutive
 // positions and reads their
-// emission records (candidate rectangle + instance count + emit mask, written by preprocess, brought into this order by
-// bucket_sort_kernel: coalesced); the chunk scans the counts into output offsets; then instances are
-// written (see (1) and (2) in the body).  The run's first output offset is the sum of the instance totals of the runs before
-// it (chunk_inst, summed by every workgroup for itself).
+// emission records (candidate rectangle + instance count + emit mask) where the preprocess kernel wrote them, bin[order[s]]: a gather of
+// 16-byte records, issued before the workgroup sums chunk_inst so that its latency hides behind that prefix.  A frame of the direct depth
+// placement (its first half latched counters[GM_CNT_DEPTH_STALE]; the second half is a call of its own and is not told) has no bin array:
+// its records were brought into this order by bucket_sort_kernel<true> and are read sequentially from bin_sorted.  The chunk scans the
+// counts into output offsets; then instances are written (see (1) and (2) in the body).  The run's first output offset is the sum
+// of the instance totals of the runs before it (chunk_inst, summed by every workgroup for itself).
 // Emitted order = Gaussian order (depth, id), then rectangle row-major - the reference's order
 // (RAST/rasterizer_impl.cu:98-109) restricted to the emitted tiles.
 // S > 0: one instance per PARENT tile (2^S x 2^S tiles) that has a reached child; key = parent id | child mask << 16
 // (child bit = (row in parent) << S | column in parent).  S == 0: key = tile id | 1 << 16.
 template <int S, int BN_PER_THREAD>
 __global__ __launch_bounds__(BN_THREADS) void duplicate_kernel(const uint32_t* __restrict__ order, const uint32_t* __restrict__ tiles,
-                                                                const uint4* __restrict__ bin_sorted, const float4* __restrict__ splat,
+                                                                const uint4* __restrict__ bin, const uint4* __restrict__ bin_sorted,
+                                                                const float4* __restrict__ splat,
                                                                 uint32_t* __restrict__ counters, const uint32_t* __restrict__ chunk_inst,
                                                                 int gx, int pgx, int mode,
                                                                 uint32_t capacity, uint2* __restrict__ pairs_out,
                                                                 uint32_t* __restrict__ acc, uint32_t acc_words, const FrameOfs go, const FrameOfs bo) {
-  order = frame_ptr(order, go); tiles = frame_ptr(tiles, go); bin_sorted = frame_ptr(bin_sorted, go); splat = frame_ptr(splat, go);
+  order = frame_ptr(order, go); tiles = frame_ptr(tiles, go); bin = frame_ptr(bin, go); bin_sorted = frame_ptr(bin_sorted, go); splat = frame_ptr(splat, go);
   counters = frame_ptr(counters, go); chunk_inst = frame_ptr(chunk_inst, go);            // frame blockIdx.z of a batch (gm_common.h FrameOfs)
   pairs_out = frame_ptr(pairs_out, bo); acc = frame_ptr(acc, bo);
   __shared__ uint32_t wsum[BN_THREADS / 64];
@@ -106,6 +119,13 @@ __global__ __launch_bounds__(BN_THREADS) void duplicate_kernel(const uint32_t* _
   static_assert(RUN % GM_SCAN_ITEMS == 0, "a workgroup takes whole runs");
   const uint32_t P0 = min(run * RUN, V), P1 = min(P0 + RUN, V);
   if (P0 == P1) return;
+  // (P1 - P0 <= RUN: one chunk per workgroup)
+  const uint32_t base = P0 + threadIdx.x * BN_PER_THREAD;
+  uint32_t gid[BN_PER_THREAD], cnt[BN_PER_THREAD], offs[BN_PER_THREAD], sum = 0;
+  uint4 rc[BN_PER_THREAD];
+  const bool direct = counters[GM_CNT_DEPTH_STALE] != 0u;                // (workgroup-uniform)
+  if (direct) load_records<true, BN_PER_THREAD>(order, bin_sorted, base, P1, gid, rc);
+  else load_records<false, BN_PER_THREAD>(order, bin, base, P1, gid, rc);
   uint32_t ibase;
   {
     uint32_t part = 0;
@@ -115,16 +135,11 @@ __global__ __launch_bounds__(BN_THREADS) void duplicate_kernel(const uint32_t* _
     ibase = tot;
     __syncthreads();
   }
-  for (uint32_t c0 = P0; c0 < P1; c0 += RUN) {
-  const uint32_t base = c0 + threadIdx.x * BN_PER_THREAD;
-  uint32_t gid[BN_PER_THREAD], cnt[BN_PER_THREAD], offs[BN_PER_THREAD], sum = 0;
-  uint4 rc[BN_PER_THREAD];
 #pragma unroll
   for (int i = 0; i < BN_PER_THREAD; i++) {
     const uint32_t s = base + i;
-    rc[i] = s < P1 ? bin_sorted[s] : make_uint4(0u, 0u, 0u, 0u);
     cnt[i] = bin_count(rc[i]);
-    gid[i] = (s < P1 && cnt[i]) ? order[s] : 0u;
+    if (direct) gid[i] = (s < P1 && cnt[i]) ? order[s] : 0u;
     if (cnt[i] == GM_BIN_COUNT_SAT) cnt[i] = tiles[gid[i]];
     sum += cnt[i];
   }
@@ -266,9 +281,6 @@ __global__ __launch_bounds__(BN_THREADS) void duplicate_kernel(const uint32_t* _
     for (uint32_t j = threadIdx.x; j < total; j += BN_THREADS) pairs_out[block_base + j] = make_uint2(stage_k[j], stage_v[j]);
   }
 #undef EMIT
-  ibase += total;
-  __syncthreads();                                 // the stage and wsum are reused by the next chunk
-  }
 }
 
 int launch_duplicate(GeomState& g, BinningState& b, int P, int W, int H, int mode, size_t capacity, int debug, hipStream_t s, const BatchOfs* bt) {
@@ -282,7 +294,7 @@ int launch_duplicate(GeomState& g, BinningState& b, int P, int W, int H, int mod
     // Gaussian), one when the cloud emits more per Gaussian (4K, near cameras): unstaged runs store partial lines
     const bool two = capacity <= (size_t)P * 5;
 #define GM_DUP(SH, PER) hipLaunchKernelGGL((duplicate_kernel<SH, PER>), dim3((P + PER * BN_THREADS - 1) / (PER * BN_THREADS), 1, (uint32_t)B.frames), dim3(BN_THREADS), 0, s, g.order, \
-                                           g.tiles_touched, g.bin_sorted, g.splat, g.counters, g.chunk_inst, tg.gx, tg.pgx, mode, cap, b.pairs[0], b.acc, \
+                                           g.tiles_touched, g.bin, g.bin_sorted, g.splat, g.counters, g.chunk_inst, tg.gx, tg.pgx, mode, cap, b.pairs[0], b.acc, \
                                            (uint32_t)bk_acc_words(capacity), B.geom, B.binning)
     if (two) { if (tg.s == 0) GM_DUP(0, 2); else if (tg.s == 1) GM_DUP(1, 2); else GM_DUP(2, 2); }
     else { if (tg.s == 0) GM_DUP(0, 1); else if (tg.s == 1) GM_DUP(1, 1); else GM_DUP(2, 1); }

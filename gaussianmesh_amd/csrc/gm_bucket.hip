@@ -544,27 +544,28 @@ __device__ __forceinline__ void chunk_add(uint32_t* __restrict__ chunk_inst, uin
 }
 
 // One workgroup per bucket of the MSD partition: (key, id) pairs [start, end) of p1 -> final order.
-// Outputs: order0[start..end) = ids in (key, id) order, bin_sorted[start..end) = emission records of those ids,
-// chunk_inst[run] += instance counts of the sorted positions of that run.  p0[start..end) is scratch for the slow path.
+// Outputs: order0[start..end) = ids in (key, id) order, chunk_inst[run] += instance counts of the sorted positions of that run (from
+// inst16[id]: the records stay where the preprocess kernel wrote them and duplicate_kernel reads bins[order0[s]] itself - copying them into
+// depth order cost 16 B written and 16 B read per Gaussian for one use).  p0[start..end) is scratch for the slow path.
 // DIRECT (direct depth placement): bucket b's entries are the first (end - start) of its slab, p1 + b * cap and bins + b * cap, in
 // ARRIVAL order (the preprocess kernel's atomics), so position says nothing about the id: the bucket's key range is taken from the
 // entries themselves (the table that placed them is an earlier frame's), equal keys are ordered by comparing ids, and what the
 // one-word sort cannot do - a key range above 20 bits, a pile of more than BS_BIN_MAX equal keys - refuses the frame
 // (counters[GM_CNT_DIRECT_FAIL]; the caller renders it again on the partition path).  The record is read from the workgroup's own
-// slab: contiguous memory, every fetched line used.
+// slab: contiguous memory, every fetched line used - and copied to bin_sorted[start..end), which the emission then reads sequentially.
 template <bool DIRECT>
 __global__ __launch_bounds__(BK_THREADS) void bucket_sort_kernel(uint32_t* __restrict__ counters,
                                                                   const uint32_t* __restrict__ bmap, const uint32_t* __restrict__ bucket_start,
                                                                   uint2* __restrict__ p1, uint2* __restrict__ p0, uint32_t* __restrict__ order0,
                                                                   const uint32_t* __restrict__ tiles, const uint4* __restrict__ bins,
-                                                                  uint4* __restrict__ bin_sorted, uint32_t* __restrict__ chunk_inst,
+                                                                  const uint16_t* __restrict__ inst16, uint4* __restrict__ bin_sorted, uint32_t* __restrict__ chunk_inst,
                                                                   unsigned long long* __restrict__ trace, uint32_t cap,
                                                                   const uint32_t* __restrict__ slots, const uint32_t* __restrict__ coarse,
                                                                   const uint32_t* __restrict__ hdr, uint32_t* __restrict__ plan, const FrameOfs go) {
   const unsigned long long t_begin = trace ? wall_clock64() : 0ull;
   if (!DIRECT) {                                 // frame blockIdx.z of a batch: everything lives in the geometry buffer (the direct placement is not batched)
     counters = frame_ptr(counters, go); bmap = frame_ptr(bmap, go); bucket_start = frame_ptr(bucket_start, go); p1 = frame_ptr(p1, go); p0 = frame_ptr(p0, go);
-    order0 = frame_ptr(order0, go); tiles = frame_ptr(tiles, go); bins = frame_ptr(bins, go); bin_sorted = frame_ptr(bin_sorted, go);
+    order0 = frame_ptr(order0, go); tiles = frame_ptr(tiles, go); inst16 = frame_ptr(inst16, go);
     chunk_inst = frame_ptr(chunk_inst, go);
   }
   __shared__ uint32_t wcnt[BK_WAVES][256];
@@ -794,13 +795,17 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_sort_kernel(uint32_t* __res
         const uint32_t p = (wave * rounds + r) * 64u + lane;
         uint32_t inst = 0;
         if (p < n) {
-          // the one random access per Gaussian of the whole ordering: its emission record travels to its sorted position
           const uint32_t id = p1[start + (key[r] & 0xFFFu)].y;
-          const uint4 rec = bins[DIRECT ? (key[r] & 0xFFFu) : id];
-          uint32_t c = bin_count(rec);
+          uint32_t c;
+          if (DIRECT) {                                 // the record travels from the slab to its sorted position
+            const uint4 rec = bins[key[r] & 0xFFFu];
+            c = bin_count(rec);
+            bin_sorted[obase + p] = rec;
+          } else {
+            c = inst16[id];                             // the one random access per Gaussian of the ordering: 2 bytes of an array the L2s hold
+          }
           if (c == GM_BIN_COUNT_SAT) c = tiles[id];
           order0[obase + p] = id;
-          bin_sorted[obase + p] = rec;
           inst = c;
         }
         chunk_add(chunk_inst, obase + (wave * rounds + r) * 64u, lane, inst);
@@ -888,12 +893,10 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_sort_kernel(uint32_t* __res
       const uint32_t i = i0 + threadIdx.x;
       uint32_t c = 0;
       if (i < n) {
-        const uint32_t id = sp[start + i].y;
-        const uint4 rec = bins[id];
-        c = bin_count(rec);
+        const uint32_t id = sp[start + i].y;                        // (partition path only: a slab never exceeds the LDS sort)
+        c = DIRECT ? 0u : inst16[id];
         if (c == GM_BIN_COUNT_SAT) c = tiles[id];
         order0[start + i] = id;
-        bin_sorted[start + i] = rec;
       }
       chunk_add(chunk_inst, start + i0 + wave * 64u, lane, c);
     }
@@ -936,7 +939,7 @@ int launch_depth_order(GeomState& g, int P, int debug, hipStream_t s, int* num_r
                      B.geom, B.binning, B.image);
   GM_LAUNCH_CHECK(debug, s);
   hipLaunchKernelGGL(bucket_sort_kernel<false>, dim3(1 << DB, 1, nf), dim3(BK_THREADS), 0, s, g.counters, g.bmap, g.bucket_start, g.dpairs[1], g.dpairs[0], g.order,
-                     g.tiles_touched, g.bin, g.bin_sorted, g.chunk_inst, nf == 1 ? g_bucket_trace : nullptr, 0u, nullptr, nullptr, nullptr, nullptr, B.geom);
+                     g.tiles_touched, nullptr, g.inst16, nullptr, g.chunk_inst, nf == 1 ? g_bucket_trace : nullptr, 0u, nullptr, nullptr, nullptr, nullptr, B.geom);
   GM_LAUNCH_CHECK(debug, s);
   return 0;
 }
@@ -1075,7 +1078,7 @@ int launch_depth_order_direct(GeomState& g, DepthSlab& d, uint32_t* plan, int P,
     if (count_event) GM_HIP(hipEventRecord(count_event, s));
   }
   hipLaunchKernelGGL(bucket_sort_kernel<true>, dim3((1 << GM_BUCKET_BITS) + 1), dim3(BK_THREADS), 0, s, g.counters, g.bmap, g.bucket_start, d.pairs, g.dpairs[0],
-                     g.order, g.tiles_touched, d.recs, g.bin_sorted, g.chunk_inst, g_bucket_trace, d.cap, g.slots, g.coarse, d.hdr, plan, FrameOfs{});
+                     g.order, g.tiles_touched, d.recs, nullptr, g.bin_sorted, g.chunk_inst, g_bucket_trace, d.cap, g.slots, g.coarse, d.hdr, plan, FrameOfs{});
   GM_LAUNCH_CHECK(debug, s);
   return 0;
 }

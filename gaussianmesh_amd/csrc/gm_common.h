@@ -161,12 +161,15 @@ struct GeomState {              // per-Gaussian state (P-sized)
   uint32_t* tiles_touched;      // [P]
   uint4* bin;                   // [P] emission record (bin_pack below): candidate tile rectangle, instance count and, for rectangles
                                 //     of <= 64 tiles, the bit mask (row-major) of the tiles actually emitted
+  uint16_t* inst16;             // [P] the instance count as the record carries it (bin_count: GM_BIN_COUNT_SAT = see tiles_touched; 0 for a culled row):
+                                //     what bucket_sort_kernel gathers per id - 2 MB per million Gaussians stay in the L2s where 16 MB of records do not
   float* cov3D;                 // [P][6] (computed from scale/rot)
   uint8_t* clamped;             // [P] bit ch = SH colour channel ch was clamped at 0
   uint32_t* depth_key;          // [P] float bits of view z per Gaussian (0xFFFFFFFF = culled)
   uint2* dpairs[2];             // [P] (depth key, id): [1] partitioned into buckets, [0] scratch of an overfull bucket's sort
   uint32_t* order;              // [P] ids of the VISIBLE Gaussians in (depth, id) order
-  uint4* bin_sorted;            // [P] the emission records in that order (duplicate_kernel reads them sequentially)
+  uint4* bin_sorted;            // [P] direct depth placement only: the emission records in that order, copied from the frame's slab (on the partition path
+                                //     duplicate_kernel gathers bin[order[s]] itself and this array is not touched)
   uint32_t* hist;               // [bk_blocks(P)][2048] bucket histograms of the partition -> absolute output offsets
   uint32_t* bucket_start;       // [2049] first sorted position of each bucket (+ total)
   uint32_t* chunk_inst;         // [P / GM_SCAN_ITEMS + 1] instances emitted by each run of GM_SCAN_ITEMS sorted positions (zeroed with the slots)
@@ -185,6 +188,7 @@ struct GeomState {              // per-Gaussian state (P-sized)
     g.radii = carve<int>(p, P);
     g.tiles_touched = carve<uint32_t>(p, P);
     g.bin = carve<uint4>(p, P);
+    g.inst16 = carve<uint16_t>(p, P);
     g.cov3D = carve<float>(p, 6 * P);
     g.clamped = carve<uint8_t>(p, P);
     g.depth_key = carve<uint32_t>(p, P);

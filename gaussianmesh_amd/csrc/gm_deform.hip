@@ -213,10 +213,10 @@ __device__ __forceinline__ void shade_rotated(int deg, const float* Rt, const fl
 }
 
 // Where a fused pass leaves a row's preprocess results: the frame's geometry buffer and the caller's radii
-struct PreSinks { float4* splat; int* radii_int; int* radii_out; uint32_t* tiles; uint4* bin; uint32_t* counters; uint32_t* slots; uint32_t* coarse; uint32_t* depth_key; };
+struct PreSinks { float4* splat; int* radii_int; int* radii_out; uint32_t* tiles; uint4* bin; uint16_t* inst16; uint32_t* counters; uint32_t* slots; uint32_t* coarse; uint32_t* depth_key; };
 
 static PreSinks pre_sinks(const GeomState& g, int* radii) {
-  return PreSinks{g.splat, g.radii, radii, g.tiles_touched, g.bin, g.counters, g.slots, g.coarse, g.depth_key};
+  return PreSinks{g.splat, g.radii, radii, g.tiles_touched, g.bin, g.inst16, g.counters, g.slots, g.coarse, g.depth_key};
 }
 
 // Written once, where it is read: the radius goes to the caller's array (the internal copy exists for callers that pass none);
@@ -231,6 +231,7 @@ __device__ __forceinline__ void pre_write_row(const PreSinks& o, size_t i, int r
   if (tiles >= GM_BIN_COUNT_SAT) o.tiles[i] = tiles;
   if (!DIRECT) {
     o.bin[i] = dbin;
+    o.inst16[i] = (uint16_t)bin_count(dbin);       // what the ordering gathers per id; the record itself is read where it lies (duplicate_kernel)
     o.depth_key[i] = dkey;
   }
   if (i == 0) o.counters[GM_CNT_POLICY] = (uint32_t)tile_cull;

@@ -182,7 +182,11 @@ int gm_mark_visible(int P, const float* means3D, const float* viewmatrix, const 
  *            "clamped" uint8[P] (bit ch set = channel ch clamped), "order" uint32[V] (ids of the V visible Gaussians
  *            in (depth, id) order; V = "bucket_start"[2048]), "bucket_start" uint32[2049], "counters" uint32[32], and the depth-bucket
  *            table of the frame, for tests that ask which route the ordering took: "dmap" uint32[2048] (coarse bin key >> 20 ->
- *            first bucket << 16 | buckets), "bmap" uint32[2048][2] (bucket -> first key, bits of the key range; partition path only)
+ *            first bucket << 16 | buckets), "bmap" uint32[2048][2] (bucket -> first key, bits of the key range; partition path only);
+ *            the emission's inputs: "bin" uint32[P][4] (the emission record of each Gaussian, written by the preprocess kernels of the
+ *            partition path and read in place), "inst16" uint16[P] (the record's instance count: 0xFFFF = 65535 or more, see
+ *            "tiles_touched"; 0 for a culled row), "bin_sorted" uint32[V][4] (the records in depth order: direct placement only);
+ *            "grad_acc" float[P][12] (the backward pass's accumulators: the last field, gm_geom_bytes(P) ends 256 bytes behind it)
  *   image:   "final_T" float[H*W], "n_contrib" uint32[H*W], "ranges" uint32[T][2], "tile_order" uint32[T] (the forward blend's
  *            dispatch order: a permutation of the list tiles)
  *   binning: "pairs" uint32[R][2] = (list tile id | child mask << 16, Gaussian id) per instance, sorted by tile then
