@@ -84,6 +84,7 @@ SIGNATURES = {
     "gm_mesh_rs_packed_batch": (i32, [i32, i32, i32, vp, C.POINTER(vp), vp, vp, vp, C.POINTER(vp), vp]),
     "gm_deform_shade_packed": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gm_cov_to_scale_rot": (i32, [i32, vp, vp, vp, vp]),
+    "gm_sh_rotate": (i32, [i32, i32, i32, vp, vp, vp, vp]),
     "gm_mesh_rs": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gm_mesh_rs_packed": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "gm_mesh_activate_fwd": (i32, [i32, f32] + [vp] * 10 + [vp] * 4 + [f32, vp] + [vp]),

@@ -801,6 +801,18 @@ int gm_cov_to_scale_rot(int N, const float* cov, float* scales, float* rots, voi
   return launch_cov_to_scale_rot(N, cov, scales, rots, reinterpret_cast<hipStream_t>(stream));
 }
 
+int gm_sh_rotate(int N, int deg, int M, const float* shs, const float* rot, float* shs_out, void* stream) {
+  if (N < 0) { set_error("gm_sh_rotate: negative N = %d", N); return GM_ERR_INVALID_ARG; }
+  if (N == 0) return GM_OK;
+  if (deg < 0 || deg > 3) { set_error("gm_sh_rotate: degree %d out of range 0..3", deg); return GM_ERR_INVALID_ARG; }
+  if (M < (deg + 1) * (deg + 1)) { set_error("gm_sh_rotate: rows of M = %d coefficients hold no degree %d", M, deg); return GM_ERR_INVALID_ARG; }
+  if (!shs || !rot || !shs_out) { set_error("gm_sh_rotate: null pointer"); return GM_ERR_INVALID_ARG; }
+  const size_t n = (size_t)N * (size_t)M * 3;
+  if (shs_out != shs && overlaps(shs_out, n, shs, n)) { set_error("gm_sh_rotate: shs_out overlaps shs without being equal to it"); return GM_ERR_INVALID_ARG; }
+  if (overlaps(shs_out, n, rot, (size_t)N * 9)) { set_error("gm_sh_rotate: shs_out overlaps rot"); return GM_ERR_INVALID_ARG; }
+  return launch_sh_rotate(N, deg, M, shs, rot, shs_out, reinterpret_cast<hipStream_t>(stream));
+}
+
 int64_t gm_ssim_partials(int planes, int H, int W) {
   if (planes < 0 || H < 0 || W < 0) return 0;
   return (int64_t)planes * ((H + 31) / 32) * ((W + 31) / 32);

@@ -408,6 +408,8 @@ int launch_deform_shade_packed(int N, int deg, int M, const int* tri, const floa
                                const float* pos, const float* shs, const float* campos, float* pos_out, float* cov6_out,
                                float* rgb_out, float* cov_out, float* rot_out, hipStream_t s);
 int launch_cov_to_scale_rot(int N, const float* cov, float* scales, float* rots, hipStream_t s);
+// gm_shrot.hip: SH rows re-expressed in the frame rot turns away from (shs_out == shs allowed)
+int launch_sh_rotate(int N, int deg, int M, const float* shs, const float* rot, float* shs_out, hipStream_t s);
 int launch_mesh_rs(int Vm, const float* V0, const float* V1, const int* faces, const int* adj_offsets, const int* adj_faces, float* R,
                    float* S, float* state, float* packed, hipStream_t s);
 // the packed gather tables of `frames` deformation frames in one launch (gridDim.z = frame): V1[f] -> packed[f]

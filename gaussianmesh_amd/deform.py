@@ -151,6 +151,30 @@ def cov_to_scale_rot(cov):
     return scales, rots
 
 
+def rotate_sh(shs, rot, deg=3, out=None):
+    """gm_sh_rotate: the SH rows [N,M,3] re-expressed in the unrotated frame - row i becomes the c' with
+    SH_deg(d) . c' == SH_deg(rot_i^T d) . c_i for every unit d, so that sh_colors(pos, campos, rotate_sh(shs, rot), rot=None) is
+    sh_colors(pos, campos, shs, rot=rot) up to float32 rounding (exact for any 3x3 rot [N,3,3], e.g. deform_tensors' rot_out).
+    Coefficients k >= (deg+1)^2 are copied.  out: the result's tensor ([N,M,3] float32, contiguous; may be shs itself: in place)."""
+    lib = _lib.lib()
+    device = shs.device
+    if device.type != "cuda":
+        raise _lib.GmeshError("rotate_sh needs tensors on a HIP (cuda) device; there is no CPU path")
+    shs, rot = _f(shs), _f(rot)
+    if shs.dim() != 3 or shs.shape[2] != 3:
+        raise ValueError("rotate_sh: shs must be [N,M,3]")
+    N, M = shs.shape[0], shs.shape[1]
+    if rot.numel() != 9 * N:
+        raise ValueError("rotate_sh: rot must be [%d,3,3]" % N)
+    if out is None:
+        out = torch.empty_like(shs)
+    elif out.dtype is not torch.float32 or not out.is_contiguous() or out.shape != shs.shape or out.device != device:
+        raise ValueError("rotate_sh: out must be a contiguous float32 tensor of shs' shape on its device")
+    with torch.cuda.device(device):
+        _lib.check(lib.gm_sh_rotate(N, int(deg), M, shs.data_ptr(), rot.data_ptr(), out.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
+    return out
+
+
 def vertex_face_adjacency(faces, Vm):
     """CSR list of the faces incident to each vertex: (offsets int32 [Vm+1], face ids int32 [3F]), host side, once per mesh."""
     import numpy as np
@@ -397,13 +421,32 @@ class SingleObjectDeform:
         self.deform_state = (_f(deform_vertex), cur_rot, cur_shear)
         return pos, cov, rot
 
+    def bake(self, deg=3):
+        """The object in its current state as a PLAIN Gaussian cloud, a dict on the device: xyz [N,3], scales [N,3], rotations [N,4],
+        opacity [N,1], shs [N,M,3] - activated values, ready for GaussianRasterizer(scales=, rotations=, shs=).  Computed from
+        deform_state (not from the cached gaussian_deform_* attributes, of which deform_and_shade updates only some):
+        deform_tensors -> cov_to_scale_rot(cov') -> rotate_sh(gaussian_feature, rot, deg), so a viewer that evaluates SH at the
+        unrotated direction shows the colours the edit path shows.  At rest (deform_state is None) xyz and shs are the object's own
+        tensors and (scales, rotations) come from gaussian_cov.  Changes no attribute; only enqueues."""
+        if self.deform_state is None:
+            pos, cov, shs = self.gaussian_pos, self.gaussian_cov, self.gaussian_feature
+        else:
+            V1, R, S = self.deform_state
+            pos, cov, rot, _ = deform_tensors(self.gaussian_triangles, self.coord, V1 - self.vertex, R.reshape(-1, 3, 3), S.reshape(-1, 3, 3),
+                                              self.gaussian_cov, self.gaussian_pos)
+            shs = rotate_sh(self.gaussian_feature, rot, deg)
+        scales, rotations = cov_to_scale_rot(cov)
+        return dict(xyz=pos, scales=scales, rotations=rotations, opacity=self.gaussian_o, shs=shs)
+
     def deform_and_shade(self, deform_vertex, cur_rot, cur_shear, campos, deg=3):
         """One fused pass for the render loop: updates gaussian_deform_pos / gaussian_deform_cov6 and returns
-        (means3D, colors_precomp, cov3D_precomp) for NewGaussianRasterizer (edittool/__init__.py:464-472)."""
+        (means3D, colors_precomp, cov3D_precomp) for NewGaussianRasterizer (edittool/__init__.py:464-472).  gaussian_deform_cov /
+        gaussian_deform_rot are NOT refreshed (the pass never writes them); deform_state records the state, which is what bake() reads."""
         dV = _f(deform_vertex) - self.vertex
         pos, cov6, rgb = deform_shade(self.gaussian_triangles, self.coord, dV, cur_rot.reshape(-1, 3, 3), cur_shear.reshape(-1, 3, 3),
                                       self.gaussian_cov, self.gaussian_pos, self.gaussian_feature, campos, deg)
         self.gaussian_deform_pos, self.gaussian_deform_cov6 = pos, cov6
+        self.deform_state = (_f(deform_vertex), cur_rot, cur_shear)
         return pos, rgb, cov6
 
     def deform_and_render(self, deform_vertex, cur_rot, cur_shear, viewpoint_camera, bg_color=None, workspace=None, begin_only=False):

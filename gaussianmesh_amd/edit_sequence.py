@@ -2,7 +2,7 @@
 
     python -m gaussianmesh_amd.edit_sequence (--object_gaussian fg.ply | --object_plain_gaussian cloud.ply) --object_origin_mesh mesh.obj \
         (--mesh_sequence DIR | --handle_sequence FILE.npz | --pick_sequence FILE.json) --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N]
-        [--frames_per_launch 4] [--save_maps] [--save_meshes] [--background_gaussian BG.ply [--is_exist_bg]]
+        [--frames_per_launch 4] [--save_maps] [--save_meshes] [--save_baked PATH] [--background_gaussian BG.ply [--is_exist_bg]]
 
 --object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
 faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of the two.
@@ -21,6 +21,9 @@ Exactly one of --mesh_sequence / --handle_sequence / --pick_sequence.  --save_me
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
 files are written on the host while the device renders the next batch (the generator issues batch b + 1 before it yields batch b).
+--save_baked PATH: after rendering, the object in the state of the LAST frame of the sequence as a plain Gaussian PLY (the tool's
+save_baked: positions, (scale, quaternion) of the deformed covariances, SH rows re-expressed in the unrotated frame), for any 3DGS viewer or
+trainer, or --object_plain_gaussian with that frame's mesh.  One file, not one per frame (about 250 MB each at a million Gaussians).
 --background_gaussian BG.ply: the object in front of a free-standing background cloud (edit.py's --is_exist_bg mode, SceneVisualTool;
 --is_exist_bg is accepted and needs the background): frames through SceneVisualTool.render_sequence.  A scene renders no maps, so
 --save_maps with a background is refused.
@@ -91,6 +94,7 @@ def main(argv=None):
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
     parser.add_argument("--save_maps", action="store_true", default=False)
+    parser.add_argument("--save_baked", type=str, default=None)
     parser.add_argument("--background_gaussian", type=str, default=None)
     parser.add_argument("--is_exist_bg", action="store_true", default=False)
     args = parser.parse_args(argv)
@@ -158,6 +162,12 @@ def main(argv=None):
             if args.save_meshes:
                 m = meshes[i]
                 write_obj(stem + ".obj", read_obj(m)[0] if isinstance(m, str) else m.cpu().numpy(), tool.gaussians_list[-1].faces.cpu().numpy())
+    if args.save_baked is not None:
+        last = meshes[-1]
+        for o in tool.gaussians_list:
+            if o.get_name() == args.object_name:
+                o.deform_gaussian(last) if isinstance(last, str) else o.deform_vertices(last)
+        tool.save_baked(args.save_baked, name=args.object_name)
     return len(frames)
 
 

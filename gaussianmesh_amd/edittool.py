@@ -118,6 +118,23 @@ class SingleObjectDeform(_TensorObject):
         self.name = mesh_path if name is None else name
         return self
 
+    def baked_rows(self, deg=3):
+        """bake() as the raw (pre-activation) columns of a plain Gaussian PLY, host arrays keyed as io.save_plain_gaussians takes them:
+        xyz, features_dc / features_rest (the re-expressed SH rows, split), opacity (the raw column of the loaded file, bit for bit: an
+        edit does not touch it), scaling = log(max(scales, 1e-12)) (float32, on the host; the floor keeps a degenerate covariance's zero
+        scale finite), rotation = bake()'s unit quaternions."""
+        b = self.bake(deg)
+        host = lambda t: t.detach().cpu().numpy()
+        shs = host(b["shs"])
+        return dict(xyz=host(b["xyz"]), features_dc=np.ascontiguousarray(shs[:, :1]), features_rest=np.ascontiguousarray(shs[:, 1:]),
+                    opacity=np.asarray(self._loaded["opacity"], np.float32).reshape(-1, 1),
+                    scaling=np.log(np.maximum(host(b["scales"]), np.float32(1e-12))), rotation=host(b["rotations"]))
+
+    def save_baked(self, path, deg=3):
+        """Write the object in its current state as a plain Gaussian PLY (io.save_plain_gaussians' format, unchanged): what another
+        3DGS viewer or trainer opens, and what add_plain_gaussian / load_bg_gaussian read back."""
+        gio.save_plain_gaussians(path, self.baked_rows(deg))
+
     def load_gaussian(self, gaussian_path):
         """:48-64.  The edit tool's loader fills _bc from the saved x, y, z (edittool/mesh_based_gaussian.py:183-184), so
         get_proj_xyz = softmax(xyz) . (v1, v2, v3); positions are the SAVED x, y, z (get_load_xyz)."""
@@ -206,6 +223,23 @@ class ObjectVisualTool:
             if g.get_name() == name:
                 return g.pick(camera, pixels)
         raise ValueError("pick_one_gaussian: no object named %r" % (name,))
+
+    def _baked_objects(self, name, deg):
+        objs = [g for g in self.gaussians_list if name is None or g.get_name() == name]
+        if name is not None and not objs:
+            raise ValueError("save_baked: no object named %r" % (name,))
+        return [g.baked_rows(deg) for g in objs]
+
+    @staticmethod
+    def _write_baked(path, parts):
+        if not parts:
+            raise ValueError("save_baked: nothing to save")
+        gio.save_plain_gaussians(path, {k: np.concatenate([p[k] for p in parts], axis=0) for k in parts[0]})
+
+    def save_baked(self, path, name=None, deg=3):
+        """Every object (or the ones called `name`) in its current state, in list order, as ONE plain Gaussian PLY
+        (SingleObjectDeform.save_baked's columns, concatenated)."""
+        self._write_baked(path, self._baked_objects(name, deg))
 
     def get_camera(self, path):
         """cameras.json of a model directory -> cameras with the reference's attribute names (:547-584)"""
@@ -399,6 +433,7 @@ class SceneVisualTool(ObjectVisualTool):
     def load_bg_gaussian(self, path):
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device=self.device)
         m = gio.load_plain_gaussians(path)
+        self._bg_loaded = m                          # the raw rows, for save_baked(include_background=True)
         self.bg_scale = torch.exp(t(m["scaling"]))
         self.bg_rot = torch.nn.functional.normalize(t(m["rotation"]))
         self.bg_cov3D = _covariance(t(m["scaling"]), t(m["rotation"]))
@@ -407,6 +442,13 @@ class SceneVisualTool(ObjectVisualTool):
         self.bg_opacity = torch.sigmoid(t(m["opacity"]))
         self.bg_deform_rot = torch.eye(3, device=self.device).repeat(self.bg_scale.shape[0], 1, 1)
         self._scene_seq = None                       # the static scene cloud of render_sequence: rebuilt from the new background
+
+    def save_baked(self, path, name=None, deg=3, include_background=False):
+        """ObjectVisualTool.save_baked for a scene; with include_background the background's raw rows come first, bit for bit as loaded:
+        the whole edited scene as one plain Gaussian PLY."""
+        keys = ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")
+        bg = [{k: np.asarray(self._bg_loaded[k], np.float32) for k in keys}] if include_background else []
+        self._write_baked(path, bg + self._baked_objects(name, deg))
 
     def render_sequence(self, frames, *, frames_per_launch=4, aux=False, bg_color=None):
         """ObjectVisualTool.render_sequence for a scene: each frame equals, bit for bit, render_gaussian with the objects the frame names

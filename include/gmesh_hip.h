@@ -511,6 +511,17 @@ int gm_mesh_rs_packed(int Vm, int nfaces, const float* V0, const float* V1, cons
  * eigenvector matrix made right-handed, such that R(q) diag(scales^2) R(q)^T reproduces cov. */
 int gm_cov_to_scale_rot(int N, const float* cov, float* scales, float* rots, void* stream);
 
+/* Spherical-harmonics rows re-expressed in the unrotated frame: the colour half of baking an edit into a plain cloud (deform.rotate_sh).
+ * shs_out row i, coefficients k < (deg+1)^2: the unique c' with  SH_deg(d) . c' == SH_deg(A_i^T d) . c_i  for every unit d,
+ * SH_deg the polynomial of gm_sh.h, A_i = rot[9 i ..] row-major (what gm_deform writes as rot_out), so A^T d is
+ * gm_sh_colors' dir_rot.  Coefficients k >= (deg+1)^2 of a row are copied bit for bit; deg == 0 copies the rows.
+ * shs, shs_out float [N,M,3]; rot float [N,3,3]; shs_out == shs is allowed (a row is read before it is written).  Exact for any 3x3
+ * matrix up to float32 rounding (csrc/gm_shrot.hip); non-finite entries of rot or shs propagate into that row only.  No workspace, no
+ * device allocation, no host wait: stream-ordered; the same input gives the same bits.  N == 0 succeeds and launches nothing.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work, when N > 0: N < 0, deg outside 0..3, M < (deg+1)^2, a NULL pointer, shs_out
+ * overlapping shs other than exactly equal, shs_out overlapping rot. */
+int gm_sh_rotate(int N, int deg, int M, const float* shs, const float* rot, float* shs_out, void* stream);
+
 /* Photometric loss of the training loop (train_mesh_gaussian.py:92-94): replaces utils/loss_utils.py:17-18 (l1_loss) and
  * :23-81 (ssim: 11x11 Gaussian window of sigma 1.5, zero padding 5, depthwise) and the autograd pass through them.
  * img1 (rendered) / img2 (ground truth): float [planes,H,W] (planes = channels, or batch x channels).
