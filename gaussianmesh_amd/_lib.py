@@ -61,6 +61,8 @@ SIGNATURES = {
     "gm_closest_face": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
     "gm_arap_workspace_bytes": (sz, [i32]),
     "gm_arap_solve": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp, sz, vp]),
+    "gm_arap_grid_workspace_bytes": (sz, [i32]),
+    "gm_arap_solve_grid": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp, sz, vp]),
     "gm_ray_mesh_workspace_bytes": (sz, [i32, i32]),
     "gm_ray_mesh": (i32, [i32, vp, vp, i32, vp, i32, vp, f32, f32, vp, vp, vp, vp, sz, vp]),
     "gm_deform": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

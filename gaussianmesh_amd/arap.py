@@ -104,8 +104,10 @@ class ArapSolver:
         self._handle_idx = t(h, torch.int64)
         self._nbytes = _lib.lib().gm_arap_workspace_bytes(Vm)
         self._ws = torch.empty((self._nbytes,), dtype=torch.uint8, device=self.device)
+        self._grid_ws = None                                           # the whole-chip global step's own workspace: made by its first solve
 
-    def solve(self, handle_positions, init=None, outer_iterations=4, cg_iterations=64, cg_tolerance=1e-6, out=None, want_stats=False):
+    def solve(self, handle_positions, init=None, outer_iterations=4, cg_iterations=64, cg_tolerance=1e-6, out=None, want_stats=False,
+              global_step="column"):
         """Positions [Vm,3] float32 on the device with the handles at handle_positions [H,3] (in the order of `handles`) and the rest of
         the mesh following as rigidly as it can.  init: the starting positions (None: the rest pose; the previous frame's solution
         warm-starts a drag); its handle rows are replaced by handle_positions (index_copy on the device).  out: where to write; it may
@@ -113,9 +115,15 @@ class ArapSolver:
         [outer_iterations, 8] on the device = E after the local step, E after the global step, CG steps used for x / y / z, final
         |r| / |b| for x / y / z.  Stream-ordered; nothing here waits for the device (reading stats does).  Two identical calls give
         identical bits.
+        global_step: "column" (gm_arap_solve: one workgroup per coordinate runs the whole CG, no launch per step) or "grid"
+        (gm_arap_solve_grid: rows over the whole chip, two launches per CG step; the same definition, sums in another order, so the
+        last bits differ; its workspace is allocated by the first such solve and kept).  ValueError for any other value, before
+        anything else is checked.  Which is faster at which size: INTEGRATION.md section Q.
         The defaults (4 outer iterations, at most 64 CG steps each, relative residual 1e-6) began as unmeasured starting values and
         were kept after tools/arap_time.py: 7.3 ms at 7.5 k vertices on an MI355X; from the rest pose the
         64-step cap binds before the tolerance, and four such outer iterations reach a lower energy than four with converged solves."""
+        if global_step not in ("column", "grid"):
+            raise ValueError('ArapSolver.solve: global_step must be "column" or "grid"; got %r' % (global_step,))
         if self.device.type != "cuda":
             raise _lib.GmeshError("ArapSolver.solve needs a HIP (cuda) device; there is no CPU path")
         lib = _lib.lib()
@@ -140,11 +148,17 @@ class ArapSolver:
         if out is None:
             out = guess
         stats = torch.zeros((int(outer_iterations), 8), dtype=torch.float64, device=dev) if want_stats and outer_iterations > 0 else None
+        if global_step == "grid":
+            if self._grid_ws is None:
+                self._grid_ws = torch.empty((lib.gm_arap_grid_workspace_bytes(Vm),), dtype=torch.uint8, device=dev)
+            entry, ws = lib.gm_arap_solve_grid, self._grid_ws
+        else:
+            entry, ws = lib.gm_arap_solve, self._ws
         with torch.cuda.device(dev):
-            _lib.check(lib.gm_arap_solve(Vm, self._off.data_ptr(), self._cols.data_ptr(), self._w.data_ptr(), self.rest.data_ptr(),
-                                         self._fixed.data_ptr(), guess.data_ptr(), int(outer_iterations), int(cg_iterations), float(cg_tolerance),
-                                         out.data_ptr(), None if stats is None else stats.data_ptr(), self._ws.data_ptr(), self._nbytes,
-                                         torch.cuda.current_stream(dev).cuda_stream))
+            _lib.check(entry(Vm, self._off.data_ptr(), self._cols.data_ptr(), self._w.data_ptr(), self.rest.data_ptr(),
+                             self._fixed.data_ptr(), guess.data_ptr(), int(outer_iterations), int(cg_iterations), float(cg_tolerance),
+                             out.data_ptr(), None if stats is None else stats.data_ptr(), ws.data_ptr(), ws.numel(),
+                             torch.cuda.current_stream(dev).cuda_stream))
         if want_stats:
             return out, (stats if stats is not None else torch.zeros((0, 8), dtype=torch.float64, device=dev))
         return out

@@ -102,6 +102,36 @@ static int check_raster_args(const RasterArgs& a) {
   return 0;
 }
 
+// gm_arap_solve and gm_arap_solve_grid: one set of refusals, then the launcher of the chosen global step
+typedef int (*ArapLauncher)(int, const int*, const int*, const double*, const float*, const unsigned char*, const float*, int, int, double, float*, double*,
+                            void*, size_t, hipStream_t);
+static int arap_solve_checked(const char* fn, ArapLauncher launch, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                              const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                              double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  if (Vm <= 0) { set_error("%s: Vm = %d (must be positive)", fn, Vm); return GM_ERR_INVALID_ARG; }
+  if (outer_iterations < 0) { set_error("%s: outer_iterations = %d (negative)", fn, outer_iterations); return GM_ERR_INVALID_ARG; }
+  if (cg_iterations < 1) { set_error("%s: cg_iterations = %d (at least 1)", fn, cg_iterations); return GM_ERR_INVALID_ARG; }
+  if (!(cg_tolerance >= 0.0) || cg_tolerance > 1.7976931348623157e308) {
+    set_error("%s: cg_tolerance must be finite and not negative", fn); return GM_ERR_INVALID_ARG;
+  }
+  if (!row_offsets || !cols || !weights || !V0 || !fixed || !V_init || !V_out || !workspace) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  // V_out == V_init is the in-place call; every other meeting of two of these ranges is refused
+  struct { const char* p; size_t n; const char* what; } rg[5] = {
+      {reinterpret_cast<const char*>(V0), 12 * (size_t)Vm, "V0"}, {reinterpret_cast<const char*>(V_init), 12 * (size_t)Vm, "V_init"},
+      {reinterpret_cast<const char*>(V_out), 12 * (size_t)Vm, "V_out"}, {reinterpret_cast<const char*>(stats), 64 * (size_t)outer_iterations, "stats"},
+      {reinterpret_cast<const char*>(workspace), workspace_bytes, "workspace"}};
+  for (int a = 0; a < 5; a++)
+    for (int b = a + 1; b < 5; b++) {
+      if (!rg[a].p || !rg[b].p || !rg[a].n || !rg[b].n) continue;
+      if (a == 1 && b == 2 && rg[a].p == rg[b].p) continue;
+      if (rg[a].p < rg[b].p + rg[b].n && rg[b].p < rg[a].p + rg[a].n) {
+        set_error("%s: %s overlaps %s", fn, rg[a].what, rg[b].what); return GM_ERR_INVALID_ARG;
+      }
+    }
+  return launch(Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats, workspace, workspace_bytes,
+                reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // namespace gm
 
 using namespace gm;
@@ -691,28 +721,16 @@ size_t gm_arap_workspace_bytes(int Vm) { return arap_workspace_bytes(Vm); }
 int gm_arap_solve(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
                   const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
                   void* workspace, size_t workspace_bytes, void* stream) {
-  if (Vm <= 0) { set_error("gm_arap_solve: Vm = %d (must be positive)", Vm); return GM_ERR_INVALID_ARG; }
-  if (outer_iterations < 0) { set_error("gm_arap_solve: outer_iterations = %d (negative)", outer_iterations); return GM_ERR_INVALID_ARG; }
-  if (cg_iterations < 1) { set_error("gm_arap_solve: cg_iterations = %d (at least 1)", cg_iterations); return GM_ERR_INVALID_ARG; }
-  if (!(cg_tolerance >= 0.0) || cg_tolerance > 1.7976931348623157e308) {
-    set_error("gm_arap_solve: cg_tolerance must be finite and not negative"); return GM_ERR_INVALID_ARG;
-  }
-  if (!row_offsets || !cols || !weights || !V0 || !fixed || !V_init || !V_out || !workspace) { set_error("gm_arap_solve: null pointer"); return GM_ERR_INVALID_ARG; }
-  // V_out == V_init is the in-place call; every other meeting of two of these ranges is refused
-  struct { const char* p; size_t n; const char* what; } rg[5] = {
-      {reinterpret_cast<const char*>(V0), 12 * (size_t)Vm, "V0"}, {reinterpret_cast<const char*>(V_init), 12 * (size_t)Vm, "V_init"},
-      {reinterpret_cast<const char*>(V_out), 12 * (size_t)Vm, "V_out"}, {reinterpret_cast<const char*>(stats), 64 * (size_t)outer_iterations, "stats"},
-      {reinterpret_cast<const char*>(workspace), workspace_bytes, "workspace"}};
-  for (int a = 0; a < 5; a++)
-    for (int b = a + 1; b < 5; b++) {
-      if (!rg[a].p || !rg[b].p || !rg[a].n || !rg[b].n) continue;
-      if (a == 1 && b == 2 && rg[a].p == rg[b].p) continue;
-      if (rg[a].p < rg[b].p + rg[b].n && rg[b].p < rg[a].p + rg[a].n) {
-        set_error("gm_arap_solve: %s overlaps %s", rg[a].what, rg[b].what); return GM_ERR_INVALID_ARG;
-      }
-    }
-  return launch_arap_solve(Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats, workspace,
-                           workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  return arap_solve_checked("gm_arap_solve", launch_arap_solve, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations,
+                            cg_tolerance, V_out, stats, workspace, workspace_bytes, stream);
+}
+
+size_t gm_arap_grid_workspace_bytes(int Vm) { return arap_grid_workspace_bytes(Vm); }
+int gm_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
+                       const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  return arap_solve_checked("gm_arap_solve_grid", launch_arap_solve_grid, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations,
+                            cg_iterations, cg_tolerance, V_out, stats, workspace, workspace_bytes, stream);
 }
 
 size_t gm_ray_mesh_workspace_bytes(int R, int F) { return ray_mesh_workspace_bytes(R, F); }

@@ -1,4 +1,4 @@
-// gm_arap.hip -- as-rigid-as-possible deformation of a proxy mesh from dragged handle vertices (gm_arap_solve): the stage that
+// gm_arap.hip -- as-rigid-as-possible deformation of a proxy mesh from dragged handle vertices (gm_arap_solve, gm_arap_solve_grid): the stage that
 // MAKES the deformed mesh gm_mesh_rs then reads (R, S) from.  The reference delegates it to pyACAP, a binary outside its tree;
 // restated from the published algorithm (Sorkine & Alexa, "As-Rigid-As-Possible Surface Modeling", SGP 2007).
 //
@@ -25,6 +25,10 @@
 //   Dot products: butterfly inside each wave, 16 wave partials in LDS, then EVERY thread adds the 16 in index order - all threads
 //   hold the same bits, so the loop's exit tests are uniform, and the result is the same from run to run (no atomics anywhere).
 //   With stats, arap_energy (one workgroup, same reduction) runs after the local and after the global step; without, E is never formed.
+// A SECOND GLOBAL STEP (gm_arap_solve_grid, below arap_global_kernel) spreads the rows over ceil(Vm / 256) workgroups that meet only at
+//   kernel boundaries: arap_grid_rhs once per outer iteration, then arap_grid_product + arap_grid_update per CG step.  Same definition,
+//   same stopping rule, same stats; only the order of the sums differs.  init, local and energy kernels are shared.  No workgroup waits
+//   on another there either, and the sums are again taken in a fixed order (of Vm alone), with no atomics.
 // Conventions of gm_closest.hip: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
 
@@ -150,10 +154,10 @@ __device__ __forceinline__ void arap_rotation(const double F[3][3], double Q[3][
 // a column index forced into [0, Vm): an index outside cannot be reported without a read-back, but it must not fault
 __device__ __forceinline__ int arap_col(const int* cols, int k, int Vm) { return min(max(cols[k], 0), Vm - 1); }
 
-// sum of N values over the workgroup, the same bits in every thread: wave butterfly, ARAP_WAVES partials in LDS, fixed-order sum.
+// sum of N values over the workgroup of W waves, the same bits in every thread: wave butterfly, W partials in LDS, fixed-order sum.
 // The barrier inside is reached by all threads; `part` must not be the array of the previous call (a slow thread may still read it).
-template <int N>
-__device__ __forceinline__ void arap_block_sum(double (&v)[N], double (*part)[ARAP_WAVES]) {
+template <int N, int W = ARAP_WAVES>
+__device__ __forceinline__ void arap_block_sum(double (&v)[N], double (*part)[W]) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < N; k++) {
@@ -166,7 +170,7 @@ __device__ __forceinline__ void arap_block_sum(double (&v)[N], double (*part)[AR
   for (int k = 0; k < N; k++) {
     double s = part[k][0];
 #pragma unroll
-    for (int w = 1; w < ARAP_WAVES; w++) s += part[k][w];
+    for (int w = 1; w < W; w++) s += part[k][w];
     v[k] = s;
   }
 }
@@ -346,6 +350,298 @@ int launch_arap_solve(int Vm, const int* row_offsets, const int* cols, const dou
     if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row);
     hipLaunchKernelGGL(arap_global_kernel, dim3(3), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.diag, k.free_row, k.x, k.r,
                        k.p, k.q, cg_iterations, cg_tolerance * cg_tolerance, it == outer_iterations - 1 ? V_out : nullptr, row);
+    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row + 1);
+  }
+  GM_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- the whole-chip global step (gm_arap_solve_grid): the same systems, the same stopping rule, rows over G = ceil(Vm / 256) workgroups ----
+// One row per thread, all three coordinates in that thread (the CSR row is read once for three products).  The ONLY synchronisation
+// between workgroups is the kernel boundary, so a CG step costs launches; the single-reduction recurrences of Chronopoulos & Gear
+// ("s-step iterative methods for symmetric linear systems", 1989) need two per step where the classic ones need three:
+//   u = r / diag, w = A u, gamma = r . u, delta = w . u;   beta = gamma / gamma_prev, p . A p = delta - beta gamma / alpha_prev,
+//   alpha = gamma / (p . A p);   p = u + beta p, s = w + beta s (= A p), x += alpha p, r -= alpha s.
+//   arap_grid_rhs      r = b - L x, u, |b|^2 partials (once per outer iteration, behind arap_local)
+//   arap_grid_product  w = A u and the workgroup's partial sums of r . u, w . u, r . r: one slot per workgroup, quantity and coordinate
+//   arap_grid_update   every workgroup adds the G slots (arap_slot_sum: the same bits everywhere), makes the column kernel's two exit
+//                      tests per coordinate, and updates p, s, x, r, u of its rows
+// The host cannot see convergence without a wait, so product / update pairs are enqueued for the full cg_iterations; a coordinate that
+// has stopped is frozen (its steps and |r|^2 are carried), and once all three have stopped a launch reads its state and changes nothing.
+// WHO WRITES WHAT.  rhs and product write slots and read none; update reads slots and writes none.  The carried scalars are read and
+// written by update, so they live in a pair: launch k reads carry[k & 1] and workgroup 0 writes carry[(k + 1) & 1] - no workgroup can
+// overwrite what a slower one of the same launch still reads.  Every other array is written by the thread that owns the row.
+#define ARAP_ROW_WAVES 4
+#define ARAP_EDGE_BATCH 8     // arap_grid_product: edges of a row in flight together (a closed triangle mesh has 6 per vertex on average)
+#define ARAP_CARRY 6          // per coordinate: alpha and gamma of the previous step, |b|^2, |r|^2, steps used, stopped (0 / 1)
+
+struct ArapGridWs {
+  double *x, *r, *u, *w, *p, *s;   // [3][Vm] each
+  double* R;                       // [3][Vm][3]
+  double* diag;                    // [Vm]
+  double* bb_slots;                // [3][G]
+  double* slots;                   // [3 quantities][3][G]
+  double* carry;                   // [2][3][ARAP_CARRY]
+  int* free_row;                   // [Vm]
+  char* end;
+  static ArapGridWs from(void* ws, size_t Vm) {
+    char* p = reinterpret_cast<char*>(ws);
+    const size_t G = (Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS;
+    ArapGridWs k;
+    k.x = carve<double>(p, 3 * Vm); k.r = carve<double>(p, 3 * Vm); k.u = carve<double>(p, 3 * Vm);
+    k.w = carve<double>(p, 3 * Vm); k.p = carve<double>(p, 3 * Vm); k.s = carve<double>(p, 3 * Vm);
+    k.R = carve<double>(p, 9 * Vm);
+    k.diag = carve<double>(p, Vm);
+    k.bb_slots = carve<double>(p, 3 * G);
+    k.slots = carve<double>(p, 9 * G);
+    k.carry = carve<double>(p, 2 * 3 * ARAP_CARRY);
+    k.free_row = carve<int>(p, Vm);
+    k.end = p;
+    return k;
+  }
+};
+
+size_t arap_grid_workspace_bytes(int Vm) {
+  ArapGridWs k = ArapGridWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 1));
+  return (size_t)k.end + 256;
+}
+
+// the sums of N rows of G workgroup slots, the same bits in every thread of every workgroup: each wave adds all G for itself, lane l
+// the slots l, l + 64, ... in ascending order, then the butterfly.  The order depends on G alone.  Reached by whole waves only.
+// (The N loads of a pass are in flight together: one memory round trip per 64 workgroups, not one per quantity.)
+template <int N>
+__device__ __forceinline__ void arap_slot_sum(const double* __restrict__ slots, int G, double (&v)[N]) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < N; k++) v[k] = 0.0;
+  for (int g = lane; g < G; g += 64)
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] += slots[(size_t)k * G + g];
+#pragma unroll
+  for (int k = 0; k < N; k++)
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d);
+}
+
+// r = b - L x and u = r / diag of the free rows (held rows: r = u = 0 for the whole solve), |b|^2 partials.  The row arithmetic of
+// arap_global_kernel's first loop, three coordinates at once.
+__global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_rhs_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                         const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                         const double* __restrict__ R, const double* __restrict__ diag,
+                                                                         const int* __restrict__ free_row, const double* __restrict__ x,
+                                                                         double* __restrict__ r, double* __restrict__ u, double* __restrict__ bb_slots) {
+  __shared__ double part[3][ARAP_ROW_WAVES];
+  const int i = blockIdx.x * ARAP_ROW_THREADS + threadIdx.x;
+  double bb[3] = {0.0, 0.0, 0.0};
+  if (i < Vm) {
+    double ri[3] = {0.0, 0.0, 0.0}, ui[3] = {0.0, 0.0, 0.0};
+    if (free_row[i]) {
+      double Ri[3][3], xi[3], pi[3], b[3] = {0.0, 0.0, 0.0}, Lx[3] = {0.0, 0.0, 0.0}, bc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        xi[c] = x[(size_t)c * Vm + i]; pi[c] = (double)V0[3 * (size_t)i + c];
+#pragma unroll
+        for (int a = 0; a < 3; a++) Ri[c][a] = R[((size_t)c * Vm + i) * 3 + a];
+      }
+      for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) {
+        const int j = arap_col(cols, k, Vm);
+        const double wk = weights[k];
+        const int held = !free_row[j];
+        double e[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++) e[a] = pi[a] - (double)V0[3 * (size_t)j + a];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          const double xj = x[(size_t)c * Vm + j];
+          double t = 0.0;
+#pragma unroll
+          for (int a = 0; a < 3; a++) t += (Ri[c][a] + R[((size_t)c * Vm + j) * 3 + a]) * e[a];
+          b[c] += 0.5 * wk * t;
+          Lx[c] += wk * (xi[c] - xj);
+          if (held) bc[c] += wk * xj;                              // a held neighbour moves to the right-hand side
+        }
+      }
+      const double d = diag[i];
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        bc[c] += b[c];
+        ri[c] = b[c] - Lx[c]; ui[c] = ri[c] / d;
+        bb[c] = bc[c] * bc[c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) { r[(size_t)c * Vm + i] = ri[c]; u[(size_t)c * Vm + i] = ui[c]; }
+  }
+  arap_block_sum<3, ARAP_ROW_WAVES>(bb, part);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int c = 0; c < 3; c++) bb_slots[(size_t)c * gridDim.x + blockIdx.x] = bb[c];
+}
+
+// w = A u of the free rows; slots [0..3) r . u, [3..6) w . u, [6..9) r . r.  carry: null in the first launch of an outer iteration
+__global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_product_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                             const double* __restrict__ weights, const int* __restrict__ free_row,
+                                                                             const double* __restrict__ r, const double* __restrict__ u,
+                                                                             double* __restrict__ w, const double* __restrict__ carry,
+                                                                             double* __restrict__ slots) {
+  __shared__ double part[9][ARAP_ROW_WAVES];
+  // the row's own loads are issued ahead of the carry test, so that the test costs no memory round trip of its own
+  // (a thread past the last row reads the last row and adds nothing)
+  const int i = min(blockIdx.x * ARAP_ROW_THREADS + threadIdx.x, Vm - 1);
+  const bool row = blockIdx.x * ARAP_ROW_THREADS + threadIdx.x < Vm;
+  const int k0 = row_offsets[i], k1 = row_offsets[i + 1], fr = free_row[i];
+  double ui[3], ri[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) { ui[c] = u[(size_t)c * Vm + i]; ri[c] = r[(size_t)c * Vm + i]; }
+  if (carry && carry[ARAP_CARRY - 1] != 0.0 && carry[2 * ARAP_CARRY - 1] != 0.0 && carry[3 * ARAP_CARRY - 1] != 0.0) return;   // all stopped: the same in every thread of the grid
+  double s9[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (row && fr) {
+    double q[3] = {0.0, 0.0, 0.0};
+    // ARAP_EDGE_BATCH edges at a time: their column ids and weights are asked for together, then their u together.  An edge at a time
+    // compiled to a wait after the column id and another after u[j] in every trip of the loop.  Past the row's end the last edge is
+    // read again and not added.  Added in CSR order.  (Measured only together with the hoisted loads: INTEGRATION.md section Q.)
+    for (int kb = k0; kb < k1; kb += ARAP_EDGE_BATCH) {
+      int j[ARAP_EDGE_BATCH];
+      double wk[ARAP_EDGE_BATCH], uj[ARAP_EDGE_BATCH][3];
+#pragma unroll
+      for (int t = 0; t < ARAP_EDGE_BATCH; t++) {
+        const int k = min(kb + t, k1 - 1);
+        j[t] = arap_col(cols, k, Vm); wk[t] = weights[k];
+      }
+#pragma unroll
+      for (int t = 0; t < ARAP_EDGE_BATCH; t++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) uj[t][c] = u[(size_t)c * Vm + j[t]];
+#pragma unroll
+      for (int t = 0; t < ARAP_EDGE_BATCH; t++)
+        if (kb + t < k1)
+#pragma unroll
+          for (int c = 0; c < 3; c++) q[c] += wk[t] * (ui[c] - uj[t][c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      w[(size_t)c * Vm + i] = q[c];
+      s9[c] = ri[c] * ui[c]; s9[3 + c] = q[c] * ui[c]; s9[6 + c] = ri[c] * ri[c];
+    }
+  }
+  arap_block_sum<9, ARAP_ROW_WAVES>(s9, part);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int k = 0; k < 9; k++) slots[(size_t)k * gridDim.x + blockIdx.x] = s9[k];
+}
+
+// step `first ? 0 : k` of all three columns: the sums, the exit tests, the update of this thread's row.  last: the launch behind the
+// final product - it only closes the books (|r|^2 of the columns still running) and writes stats_row.  V_out: written when not null.
+__global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_update_kernel(int Vm, const double* __restrict__ diag, const int* __restrict__ free_row,
+                                                                            double* __restrict__ x, double* __restrict__ r, double* __restrict__ u,
+                                                                            const double* __restrict__ w, double* __restrict__ p, double* __restrict__ s,
+                                                                            const double* __restrict__ bb_slots, const double* __restrict__ slots,
+                                                                            const double* __restrict__ carry_in, double* __restrict__ carry_out,
+                                                                            int first, int last, double tol2, float* __restrict__ V_out,
+                                                                            double* __restrict__ stats_row) {
+  // Everything this thread reads is asked for before anything is decided: the row, the slots and the carry arrive in one memory round
+  // trip instead of three in a row.  (p and s of the first step are read and not used.)
+  // (A thread past the last row reads the last row and writes nothing.)
+  const int G = gridDim.x;
+  const int i = min(blockIdx.x * ARAP_ROW_THREADS + threadIdx.x, Vm - 1);
+  const bool row = blockIdx.x * ARAP_ROW_THREADS + threadIdx.x < Vm;
+  const int fr = free_row[i];
+  const double d = diag[i];
+  double xi[3], ri[3], ui[3], wi[3], pi[3], si[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const size_t o = (size_t)c * Vm + i;
+    xi[c] = x[o]; ri[c] = r[o]; ui[c] = u[o]; wi[c] = w[o]; pi[c] = p[o]; si[c] = s[o];
+  }
+  double st[3][ARAP_CARRY], t9[9], alpha[3] = {0.0, 0.0, 0.0}, beta[3] = {0.0, 0.0, 0.0};
+  int act[3] = {0, 0, 0};                                          // this launch updates the column
+  arap_slot_sum<9>(slots, G, t9);
+  if (first) {
+    double bb[3];
+    arap_slot_sum<3>(bb_slots, G, bb);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+#pragma unroll
+      for (int k = 0; k < ARAP_CARRY; k++) st[c][k] = 0.0;
+      st[c][2] = bb[c];
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+      for (int k = 0; k < ARAP_CARRY; k++) st[c][k] = carry_in[c * ARAP_CARRY + k];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++) {                                    // uniform over the grid: everyone holds the same sums and the same carry
+    if (st[c][5] != 0.0) continue;                                 // stopped: frozen, the slots of this column are not looked at
+    const double gamma = t9[c], delta = t9[3 + c], rr = t9[6 + c];
+    st[c][3] = rr;
+    const double bt = first ? 0.0 : gamma / st[c][1];
+    const double pq = first ? delta : delta - bt * gamma / st[c][0];
+    if (!(rr > tol2 * st[c][2]) || !(pq > 0.0)) {                  // converged (or not finite), or p = 0: the column kernel's two exits
+      st[c][5] = 1.0;
+    } else if (!last) {
+      beta[c] = bt; alpha[c] = gamma / pq; act[c] = 1;
+      st[c][0] = alpha[c]; st[c][1] = gamma; st[c][4] += 1.0;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+#pragma unroll
+      for (int k = 0; k < ARAP_CARRY; k++) carry_out[c * ARAP_CARRY + k] = st[c][k];
+      if (stats_row) {
+        const double bb = st[c][2], rr = st[c][3];
+        stats_row[2 + c] = st[c][4];
+        stats_row[5 + c] = bb > 0.0 ? sqrt(rr / bb) : (rr > 0.0 ? (double)INFINITY : 0.0);
+      }
+    }
+  }
+  if (!row) return;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const size_t o = (size_t)c * Vm + i;
+    double xv = xi[c];
+    if (fr && act[c]) {
+      const double pc = first ? ui[c] : ui[c] + beta[c] * pi[c];
+      const double sc = first ? wi[c] : wi[c] + beta[c] * si[c];
+      const double rv = ri[c] - alpha[c] * sc;
+      xv += alpha[c] * pc;
+      p[o] = pc; s[o] = sc; x[o] = xv; r[o] = rv; u[o] = rv / d;
+    }
+    if (V_out) V_out[3 * (size_t)i + c] = (float)xv;
+  }
+}
+
+int launch_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
+                           const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
+                           size_t ws_bytes, hipStream_t s) {
+  const size_t need = arap_grid_workspace_bytes(Vm);
+  if (ws_bytes < need) { set_error("gm_arap_solve_grid: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
+  ArapGridWs k = ArapGridWs::from(ws, (size_t)Vm);
+  const dim3 rows((Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS), threads(ARAP_ROW_THREADS);
+  const double tol2 = cg_tolerance * cg_tolerance;
+  hipLaunchKernelGGL(arap_init_kernel, rows, threads, 0, s, Vm, row_offsets, weights, fixed, V_init, V_out, k.x, k.diag, k.free_row,
+                     outer_iterations == 0 ? 1 : 0);
+  for (int it = 0; it < outer_iterations; it++) {
+    double* row = stats ? stats + 8 * (size_t)it : nullptr;
+    float* out = it == outer_iterations - 1 ? V_out : nullptr;
+    hipLaunchKernelGGL(arap_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R);
+    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row);
+    hipLaunchKernelGGL(arap_grid_rhs_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.diag, k.free_row, k.x, k.r, k.u, k.bb_slots);
+    // steps 0 .. cg_iterations - 1 update; the pair behind them only forms the final |r|^2, which nothing but stats reads
+    // (Unlike the column step, whose loop leaves on the device, a cap costs 2 * cg_iterations host launches per outer iteration whether
+    // or not the solve stops early: a cap far above the steps needed is paid for.  64-bit, so that cap + 1 cannot overflow.)
+    const long long pairs = (long long)cg_iterations + (row ? 1 : 0);
+    for (long long step = 0; step < pairs; step++) {
+      const double* carry_in = k.carry + (step & 1) * 3 * ARAP_CARRY;
+      double* carry_out = k.carry + ((step + 1) & 1) * 3 * ARAP_CARRY;
+      const int last = step == cg_iterations;
+      hipLaunchKernelGGL(arap_grid_product_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, k.free_row, k.r, k.u, k.w, step ? carry_in : nullptr,
+                         k.slots);
+      hipLaunchKernelGGL(arap_grid_update_kernel, rows, threads, 0, s, Vm, k.diag, k.free_row, k.x, k.r, k.u, k.w, k.p, k.s, k.bb_slots, k.slots, carry_in,
+                         carry_out, step == 0 ? 1 : 0, last, tol2, step == pairs - 1 ? out : nullptr, last ? row : nullptr);
+    }
     if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row + 1);
   }
   GM_HIP(hipGetLastError());

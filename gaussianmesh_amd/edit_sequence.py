@@ -3,6 +3,7 @@
     python -m gaussianmesh_amd.edit_sequence (--object_gaussian fg.ply | --object_plain_gaussian cloud.ply) --object_origin_mesh mesh.obj \
         (--mesh_sequence DIR | --handle_sequence FILE.npz | --pick_sequence FILE.json) --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N]
         [--frames_per_launch 4] [--save_maps] [--save_meshes] [--save_baked PATH] [--background_gaussian BG.ply [--is_exist_bg]]
+        [--arap_global_step {column,grid}]
 
 --object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
 faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of the two.
@@ -17,6 +18,8 @@ rest mesh (SingleObjectDeform.pick: the hit face's corner nearest the hit); a pi
 the run.  Frame t has the handles at their rest positions moved by offsets[t] parallel to the image plane (mesh_pick.screen_offset) and
 the anchors in place, solved from frame t - 1's solution as above.
 Exactly one of --mesh_sequence / --handle_sequence / --pick_sequence.  --save_meshes also writes every frame's mesh as {i:05d}.obj.
+--arap_global_step: the solver's global step for --handle_sequence / --pick_sequence, ArapSolver.solve's global_step: column (the default:
+one workgroup per coordinate) or grid (rows over the whole chip; the same meshes to within the last bits).
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
@@ -91,6 +94,7 @@ def main(argv=None):
     source.add_argument("--handle_sequence", type=str, default=None)
     source.add_argument("--pick_sequence", type=str, default=None)
     parser.add_argument("--save_meshes", action="store_true", default=False)
+    parser.add_argument("--arap_global_step", choices=("column", "grid"), default="column")
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
     parser.add_argument("--save_maps", action="store_true", default=False)
@@ -146,7 +150,7 @@ def main(argv=None):
         solver = tool.gaussians_list[-1].set_handles(handles)
         meshes, current = [], None
         for t in range(len(positions)):                           # enqueued back to back: no host wait between the solves
-            current = solver.solve(positions[t], init=current)
+            current = solver.solve(positions[t], init=current, global_step=args.arap_global_step)
             meshes.append(current)
     frames = [(cams[args.camera_id] if args.camera_id is not None else cams[i % len(cams)], {args.object_name: m})
               for i, m in enumerate(meshes)]

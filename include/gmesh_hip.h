@@ -268,6 +268,19 @@ int gm_arap_solve(int Vm, const int* row_offsets, const int* cols, const double*
                   const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* gm_arap_solve with the global step spread over the whole chip: the same definition, parameters, stats layout and refusals, rows over
+ * ceil(Vm / 256) workgroups that meet only at kernel boundaries (no grid barrier, no flag, no cooperative launch).  Per CG step two
+ * launches (single-reduction recurrences of Chronopoulos & Gear), enqueued for the full cg_iterations: a coordinate that has converged,
+ * or whose p . A p is no longer positive, is frozen, and once all three are the remaining launches return after reading the carried
+ * state.  Only the order of the sums differs from gm_arap_solve, and with it the last bits; it is fixed by Vm alone, so two calls on the
+ * same input give the same bits.  Its own workspace: gm_arap_grid_workspace_bytes(Vm) (O(Vm), monotonic, the same for 0 and 1).
+ * cg_iterations has no upper bound here either, but each step of the cap is two host launches per outer iteration, stopped or not:
+ * choose the cap near the steps wanted (the column step, whose loop leaves on the device, takes any cap for free). */
+size_t gm_arap_grid_workspace_bytes(int Vm);
+int gm_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
+                       const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* First hit of every ray on a mesh: what takes an editor from a pixel to a vertex of the current, deformed proxy mesh
  * (mesh_pick.ray_mesh_hits / pick / visible_vertices).  The reference has no such stage: the result is defined by arithmetic.
  * origins, dirs float [R,3], vertices float [Vm,3], faces int32 [F,3] vertex ids.  out_t float [R], out_face int32 [R], out_uv float
