@@ -748,6 +748,71 @@ int gm_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const fl
                          reinterpret_cast<hipStream_t>(stream));
 }
 
+// the grid rules gm_tsdf_integrate and gm_surface_nets share: sizes, the sample count one launch indexes, origin and voxel
+#define GM_TSDF_MAX_SAMPLES (1ll << 28)
+static int check_tsdf_grid(const char* fn, int nx, int ny, int nz, int least, const float* origin, float voxel) {
+  if (nx < least || ny < least || nz < least) { set_error("%s: grid %d x %d x %d (every side at least %d)", fn, nx, ny, nz, least); return GM_ERR_INVALID_ARG; }
+  if ((long long)nx * ny > GM_TSDF_MAX_SAMPLES || (long long)nx * ny * nz > GM_TSDF_MAX_SAMPLES) {
+    set_error("%s: grid %d x %d x %d has more than 2^28 samples", fn, nx, ny, nz); return GM_ERR_INVALID_ARG;
+  }
+  if (!origin) { set_error("%s: null pointer (origin)", fn); return GM_ERR_INVALID_ARG; }
+  if (!(voxel > 0.f) || voxel > 3.4028234e38f || !(origin[0] - origin[0] == 0.f) || !(origin[1] - origin[1] == 0.f) || !(origin[2] - origin[2] == 0.f)) {
+    set_error("%s: voxel must be positive and finite, origin finite", fn); return GM_ERR_INVALID_ARG;
+  }
+  return 0;
+}
+
+int gm_tsdf_integrate(int K, int H, int W, const float* depth, const float* alpha, const float* views, const float* tanfov, int nx, int ny, int nz,
+                      const float* origin, float voxel, float trunc, float alpha_min, int carve, float* tsdf, float* weight, void* stream) {
+  if (K < 0 || H <= 0 || W <= 0 || H > (1 << 24) || W > (1 << 24)) {
+    set_error("gm_tsdf_integrate: invalid sizes K=%d H=%d W=%d", K, H, W); return GM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_tsdf_grid("gm_tsdf_integrate", nx, ny, nz, 1, origin, voxel)) return rc;
+  if (!(trunc > 0.f) || trunc > 3.4028234e38f || alpha_min != alpha_min) {
+    set_error("gm_tsdf_integrate: trunc must be positive and finite, alpha_min not NaN"); return GM_ERR_INVALID_ARG;
+  }
+  if (!tsdf || !weight) { set_error("gm_tsdf_integrate: null pointer (tsdf / weight)"); return GM_ERR_INVALID_ARG; }
+  const size_t n = (size_t)nx * ny * nz, maps = (size_t)K * H * W;
+  if (overlaps(tsdf, n, weight, n)) { set_error("gm_tsdf_integrate: tsdf overlaps weight"); return GM_ERR_INVALID_ARG; }
+  if (K == 0) return GM_OK;
+  if (!depth || !alpha || !views || !tanfov) { set_error("gm_tsdf_integrate: null pointer"); return GM_ERR_INVALID_ARG; }
+  const struct { const float* p; size_t n; const char* what; } in[4] = {{depth, maps, "depth"}, {alpha, maps, "alpha"}, {views, 16 * (size_t)K, "views"},
+                                                                       {tanfov, 2 * (size_t)K, "tanfov"}};
+  for (int i = 0; i < 4; i++)
+    if (overlaps(tsdf, n, in[i].p, in[i].n) || overlaps(weight, n, in[i].p, in[i].n)) {
+      set_error("gm_tsdf_integrate: the volume overlaps %s", in[i].what); return GM_ERR_INVALID_ARG;
+    }
+  return launch_tsdf_integrate(K, H, W, depth, alpha, views, tanfov, nx, ny, nz, origin, voxel, trunc, alpha_min, carve, tsdf, weight,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t gm_surface_nets_workspace_bytes(int nx, int ny, int nz) { return surface_nets_workspace_bytes(nx, ny, nz); }
+int gm_surface_nets(int nx, int ny, int nz, const float* origin, float voxel, const float* tsdf, const float* weight, float min_weight,
+                    int max_vertices, float* out_vertices, int max_faces, int* out_faces, int* out_counts, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  if (int rc = check_tsdf_grid("gm_surface_nets", nx, ny, nz, 2, origin, voxel)) return rc;
+  if (min_weight != min_weight) { set_error("gm_surface_nets: min_weight is NaN"); return GM_ERR_INVALID_ARG; }
+  if (max_vertices < 0 || max_faces < 0) { set_error("gm_surface_nets: negative capacity (%d vertices, %d faces)", max_vertices, max_faces); return GM_ERR_INVALID_ARG; }
+  if (!tsdf || !weight || !out_counts || !workspace || (max_vertices > 0 && !out_vertices) || (max_faces > 0 && !out_faces)) {
+    set_error("gm_surface_nets: null pointer"); return GM_ERR_INVALID_ARG;
+  }
+  const size_t n = (size_t)nx * ny * nz;
+  const struct { const char* p; size_t n; const char* what; } rg[6] = {
+      {reinterpret_cast<const char*>(tsdf), 4 * n, "tsdf"}, {reinterpret_cast<const char*>(weight), 4 * n, "weight"},
+      {reinterpret_cast<const char*>(out_vertices), 12 * (size_t)max_vertices, "out_vertices"},
+      {reinterpret_cast<const char*>(out_faces), 12 * (size_t)max_faces, "out_faces"}, {reinterpret_cast<const char*>(out_counts), 8, "out_counts"},
+      {reinterpret_cast<const char*>(workspace), workspace_bytes, "workspace"}};
+  for (int a = 0; a < 6; a++)
+    for (int b = (a < 2 ? 2 : a + 1); b < 6; b++) {             // (tsdf and weight are only read: they may be one buffer)
+      if (!rg[a].p || !rg[b].p || !rg[a].n || !rg[b].n) continue;
+      if (rg[a].p < rg[b].p + rg[b].n && rg[b].p < rg[a].p + rg[a].n) {
+        set_error("gm_surface_nets: %s overlaps %s", rg[a].what, rg[b].what); return GM_ERR_INVALID_ARG;
+      }
+    }
+  return launch_surface_nets(nx, ny, nz, origin, voxel, tsdf, weight, min_weight, max_vertices, out_vertices, max_faces, out_faces, out_counts, workspace,
+                             workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
 int gm_deform(int N, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
               const float* cov, const float* pos, float* pos_out, float* cov_out, float* rot_out, float* cov6_out,
               void* stream) {

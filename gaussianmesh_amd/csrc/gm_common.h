@@ -498,6 +498,14 @@ int launch_ray_mesh(int R, const float* origins, const float* dirs, int Vm, cons
                     float t_max, float* out_t, int* out_face, float* out_uv, void* ws, size_t ws_bytes, hipStream_t s);
 size_t ray_mesh_workspace_bytes(int R, int F);
 unsigned long long ray_mesh_blocks(int R, int F);
+// gm_tsdf.hip: depth / opacity maps -> signed distance volume -> indexed mesh (origin: three floats on the host)
+int launch_tsdf_integrate(int K, int H, int W, const float* depth, const float* alpha, const float* views, const float* tans, int nx, int ny,
+                          int nz, const float* origin, float voxel, float trunc, float alpha_min, int carve, float* tsdf, float* weight,
+                          hipStream_t s);
+int launch_surface_nets(int nx, int ny, int nz, const float* origin, float voxel, const float* tsdf, const float* weight, float min_weight,
+                        int max_vertices, float* out_vertices, int max_faces, int* out_faces, int* out_counts, void* ws, size_t ws_bytes,
+                        hipStream_t s);
+size_t surface_nets_workspace_bytes(int nx, int ny, int nz);
 
 // number of set bits of a wave-wide 64-bit mask (a ballot) at positions BELOW the calling lane: v_mbcnt_lo + v_mbcnt_hi, two
 // vector instructions and no per-lane mask registers (popcount(mask & lanes_lt) costs four and two registers)

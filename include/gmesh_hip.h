@@ -303,6 +303,55 @@ size_t gm_ray_mesh_workspace_bytes(int R, int F);
 int gm_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const float* vertices, int F, const int* faces, float t_min, float t_max,
                 float* out_t, int* out_face, float* out_uv, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Fuse the depth / opacity maps of K views of one resolution into a truncated signed distance volume: the first half of the step from a
+ * trained cloud to its proxy mesh (proxy_mesh.TsdfVolume.integrate).  The reference has no such stage: the result is defined by arithmetic.
+ * depth, alpha float [K,H,W]: the rasterizer's own maps (depth = sum alpha_i T_i z_i, not normalised; alpha = 1 - T).  views float
+ * [K,16]: each view's world_view_transform, stored transposed as everywhere here (v[4 r + c]); tanfov float [K,2]: tan(FoVx/2),
+ * tan(FoVy/2).  All four on the device.  origin: three floats ON THE HOST, the low corner of the box; voxel: the cell size; sample
+ * (ix, iy, iz) of tsdf / weight float [nz,ny,nx] (read AND written: the volume is state; a fresh one is tsdf = weight = 0) sits at the
+ * voxel's centre.  Per voxel, per view k = 0 .. K-1 in this order, in float32, no contraction, correctly rounded division:
+ *   p = origin + ((float)i + 0.5f) * voxel per axis; xv = ((p.x v[0] + p.y v[4]) + p.z v[8]) + v[12], yv (v[1 + ..]), zv (v[2 + ..])
+ *   not (zv > 0): skip.  px = ((xv / (zv tanx) + 1) W - 1) 0.5, py alike with H; fx = floor(px + 0.5), fy = floor(py + 0.5): the nearest
+ *   pixel; outside the image: skip.  a = alpha[k, fy, fx].
+ *   not (a >= alpha_min): with carve != 0 the sample is FREE SPACE, t = 1; with carve == 0 skip.
+ *   else s = depth[k, fy, fx] / a - zv; not (s >= -trunc): skip (behind the surface: UNOBSERVED, not inside); t = min(1, s / trunc).
+ *   w' = w + 1, D = (D w + t) / w', w = w'.
+ * Every comparison is false on NaN: a NaN skips the view.  K views in one call equal K calls of one view each, bit for bit.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: K < 0, H or W outside [1, 2^24], a grid side < 1 or more than 2^28 samples, a
+ * NULL origin, tsdf or weight (and with K > 0: depth, alpha, views, tanfov), voxel or trunc not positive and finite, a NaN alpha_min or
+ * origin, tsdf overlapping weight, either overlapping a map or the camera rows.  K == 0 succeeds and launches nothing.  One thread per
+ * voxel; the volume is read once and written once per call.  Stream-ordered, no device allocation, no host synchronisation. */
+int gm_tsdf_integrate(int K, int H, int W, const float* depth, const float* alpha, const float* views, const float* tanfov, int nx, int ny, int nz,
+                      const float* origin, float voxel, float trunc, float alpha_min, int carve, float* tsdf, float* weight, void* stream);
+
+/* The volume's zero surface as an indexed triangle mesh, by naive surface nets (no case table; one vertex per crossed cell, shared by
+ * construction; two triangles per crossed grid edge): the second half (proxy_mesh.TsdfVolume.extract).  Defined by arithmetic, float32.
+ * Cell (cx, cy, cz) has the corners (cx + dx, cy + dy, cz + dz), numbered dx + 2 dy + 4 dz; `inside` is D < 0 (an exact 0 is outside).
+ *   A cell is active iff every corner has weight >= min_weight and its corners differ in `inside`.  Its vertex: over the edges in the
+ *   order x: (0,1) (2,3) (4,5) (6,7), y: (0,2) (1,3) (4,6) (5,7), z: (0,4) (1,5) (2,6) (3,7), for each edge (a, b) whose ends differ:
+ *   t = D[a] / (D[a] - D[b]) and three running sums (from 0) each take corner a's offset on their axis, t on the edge's own; m = sum /
+ *   (float)count; position = origin + (((float)c + m) + 0.5f) * voxel per axis.  Vertex ids: the exclusive scan of the active flags over
+ *   the cells in linear order, x fastest.
+ *   Faces: per sample g in linear order and axis a = x, y, z (u, v the next two axes cyclically) the grid edge g -> g + e_a yields a quad
+ *   iff its ends differ and the cells q0 = g - e_u - e_v, q1 = g - e_v, q2 = g, q3 = g - e_u all exist and are active; rows
+ *   (q0, q1, q2), (q0, q2, q3) when g is inside, (q0, q2, q1), (q0, q3, q2) otherwise: the normal points from negative to positive.
+ *   Rows 2 r and 2 r + 1, r the exclusive scan of the quads over (g, a).  An edge next to an inactive cell or the grid's side yields
+ *   nothing: a half-observed volume gives an open boundary there.
+ * out_vertices float [max_vertices,3], out_faces int32 [max_faces,3], out_counts int32 [2] ON THE DEVICE = {vertices, faces} the volume
+ * needs.  A row at or beyond its capacity is NOT written - the rows below it are the prefix of the full result (faces may then name
+ * vertices beyond max_vertices) - and the counts still say what is needed: the caller reads them and re-runs with more room.
+ * The scan is three plain passes between kernel boundaries (sums per 256 entries, recursively; scan of the sums; scatter): the same
+ * bits every run, and no workgroup waits for another.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: a grid side < 2, more than 2^28 samples, a NULL origin, tsdf, weight, out_counts
+ * or workspace (out_vertices / out_faces with a capacity > 0), voxel not positive and finite, NaN origin or min_weight, a negative
+ * capacity, an output or the workspace overlapping anything else; with GM_ERR_BUFFER: a workspace below
+ * gm_surface_nets_workspace_bytes(nx, ny, nz) (about 6 bytes a sample, monotonic in each side, positive at (2, 2, 2)).
+ * Stream-ordered, no device allocation, no host synchronisation. */
+size_t gm_surface_nets_workspace_bytes(int nx, int ny, int nz);
+int gm_surface_nets(int nx, int ny, int nz, const float* origin, float voxel, const float* tsdf, const float* weight, float min_weight,
+                    int max_vertices, float* out_vertices, int max_faces, int* out_faces, int* out_counts, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* Mesh-driven deformation of bound Gaussians; replaces the Jittor tensor algebra of
  * SingleObjectDeform.deform_gaussian (edittool/__init__.py:116-131), tensor-in form:
  *   tri int32 [N,3] vertex ids of the bound face, w float [N,3] barycentric weights,
