@@ -748,6 +748,21 @@ int gm_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const fl
                          reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t gm_mesh_geodesic_workspace_bytes(int Vm, int B, int sweeps) { return mesh_geodesic_workspace_bytes(Vm, B, sweeps); }
+int gm_mesh_geodesic(int Vm, const int* row_offsets, const int* cols, const float* lengths, int B, const int* source_offsets, const int* sources,
+                     float max_distance, int sweeps, int resume, float* dist, int* unsettled, void* workspace, size_t workspace_bytes, void* stream) {
+  if (Vm < 0 || B < 0) { set_error("gm_mesh_geodesic: negative size Vm=%d B=%d", Vm, B); return GM_ERR_INVALID_ARG; }
+  if (sweeps < 1) { set_error("gm_mesh_geodesic: sweeps must be >= 1; got %d", sweeps); return GM_ERR_INVALID_ARG; }
+  if (!(max_distance >= 0.f)) { set_error("gm_mesh_geodesic: max_distance must be >= 0 and not NaN (+inf: no cutoff)"); return GM_ERR_INVALID_ARG; }
+  if (Vm == 0) return GM_OK;
+  if (B < 1 || B > 65535) { set_error("gm_mesh_geodesic: B must be 1 .. 65535 source sets; got %d", B); return GM_ERR_INVALID_ARG; }
+  if (!row_offsets || !cols || !lengths || !source_offsets || !sources || !dist || !unsettled || !workspace) {
+    set_error("gm_mesh_geodesic: null pointer"); return GM_ERR_INVALID_ARG;
+  }
+  return launch_mesh_geodesic(Vm, row_offsets, cols, lengths, B, source_offsets, sources, max_distance, sweeps, resume, dist, unsettled, workspace,
+                              workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
 // the grid rules gm_tsdf_integrate and gm_surface_nets share: sizes, the sample count one launch indexes, origin and voxel
 #define GM_TSDF_MAX_SAMPLES (1ll << 28)
 static int check_tsdf_grid(const char* fn, int nx, int ny, int nz, int least, const float* origin, float voxel) {

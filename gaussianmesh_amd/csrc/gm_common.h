@@ -498,6 +498,10 @@ int launch_ray_mesh(int R, const float* origins, const float* dirs, int Vm, cons
                     float t_max, float* out_t, int* out_face, float* out_uv, void* ws, size_t ws_bytes, hipStream_t s);
 size_t ray_mesh_workspace_bytes(int R, int F);
 unsigned long long ray_mesh_blocks(int R, int F);
+int launch_mesh_geodesic(int Vm, const int* row_offsets, const int* cols, const float* lengths, int B, const int* source_offsets,
+                         const int* sources, float max_distance, int sweeps, int resume, float* dist, int* unsettled, void* ws,
+                         size_t ws_bytes, hipStream_t s);
+size_t mesh_geodesic_workspace_bytes(int Vm, int B, int sweeps);
 // gm_tsdf.hip: depth / opacity maps -> signed distance volume -> indexed mesh (origin: three floats on the host)
 int launch_tsdf_integrate(int K, int H, int W, const float* depth, const float* alpha, const float* views, const float* tans, int nx, int ny,
                           int nz, const float* origin, float voxel, float trunc, float alpha_min, int carve, float* tsdf, float* weight,

@@ -335,6 +335,7 @@ class SingleObjectDeform:
         self.gaussian_deform_cov6 = None
         self.deform_state = None         # (V1, R, S) of the last deform(); None: the rest pose (edittool render_sequence renders it)
         self.arap = None                 # the ArapSolver of set_handles()
+        self.region = None               # set_region_handles(): (picked vertex ids int64 [H], owner int64 [n]) on the device
 
     def get_name(self):
         return self.name
@@ -344,18 +345,83 @@ class SingleObjectDeform:
         """The proxy mesh's vertices as last deformed ([Vm,3], the V1 of deform_state); None: the rest pose.  drag() starts from them."""
         return None if self.deform_state is None else self.deform_state[0]
 
+    def _set_faces(self, faces):
+        self.faces = torch.as_tensor(faces).detach().to(device=self.vertex.device, dtype=torch.int32).contiguous()
+        off, adj = vertex_face_adjacency(self.faces, self.vertex.shape[0])
+        self._adjacency = (torch.tensor(off, device=self.vertex.device), torch.tensor(adj, device=self.vertex.device))
+
     def set_handles(self, vertex_ids, faces=None):
         """Choose the handle vertices of drag(): builds the arap.ArapSolver of this object's rest mesh (its refusals apply).  faces
         [F,3]: the proxy mesh's triangles, for an object built from tensors alone (the file-based object has them)."""
         from .arap import ArapSolver
         if faces is not None:
-            self.faces = torch.as_tensor(faces).detach().to(device=self.vertex.device, dtype=torch.int32).contiguous()
-            off, adj = vertex_face_adjacency(self.faces, self.vertex.shape[0])
-            self._adjacency = (torch.tensor(off, device=self.vertex.device), torch.tensor(adj, device=self.vertex.device))
+            self._set_faces(faces)
         if getattr(self, "faces", None) is None:
             raise ValueError("set_handles: this object has no faces; pass faces=[F,3]")
         self.arap = ArapSolver(self.vertex, self.faces, vertex_ids, device=self.vertex.device)
+        self.region = None
         return self.arap
+
+    def surface_distances(self, vertex_sets, max_distance=None):
+        """Distances along the REST mesh (where picks are resolved and ARAP's energy lives) from each of vertex_sets, a list of id
+        lists: float32 [B,Vm] on the device, +inf beyond max_distance (mesh_region.SurfaceGraph.distances; one 4-byte read-back per
+        64 sweeps).  The graph is built on the host the first time this face tensor is seen and kept."""
+        from .mesh_region import SurfaceGraph
+        if getattr(self, "faces", None) is None:
+            raise ValueError("surface_distances: this object has no faces; set_handles(..., faces=[F,3]) supplies them")
+        cached = getattr(self, "_surface_graph", None)
+        if cached is None or cached[0] is not self.faces:
+            cached = self._surface_graph = (self.faces, SurfaceGraph(self.vertex, self.faces, device=self.vertex.device))
+        return cached[1].distances(vertex_sets, max_distance=max_distance)
+
+    def set_region_handles(self, handle_vertices, grab_radius, free_radius=None, anchor_vertices=(), faces=None):
+        """Choose drag_region()'s handles as surface regions around picked vertices: every vertex within grab_radius (along the rest
+        mesh, surface_distances) of handle_vertices[i] moves with pick i; every vertex within grab_radius of an anchor vertex and, with
+        free_radius, every vertex farther than free_radius from all picks is held at rest; the others bend
+        (mesh_region.region_handles: its order, its refusals).  Distances are computed up to free_radius (grab_radius without it).
+        Builds the ArapSolver through set_handles (faces: as there) and returns it; the region ids are arap.handles."""
+        from .mesh_region import _check_radii, region_handles
+        import numpy as np
+        grab, free = _check_radii("set_region_handles", grab_radius, free_radius)
+        hv = np.asarray(handle_vertices.detach().cpu() if torch.is_tensor(handle_vertices) else handle_vertices).reshape(-1)
+        av = np.asarray(anchor_vertices.detach().cpu() if torch.is_tensor(anchor_vertices) else anchor_vertices).reshape(-1)
+        if hv.size == 0:
+            raise ValueError("set_region_handles: the handle set is empty")
+        if faces is not None:
+            self._set_faces(faces)
+        d = self.surface_distances([[v] for v in hv] + [[v] for v in av], max_distance=grab if free is None else free).cpu().numpy()
+        ids, owner = region_handles(d[:len(hv)], d[len(hv):] if len(av) else None, grab, free)
+        solver = self.set_handles(ids)
+        dev = self.vertex.device
+        self.region = (torch.as_tensor(hv.astype(np.int64), device=dev), torch.as_tensor(owner.astype(np.int64), device=dev))
+        return solver
+
+    def region_targets(self, displacements):
+        """The handle positions [n,3] (in the order of arap.handles) that drag_region(displacements) hands to drag()."""
+        if self.region is None:
+            raise ValueError("drag_region: call set_region_handles(handle_vertices, grab_radius, ...) first")
+        picks, owner = self.region
+        disp = torch.as_tensor(displacements, dtype=torch.float32, device=self.vertex.device) if not torch.is_tensor(displacements) else \
+            displacements.detach().to(device=self.vertex.device, dtype=torch.float32)
+        if disp.shape != (len(picks), 3):
+            raise ValueError("drag_region: displacements must be [%d,3]; got %s" % (len(picks), tuple(disp.shape)))
+        rest = self.vertex.index_select(0, self.arap._handle_idx)
+        moved = rest + disp.index_select(0, owner.clamp(min=0))
+        return torch.where((owner >= 0)[:, None], moved, rest)                             # (held rows: the rest bits themselves)
+
+    def drag_region(self, displacements, **solve_options):
+        """Move the regions of set_region_handles(): the rows grabbed by pick i go to their rest position + displacements[i] ([H,3]: a
+        rigid translation of each grabbed patch), the held rows to their rest position; then drag().  No host wait."""
+        return self.drag(self.region_targets(displacements), **solve_options)
+
+    def drag_region_pixels(self, camera, pixel_offsets, **solve_options):
+        """drag_region() from the screen: pick i's displacement is mesh_pick.screen_offset of the picked vertex's REST position by
+        pixel_offsets[i] ([H,2], parallel to the image plane at that vertex's depth) minus that position.  No host wait."""
+        from . import mesh_pick
+        if self.region is None:
+            raise ValueError("drag_region_pixels: call set_region_handles(handle_vertices, grab_radius, ...) first")
+        at = self.vertex.index_select(0, self.region[0])
+        return self.drag_region(mesh_pick.screen_offset(camera, at, pixel_offsets) - at, **solve_options)
 
     def deform_vertices(self, deform_vertex):
         """deform() from the deformed vertices alone: their per-vertex (R, S) by gm_mesh_rs first."""

@@ -17,6 +17,12 @@ position) and "offsets" [T][len(handles)][2] (per frame the pixel offsets from t
 rest mesh (SingleObjectDeform.pick: the hit face's corner nearest the hit); a pick that misses the mesh, or two picks of one vertex, end
 the run.  Frame t has the handles at their rest positions moved by offsets[t] parallel to the image plane (mesh_pick.screen_offset) and
 the anchors in place, solved from frame t - 1's solution as above.
+Two optional keys turn the picks into surface REGIONS (mesh_region): "grab_radius" (a number >= 0, in mesh units; 0 when only
+"free_radius" is given) and "free_radius" (a number >= grab_radius).  Every vertex within grab_radius of a handle's picked vertex, measured
+along the rest mesh, moves with that handle as one rigid patch; every vertex within grab_radius of an anchor's and, with "free_radius",
+every vertex farther than free_radius from all handles stays at its rest position; the band in between bends
+(SingleObjectDeform.set_region_handles / drag_region).  Two handle regions that overlap, or a handle region that meets an anchor's, end
+the run with a message naming the picks.  With neither key nothing changes: single-vertex handles as above.
 Exactly one of --mesh_sequence / --handle_sequence / --pick_sequence.  --save_meshes also writes every frame's mesh as {i:05d}.obj.
 --arap_global_step: the solver's global step for --handle_sequence / --pick_sequence, ArapSolver.solve's global_step: column (the default:
 one workgroup per coordinate) or grid (rows over the whole chip; the same meshes to within the last bits).
@@ -45,7 +51,8 @@ def mesh_sequence(folder):
 
 def read_pick_sequence(path):
     """A --pick_sequence file -> (camera_id, handles float32 [H,2], anchors float32 [A,2], offsets float32 [T,H,2]); SystemExit naming
-    what is wrong with it.  Host work only."""
+    what is wrong with it.  Host work only.  A file with "grab_radius" or "free_radius" gives a fifth element, (grab_radius float,
+    free_radius float or None)."""
     import json
     import numpy as np
     bad = lambda what: SystemExit("edit_sequence: %s: %s" % (path, what))
@@ -77,7 +84,19 @@ def read_pick_sequence(path):
         offsets = None
     if offsets is None or offsets.ndim != 3 or offsets.shape[0] == 0 or offsets.shape[1:] != (len(handles), 2) or not np.isfinite(offsets).all():
         raise bad('"offsets" must be [T][%d][2] pixel offsets, T >= 1; got shape %s' % (len(handles), None if offsets is None else offsets.shape))
-    return cam, handles, anchors, offsets
+    if "grab_radius" not in doc and "free_radius" not in doc:
+        return cam, handles, anchors, offsets
+
+    def radius(key):
+        r = doc.get(key)
+        if isinstance(r, bool) or not isinstance(r, (int, float)) or not 0.0 <= float(r) < float("inf"):
+            raise bad('"%s" must be a finite number >= 0 (a distance along the mesh, in its units); got %r' % (key, r))
+        return float(r)
+    grab = radius("grab_radius") if "grab_radius" in doc else 0.0
+    free = radius("free_radius") if "free_radius" in doc else None
+    if free is not None and free < grab:
+        raise bad('"free_radius" %g is below "grab_radius" %g' % (free, grab))
+    return cam, handles, anchors, offsets, (grab, free)
 
 
 def main(argv=None):
@@ -107,7 +126,8 @@ def main(argv=None):
     if args.background_gaussian is not None and args.save_maps:
         parser.error("--save_maps: a scene with a background renders no depth / alpha maps; drop --save_maps or the background")
     if args.pick_sequence is not None:
-        pick_camera, pick_handles, pick_anchors, pick_offsets = read_pick_sequence(args.pick_sequence)
+        pick = read_pick_sequence(args.pick_sequence)
+        (pick_camera, pick_handles, pick_anchors, pick_offsets), pick_radii = pick[:4], (pick[4] if len(pick) > 4 else None)
 
     import numpy as np
     import torch
@@ -124,7 +144,7 @@ def main(argv=None):
         tool.add_plain_gaussian(args.object_plain_gaussian, args.object_origin_mesh, args.object_name)
     else:
         tool.add_gaussian(args.object_gaussian, args.object_origin_mesh, args.object_name)
-    handles = None
+    handles = solver = None
     if args.handle_sequence is not None:
         with np.load(args.handle_sequence) as z:
             handles, positions = np.asarray(z["handles"]).reshape(-1), np.asarray(z["positions"], np.float32)
@@ -145,9 +165,19 @@ def main(argv=None):
                 raise SystemExit("edit_sequence: %s: %s and %s pick the same vertex %d" % (args.pick_sequence, names[list(handles[:i]).index(v)], names[i], v))
         rest = obj.vertex[torch.as_tensor(handles, device=obj.vertex.device)]
         offsets = torch.as_tensor(pick_offsets, device=rest.device)
-        positions = [torch.cat([screen_offset(cam, rest[:len(pick_handles)], offsets[t]), rest[len(pick_handles):]], 0) for t in range(len(offsets))]
+        if pick_radii is None:
+            positions = [torch.cat([screen_offset(cam, rest[:len(pick_handles)], offsets[t]), rest[len(pick_handles):]], 0) for t in range(len(offsets))]
+        else:                                                                         # the picks grown into surface regions
+            H = len(pick_handles)
+            try:
+                solver = obj.set_region_handles(handles[:H], pick_radii[0], pick_radii[1], anchor_vertices=handles[H:])
+            except ValueError as e:
+                raise SystemExit("edit_sequence: %s: %s" % (args.pick_sequence, e))
+            handles = solver.handles
+            positions = [obj.region_targets(screen_offset(cam, rest[:H], offsets[t]) - rest[:H]) for t in range(len(offsets))]
     if handles is not None:
-        solver = tool.gaussians_list[-1].set_handles(handles)
+        if solver is None:
+            solver = tool.gaussians_list[-1].set_handles(handles)
         meshes, current = [], None
         for t in range(len(positions)):                           # enqueued back to back: no host wait between the solves
             current = solver.solve(positions[t], init=current, global_step=args.arap_global_step)

@@ -216,6 +216,21 @@ class ObjectVisualTool:
                     g.set_handles(ids)
                 g.drag(handle_positions, **solve_options)
 
+    def drag_region_one_gaussian(self, name, handle_vertices, displacements, grab_radius, free_radius=None, anchor_vertices=(), **solve_options):
+        """drag_one_gaussian with surface regions for handles: on the objects called `name`, everything within grab_radius (along the
+        rest mesh) of handle_vertices[i] moves by displacements[i] ([H,3]), everything within grab_radius of an anchor vertex or, with
+        free_radius, farther than free_radius from every pick stays at rest (SingleObjectDeform.set_region_handles / drag_region).  The
+        regions and the solver are built on the first call and kept while the vertices and radii stay the same."""
+        as_ids = lambda a: np.asarray(a.detach().cpu() if torch.is_tensor(a) else a).reshape(-1)
+        key = (tuple(as_ids(handle_vertices).tolist()), tuple(as_ids(anchor_vertices).tolist()), float(grab_radius),
+               None if free_radius is None else float(free_radius))
+        for g in self.gaussians_list:
+            if g.get_name() == name:
+                if g.region is None or getattr(g, "_region_key", None) != key:
+                    g.set_region_handles(key[0], key[2], key[3], key[1])
+                    g._region_key = key
+                g.drag_region(displacements, **solve_options)
+
     def pick_one_gaussian(self, name, camera, pixels):
         """What lies under pixels [P,2] of the camera on the current proxy mesh of the (first) object called `name`
         (SingleObjectDeform.pick): dict(face, vertex, point, depth) on the device; the vertex ids are drag_one_gaussian's."""

@@ -303,6 +303,32 @@ size_t gm_ray_mesh_workspace_bytes(int R, int F);
 int gm_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const float* vertices, int F, const int* faces, float t_min, float t_max,
                 float* out_t, int* out_face, float* out_uv, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Shortest-path distances along a proxy mesh from B independent source sets: what grows a picked vertex into a surface region
+ * (mesh_region.SurfaceGraph.distances / region_handles).  The reference has no such stage: the result is defined by arithmetic.
+ * (row_offsets int32 [Vm+1], cols int32 [nnz], lengths float [nnz]): a symmetric CSR with lengths >= 0 (mesh_region.surface_graph: the
+ * mesh's edges and one unfolded edge across each interior edge).  source_offsets int32 [B+1], sources int32 [source_offsets[B]]: set b
+ * is sources[source_offsets[b] .. source_offsets[b+1]); dist float [B,Vm], unsettled int32 [1].  ALL ON THE DEVICE.  Per set:
+ *   d*[v] = the minimum over paths s = p0, .., pk = v from a source s of the float32 sum taken left to right,
+ *   fl(..fl(fl(0 + l01) + l12).. ); 0 at sources, +inf where no path arrives; dist[b][v] = d*[v] if d*[v] <= max_distance, else +inf
+ *   (the cutoff is inclusive; +inf: none).  A candidate above the cutoff is dropped, a NaN candidate never wins.
+ * fl(d + l) >= d and d <= d' => fl(d + l) <= fl(d' + l), so every order of relaxations d[v] <- min(d[v], fl(d[u] + l_uv)) run until
+ * none lowers anything ends at d*: the bits are those of a float32 Dijkstra, whatever the schedule (csrc/gm_geodesic.hip).
+ * resume == 0: dist is initialised (+inf, then 0 at each source of its own set; a source id outside [0, Vm) is skipped, an empty set
+ * leaves its row +inf).  resume != 0: dist is taken as it stands and source_offsets / sources are not read.  Then `sweeps` relaxation
+ * launches on a grid of ceil(Vm / 256) x B are enqueued, in place, one thread per row, only the row's thread stores it; each counts the
+ * rows it lowered, and one whose predecessor lowered nothing returns at once.  *unsettled = the count of the last sweep: 0 means dist
+ * is final; otherwise call again with resume = 1 (no workgroup ever waits for another: termination is decided between launches).
+ * At most Vm sweeps are ever needed.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: a negative size, sweeps < 1, a NaN or negative max_distance, and with Vm > 0: B
+ * outside 1 .. 65535, a NULL among the pointers (sources and source_offsets too, also with resume); with GM_ERR_BUFFER: a workspace
+ * below gm_mesh_geodesic_workspace_bytes(Vm, B, sweeps) (O(sweeps), monotonic, positive at 0).  Vm == 0 succeeds and launches nothing.
+ * The CSR cannot be checked here without a read-back: column ids are forced into [0, Vm) - no fault, no meaning -, row_offsets and
+ * source_offsets must ascend within their arrays (SurfaceGraph builds them itself); negative lengths are the caller's error, and the
+ * sweep budget bounds the work regardless.  Stream-ordered, no device allocation, no host synchronisation. */
+size_t gm_mesh_geodesic_workspace_bytes(int Vm, int B, int sweeps);
+int gm_mesh_geodesic(int Vm, const int* row_offsets, const int* cols, const float* lengths, int B, const int* source_offsets, const int* sources,
+                     float max_distance, int sweeps, int resume, float* dist, int* unsettled, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fuse the depth / opacity maps of K views of one resolution into a truncated signed distance volume: the first half of the step from a
  * trained cloud to its proxy mesh (proxy_mesh.TsdfVolume.integrate).  The reference has no such stage: the result is defined by arithmetic.
  * depth, alpha float [K,H,W]: the rasterizer's own maps (depth = sum alpha_i T_i z_i, not normalised; alpha = 1 - T).  views float
