@@ -57,6 +57,15 @@ def _components(Vm, rows, cols):
         label = new
 
 
+def sequence_runs(T, batch):
+    """The runs of ArapSolver.solve_sequence: [(start, end)] covering frames 0 .. T - 1 in order, `batch` frames each, the last one
+    possibly shorter; [] for T == 0.  Host arithmetic only."""
+    T, batch = int(T), int(batch)
+    if T < 0 or batch < 1:
+        raise ValueError("sequence_runs: T >= 0 and batch >= 1; got T = %d, batch = %d" % (T, batch))
+    return [(a, min(a + batch, T)) for a in range(0, T, batch)]
+
+
 class ArapSolver:
     """As-rigid-as-possible deformation of one mesh from one set of handle vertices.  Built once: the edge CSR (edge_csr), the mask of
     held rows (the handles, and PINNED vertices: those whose weights sum to 0 - unreferenced, or every face at them degenerate - which
@@ -105,6 +114,7 @@ class ArapSolver:
         self._nbytes = _lib.lib().gm_arap_workspace_bytes(Vm)
         self._ws = torch.empty((self._nbytes,), dtype=torch.uint8, device=self.device)
         self._grid_ws = None                                           # the whole-chip global step's own workspace: made by its first solve
+        self._batch_ws = {}                                            # global_step -> solve_batch's workspace, grown to the largest B seen
 
     def solve(self, handle_positions, init=None, outer_iterations=4, cg_iterations=64, cg_tolerance=1e-6, out=None, want_stats=False,
               global_step="column"):
@@ -162,3 +172,98 @@ class ArapSolver:
         if want_stats:
             return out, (stats if stats is not None else torch.zeros((0, 8), dtype=torch.float64, device=dev))
         return out
+
+    def solve_batch(self, handle_positions, init=None, outer_iterations=4, cg_iterations=64, cg_tolerance=1e-6, out=None, want_stats=False,
+                    global_step="column"):
+        """B solves of this mesh and handle set in ONE launch chain (gm_arap_solve_batch): handle_positions [B,H,3], B in
+        1 .. GM_ARAP_BATCH_MAX (64).  Returns [B,Vm,3] float32 on the device, with want_stats also float64 [B,outer_iterations,8]; item
+        b is bit for bit solve(handle_positions[b], init=init[b], ...) with the same options - every item stops on its own sums, and
+        the chain has the launches of one single solve, whatever B.  init: None (the rest pose), one [Vm,3] start shared by all items,
+        or [B,Vm,3]; out: where to write, which may be the [B,Vm,3] init itself.  The workspace of each global step is allocated by the
+        first such call and grown to the largest B seen.  Stream-ordered; nothing here waits for the device.
+        THE TRADE.  The items of a batch cannot start from one another: where a chain of solve() calls warm-starts frame t from frame
+        t - 1, a batch starts all its frames from one mesh (solve_sequence: the last frame of the previous run), so a frame deep in
+        a run starts farther from its answer and, at a fixed number of iterations, may end at a higher energy.  What that costs against
+        the time saved: tools/arap_time.py --batch, INTEGRATION.md section Q.
+        ValueError for a bad global_step first, then for shapes and B; GmeshError on a solver without a device."""
+        if global_step not in ("column", "grid"):
+            raise ValueError('ArapSolver.solve_batch: global_step must be "column" or "grid"; got %r' % (global_step,))
+        if self.device.type != "cuda":
+            raise _lib.GmeshError("ArapSolver.solve_batch needs a HIP (cuda) device; there is no CPU path")
+        lib = _lib.lib()
+        Vm, dev, H = self.Vm, self.device, len(self.handles)
+        hp = torch.as_tensor(np.asarray(handle_positions), dtype=torch.float32, device=dev) if not torch.is_tensor(handle_positions) else \
+            handle_positions.detach().to(device=dev, dtype=torch.float32)
+        if hp.dim() != 3 or hp.shape[1:] != (H, 3):
+            raise ValueError("ArapSolver.solve_batch: handle_positions must be [B,%d,3]; got %s" % (H, tuple(hp.shape)))
+        B = hp.shape[0]
+        if not 1 <= B <= _lib.GM_ARAP_BATCH_MAX:
+            raise ValueError("ArapSolver.solve_batch: B = %d; a batch holds 1 .. %d solves" % (B, _lib.GM_ARAP_BATCH_MAX))
+        if init is not None:
+            if not torch.is_tensor(init):
+                init = torch.as_tensor(np.asarray(init), dtype=torch.float32, device=dev)
+            if init.shape != (Vm, 3) and init.shape != (B, Vm, 3):
+                raise ValueError("ArapSolver.solve_batch: init must be [%d,3] or [%d,%d,3]; got %s" % (Vm, B, Vm, tuple(init.shape)))
+        if out is not None and (not torch.is_tensor(out) or out.shape != (B, Vm, 3) or out.dtype is not torch.float32 or not out.is_contiguous()
+                                or out.device != self.rest.device):
+            raise ValueError("ArapSolver.solve_batch: out must be a contiguous float32 [%d,%d,3] tensor on the solver's device" % (B, Vm))
+        if out is not None and out is init:
+            guess = out                                                # in place
+        else:
+            start = self.rest if init is None else init.detach().to(device=dev, dtype=torch.float32)
+            guess = start.expand(B, Vm, 3).clone(memory_format=torch.contiguous_format)
+        guess.index_copy_(1, self._handle_idx, hp)
+        if out is None:
+            out = guess
+        stats = torch.zeros((B, int(outer_iterations), 8), dtype=torch.float64, device=dev) if want_stats and outer_iterations > 0 else None
+        step = 1 if global_step == "grid" else 0
+        need = lib.gm_arap_batch_workspace_bytes(Vm, B, step)
+        ws = self._batch_ws.get(global_step)
+        if ws is None or ws.numel() < need:
+            ws = self._batch_ws[global_step] = torch.empty((need,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.gm_arap_solve_batch(B, step, Vm, self._off.data_ptr(), self._cols.data_ptr(), self._w.data_ptr(), self.rest.data_ptr(),
+                                               self._fixed.data_ptr(), guess.data_ptr(), int(outer_iterations), int(cg_iterations),
+                                               float(cg_tolerance), out.data_ptr(), None if stats is None else stats.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+        if want_stats:
+            return out, (stats if stats is not None else torch.zeros((B, 0, 8), dtype=torch.float64, device=dev))
+        return out
+
+    def solve_sequence(self, positions, init=None, batch=4, **solve_options):
+        """The meshes [T,Vm,3] of a drag whose frame t has the handles at positions[t] ([T,H,3]), `batch` frames per launch chain
+        (sequence_runs; the last run may be shorter).  Every frame of a run starts from the LAST frame of the previous run, the first
+        run from init (None: the rest pose).  batch=1 is the chain solve(positions[t], init=frame t - 1) bit for bit (through solve
+        itself); a larger batch gives up the warm start inside a run for its launches (solve_batch: THE TRADE).  solve_options: those
+        of solve / solve_batch; with want_stats returns (meshes, stats [T,outer_iterations,8]).  Nothing here waits for the device."""
+        step = solve_options.get("global_step", "column")
+        if step not in ("column", "grid"):
+            raise ValueError('ArapSolver.solve_sequence: global_step must be "column" or "grid"; got %r' % (step,))
+        if self.device.type != "cuda":
+            raise _lib.GmeshError("ArapSolver.solve_sequence needs a HIP (cuda) device; there is no CPU path")
+        if "out" in solve_options:
+            raise ValueError("ArapSolver.solve_sequence: out is not an option here; the [T,Vm,3] result is allocated")
+        if isinstance(batch, bool) or int(batch) != batch or not 1 <= batch <= _lib.GM_ARAP_BATCH_MAX:
+            raise ValueError("ArapSolver.solve_sequence: batch = %r; a run holds 1 .. %d frames" % (batch, _lib.GM_ARAP_BATCH_MAX))
+        dev, H = self.device, len(self.handles)
+        if isinstance(positions, (list, tuple)) and len(positions) and all(torch.is_tensor(p) for p in positions):
+            positions = torch.stack([p.detach().to(device=dev, dtype=torch.float32) for p in positions], 0)
+        pos = torch.as_tensor(np.asarray(positions), dtype=torch.float32, device=dev) if not torch.is_tensor(positions) else \
+            positions.detach().to(device=dev, dtype=torch.float32)
+        if pos.dim() != 3 or pos.shape[1:] != (H, 3):
+            raise ValueError("ArapSolver.solve_sequence: positions must be [T,%d,3]; got %s" % (H, tuple(pos.shape)))
+        T, want_stats = pos.shape[0], bool(solve_options.get("want_stats"))
+        meshes = torch.empty((T, self.Vm, 3), dtype=torch.float32, device=dev)
+        stats, current = [], init
+        for a, b in sequence_runs(T, int(batch)):
+            if batch == 1:
+                got = self.solve(pos[a], init=current, out=meshes[a], **solve_options)
+            else:
+                got = self.solve_batch(pos[a:b], init=current, out=meshes[a:b], **solve_options)
+            if want_stats:
+                stats.append(got[1].reshape(b - a, -1, 8))
+            current = meshes[b - 1]
+        if want_stats:
+            outer = int(solve_options.get("outer_iterations", 4))
+            return meshes, (torch.cat(stats, 0) if stats else torch.zeros((0, max(outer, 0), 8), dtype=torch.float64, device=dev))
+        return meshes

@@ -102,12 +102,11 @@ static int check_raster_args(const RasterArgs& a) {
   return 0;
 }
 
-// gm_arap_solve and gm_arap_solve_grid: one set of refusals, then the launcher of the chosen global step
-typedef int (*ArapLauncher)(int, const int*, const int*, const double*, const float*, const unsigned char*, const float*, int, int, double, float*, double*,
-                            void*, size_t, hipStream_t);
-static int arap_solve_checked(const char* fn, ArapLauncher launch, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
-                              const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
-                              double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+// gm_arap_solve, gm_arap_solve_grid and gm_arap_solve_batch: one set of refusals (B items: V_init, V_out and stats span B solves'
+// worth), then the launcher of the chosen global step
+static int arap_args_checked(const char* fn, int B, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                             const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                             double* stats, void* workspace, size_t workspace_bytes) {
   if (Vm <= 0) { set_error("%s: Vm = %d (must be positive)", fn, Vm); return GM_ERR_INVALID_ARG; }
   if (outer_iterations < 0) { set_error("%s: outer_iterations = %d (negative)", fn, outer_iterations); return GM_ERR_INVALID_ARG; }
   if (cg_iterations < 1) { set_error("%s: cg_iterations = %d (at least 1)", fn, cg_iterations); return GM_ERR_INVALID_ARG; }
@@ -117,8 +116,8 @@ static int arap_solve_checked(const char* fn, ArapLauncher launch, int Vm, const
   if (!row_offsets || !cols || !weights || !V0 || !fixed || !V_init || !V_out || !workspace) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
   // V_out == V_init is the in-place call; every other meeting of two of these ranges is refused
   struct { const char* p; size_t n; const char* what; } rg[5] = {
-      {reinterpret_cast<const char*>(V0), 12 * (size_t)Vm, "V0"}, {reinterpret_cast<const char*>(V_init), 12 * (size_t)Vm, "V_init"},
-      {reinterpret_cast<const char*>(V_out), 12 * (size_t)Vm, "V_out"}, {reinterpret_cast<const char*>(stats), 64 * (size_t)outer_iterations, "stats"},
+      {reinterpret_cast<const char*>(V0), 12 * (size_t)Vm, "V0"}, {reinterpret_cast<const char*>(V_init), 12 * (size_t)Vm * B, "V_init"},
+      {reinterpret_cast<const char*>(V_out), 12 * (size_t)Vm * B, "V_out"}, {reinterpret_cast<const char*>(stats), 64 * (size_t)outer_iterations * B, "stats"},
       {reinterpret_cast<const char*>(workspace), workspace_bytes, "workspace"}};
   for (int a = 0; a < 5; a++)
     for (int b = a + 1; b < 5; b++) {
@@ -128,6 +127,17 @@ static int arap_solve_checked(const char* fn, ArapLauncher launch, int Vm, const
         set_error("%s: %s overlaps %s", fn, rg[a].what, rg[b].what); return GM_ERR_INVALID_ARG;
       }
     }
+  return 0;
+}
+
+typedef int (*ArapLauncher)(int, const int*, const int*, const double*, const float*, const unsigned char*, const float*, int, int, double, float*, double*,
+                            void*, size_t, hipStream_t);
+static int arap_solve_checked(const char* fn, ArapLauncher launch, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                              const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                              double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = arap_args_checked(fn, 1, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats,
+                                 workspace, workspace_bytes))
+    return rc;
   return launch(Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats, workspace, workspace_bytes,
                 reinterpret_cast<hipStream_t>(stream));
 }
@@ -731,6 +741,23 @@ int gm_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const do
                        void* workspace, size_t workspace_bytes, void* stream) {
   return arap_solve_checked("gm_arap_solve_grid", launch_arap_solve_grid, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations,
                             cg_iterations, cg_tolerance, V_out, stats, workspace, workspace_bytes, stream);
+}
+
+size_t gm_arap_batch_workspace_bytes(int Vm, int B, int global_step) {
+  if (Vm <= 0 || B < 1 || B > GM_ARAP_BATCH_MAX || (global_step != 0 && global_step != 1)) return 0;
+  return arap_batch_workspace_bytes(Vm, B, global_step);
+}
+int gm_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                        const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                        double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "gm_arap_solve_batch";
+  if (B < 1 || B > GM_ARAP_BATCH_MAX) { set_error("%s: B = %d (1 .. %d)", fn, B, GM_ARAP_BATCH_MAX); return GM_ERR_INVALID_ARG; }
+  if (global_step != 0 && global_step != 1) { set_error("%s: global_step = %d (0 column, 1 grid)", fn, global_step); return GM_ERR_INVALID_ARG; }
+  if (int rc = arap_args_checked(fn, B, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats,
+                                 workspace, workspace_bytes))
+    return rc;
+  return launch_arap_solve_batch(B, global_step, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats,
+                                 workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 size_t gm_ray_mesh_workspace_bytes(int R, int F) { return ray_mesh_workspace_bytes(R, F); }

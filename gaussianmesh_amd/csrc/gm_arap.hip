@@ -29,6 +29,10 @@
 //   kernel boundaries: arap_grid_rhs once per outer iteration, then arap_grid_product + arap_grid_update per CG step.  Same definition,
 //   same stopping rule, same stats; only the order of the sums differs.  init, local and energy kernels are shared.  No workgroup waits
 //   on another there either, and the sums are again taken in a fixed order (of Vm alone), with no atomics.
+// A BATCH (gm_arap_solve_batch) is the second grid dimension of every kernel: workgroup (., b) runs item b - its own V_init / V_out, stats
+//   rows and workspace slab (state columns, R, slots, carry), `slab` doubles from item b - 1's - on the one mesh: CSR, weights, V0, diag
+//   and free_row are shared (item 0's workgroups write the last two, in arap_init).  The single solves are a batch of one, through the
+//   same kernels: an item's bits do not depend on the batch it rides in.  No workgroup reads what another item's wrote.
 // Conventions of gm_closest.hip: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
 
@@ -55,6 +59,18 @@ struct ArapWs {
     k.diag = carve<double>(p, Vm);
     k.free_row = carve<int>(p, Vm);
     k.end = p;
+    return k;
+  }
+  // B items: diag and free_row once, then per item a slab of *slab doubles (x, r, p, q, R); the pointers are item 0's
+  static ArapWs batch(void* ws, size_t Vm, size_t B, size_t* slab) {
+    char* p = reinterpret_cast<char*>(ws);
+    ArapWs k;
+    k.diag = carve<double>(p, Vm);
+    k.free_row = carve<int>(p, Vm);
+    k.x = carve<double>(p, 3 * Vm); k.r = carve<double>(p, 3 * Vm); k.p = carve<double>(p, 3 * Vm); k.q = carve<double>(p, 3 * Vm);
+    k.R = carve<double>(p, 9 * Vm);
+    *slab = (size_t)(carve<double>(p, 0) - k.x);                   // a multiple of 256 bytes: every item's arrays are aligned as item 0's
+    k.end = reinterpret_cast<char*>(k.x + B * *slab);
     return k;
   }
 };
@@ -179,28 +195,31 @@ __device__ __forceinline__ void arap_block_sum(double (&v)[N], double (*part)[W]
 __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_init_kernel(int Vm, const int* __restrict__ row_offsets, const double* __restrict__ weights,
                                                                      const unsigned char* __restrict__ fixed, const float* V_init, float* V_out,
                                                                      double* __restrict__ x, double* __restrict__ diag, int* __restrict__ free_row,
-                                                                     int copy_only) {
+                                                                     int copy_only, size_t slab) {
   const int i = blockIdx.x * ARAP_ROW_THREADS + threadIdx.x;
   if (i >= Vm) return;
+  V_init += (size_t)blockIdx.y * 3 * Vm; V_out += (size_t)blockIdx.y * 3 * Vm; x += blockIdx.y * slab;
   const float v[3] = {V_init[3 * (size_t)i], V_init[3 * (size_t)i + 1], V_init[3 * (size_t)i + 2]};
   if (copy_only) {
 #pragma unroll
     for (int c = 0; c < 3; c++) V_out[3 * (size_t)i + c] = v[c];
     return;
   }
-  double d = 0.0;
-  for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) d += weights[k];
 #pragma unroll
   for (int c = 0; c < 3; c++) x[(size_t)c * Vm + i] = (double)v[c];
+  if (blockIdx.y) return;                                          // the mesh's own words have one writer: item 0
+  double d = 0.0;
+  for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) d += weights[k];
   diag[i] = d;
   free_row[i] = (fixed[i] == 0 && d > 0.0) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
                                                                       const double* __restrict__ weights, const float* __restrict__ V0,
-                                                                      const double* __restrict__ x, double* __restrict__ R) {
+                                                                      const double* __restrict__ x, double* __restrict__ R, size_t slab) {
   const int i = blockIdx.x * ARAP_ROW_THREADS + threadIdx.x;
   if (i >= Vm) return;
+  x += blockIdx.y * slab; R += blockIdx.y * slab;
   double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Q[3][3];
   const double pi[3] = {(double)V0[3 * (size_t)i], (double)V0[3 * (size_t)i + 1], (double)V0[3 * (size_t)i + 2]};
   const double xi[3] = {x[i], x[(size_t)Vm + i], x[2 * (size_t)Vm + i]};
@@ -222,12 +241,14 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_local_kernel(int Vm, co
     for (int k = 0; k < 3; k++) R[((size_t)c * Vm + i) * 3 + k] = Q[c][k];
 }
 
-// E(P', R) of the state, into *out; one workgroup
+// E(P', R) of the state, into *out; one workgroup per item (out_stride: doubles between two items' stats)
 __global__ __launch_bounds__(ARAP_THREADS) void arap_energy_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
                                                                    const double* __restrict__ weights, const float* __restrict__ V0,
-                                                                   const double* __restrict__ x, const double* __restrict__ R, double* out) {
+                                                                   const double* __restrict__ x, const double* __restrict__ R, double* out,
+                                                                   size_t slab, size_t out_stride) {
   __shared__ double part[1][ARAP_WAVES];
   double acc[1] = {0.0};
+  x += blockIdx.y * slab; R += blockIdx.y * slab; out += blockIdx.y * out_stride;
   for (int i = threadIdx.x; i < Vm; i += ARAP_THREADS) {
     double Ri[3][3];
 #pragma unroll
@@ -254,21 +275,24 @@ __global__ __launch_bounds__(ARAP_THREADS) void arap_energy_kernel(int Vm, const
   if (threadIdx.x == 0) *out = acc[0];
 }
 
-// workgroup c: column c of the right-hand side, then the whole PCG of that column.  Every test that leaves a loop holding a
+// workgroup (c, b): column c of item b's right-hand side, then the whole PCG of that column.  Every test that leaves a loop holding a
 // barrier is made on sums that arap_block_sum left identical in all threads.
 __global__ __launch_bounds__(ARAP_THREADS) void arap_global_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
                                                                    const double* __restrict__ weights, const float* __restrict__ V0,
                                                                    const double* __restrict__ Rall, const double* __restrict__ diag,
                                                                    const int* __restrict__ free_row, double* xall, double* rall, double* pall,
                                                                    double* qall, int cg_iterations, double tol2, float* V_out,
-                                                                   double* stats_row) {
+                                                                   double* stats_row, size_t slab, size_t stats_stride) {
   __shared__ double partA[1][ARAP_WAVES], partB[3][ARAP_WAVES];
   const int c = blockIdx.x;
-  const double* R = Rall + (size_t)c * Vm * 3;
-  double* x = xall + (size_t)c * Vm;
-  double* r = rall + (size_t)c * Vm;
-  double* p = pall + (size_t)c * Vm;
-  double* q = qall + (size_t)c * Vm;
+  const size_t item = blockIdx.y * slab;
+  const double* R = Rall + item + (size_t)c * Vm * 3;
+  double* x = xall + item + (size_t)c * Vm;
+  double* r = rall + item + (size_t)c * Vm;
+  double* p = pall + item + (size_t)c * Vm;
+  double* q = qall + item + (size_t)c * Vm;
+  if (V_out) V_out += (size_t)blockIdx.y * 3 * Vm;
+  if (stats_row) stats_row += blockIdx.y * stats_stride;
   double s3[3] = {0.0, 0.0, 0.0};                                  // |b|^2, |r|^2, r . z
   for (int i = threadIdx.x; i < Vm; i += ARAP_THREADS) {
     double ri = 0.0, zi = 0.0;
@@ -335,23 +359,31 @@ __global__ __launch_bounds__(ARAP_THREADS) void arap_global_kernel(int Vm, const
   }
 }
 
+// the launch chain of the column step over B items: B = 1 (slab unused) is the single solve
+static void arap_column_chain(int B, size_t slab, const ArapWs& k, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                              const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                              double* stats, hipStream_t s) {
+  const dim3 rows((Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS, B);
+  const size_t stride = 8 * (size_t)outer_iterations;              // doubles between two items' stats
+  hipLaunchKernelGGL(arap_init_kernel, rows, dim3(ARAP_ROW_THREADS), 0, s, Vm, row_offsets, weights, fixed, V_init, V_out, k.x, k.diag, k.free_row,
+                     outer_iterations == 0 ? 1 : 0, slab);
+  for (int it = 0; it < outer_iterations; it++) {
+    double* row = stats ? stats + 8 * (size_t)it : nullptr;
+    hipLaunchKernelGGL(arap_local_kernel, rows, dim3(ARAP_ROW_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, slab);
+    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row, slab, stride);
+    hipLaunchKernelGGL(arap_global_kernel, dim3(3, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.diag, k.free_row, k.x, k.r,
+                       k.p, k.q, cg_iterations, cg_tolerance * cg_tolerance, it == outer_iterations - 1 ? V_out : nullptr, row, slab, stride);
+    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row + 1, slab, stride);
+  }
+}
+
 int launch_arap_solve(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
                       const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
                       size_t ws_bytes, hipStream_t s) {
   const size_t need = arap_workspace_bytes(Vm);
   if (ws_bytes < need) { set_error("gm_arap_solve: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
-  ArapWs k = ArapWs::from(ws, (size_t)Vm);
-  const dim3 rows((Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS);
-  hipLaunchKernelGGL(arap_init_kernel, rows, dim3(ARAP_ROW_THREADS), 0, s, Vm, row_offsets, weights, fixed, V_init, V_out, k.x, k.diag, k.free_row,
-                     outer_iterations == 0 ? 1 : 0);
-  for (int it = 0; it < outer_iterations; it++) {
-    double* row = stats ? stats + 8 * (size_t)it : nullptr;
-    hipLaunchKernelGGL(arap_local_kernel, rows, dim3(ARAP_ROW_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R);
-    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row);
-    hipLaunchKernelGGL(arap_global_kernel, dim3(3), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.diag, k.free_row, k.x, k.r,
-                       k.p, k.q, cg_iterations, cg_tolerance * cg_tolerance, it == outer_iterations - 1 ? V_out : nullptr, row);
-    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row + 1);
-  }
+  arap_column_chain(1, 0, ArapWs::from(ws, (size_t)Vm), Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance,
+                    V_out, stats, s);
   GM_HIP(hipGetLastError());
   return 0;
 }
@@ -399,6 +431,24 @@ struct ArapGridWs {
     k.end = p;
     return k;
   }
+  // B items: diag and free_row once, then per item a slab of *slab doubles (the six state columns, R, both slot arrays, the carry
+  // pair); the pointers are item 0's
+  static ArapGridWs batch(void* ws, size_t Vm, size_t B, size_t* slab) {
+    char* p = reinterpret_cast<char*>(ws);
+    const size_t G = (Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS;
+    ArapGridWs k;
+    k.diag = carve<double>(p, Vm);
+    k.free_row = carve<int>(p, Vm);
+    k.x = carve<double>(p, 3 * Vm); k.r = carve<double>(p, 3 * Vm); k.u = carve<double>(p, 3 * Vm);
+    k.w = carve<double>(p, 3 * Vm); k.p = carve<double>(p, 3 * Vm); k.s = carve<double>(p, 3 * Vm);
+    k.R = carve<double>(p, 9 * Vm);
+    k.bb_slots = carve<double>(p, 3 * G);
+    k.slots = carve<double>(p, 9 * G);
+    k.carry = carve<double>(p, 2 * 3 * ARAP_CARRY);
+    *slab = (size_t)(carve<double>(p, 0) - k.x);
+    k.end = reinterpret_cast<char*>(k.x + B * *slab);
+    return k;
+  }
 };
 
 size_t arap_grid_workspace_bytes(int Vm) {
@@ -429,9 +479,12 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_rhs_kernel(int Vm,
                                                                          const double* __restrict__ weights, const float* __restrict__ V0,
                                                                          const double* __restrict__ R, const double* __restrict__ diag,
                                                                          const int* __restrict__ free_row, const double* __restrict__ x,
-                                                                         double* __restrict__ r, double* __restrict__ u, double* __restrict__ bb_slots) {
+                                                                         double* __restrict__ r, double* __restrict__ u, double* __restrict__ bb_slots,
+                                                                         size_t slab) {
   __shared__ double part[3][ARAP_ROW_WAVES];
   const int i = blockIdx.x * ARAP_ROW_THREADS + threadIdx.x;
+  const size_t item = blockIdx.y * slab;
+  R += item; x += item; r += item; u += item; bb_slots += item;
   double bb[3] = {0.0, 0.0, 0.0};
   if (i < Vm) {
     double ri[3] = {0.0, 0.0, 0.0}, ui[3] = {0.0, 0.0, 0.0};
@@ -478,13 +531,17 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_rhs_kernel(int Vm,
     for (int c = 0; c < 3; c++) bb_slots[(size_t)c * gridDim.x + blockIdx.x] = bb[c];
 }
 
-// w = A u of the free rows; slots [0..3) r . u, [3..6) w . u, [6..9) r . r.  carry: null in the first launch of an outer iteration
+// w = A u of the free rows; slots [0..3) r . u, [3..6) w . u, [6..9) r . r.  carry: null in the first launch of an outer iteration.
+// The early return is item b's own: all three of ITS columns have stopped, whatever the other items do.
 __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_product_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
                                                                              const double* __restrict__ weights, const int* __restrict__ free_row,
                                                                              const double* __restrict__ r, const double* __restrict__ u,
                                                                              double* __restrict__ w, const double* __restrict__ carry,
-                                                                             double* __restrict__ slots) {
+                                                                             double* __restrict__ slots, size_t slab) {
   __shared__ double part[9][ARAP_ROW_WAVES];
+  const size_t item = blockIdx.y * slab;
+  r += item; u += item; w += item; slots += item;
+  if (carry) carry += item;
   // the row's own loads are issued ahead of the carry test, so that the test costs no memory round trip of its own
   // (a thread past the last row reads the last row and adds nothing)
   const int i = min(blockIdx.x * ARAP_ROW_THREADS + threadIdx.x, Vm - 1);
@@ -493,7 +550,7 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_product_kernel(int
   double ui[3], ri[3];
 #pragma unroll
   for (int c = 0; c < 3; c++) { ui[c] = u[(size_t)c * Vm + i]; ri[c] = r[(size_t)c * Vm + i]; }
-  if (carry && carry[ARAP_CARRY - 1] != 0.0 && carry[2 * ARAP_CARRY - 1] != 0.0 && carry[3 * ARAP_CARRY - 1] != 0.0) return;   // all stopped: the same in every thread of the grid
+  if (carry && carry[ARAP_CARRY - 1] != 0.0 && carry[2 * ARAP_CARRY - 1] != 0.0 && carry[3 * ARAP_CARRY - 1] != 0.0) return;   // all stopped: the same in every thread of the item
   double s9[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (row && fr) {
     double q[3] = {0.0, 0.0, 0.0};
@@ -538,7 +595,11 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_update_kernel(int 
                                                                             const double* __restrict__ bb_slots, const double* __restrict__ slots,
                                                                             const double* __restrict__ carry_in, double* __restrict__ carry_out,
                                                                             int first, int last, double tol2, float* __restrict__ V_out,
-                                                                            double* __restrict__ stats_row) {
+                                                                            double* __restrict__ stats_row, size_t slab, size_t stats_stride) {
+  const size_t item = blockIdx.y * slab;
+  x += item; r += item; u += item; w += item; p += item; s += item; bb_slots += item; slots += item; carry_in += item; carry_out += item;
+  if (V_out) V_out += (size_t)blockIdx.y * 3 * Vm;
+  if (stats_row) stats_row += blockIdx.y * stats_stride;
   // Everything this thread reads is asked for before anything is decided: the row, the slots and the carry arrive in one memory round
   // trip instead of three in a row.  (p and s of the first step are read and not used.)
   // (A thread past the last row reads the last row and writes nothing.)
@@ -572,7 +633,7 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_update_kernel(int 
       for (int k = 0; k < ARAP_CARRY; k++) st[c][k] = carry_in[c * ARAP_CARRY + k];
   }
 #pragma unroll
-  for (int c = 0; c < 3; c++) {                                    // uniform over the grid: everyone holds the same sums and the same carry
+  for (int c = 0; c < 3; c++) {                                    // uniform over the item: all its workgroups hold the same sums and the same carry
     if (st[c][5] != 0.0) continue;                                 // stopped: frozen, the slots of this column are not looked at
     const double gamma = t9[c], delta = t9[3 + c], rr = t9[6 + c];
     st[c][3] = rr;
@@ -613,22 +674,21 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_update_kernel(int 
   }
 }
 
-int launch_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
-                           const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
-                           size_t ws_bytes, hipStream_t s) {
-  const size_t need = arap_grid_workspace_bytes(Vm);
-  if (ws_bytes < need) { set_error("gm_arap_solve_grid: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
-  ArapGridWs k = ArapGridWs::from(ws, (size_t)Vm);
-  const dim3 rows((Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS), threads(ARAP_ROW_THREADS);
+// the launch chain of the grid step over B items: B = 1 (slab unused) is the single solve
+static void arap_grid_chain(int B, size_t slab, const ArapGridWs& k, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                            const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                            double* stats, hipStream_t s) {
+  const dim3 rows((Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS, B), threads(ARAP_ROW_THREADS);
   const double tol2 = cg_tolerance * cg_tolerance;
+  const size_t stride = 8 * (size_t)outer_iterations;              // doubles between two items' stats
   hipLaunchKernelGGL(arap_init_kernel, rows, threads, 0, s, Vm, row_offsets, weights, fixed, V_init, V_out, k.x, k.diag, k.free_row,
-                     outer_iterations == 0 ? 1 : 0);
+                     outer_iterations == 0 ? 1 : 0, slab);
   for (int it = 0; it < outer_iterations; it++) {
     double* row = stats ? stats + 8 * (size_t)it : nullptr;
     float* out = it == outer_iterations - 1 ? V_out : nullptr;
-    hipLaunchKernelGGL(arap_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R);
-    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row);
-    hipLaunchKernelGGL(arap_grid_rhs_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.diag, k.free_row, k.x, k.r, k.u, k.bb_slots);
+    hipLaunchKernelGGL(arap_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, slab);
+    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row, slab, stride);
+    hipLaunchKernelGGL(arap_grid_rhs_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.diag, k.free_row, k.x, k.r, k.u, k.bb_slots, slab);
     // steps 0 .. cg_iterations - 1 update; the pair behind them only forms the final |r|^2, which nothing but stats reads
     // (Unlike the column step, whose loop leaves on the device, a cap costs 2 * cg_iterations host launches per outer iteration whether
     // or not the solve stops early: a cap far above the steps needed is paid for.  64-bit, so that cap + 1 cannot overflow.)
@@ -638,11 +698,44 @@ int launch_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, cons
       double* carry_out = k.carry + ((step + 1) & 1) * 3 * ARAP_CARRY;
       const int last = step == cg_iterations;
       hipLaunchKernelGGL(arap_grid_product_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, k.free_row, k.r, k.u, k.w, step ? carry_in : nullptr,
-                         k.slots);
+                         k.slots, slab);
       hipLaunchKernelGGL(arap_grid_update_kernel, rows, threads, 0, s, Vm, k.diag, k.free_row, k.x, k.r, k.u, k.w, k.p, k.s, k.bb_slots, k.slots, carry_in,
-                         carry_out, step == 0 ? 1 : 0, last, tol2, step == pairs - 1 ? out : nullptr, last ? row : nullptr);
+                         carry_out, step == 0 ? 1 : 0, last, tol2, step == pairs - 1 ? out : nullptr, last ? row : nullptr, slab, stride);
     }
-    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row + 1);
+    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row + 1, slab, stride);
+  }
+}
+
+int launch_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
+                           const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
+                           size_t ws_bytes, hipStream_t s) {
+  const size_t need = arap_grid_workspace_bytes(Vm);
+  if (ws_bytes < need) { set_error("gm_arap_solve_grid: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
+  arap_grid_chain(1, 0, ArapGridWs::from(ws, (size_t)Vm), Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance,
+                  V_out, stats, s);
+  GM_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- B solves in one chain (gm_arap_solve_batch): the chains above with the batch as the second grid dimension ----
+size_t arap_batch_workspace_bytes(int Vm, int B, int global_step) {
+  size_t slab;
+  const size_t v = (size_t)(Vm > 0 ? Vm : 1), b = (size_t)(B > 0 ? B : 1);
+  return (size_t)(global_step ? ArapGridWs::batch(nullptr, v, b, &slab).end : ArapWs::batch(nullptr, v, b, &slab).end) + 256;
+}
+
+int launch_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                            const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                            double* stats, void* ws, size_t ws_bytes, hipStream_t s) {
+  const size_t need = arap_batch_workspace_bytes(Vm, B, global_step);
+  if (ws_bytes < need) { set_error("gm_arap_solve_batch: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
+  size_t slab;
+  if (global_step) {
+    const ArapGridWs k = ArapGridWs::batch(ws, (size_t)Vm, (size_t)B, &slab);
+    arap_grid_chain(B, slab, k, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats, s);
+  } else {
+    const ArapWs k = ArapWs::batch(ws, (size_t)Vm, (size_t)B, &slab);
+    arap_column_chain(B, slab, k, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats, s);
   }
   GM_HIP(hipGetLastError());
   return 0;

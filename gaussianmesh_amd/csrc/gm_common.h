@@ -494,6 +494,10 @@ int launch_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, cons
                            const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
                            size_t ws_bytes, hipStream_t s);
 size_t arap_grid_workspace_bytes(int Vm);
+int launch_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                            const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                            double* stats, void* ws, size_t ws_bytes, hipStream_t s);
+size_t arap_batch_workspace_bytes(int Vm, int B, int global_step);
 int launch_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const float* vertices, int F, const int* faces, float t_min,
                     float t_max, float* out_t, int* out_face, float* out_uv, void* ws, size_t ws_bytes, hipStream_t s);
 size_t ray_mesh_workspace_bytes(int R, int F);

@@ -440,6 +440,20 @@ class SingleObjectDeform:
             raise ValueError("drag: want_stats is ArapSolver.solve's; call self.arap.solve for the statistics")
         return self.deform_vertices(self.arap.solve(handle_positions, init=self.mesh_vertex_current, **solve_options))
 
+    def drag_sequence(self, handle_positions, batch=4, **solve_options):
+        """A whole drag at once: the meshes [T,Vm,3] with the handles of set_handles() at handle_positions[t] ([T,H,3]), `batch` frames
+        per launch chain: exactly self.arap.solve_sequence(handle_positions, init=mesh_vertex_current, batch=batch, **solve_options),
+        then deform_vertices of the last frame, which leaves the object as drag(handle_positions[-1]) would.  Inside a run the frames do
+        not warm-start from their neighbour (ArapSolver.solve_batch: THE TRADE).  Returns the meshes; no host wait."""
+        if self.arap is None:
+            raise ValueError("drag_sequence: call set_handles(vertex_ids) first")
+        if solve_options.get("want_stats"):
+            raise ValueError("drag_sequence: want_stats is ArapSolver.solve_sequence's; call self.arap.solve_sequence for the statistics")
+        meshes = self.arap.solve_sequence(handle_positions, init=self.mesh_vertex_current, batch=batch, **solve_options)
+        if len(meshes):
+            self.deform_vertices(meshes[-1])
+        return meshes
+
     def _screen_mesh(self, who):
         """(current vertices, faces, check_faces) for the screen-space methods: the face indices are checked on the host the first
         time this face tensor is seen (mesh_pick), afterwards nothing waits for the device."""

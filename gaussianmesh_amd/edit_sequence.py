@@ -3,7 +3,7 @@
     python -m gaussianmesh_amd.edit_sequence (--object_gaussian fg.ply | --object_plain_gaussian cloud.ply) --object_origin_mesh mesh.obj \
         (--mesh_sequence DIR | --handle_sequence FILE.npz | --pick_sequence FILE.json) --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N]
         [--frames_per_launch 4] [--save_maps] [--save_meshes] [--save_baked PATH] [--background_gaussian BG.ply [--is_exist_bg]]
-        [--arap_global_step {column,grid}]
+        [--arap_global_step {column,grid}] [--arap_batch K]
 
 --object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
 faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of the two.
@@ -26,6 +26,10 @@ the run with a message naming the picks.  With neither key nothing changes: sing
 Exactly one of --mesh_sequence / --handle_sequence / --pick_sequence.  --save_meshes also writes every frame's mesh as {i:05d}.obj.
 --arap_global_step: the solver's global step for --handle_sequence / --pick_sequence, ArapSolver.solve's global_step: column (the default:
 one workgroup per coordinate) or grid (rows over the whole chip; the same meshes to within the last bits).
+--arap_batch K: for --handle_sequence / --pick_sequence, K frames' solves per launch chain (ArapSolver.solve_sequence, K in 1 .. 64): the
+frames go in runs of K, and every frame of a run starts from the last frame of the previous run instead of from its own predecessor, so
+the meshes differ a little from K = 1's.  The default 1 is the chain described above, bit for bit.  What K buys and costs: INTEGRATION.md
+section Q.
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
@@ -40,6 +44,9 @@ trainer, or --object_plain_gaussian with that frame's mesh.  One file, not one p
 import os
 import re
 from argparse import ArgumentParser
+
+
+ARAP_BATCH_MAX = 64           # GM_ARAP_BATCH_MAX (include/gmesh_hip.h, _lib.GM_ARAP_BATCH_MAX): here so that --arap_batch is refused before any import
 
 
 def mesh_sequence(folder):
@@ -114,6 +121,7 @@ def main(argv=None):
     source.add_argument("--pick_sequence", type=str, default=None)
     parser.add_argument("--save_meshes", action="store_true", default=False)
     parser.add_argument("--arap_global_step", choices=("column", "grid"), default="column")
+    parser.add_argument("--arap_batch", type=int, default=1)
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
     parser.add_argument("--save_maps", action="store_true", default=False)
@@ -125,6 +133,8 @@ def main(argv=None):
         parser.error("--is_exist_bg needs --background_gaussian (the background cloud's PLY)")
     if args.background_gaussian is not None and args.save_maps:
         parser.error("--save_maps: a scene with a background renders no depth / alpha maps; drop --save_maps or the background")
+    if not 1 <= args.arap_batch <= ARAP_BATCH_MAX:
+        raise SystemExit("edit_sequence: --arap_batch %d: a launch chain carries 1 .. %d frames' solves" % (args.arap_batch, ARAP_BATCH_MAX))
     if args.pick_sequence is not None:
         pick = read_pick_sequence(args.pick_sequence)
         (pick_camera, pick_handles, pick_anchors, pick_offsets), pick_radii = pick[:4], (pick[4] if len(pick) > 4 else None)
@@ -178,10 +188,8 @@ def main(argv=None):
     if handles is not None:
         if solver is None:
             solver = tool.gaussians_list[-1].set_handles(handles)
-        meshes, current = [], None
-        for t in range(len(positions)):                           # enqueued back to back: no host wait between the solves
-            current = solver.solve(positions[t], init=current, global_step=args.arap_global_step)
-            meshes.append(current)
+        # enqueued back to back: no host wait between the solves; --arap_batch frames per launch chain
+        meshes = list(solver.solve_sequence(positions, batch=args.arap_batch, global_step=args.arap_global_step))
     frames = [(cams[args.camera_id] if args.camera_id is not None else cams[i % len(cams)], {args.object_name: m})
               for i, m in enumerate(meshes)]
     os.makedirs(args.render_path, exist_ok=True)

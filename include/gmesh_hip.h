@@ -281,6 +281,22 @@ int gm_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const do
                        const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* B solves of one mesh and one handle set in ONE launch chain: item b of V_out (and of stats) is bit for bit what gm_arap_solve
+ * (global_step 0) or gm_arap_solve_grid (global_step 1) returns for V_init[b] and the same other arguments.  The CSR, weights, V0 and
+ * fixed are shared by all items; V_init float [B][Vm][3], whose held rows already carry item b's targets; V_out float [B][Vm][3], which
+ * may be V_init itself; stats NULL or double [B][outer_iterations][8], the single solve's rows.  The batch is the second grid dimension
+ * of every kernel, so the chain has exactly the launches of one single solve; every item stops on its own sums: one that converges at
+ * once neither holds back nor disturbs one that runs to the cap.  outer_iterations == 0 copies V_init to V_out.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: B < 1 or B > GM_ARAP_BATCH_MAX, a global_step other than 0 or 1, everything
+ * gm_arap_solve refuses, any overlap among V0, V_init, V_out, stats and the workspace over their full [B] extents other than
+ * V_out == V_init; with GM_ERR_BUFFER a workspace below gm_arap_batch_workspace_bytes(Vm, B, global_step) (0 for arguments that would
+ * be refused).  Stream-ordered, no device allocation, no host synchronisation, no atomics. */
+#define GM_ARAP_BATCH_MAX 64
+size_t gm_arap_batch_workspace_bytes(int Vm, int B, int global_step /* 0 column / 1 grid */);
+int gm_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                        const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance,
+                        float* V_out, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* First hit of every ray on a mesh: what takes an editor from a pixel to a vertex of the current, deformed proxy mesh
  * (mesh_pick.ray_mesh_hits / pick / visible_vertices).  The reference has no such stage: the result is defined by arithmetic.
  * origins, dirs float [R,3], vertices float [Vm,3], faces int32 [F,3] vertex ids.  out_t float [R], out_face int32 [R], out_uv float

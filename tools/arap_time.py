@@ -11,7 +11,12 @@ the defaults from the previous frame's solution, timed as one window; beside it 
 And a solve with the handles at rest, which converges before its first step: on the grid path the price of a solve's launches when
 every product / update pair returns after reading the carried state.
 With --sizes a list of NUxNV tori instead of the two above (the crossover between the two global steps).
-    python tools/arap_time.py [--global_step both] [--sizes 16x16,40x25,...]"""
+With --batch B1,B2,... instead of all the above: a 32-frame drag (the moved ring at 1/32, 2/32, ... of its path) through
+ArapSolver.solve_sequence at each batch size, on torus_mesh(32, 32), (100, 75) and (300, 200) unless --sizes says otherwise and for both
+global steps unless --global_step names one: milliseconds per frame (the whole drag as one window of device events, median of 20 after 5
+warm-ups, over 32) and, from a separate untimed pass with want_stats, the final energy of every frame.  The baseline beside them is
+the same 32 frames through the chain of solve() calls, each warm-started from the frame before: the code path without batches.
+    python tools/arap_time.py [--global_step both] [--sizes 16x16,40x25,...] [--batch 1,2,4,8,16]"""
 import argparse, math, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import numpy as np
@@ -44,11 +49,52 @@ def ring_handles(V0, fraction=1.0):
     return np.concatenate([still, moved]), np.concatenate([V0[still].astype(np.float64), target], 0).astype(np.float32)
 
 
+def batch_report(sizes, paths, batches, frames=32):
+    for nu, nv in sizes:
+        verts, faces = scenes.torus_mesh(nu, nv)
+        V0 = verts.astype(np.float32)
+        handles = ring_handles(V0)[0]
+        solver = ArapSolver(V0, faces, handles, device=dev)
+        pos = torch.as_tensor(np.stack([ring_handles(V0, (t + 1) / float(frames))[1] for t in range(frames)], 0), device=dev)
+        out = torch.empty((len(V0), 3), dtype=torch.float32, device=dev)
+        print("torus_mesh(%d, %d): %d vertices, %d handles, %d workgroups of 256 rows, %d-frame drag" % (
+            nu, nv, len(V0), len(handles), (len(V0) + 255) // 256, frames), flush=True)
+        for path in paths:
+            g = dict(global_step=path)
+
+            def chain(stats=False):
+                cur, energy = None, []
+                for t in range(frames):
+                    cur = solver.solve(pos[t], init=cur, out=out, want_stats=stats, **g)
+                    if stats:
+                        energy.append(cur[1][-1, 1]); cur = cur[0]
+                return energy
+            base = median_ms(chain)
+            e_base = torch.stack(chain(True)).cpu().numpy()
+            print(" global_step=%s" % path, flush=True)
+            print("  baseline: chain of solve(), warm-started   %8.3f ms / frame (drag median %.3f ms, min %.3f, max %.3f)" % ((base[0] / frames,) + base), flush=True)
+            print("    final E per frame: %s" % " ".join("%.6g" % e for e in e_base), flush=True)
+            for B in batches:
+                m = median_ms(lambda: solver.solve_sequence(pos, batch=B, **g))
+                e = solver.solve_sequence(pos, batch=B, want_stats=True, **g)[1][:, -1, 1].cpu().numpy()
+                rel = e / e_base
+                print("  solve_sequence(batch=%-2d)                   %8.3f ms / frame (drag median %.3f ms, min %.3f, max %.3f)  baseline / this %.2fx" % (
+                    (B, m[0] / frames) + m + (base[0] / m[0],)), flush=True)
+                print("    final E per frame: %s" % " ".join("%.6g" % v for v in e), flush=True)
+                print("    E / baseline's E per frame: mean %.4f, max %.4f (frame %d); sum over the drag %.4f" % (
+                    rel.mean(), rel.max(), int(rel.argmax()), e.sum() / e_base.sum()), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--global_step", choices=("column", "grid", "both"), default="column")
-    ap.add_argument("--sizes", type=str, default="100x75,300x200")
+    ap.add_argument("--global_step", choices=("column", "grid", "both"), default=None)
+    ap.add_argument("--sizes", type=str, default=None)
+    ap.add_argument("--batch", type=str, default=None)
     args = ap.parse_args()
+    if args.batch is not None:
+        sizes = [tuple(int(v) for v in item.split("x")) for item in (args.sizes or "32x32,100x75,300x200").split(",")]
+        return batch_report(sizes, ("column", "grid") if args.global_step in (None, "both") else (args.global_step,), [int(b) for b in args.batch.split(",")])
+    args.global_step, args.sizes = args.global_step or "column", args.sizes or "100x75,300x200"
     paths = ("column", "grid") if args.global_step == "both" else (args.global_step,)
     for nu, nv in (tuple(int(v) for v in item.split("x")) for item in args.sizes.split(",")):
         verts, faces = scenes.torus_mesh(nu, nv)
