@@ -80,7 +80,6 @@ struct U8Target {
 #define LS_U8_BEGIN const U8Target<HAS_MASK> tgt{rgb, mask, mask_stride, HAS_MASK ? bg[blockIdx.z] : 0.f};
 #define LS_U8(p) tgt.load(p, (p) - plane, blockIdx.z)
 
-template <bool WRITE_MAPS>
 __global__ __launch_bounds__(LS_THREADS) void ssim_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
                                                               int H, int W, LossWindow win, float* __restrict__ d_mu1,
                                                               float* __restrict__ d_e11, float* __restrict__ d_e12,
@@ -92,7 +91,7 @@ __global__ __launch_bounds__(LS_THREADS) void ssim_fwd_kernel(const float* __res
 #undef LS_TARGET
 }
 
-template <bool WRITE_MAPS, bool HAS_MASK>
+template <bool HAS_MASK>
 __global__ __launch_bounds__(LS_THREADS) void ssim_fwd_u8_kernel(const float* __restrict__ img1, const unsigned char* __restrict__ rgb,
                                                                  const unsigned char* __restrict__ mask, size_t mask_stride,
                                                                  const float* __restrict__ bg, int H, int W, LossWindow win,
@@ -170,10 +169,7 @@ int launch_ssim_fwd(const float* img1, const float* img2, int planes, int H, int
   StageScope sc(ST_LOSS, s);
   const dim3 grid((W + LS_TILE - 1) / LS_TILE, (H + LS_TILE - 1) / LS_TILE, planes);
   const LossWindow win = make_window();
-  if (d_mu1)
-    hipLaunchKernelGGL(ssim_fwd_kernel<true>, grid, dim3(LS_THREADS), 0, s, img1, img2, H, W, win, d_mu1, d_e11, d_e12, partial);
-  else
-    hipLaunchKernelGGL(ssim_fwd_kernel<false>, grid, dim3(LS_THREADS), 0, s, img1, img2, H, W, win, d_mu1, d_e11, d_e12, partial);
+  hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(LS_THREADS), 0, s, img1, img2, H, W, win, d_mu1, d_e11, d_e12, partial);
   GM_HIP(hipGetLastError());
   return 0;
 }
@@ -193,10 +189,9 @@ int launch_ssim_fwd_u8(const float* img1, const unsigned char* rgb, const unsign
   StageScope sc(ST_LOSS, s);
   const dim3 grid((W + LS_TILE - 1) / LS_TILE, (H + LS_TILE - 1) / LS_TILE, 3);
   const LossWindow win = make_window();
-#define LS_FWD_U8(MAPS, MASK) \
-  hipLaunchKernelGGL((ssim_fwd_u8_kernel<MAPS, MASK>), grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, bg, H, W, win, d_mu1, d_e11, d_e12, partial)
-  if (d_mu1) { if (mask) LS_FWD_U8(true, true); else LS_FWD_U8(true, false); }
-  else { if (mask) LS_FWD_U8(false, true); else LS_FWD_U8(false, false); }
+#define LS_FWD_U8(MASK) \
+  hipLaunchKernelGGL(ssim_fwd_u8_kernel<MASK>, grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, bg, H, W, win, d_mu1, d_e11, d_e12, partial)
+  if (mask) LS_FWD_U8(true); else LS_FWD_U8(false);
 #undef LS_FWD_U8
   GM_HIP(hipGetLastError());
   return 0;

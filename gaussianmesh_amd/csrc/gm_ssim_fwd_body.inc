@@ -77,6 +77,10 @@
   }
   __syncthreads();
   const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+  // With or without the maps the same instructions make S: the maps are a uniform branch of ONE kernel.  As two template instantiations
+  // the compiler fused different products into the sums of S in each, and where E[xx] - mu^2 cancels (flat regions) the partial sums
+  // of a call without the maps differed by several ulps from those of a call with them.
+  const bool write_maps = d_mu1 != nullptr;
   const int c = tid & 31;
   float s_sum = 0.f, l1_sum = 0.f;
   // vertical taps: a thread owns 4 adjacent rows of one column (14 values per quantity feed 4 x 11 taps)
@@ -115,7 +119,7 @@
       const float S = (A1 * A2) * (inv_b1 * inv_b2);
       s_sum += S;
       l1_sum += fabsf(own[j].x - own[j].y);
-      if (WRITE_MAPS) {
+      if (write_maps) {
         const size_t p = plane + (size_t)gy * W + gx;
         // S as a function of (mu1, E[xx], E[xy]) with sigma1^2 = E[xx] - mu1^2, sigma12 = E[xy] - mu1 mu2
         const float dS_ds1 = -S * inv_b2;                       // = dS/dE[xx]

@@ -632,7 +632,7 @@ int gm_sh_rotate(int N, int deg, int M, const float* shs, const float* rot, floa
  * gm_ssim_fwd writes per 32x32-pixel workgroup {sum of the ssim map, sum of |img1-img2|} into partial
  * (float [gm_ssim_partials(planes,H,W)][2], plane-major then tile rows): ssim(...) = sum/(planes H W), per-image means
  * for size_average=False by summing a plane range.  dS_dmu1 / dS_dE11 / dS_dE12 (float [planes,H,W] each; all three or
- * all NULL) receive the per-pixel partial derivatives gm_ssim_bwd needs.
+ * all NULL) receive the per-pixel partial derivatives gm_ssim_bwd needs; partial holds the same bits with and without them.
  * gm_ssim_bwd: dL_dimg1 = g_ssim[plane] * d(sum of ssim map)/d img1 + g_l1[0] * sign(img1 - img2); g_ssim (device float
  * [planes]) and g_l1 (device float [1], may be NULL) carry the upstream gradient times 1/count, so no host
  * synchronisation is needed between forward and backward.
