@@ -855,6 +855,56 @@ int gm_surface_nets(int nx, int ny, int nz, const float* origin, float voxel, co
                              workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
+// byte ranges of a call: every one of the last n_out (the outputs) against every other range; NULL or empty ranges never overlap
+struct ByteRange { const void* p; size_t n; const char* what; };
+static int check_outputs_apart(const char* fn, const ByteRange* rg, int n, int n_out) {
+  for (int a = 0; a < n; a++)
+    for (int b = (a < n - n_out ? n - n_out : a + 1); b < n; b++) {
+      const uintptr_t pa = reinterpret_cast<uintptr_t>(rg[a].p), pb = reinterpret_cast<uintptr_t>(rg[b].p);      // (integers: no pointer is formed past a range)
+      if (!pa || !pb || !rg[a].n || !rg[b].n) continue;
+      if (pa < pb + rg[b].n && pb < pa + rg[a].n) { set_error("%s: %s overlaps %s", fn, rg[a].what, rg[b].what); return GM_ERR_INVALID_ARG; }
+    }
+  return 0;
+}
+
+int gm_mesh_quadrics(int Vm, const float* vertices, int F, const int* faces, const int* vf_offsets, const int* vf_faces, float* out_quadrics,
+                     void* stream) {
+  if (Vm < 0 || F < 0) { set_error("gm_mesh_quadrics: negative size Vm=%d F=%d", Vm, F); return GM_ERR_INVALID_ARG; }
+  if (F > 0x7FFFFFFF / 3) { set_error("gm_mesh_quadrics: F=%d: 3 F must fit an int", F); return GM_ERR_INVALID_ARG; }
+  if (Vm == 0) return GM_OK;
+  if (!vertices || !vf_offsets || !out_quadrics || (F > 0 && (!faces || !vf_faces))) { set_error("gm_mesh_quadrics: null pointer"); return GM_ERR_INVALID_ARG; }
+  const ByteRange rg[5] = {{vertices, 12 * (size_t)Vm, "vertices"}, {faces, 12 * (size_t)F, "faces"}, {vf_offsets, 4 * ((size_t)Vm + 1), "vf_offsets"},
+                           {vf_faces, 12 * (size_t)F, "vf_faces"}, {out_quadrics, 40 * (size_t)Vm, "out_quadrics"}};
+  if (int rc = check_outputs_apart("gm_mesh_quadrics", rg, 5, 1)) return rc;
+  return launch_mesh_quadrics(Vm, vertices, F, faces, vf_offsets, vf_faces, out_quadrics, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t gm_mesh_collapse_round_workspace_bytes(int Vm) { return mesh_collapse_round_workspace_bytes(Vm); }
+int gm_mesh_collapse_round(int Vm, const float* vertices, const float* quadrics, int F, const int* faces, const int* vf_offsets, const int* vf_faces,
+                           int E, const int* edges, const int* edge_faces, float min_cos, float max_error, unsigned char* out_selected, int* out_from,
+                           int* out_to, unsigned long long* out_key, int* out_count, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "gm_mesh_collapse_round";
+  if (Vm < 0 || F < 0 || E < 0) { set_error("%s: negative size Vm=%d F=%d E=%d", fn, Vm, F, E); return GM_ERR_INVALID_ARG; }
+  if (F > 0x7FFFFFFF / 3) { set_error("%s: F=%d: 3 F must fit an int", fn, F); return GM_ERR_INVALID_ARG; }
+  if (!(min_cos >= 0.f) || min_cos > 3.4028234e38f) { set_error("%s: min_cos must be >= 0, finite and not NaN", fn); return GM_ERR_INVALID_ARG; }
+  if (!(max_error >= 0.f)) { set_error("%s: max_error must be >= 0 and not NaN (+inf: no bound)", fn); return GM_ERR_INVALID_ARG; }
+  if (E == 0) return GM_OK;
+  if (Vm == 0 || F == 0) { set_error("%s: %d edges of an empty mesh (Vm == %d, F == %d)", fn, E, Vm, F); return GM_ERR_INVALID_ARG; }
+  if (!vertices || !quadrics || !faces || !vf_offsets || !vf_faces || !edges || !edge_faces || !out_selected || !out_from || !out_to || !out_key ||
+      !out_count || !workspace) {
+    set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG;
+  }
+  if (reinterpret_cast<uintptr_t>(out_key) & 7) { set_error("%s: out_key must be 8-byte aligned", fn); return GM_ERR_INVALID_ARG; }
+  const ByteRange rg[13] = {{vertices, 12 * (size_t)Vm, "vertices"}, {quadrics, 40 * (size_t)Vm, "quadrics"}, {faces, 12 * (size_t)F, "faces"},
+                            {vf_offsets, 4 * ((size_t)Vm + 1), "vf_offsets"}, {vf_faces, 12 * (size_t)F, "vf_faces"}, {edges, 8 * (size_t)E, "edges"},
+                            {edge_faces, 4 * (size_t)E, "edge_faces"}, {out_selected, (size_t)E, "out_selected"}, {out_from, 4 * (size_t)E, "out_from"},
+                            {out_to, 4 * (size_t)E, "out_to"}, {out_key, 8 * (size_t)E, "out_key"}, {out_count, 4, "out_count"},
+                            {workspace, workspace_bytes, "workspace"}};
+  if (int rc = check_outputs_apart(fn, rg, 13, 6)) return rc;
+  return launch_mesh_collapse_round(Vm, vertices, quadrics, F, faces, vf_offsets, vf_faces, E, edges, edge_faces, min_cos, max_error, out_selected,
+                                    out_from, out_to, out_key, out_count, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
 int gm_deform(int N, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
               const float* cov, const float* pos, float* pos_out, float* cov_out, float* rot_out, float* cov6_out,
               void* stream) {

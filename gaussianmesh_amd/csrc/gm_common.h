@@ -514,6 +514,12 @@ int launch_surface_nets(int nx, int ny, int nz, const float* origin, float voxel
                         int max_vertices, float* out_vertices, int max_faces, int* out_faces, int* out_counts, void* ws, size_t ws_bytes,
                         hipStream_t s);
 size_t surface_nets_workspace_bytes(int nx, int ny, int nz);
+// gm_simplify.hip: error quadrics, and one round of independent edge collapses (subset placement)
+int launch_mesh_quadrics(int Vm, const float* V, int F, const int* faces, const int* off, const int* adj, float* Q, hipStream_t s);
+int launch_mesh_collapse_round(int Vm, const float* V, const float* Q, int F, const int* faces, const int* off, const int* adj, int E,
+                               const int* edges, const int* uses, float min_cos, float max_error, unsigned char* selected, int* from, int* to,
+                               unsigned long long* key, int* count, void* ws, size_t ws_bytes, hipStream_t s);
+size_t mesh_collapse_round_workspace_bytes(int Vm);
 
 // number of set bits of a wave-wide 64-bit mask (a ballot) at positions BELOW the calling lane: v_mbcnt_lo + v_mbcnt_hi, two
 // vector instructions and no per-lane mask registers (popcount(mask & lanes_lt) costs four and two registers)

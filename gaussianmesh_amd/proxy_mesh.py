@@ -12,6 +12,7 @@ import json
 import math
 import sys
 import time
+import warnings
 from types import SimpleNamespace
 
 import numpy as np
@@ -103,6 +104,7 @@ class TsdfVolume:
         self.weight = torch.zeros_like(self.tsdf)
         self._origin_c = (C.c_float * 3)(*self.origin.tolist())
         self.views = 0
+        self.simplified = None
 
     def integrate(self, cameras, depth, alpha, alpha_min=0.5, carve=True):
         """Fuse views: cameras (renderer.Camera-like objects or scenes.camera_from_RT dicts), depth and alpha the rasterizer's own maps
@@ -164,13 +166,20 @@ class TsdfVolume:
         nv, nf = (int(c) for c in counts.cpu())                       # the one host wait
         return V, F, nv, nf
 
-    def extract(self, min_weight=1, keep="largest"):
+    def extract(self, min_weight=1, keep="largest", target_faces=None, simplify_max_rounds=1024):
         """(vertices float32 [V,3], faces int32 [F,3]) on the device: the zero surface among the samples that at least min_weight views
         observed, by naive surface nets (gm_surface_nets: ids and rows in scan order).  It starts from a capacity guess (a few times
         the largest face of the grid), reads the counts - the one host wait - and runs once more if the guess was short.
         keep="largest": only the connected component with the most faces (ties: the smallest vertex id), unreferenced vertices
         dropped and ids re-numbered in order (on the host: the mesh is small) - a floater would make the mesh unusable, ArapSolver
-        refuses a component without a handle; keep="all": everything.  self.stats = vertices / faces / components before the choice."""
+        refuses a component without a handle; keep="all": everything.  self.stats = vertices / faces / components before the choice.
+        target_faces: simplify what was kept to at most that many faces (mesh_simplify.simplify: output vertices are rows of the dense
+        mesh) in at most simplify_max_rounds rounds; self.stats then also holds faces_before_simplify, simplify_rounds,
+        simplify_stalled, simplify_reached and seconds_simplify (`faces` stays the dense count; the returned F has the final one), and
+        self.simplified the whole result (kept, vertex_map; None after an extract without a target).  A run that ends above the target -
+        stalled on locked borders, or out of rounds, which a very finely sampled smooth surface can be - is
+        returned as it is, with simplify_reached False and a RuntimeWarning.  None: nothing changes."""
+        self.simplified = None
         if keep not in ("largest", "all"):
             raise ValueError("TsdfVolume.extract: keep must be 'largest' or 'all'; got %r" % (keep,))
         side = max(self.nx * self.ny, self.ny * self.nz, self.nx * self.nz)
@@ -185,6 +194,18 @@ class TsdfVolume:
             v, f, comps = largest_component(V.cpu().numpy(), F.cpu().numpy())
             self.stats.update(components=comps, components_dropped=max(comps - 1, 0))
             V, F = torch.as_tensor(v, device=self.device), torch.as_tensor(f, device=self.device)
+        if target_faces is not None:
+            from .mesh_simplify import simplify
+            t0 = time.perf_counter()
+            self.simplified = simplify(V.contiguous(), F.contiguous(), target_faces=target_faces, max_rounds=simplify_max_rounds)
+            torch.cuda.synchronize(self.device)
+            st = self.simplified.stats
+            self.stats.update(faces_before_simplify=int(F.shape[0]), simplify_rounds=st["rounds"], simplify_stalled=st["stalled"],
+                              simplify_reached=st["reached"], seconds_simplify=time.perf_counter() - t0)
+            if not st["reached"]:
+                warnings.warn("proxy_mesh: simplification ended at %d faces, above target_faces=%d (%s after %d rounds)" % (
+                    st["faces"], int(target_faces), "stalled" if st["stalled"] else "out of rounds", st["rounds"]), RuntimeWarning, stacklevel=2)
+            V, F = self.simplified.vertices, self.simplified.faces
         return V.contiguous(), F.contiguous()
 
 
@@ -237,12 +258,12 @@ def fuse_cloud(pc, cameras, pipe=None, bg_gaussian=None, resolution=96, bounds=N
 
 
 def from_cloud(pc, cameras, pipe=None, bg_gaussian=None, resolution=96, bounds=None, views_per_call=8, trunc_voxels=3.0, alpha_min=0.5,
-               carve=True, min_weight=1, keep="largest", bg_color=None):
+               carve=True, min_weight=1, keep="largest", bg_color=None, target_faces=None, simplify_max_rounds=1024):
     """The proxy mesh of a trained cloud: (vertices float32 [V,3], faces int32 [F,3]) on the device: fuse_cloud(...).extract(min_weight,
-    keep)."""
+    keep, target_faces, simplify_max_rounds)."""
     vol = fuse_cloud(pc, cameras, pipe=pipe, bg_gaussian=bg_gaussian, resolution=resolution, bounds=bounds, views_per_call=views_per_call,
                      trunc_voxels=trunc_voxels, alpha_min=alpha_min, carve=carve, bg_color=bg_color)
-    return vol.extract(min_weight=min_weight, keep=keep)
+    return vol.extract(min_weight=min_weight, keep=keep, target_faces=target_faces, simplify_max_rounds=simplify_max_rounds)
 
 
 def _load_model(path, mesh_gaussian, dev):
@@ -273,6 +294,8 @@ def main(argv=None):
     ap.add_argument("--trunc_voxels", type=float, default=3.0)
     ap.add_argument("--alpha_min", type=float, default=0.5)
     ap.add_argument("--keep", choices=("largest", "all"), default="largest")
+    ap.add_argument("--target_faces", type=int, help="simplify the mesh to at most this many faces (mesh_simplify)")
+    ap.add_argument("--simplify_max_rounds", type=int, default=1024)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("proxy_mesh needs a HIP (cuda) device; there is no CPU path")
@@ -289,15 +312,20 @@ def main(argv=None):
     vol = fuse_cloud(pc, cams, resolution=a.resolution, bounds=bounds, trunc_voxels=a.trunc_voxels, alpha_min=a.alpha_min)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
-    V, F = vol.extract(keep=a.keep)
+    V, F = vol.extract(keep=a.keep, target_faces=a.target_faces, simplify_max_rounds=a.simplify_max_rounds)
     torch.cuda.synchronize()
     t3 = time.perf_counter()
     v, f = V.cpu().numpy(), F.cpu().numpy()
     gio.write_obj(a.out, v, f)
     t4 = time.perf_counter()
-    print(json.dumps(dict(vertices=int(v.shape[0]), faces=int(f.shape[0]), components_dropped=int(vol.stats["components_dropped"]),
-                          boundary_edges=boundary_edges(f), grid=[vol.nx, vol.ny, vol.nz], views=len(cams),
-                          seconds=dict(load=t1 - t0, render_fuse=t2 - t1, extract=t3 - t2, write=t4 - t3))))
+    out = dict(vertices=int(v.shape[0]), faces=int(f.shape[0]), components_dropped=int(vol.stats["components_dropped"]),
+               boundary_edges=boundary_edges(f), grid=[vol.nx, vol.ny, vol.nz], views=len(cams),
+               seconds=dict(load=t1 - t0, render_fuse=t2 - t1, extract=t3 - t2, write=t4 - t3))
+    if a.target_faces is not None:                                     # (extract's time then includes the simplification)
+        out.update(faces_before_simplify=vol.stats["faces_before_simplify"], simplify_rounds=vol.stats["simplify_rounds"],
+                   simplify_reached=vol.stats["simplify_reached"])
+        out["seconds"]["simplify"] = vol.stats["seconds_simplify"]
+    print(json.dumps(out))
     return 0
 
 

@@ -394,6 +394,56 @@ int gm_surface_nets(int nx, int ny, int nz, const float* origin, float voxel, co
                     int max_vertices, float* out_vertices, int max_faces, int* out_faces, int* out_counts, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* Mesh simplification by rounds of quadric-error edge collapses with SUBSET PLACEMENT (mesh_simplify.simplify): a collapse i -> j removes
+ * vertex i and moves nothing, so the output vertices are rows of the input; the error quadrics (Garland & Heckbert 1997) are the only
+ * floating-point state.  The reference sends its users to MeshLab for this step: the result is defined by arithmetic - float32, no
+ * contraction, correctly rounded sqrt and division, dot(x, y) = (x.x y.x + x.y y.y) + x.z y.z, cross(x, y) = (x.y y.z - x.z y.y,
+ * x.z y.x - x.x y.z, x.x y.y - x.y y.x) - and tests/simplify_ref.py restates it in numpy bit for bit.  ALL ARRAYS ON THE DEVICE.
+ * vertices float [Vm,3], faces int32 [F,3] (the live faces), (vf_offsets int32 [Vm+1], vf_faces int32 [3F]): the faces at each vertex in
+ * ascending face order (deform.vertex_face_adjacency).
+ * gm_mesh_quadrics: out_quadrics float [Vm,10], the upper triangle of the 4 x 4 quadric in row order 00 01 02 03 11 12 13 22 23 33; from 0,
+ * over the faces (a, b, c) of v in CSR order:
+ *   n = cross(b - a, c - a), l = sqrt(dot(n, n)); not (l > 0 and l <= FLT_MAX): the face adds nothing (zero area, NaN, overflow)
+ *   u = n / l per component, p = (u.x, u.y, u.z, -dot(u, a)), area = l * 0.5f; Q[k] = Q[k] + area * (p_r * p_c) for k = (r, c).
+ *   One thread per vertex, a gather, no float atomics.
+ * gm_mesh_collapse_round: one round.  edges int32 [E,2]: the unique undirected edges (lo, hi), lo < hi, of the live faces sorted by
+ * lo Vm + hi - the index is the edge id e -, edge_faces int32 [E]: how many faces hold each; quadrics float [Vm,10] the current quadrics.
+ *   locked[v]: v is an end of an edge whose face count != 2 (borders; the four-face edges naive surface nets leave).
+ *   Candidates: per edge with face count 2 and per direction i -> j (i removed) whose i is not locked:
+ *     link: the distinct vertices w outside {i, j} that share a face with i and share a face with j are exactly 2, and no face of i
+ *       without j has its other two corners in one face of j (a tetrahedron never folds flat, no two faces over the same three vertices);
+ *     flip: over every face of i that does not hold j, (p0, p1, p2) its corners' positions in row order, n0 = cross(p1 - p0, p2 - p0), n1
+ *       the same with V[j] at i's corner, d = dot(n0, n1), s = dot(n0, n0) * dot(n1, n1): the direction stands only if on every such face
+ *       d > 0 and d d <= FLT_MAX and s <= FLT_MAX and d d >= (min_cos * min_cos) * s (every comparison false on NaN);
+ *     cost: q[k] = Q[i][k] + Q[j][k], (x, y, z) = V[j], r0 = ((q00 x + q01 y) + q02 z) + q03, r1 = ((q01 x + q11 y) + q12 z) + q13,
+ *       r2 = ((q02 x + q12 y) + q22 z) + q23, r3 = ((q03 x + q13 y) + q23 z) + q33, c = ((x r0 + y r1) + z r2) + r3; not |c| <= FLT_MAX:
+ *       rejected; cost = c > 0 ? c : +0; cost > max_error: rejected (+inf: no bound).
+ *   The edge keeps the cheaper direction that stands, on a tie the one that removes the larger id.  out_key uint64 [E] = (bits of cost)
+ *   << 32 | e (the bits of a non-negative float order as integers); out_from / out_to int32 [E] = i / j.  No direction stands: key all
+ *   ones, from = to = -1.
+ *   Selection: vmin[v] = the least key among the candidate edges at v; out_selected uint8 [E] = 1 iff the edge is a candidate and its key
+ *   == the minimum of vmin[u] over u in N[i] + N[j] + {i, j} (N[v]: the corners of the faces of v).  *out_count int32 = how many.
+ *   If e and e' are both selected and an end u of e' lies in the closed neighbourhood of an end x of e, then key(e) <= vmin[u] <= key(e')
+ *   and, adjacency being symmetric, key(e') <= vmin[x] <= key(e): the keys hold the edge id, e = e'.  So no end of one selected edge is an
+ *   end or a neighbour of an end of another: the collapses of a round change disjoint face sets, read no corner that another removes (and
+ *   nothing ever moves), leave each other's N[i], N[j] as they were, all j are distinct and no j is an i - each one's link and flip tests
+ *   stay true while any of the others apply, in any order (the caller may apply only the smallest keys to land on a face count).
+ *   vmin by 64-bit atomicMin, the count by integer atomicAdd: order-independent, the same bits every run; no workgroup waits for another.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: a negative size, F > (2^31 - 1) / 3, and for the round: min_cos negative, NaN or
+ * infinite, max_error negative or NaN, E > 0 with Vm == 0 or F == 0, a NULL pointer, out_key not 8-byte aligned, an output or the workspace
+ * overlapping anything else (gm_mesh_quadrics: a NULL with Vm > 0, out_quadrics overlapping an input); with GM_ERR_BUFFER: a workspace below
+ * gm_mesh_collapse_round_workspace_bytes(Vm) (9 bytes a vertex, monotonic, positive at 0).  Vm == 0 (quadrics) / E == 0 (round) succeeds
+ * and launches nothing: then *out_count is not written.  Vertex ids read from faces and edges, face ids and offsets read from the CSR are
+ * forced into range: no fault, no meaning; mesh_simplify.simplify checks the faces on the host.  An edge's thread reads
+ * O(valence(i)^2 + valence(i) valence(j)) faces: made for proxy meshes (valence 4 to 8), slow at a vertex of valence in the thousands.  Stream-ordered, no device allocation, no
+ * host synchronisation. */
+int gm_mesh_quadrics(int Vm, const float* vertices, int F, const int* faces, const int* vf_offsets, const int* vf_faces, float* out_quadrics,
+                     void* stream);
+size_t gm_mesh_collapse_round_workspace_bytes(int Vm);
+int gm_mesh_collapse_round(int Vm, const float* vertices, const float* quadrics, int F, const int* faces, const int* vf_offsets, const int* vf_faces,
+                           int E, const int* edges, const int* edge_faces, float min_cos, float max_error, unsigned char* out_selected, int* out_from,
+                           int* out_to, unsigned long long* out_key, int* out_count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Mesh-driven deformation of bound Gaussians; replaces the Jittor tensor algebra of
  * SingleObjectDeform.deform_gaussian (edittool/__init__.py:116-131), tensor-in form:
  *   tri int32 [N,3] vertex ids of the bound face, w float [N,3] barycentric weights,
