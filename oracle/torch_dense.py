@@ -19,6 +19,7 @@ Reference semantics that are NOT plain autograd and are reproduced on purpose:
 """
 import math
 
+import numpy as np
 import torch
 
 SH_C0 = 0.28209479177387814
@@ -53,10 +54,19 @@ def quat_to_rot(q):
                         2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
 
 
-def render(means, opac, view, proj, campos, W, H, tanx, tany, bg, D=3, shs=None, colors_precomp=None,
-           scales=None, rots=None, cov3D_precomp=None, mod=1.0, means2D=None):
-    """All tensor args float64 torch tensors (requires_grad as desired).  view/proj are the
-    reference's transposed 4x4 (row-vector convention).  Returns (color[3,H,W], aux dict)."""
+def per_gaussian(means, view, proj, campos, W, H, tanx, tany, D=3, shs=None, colors_precomp=None, scales=None, rots=None,
+                 cov3D_precomp=None, mod=1.0, means2D=None, decisions=None):
+    """The per-Gaussian stage of `render` (projection, frustum clamp, cov2D, conic, radius, tile rectangle, SH colour): everything the
+    preprocess kernels compute, before any pixel is touched.  Returns a dict of live (non-detached) tensors.
+    decisions (optional dict of numpy / torch bool arrays): the stage's DISCRETE decisions taken from elsewhere - the float32 arithmetic of
+    the kernels - instead of from the float64 values here.  A Gaussian within rounding distance of a threshold takes another branch in
+    float32 than in float64, and the gradient jumps there (tests/test_preprocess_edges_host.py), so a float64 reference of a float32
+    kernel has to branch where the kernel branches:
+      inx, iny [P]     t.x / t.z (t.y / t.z) inside +-1.3 tan(fov/2): the clamp is NOT active (xmul / ymul = 1)
+      clamped  [P,3]   the colour channel was clamped at 0 (no gradient through it)
+      overflow [P]     denom2inv == 0 (backward.cu:203-205): no gradient through the conic
+      visible  [P]     radii > 0 (returned as `vis`; stage_vjp gives every other row zero gradient)"""
+    dec = {} if decisions is None else {k: torch.as_tensor(v, dtype=torch.bool) for k, v in decisions.items() if v is not None}
     P = means.shape[0]
     dt = means.dtype
     fx, fy = W / (2.0 * tanx), H / (2.0 * tany)
@@ -79,8 +89,8 @@ def render(means, opac, view, proj, campos, W, H, tanx, tany, bg, D=3, shs=None,
     limx, limy = 1.3 * tanx, 1.3 * tany
     tz = t[:, 2]
     txtz, tytz = t[:, 0] / tz, t[:, 1] / tz
-    inx = (txtz >= -limx) & (txtz <= limx)
-    iny = (tytz >= -limy) & (tytz <= limy)
+    inx = dec["inx"] if "inx" in dec else (txtz >= -limx) & (txtz <= limx)
+    iny = dec["iny"] if "iny" in dec else (tytz >= -limy) & (tytz <= limy)
     tx = torch.where(inx, t[:, 0], (txtz.clamp(-limx, limx) * tz).detach())
     ty = torch.where(iny, t[:, 1], (tytz.clamp(-limy, limy) * tz).detach())
     zero = torch.zeros_like(tz)
@@ -93,6 +103,8 @@ def render(means, opac, view, proj, campos, W, H, tanx, tany, bg, D=3, shs=None,
     cc = cov2[:, 1, 1] + 0.3
     det = a * cc - b * b
     conic = torch.stack([cc / det, -b / det, a / det], 1)
+    if "overflow" in dec:
+        conic = torch.where(dec["overflow"][:, None], conic.detach(), conic)
     mid = 0.5 * (a + cc)
     lam = mid + torch.sqrt(torch.clamp(mid * mid - det, min=0.1))
     radius = torch.ceil(3.0 * torch.sqrt(lam)).detach()
@@ -107,13 +119,62 @@ def render(means, opac, view, proj, campos, W, H, tanx, tany, bg, D=3, shs=None,
     x0 = torch.trunc((pxd - ri) / 16).clamp(0, gx); x1 = torch.trunc((pxd + ri + 15) / 16).clamp(0, gx)
     y0 = torch.trunc((pyd - ri) / 16).clamp(0, gy); y1 = torch.trunc((pyd + ri + 15) / 16).clamp(0, gy)
     vis = vis & (det != 0) & ((x1 - x0) * (y1 - y0) > 0)
+    if "visible" in dec:
+        vis = dec["visible"]
     # colours
     if colors_precomp is not None:
         col = colors_precomp
     else:
         d = means - campos[None, :]
         d = d / d.norm(dim=1, keepdim=True)
-        col = torch.clamp(eval_sh(D, shs, d) + 0.5, min=0.0)
+        col = eval_sh(D, shs, d) + 0.5
+        col = torch.where(dec["clamped"], torch.zeros_like(col), col) if "clamped" in dec else torch.clamp(col, min=0.0)
+    return dict(t=t, vis=vis, ndc=ndc, a=a, b=b, cc=cc, det=det, conic=conic, radius=radius, px=px, py=py, x0=x0, x1=x1, y0=y0, y1=y1,
+                col=col, inx=inx, iny=iny)
+
+
+def stage_vjp(dmean2D, dconic, dcolor, means, cam, D=3, shs=None, colors_precomp=None, scales=None, rots=None, cov3D_precomp=None,
+              mod=1.0, decisions=None):
+    """Float64 vector-Jacobian product of the per-Gaussian stage, in the conventions of the preprocess backward kernel
+    (gm_preprocess.hip preprocess_bwd_body / backward.cu:144-396).  Inputs are what that kernel consumes, as numpy arrays:
+      dmean2D [P,2+]  dL/d(ndc-scaled pixel position) = pixel-space gradient x (0.5 W, 0.5 H)  (backward.cu:545-546)
+      dconic  [P,4]   (dL/dconic.x, HALF of dL/dconic.y, unused, dL/dconic.z)                 (backward.cu:549-551)
+      dcolor  [P,3]   dL/d(clamped colour)
+    Every other argument is a float32 numpy input of the rasterizer (cam: the camera dict).  Returns numpy float64
+    dict(means, and cov | scales + rots, and shs | colors): autograd of sum(g . stage output) through per_gaussian, with the discrete
+    decisions of `decisions` (see per_gaussian); rows that are not visible get zero."""
+    t64 = lambda x, rg=False: None if x is None else torch.tensor(np.asarray(x, np.float64), dtype=torch.float64, requires_grad=rg)
+    leaves = dict(means=t64(means, True))
+    kw = {}
+    if colors_precomp is not None:
+        kw["colors_precomp"] = leaves["colors"] = t64(colors_precomp, True)
+    else:
+        kw["shs"] = leaves["shs"] = t64(shs, True)
+    if cov3D_precomp is not None:
+        kw["cov3D_precomp"] = leaves["cov"] = t64(cov3D_precomp, True)
+    else:
+        kw["scales"] = leaves["scales"] = t64(scales, True); kw["rots"] = leaves["rots"] = t64(rots, True)
+    g = per_gaussian(leaves["means"], t64(cam["view"]), t64(cam["proj"]), t64(cam["campos"]), cam["W"], cam["H"], cam["tanx"], cam["tany"],
+                     D=D, mod=mod, decisions=decisions, **kw)
+    g2d, gc, gcol = t64(dmean2D), t64(dconic), t64(dcolor)
+    vis = g["vis"].to(torch.float64)
+    loss = (vis * (g2d[:, 0] * g["ndc"][:, 0] + g2d[:, 1] * g["ndc"][:, 1]
+                   + gc[:, 0] * g["conic"][:, 0] + 2.0 * gc[:, 1] * g["conic"][:, 1] + gc[:, 3] * g["conic"][:, 2]
+                   + (gcol * g["col"]).sum(1))).sum()
+    loss.backward()
+    return {k: (v.grad if v.grad is not None else torch.zeros_like(v)).numpy() for k, v in leaves.items()}
+
+
+def render(means, opac, view, proj, campos, W, H, tanx, tany, bg, D=3, shs=None, colors_precomp=None,
+           scales=None, rots=None, cov3D_precomp=None, mod=1.0, means2D=None):
+    """All tensor args float64 torch tensors (requires_grad as desired).  view/proj are the
+    reference's transposed 4x4 (row-vector convention).  Returns (color[3,H,W], aux dict)."""
+    P = means.shape[0]
+    dt = means.dtype
+    g = per_gaussian(means, view, proj, campos, W, H, tanx, tany, D=D, shs=shs, colors_precomp=colors_precomp, scales=scales, rots=rots,
+                     cov3D_precomp=cov3D_precomp, mod=mod, means2D=means2D)
+    t, vis, conic, radius, px, py, col = g["t"], g["vis"], g["conic"], g["radius"], g["px"], g["py"], g["col"]
+    a, b, cc, x0, x1, y0, y1 = g["a"], g["b"], g["cc"], g["x0"], g["x1"], g["y0"], g["y1"]
     # order: (depth as float32 bits, index) ascending
     depth32 = t[:, 2].detach().to(torch.float32)
     order = sorted(range(P), key=lambda i: (float(depth32[i]), i))

@@ -87,3 +87,28 @@ def forward_state(scene, cam, bg, D=3, use_precomp_cov=False, use_precomp_color=
     out["child_mask"] = out["tile_keys"] >> 16
     out["tile_keys"] = out["tile_keys"] & 0xFFFF
     return out
+
+
+def stage_grads_gpu(sc, cam, bg, dpix, D, pre_cov, pre_col, shs=None, sh_step=None):
+    """Forward + backward through the low-level pair, keeping the BLEND stage's outputs (dL/dmean2D, dL/dconic, dL/dcolour, dL/dopacity)
+    next to the final gradients: what the preprocess backward consumed and what it made of it.
+    shs (optional): the [P,M,3] device tensor to pass as the SH operand of both passes (its layout and alignment pick the kernels);
+    sh_step (optional, an ShStep on that operand): the backward takes the fused SH Adam step - dL/dSH, dL/dcolour, dL/dcov3D and dL/dconic
+    are then not returned (None)."""
+    t = lambda k: T(sc[k])
+    means, opac = t("means"), t("opac")
+    if shs is None:
+        shs = None if pre_col else t("shs")
+    colors = t("colors_precomp") if pre_col else None
+    scales = None if pre_cov else t("scales"); rots = None if pre_cov else t("rots"); cov = t("cov3D_precomp") if pre_cov else None
+    H, W = cam["H"], cam["W"]
+    a = (T(bg), means, colors, opac, scales, rots, 1.0, cov, T(cam["view"]), T(cam["proj"]), cam["tanx"], cam["tany"])
+    nr, color, radii, geom, binning, img = R.rasterize_forward_begin(*a, H, W, shs, D, T(cam["campos"])).finish(exact_exponent=True)
+    kw = dict(want_conic=True) if sh_step is None else dict(sh_step=sh_step)
+    out = R.rasterize_backward(a[0], means, radii, colors, scales, rots, 1.0, cov, a[8], a[9], cam["tanx"], cam["tany"], T(dpix), shs, D,
+                               T(cam["campos"]), geom, nr, binning, img, False, **kw)
+    torch.cuda.synchronize()
+    names = ("dmean2D", "dcolor", "dopacity", "dmean3D", "dcov3D", "dsh", "dscale", "drot", "dconic")
+    res = {k: (None if v is None else v.cpu().numpy()) for k, v in zip(names, out)}
+    res["radii"] = radii.cpu().numpy()
+    return res

@@ -203,14 +203,11 @@ def assert_forward_gate(fw, color, W, H, tol=1e-4, what="", plain_tol=None, bg=N
     return n_out
 
 
-def _check_geometry(orc, st, fw, scene, use_precomp_color):
-    """gpu_utils.forward_state against oracle.forward_full: radii, tiles, instance lists and ranges bit-exact, and the per-Gaussian
-    geometry (means2D, conic, opacity, depth key, rgb, clamp bits) of every visible Gaussian bit-identical under the arithmetic contract."""
-    g = fw["geo"]
+def _check_per_gaussian(st, g, use_precomp_color):
+    """radii and the per-Gaussian geometry (means2D, conic, opacity, depth key, rgb, clamp bits) of every visible Gaussian bit-identical to the
+    oracle's preprocess output `g` under the arithmetic contract - the part of _check_geometry that holds under every emission policy."""
     vis = g["radii"] > 0
     assert np.array_equal(st["radii"], g["radii"])
-    assert np.array_equal(st["tiles"], g["tiles"])
-    assert st["R"] == fw["bins"]["R"]
     sp = st["splat"]
     assert np.array_equal(sp[vis, 0:2].view(np.uint32), g["xy"][vis].view(np.uint32))
     con = np.concatenate([sp[:, 2:4], sp[:, 4:5]], 1)
@@ -222,6 +219,15 @@ def _check_geometry(orc, st, fw, scene, use_precomp_color):
     if not use_precomp_color:
         cl = np.stack([(st["clamped"] >> c) & 1 for c in range(3)], 1)
         assert np.array_equal(cl[vis], g["clamped"][vis])
+
+
+def _check_geometry(orc, st, fw, scene, use_precomp_color):
+    """gpu_utils.forward_state against oracle.forward_full: radii, tiles, instance lists and ranges bit-exact, and the per-Gaussian
+    geometry (means2D, conic, opacity, depth key, rgb, clamp bits) of every visible Gaussian bit-identical under the arithmetic contract."""
+    g = fw["geo"]
+    _check_per_gaussian(st, g, use_precomp_color)
+    assert np.array_equal(st["tiles"], g["tiles"])
+    assert st["R"] == fw["bins"]["R"]
     assert np.array_equal(st["point_list"], fw["bins"]["point_list"])
     assert np.array_equal(st["tile_keys"], (fw["bins"]["keys"] >> np.uint64(32)).astype(np.uint32))
     assert np.array_equal(st["ranges"], fw["bins"]["ranges"])

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_utils import stage_grads_gpu as _stage_grads_gpu
 from helpers import fuzz_scene, assert_forward_gate
 from test_gpu_parity import _grads_gpu, _rel
 
@@ -108,25 +109,6 @@ def test_needle_scenes_against_the_oracle_and_float64_truth(oracle):
     print("tensors more than 1e-3 from the C oracle: %d of %d; every one of them within 1e-3 of float64 autograd: %s" % (
         n_over, len(rows), all(r[3] <= 1e-3 for r in rows if r[2] > 1e-3)))
     assert not problems, problems
-
-
-def _stage_grads_gpu(sc, cam, bg, dpix, D, pre_cov, pre_col):
-    """Forward + backward through the low-level pair, keeping the BLEND stage's outputs (dL/dmean2D, dL/dconic, dL/dcolour, dL/dopacity)
-    next to the final gradients: what the preprocess backward consumed and what it made of it."""
-    from gpu_utils import T
-    from gaussianmesh_amd import rasterizer as Rz
-    t = lambda k: T(sc[k])
-    means, opac = t("means"), t("opac")
-    shs = None if pre_col else t("shs"); colors = t("colors_precomp") if pre_col else None
-    scales = None if pre_cov else t("scales"); rots = None if pre_cov else t("rots"); cov = t("cov3D_precomp") if pre_cov else None
-    H, W = cam["H"], cam["W"]
-    a = (T(bg), means, colors, opac, scales, rots, 1.0, cov, T(cam["view"]), T(cam["proj"]), cam["tanx"], cam["tany"])
-    nr, color, radii, geom, binning, img = Rz.rasterize_forward_begin(*a, H, W, shs, D, T(cam["campos"])).finish(exact_exponent=True)
-    out = Rz.rasterize_backward(a[0], means, radii, colors, scales, rots, 1.0, cov, a[8], a[9], cam["tanx"], cam["tany"], T(dpix), shs, D,
-                                T(cam["campos"]), geom, nr, binning, img, False, want_conic=True)
-    torch.cuda.synchronize()
-    names = ("dmean2D", "dcolor", "dopacity", "dmean3D", "dcov3D", "dsh", "dscale", "drot", "dconic")
-    return {k: (None if v is None else v.cpu().numpy()) for k, v in zip(names, out)}
 
 
 def test_needle_scenes_reference_float32_block_is_the_only_divergence(oracle):

@@ -149,7 +149,7 @@ def _abi_backward(sc, cam, bg, st, shs, D, dpix, dsh_offset, keep=None):
     return out, dbuf.cpu().numpy()
 
 
-def _two_pixel_gradient(seed):
+def _two_pixel_gradient(seed, W=W, H=H):
     """dL/dpix non-zero on two pixels only: every accumulator then sums at most two non-zero terms (and exact zeros), so its value is the
     same in every summation order and two backward passes give the same bits"""
     dpix = np.zeros((3, H, W), np.float32)
