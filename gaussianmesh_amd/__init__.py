@@ -7,6 +7,8 @@
   arap.ArapSolver (the proxy mesh deformed from dragged handle vertices, as rigidly as possible)
   mesh_pick.ray_mesh_hits / pick / visible_vertices / screen_offset (from a pixel to a vertex of the current mesh and back)
   mesh_region.surface_graph / SurfaceGraph / region_handles (distances along the mesh: a picked vertex grown into a surface region)
+  contribution.blend_weights / accumulate / select / importance_rows / split_plain (2-D masks lifted onto a cloud: the object and the
+    background out of one trained scene; pruning by contribution)
 All compute runs in csrc/libgmesh_hip.so (hand-written HIP for gfx950) through include/gmesh_hip.h.
 """
 import os as _os

@@ -88,6 +88,7 @@ SIGNATURES = {
     "gm_depth_slab_bytes": (sz, [i32]),
     "gm_forward_1_geom": (i32, [i32, vp, vp, vp, i32, i32, i64, vp, i32, i32, vp, i32, vp, vp, i32, vp]),
     "gm_forward_1_aux": (i32, [i32, vp, vp, vp, i32, i32, i64, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp]),
+    "gm_blend_weights": (i32, [i32, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, i32, vp]),
     "gm_forward_status_async": (i32, [vp, i32, vp, vp]),
     "gm_forward_deformed_batch_async": (i32, [i32, i32, C.POINTER(BatchFrame), i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, i32, vp]),
     "gm_forward_deformed_batch_aux_async": (i32, [i32, i32, C.POINTER(BatchFrame), i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp,

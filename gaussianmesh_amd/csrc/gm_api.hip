@@ -867,6 +867,30 @@ static int check_outputs_apart(const char* fn, const ByteRange* rg, int n, int n
   return 0;
 }
 
+int gm_blend_weights(int emission_policy, void* geom_buffer, void* binning_buffer, void* image_buffer, int P, int64_t binning_capacity,
+                     int width, int height, const uint8_t* mask, unsigned long long* sums, unsigned int* peak, int debug, void* stream) {
+  if (int rc = check_policy(emission_policy)) return rc;
+  if (P < 0 || width <= 0 || height <= 0) { set_error("gm_blend_weights: invalid sizes P=%d W=%d H=%d", P, width, height); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_tile_grid(width, height)) return rc;
+  const int tiles = TileGrid(width, height, emission_policy).ptiles;
+  if (tiles > 65536) { set_error("gm_blend_weights: too many list tiles for emission policy %d", emission_policy); return GM_ERR_INVALID_ARG; }
+  if (binning_capacity < 0) { set_error("gm_blend_weights: negative binning capacity"); return GM_ERR_INVALID_ARG; }
+  if (P == 0) return GM_OK;
+  if (!geom_buffer || !binning_buffer || !image_buffer || !sums) {
+    set_error("gm_blend_weights: null geom_buffer / binning_buffer / image_buffer / sums"); return GM_ERR_INVALID_ARG;
+  }
+  const ByteRange rg[6] = {{geom_buffer, gm_geom_bytes(P), "geom_buffer"}, {binning_buffer, gm_binning_bytes(binning_capacity), "binning_buffer"},
+                           {image_buffer, gm_image_bytes(width, height), "image_buffer"}, {mask, (size_t)width * height, "mask"},
+                           {sums, 16 * (size_t)P, "sums"}, {peak, 4 * (size_t)P, "peak"}};
+  if (int rc = check_outputs_apart("gm_blend_weights", rg, 6, 2)) return rc;
+  if (binning_capacity == 0) return GM_OK;                       // a frame without instances: every list is empty
+  GeomState g = GeomState::from(geom_buffer, (size_t)P);
+  ImageState img = ImageState::from(image_buffer, width, height);
+  BinningState b = BinningState::from(binning_buffer, (size_t)binning_capacity);
+  return launch_blend_weights(g, b.pairs[sort_final_slot(tiles)], img, width, height, emission_policy, mask,
+                              sums, peak, debug, reinterpret_cast<hipStream_t>(stream));
+}
+
 int gm_mesh_quadrics(int Vm, const float* vertices, int F, const int* faces, const int* vf_offsets, const int* vf_faces, float* out_quadrics,
                      void* stream) {
   if (Vm < 0 || F < 0) { set_error("gm_mesh_quadrics: negative size Vm=%d F=%d", Vm, F); return GM_ERR_INVALID_ARG; }

@@ -389,6 +389,9 @@ int launch_render_fwd(const GeomState& g, const uint2* pairs, ImageState& img, i
 int launch_render_bwd(const GeomState& g, const uint2* pairs, ImageState& img, int W, int H, int mode,
                       const float* background, const float* dL_dpix, int debug, hipStream_t s,
                       bool aux = false, const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr);   // accumulates into g.grad_acc
+// gm_blend_weights: the forward's walk over a completed frame's lists, accumulating per Gaussian (gm_render.hip)
+int launch_blend_weights(const GeomState& g, const uint2* pairs, ImageState& img, int W, int H, int mode, const uint8_t* mask,
+                         unsigned long long* sums, uint32_t* peak, int debug, hipStream_t s);
 // gm_backward_aux: dL/dmean3D += dL/dz (view[2], view[6], view[10]); dL/dz = grad_acc[12 i + 9] (written to dL_dz too when given)
 int launch_depth_grad(int P, const GeomState& g, const float* viewmatrix, float* dL_dmean3D, float* dL_dz, hipStream_t s);
 

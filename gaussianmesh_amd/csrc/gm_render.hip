@@ -452,4 +452,210 @@ int launch_render_bwd(const GeomState& g, const uint2* pairs, ImageState& img, i
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-Gaussian blend weights (gm_blend_weights): the forward's walk, scattering per Gaussian instead of writing per pixel.
+//
+// The weight of an (entry, pixel) pair, w = alpha T - the float the colour blend multiplies the entry's colour by - exists only inside the
+// blend kernels.  This one repeats the walk of the EXACT forward (same front end, same cull, staged_exponent, the same decisions and the same
+// T recurrence, instruction for instruction: T (1 - alpha) is ONE fused multiply-add there, -alpha T + T, and is spelled as one here) and keeps,
+// per Gaussian and summed over the pixels of the frame,
+//   sums[i][0] += u,  sums[i][1] += u k,  peak[i] = max(peak[i], bits(w)),   u = rint(w 2^24) (w <= 0.99: exact in a u32), k = the pixel's mask byte.
+// Integers, so that the result does not depend on the order in which waves, policies or views arrive.
+// Phase 1, lane = pixel, 16 survivors at a time: w of every (survivor, pixel) pair goes to an LDS matrix M[survivor][pixel].
+// Phase 2, lane = (survivor es = lane / 4, quarter qd = lane % 4): each lane folds 16 pixels of its survivor (row stride 65: the 64 lanes read 64
+// different banks), two cross-lane steps join the quarters, and the totals of the batch's up to 64 survivors wait in LDS until the batch is done:
+// then lane j commits survivor j - one 64-bit atomic add per non-zero sum and one atomic max, issued from as many lanes of one instruction as the
+// batch has survivors with a weight (the backward blend's shape).  u k <= 0.99 * 2^24 * 255 < 2^32, a wave's sum of u < 2^30.
+struct WgtLds {                  // per wave: 8.2 KiB
+  uint2 qa[RQ_QA];               // candidate ring of the front end
+  float4 ra[68];                 // staged batch: (x, y, a', c'), b', opacity, Gaussian id (+ 4 entries of padding with opacity 0 behind the last)
+  float bq[68];
+  float op[68];
+  uint32_t id[64];
+  float M[16][65];               // w per (survivor of the group, pixel)
+  uint32_t kk[64];               // mask byte per pixel (kernel start)
+  uint32_t rt[64], rp[64];       // per survivor of the batch: sum of u, largest bits(w)
+  unsigned long long ri[64];     //                            sum of u k
+};
+__global__ __launch_bounds__(64) void blend_weights_kernel(const uint2* __restrict__ ranges, const uint2* __restrict__ pairs,
+                                                           const float4* __restrict__ splat, int W, int H, TileMap tm,
+                                                           const uint32_t* __restrict__ counters, int mode, const uint8_t* __restrict__ mask,
+                                                           unsigned long long* __restrict__ sums, uint32_t* __restrict__ peak) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x >> 3) & 3);
+  const int tile_block = (int)(((blockIdx.x >> 5) << 3) | (blockIdx.x & 7));
+  if ((int)counters[GM_CNT_POLICY] != mode || counters[GM_CNT_REFUSED] != 0u) return;   // refused, or lists of another policy: add nothing
+  int tx, ty, parent;
+  uint32_t child_bit;
+  if (!tm.locate(tile_block, tx, ty, parent, child_bit)) return;
+  if (tm.s == 1) child_bit = quadrant_bit(tx, ty, wave);
+  const uint2 range = ranges[parent];
+  const int n = (int)(range.y - range.x);
+  if (n <= 0) return;
+  const uint2* list = pairs + range.x;
+
+  const int px = tx * GM_TILE + (wave & 1) * 8 + (lane & 7);
+  const int py = ty * GM_TILE + (wave >> 1) * 8 + (lane >> 3);
+  const bool inside = px < W && py < H;
+  float T = inside ? 1.0f : -1.0f;               // T < 0: stopped (or outside the frame), as in the forward
+  const float rx0 = (float)(tx * GM_TILE + (wave & 1) * 8), ry0 = (float)(ty * GM_TILE + (wave >> 1) * 8);
+  const v2f pixf = {(float)px, (float)py};
+  __shared__ WgtLds L;
+  L.kk[lane] = inside ? (mask ? (uint32_t)mask[(size_t)W * py + px] : 255u) : 0u;   // (a pixel outside the frame has no weight: its byte is never read)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  const int es = lane >> 2, qd = lane & 3;       // phase 2 role
+#pragma unroll
+  for (int i = 0; i < 16; i++) L.M[i][lane] = 0.f;                // phase 2 also converts the rows behind a group's last survivor: M only ever holds weights
+  uint32_t kq[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) kq[i] = L.kk[16 * qd + i];
+
+  const int nlast = n - 1;
+  int kpos = 0;
+  uint32_t qa_head = 0, qa_cnt = 0;
+  uint2 kv[RQ_K];
+  auto scan = [&]() {                            // the forward's front end (gm_render_fwd_body.inc)
+    bool go = true;
+#pragma unroll
+    for (int k = 0; k < RQ_K; k++) {
+      go = go && kpos < n && qa_cnt + 64u <= (uint32_t)RQ_QA;
+      if (go) {
+        const int p = kpos + lane;
+        const bool mine = p < n && (kv[k].x & child_bit) != 0u;
+        const unsigned long long bal = __ballot(mine);
+        if (mine) L.qa[(qa_head + qa_cnt + lanes_below(bal)) & (RQ_QA - 1)] = make_uint2(kv[k].y, (uint32_t)p);
+        qa_cnt += (uint32_t)__popcll(bal);
+        kpos += 64;
+      }
+    }
+  };
+  auto load_keys = [&]() {
+#pragma unroll
+    for (int k = 0; k < RQ_K; k++) kv[k] = list[min(kpos + k * 64 + lane, nlast)];
+  };
+  auto pop = [&](int& count) {
+    count = (int)min(qa_cnt, 64u);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const uint2 cand = lane < count ? L.qa[(qa_head + (uint32_t)lane) & (RQ_QA - 1)] : make_uint2(0u, 0u);
+    qa_head += (uint32_t)count; qa_cnt -= (uint32_t)count;
+    return issue_gather(splat, cand);
+  };
+  load_keys();
+  scan();
+  load_keys();
+  auto step = [&](Gather& cur, int& n0, Gather& nxt, int& n2) -> bool {
+    const unsigned long long live = __ballot(T > 0.0f);
+    if (live == 0ull) return false;
+    if (n0 == 0 && qa_cnt == 0u && kpos >= n) return false;
+    uint32_t cols = (uint32_t)live | (uint32_t)(live >> 32);
+    cols |= cols >> 16; cols |= cols >> 8; cols &= 0xFFu;
+    const float cx0 = rx0 + (float)(__ffs((int)cols) - 1), cx1 = rx0 + (float)(31 - __clz((int)cols));
+    const float cy0 = ry0 + (float)((__ffsll(live) - 1) >> 3), cy1 = ry0 + (float)((63 - __clzll((long long)live)) >> 3);
+    __builtin_amdgcn_s_waitcnt(0x0F70);                                  // vmcnt(0)
+    scan();
+    load_keys();
+    nxt = pop(n2);
+    if (n0 > 0) {
+      const bool keep = lane < n0 && may_touch(cur.a.x, cur.a.y, cur.a.z, cur.a.w, cur.b.x, cur.b.y, cx0, cx1, cy0, cy1);
+      const unsigned long long kb = __ballot(keep);
+      const int ns = __popcll(kb);
+      if (keep) {
+        const int slot = (int)lanes_below(kb);
+        L.ra[slot] = make_float4(cur.a.x, cur.a.y, (-0.5f * LOG2E) * cur.a.z, (-0.5f * LOG2E) * cur.b.x);
+        L.bq[slot] = (-LOG2E) * cur.a.w;
+        L.op[slot] = cur.b.y;
+        L.id[slot] = cur.id;
+      }
+      if (lane < 4) {                                                    // survivors are taken four at a time: alpha = 0 behind the last
+        L.ra[ns + lane] = make_float4(0.f, 0.f, 0.f, 0.f); L.bq[ns + lane] = 0.f; L.op[ns + lane] = 0.f;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      int processed = 0;                                                 // survivors of the batch whose totals are in rt / ri / rp
+      bool alive = true;
+      for (int j = 0; j < ns && alive; j += 16) {
+        int gdone = 0;                                                   // survivors of this group that phase 1 walked
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          if (j + 4 * q >= ns || !alive) break;
+          float al[4];
+#pragma unroll
+          for (int t = 0; t < 4; t++) {
+            const int sl = j + 4 * q + t;
+            v2f dd;
+            const float e = staged_exponent(L.ra[sl], L.bq[sl], pixf, dd);
+            const float oG = L.op[sl] * __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(e), 0.0f, 1.0f);
+            al[t] = (oG >= 1.0f / 255.0f) ? fminf(0.99f, oG) : 0.0f;
+          }
+#pragma unroll
+          for (int t = 0; t < 4; t++) {
+            const float wa = al[t] * T, tt = __builtin_fmaf(-al[t], T, T);   // the forward's two instructions (see above)
+            const bool stop = tt < 0.0001f;
+            L.M[4 * q + t][lane] = stop ? 0.0f : wa;
+            T = stop ? -__builtin_fabsf(T) : tt;
+          }
+          gdone = min(4 * q + 4, ns - j);
+          alive = __any(T > 0.0f);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        uint32_t tot = 0u, pk = 0u;
+        unsigned long long ins = 0ull;
+        const float* mr = &L.M[es][16 * qd];
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+          const float w = mr[i];
+          const uint32_t u = (uint32_t)__builtin_rintf(w * 16777216.0f);
+          tot += u;
+          ins += (unsigned long long)u * kq[i];
+          pk = max(pk, __float_as_uint(w));
+        }
+#pragma unroll
+        for (int d = 1; d <= 2; d <<= 1) {
+          tot += (uint32_t)__shfl_xor((int)tot, d);
+          pk = max(pk, (uint32_t)__shfl_xor((int)pk, d));
+          const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)ins, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(ins >> 32), d);
+          ins += ((unsigned long long)hi << 32) | lo;
+        }
+        if (qd == 0 && es < gdone) { L.rt[j + es] = tot; L.rp[j + es] = pk; L.ri[j + es] = ins; }
+        processed = j + gdone;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");          // M has been read before the next group writes it
+        __builtin_amdgcn_wave_barrier();
+      }
+      if (lane < processed) {
+        const uint32_t tot = L.rt[lane];
+        if (tot != 0u) {                                                 // (an accepted pair has w >= 1e-4 / 255: u >= 6)
+          const size_t gid = (size_t)L.id[lane];
+          const unsigned long long ins = L.ri[lane];
+          atomicAdd(sums + 2 * gid, (unsigned long long)tot);
+          if (ins != 0ull) atomicAdd(sums + 2 * gid + 1, ins);
+          if (peak) atomicMax(peak + gid, L.rp[lane]);
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");            // the batch's rows have been read before the next is staged
+      __builtin_amdgcn_wave_barrier();
+    }
+    return true;
+  };
+  int n0, n1 = 0;
+  Gather g0 = pop(n0), g1 = g0;
+  for (;;) {
+    if (!step(g0, n0, g1, n1)) break;
+    if (!step(g1, n1, g0, n0)) break;
+  }
+}
+
+int launch_blend_weights(const GeomState& g, const uint2* pairs, ImageState& img, int W, int H, int mode, const uint8_t* mask,
+                         unsigned long long* sums, uint32_t* peak, int debug, hipStream_t s) {
+  const TileGrid tg(W, H, mode);
+  const TileMap tm{tg.gx, tg.gy, tg.pgx, tg.pgy, tg.s, img.tile_order};
+  if (tg.ptiles > 0)
+    hipLaunchKernelGGL(blend_weights_kernel, dim3(tm.blocks() * 4), dim3(64), 0, s, img.ranges, pairs, g.splat, W, H, tm, g.counters, mode, mask,
+                       sums, peak);
+  GM_LAUNCH_CHECK(debug, s);
+  return 0;
+}
+
 }  // namespace gm

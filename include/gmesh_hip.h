@@ -575,6 +575,28 @@ int gm_forward_1_aux(int emission_policy, void* geom_buffer, void* binning_buffe
                      int64_t binning_capacity, const float* background, int width, int height, float* out_color, int debug, void* stream,
                      int* status_host, int flags, unsigned int* work_hint, float* out_depth, float* out_alpha);
 
+/* Per-Gaussian blend weights of a completed frame: what lifting 2-D masks onto a cloud and pruning by contribution sum.
+ * One more walk of the frame's tile lists with the arithmetic of the GM_FWD_EXACT_EXPONENT blend (forward.cu:330-365): per (entry, pixel)
+ *   oG = opacity * min(1, exp2(E)); skipped when oG < 1/255; alpha = min(0.99, oG); w = alpha * T; stop WITHOUT applying the entry when
+ *   T - w < 1e-4; T starts at 1 -
+ * the float32 w is the value the colour blend multiplies the entry's colour by.  Per Gaussian i, over the pixels of the frame, the call ADDS
+ *   sums[2 i]     += sum of u,      u = (uint32) rintf(w * 2^24)      (total weight, unit 2^-24)
+ *   sums[2 i + 1] += sum of u * k,  k = the pixel's mask byte 0..255  (weight inside the mask, unit 2^-24 / 255; mask == NULL: 255 everywhere)
+ *   peak[i]        = max(peak[i], float bits of w)                    (w >= 0: an unsigned max on the bits is a max on the value; may be NULL)
+ * to what the buffers hold: the caller zeroes sums (uint64 [P][2]) and peak (uint32 [P]) once and hands them to every view.  Integer
+ * accumulators: the result does not depend on the emission policy, on the order of the views or on the run, bit for bit.
+ * The call follows ANY completed second half (gm_forward_1_geom / gm_forward_1_aux, whatever its flags, image-only frames and frames
+ * begun with GM_STREAM_DIRECT included: neither colour, final_T, n_contrib nor depth_key is read) on the same stream, with the same policy,
+ * geometry, binning and image buffers, before they are reused.  binning_capacity: the instance count the binning buffer was laid out
+ * for - the second half's num_rendered when that was >= 0, else its binning_capacity (gm_backward's R).
+ * A refused frame (status word 3 != 0) or one whose lists were built under another policy adds nothing (decided on the device).
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: a policy outside 0..3, P < 0, a frame size the forward entry points refuse, a
+ * negative capacity, and with P > 0: a NULL geom_buffer, binning_buffer, image_buffer or sums; sums or peak overlapping each other, the
+ * mask or one of the three buffers (taken as gm_geom_bytes(P), gm_binning_bytes(binning_capacity), gm_image_bytes(width, height)).
+ * P == 0 returns GM_OK and touches nothing. */
+int gm_blend_weights(int emission_policy, void* geom_buffer, void* binning_buffer, void* image_buffer, int P, int64_t binning_capacity,
+                     int width, int height, const uint8_t* mask, unsigned long long* sums, unsigned int* peak, int debug, void* stream);
+
 /* K frames of ONE view stream per launch chain (the edit tool replaying a deformation sequence, a camera path: the frames the render
  * loop would otherwise keep in flight on K HIP streams).  Equivalent, frame by frame and bit for bit (radii, lists, image, status words), to
  *   gm_forward_0_deformed_stream_async(policy, frame.geom_buffer, ..., frame.packed, ..., frame.viewmatrix, ..., flags & GM_BATCH_COV6)
