@@ -10,6 +10,7 @@
 // depth-ordered and only needs a stable sort by list tile afterwards.
 #include "gm_common.h"
 #include "gm_cull.h"
+#include "gm_wave.h"
 #pragma clang fp contract(off)
 
 namespace gm {
@@ -17,27 +18,6 @@ namespace gm {
 #define BN_THREADS 256
 #define DUP_STAGE 2048                               // instances a block can assemble in LDS (2 x 8 KB; 4096 is no faster alone and makes the
                                                      // workgroup harder to place next to other frames' blend kernels: 4350 -> 4400 frames/s)
-
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wsum /*[4] shared*/, uint32_t& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(incl, d);
-    if (lane >= d) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t woff = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < BN_THREADS / 64; w++) {
-    const uint32_t s = wsum[w];
-    woff += (w < wave) ? s : 0;
-    tot += s;
-  }
-  total = tot;
-  return woff + incl - v;
-}
 
 // the armed blocks of the frames of a batch in one launch (a single frame: one memset)
 __global__ __launch_bounds__(256) void arm_batch_kernel(uint4* __restrict__ arm, uint32_t arm_vec, const FrameOfs go) {
@@ -131,7 +111,7 @@ __global__ __launch_bounds__(BN_THREADS) void duplicate_kernel(const uint32_t* _
     uint32_t part = 0;
     for (uint32_t k = threadIdx.x; k < run * (RUN / GM_SCAN_ITEMS); k += BN_THREADS) part += chunk_inst[k];
     uint32_t tot;
-    block_exclusive_scan(part, wsum, tot);
+    block_exclusive_scan<BN_THREADS / 64>(part, wsum, tot);
     ibase = tot;
     __syncthreads();
   }
@@ -145,7 +125,7 @@ __global__ __launch_bounds__(BN_THREADS) void duplicate_kernel(const uint32_t* _
   }
   uint32_t total;
   const uint32_t block_base = ibase;
-  uint32_t off = block_exclusive_scan(sum, wsum, total);
+  uint32_t off = block_exclusive_scan<BN_THREADS / 64>(sum, wsum, total);
   // The chunk's instances form one contiguous output range.  When it fits the LDS stage (nearly always) they are
   // assembled there and copied out with full-line stores: per-lane runs written straight to HBM cost 2.3x the bytes
   // (partial lines, WRITE_SIZE 114 MB for 48.7 MB of pairs).  Otherwise the runs are stored directly.

@@ -28,7 +28,8 @@
 //    bk_hist -> bk_scan -> bk_scatter; the scan's exclusive digit bases ARE the tile ranges, so identifyTileRanges and
 //    its memset disappear.  More list tiles: two 8-bit passes + tile_ranges_kernel.
 //
-// Streams are (key, value) pairs interleaved as uint2 (one 8-byte access per entry everywhere).
+// Streams are (key, value) pairs interleaved as uint2 (one 8-byte access per entry everywhere).  The stable match-any rank, the workgroup
+// exclusive scan and the per-wave counts -> offsets step that every kernel here is built from are gm_wave.h's, shared with gm_sort.hip.
 //
 // One pass = three kernels, no workgroup ever waits for another one of the same launch:
 //   bk_hist     workgroup b counts the digits of its 4096 keys -> hist[b][digit] (one contiguous row), and adds the row to
@@ -46,6 +47,7 @@
 //               rate (25-34 us per pass); larger tiles make longer runs (tile / 2048 pairs per digit).
 #include "gm_common.h"
 #include "gm_tile_order.h"
+#include "gm_wave.h"
 
 namespace gm {
 
@@ -63,38 +65,6 @@ static_assert(BS_BINS == BK_WAVES * 256, "the counting split's bins live in wcnt
 #define BS_BIN_MAX 48u               // largest bin the counting split accepts before the stable radix passes take over
 
 struct DigitSpec { uint32_t sub, shift, mask; };       // digit(k) = ((k - sub) >> shift) & mask
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-  return v;
-}
-
-__device__ __forceinline__ uint32_t block_exclusive_scan_256(uint32_t v, uint32_t* wsum /*[4] shared*/, uint32_t& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(incl, d);
-    if (lane >= d) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t woff = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    const uint32_t s = wsum[w];
-    woff += (w < wave) ? s : 0;
-    tot += s;
-  }
-  total = tot;
-  return woff + incl - v;
-}
 
 // agent-scope accesses to memory that kernels of OTHER streams read or write while this one runs (the view stream's DepthPlan): they
 // bypass the XCD-local L2s, which are not coherent with each other inside a launch
@@ -182,12 +152,12 @@ __device__ __forceinline__ uint32_t block_build_depth_map(const uint32_t* __rest
   }
   (void)visible;
   uint32_t total_b;
-  uint32_t excl = block_exclusive_scan_256(nsum, wsum, total_b);
+  uint32_t excl = block_exclusive_scan<BK_WAVES>(nsum, wsum, total_b);
   __syncthreads();
   if (total_b > (1u << GM_BUCKET_BITS)) {                            // (uniform) fall back to one bucket per non-empty coarse bin
 #pragma unroll
     for (int j = 0; j < PER; j++) nbk[j] = cnt[j] ? 1u : 0u;
-    excl = block_exclusive_scan_256(nonempty, wsum, total_b);
+    excl = block_exclusive_scan<BK_WAVES>(nonempty, wsum, total_b);
     __syncthreads();
   }
 #pragma unroll
@@ -351,7 +321,7 @@ __global__ __launch_bounds__(BK_THREADS) void bk_scan_kernel(uint32_t* __restric
     if (lane == 0) gsum[wave] = part;
   }
   uint32_t gtotal;
-  const uint32_t excl = block_exclusive_scan_256(tot, wsum, gtotal);    // (its barrier also publishes gsum)
+  const uint32_t excl = block_exclusive_scan<BK_WAVES>(tot, wsum, gtotal);    // (its barrier also publishes gsum)
   below = gsum[0] + gsum[1] + gsum[2] + gsum[3];
   const uint32_t base = below + excl;
   if (c == 0) {
@@ -450,22 +420,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void bk_scatter_kernel(const void* _
     const bool valid = idx < n && (!MSD || key[r] != 0xFFFFFFFFu);
     vmask |= valid ? (1u << r) : 0u;
     const uint32_t d = digit(key[r]);
-    uint64_t peers = __ballot(valid);          // match-any over the digit bits among the valid lanes
-#pragma unroll
-    for (int b = 0; b < DB; b++) {
-      const uint64_t bal = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? bal : ~bal;
-    }
-    const uint32_t before = lanes_below(peers);
-    const int leader = __ffsll((unsigned long long)peers) - 1;
-    uint32_t old = 0;
-    if (valid && lane == leader) {
-      old = wcnt[wave][d];
-      wcnt[wave][d] = (uint16_t)(old + __popcll(peers));
-    }
-    old = __shfl(old, leader < 0 ? 0 : leader);
-    rank[r] = old + before;
-    __builtin_amdgcn_wave_barrier();           // keep the per-wave LDS counter updates of successive rounds in order
+    rank[r] = wave_match_rank<DB>(d, valid, wcnt[wave], lane);   // match-any over the digit bits among the valid lanes
   }
   __syncthreads();
   uint32_t tile_n;
@@ -475,34 +430,10 @@ __global__ __launch_bounds__(WAVES * 64, 4) void bk_scatter_kernel(const void* _
 #pragma unroll
     for (int j = 0; j < DPT; j++) {
       const int d = threadIdx.x * DPT + j;
-      uint32_t run = 0;
-      if (d < ND) {
-#pragma unroll
-        for (int w = 0; w < WAVES; w++) {
-          const uint32_t c = wcnt[w][d];
-          wcnt[w][d] = (uint16_t)run;
-          run += c;
-        }
-      }
-      dc[j] = run; sum += run;
+      dc[j] = d < ND ? wave_counts_to_offsets<WAVES>(&wcnt[0][d], ND) : 0u;
+      sum += dc[j];
     }
-    uint32_t incl = sum;                                       // workgroup-wide exclusive scan of `sum`
-#pragma unroll
-    for (int dd = 1; dd < 64; dd <<= 1) {
-      const uint32_t t = __shfl_up(incl, dd);
-      if (lane >= dd) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; w++) {
-      const uint32_t t = wsum[w];
-      woff += (w < wave) ? t : 0;
-      tot += t;
-    }
-    tile_n = tot;
-    uint32_t excl = woff + incl - sum;
+    uint32_t excl = block_exclusive_scan<WAVES>(sum, wsum, tile_n);
 #pragma unroll
     for (int j = 0; j < DPT; j++) {
       const int d = threadIdx.x * DPT + j;
@@ -543,6 +474,120 @@ __device__ __forceinline__ void chunk_add(uint32_t* __restrict__ chunk_inst, uin
   }
 }
 
+// Phases of bucket_sort_kernel (below) that stand on their own.  Every thread of the workgroup calls them (they contain workgroup
+// barriers); lane / wave are the caller's.  The in-LDS sort itself (counting split, stable passes, write-out) stays in the kernel's body:
+// it sits at the 128-VGPR edge of four waves per SIMD, and each of the three, moved into a function of its own, came back from the
+// compiler with other registers, spills and occupancy (the function is optimised alone before it is inlined).
+
+// The DIRECT launch's extra workgroup, beside the sorting ones: this frame's coarse histogram -> the table the stream's LATER frames place
+// their Gaussians with (slot = this frame's sequence number % slots; stamp 0 while the words change, the sequence number after)
+__device__ __forceinline__ void bs_publish_next_table(const uint32_t* slots, const uint32_t* coarse, const uint32_t* hdr,
+                                                      uint32_t* plan, DepthMap& m, uint32_t* wsum /*[4]*/, uint32_t* s_tmp /*[4]*/) {
+  const uint32_t seq = hdr[0], slot = seq % GM_PLAN_SLOTS;
+  uint32_t* stamp = plan + 2 + slot;
+  if (threadIdx.x == 0) st_agent(stamp, 0u);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");          // (the store has left before the table words do)
+  __syncthreads();
+  block_build_depth_map(slots, coarse, m, wsum, s_tmp, plan + 2 + GM_PLAN_SLOTS + (size_t)slot * GM_COARSE_BINS, nullptr, nullptr, 2);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    st_agent(stamp, seq);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    atomicMax(plan, seq);
+  }
+}
+
+// DIRECT: {first key, bits of (key - first key)} from the range of the keys that arrived in the slab p1[0..n).  false: the range needs
+// more than the 20 bits the sort's word has for the key, and the frame is refused (workgroup-uniform).
+__device__ __forceinline__ bool bs_arrived_key_range(const uint2* p1, uint32_t n, uint32_t* part /*[8] shared*/, uint32_t* counters,
+                                                     uint2& krange, int lane, int wave) {
+  uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
+  for (uint32_t p = threadIdx.x; p < n; p += BK_THREADS) { const uint32_t k = p1[p].x; kmin = min(kmin, k); kmax = max(kmax, k); }
+  kmin = ~wave_max_u32(~kmin); kmax = wave_max_u32(kmax);
+  if (lane == 0) { part[wave] = kmin; part[4 + wave] = kmax; }
+  __syncthreads();
+  kmin = min(min(part[0], part[1]), min(part[2], part[3]));
+  kmax = max(max(part[4], part[5]), max(part[6], part[7]));
+  __syncthreads();
+  const uint32_t width = kmax - kmin;
+  krange = make_uint2(kmin, width ? 32u - (uint32_t)__clz((int)width) : 0u);
+  if (krange.y > 20u) {
+    if (threadIdx.x == 0) counters[GM_CNT_DIRECT_FAIL] = 1u;
+    return false;
+  }
+  return true;
+}
+
+// Slow path (more equal-depth Gaussians than the LDS holds): the workgroup sorts its own range through global memory,
+// ping-ponging between p1 and p0 restricted to [start, start + n): per pass a digit histogram over the
+// range, then 1024-entry tiles in order, each ranked stably as above.  Exact, sequential, rare.
+template <bool DIRECT>
+__device__ __forceinline__ void bs_slow_path(uint2* p1, uint2* p0, uint32_t start, uint32_t n, uint32_t first_key, uint32_t low_bits,
+                                             uint32_t npass, uint32_t pb, uint32_t (*wcnt)[256], uint32_t* wsum, const uint16_t* inst16,
+                                             const uint32_t* tiles, uint32_t* order0, uint32_t* chunk_inst, uint32_t* base /*[256] shared*/,
+                                             uint32_t* tcount /*[256] shared*/, int lane, int wave) {
+  uint2* sp = p1; uint2* dp = p0;
+  for (uint32_t pass = 0; pass < npass; pass++) {
+    const uint32_t lo = pass * pb, pmask = (1u << min(pb, low_bits - lo)) - 1u;
+    base[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n; i += BK_THREADS) atomicAdd(&base[((sp[start + i].x - first_key) >> lo) & pmask], 1u);
+    __syncthreads();
+    {
+      uint32_t tot;
+      const uint32_t v = base[threadIdx.x];
+      const uint32_t e = block_exclusive_scan<BK_WAVES>(v, wsum, tot);
+      __syncthreads();
+      base[threadIdx.x] = e;
+    }
+    __syncthreads();
+    for (uint32_t t0 = 0; t0 < n; t0 += 1024u) {
+      wcnt[0][threadIdx.x] = 0; wcnt[1][threadIdx.x] = 0; wcnt[2][threadIdx.x] = 0; wcnt[3][threadIdx.x] = 0;
+      __syncthreads();
+      uint32_t kk[4], vv[4], rk[4];
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const uint32_t p = t0 + (wave * 4u + r) * 64u + lane;
+        const bool valid = p < n;
+        const uint2 kv = valid ? sp[start + p] : make_uint2(0u, 0u);
+        kk[r] = kv.x; vv[r] = kv.y;
+        const uint32_t d = ((kk[r] - first_key) >> lo) & pmask;
+        rk[r] = wave_match_rank<8>(d, valid, wcnt[wave], lane);
+      }
+      __syncthreads();
+      tcount[threadIdx.x] = wave_counts_to_offsets<BK_WAVES>(&wcnt[0][threadIdx.x], 256);
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const uint32_t p = t0 + (wave * 4u + r) * 64u + lane;
+        if (p < n) {
+          const uint32_t d = ((kk[r] - first_key) >> lo) & pmask;
+          const uint32_t dst = start + base[d] + wcnt[wave][d] + rk[r];
+          dp[dst] = make_uint2(kk[r], vv[r]);
+        }
+      }
+      __syncthreads();
+      base[threadIdx.x] += tcount[threadIdx.x];
+      __syncthreads();
+    }
+    __threadfence();                               // this workgroup's stores reach L2, its L1 forgets the old lines
+    __syncthreads();
+    uint2* t = sp; sp = dp; dp = t;
+  }
+  for (uint32_t i0 = 0; i0 < n; i0 += BK_THREADS) {
+    const uint32_t i = i0 + threadIdx.x;
+    uint32_t c = 0;
+    if (i < n) {
+      const uint32_t id = sp[start + i].y;                        // (partition path only: a slab never exceeds the LDS sort)
+      c = DIRECT ? 0u : inst16[id];
+      if (c == GM_BIN_COUNT_SAT) c = tiles[id];
+      order0[start + i] = id;
+    }
+    chunk_add(chunk_inst, start + i0 + wave * 64u, lane, c);
+  }
+}
+
 // One workgroup per bucket of the MSD partition: (key, id) pairs [start, end) of p1 -> final order.
 // Outputs: order0[start..end) = ids in (key, id) order, chunk_inst[run] += instance counts of the sorted positions of that run (from
 // inst16[id]: the records stay where the preprocess kernel wrote them and duplicate_kernel reads bins[order0[s]] itself - copying them into
@@ -574,23 +619,8 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_sort_kernel(uint32_t* __res
   __shared__ uint32_t wsum[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (DIRECT && blockIdx.x == gridDim.x - 1) {
-    // the launch's extra workgroup, beside the sorting ones: this frame's coarse histogram -> the table the stream's LATER frames place
-    // their Gaussians with (slot = this frame's sequence number % slots; stamp 0 while the words change, the sequence number after)
     static_assert(sizeof(DepthMap) <= sizeof(lkey), "the builder's map lives in the sort's key array");
-    DepthMap& m = *reinterpret_cast<DepthMap*>(lkey);
-    const uint32_t seq = hdr[0], slot = seq % GM_PLAN_SLOTS;
-    uint32_t* stamp = plan + 2 + slot;
-    if (threadIdx.x == 0) st_agent(stamp, 0u);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");          // (the store has left before the table words do)
-    __syncthreads();
-    block_build_depth_map(slots, coarse, m, wsum, dstart, plan + 2 + GM_PLAN_SLOTS + (size_t)slot * GM_COARSE_BINS, nullptr, nullptr, 2);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      st_agent(stamp, seq);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      atomicMax(plan, seq);
-    }
+    bs_publish_next_table(slots, coarse, hdr, plan, *reinterpret_cast<DepthMap*>(lkey), wsum, dstart);
     return;
   }
   const uint32_t nb = counters[GM_CNT_VISIBLE] ? counters[GM_CNT_NBUCKETS] : 0u;
@@ -606,25 +636,8 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_sort_kernel(uint32_t* __res
   const uint32_t obase = DIRECT ? bucket_start[b] : start;
   uint2 krange = make_uint2(0u, 0u);
   if (!DIRECT) krange = reinterpret_cast<const uint2*>(bmap)[b];    // {first key of the bucket, bits of (key - first key) inside it}
-  if (DIRECT) {                                                     // the range of the keys that arrived
-    uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
-    for (uint32_t p = threadIdx.x; p < n; p += BK_THREADS) { const uint32_t k = p1[p].x; kmin = min(kmin, k); kmax = max(kmax, k); }
-    kmin = ~wave_max_u32(~kmin); kmax = wave_max_u32(kmax);
-    if (lane == 0) { dstart[wave] = kmin; dstart[4 + wave] = kmax; }
-    __syncthreads();
-    kmin = min(min(dstart[0], dstart[1]), min(dstart[2], dstart[3]));
-    kmax = max(max(dstart[4], dstart[5]), max(dstart[6], dstart[7]));
-    __syncthreads();
-    const uint32_t width = kmax - kmin;
-    krange = make_uint2(kmin, width ? 32u - (uint32_t)__clz((int)width) : 0u);
-    if (krange.y > 20u) {                                           // (workgroup-uniform) the word has 20 bits for the key
-      if (threadIdx.x == 0) counters[GM_CNT_DIRECT_FAIL] = 1u;
-      return;
-    }
-  }
-  DigitSpec ds;
-  ds.sub = krange.x; ds.shift = 0; ds.mask = 0xFFFFFFFFu;
-  const uint32_t low_bits = krange.y;
+  if (DIRECT && !bs_arrived_key_range(p1, n, dstart, counters, krange, lane, wave)) return;
+  const uint32_t first_key = krange.x, low_bits = krange.y;
   const uint32_t npass = (low_bits + 7u) / 8u;
   const uint32_t pb = npass ? (low_bits + npass - 1u) / npass : 0u;
   if (n <= BS_CAP) {
@@ -638,7 +651,7 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_sort_kernel(uint32_t* __res
     for (int r = 0; r < BS_ROUNDS; r++) {
       const uint32_t p = (wave * rounds + r) * 64u + lane;
       const bool valid = (uint32_t)r < rounds && p < n;
-      key[r] = valid ? ((p1[start + p].x - ds.sub) << 12) | p : 0u;
+      key[r] = valid ? ((p1[start + p].x - first_key) << 12) | p : 0u;
     }
     // Fast path: the words are UNIQUE (position in the low bits), so any correct sort of them is THE order and no pass has to be
     // stable.  One counting split on the top <= 10 bits of the bucket's key range with LDS atomics (a key's slot inside its bin is
@@ -667,11 +680,10 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_sort_kernel(uint32_t* __res
 #pragma unroll
         for (int j = 0; j < PER; j++) { c[j] = hist[threadIdx.x * PER + j]; sum += c[j]; mx = max(mx, c[j]); }
         uint32_t tot;
-        uint32_t excl = block_exclusive_scan_256(sum, wsum, tot);
+        uint32_t excl = block_exclusive_scan<BK_WAVES>(sum, wsum, tot);
 #pragma unroll
         for (int j = 0; j < PER; j++) { hist[threadIdx.x * PER + j] = excl; excl += c[j]; }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d));
+        mx = wave_max_u32(mx);
         if (lane == 0) atomicMax(&dstart[0], mx);
       }
       __syncthreads();
@@ -737,35 +749,13 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_sort_kernel(uint32_t* __res
           const uint32_t p = (wave * rounds + r) * 64u + lane;
           const bool valid = p < n;
           const uint32_t d = (key[r] >> (12u + lo)) & pmask;
-          uint64_t peers = __ballot(valid);
-#pragma unroll
-          for (int bb = 0; bb < 8; bb++) {
-            const uint64_t bal = __ballot((d >> bb) & 1u);
-            peers &= ((d >> bb) & 1u) ? bal : ~bal;
-          }
-          const uint32_t before = lanes_below(peers);
-          const int leader = __ffsll((unsigned long long)peers) - 1;
-          uint32_t old = 0;
-          if (valid && lane == leader) {
-            old = wcnt[wave][d];
-            wcnt[wave][d] = old + __popcll(peers);
-          }
-          old = __shfl(old, leader < 0 ? 0 : leader);
-          rank[r] = old + before;
-          __builtin_amdgcn_wave_barrier();
+          rank[r] = wave_match_rank<8>(d, valid, wcnt[wave], lane);
         }
       }
       __syncthreads();
       {
-        uint32_t run = 0;
-#pragma unroll
-        for (int w = 0; w < BK_WAVES; w++) {
-          const uint32_t c = wcnt[w][threadIdx.x];
-          wcnt[w][threadIdx.x] = run;
-          run += c;
-        }
         uint32_t tot;
-        dstart[threadIdx.x] = block_exclusive_scan_256(run, wsum, tot);
+        dstart[threadIdx.x] = block_exclusive_scan<BK_WAVES>(wave_counts_to_offsets<BK_WAVES>(&wcnt[0][threadIdx.x], 256), wsum, tot);
       }
       __syncthreads();
 #pragma unroll
@@ -812,94 +802,9 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_sort_kernel(uint32_t* __res
       }
     }
   } else {
-    // Slow path (more equal-depth Gaussians than the LDS holds): the workgroup sorts its own range through global memory,
-    // ping-ponging between p1 and p0 restricted to [start, end): per pass a digit histogram over the
-    // range, then 1024-entry tiles in order, each ranked stably as above.  Exact, sequential, rare.
     __shared__ uint32_t base[256];
     __shared__ uint32_t tcount[256];
-    uint2* sp = p1; uint2* dp = p0;
-    for (uint32_t pass = 0; pass < npass; pass++) {
-      const uint32_t lo = pass * pb, pmask = (1u << min(pb, low_bits - lo)) - 1u;
-      base[threadIdx.x] = 0;
-      __syncthreads();
-      for (uint32_t i = threadIdx.x; i < n; i += BK_THREADS) atomicAdd(&base[((sp[start + i].x - ds.sub) >> lo) & pmask], 1u);
-      __syncthreads();
-      {
-        uint32_t tot;
-        const uint32_t v = base[threadIdx.x];
-        const uint32_t e = block_exclusive_scan_256(v, wsum, tot);
-        __syncthreads();
-        base[threadIdx.x] = e;
-      }
-      __syncthreads();
-      for (uint32_t t0 = 0; t0 < n; t0 += 1024u) {
-        wcnt[0][threadIdx.x] = 0; wcnt[1][threadIdx.x] = 0; wcnt[2][threadIdx.x] = 0; wcnt[3][threadIdx.x] = 0;
-        __syncthreads();
-        uint32_t kk[4], vv[4], rk[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const uint32_t p = t0 + (wave * 4u + r) * 64u + lane;
-          const bool valid = p < n;
-          const uint2 kv = valid ? sp[start + p] : make_uint2(0u, 0u);
-          kk[r] = kv.x; vv[r] = kv.y;
-          const uint32_t d = ((kk[r] - ds.sub) >> lo) & pmask;
-          uint64_t peers = __ballot(valid);
-#pragma unroll
-          for (int bb = 0; bb < 8; bb++) {
-            const uint64_t bal = __ballot((d >> bb) & 1u);
-            peers &= ((d >> bb) & 1u) ? bal : ~bal;
-          }
-          const uint32_t before = lanes_below(peers);
-          const int leader = __ffsll((unsigned long long)peers) - 1;
-          uint32_t old = 0;
-          if (valid && lane == leader) {
-            old = wcnt[wave][d];
-            wcnt[wave][d] = old + __popcll(peers);
-          }
-          old = __shfl(old, leader < 0 ? 0 : leader);
-          rk[r] = old + before;
-          __builtin_amdgcn_wave_barrier();
-        }
-        __syncthreads();
-        {
-          uint32_t run = 0;
-#pragma unroll
-          for (int w = 0; w < BK_WAVES; w++) {
-            const uint32_t c = wcnt[w][threadIdx.x];
-            wcnt[w][threadIdx.x] = run;
-            run += c;
-          }
-          tcount[threadIdx.x] = run;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const uint32_t p = t0 + (wave * 4u + r) * 64u + lane;
-          if (p < n) {
-            const uint32_t d = ((kk[r] - ds.sub) >> lo) & pmask;
-            const uint32_t dst = start + base[d] + wcnt[wave][d] + rk[r];
-            dp[dst] = make_uint2(kk[r], vv[r]);
-          }
-        }
-        __syncthreads();
-        base[threadIdx.x] += tcount[threadIdx.x];
-        __syncthreads();
-      }
-      __threadfence();                               // this workgroup's stores reach L2, its L1 forgets the old lines
-      __syncthreads();
-      uint2* t = sp; sp = dp; dp = t;
-    }
-    for (uint32_t i0 = 0; i0 < n; i0 += BK_THREADS) {
-      const uint32_t i = i0 + threadIdx.x;
-      uint32_t c = 0;
-      if (i < n) {
-        const uint32_t id = sp[start + i].y;                        // (partition path only: a slab never exceeds the LDS sort)
-        c = DIRECT ? 0u : inst16[id];
-        if (c == GM_BIN_COUNT_SAT) c = tiles[id];
-        order0[start + i] = id;
-      }
-      chunk_add(chunk_inst, start + i0 + wave * 64u, lane, c);
-    }
+    bs_slow_path<DIRECT>(p1, p0, start, n, first_key, low_bits, npass, pb, wcnt, wsum, inst16, tiles, order0, chunk_inst, base, tcount, lane, wave);
   }
   if (trace && threadIdx.x == 0) { trace[3 * b] = t_begin; trace[3 * b + 1] = wall_clock64(); trace[3 * b + 2] = n; }
 }
@@ -1023,7 +928,7 @@ __global__ __launch_bounds__(BK_THREADS) void direct_plan_kernel(const uint32_t*
   const uint32_t inst = wave_sum_u32(sl.x), vis = wave_sum_u32(sl.y);
   if (lane == 0) { s_part[wave] = inst; s_part[4 + wave] = vis; }
   uint32_t total;
-  uint32_t excl = block_exclusive_scan_256(sum, s_w, total);         // (its barrier publishes s_part too)
+  uint32_t excl = block_exclusive_scan<BK_WAVES>(sum, s_w, total);         // (its barrier publishes s_part too)
 #pragma unroll
   for (int j = 0; j < PER; j++) { bucket_start[threadIdx.x * PER + j] = excl; excl += c[j]; }
   const uint32_t visible = (s_part[4] + s_part[5]) + (s_part[6] + s_part[7]);

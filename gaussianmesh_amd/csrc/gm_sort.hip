@@ -28,6 +28,7 @@
 // walks it in 16 rounds of 64 consecutive keys (lane l <-> key round*64+l), so loads are fully
 // coalesced and rank order == index order (stability).
 #include "gm_common.h"
+#include "gm_wave.h"
 
 namespace gm {
 
@@ -54,12 +55,7 @@ __global__ __launch_bounds__(RS_THREADS) void radix_hist_kernel(const uint32_t* 
     const uint32_t idx = wbase + r * 64 + lane;
     const bool valid = idx < n;
     const uint32_t d = valid ? (keys[idx] >> shift) & mask : 0u;
-    uint64_t peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-      const uint64_t bal = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? bal : ~bal;
-    }
+    const uint64_t peers = wave_match_peers<8>(d, valid);
     if (valid && lane == __ffsll((unsigned long long)peers) - 1) atomicAdd(&h[d], (uint32_t)__popcll(peers));
   }
   __syncthreads();
@@ -109,18 +105,8 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const uint32_
       below += c < mychunk ? t : 0u;
     }
     __shared__ uint32_t wsum[RS_WAVES];
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t woff = 0;
-#pragma unroll
-    for (int w = 0; w < RS_WAVES; w++) woff += (w < wave) ? wsum[w] : 0;
-    gbase[threadIdx.x] = woff + incl - v + below + hist[(size_t)blockIdx.x * 256 + threadIdx.x];
+    uint32_t tot;
+    gbase[threadIdx.x] = block_exclusive_scan<RS_WAVES>(v, wsum, tot) + below + hist[(size_t)blockIdx.x * 256 + threadIdx.x];
   }
   __syncthreads();
 
@@ -136,49 +122,14 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const uint32_
     const uint32_t idx = wbase + r * 64 + lane;
     const bool valid = idx < n;
     const uint32_t d = (key[r] >> shift) & mask;
-    // match-any over the 8 digit bits among valid lanes
-    uint64_t peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-      const uint64_t bal = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? bal : ~bal;
-    }
-    const uint32_t before = lanes_below(peers);
-    const int leader = __ffsll((unsigned long long)peers) - 1;
-    uint32_t old = 0;
-    if (valid && lane == leader) {
-      old = wcnt[wave][d];
-      wcnt[wave][d] = old + __popcll(peers);
-    }
-    old = __shfl(old, leader < 0 ? 0 : leader);
-    rank[r] = old + before;
-    __builtin_amdgcn_wave_barrier();         // keep the per-wave LDS counter updates of successive rounds in order
+    rank[r] = wave_match_rank<8>(d, valid, wcnt[wave], lane);   // match-any over the 8 digit bits among valid lanes
   }
   __syncthreads();
-  uint32_t dcount;
-  {  // turn per-wave counts into per-wave exclusive offsets (thread d handles digit d)
-    uint32_t run = 0;
-#pragma unroll
-    for (int w = 0; w < RS_WAVES; w++) {
-      const uint32_t c = wcnt[w][threadIdx.x];
-      wcnt[w][threadIdx.x] = run;
-      run += c;
-    }
-    dcount = run;                               // keys of this workgroup with digit == threadIdx.x
-  }
-  {  // dstart[d] = exclusive scan of dcount over digits: position of digit d's run inside the sorted tile
-    uint32_t incl = dcount;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
-    if (lane == 63) wsum2[wave] = incl;
-    __syncthreads();
-    uint32_t woff = 0;
-#pragma unroll
-    for (int w = 0; w < RS_WAVES; w++) woff += (w < wave) ? wsum2[w] : 0;
-    dstart[threadIdx.x] = woff + incl - dcount;
+  {  // per-wave counts -> per-wave exclusive offsets (thread d handles digit d); dcount = keys of this workgroup with digit d;
+     // dstart[d] = exclusive scan of dcount over digits: position of digit d's run inside the sorted tile
+    const uint32_t dcount = wave_counts_to_offsets<RS_WAVES>(&wcnt[0][threadIdx.x], 256);
+    uint32_t tot;
+    dstart[threadIdx.x] = block_exclusive_scan<RS_WAVES>(dcount, wsum2, tot);
   }
   __syncthreads();
   // local scatter into LDS: the tile becomes sorted by digit (stable), so the global stores below are

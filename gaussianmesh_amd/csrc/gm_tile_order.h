@@ -5,6 +5,7 @@
 // it only moves work in time, results do not depend on it.
 #pragma once
 #include "gm_common.h"
+#include "gm_wave.h"
 
 namespace gm {
 
@@ -19,7 +20,6 @@ __device__ __forceinline__ void tile_order_by(Key key, int tiles, uint32_t* __re
                                               uint32_t* cnt /*[256] shared*/, uint32_t* wsum /*[THREADS / 64] shared*/,
                                               uint32_t* __restrict__ scratch = nullptr) {
   static_assert(THREADS >= 256 && THREADS % 64 == 0, "tile_order_block: 256 or more threads");
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x < 256) cnt[threadIdx.x] = 0;
   __syncthreads();
   auto bucket = [&](int t) { return 255u - min(key(t) >> 5, 255u); };   // bucket 0 = most work
@@ -28,18 +28,10 @@ __device__ __forceinline__ void tile_order_by(Key key, int tiles, uint32_t* __re
     if (scratch) scratch[t] = b | (r << 8);                             // (tiles <= 65536: the rank fits 24 bits)
   }
   __syncthreads();
-  uint32_t v = threadIdx.x < 256 ? cnt[threadIdx.x] : 0u, incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t u = __shfl_up(incl, d);
-    if (lane >= d) incl += u;
-  }
-  if (lane == 63) wsum[wave] = incl;
+  uint32_t total;
+  const uint32_t first = block_exclusive_scan<THREADS / 64>(threadIdx.x < 256 ? cnt[threadIdx.x] : 0u, wsum, total);
   __syncthreads();
-  uint32_t woff = 0;
-  for (int w = 0; w < wave; w++) woff += wsum[w];
-  __syncthreads();
-  if (threadIdx.x < 256) cnt[threadIdx.x] = woff + incl - v;          // exclusive start of each bucket
+  if (threadIdx.x < 256) cnt[threadIdx.x] = first;                    // exclusive start of each bucket
   __syncthreads();
   if (scratch) {                                                        // same thread, same t as in the counting pass: its own words
     for (int t = threadIdx.x; t < tiles; t += THREADS) { const uint32_t p = scratch[t]; order[cnt[p & 255u] + (p >> 8)] = (uint32_t)t; }

@@ -35,6 +35,7 @@
 // boundaries: deterministic, and no workgroup ever waits for another.
 // Conventions of gm_closest_face: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
+#include "gm_wave.h"
 #pragma clang fp contract(off)   // every product and sum rounds on its own, as the definition above says
 
 namespace gm {
@@ -133,25 +134,9 @@ size_t surface_nets_workspace_bytes(int nx, int ny, int nz) {
 
 // exclusive scan of one value per thread over the 256 threads of the workgroup (every thread calls it); total = the sum of all
 __device__ __forceinline__ uint32_t sn_block_scan(uint32_t v, uint32_t* lds, uint32_t& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) lds[wv] = x;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const uint32_t s = lds[j];
-    if (j < wv) base += s;
-    tot += s;
-  }
-  total = tot;
+  const uint32_t r = block_exclusive_scan<SN_BLOCK / 64>(v, lds, total);
   __syncthreads();               // the next call writes lds again
-  return base + x - v;
+  return r;
 }
 
 struct SnDims {

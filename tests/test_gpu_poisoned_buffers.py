@@ -13,9 +13,9 @@ route (outputs, gradients, scratch, caller workspaces) filled with the byte and 
 
 WHO WRITES WHAT FIRST (read from the kernels before anything here ran on a device; a poisoned counter that a kernel trusted would be a
 loop bound of four billion):
-  rasterizer, geometry buffer   launch_arm_counters (gm_binning.hip:49) zero-fills slots | counters | coarse | acc | chunk_inst in one
+  rasterizer, geometry buffer   launch_arm_counters (gm_binning.hip:29) zero-fills slots | counters | coarse | acc | chunk_inst in one
                                 memset (arm_words) as the first launch of every first half; the direct placement's arm_direct_kernel
-                                (gm_bucket.hip:966) does the same plus the slab's bucket counters.  The preprocess kernels write radii,
+                                (gm_bucket.hip:871) does the same plus the slab's bucket counters.  The preprocess kernels write radii,
                                 tiles_touched, bin, inst16, depth_key of EVERY row (gm_preprocess.hip:147-153: radius 0, an empty record,
                                 key 0xFFFFFFFF for a culled row).  splat, clamped and cov3D of a culled row stay UNWRITTEN: the kernel
                                 breaks out before those stores (gm_preprocess.hip:96-116, 140-142).  Nothing reads them: the ordering
@@ -24,9 +24,9 @@ loop bound of four billion):
                                 bk_hist_kernel writes hist, dmap, bmap and counters[VISIBLE / NBUCKETS / RENDERED / CMIN / CMAX],
                                 bk_scan_kernel bucket_start, bk_scatter dpairs, bucket_sort_kernel order[:V] and chunk_inst.  Every loop
                                 bound read from memory is one of those counters or bucket_start, behind their writers.
-  rasterizer, binning buffer    duplicate_kernel zeroes acc (gm_binning.hip:103) and writes pairs[0][:num_rendered], refusing when
+  rasterizer, binning buffer    duplicate_kernel zeroes acc (gm_binning.hip:83) and writes pairs[0][:num_rendered], refusing when
                                 counters[RENDERED] > capacity; the tile pass writes hist before bk_scan reads it and pairs[1].
-  rasterizer, image buffer      ranges: hipMemsetAsync (gm_api.hip:309, gm_binning.hip:326, gm_bucket.hip:1127) or every entry by bk_scan;
+  rasterizer, image buffer      ranges: hipMemsetAsync (gm_api.hip:309, gm_binning.hip:306, gm_bucket.hip:1032) or every entry by bk_scan;
                                 tile_order / tile_work by tile_order_by before the blend reads them; final_T / n_contrib by the blend for
                                 every pixel inside the image (unless image_only); epoch only read with a work hint, which writes it first.
   rasterizer, backward          grad_acc: hipMemsetAsync (gm_api.hip:590, "the only zero-fill of a backward"); preprocess_bwd writes
