@@ -294,7 +294,7 @@ static int forward_1_impl(int emission_policy, void* geom_buffer, void* binning_
   if (tiles > 65536) { set_error("too many list tiles for emission policy %d", mode); return GM_ERR_INVALID_ARG; }
   GeomState g = GeomState::from(geom_buffer, (size_t)(P > 0 ? P : 1));
   BinningState b = BinningState::from(binning_buffer, (size_t)cap);
-  const int slot = sort_final_slot(tiles);
+  const int slot = tile_sort_final_slot(tiles);
   bool order_done = false;
   if (const int stop = debug_stop_after()) {
     if (stop <= 2) return GM_OK;
@@ -476,7 +476,7 @@ static int forward_batch_impl(const char* who, int emission_policy, int K, const
   bool order_done = false;
   if (int rc = launch_tile_sort(g, b, img, (size_t)binning_capacity, g.counters + GM_CNT_RENDERED, tg.ptiles, &order_done, work_hint, debug, st, &B)) return rc;
   if (!order_done) { set_error("%s: internal: the tile pass did not produce the dispatch order", who); return GM_ERR_INVALID_ARG; }
-  return launch_render_fwd(g, b.pairs[sort_final_slot(tg.ptiles)], img, width, height, emission_policy, background, frames[0].out_color, frames[0].status_host,
+  return launch_render_fwd(g, b.pairs[tile_sort_final_slot(tg.ptiles)], img, width, height, emission_policy, background, frames[0].out_color, frames[0].status_host,
                            (flags & GM_BATCH_IMAGE_ONLY) != 0, work_hint, debug, st, false, &B,
                            aux && out_depth ? out_depth[0] : nullptr, aux && out_alpha ? out_alpha[0] : nullptr, aux, aux ? g.counters : nullptr);
 }
@@ -586,7 +586,7 @@ static int backward_impl(int emission_policy, int P, int D, int M, int R, const 
   GeomState g = GeomState::from(geom_buffer, (size_t)P);
   ImageState img = ImageState::from(image_buffer, width, height);
   BinningState b = BinningState::from(binning_buffer, (size_t)(R > 0 ? R : 0));
-  const int slot = sort_final_slot(TileGrid(width, height, a.tile_cull).ptiles);
+  const int slot = tile_sort_final_slot(TileGrid(width, height, a.tile_cull).ptiles);
   GM_HIP(hipMemsetAsync(g.grad_acc, 0, sizeof(float) * 12 * (size_t)P, a.stream));   // the only zero-fill of a backward
   if (R > 0) {
     if (!binning_buffer) { set_error("gm_backward: null binning buffer"); return GM_ERR_INVALID_ARG; }
@@ -696,7 +696,7 @@ void* gm_image_field(void* image_buffer, int W, int H, const char* name) {
 }
 void* gm_binning_field(void* binning_buffer, int64_t R, int W, int H, int emission_policy, const char* name) {
   BinningState b = BinningState::from(binning_buffer, (size_t)(R > 0 ? R : 0));
-  const int slot = sort_final_slot(TileGrid(W, H, emission_policy < 0 ? 0 : (emission_policy > 3 ? 3 : emission_policy)).ptiles);
+  const int slot = tile_sort_final_slot(TileGrid(W, H, emission_policy < 0 ? 0 : (emission_policy > 3 ? 3 : emission_policy)).ptiles);
   if (!strcmp(name, "pairs")) return b.pairs[slot];
   return nullptr;
 }
@@ -887,7 +887,7 @@ int gm_blend_weights(int emission_policy, void* geom_buffer, void* binning_buffe
   GeomState g = GeomState::from(geom_buffer, (size_t)P);
   ImageState img = ImageState::from(image_buffer, width, height);
   BinningState b = BinningState::from(binning_buffer, (size_t)binning_capacity);
-  return launch_blend_weights(g, b.pairs[sort_final_slot(tiles)], img, width, height, emission_policy, mask,
+  return launch_blend_weights(g, b.pairs[tile_sort_final_slot(tiles)], img, width, height, emission_policy, mask,
                               sums, peak, debug, reinterpret_cast<hipStream_t>(stream));
 }
 

@@ -35,6 +35,7 @@
 //   same kernels: an item's bits do not depend on the batch it rides in.  No workgroup reads what another item's wrote.
 // Conventions of gm_closest.hip: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
+#include "gm_mat3.h"
 
 namespace gm {
 
@@ -80,43 +81,6 @@ size_t arap_workspace_bytes(int Vm) {
   return (size_t)k.end + 256;
 }
 
-__device__ __forceinline__ void arap_cross3(const double* a, const double* b, double* o) {
-  o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// eigen-decomposition of a symmetric 3x3 (cyclic Jacobi): gm_mesh.hip's jacobi3 line for line (sweeps and threshold included), restated
-// because sharing it would have to leave mesh_rs_kernel's machine code unchanged.  A -> diagonal in place, V columns = eigenvectors
-__device__ __forceinline__ void arap_jacobi3(double A[3][3], double V[3][3]) {
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) V[i][j] = i == j ? 1.0 : 0.0;
-  const double scale = fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]) + 1e-300;
-  for (int sweep = 0; sweep < 10; sweep++) {
-    const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-    if (off <= 1e-16 * scale) break;
-#pragma unroll
-    for (int pq = 0; pq < 3; pq++) {
-      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-      const double apq = A[p][q];
-      if (fabs(apq) <= 1e-300) continue;
-      const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-      const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-      const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-      const int r = 3 - p - q;
-      const double arp = A[r][p], arq = A[r][q];
-      A[p][p] -= t * apq; A[q][q] += t * apq; A[p][q] = A[q][p] = 0.0;
-      A[r][p] = A[p][r] = cs * arp - sn * arq;
-      A[r][q] = A[q][r] = sn * arp + cs * arq;
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        const double vp = V[k][p], vq = V[k][q];
-        V[k][p] = cs * vp - sn * vq; V[k][q] = sn * vp + cs * vq;
-      }
-    }
-  }
-}
-
 // the proper rotation closest to F (max tr(Q^T F)); identity for rank <= 1
 __device__ __forceinline__ void arap_rotation(const double F[3][3], double Q[3][3]) {
 #pragma unroll
@@ -128,7 +92,7 @@ __device__ __forceinline__ void arap_rotation(const double F[3][3], double Q[3][
   for (int i = 0; i < 3; i++)
 #pragma unroll
     for (int j = 0; j < 3; j++) C[i][j] = F[0][i] * F[0][j] + F[1][i] * F[1][j] + F[2][i] * F[2][j];   // F^T F
-  arap_jacobi3(C, E);
+  jacobi3(C, E);
   double FE[3][3], sig[3];                                        // F E and its column lengths: the singular values (never sqrt(lambda))
 #pragma unroll
   for (int i = 0; i < 3; i++)
@@ -151,7 +115,7 @@ __device__ __forceinline__ void arap_rotation(const double F[3][3], double Q[3][
   if (!(sig[1] > 1e-12 * sig[0])) return;                         // a line or a point (or F = 0, or not finite): no rotation is singled out
   const double ep[3] = {E[0][0], E[1][0], E[2][0]}, eq[3] = {E[0][1], E[1][1], E[2][1]};
   double em[3], up[3], uq[3], um[3];
-  arap_cross3(ep, eq, em);                                        // right-handed (ep, eq, em) and (up, uq, um): det Q = +1
+  cross3(ep, eq, em);                                        // right-handed (ep, eq, em) and (up, uq, um): det Q = +1
   double dpq = 0.0, lq = 0.0;
 #pragma unroll
   for (int i = 0; i < 3; i++) { up[i] = FE[i][0] / sig[0]; dpq += up[i] * FE[i][1]; }
@@ -160,15 +124,12 @@ __device__ __forceinline__ void arap_rotation(const double F[3][3], double Q[3][
   lq = sqrt(lq);
 #pragma unroll
   for (int i = 0; i < 3; i++) uq[i] /= lq;
-  arap_cross3(up, uq, um);
+  cross3(up, uq, um);
 #pragma unroll
   for (int i = 0; i < 3; i++)
 #pragma unroll
     for (int j = 0; j < 3; j++) Q[i][j] = up[i] * ep[j] + uq[i] * eq[j] + um[i] * em[j];
 }
-
-// a column index forced into [0, Vm): an index outside cannot be reported without a read-back, but it must not fault
-__device__ __forceinline__ int arap_col(const int* cols, int k, int Vm) { return min(max(cols[k], 0), Vm - 1); }
 
 // sum of N values over the workgroup of W waves, the same bits in every thread: wave butterfly, W partials in LDS, fixed-order sum.
 // The barrier inside is reached by all threads; `part` must not be the array of the previous call (a slow thread may still read it).
@@ -224,7 +185,7 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_local_kernel(int Vm, co
   const double pi[3] = {(double)V0[3 * (size_t)i], (double)V0[3 * (size_t)i + 1], (double)V0[3 * (size_t)i + 2]};
   const double xi[3] = {x[i], x[(size_t)Vm + i], x[2 * (size_t)Vm + i]};
   for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) {
-    const int j = arap_col(cols, k, Vm);
+    const int j = clamp_index(cols[k], Vm);
     const double w = weights[k];
     double e[3], d[3];
 #pragma unroll
@@ -257,7 +218,7 @@ __global__ __launch_bounds__(ARAP_THREADS) void arap_energy_kernel(int Vm, const
       for (int k = 0; k < 3; k++) Ri[c][k] = R[((size_t)c * Vm + i) * 3 + k];
     double e_i = 0.0;
     for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) {
-      const int j = arap_col(cols, k, Vm);
+      const int j = clamp_index(cols[k], Vm);
       double e[3];
 #pragma unroll
       for (int c = 0; c < 3; c++) e[c] = (double)V0[3 * (size_t)i + c] - (double)V0[3 * (size_t)j + c];
@@ -301,7 +262,7 @@ __global__ __launch_bounds__(ARAP_THREADS) void arap_global_kernel(int Vm, const
       const double xi = x[i];
       double b = 0.0, Lx = 0.0, bc = 0.0;
       for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) {
-        const int j = arap_col(cols, k, Vm);
+        const int j = clamp_index(cols[k], Vm);
         const double w = weights[k], xj = x[j];
         double t = 0.0;
 #pragma unroll
@@ -327,7 +288,7 @@ __global__ __launch_bounds__(ARAP_THREADS) void arap_global_kernel(int Vm, const
       if (!free_row[i]) continue;
       const double pi = p[i];
       double qi = 0.0;
-      for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) qi += weights[k] * (pi - p[arap_col(cols, k, Vm)]);
+      for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) qi += weights[k] * (pi - p[clamp_index(cols[k], Vm)]);
       q[i] = qi;
       s1[0] += pi * qi;
     }
@@ -497,7 +458,7 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_rhs_kernel(int Vm,
         for (int a = 0; a < 3; a++) Ri[c][a] = R[((size_t)c * Vm + i) * 3 + a];
       }
       for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) {
-        const int j = arap_col(cols, k, Vm);
+        const int j = clamp_index(cols[k], Vm);
         const double wk = weights[k];
         const int held = !free_row[j];
         double e[3];
@@ -563,7 +524,7 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_product_kernel(int
 #pragma unroll
       for (int t = 0; t < ARAP_EDGE_BATCH; t++) {
         const int k = min(kb + t, k1 - 1);
-        j[t] = arap_col(cols, k, Vm); wk[t] = weights[k];
+        j[t] = clamp_index(cols[k], Vm); wk[t] = weights[k];
       }
 #pragma unroll
       for (int t = 0; t < ARAP_EDGE_BATCH; t++)

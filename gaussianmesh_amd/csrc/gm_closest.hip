@@ -64,6 +64,8 @@
 //
 // Conventions of gm_knn_nearest: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
+#include "gm_spatial.h"
+#include "gm_wave.h"
 #include <cfloat>
 #pragma clang fp contract(off)   // every product and sum rounds on its own, as the definition above says
 
@@ -73,42 +75,20 @@ namespace gm {
 #define CF_SUPER 64      // boxes per super-box
 #define CF_WIN 4         // sorted faces on either side of a query's own Morton code evaluated first
 
-// workgroups of the radix sort for up to n keys: its tile grows with n, so sort_blocks drops behind each threshold - the largest count below n
-static inline size_t cf_sort_blocks(size_t n) {
-  size_t b = sort_blocks(n);
-  if (n > GM_SORT_SMALL_N && sort_blocks(GM_SORT_SMALL_N) > b) b = sort_blocks(GM_SORT_SMALL_N);
-  if (n > GM_SORT_MID_N && sort_blocks(GM_SORT_MID_N) > b) b = sort_blocks(GM_SORT_MID_N);
-  return b;
-}
-
 struct CfWs {
-  float* bbox_partial;   // [256][6]
-  float* bbox;           // [8] min xyz, max xyz of the vertices
-  uint32_t* fkeys[2];
-  uint32_t* fidx[2];
-  uint32_t* qkeys[2];
-  uint32_t* qidx[2];
-  uint32_t* hist;
-  uint32_t* digit_total;
+  MortonWs front;        // bbox of the vertices; sort scratch for the larger of the two sets
+  MortonSet fset, qset;
   float4* recs;          // [F][3] ax ay az bx | by bz cx cy | cz index(bits) 0 0, in Morton order
   float4* boxes;         // [nboxes][2] lo xyz, tau | hi xyz, M
   float4* sboxes;        // [nsuper][2]
   char* end;
   static CfWs from(void* ws, size_t N, size_t F) {
     char* p = reinterpret_cast<char*>(ws);
-    // histogram rows of the larger sort, made monotonic in N and in F (cf_sort_blocks)
-    const size_t hb = cf_sort_blocks(N) > cf_sort_blocks(F) ? cf_sort_blocks(N) : cf_sort_blocks(F);
-    const size_t dc = 256 * ((hb + GM_SORT_CHUNK - 1) / GM_SORT_CHUNK);
     const size_t nboxes = (F + CF_BOX - 1) / CF_BOX;
     CfWs k;
-    k.bbox_partial = carve<float>(p, 256 * 6);
-    k.bbox = carve<float>(p, 8);
-    k.fkeys[0] = carve<uint32_t>(p, F); k.fkeys[1] = carve<uint32_t>(p, F);
-    k.fidx[0] = carve<uint32_t>(p, F); k.fidx[1] = carve<uint32_t>(p, F);
-    k.qkeys[0] = carve<uint32_t>(p, N); k.qkeys[1] = carve<uint32_t>(p, N);
-    k.qidx[0] = carve<uint32_t>(p, N); k.qidx[1] = carve<uint32_t>(p, N);
-    k.hist = carve<uint32_t>(p, 256 * hb);
-    k.digit_total = carve<uint32_t>(p, dc);
+    k.front = MortonWs::carve_from(p, N > F ? N : F);
+    k.fset = MortonSet::carve_from(p, F);
+    k.qset = MortonSet::carve_from(p, N);
     k.recs = carve<float4>(p, 3 * F);
     k.boxes = carve<float4>(p, 2 * nboxes);
     k.sboxes = carve<float4>(p, 2 * ((nboxes + CF_SUPER - 1) / CF_SUPER));
@@ -122,88 +102,16 @@ size_t closest_face_workspace_bytes(int N, int F) {
   return (size_t)k.end + 256;
 }
 
-__device__ __forceinline__ float cf_wave_min(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d));
-  return v;
-}
-__device__ __forceinline__ float cf_wave_max(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
-  return v;
-}
-
-// bounding box of the vertices: per-workgroup partials, then one workgroup
-__global__ __launch_bounds__(256) void cf_bbox_partial(int n, const float* __restrict__ pts, float* __restrict__ partial) {
-  __shared__ float sm[4][6];
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
-#pragma unroll
-    for (int k = 0; k < 3; k++) { const float v = pts[3 * (size_t)i + k]; mn[k] = fminf(mn[k], v); mx[k] = fmaxf(mx[k], v); }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; k++) { mn[k] = cf_wave_min(mn[k]); mx[k] = cf_wave_max(mx[k]); }
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < 3; k++) { sm[wave][k] = mn[k]; sm[wave][3 + k] = mx[k]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    float v = sm[0][threadIdx.x];
-    for (int w = 1; w < 4; w++) v = threadIdx.x < 3 ? fminf(v, sm[w][threadIdx.x]) : fmaxf(v, sm[w][threadIdx.x]);
-    partial[6 * blockIdx.x + threadIdx.x] = v;
-  }
-}
-__global__ __launch_bounds__(64) void cf_bbox_final(int nb, const float* __restrict__ partial, float* __restrict__ bbox) {
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (int i = threadIdx.x; i < nb; i += 64)
-#pragma unroll
-    for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], partial[6 * i + k]); mx[k] = fmaxf(mx[k], partial[6 * i + 3 + k]); }
-#pragma unroll
-  for (int k = 0; k < 3; k++) { mn[k] = cf_wave_min(mn[k]); mx[k] = cf_wave_max(mx[k]); }
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < 3; k++) { bbox[k] = mn[k]; bbox[3 + k] = mx[k]; }
-}
-
-__device__ __forceinline__ uint32_t cf_spread(uint32_t x) {      // 10 bits -> every third bit
-  x = (x | (x << 16)) & 0x030000FF;
-  x = (x | (x << 8)) & 0x0300F00F;
-  x = (x | (x << 4)) & 0x030C30C3;
-  x = (x | (x << 2)) & 0x09249249;
-  return x;
-}
-// 30-bit Morton code against the vertices' bounding box; a point outside is clamped onto it, a flat axis maps to 0 (as nn_morton_code)
-__device__ __forceinline__ uint32_t cf_morton_code(float x, float y, float z, const float* bb) {
-  const float v[3] = {x, y, z};
-  uint32_t c[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float ext = bb[3 + k] - bb[k];
-    float t = ext > 0.f ? (v[k] - bb[k]) / ext : 0.f;
-    t = fminf(fmaxf(t, 0.f), 1.f);               // (NaN -> 0)
-    c[k] = cf_spread((uint32_t)(t * ((1 << 10) - 1)));
-  }
-  return c[0] | (c[1] << 1) | (c[2] << 2);
-}
-
-__global__ __launch_bounds__(256) void cf_point_morton(int n, const float* __restrict__ pts, const float* __restrict__ bbox, uint32_t* __restrict__ codes) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  codes[i] = cf_morton_code(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2], bbox);
-}
-
-// a face's vertex index, forced into [0, Vm): an index outside cannot be reported without a read-back, but it must not fault
-__device__ __forceinline__ size_t cf_vertex(const int* faces, size_t slot, int Vm) { return (size_t)min(max(faces[slot], 0), Vm - 1); }
-
+// Morton code of a face: that of its centroid against the vertices' bounding box
 __global__ __launch_bounds__(256) void cf_face_morton(int F, int Vm, const float* __restrict__ verts, const int* __restrict__ faces,
                                                       const float* __restrict__ bbox, uint32_t* __restrict__ codes) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= F) return;
-  const size_t ia = cf_vertex(faces, 3 * (size_t)f, Vm), ib = cf_vertex(faces, 3 * (size_t)f + 1, Vm), ic = cf_vertex(faces, 3 * (size_t)f + 2, Vm);
+  const size_t ia = face_vertex(faces, 3 * (size_t)f, Vm), ib = face_vertex(faces, 3 * (size_t)f + 1, Vm), ic = face_vertex(faces, 3 * (size_t)f + 2, Vm);
   float c[3];
 #pragma unroll
   for (int k = 0; k < 3; k++) c[k] = ((verts[3 * ia + k] + verts[3 * ib + k]) + verts[3 * ic + k]) / 3.0f;
-  codes[f] = cf_morton_code(c[0], c[1], c[2], bbox);
+  codes[f] = morton_code30(c[0], c[1], c[2], bbox);
 }
 
 // one wave per box: the sorted face records, and the box record (lo, tau | hi, M)
@@ -214,7 +122,7 @@ __global__ __launch_bounds__(CF_BOX) void cf_gather_boxes(int F, int Vm, const f
   const int i = blockIdx.x * CF_BOX + threadIdx.x;
   if (i < F) {
     const uint32_t g = idx[i];
-    const size_t ia = cf_vertex(faces, 3 * (size_t)g, Vm), ib = cf_vertex(faces, 3 * (size_t)g + 1, Vm), ic = cf_vertex(faces, 3 * (size_t)g + 2, Vm);
+    const size_t ia = face_vertex(faces, 3 * (size_t)g, Vm), ib = face_vertex(faces, 3 * (size_t)g + 1, Vm), ic = face_vertex(faces, 3 * (size_t)g + 2, Vm);
     float a[3], b[3], c[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -233,8 +141,8 @@ __global__ __launch_bounds__(CF_BOX) void cf_gather_boxes(int F, int Vm, const f
     if (!(tau < FLT_MAX)) tau = INFINITY;        // no area (S == 0, or 0 / 0 for three equal vertices): the box is never skipped
   }
 #pragma unroll
-  for (int k = 0; k < 3; k++) { mn[k] = cf_wave_min(mn[k]); mx[k] = cf_wave_max(mx[k]); }
-  tau = cf_wave_max(tau);
+  for (int k = 0; k < 3; k++) { mn[k] = wave_min_f32(mn[k]); mx[k] = wave_max_f32(mx[k]); }
+  tau = wave_max_f32(tau);
   if (threadIdx.x == 0) {
     float M = 0.f;
 #pragma unroll
@@ -255,8 +163,8 @@ __global__ __launch_bounds__(CF_SUPER) void cf_super_boxes(int nboxes, const flo
     mx[0] = hi.x; mx[1] = hi.y; mx[2] = hi.z; M = hi.w;
   }
 #pragma unroll
-  for (int k = 0; k < 3; k++) { mn[k] = cf_wave_min(mn[k]); mx[k] = cf_wave_max(mx[k]); }
-  tau = cf_wave_max(tau); M = cf_wave_max(M);
+  for (int k = 0; k < 3; k++) { mn[k] = wave_min_f32(mn[k]); mx[k] = wave_max_f32(mx[k]); }
+  tau = wave_max_f32(tau); M = wave_max_f32(M);
   if (threadIdx.x == 0) {
     sboxes[2 * blockIdx.x] = make_float4(mn[0], mn[1], mn[2], tau);
     sboxes[2 * blockIdx.x + 1] = make_float4(mx[0], mx[1], mx[2], M);
@@ -318,13 +226,8 @@ __global__ __launch_bounds__(256) void cf_query(int N, const float* __restrict__
   const float pinf = fmaxf(fabsf(px), fmaxf(fabsf(py), fabsf(pz)));
   float best = INFINITY, bqx = __uint_as_float(0x7FC00000u), bqy = bqx, bqz = bqx;     // (an infinite dist2 is still taken, lowest index first)
   uint32_t bid = 0xFFFFFFFFu;
-  // start: the sorted faces around the query's own Morton code
-  const uint32_t code = cf_morton_code(px, py, pz, bbox);
-  int lo = 0, hi = F;                              // lower_bound
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (fkeys[mid] < code) lo = mid + 1; else hi = mid;
-  }
+  // start: the sorted faces around the query's own Morton code (a query outside the vertices' box is clamped onto it)
+  const int lo = morton_lower_bound(fkeys, F, morton_code30(px, py, pz, bbox));
   const int j0 = max(0, lo - CF_WIN), j1 = min(F, lo + CF_WIN);
   for (int j = j0; j < j1; j++) cf_eval(px, py, pz, recs[3 * (size_t)j], recs[3 * (size_t)j + 1], recs[3 * (size_t)j + 2], best, bid, bqx, bqy, bqz);
   for (int sb = 0; sb < nsuper; sb++) {
@@ -352,22 +255,17 @@ int launch_closest_face(int N, const float* points, int Vm, const float* vertice
   const size_t need = closest_face_workspace_bytes(N, F);
   if (ws_bytes < need) { set_error("gm_closest_face: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
   CfWs k = CfWs::from(ws, (size_t)N, (size_t)F);
-  const int nb = min(256, (Vm + 255) / 256);
-  hipLaunchKernelGGL(cf_bbox_partial, dim3(nb), dim3(256), 0, s, Vm, vertices, k.bbox_partial);
-  hipLaunchKernelGGL(cf_bbox_final, dim3(1), dim3(64), 0, s, nb, k.bbox_partial, k.bbox);
-  hipLaunchKernelGGL(cf_face_morton, dim3((F + 255) / 256), dim3(256), 0, s, F, Vm, vertices, faces, k.bbox, k.fkeys[0]);
-  hipLaunchKernelGGL(cf_point_morton, dim3((N + 255) / 256), dim3(256), 0, s, N, points, k.bbox, k.qkeys[0]);
-  GM_HIP(hipGetLastError());
-  // 30-bit keys: 4 passes of 8 bits, the result lands back in slot 0
-  int rc = radix_sort_pairs(k.fkeys, k.fidx, k.hist, k.digit_total, (size_t)F, 30, true, 0, s);
-  if (rc) return rc;
-  rc = radix_sort_pairs(k.qkeys, k.qidx, k.hist, k.digit_total, (size_t)N, 30, true, 0, s);
-  if (rc) return rc;
+  if (int rc = launch_point_bbox(Vm, vertices, k.front.bbox_partial, k.front.bbox, s)) return rc;
+  hipLaunchKernelGGL(cf_face_morton, dim3((F + 255) / 256), dim3(256), 0, s, F, Vm, vertices, faces, k.front.bbox, k.fset.keys[0]);
+  if (int rc = launch_point_morton(N, points, k.front.bbox, k.qset.keys[0], s)) return rc;
+  MortonSorted f, q;
+  if (int rc = morton_sort(k.fset, k.front, (size_t)F, &f, s)) return rc;
+  if (int rc = morton_sort(k.qset, k.front, (size_t)N, &q, s)) return rc;
   const int nboxes = (F + CF_BOX - 1) / CF_BOX, nsuper = (nboxes + CF_SUPER - 1) / CF_SUPER;
-  hipLaunchKernelGGL(cf_gather_boxes, dim3(nboxes), dim3(CF_BOX), 0, s, F, Vm, vertices, faces, k.fidx[0], k.recs, k.boxes);
+  hipLaunchKernelGGL(cf_gather_boxes, dim3(nboxes), dim3(CF_BOX), 0, s, F, Vm, vertices, faces, f.idx, k.recs, k.boxes);
   hipLaunchKernelGGL(cf_super_boxes, dim3(nsuper), dim3(CF_SUPER), 0, s, nboxes, k.boxes, k.sboxes);
-  hipLaunchKernelGGL(cf_query, dim3((N + 255) / 256), dim3(256), 0, s, N, points, k.qidx[0], F, k.fkeys[0], k.recs, k.boxes, nboxes, k.sboxes,
-                     nsuper, k.bbox, out_d2, out_face, out_closest);
+  hipLaunchKernelGGL(cf_query, dim3((N + 255) / 256), dim3(256), 0, s, N, points, q.idx, F, f.keys, k.recs, k.boxes, nboxes, k.sboxes,
+                     nsuper, k.front.bbox, out_d2, out_face, out_closest);
   GM_HIP(hipGetLastError());
   return 0;
 }

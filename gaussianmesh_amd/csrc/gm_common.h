@@ -68,6 +68,42 @@ static inline size_t sort_blocks(size_t n) {
 #define GM_SORT_CHUNK 32             // histogram rows (workgroups) per scan workgroup
 // counters of the per-chunk digit totals: [chunks][256]
 static inline size_t sort_chunk_counters(size_t n) { return 256 * ((sort_blocks(n) + GM_SORT_CHUNK - 1) / GM_SORT_CHUNK); }
+// workgroups of the radix sort for UP TO n keys, monotonic in n: the tile grows with n, so sort_blocks drops behind each threshold
+static inline size_t sort_blocks_upto(size_t n) {
+  size_t b = sort_blocks(n);
+  if (n > GM_SORT_SMALL_N && sort_blocks(GM_SORT_SMALL_N) > b) b = sort_blocks(GM_SORT_SMALL_N);
+  if (n > GM_SORT_MID_N && sort_blocks(GM_SORT_MID_N) > b) b = sort_blocks(GM_SORT_MID_N);
+  return b;
+}
+
+// Workspace of the Morton front end of the geometry queries (gm_spatial.hip): the bounding box, and the scratch of one radix sort at a
+// time of up to n_max keys; every sorted set (the points, the queries) has its own ping-pong pair of (code, index) arrays.
+#define GM_BBOX_PARTIALS 1024
+struct MortonSet {                     // codes go into keys[0]; morton_sort says where the sorted arrays are
+  uint32_t* keys[2]; uint32_t* idx[2];
+  static MortonSet carve_from(char*& p, size_t n) {
+    MortonSet m;
+    m.keys[0] = carve<uint32_t>(p, n); m.keys[1] = carve<uint32_t>(p, n);
+    m.idx[0] = carve<uint32_t>(p, n); m.idx[1] = carve<uint32_t>(p, n);
+    return m;
+  }
+};
+struct MortonSorted { const uint32_t* keys; const uint32_t* idx; };      // what morton_sort hands back: codes ascending, original indices
+struct MortonWs {
+  float* bbox_partial;   // [GM_BBOX_PARTIALS][6]
+  float* bbox;           // [8] min xyz, max xyz
+  uint32_t* hist;
+  uint32_t* digit_total;
+  static MortonWs carve_from(char*& p, size_t n_max) {
+    const size_t hb = sort_blocks_upto(n_max);
+    MortonWs w;
+    w.bbox_partial = carve<float>(p, GM_BBOX_PARTIALS * 6);
+    w.bbox = carve<float>(p, 8);
+    w.hist = carve<uint32_t>(p, 256 * hb);
+    w.digit_total = carve<uint32_t>(p, 256 * ((hb + GM_SORT_CHUNK - 1) / GM_SORT_CHUNK));
+    return w;
+  }
+};
 
 // ordering of a forward (gm_bucket.hip)
 #define GM_BUCKET_BITS 11            // MSD partition of the depth keys into <= 2048 buckets; also the digit of the one-pass tile sort
@@ -322,7 +358,7 @@ static inline int tile_bits(int tiles) {      // bits needed to hold tile ids 0.
 }
 // which ping-pong slot holds the tile-sorted instance stream (launch_tile_sort: one 11-bit pass for up to 2048 list tiles,
 // two 8-bit passes above)
-static inline int sort_final_slot(int tiles) { return tiles <= (1 << GM_BUCKET_BITS) ? 1 : 0; }
+static inline int tile_sort_final_slot(int tiles) { return tiles <= (1 << GM_BUCKET_BITS) ? 1 : 0; }
 
 // Emission policy (gm_set_tile_culling): 0 = the reference's lists (every tile of the rectangle, 16-px tiles);
 // 1 = exact culling, lists per 16-px tile; 2 / 3 = exact culling, lists per 32- / 64-px PARENT tile (the instance
@@ -366,6 +402,13 @@ int launch_preprocess_bwd(const RasterArgs& a, GeomState& g, const int* radii, f
 // used for grid sizing.  iota_values: pass 1 synthesises values = index instead of reading vals[0].
 int radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_total, size_t n,
                      int bits, bool iota_values, int debug, hipStream_t s);
+static inline int radix_final_slot(int bits) { return ((bits + 7) / 8) & 1; }      // the slot that holds the result: one flip per 8-bit pass
+// gm_spatial.hip, the front end of gm_knn / gm_knn_nearest / gm_closest_face.  launch_point_bbox: the true bounding box of n points
+// (n >= 1) -> bbox, through partial [GM_BBOX_PARTIALS][6]; launch_point_morton: codes[i] = morton_code30(pts[i], bbox) (gm_spatial.h);
+// morton_sort: set.keys[0] holds n codes, *out the sorted codes and the permutation - the caller never picks a ping-pong slot
+int launch_point_bbox(int n, const float* pts, float* partial, float* bbox, hipStream_t s);
+int launch_point_morton(int n, const float* pts, const float* bbox, uint32_t* codes, hipStream_t s);
+int morton_sort(MortonSet& set, const MortonWs& w, size_t n, MortonSorted* out, hipStream_t s);
 
 // (depth, id) order of the visible Gaussians + per-bucket instance totals; counters[GM_CNT_RENDERED] = num_rendered.
 // num_rendered_host (optional, pinned): receives the count by a stream-ordered copy issued as soon as it is known;
@@ -529,5 +572,10 @@ size_t mesh_collapse_round_workspace_bytes(int Vm);
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
+
+// an index forced into [0, n): one outside cannot be reported without a read-back, but it must not fault (no meaning for such an entry)
+__device__ __forceinline__ int clamp_index(int v, int n) { return min(max(v, 0), n - 1); }
+// a face's vertex index, forced into [0, Vm)
+__device__ __forceinline__ size_t face_vertex(const int* faces, size_t slot, int Vm) { return (size_t)clamp_index(faces[slot], Vm); }
 
 }  // namespace gm

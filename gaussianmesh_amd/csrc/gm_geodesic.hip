@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void gd_sweep(int Vm, const int* __restrict__ 
     float best = dv;
     const int e1 = row_offsets[v + 1];
     for (int e = row_offsets[v]; e < e1; e++) {
-      const int u = min(max(cols[e], 0), Vm - 1);         // forced into range: no fault, no meaning
+      const int u = clamp_index(cols[e], Vm);
       const float cand = gd_load(row + u) + lengths[e];
       if (cand <= max_distance && cand < best) best = cand;
     }

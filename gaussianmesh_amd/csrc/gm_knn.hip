@@ -8,6 +8,8 @@
 // Differences by design: no internal allocation (caller workspace), no host readback of the bounding box
 // (it stays on the device), our own radix sort (gm_sort.hip).
 #include "gm_common.h"
+#include "gm_spatial.h"
+#include "gm_wave.h"
 #include <cfloat>
 #pragma clang fp contract(off)   // squared distances evaluated exactly as the CPU oracle does
 
@@ -16,23 +18,15 @@ namespace gm {
 #define KNN_BOX 1024
 
 struct KnnWs {
-  float* bbox_partial;   // [1024][6]
-  float* bbox;           // [6] min xyz, max xyz (reduction seeded with 0 like the reference, simple_knn.cu:191-200)
-  uint32_t* keys[2];
-  uint32_t* idx[2];
-  uint32_t* hist;
-  uint32_t* digit_total;
+  MortonWs front;        // bbox = the true bounding box (the reference seeds its reduction with 0, simple_knn.cu:191-200: no output depends on it)
+  MortonSet set;
   float* boxes;          // [nboxes][6]
   char* end;
   static KnnWs from(void* ws, size_t P) {
     char* p = reinterpret_cast<char*>(ws);
     KnnWs k;
-    k.bbox_partial = carve<float>(p, 1024 * 6);
-    k.bbox = carve<float>(p, 8);
-    k.keys[0] = carve<uint32_t>(p, P); k.keys[1] = carve<uint32_t>(p, P);
-    k.idx[0] = carve<uint32_t>(p, P); k.idx[1] = carve<uint32_t>(p, P);
-    k.hist = carve<uint32_t>(p, 256 * sort_blocks(P));
-    k.digit_total = carve<uint32_t>(p, sort_chunk_counters(P));
+    k.front = MortonWs::carve_from(p, P);
+    k.set = MortonSet::carve_from(p, P);
     k.boxes = carve<float>(p, 6 * ((P + KNN_BOX - 1) / KNN_BOX));
     k.end = p;
     return k;
@@ -42,79 +36,6 @@ struct KnnWs {
 size_t knn_workspace_bytes(int P) {
   KnnWs k = KnnWs::from(nullptr, (size_t)(P > 0 ? P : 1));
   return (size_t)k.end + 256;
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
-  return v;
-}
-
-// block-wide min/max of 6 values; result valid in thread 0
-__device__ __forceinline__ void block_minmax(float* mn, float* mx, float (*sm)[6]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; k++) { mn[k] = wave_min(mn[k]); mx[k] = wave_max(mx[k]); }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { sm[wave][k] = mn[k]; sm[wave][3 + k] = mx[k]; }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < (int)(blockDim.x >> 6); w++)
-#pragma unroll
-      for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], sm[w][k]); mx[k] = fmaxf(mx[k], sm[w][3 + k]); }
-  }
-}
-
-__global__ __launch_bounds__(256) void knn_bbox_partial(int P, const float* __restrict__ pts, float* __restrict__ partial) {
-  __shared__ float sm[4][6];
-  float mn[3] = {0.f, 0.f, 0.f}, mx[3] = {0.f, 0.f, 0.f};
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < P; i += gridDim.x * 256) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { const float v = pts[3 * (size_t)i + k]; mn[k] = fminf(mn[k], v); mx[k] = fmaxf(mx[k], v); }
-  }
-  block_minmax(mn, mx, sm);
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < 3; k++) { partial[6 * blockIdx.x + k] = mn[k]; partial[6 * blockIdx.x + 3 + k] = mx[k]; }
-}
-
-__global__ __launch_bounds__(256) void knn_bbox_final(int nb, const float* __restrict__ partial, float* __restrict__ bbox) {
-  __shared__ float sm[4][6];
-  float mn[3] = {0.f, 0.f, 0.f}, mx[3] = {0.f, 0.f, 0.f};
-  for (int i = threadIdx.x; i < nb; i += 256)
-#pragma unroll
-    for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], partial[6 * i + k]); mx[k] = fmaxf(mx[k], partial[6 * i + 3 + k]); }
-  block_minmax(mn, mx, sm);
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < 3; k++) { bbox[k] = mn[k]; bbox[3 + k] = mx[k]; }
-}
-
-// simple_knn.cu:45-61
-__device__ __forceinline__ uint32_t prep_morton(uint32_t x) {
-  x = (x | (x << 16)) & 0x030000FF;
-  x = (x | (x << 8)) & 0x0300F00F;
-  x = (x | (x << 4)) & 0x030C30C3;
-  x = (x | (x << 2)) & 0x09249249;
-  return x;
-}
-
-__global__ __launch_bounds__(256) void knn_morton(int P, const float* __restrict__ pts, const float* __restrict__ bbox,
-                                                  uint32_t* __restrict__ codes) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  const float mnx = bbox[0], mny = bbox[1], mnz = bbox[2], mxx = bbox[3], mxy = bbox[4], mxz = bbox[5];
-  const uint32_t x = prep_morton((uint32_t)(((pts[3 * (size_t)i] - mnx) / (mxx - mnx)) * ((1 << 10) - 1)));
-  const uint32_t y = prep_morton((uint32_t)(((pts[3 * (size_t)i + 1] - mny) / (mxy - mny)) * ((1 << 10) - 1)));
-  const uint32_t z = prep_morton((uint32_t)(((pts[3 * (size_t)i + 2] - mnz) / (mxz - mnz)) * ((1 << 10) - 1)));
-  codes[i] = x | (y << 1) | (z << 2);
 }
 
 // one workgroup per box of 1024 Morton-consecutive points (simple_knn.cu:78-117)
@@ -131,7 +52,7 @@ __global__ __launch_bounds__(256) void knn_box_minmax(int P, const float* __rest
       for (int k = 0; k < 3; k++) { const float v = pts[3 * (size_t)g + k]; mn[k] = fminf(mn[k], v); mx[k] = fmaxf(mx[k], v); }
     }
   }
-  block_minmax(mn, mx, sm);
+  block_minmax3(mn, mx, sm);
   if (threadIdx.x == 0)
 #pragma unroll
     for (int k = 0; k < 3; k++) { boxes[6 * blockIdx.x + k] = mn[k]; boxes[6 * blockIdx.x + 3 + k] = mx[k]; }
@@ -187,17 +108,13 @@ int launch_knn(int P, const float* points, float* meanDists, void* ws, size_t ws
   if (P <= 0) return 0;
   if (ws_bytes < knn_workspace_bytes(P)) { set_error("gm_knn: workspace too small (%zu < %zu)", ws_bytes, knn_workspace_bytes(P)); return 3; }
   KnnWs k = KnnWs::from(ws, (size_t)P);
-  const int nb = min(1024, (P + 255) / 256);
-  hipLaunchKernelGGL(knn_bbox_partial, dim3(nb), dim3(256), 0, s, P, points, k.bbox_partial);
-  hipLaunchKernelGGL(knn_bbox_final, dim3(1), dim3(256), 0, s, nb, k.bbox_partial, k.bbox);
-  hipLaunchKernelGGL(knn_morton, dim3((P + 255) / 256), dim3(256), 0, s, P, points, k.bbox, k.keys[0]);
-  GM_HIP(hipGetLastError());
-  int rc = radix_sort_pairs(k.keys, k.idx, k.hist, k.digit_total, (size_t)P, 30, true, 0, s);
-  if (rc) return rc;
-  const uint32_t* sorted_idx = k.idx[sort_final_slot(30)];
+  if (int rc = launch_point_bbox(P, points, k.front.bbox_partial, k.front.bbox, s)) return rc;
+  if (int rc = launch_point_morton(P, points, k.front.bbox, k.set.keys[0], s)) return rc;
+  MortonSorted sorted;
+  if (int rc = morton_sort(k.set, k.front, (size_t)P, &sorted, s)) return rc;
   const int nboxes = (P + KNN_BOX - 1) / KNN_BOX;
-  hipLaunchKernelGGL(knn_box_minmax, dim3(nboxes), dim3(256), 0, s, P, points, sorted_idx, k.boxes);
-  hipLaunchKernelGGL(knn_box_mean_dist, dim3((P + 255) / 256), dim3(256), 0, s, P, points, sorted_idx, k.boxes, meanDists);
+  hipLaunchKernelGGL(knn_box_minmax, dim3(nboxes), dim3(256), 0, s, P, points, sorted.idx, k.boxes);
+  hipLaunchKernelGGL(knn_box_mean_dist, dim3((P + 255) / 256), dim3(256), 0, s, P, points, sorted.idx, k.boxes, meanDists);
   GM_HIP(hipGetLastError());
   return 0;
 }
@@ -215,31 +132,17 @@ int launch_knn(int P, const float* points, float* meanDists, void* ws, size_t ws
 #define NN_WIN 8
 
 struct NnWs {
-  float* bbox_partial;   // [1024][6]
-  float* bbox;           // [8]
-  uint32_t* rkeys[2];
-  uint32_t* ridx[2];
-  uint32_t* qkeys[2];
-  uint32_t* qidx[2];
-  uint32_t* hist;
-  uint32_t* digit_total;
+  MortonWs front;        // bbox of the reference points; sort scratch for the larger of the two sets
+  MortonSet rset, qset;
   float4* rsorted;       // [Pr] x, y, z, original index (bits)
   float4* boxes;         // [nboxes][2] min xyz, max xyz
   char* end;
   static NnWs from(void* ws, size_t Pq, size_t Pr) {
     char* p = reinterpret_cast<char*>(ws);
-    // (the sort's tile size grows with n, so its block count is not monotonic in n: size for both sorts)
-    const size_t hb = sort_blocks(Pq) > sort_blocks(Pr) ? sort_blocks(Pq) : sort_blocks(Pr);
-    const size_t dc = sort_chunk_counters(Pq) > sort_chunk_counters(Pr) ? sort_chunk_counters(Pq) : sort_chunk_counters(Pr);
     NnWs k;
-    k.bbox_partial = carve<float>(p, 1024 * 6);
-    k.bbox = carve<float>(p, 8);
-    k.rkeys[0] = carve<uint32_t>(p, Pr); k.rkeys[1] = carve<uint32_t>(p, Pr);
-    k.ridx[0] = carve<uint32_t>(p, Pr); k.ridx[1] = carve<uint32_t>(p, Pr);
-    k.qkeys[0] = carve<uint32_t>(p, Pq); k.qkeys[1] = carve<uint32_t>(p, Pq);
-    k.qidx[0] = carve<uint32_t>(p, Pq); k.qidx[1] = carve<uint32_t>(p, Pq);
-    k.hist = carve<uint32_t>(p, 256 * hb);
-    k.digit_total = carve<uint32_t>(p, dc);
+    k.front = MortonWs::carve_from(p, Pq > Pr ? Pq : Pr);
+    k.rset = MortonSet::carve_from(p, Pr);
+    k.qset = MortonSet::carve_from(p, Pq);
     k.rsorted = carve<float4>(p, Pr);
     k.boxes = carve<float4>(p, 2 * ((Pr + NN_BOX - 1) / NN_BOX));
     k.end = p;
@@ -250,26 +153,6 @@ struct NnWs {
 size_t knn_nearest_workspace_bytes(int Pq, int Pr) {
   NnWs k = NnWs::from(nullptr, (size_t)(Pq > 0 ? Pq : 1), (size_t)(Pr > 0 ? Pr : 1));
   return (size_t)k.end + 256;
-}
-
-// Morton code against the reference bbox; queries outside it are clamped onto it (and a flat axis maps to 0)
-__device__ __forceinline__ uint32_t nn_morton_code(float x, float y, float z, const float* bb) {
-  const float v[3] = {x, y, z};
-  uint32_t c[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float ext = bb[3 + k] - bb[k];
-    float t = ext > 0.f ? (v[k] - bb[k]) / ext : 0.f;
-    t = fminf(fmaxf(t, 0.f), 1.f);               // (NaN -> 0)
-    c[k] = prep_morton((uint32_t)(t * ((1 << 10) - 1)));
-  }
-  return c[0] | (c[1] << 1) | (c[2] << 2);
-}
-
-__global__ __launch_bounds__(256) void nn_morton(int P, const float* __restrict__ pts, const float* __restrict__ bbox, uint32_t* __restrict__ codes) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  codes[i] = nn_morton_code(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2], bbox);
 }
 
 // sorted reference points as float4 (w = original index) and the bounding box of every NN_BOX of them (one workgroup per box)
@@ -284,7 +167,7 @@ __global__ __launch_bounds__(NN_BOX) void nn_gather_boxes(int Pr, const float* _
     rsorted[i] = make_float4(x, y, z, __uint_as_float(g));
     mn[0] = mx[0] = x; mn[1] = mx[1] = y; mn[2] = mx[2] = z;
   }
-  block_minmax(mn, mx, sm);
+  block_minmax3(mn, mx, sm);
   if (threadIdx.x == 0) {
     boxes[2 * blockIdx.x] = make_float4(mn[0], mn[1], mn[2], 0.f);
     boxes[2 * blockIdx.x + 1] = make_float4(mx[0], mx[1], mx[2], 0.f);
@@ -309,13 +192,8 @@ __global__ __launch_bounds__(256) void nn_query(int Pq, const float* __restrict_
   if (i >= Pq) return;
   const uint32_t q = qidx[i];
   const float px = query[3 * (size_t)q], py = query[3 * (size_t)q + 1], pz = query[3 * (size_t)q + 2];
-  // start: the sorted reference points around the query's own Morton code
-  const uint32_t code = nn_morton_code(px, py, pz, bbox);
-  int lo = 0, hi = Pr;                           // lower_bound
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (rkeys[mid] < code) lo = mid + 1; else hi = mid;
-  }
+  // start: the sorted reference points around the query's own Morton code (a query outside the reference box is clamped onto it)
+  const int lo = morton_lower_bound(rkeys, Pr, morton_code30(px, py, pz, bbox));
   float best = INFINITY;                         // (an infinite distance is still taken, lowest index first)
   uint32_t bid = 0xFFFFFFFFu;
   const int j0 = max(0, lo - NN_WIN), j1 = min(Pr, lo + NN_WIN);
@@ -343,21 +221,16 @@ int launch_knn_nearest(int Pq, const float* query, int Pr, const float* ref, flo
   const size_t need = knn_nearest_workspace_bytes(Pq, Pr);
   if (ws_bytes < need) { set_error("gm_knn_nearest: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
   NnWs k = NnWs::from(ws, (size_t)Pq, (size_t)Pr);
-  const int nb = min(1024, (Pr + 255) / 256);
-  hipLaunchKernelGGL(knn_bbox_partial, dim3(nb), dim3(256), 0, s, Pr, ref, k.bbox_partial);
-  hipLaunchKernelGGL(knn_bbox_final, dim3(1), dim3(256), 0, s, nb, k.bbox_partial, k.bbox);
-  hipLaunchKernelGGL(nn_morton, dim3((Pr + 255) / 256), dim3(256), 0, s, Pr, ref, k.bbox, k.rkeys[0]);
-  hipLaunchKernelGGL(nn_morton, dim3((Pq + 255) / 256), dim3(256), 0, s, Pq, query, k.bbox, k.qkeys[0]);
-  GM_HIP(hipGetLastError());
-  // 30-bit keys: 4 passes of 8 bits, the result lands back in slot 0
-  int rc = radix_sort_pairs(k.rkeys, k.ridx, k.hist, k.digit_total, (size_t)Pr, 30, true, 0, s);
-  if (rc) return rc;
-  rc = radix_sort_pairs(k.qkeys, k.qidx, k.hist, k.digit_total, (size_t)Pq, 30, true, 0, s);
-  if (rc) return rc;
+  if (int rc = launch_point_bbox(Pr, ref, k.front.bbox_partial, k.front.bbox, s)) return rc;
+  if (int rc = launch_point_morton(Pr, ref, k.front.bbox, k.rset.keys[0], s)) return rc;
+  if (int rc = launch_point_morton(Pq, query, k.front.bbox, k.qset.keys[0], s)) return rc;
+  MortonSorted r, q;
+  if (int rc = morton_sort(k.rset, k.front, (size_t)Pr, &r, s)) return rc;
+  if (int rc = morton_sort(k.qset, k.front, (size_t)Pq, &q, s)) return rc;
   const int nboxes = (Pr + NN_BOX - 1) / NN_BOX;
-  hipLaunchKernelGGL(nn_gather_boxes, dim3(nboxes), dim3(NN_BOX), 0, s, Pr, ref, k.ridx[0], k.rsorted, k.boxes);
-  hipLaunchKernelGGL(nn_query, dim3((Pq + 255) / 256), dim3(256), 0, s, Pq, query, k.qidx[0], Pr, k.rkeys[0], k.rsorted, k.boxes, nboxes,
-                     k.bbox, out_d2, out_idx);
+  hipLaunchKernelGGL(nn_gather_boxes, dim3(nboxes), dim3(NN_BOX), 0, s, Pr, ref, r.idx, k.rsorted, k.boxes);
+  hipLaunchKernelGGL(nn_query, dim3((Pq + 255) / 256), dim3(256), 0, s, Pq, query, q.idx, Pr, r.keys, k.rsorted, k.boxes, nboxes,
+                     k.front.bbox, out_d2, out_idx);
   GM_HIP(hipGetLastError());
   return 0;
 }

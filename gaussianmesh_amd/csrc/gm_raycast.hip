@@ -54,15 +54,12 @@ static inline int rc_div_up(int n, int d) { return n > 0 ? (n - 1) / d + 1 : 0; 
 // workgroups of rc_cast; more than a grid holds is refused by gm_ray_mesh
 unsigned long long ray_mesh_blocks(int R, int F) { return (unsigned long long)rc_div_up(R, 256) * (unsigned long long)rc_div_up(F, RC_CHUNK); }
 
-// a face's vertex index forced into [0, Vm), as cf_vertex (gm_closest.hip): no fault, no meaningful result for such a face
-__device__ __forceinline__ size_t rc_vertex(const int* faces, size_t slot, int Vm) { return (size_t)min(max(faces[slot], 0), Vm - 1); }
-
 __global__ __launch_bounds__(256) void rc_prepare(int F, int Vm, const float* __restrict__ verts, const int* __restrict__ faces,
                                                   float4* __restrict__ recs, int R, unsigned long long* __restrict__ slots) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < R) slots[i] = RC_MISS;
   if (i >= F) return;
-  const size_t ia = rc_vertex(faces, 3 * (size_t)i, Vm), ib = rc_vertex(faces, 3 * (size_t)i + 1, Vm), ic = rc_vertex(faces, 3 * (size_t)i + 2, Vm);
+  const size_t ia = face_vertex(faces, 3 * (size_t)i, Vm), ib = face_vertex(faces, 3 * (size_t)i + 1, Vm), ic = face_vertex(faces, 3 * (size_t)i + 2, Vm);
   const float ax = verts[3 * ia], ay = verts[3 * ia + 1], az = verts[3 * ia + 2];
   recs[3 * (size_t)i] = make_float4(ax, ay, az, verts[3 * ib] - ax);
   recs[3 * (size_t)i + 1] = make_float4(verts[3 * ib + 1] - ay, verts[3 * ib + 2] - az, verts[3 * ic] - ax, verts[3 * ic + 1] - ay);

@@ -63,7 +63,7 @@ struct SpMesh {
   const int* __restrict__ faces;
   const int* __restrict__ off;
   const int* __restrict__ adj;
-  __device__ __forceinline__ int vid(int v) const { return v < 0 ? 0 : (v >= Vm ? Vm - 1 : v); }
+  __device__ __forceinline__ int vid(int v) const { return clamp_index(v, Vm); }
   __device__ __forceinline__ void range(int v, int& b, int& e) const {
     const int nnz = 3 * F;
     b = off[v]; e = off[v + 1];
@@ -155,8 +155,8 @@ __global__ __launch_bounds__(256) void sp_lock(int Vm, int E, const int* __restr
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= E || uses[e] == 2) return;
   const int lo = edges[2 * (size_t)e], hi = edges[2 * (size_t)e + 1];
-  locked[lo < 0 ? 0 : (lo >= Vm ? Vm - 1 : lo)] = 1;       // (every writer stores the same byte)
-  locked[hi < 0 ? 0 : (hi >= Vm ? Vm - 1 : hi)] = 1;
+  locked[clamp_index(lo, Vm)] = 1;       // (every writer stores the same byte)
+  locked[clamp_index(hi, Vm)] = 1;
 }
 
 // does w hold a corner of a face of a

@@ -1,7 +1,7 @@
 // gm_wave.h -- the wave64 / workgroup primitives of the ordering kernels (gm_bucket.hip, gm_sort.hip, gm_binning.hip, gm_tile_order.h,
 // gm_tsdf.hip), one copy each: wave reductions, the stable match-any rank of a radix pass, the workgroup exclusive scan and the
-// per-wave digit counts -> per-wave offsets step.  Everything is uint32_t and exact; the float reductions of other files fix their own
-// summation order and stay where they are.
+// per-wave digit counts -> per-wave offsets step, all uint32_t and exact; and the float min / max reductions of the geometry queries
+// (gm_spatial.hip, gm_knn.hip, gm_closest.hip), exact as well.  The float SUMS of other files fix their own order and stay where they are.
 #pragma once
 #include "gm_common.h"
 
@@ -16,6 +16,34 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
   return v;
+}
+__device__ __forceinline__ float wave_min_f32(float v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d));
+  return v;
+}
+__device__ __forceinline__ float wave_max_f32(float v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
+  return v;
+}
+
+// min of mn[3] and max of mx[3] over the workgroup (a bounding box); the result is valid in thread 0.  Every thread calls it (ONE
+// __syncthreads inside); sm holds a row per wave.
+__device__ __forceinline__ void block_minmax3(float* mn, float* mx, float (*sm)[6]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { mn[k] = wave_min_f32(mn[k]); mx[k] = wave_max_f32(mx[k]); }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { sm[wave][k] = mn[k]; sm[wave][3 + k] = mx[k]; }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < (int)(blockDim.x >> 6); w++)
+#pragma unroll
+      for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], sm[w][k]); mx[k] = fmaxf(mx[k], sm[w][3 + k]); }
+  }
 }
 
 // match-any over the low DB bits of the digit among the valid lanes: the lanes of the wave whose key has this lane's digit (DB + 1

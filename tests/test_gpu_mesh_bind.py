@@ -119,7 +119,7 @@ def _case(kind, N, F, seed):
     return V2, faces, P
 
 
-SIZES = [(1, 1), (1, 50), (50, 1), (300, 2400), (777, 333), (4097, 1025), (300, 70000)]
+SIZES = [(1, 1), (1, 50), (50, 1), (300, 2400), (777, 333), (4097, 1025), (65, 4097), (300, 70000)]      # (65, 4097): a super-box and one face
 
 
 @pytest.mark.parametrize("kind", ["grid_ties", "degenerate_far", "shifted"])

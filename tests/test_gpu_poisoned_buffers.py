@@ -32,9 +32,10 @@ loop bound of four billion):
   rasterizer, backward          grad_acc: hipMemsetAsync (gm_api.hip:590, "the only zero-fill of a backward"); preprocess_bwd writes
                                 every row of every gradient output, zeros for culled rows.
   radix sort (knn, closest)     hist by radix_hist_kernel, digit_total by radix_scan_kernel, both before radix_scatter reads them.
-  distCUDA2 / knn_nearest       bbox_partial[nb] by knn_bbox_partial, bbox by knn_bbox_final, keys by *_morton, boxes / rsorted by
-                                knn_box_minmax / nn_gather_boxes, all before their readers; outputs once per point.
-  closest_faces                 cf_bbox_partial writes all nb partials, cf_gather_boxes recs and boxes, cf_super_boxes sboxes.
+  Morton front end (knn,        bbox_partial[nb] by point_bbox_partial (all nb partials), bbox by point_bbox_final, keys by point_morton /
+  knn_nearest, closest_faces)   cf_face_morton, all before their readers (gm_spatial.hip).
+  distCUDA2 / knn_nearest       boxes / rsorted by knn_box_minmax / nn_gather_boxes before their readers; outputs once per point.
+  closest_faces                 cf_gather_boxes recs and boxes, cf_super_boxes sboxes.
   ray caster                    rc_prepare writes recs and arms slots = MISS before rc_cast's atomicMin.
   geodesic distances            gd_fill writes +inf and arms counters[0 .. sweeps] (resume: the counters alone); no loop on a counter.
   surface nets                  sn_cells act, sn_edges flags and lvl[0], sn_sums / sn_scan_level the upper levels and counts, sn_vertices
