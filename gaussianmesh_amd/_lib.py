@@ -73,6 +73,8 @@ SIGNATURES = {
     "gm_tsdf_integrate": (i32, [i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), f32, f32, f32, i32, vp, vp, vp]),
     "gm_surface_nets_workspace_bytes": (sz, [i32, i32, i32]),
     "gm_surface_nets": (i32, [i32, i32, i32, C.POINTER(f32), f32, vp, vp, f32, i32, vp, i32, vp, vp, vp, sz, vp]),
+    "gm_tsdf_fill_workspace_bytes": (sz, [i32, i32, i32]),
+    "gm_tsdf_fill": (i32, [i32, i32, i32, vp, vp, f32, i32, i32, f32, vp, vp, vp, vp, sz, vp]),
     "gm_mesh_quadrics": (i32, [i32, vp, i32, vp, vp, vp, vp, vp]),
     "gm_mesh_collapse_round_workspace_bytes": (sz, [i32]),
     "gm_mesh_collapse_round": (i32, [i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, sz, vp]),

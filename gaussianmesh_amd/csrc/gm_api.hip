@@ -855,6 +855,30 @@ int gm_surface_nets(int nx, int ny, int nz, const float* origin, float voxel, co
                              workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t gm_tsdf_fill_workspace_bytes(int nx, int ny, int nz) { return tsdf_fill_workspace_bytes(nx, ny, nz); }
+int gm_tsdf_fill(int nx, int ny, int nz, const float* tsdf_in, const float* weight_in, float min_weight, int iterations, int boundary_free,
+                 float fill_weight, float* tsdf_out, float* weight_out, int* out_counts, void* workspace, size_t workspace_bytes, void* stream) {
+  static const float no_origin[3] = {0.f, 0.f, 0.f};                  // (the fill knows samples, not where they lie)
+  if (int rc = check_tsdf_grid("gm_tsdf_fill", nx, ny, nz, 2, no_origin, 1.0f)) return rc;
+  if (iterations < 0) { set_error("gm_tsdf_fill: iterations = %d (negative)", iterations); return GM_ERR_INVALID_ARG; }
+  if (min_weight != min_weight || fill_weight != fill_weight) { set_error("gm_tsdf_fill: min_weight or fill_weight is NaN"); return GM_ERR_INVALID_ARG; }
+  if (!tsdf_in || !weight_in || !tsdf_out || !weight_out || !workspace) { set_error("gm_tsdf_fill: null pointer"); return GM_ERR_INVALID_ARG; }
+  const size_t n = (size_t)nx * ny * nz;
+  const struct { const char* p; size_t n; const char* what; } rg[6] = {
+      {reinterpret_cast<const char*>(tsdf_in), 4 * n, "tsdf_in"}, {reinterpret_cast<const char*>(weight_in), 4 * n, "weight_in"},
+      {reinterpret_cast<const char*>(tsdf_out), 4 * n, "tsdf_out"}, {reinterpret_cast<const char*>(weight_out), 4 * n, "weight_out"},
+      {reinterpret_cast<const char*>(out_counts), 8, "out_counts"}, {reinterpret_cast<const char*>(workspace), workspace_bytes, "workspace"}};
+  for (int a = 0; a < 6; a++)
+    for (int b = (a < 2 ? 2 : a + 1); b < 6; b++) {             // (the inputs are only read: they may be one buffer)
+      if (!rg[a].p || !rg[b].p || !rg[b].n) continue;
+      if (rg[a].p < rg[b].p + rg[b].n && rg[b].p < rg[a].p + rg[a].n) {
+        set_error("gm_tsdf_fill: %s overlaps %s", rg[a].what, rg[b].what); return GM_ERR_INVALID_ARG;
+      }
+    }
+  return launch_tsdf_fill(nx, ny, nz, tsdf_in, weight_in, min_weight, iterations, boundary_free, fill_weight, tsdf_out, weight_out, out_counts, workspace,
+                          workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
 // byte ranges of a call: every one of the last n_out (the outputs) against every other range; NULL or empty ranges never overlap
 struct ByteRange { const void* p; size_t n; const char* what; };
 static int check_outputs_apart(const char* fn, const ByteRange* rg, int n, int n_out) {

@@ -560,6 +560,10 @@ int launch_surface_nets(int nx, int ny, int nz, const float* origin, float voxel
                         int max_vertices, float* out_vertices, int max_faces, int* out_faces, int* out_counts, void* ws, size_t ws_bytes,
                         hipStream_t s);
 size_t surface_nets_workspace_bytes(int nx, int ny, int nz);
+// gm_tsdf_fill.hip: diffuse the observed distances into the unobserved samples (the inputs are only read)
+int launch_tsdf_fill(int nx, int ny, int nz, const float* tsdf_in, const float* weight_in, float min_weight, int iterations, int boundary_free,
+                     float fill_weight, float* tsdf_out, float* weight_out, int* out_counts, void* ws, size_t ws_bytes, hipStream_t s);
+size_t tsdf_fill_workspace_bytes(int nx, int ny, int nz);
 // gm_simplify.hip: error quadrics, and one round of independent edge collapses (subset placement)
 int launch_mesh_quadrics(int Vm, const float* V, int F, const int* faces, const int* off, const int* adj, float* Q, hipStream_t s);
 int launch_mesh_collapse_round(int Vm, const float* V, const float* Q, int F, const int* faces, const int* off, const int* adj, int E,

@@ -105,6 +105,8 @@ class TsdfVolume:
         self._origin_c = (C.c_float * 3)(*self.origin.tolist())
         self.views = 0
         self.simplified = None
+        self.filled_tsdf = self.filled_weight = None
+        self._fill = None
 
     def integrate(self, cameras, depth, alpha, alpha_min=0.5, carve=True):
         """Fuse views: cameras (renderer.Camera-like objects or scenes.camera_from_RT dicts), depth and alpha the rasterizer's own maps
@@ -121,6 +123,7 @@ class TsdfVolume:
             if d.shape != a.shape:
                 raise ValueError("TsdfVolume.integrate: a depth map is %s and its alpha map %s" % (tuple(d.shape), tuple(a.shape)))
         lib = _lib.lib()
+        self.filled_tsdf = self.filled_weight = self._fill = None      # a fill is of the volume as it was
         k = 0
         while k < len(cameras):                                        # runs of one resolution, in view order
             e = k + 1
@@ -146,8 +149,50 @@ class TsdfVolume:
             k = e
         return self
 
-    def _surface_nets_enqueue(self, min_weight, max_vertices, max_faces):
-        """gm_surface_nets at the given capacities: (vertex buffer, face buffer, device counts); nothing waits"""
+    def fill_holes(self, iterations=None, min_weight=1, boundary="none", fill_weight=None):
+        """Close the holes no view saw by volumetric diffusion (gm_tsdf_fill; Davis et al. 2002): the samples with weight >= min_weight
+        stay as they are and their distances diffuse, one Jacobi step per iteration, into the others, so that an underside nobody
+        photographed gets a zero crossing where extract() otherwise ends in a border.  The result goes into self.filled_tsdf /
+        self.filled_weight (new device tensors; a filled sample weighs fill_weight, by default min_weight, so the extraction that
+        follows takes it; a sample the fill did not reach weighs 0); self.tsdf / self.weight are untouched and can take more views,
+        which drops the fill.  iterations: default max(nx, ny, nz).  That is a REACH, not a convergence claim: after n iterations every
+        sample within n six-connected steps of a known one has a value, and values further from the sources are less settled.
+        boundary="none": the grid's sides contribute nothing - a hole that reaches a side stays open there; "free": the samples beyond
+        the grid count as free space (+1), which closes such a hole inside the grid.  Only enqueues; self.fill_stats (iterations,
+        filled_voxels, unreached_voxels) reads the counts when it is asked for.  Returns self."""
+        if boundary not in ("none", "free"):
+            raise ValueError("TsdfVolume.fill_holes: boundary must be 'none' or 'free'; got %r" % (boundary,))
+        _need_device(getattr(self, "tsdf", None), "TsdfVolume.fill_holes", "the volume")
+        n = max(self.nx, self.ny, self.nz) if iterations is None else int(iterations)
+        if n < 0:
+            raise ValueError("TsdfVolume.fill_holes: iterations must not be negative; got %r" % (iterations,))
+        lib = _lib.lib()
+        self.filled_tsdf, self.filled_weight = torch.empty_like(self.tsdf), torch.empty_like(self.weight)
+        counts = torch.empty((2,), dtype=torch.int32, device=self.device)
+        nbytes = lib.gm_tsdf_fill_workspace_bytes(self.nx, self.ny, self.nz)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.gm_tsdf_fill(self.nx, self.ny, self.nz, self.tsdf.data_ptr(), self.weight.data_ptr(), float(min_weight), n,
+                                        int(boundary == "free"), float(min_weight if fill_weight is None else fill_weight),
+                                        self.filled_tsdf.data_ptr(), self.filled_weight.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes,
+                                        torch.cuda.current_stream(self.device).cuda_stream))
+        self._fill = [n, counts, None]
+        return self
+
+    @property
+    def fill_stats(self):
+        """dict(iterations, filled_voxels, unreached_voxels) of the last fill_holes (the first look waits for the device); None without one"""
+        if self._fill is None:
+            return None
+        if self._fill[2] is None:
+            filled, left = (int(c) for c in self._fill[1].cpu())
+            self._fill[2] = dict(iterations=self._fill[0], filled_voxels=filled, unreached_voxels=left)
+        return dict(self._fill[2])
+
+    def _surface_nets_enqueue(self, min_weight, max_vertices, max_faces, volume=None):
+        """gm_surface_nets at the given capacities on (tsdf, weight) = volume, by default the fused pair: (vertex buffer, face buffer,
+        device counts); nothing waits"""
+        tsdf, weight = (self.tsdf, self.weight) if volume is None else volume
         lib = _lib.lib()
         f = dict(device=self.device)
         V = torch.empty((max_vertices, 3), dtype=torch.float32, **f)
@@ -156,17 +201,17 @@ class TsdfVolume:
         nbytes = lib.gm_surface_nets_workspace_bytes(self.nx, self.ny, self.nz)
         ws = torch.empty((nbytes,), dtype=torch.uint8, **f)
         with torch.cuda.device(self.device):
-            _lib.check(lib.gm_surface_nets(self.nx, self.ny, self.nz, self._origin_c, self.voxel, self.tsdf.data_ptr(), self.weight.data_ptr(),
+            _lib.check(lib.gm_surface_nets(self.nx, self.ny, self.nz, self._origin_c, self.voxel, tsdf.data_ptr(), weight.data_ptr(),
                                            float(min_weight), max_vertices, V.data_ptr(), max_faces, F.data_ptr(), counts.data_ptr(), ws.data_ptr(),
                                            nbytes, torch.cuda.current_stream(self.device).cuda_stream))
         return V, F, counts
 
-    def _surface_nets(self, min_weight, max_vertices, max_faces):
-        V, F, counts = self._surface_nets_enqueue(min_weight, max_vertices, max_faces)
+    def _surface_nets(self, min_weight, max_vertices, max_faces, volume=None):
+        V, F, counts = self._surface_nets_enqueue(min_weight, max_vertices, max_faces, volume)
         nv, nf = (int(c) for c in counts.cpu())                       # the one host wait
         return V, F, nv, nf
 
-    def extract(self, min_weight=1, keep="largest", target_faces=None, simplify_max_rounds=1024):
+    def extract(self, min_weight=1, keep="largest", target_faces=None, simplify_max_rounds=1024, fill_holes=None, fill_boundary="none"):
         """(vertices float32 [V,3], faces int32 [F,3]) on the device: the zero surface among the samples that at least min_weight views
         observed, by naive surface nets (gm_surface_nets: ids and rows in scan order).  It starts from a capacity guess (a few times
         the largest face of the grid), reads the counts - the one host wait - and runs once more if the guess was short.
@@ -178,18 +223,35 @@ class TsdfVolume:
         simplify_stalled, simplify_reached and seconds_simplify (`faces` stays the dense count; the returned F has the final one), and
         self.simplified the whole result (kept, vertex_map; None after an extract without a target).  A run that ends above the target -
         stalled on locked borders, or out of rounds, which a very finely sampled smooth surface can be - is
-        returned as it is, with simplify_reached False and a RuntimeWarning.  None: nothing changes."""
+        returned as it is, with simplify_reached False and a RuntimeWarning.  None: nothing changes.
+        fill_holes: an iteration count, or True for fill_holes()'s default: the fill runs first, with this call's min_weight and
+        boundary=fill_boundary, and the surface is that of the filled pair; self.stats then also holds fill_iterations, filled_voxels,
+        unreached_voxels and seconds_fill (device time between two events; no further host wait).  None: the fused volume as it is."""
         self.simplified = None
         if keep not in ("largest", "all"):
             raise ValueError("TsdfVolume.extract: keep must be 'largest' or 'all'; got %r" % (keep,))
+        volume = clock = None
+        if fill_holes is not None and fill_holes is not False:
+            if fill_boundary not in ("none", "free"):
+                raise ValueError("TsdfVolume.extract: fill_boundary must be 'none' or 'free'; got %r" % (fill_boundary,))
+            _need_device(getattr(self, "tsdf", None), "TsdfVolume.extract", "the volume")
+            clock = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            clock[0].record(torch.cuda.current_stream(self.device))
+            self.fill_holes(None if fill_holes is True else fill_holes, min_weight=min_weight, boundary=fill_boundary)
+            clock[1].record(torch.cuda.current_stream(self.device))
+            volume = (self.filled_tsdf, self.filled_weight)
         side = max(self.nx * self.ny, self.ny * self.nz, self.nx * self.nz)
         cells = (self.nx - 1) * (self.ny - 1) * (self.nz - 1)
         guess = min(cells, max(4096, 8 * side))
-        V, F, nv, nf = self._surface_nets(min_weight, guess, 3 * guess)
+        V, F, nv, nf = self._surface_nets(min_weight, guess, 3 * guess, volume)
         if nv > V.shape[0] or nf > F.shape[0]:
-            V, F, nv, nf = self._surface_nets(min_weight, nv, nf)
+            V, F, nv, nf = self._surface_nets(min_weight, nv, nf, volume)
         V, F = V[:nv], F[:nf]
         self.stats = dict(vertices=nv, faces=nf, components=None, components_dropped=0)
+        if volume is not None:                                         # (the counts are there: the wait above was behind the fill)
+            st = self.fill_stats
+            self.stats.update(fill_iterations=st["iterations"], filled_voxels=st["filled_voxels"], unreached_voxels=st["unreached_voxels"],
+                              seconds_fill=clock[0].elapsed_time(clock[1]) * 1e-3)
         if keep == "largest":
             v, f, comps = largest_component(V.cpu().numpy(), F.cpu().numpy())
             self.stats.update(components=comps, components_dropped=max(comps - 1, 0))
@@ -258,12 +320,14 @@ def fuse_cloud(pc, cameras, pipe=None, bg_gaussian=None, resolution=96, bounds=N
 
 
 def from_cloud(pc, cameras, pipe=None, bg_gaussian=None, resolution=96, bounds=None, views_per_call=8, trunc_voxels=3.0, alpha_min=0.5,
-               carve=True, min_weight=1, keep="largest", bg_color=None, target_faces=None, simplify_max_rounds=1024):
+               carve=True, min_weight=1, keep="largest", bg_color=None, target_faces=None, simplify_max_rounds=1024, fill_holes=None,
+               fill_boundary="none"):
     """The proxy mesh of a trained cloud: (vertices float32 [V,3], faces int32 [F,3]) on the device: fuse_cloud(...).extract(min_weight,
-    keep, target_faces, simplify_max_rounds)."""
+    keep, target_faces, simplify_max_rounds, fill_holes, fill_boundary)."""
     vol = fuse_cloud(pc, cameras, pipe=pipe, bg_gaussian=bg_gaussian, resolution=resolution, bounds=bounds, views_per_call=views_per_call,
                      trunc_voxels=trunc_voxels, alpha_min=alpha_min, carve=carve, bg_color=bg_color)
-    return vol.extract(min_weight=min_weight, keep=keep, target_faces=target_faces, simplify_max_rounds=simplify_max_rounds)
+    return vol.extract(min_weight=min_weight, keep=keep, target_faces=target_faces, simplify_max_rounds=simplify_max_rounds, fill_holes=fill_holes,
+                       fill_boundary=fill_boundary)
 
 
 def _load_model(path, mesh_gaussian, dev):
@@ -296,6 +360,8 @@ def main(argv=None):
     ap.add_argument("--keep", choices=("largest", "all"), default="largest")
     ap.add_argument("--target_faces", type=int, help="simplify the mesh to at most this many faces (mesh_simplify)")
     ap.add_argument("--simplify_max_rounds", type=int, default=1024)
+    ap.add_argument("--fill_holes", type=int, metavar="N", help="close unobserved holes first: N diffusion iterations (gm_tsdf_fill)")
+    ap.add_argument("--fill_boundary", choices=("none", "free"), default="none", help="free: beyond the grid is free space")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("proxy_mesh needs a HIP (cuda) device; there is no CPU path")
@@ -312,7 +378,8 @@ def main(argv=None):
     vol = fuse_cloud(pc, cams, resolution=a.resolution, bounds=bounds, trunc_voxels=a.trunc_voxels, alpha_min=a.alpha_min)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
-    V, F = vol.extract(keep=a.keep, target_faces=a.target_faces, simplify_max_rounds=a.simplify_max_rounds)
+    V, F = vol.extract(keep=a.keep, target_faces=a.target_faces, simplify_max_rounds=a.simplify_max_rounds, fill_holes=a.fill_holes,
+                       fill_boundary=a.fill_boundary)
     torch.cuda.synchronize()
     t3 = time.perf_counter()
     v, f = V.cpu().numpy(), F.cpu().numpy()
@@ -325,6 +392,10 @@ def main(argv=None):
         out.update(faces_before_simplify=vol.stats["faces_before_simplify"], simplify_rounds=vol.stats["simplify_rounds"],
                    simplify_reached=vol.stats["simplify_reached"])
         out["seconds"]["simplify"] = vol.stats["seconds_simplify"]
+    if a.fill_holes is not None:                                       # (and the fill)
+        out.update(fill_iterations=vol.stats["fill_iterations"], filled_voxels=vol.stats["filled_voxels"],
+                   unreached_voxels=vol.stats["unreached_voxels"])
+        out["seconds"]["fill"] = vol.stats["seconds_fill"]
     print(json.dumps(out))
     return 0
 

@@ -394,6 +394,29 @@ int gm_surface_nets(int nx, int ny, int nz, const float* origin, float voxel, co
                     int max_vertices, float* out_vertices, int max_faces, int* out_faces, int* out_counts, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* Close the unobserved holes of a volume by volumetric diffusion (Davis, Marschner, Garr, Levoy 2002), between fusion and extraction
+ * (proxy_mesh.TsdfVolume.fill_holes): the observed samples stay fixed and their distances diffuse into the samples no view saw, until
+ * inside and outside values meet in a zero crossing where the fused volume alone ends in a border.  Defined by arithmetic, float32, no
+ * contraction, correctly rounded division; tests/tsdf_fill_ref.py restates it in numpy bit for bit.  Volumes float [nz,ny,nx], x fastest.
+ *   src(g) = weight_in[g] >= min_weight (false on NaN); val_0(g) = src ? tsdf_in[g] : +0, known_0 = src.
+ *   Iteration t = 0 .. iterations-1 is a Jacobi step that reads only val_t / known_t: s = known_t(g) ? val_t(g) : 0, c = known_t(g) ? 1 : 0;
+ *   then over the six face neighbours in the order -x, +x, -y, +y, -z, +z: one inside the grid with known_t: s = s + val_t(nb), c++; one
+ *   outside the grid: with boundary_free != 0 s = s + 1 (free space) and c++, otherwise nothing.  not src(g) and c > 0: val_{t+1}(g) =
+ *   s / (float)c, known_{t+1}(g) = 1; otherwise both carry over.  Sources never change; a filled sample is averaged again in every later
+ *   iteration.  After n iterations every sample within n six-connected steps of a known one (or, with boundary_free, of the grid's
+ *   side) has a value: iterations is a reach, not a convergence test.
+ *   tsdf_out = val_N; weight_out = src ? weight_in : (known_N ? fill_weight : 0); out_counts int32 [2] ON THE DEVICE, may be NULL =
+ *   {samples filled, samples still unknown} (integer atomics: the same in every run).  iterations == 0 copies the sources and zeroes
+ *   the rest.  tsdf_in / weight_in are only read (they may be one buffer): the volume can take more views afterwards.
+ * One launch per iteration between two copies of the state, one of them in the workspace; the last step always writes tsdf_out.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: a grid side < 2, more than 2^28 samples, iterations < 0, a NaN min_weight or
+ * fill_weight, a NULL tsdf_in, weight_in, tsdf_out, weight_out or workspace, an output, out_counts or the workspace overlapping anything
+ * else; with GM_ERR_BUFFER: a workspace below gm_tsdf_fill_workspace_bytes(nx, ny, nz) (about 6 bytes a sample, monotonic in each side,
+ * positive at (2, 2, 2)).  Stream-ordered, no device allocation, no host synchronisation. */
+size_t gm_tsdf_fill_workspace_bytes(int nx, int ny, int nz);
+int gm_tsdf_fill(int nx, int ny, int nz, const float* tsdf_in, const float* weight_in, float min_weight, int iterations, int boundary_free,
+                 float fill_weight, float* tsdf_out, float* weight_out, int* out_counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Mesh simplification by rounds of quadric-error edge collapses with SUBSET PLACEMENT (mesh_simplify.simplify): a collapse i -> j removes
  * vertex i and moves nothing, so the output vertices are rows of the input; the error quadrics (Garland & Heckbert 1997) are the only
  * floating-point state.  The reference sends its users to MeshLab for this step: the result is defined by arithmetic - float32, no
