@@ -78,6 +78,10 @@ SIGNATURES = {
     "gm_mesh_quadrics": (i32, [i32, vp, i32, vp, vp, vp, vp, vp]),
     "gm_mesh_collapse_round_workspace_bytes": (sz, [i32]),
     "gm_mesh_collapse_round": (i32, [i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "gm_mesh_vertex_normals": (i32, [i32, i32, vp, vp, vp, vp, vp, vp]),
+    "gm_mesh_color_integrate": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, f32, f32, i32, vp, vp, vp]),
+    "gm_mesh_color_spread_workspace_bytes": (sz, [i32]),
+    "gm_mesh_color_spread": (i32, [i32, i32, vp, vp, vp, vp, i32, C.POINTER(f32), vp, vp, vp, vp, sz, vp]),
     "gm_deform": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gm_sh_colors": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "gm_deform_shade": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

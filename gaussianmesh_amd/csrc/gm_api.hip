@@ -953,6 +953,64 @@ int gm_mesh_collapse_round(int Vm, const float* vertices, const float* quadrics,
                                     out_from, out_to, out_key, out_count, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
+// the mesh rules the three gm_mesh_color.hip calls share: sizes, and the CSR's pointers when there is anything to walk
+static int check_color_mesh(const char* fn, int Vm, int F) {
+  if (Vm < 0 || F < 0) { set_error("%s: negative size Vm=%d F=%d", fn, Vm, F); return GM_ERR_INVALID_ARG; }
+  if (Vm > 0x7FFFFFFF / 3 || F > 0x7FFFFFFF / 3) { set_error("%s: Vm=%d F=%d: 3 Vm and 3 F must fit an int", fn, Vm, F); return GM_ERR_INVALID_ARG; }
+  return 0;
+}
+
+int gm_mesh_vertex_normals(int Vm, int F, const float* vertices, const int* faces, const int* adj_offsets, const int* adj_faces, float* out_normals,
+                           void* stream) {
+  const char* fn = "gm_mesh_vertex_normals";
+  if (int rc = check_color_mesh(fn, Vm, F)) return rc;
+  if (Vm == 0) return GM_OK;
+  if (!vertices || !out_normals || (F > 0 && (!faces || !adj_offsets || !adj_faces))) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  const ByteRange rg[5] = {{vertices, 12 * (size_t)Vm, "vertices"}, {faces, 12 * (size_t)F, "faces"}, {adj_offsets, 4 * ((size_t)Vm + 1), "adj_offsets"},
+                           {adj_faces, 12 * (size_t)F, "adj_faces"}, {out_normals, 12 * (size_t)Vm, "out_normals"}};
+  if (int rc = check_outputs_apart(fn, rg, 5, 1)) return rc;
+  return launch_mesh_vertex_normals(Vm, F, vertices, faces, adj_offsets, adj_faces, out_normals, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gm_mesh_color_integrate(int K, int H, int W, const float* image, const float* depth, const float* alpha, const float* views, const float* tanfov,
+                            int Vm, const float* vertices, const float* normals, float alpha_min, float depth_tol, int two_sided, float* csum,
+                            float* wsum, void* stream) {
+  const char* fn = "gm_mesh_color_integrate";
+  if (K < 0 || H <= 0 || W <= 0 || H > (1 << 24) || W > (1 << 24)) { set_error("%s: invalid sizes K=%d H=%d W=%d", fn, K, H, W); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_color_mesh(fn, Vm, 0)) return rc;
+  if (alpha_min != alpha_min || !(depth_tol >= 0.f)) { set_error("%s: alpha_min must not be NaN, depth_tol >= 0 and not NaN", fn); return GM_ERR_INVALID_ARG; }
+  if (Vm == 0) return GM_OK;
+  if (!vertices || !normals || !csum || !wsum) { set_error("%s: null pointer (vertices / normals / csum / wsum)", fn); return GM_ERR_INVALID_ARG; }
+  if (K > 0 && (!image || !depth || !alpha || !views || !tanfov)) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  const size_t maps = 4 * (size_t)K * H * W;
+  const ByteRange rg[9] = {{image, 3 * maps, "image"}, {depth, maps, "depth"}, {alpha, maps, "alpha"}, {views, 64 * (size_t)K, "views"},
+                           {tanfov, 8 * (size_t)K, "tanfov"}, {vertices, 12 * (size_t)Vm, "vertices"}, {normals, 12 * (size_t)Vm, "normals"},
+                           {csum, 12 * (size_t)Vm, "csum"}, {wsum, 4 * (size_t)Vm, "wsum"}};
+  if (int rc = check_outputs_apart(fn, rg, 9, 2)) return rc;
+  return launch_mesh_color_integrate(K, H, W, image, depth, alpha, views, tanfov, Vm, vertices, normals, alpha_min, depth_tol, two_sided, csum, wsum,
+                                     reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t gm_mesh_color_spread_workspace_bytes(int Vm) { return mesh_color_spread_workspace_bytes(Vm); }
+int gm_mesh_color_spread(int Vm, int F, const int* faces, const int* adj_offsets, const int* adj_faces, const unsigned char* seen, int iterations,
+                         const float* fallback, float* colors, unsigned char* out_has, int* out_counts, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  const char* fn = "gm_mesh_color_spread";
+  if (int rc = check_color_mesh(fn, Vm, F)) return rc;
+  if (iterations < 0) { set_error("%s: iterations = %d (negative)", fn, iterations); return GM_ERR_INVALID_ARG; }
+  if (!fallback || !out_counts || !workspace || (Vm > 0 && (!seen || !colors || !out_has)) || (Vm > 0 && F > 0 && (!faces || !adj_offsets || !adj_faces))) {
+    set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG;
+  }
+  const ByteRange rg[8] = {{faces, 12 * (size_t)F, "faces"}, {adj_offsets, Vm > 0 ? 4 * ((size_t)Vm + 1) : 0, "adj_offsets"},
+                           {adj_faces, 12 * (size_t)F, "adj_faces"}, {seen, (size_t)Vm, "seen"}, {colors, 12 * (size_t)Vm, "colors"},
+                           {out_has, (size_t)Vm, "out_has"}, {out_counts, 8, "out_counts"}, {workspace, workspace_bytes, "workspace"}};
+  if (int rc = check_outputs_apart(fn, rg, 8, 4)) return rc;
+  const size_t need = mesh_color_spread_workspace_bytes(Vm);
+  if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
+  return launch_mesh_color_spread(Vm, F, faces, adj_offsets, adj_faces, seen, iterations, fallback, colors, out_has, out_counts, workspace,
+                                  workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
 int gm_deform(int N, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
               const float* cov, const float* pos, float* pos_out, float* cov_out, float* rot_out, float* cov6_out,
               void* stream) {

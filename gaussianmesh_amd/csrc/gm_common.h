@@ -570,6 +570,16 @@ int launch_mesh_collapse_round(int Vm, const float* V, const float* Q, int F, co
                                const int* edges, const int* uses, float min_cos, float max_error, unsigned char* selected, int* from, int* to,
                                unsigned long long* key, int* count, void* ws, size_t ws_bytes, hipStream_t s);
 size_t mesh_collapse_round_workspace_bytes(int Vm);
+// gm_mesh_color.hip: vertex normals, the views' renders fused into vertex colours, and their spread over the unseen vertices
+// (fallback: three floats on the host)
+int launch_mesh_vertex_normals(int Vm, int F, const float* vertices, const int* faces, const int* off, const int* adj, float* out, hipStream_t s);
+int launch_mesh_color_integrate(int K, int H, int W, const float* image, const float* depth, const float* alpha, const float* views,
+                                const float* tans, int Vm, const float* vertices, const float* normals, float alpha_min, float depth_tol,
+                                int two_sided, float* csum, float* wsum, hipStream_t s);
+int launch_mesh_color_spread(int Vm, int F, const int* faces, const int* off, const int* adj, const unsigned char* seen, int iterations,
+                             const float* fallback, float* colors, unsigned char* out_has, int* out_counts, void* ws, size_t ws_bytes,
+                             hipStream_t s);
+size_t mesh_color_spread_workspace_bytes(int Vm);
 
 // number of set bits of a wave-wide 64-bit mask (a ballot) at positions BELOW the calling lane: v_mbcnt_lo + v_mbcnt_hi, two
 // vector instructions and no per-lane mask registers (popcount(mask & lanes_lt) costs four and two registers)

@@ -158,10 +158,37 @@ def read_obj(path):
     return np.asarray(verts, np.float64).reshape(-1, 3), np.asarray(faces, np.int32).reshape(-1, 3)
 
 
-def write_obj(path, vertices, faces):
+def read_obj_colors(path):
+    """The vertex colours of an OBJ whose `v` records are `v x y z r g b` (write_obj(colors=), MeshLab, Blender): float32 [V,3], one row
+    per `v` record in order; None when no `v` record has six values (one with fewer among coloured ones reads as NaN)."""
+    cols, any_colour = [], False
+    with open(path) as f:
+        for line in f:
+            tok = line.split()
+            if tok and tok[0] == "v":
+                if len(tok) >= 7:
+                    any_colour = True
+                    cols.append((float(tok[4]), float(tok[5]), float(tok[6])))
+                else:
+                    cols.append((math.nan, math.nan, math.nan))
+    return np.asarray(cols, np.float32).reshape(-1, 3) if any_colour else None
+
+
+def write_obj(path, vertices, faces, colors=None):
+    """`v x y z` and `f a b c` records (%.17g: a float64 survives).  colors [V,3]: the records are `v x y z r g b`, the colours as %.9g
+    (a float32 survives); read_obj ignores the extra values, read_obj_colors returns them."""
+    verts = np.asarray(vertices, np.float64)
+    if colors is not None:
+        cols = np.asarray(colors, np.float32).reshape(-1, 3)
+        if cols.shape[0] != verts.shape[0]:
+            raise ValueError("write_obj: %d vertices and %d colours" % (verts.shape[0], cols.shape[0]))
     with open(path, "w") as f:
-        for v in np.asarray(vertices, np.float64):
-            f.write("v %.17g %.17g %.17g\n" % (v[0], v[1], v[2]))
+        if colors is None:
+            for v in verts:
+                f.write("v %.17g %.17g %.17g\n" % (v[0], v[1], v[2]))
+        else:
+            for v, c in zip(verts, cols):
+                f.write("v %.17g %.17g %.17g %.9g %.9g %.9g\n" % (v[0], v[1], v[2], c[0], c[1], c[2]))
         for t in np.asarray(faces, np.int64):
             f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))
 

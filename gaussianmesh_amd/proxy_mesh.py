@@ -4,7 +4,7 @@ is what train_mesh --input_mesh, SingleObjectDeform, bind_points, ArapSolver, pi
 a NeuS trainer, MeshLab and MeshFix for it.  Definition, ABI and rules: INTEGRATION.md section T.
 
     V, F = from_cloud(model, cameras, resolution=96)          # device tensors; io.write_obj(path, V.cpu(), F.cpu())
-    python -m gaussianmesh_amd.proxy_mesh --gaussian cloud.ply --cameras cameras.json --out proxy.obj
+    python -m gaussianmesh_amd.proxy_mesh --gaussian cloud.ply --cameras cameras.json --out proxy.obj [--vertex_colors]
 """
 import argparse
 import ctypes as C
@@ -321,13 +321,21 @@ def fuse_cloud(pc, cameras, pipe=None, bg_gaussian=None, resolution=96, bounds=N
 
 def from_cloud(pc, cameras, pipe=None, bg_gaussian=None, resolution=96, bounds=None, views_per_call=8, trunc_voxels=3.0, alpha_min=0.5,
                carve=True, min_weight=1, keep="largest", bg_color=None, target_faces=None, simplify_max_rounds=1024, fill_holes=None,
-               fill_boundary="none"):
+               fill_boundary="none", vertex_colors=False):
     """The proxy mesh of a trained cloud: (vertices float32 [V,3], faces int32 [F,3]) on the device: fuse_cloud(...).extract(min_weight,
-    keep, target_faces, simplify_max_rounds, fill_holes, fill_boundary)."""
+    keep, target_faces, simplify_max_rounds, fill_holes, fill_boundary).  vertex_colors=True: (vertices, faces, colors float32 [V,3]) -
+    the same mesh, and the colours of its vertices (the FINAL ones: after keep and after the simplification) from a second rendering of
+    the views: mesh_color.color_from_cloud with depth_tol = the volume's trunc and the spread on."""
     vol = fuse_cloud(pc, cameras, pipe=pipe, bg_gaussian=bg_gaussian, resolution=resolution, bounds=bounds, views_per_call=views_per_call,
                      trunc_voxels=trunc_voxels, alpha_min=alpha_min, carve=carve, bg_color=bg_color)
-    return vol.extract(min_weight=min_weight, keep=keep, target_faces=target_faces, simplify_max_rounds=simplify_max_rounds, fill_holes=fill_holes,
+    V, F = vol.extract(min_weight=min_weight, keep=keep, target_faces=target_faces, simplify_max_rounds=simplify_max_rounds, fill_holes=fill_holes,
                        fill_boundary=fill_boundary)
+    if not vertex_colors:
+        return V, F
+    from .mesh_color import color_from_cloud
+    colors = color_from_cloud(pc, cameras, V, F, pipe=pipe, bg_gaussian=bg_gaussian, views_per_call=views_per_call, alpha_min=alpha_min,
+                              depth_tol=vol.trunc, spread=True, bg_color=bg_color)
+    return V, F, colors
 
 
 def _load_model(path, mesh_gaussian, dev):
@@ -362,6 +370,8 @@ def main(argv=None):
     ap.add_argument("--simplify_max_rounds", type=int, default=1024)
     ap.add_argument("--fill_holes", type=int, metavar="N", help="close unobserved holes first: N diffusion iterations (gm_tsdf_fill)")
     ap.add_argument("--fill_boundary", choices=("none", "free"), default="none", help="free: beyond the grid is free space")
+    ap.add_argument("--vertex_colors", action="store_true", help="colour the final mesh from the views (mesh_color): v x y z r g b records")
+    ap.add_argument("--color_spread", type=int, metavar="N", help="steps of the spread over vertices no view coloured (default: min(vertices, 1024))")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("proxy_mesh needs a HIP (cuda) device; there is no CPU path")
@@ -382,12 +392,19 @@ def main(argv=None):
                        fill_boundary=a.fill_boundary)
     torch.cuda.synchronize()
     t3 = time.perf_counter()
+    colors = color_stats = None
+    if a.vertex_colors:                                                # on the final mesh, from a second rendering of the views
+        from .mesh_color import _color_from_cloud
+        colors, vc = _color_from_cloud(pc, cams, V, F, None, None, 8, a.alpha_min, vol.trunc, False, True if a.color_spread is None else a.color_spread,
+                                       None)
+        colors, color_stats = colors.cpu().numpy(), vc.stats           # (the copy waits for the device)
+    t_write = time.perf_counter()
     v, f = V.cpu().numpy(), F.cpu().numpy()
-    gio.write_obj(a.out, v, f)
+    gio.write_obj(a.out, v, f, colors)
     t4 = time.perf_counter()
     out = dict(vertices=int(v.shape[0]), faces=int(f.shape[0]), components_dropped=int(vol.stats["components_dropped"]),
                boundary_edges=boundary_edges(f), grid=[vol.nx, vol.ny, vol.nz], views=len(cams),
-               seconds=dict(load=t1 - t0, render_fuse=t2 - t1, extract=t3 - t2, write=t4 - t3))
+               seconds=dict(load=t1 - t0, render_fuse=t2 - t1, extract=t3 - t2, write=t4 - t_write))
     if a.target_faces is not None:                                     # (extract's time then includes the simplification)
         out.update(faces_before_simplify=vol.stats["faces_before_simplify"], simplify_rounds=vol.stats["simplify_rounds"],
                    simplify_reached=vol.stats["simplify_reached"])
@@ -396,6 +413,9 @@ def main(argv=None):
         out.update(fill_iterations=vol.stats["fill_iterations"], filled_voxels=vol.stats["filled_voxels"],
                    unreached_voxels=vol.stats["unreached_voxels"])
         out["seconds"]["fill"] = vol.stats["seconds_fill"]
+    if a.vertex_colors:
+        out.update(colored_vertices=color_stats["seen"], spread_vertices=color_stats["filled"], uncolored_vertices=color_stats["unreached"])
+        out["seconds"]["color"] = t_write - t3
     print(json.dumps(out))
     return 0
 

@@ -467,6 +467,55 @@ int gm_mesh_collapse_round(int Vm, const float* vertices, const float* quadrics,
                            int E, const int* edges, const int* edge_faces, float min_cos, float max_error, unsigned char* out_selected, int* out_from,
                            int* out_to, unsigned long long* out_key, int* out_count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Colour on the proxy mesh (mesh_color.VertexColors / color_from_cloud, proxy_mesh.from_cloud(vertex_colors=True)): vertex normals, the
+ * views' own renders fused into one colour per vertex, and a spread over the vertices no view coloured.  Defined by arithmetic, as
+ * gm_tsdf_integrate is - float32, no contraction, correctly rounded division, the order written here - and tests/mesh_color_ref.py
+ * restates all three in numpy bit for bit.  ALL ARRAYS ON THE DEVICE unless said otherwise.  vertices float [Vm,3], faces int32 [F,3],
+ * (adj_offsets int32 [Vm+1], adj_faces int32 [3F]): the faces at each vertex in ascending face order (deform.vertex_face_adjacency).
+ * gm_mesh_vertex_normals: out_normals float [Vm,3], unnormalised and area-weighted.  Per vertex i from N = 0, over j = adj_offsets[i] ..
+ *   adj_offsets[i + 1] - 1 in this order, f = adj_faces[j], (a, b, c) = faces[f]: e1 = V[b] - V[a], e2 = V[c] - V[a],
+ *   cr = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y - e1.y e2.x) - each product rounds, then the difference -, N = N + cr.
+ *   A vertex without faces gets (0, 0, 0).
+ * gm_mesh_color_integrate: image float [K,3,H,W], depth / alpha float [K,H,W] the rasterizer's maps (depth alpha-weighted, not normalised),
+ *   views float [K,16] the world_view_transform rows (stored transposed), tanfov float [K,2]; csum float [Vm,3] and wsum float [Vm] are
+ *   STATE, read and written.  Per vertex P with normal N and per view k = 0 .. K-1 in this order:
+ *   1. xv = ((P.x v[0] + P.y v[4]) + P.z v[8]) + v[12], yv (v[1 + ..]), zv (v[2 + ..]); not (zv > 0): skip the view.
+ *   2. px, py, fx = floor(px + 0.5), fy = floor(py + 0.5) exactly as gm_tsdf_integrate; outside the image: skip.
+ *   3. a = alpha[k, fy, fx]; not (a >= alpha_min): skip.
+ *   4. s = depth[k, fy, fx] / a - zv; not (s >= -depth_tol and s <= depth_tol): skip - something else is in front, or the vertex is off
+ *      the rendered surface.
+ *   5. nv.x = (N.x v[0] + N.y v[4]) + N.z v[8], nv.y with v[1], v[5], v[9], nv.z with v[2], v[6], v[10].
+ *   6. d = (nv.x xv + nv.y yv) + nv.z zv; with two_sided == 0: not (d < 0): skip - the vertex faces away.
+ *   7. nn = (nv.x nv.x + nv.y nv.y) + nv.z nv.z, pp = (xv xv + yv yv) + zv zv, wgt = (d d) / (nn pp): the squared cosine of the viewing
+ *      angle; not (wgt > 0): skip (a zero normal gives 0 / 0).
+ *   8. c[ch] = image[k, ch, fy, fx]; a channel with c - c != 0 (NaN, inf): skip.
+ *   9. csum[ch] = csum[ch] + wgt c[ch], wsum = wsum + wgt.
+ *   Every comparison is false on NaN.  K views in one call equal K calls of one view each, bit for bit.  One thread per vertex.
+ * gm_mesh_color_spread: seen uint8 [Vm] (non-zero: the vertex has a colour), colors float [Vm,3] in / out (read where seen), fallback
+ *   three floats ON THE HOST, out_has uint8 [Vm], out_counts int32 [2] = {filled: has and not seen, unreached: not has}.  State (colour,
+ *   has), has_0 = seen, colour_0 = colors where seen and +0 elsewhere.  Step t = 0 .. iterations-1 is a Jacobi step that reads only
+ *   (colour_t, has_t): a seen vertex keeps both; otherwise sum = 0, n = 0, and over j in adjacency order and within face adj_faces[j] its
+ *   corners q = 0, 1, 2 with u = faces[f][q]: u != i and has_t[u]: sum = sum + colour_t[u] per channel, n++ (a neighbour across an
+ *   interior edge counts once per shared face); n > 0: colour_{t+1}[i] = sum / (float)n, has_{t+1}[i] = 1; otherwise both carry over.
+ *   After the last step colors = has ? colour : fallback.  iterations is a REACH, not a convergence test: after n steps exactly the
+ *   vertices within n edges of a seen one have a value; iterations == 0 returns the seen colours and fallback elsewhere.  One launch per
+ *   step between two copies of the state, one of them in the workspace; the last step always writes colors.  No atomics.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: a negative Vm, F or K, Vm or F above (2^31 - 1) / 3, H or W outside [1, 2^24], a NaN
+ * alpha_min, a NaN or negative depth_tol, iterations < 0, a NULL pointer that would be read or written (fallback, out_counts and workspace
+ * always), an output - out_normals; csum, wsum; colors, out_has, out_counts, workspace - overlapping an input or another output; with
+ * GM_ERR_BUFFER: a workspace below gm_mesh_color_spread_workspace_bytes(Vm) (about 13 bytes a vertex, monotonic, positive at 0).  Vm == 0,
+ * K == 0 and iterations == 0 succeed (Vm == 0: out_counts = {0, 0}).  Vertex ids read from faces, face ids and offsets read from the CSR
+ * are forced into range: no fault, no meaning.  Stream-ordered, no device allocation, no host synchronisation. */
+int gm_mesh_vertex_normals(int Vm, int F, const float* vertices, const int* faces, const int* adj_offsets, const int* adj_faces, float* out_normals,
+                           void* stream);
+int gm_mesh_color_integrate(int K, int H, int W, const float* image, const float* depth, const float* alpha, const float* views, const float* tanfov,
+                            int Vm, const float* vertices, const float* normals, float alpha_min, float depth_tol, int two_sided, float* csum,
+                            float* wsum, void* stream);
+size_t gm_mesh_color_spread_workspace_bytes(int Vm);
+int gm_mesh_color_spread(int Vm, int F, const int* faces, const int* adj_offsets, const int* adj_faces, const unsigned char* seen, int iterations,
+                         const float* fallback, float* colors, unsigned char* out_has, int* out_counts, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* Mesh-driven deformation of bound Gaussians; replaces the Jittor tensor algebra of
  * SingleObjectDeform.deform_gaussian (edittool/__init__.py:116-131), tensor-in form:
  *   tri int32 [N,3] vertex ids of the bound face, w float [N,3] barycentric weights,
