@@ -35,6 +35,7 @@
 //   same kernels: an item's bits do not depend on the batch it rides in.  No workgroup reads what another item's wrote.
 // Conventions of gm_closest.hip: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
+#include "gm_check.h"
 #include "gm_mat3.h"
 
 namespace gm {
@@ -75,11 +76,6 @@ struct ArapWs {
     return k;
   }
 };
-
-size_t arap_workspace_bytes(int Vm) {
-  ArapWs k = ArapWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 1));
-  return (size_t)k.end + 256;
-}
 
 // the proper rotation closest to F (max tr(Q^T F)); identity for rank <= 1
 __device__ __forceinline__ void arap_rotation(const double F[3][3], double Q[3][3]) {
@@ -338,17 +334,6 @@ static void arap_column_chain(int B, size_t slab, const ArapWs& k, int Vm, const
   }
 }
 
-int launch_arap_solve(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
-                      const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
-                      size_t ws_bytes, hipStream_t s) {
-  const size_t need = arap_workspace_bytes(Vm);
-  if (ws_bytes < need) { set_error("gm_arap_solve: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
-  arap_column_chain(1, 0, ArapWs::from(ws, (size_t)Vm), Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance,
-                    V_out, stats, s);
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
 // ---- the whole-chip global step (gm_arap_solve_grid): the same systems, the same stopping rule, rows over G = ceil(Vm / 256) workgroups ----
 // One row per thread, all three coordinates in that thread (the CSR row is read once for three products).  The ONLY synchronisation
 // between workgroups is the kernel boundary, so a CG step costs launches; the single-reduction recurrences of Chronopoulos & Gear
@@ -411,11 +396,6 @@ struct ArapGridWs {
     return k;
   }
 };
-
-size_t arap_grid_workspace_bytes(int Vm) {
-  ArapGridWs k = ArapGridWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 1));
-  return (size_t)k.end + 256;
-}
 
 // the sums of N rows of G workgroup slots, the same bits in every thread of every workgroup: each wave adds all G for itself, lane l
 // the slots l, l + 64, ... in ascending order, then the butterfly.  The order depends on G alone.  Reached by whole waves only.
@@ -667,39 +647,96 @@ static void arap_grid_chain(int B, size_t slab, const ArapGridWs& k, int Vm, con
   }
 }
 
-int launch_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
-                           const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
-                           size_t ws_bytes, hipStream_t s) {
-  const size_t need = arap_grid_workspace_bytes(Vm);
-  if (ws_bytes < need) { set_error("gm_arap_solve_grid: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
-  arap_grid_chain(1, 0, ArapGridWs::from(ws, (size_t)Vm), Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance,
-                  V_out, stats, s);
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+// gm_arap_solve, gm_arap_solve_grid and gm_arap_solve_batch: one set of refusals (B items: V_init, V_out and stats span B solves' worth;
+// need: the workspace the chosen chain takes)
+static int arap_args_checked(const char* fn, int B, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                             const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                             double* stats, void* workspace, size_t workspace_bytes, size_t need) {
+  if (Vm <= 0) { set_error("%s: Vm = %d (must be positive)", fn, Vm); return GM_ERR_INVALID_ARG; }
+  if (outer_iterations < 0) { set_error("%s: outer_iterations = %d (negative)", fn, outer_iterations); return GM_ERR_INVALID_ARG; }
+  if (cg_iterations < 1) { set_error("%s: cg_iterations = %d (at least 1)", fn, cg_iterations); return GM_ERR_INVALID_ARG; }
+  if (!(cg_tolerance >= 0.0) || cg_tolerance > 1.7976931348623157e308) {
+    set_error("%s: cg_tolerance must be finite and not negative", fn); return GM_ERR_INVALID_ARG;
+  }
+  if (!row_offsets || !cols || !weights || !V0 || !fixed || !V_init || !V_out || !workspace) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  // every meeting of two of these ranges is refused, the read-only ones included; V_out == V_init is the in-place call (V_init stands for both)
+  const ByteRange rg[5] = {{V0, 12 * (size_t)Vm, "V0", true}, {V_init, 12 * (size_t)Vm * B, "V_init", true},
+                           {V_out == V_init ? nullptr : V_out, 12 * (size_t)Vm * B, "V_out", true},
+                           {stats, 64 * (size_t)outer_iterations * B, "stats", true}, {workspace, workspace_bytes, "workspace", true}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
+  return GM_OK;
+}
+
+extern "C" {
+
+size_t gm_arap_workspace_bytes(int Vm) {
+  ArapWs k = ArapWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 1));
+  return (size_t)k.end + 256;
+}
+
+int gm_arap_solve(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
+                  const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
+                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = arap_args_checked("gm_arap_solve", 1, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out,
+                                 stats, workspace, workspace_bytes, gm_arap_workspace_bytes(Vm)))
+    return rc;
+  arap_column_chain(1, 0, ArapWs::from(workspace, (size_t)Vm), Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations,
+                    cg_tolerance, V_out, stats, reinterpret_cast<hipStream_t>(stream));
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
+}
+
+size_t gm_arap_grid_workspace_bytes(int Vm) {
+  ArapGridWs k = ArapGridWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 1));
+  return (size_t)k.end + 256;
+}
+
+int gm_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
+                       const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = arap_args_checked("gm_arap_solve_grid", 1, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance,
+                                 V_out, stats, workspace, workspace_bytes, gm_arap_grid_workspace_bytes(Vm)))
+    return rc;
+  arap_grid_chain(1, 0, ArapGridWs::from(workspace, (size_t)Vm), Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations,
+                  cg_tolerance, V_out, stats, reinterpret_cast<hipStream_t>(stream));
+  GM_HIP(hipGetLastError());
+  return GM_OK;
 }
 
 // ---- B solves in one chain (gm_arap_solve_batch): the chains above with the batch as the second grid dimension ----
-size_t arap_batch_workspace_bytes(int Vm, int B, int global_step) {
+size_t gm_arap_batch_workspace_bytes(int Vm, int B, int global_step) {
+  if (Vm <= 0 || B < 1 || B > GM_ARAP_BATCH_MAX || (global_step != 0 && global_step != 1)) return 0;
   size_t slab;
-  const size_t v = (size_t)(Vm > 0 ? Vm : 1), b = (size_t)(B > 0 ? B : 1);
-  return (size_t)(global_step ? ArapGridWs::batch(nullptr, v, b, &slab).end : ArapWs::batch(nullptr, v, b, &slab).end) + 256;
+  return (size_t)(global_step ? ArapGridWs::batch(nullptr, (size_t)Vm, (size_t)B, &slab).end : ArapWs::batch(nullptr, (size_t)Vm, (size_t)B, &slab).end) + 256;
 }
 
-int launch_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
-                            const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
-                            double* stats, void* ws, size_t ws_bytes, hipStream_t s) {
-  const size_t need = arap_batch_workspace_bytes(Vm, B, global_step);
-  if (ws_bytes < need) { set_error("gm_arap_solve_batch: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
+int gm_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                        const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                        double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "gm_arap_solve_batch";
+  if (B < 1 || B > GM_ARAP_BATCH_MAX) { set_error("%s: B = %d (1 .. %d)", fn, B, GM_ARAP_BATCH_MAX); return GM_ERR_INVALID_ARG; }
+  if (global_step != 0 && global_step != 1) { set_error("%s: global_step = %d (0 column, 1 grid)", fn, global_step); return GM_ERR_INVALID_ARG; }
+  if (int rc = arap_args_checked(fn, B, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats,
+                                 workspace, workspace_bytes, gm_arap_batch_workspace_bytes(Vm, B, global_step)))
+    return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   size_t slab;
   if (global_step) {
-    const ArapGridWs k = ArapGridWs::batch(ws, (size_t)Vm, (size_t)B, &slab);
+    const ArapGridWs k = ArapGridWs::batch(workspace, (size_t)Vm, (size_t)B, &slab);
     arap_grid_chain(B, slab, k, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats, s);
   } else {
-    const ArapWs k = ArapWs::batch(ws, (size_t)Vm, (size_t)B, &slab);
+    const ArapWs k = ArapWs::batch(workspace, (size_t)Vm, (size_t)B, &slab);
     arap_column_chain(B, slab, k, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats, s);
   }
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

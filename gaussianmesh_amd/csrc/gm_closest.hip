@@ -64,6 +64,7 @@
 //
 // Conventions of gm_knn_nearest: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
+#include "gm_check.h"
 #include "gm_spatial.h"
 #include "gm_wave.h"
 #include <cfloat>
@@ -96,11 +97,6 @@ struct CfWs {
     return k;
   }
 };
-
-size_t closest_face_workspace_bytes(int N, int F) {
-  CfWs k = CfWs::from(nullptr, (size_t)(N > 0 ? N : 1), (size_t)(F > 0 ? F : 1));
-  return (size_t)k.end + 256;
-}
 
 // Morton code of a face: that of its centroid against the vertices' bounding box
 __global__ __launch_bounds__(256) void cf_face_morton(int F, int Vm, const float* __restrict__ verts, const int* __restrict__ faces,
@@ -249,12 +245,29 @@ __global__ __launch_bounds__(256) void cf_query(int N, const float* __restrict__
   if (out_closest) { out_closest[3 * (size_t)q] = bqx; out_closest[3 * (size_t)q + 1] = bqy; out_closest[3 * (size_t)q + 2] = bqz; }
 }
 
-int launch_closest_face(int N, const float* points, int Vm, const float* vertices, int F, const int* faces, float* out_d2, int* out_face,
-                        float* out_closest, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (N <= 0) return 0;
-  const size_t need = closest_face_workspace_bytes(N, F);
-  if (ws_bytes < need) { set_error("gm_closest_face: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
-  CfWs k = CfWs::from(ws, (size_t)N, (size_t)F);
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+extern "C" {
+
+size_t gm_closest_face_workspace_bytes(int N, int F) {
+  CfWs k = CfWs::from(nullptr, (size_t)(N > 0 ? N : 1), (size_t)(F > 0 ? F : 1));
+  return (size_t)k.end + 256;
+}
+
+int gm_closest_face(int N, const float* points, int Vm, const float* vertices, int F, const int* faces, float* out_d2, int* out_face,
+                    float* out_closest, void* workspace, size_t workspace_bytes, void* stream) {
+  if (N < 0 || Vm < 0 || F < 0) { set_error("gm_closest_face: negative size N=%d Vm=%d F=%d", N, Vm, F); return GM_ERR_INVALID_ARG; }
+  if (N == 0) return GM_OK;
+  if (F == 0 || Vm == 0) { set_error("gm_closest_face: empty mesh (F == %d, Vm == %d)", F, Vm); return GM_ERR_INVALID_ARG; }
+  if (!points || !vertices || !faces || !out_d2 || !out_face || !workspace) { set_error("gm_closest_face: null pointer"); return GM_ERR_INVALID_ARG; }
+  const size_t need = gm_closest_face_workspace_bytes(N, F);
+  if (workspace_bytes < need) { set_error("gm_closest_face: workspace too small (%zu < %zu)", workspace_bytes, need); return GM_ERR_BUFFER; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  CfWs k = CfWs::from(workspace, (size_t)N, (size_t)F);
   if (int rc = launch_point_bbox(Vm, vertices, k.front.bbox_partial, k.front.bbox, s)) return rc;
   hipLaunchKernelGGL(cf_face_morton, dim3((F + 255) / 256), dim3(256), 0, s, F, Vm, vertices, faces, k.front.bbox, k.fset.keys[0]);
   if (int rc = launch_point_morton(N, points, k.front.bbox, k.qset.keys[0], s)) return rc;
@@ -267,7 +280,7 @@ int launch_closest_face(int N, const float* points, int Vm, const float* vertice
   hipLaunchKernelGGL(cf_query, dim3((N + 255) / 256), dim3(256), 0, s, N, points, q.idx, F, f.keys, k.recs, k.boxes, nboxes, k.sboxes,
                      nsuper, k.front.bbox, out_d2, out_face, out_closest);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

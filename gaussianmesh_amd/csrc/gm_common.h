@@ -392,7 +392,6 @@ struct RasterArgs {
 };
 
 int launch_preprocess(const RasterArgs& a, GeomState& g, int* radii);
-int launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 int launch_preprocess_bwd(const RasterArgs& a, GeomState& g, const int* radii, float* dL_dmean2D, float* dL_dconic,
                           float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                           float* dL_dscale, float* dL_drot, const struct ShAdamArgs* sh_adam = nullptr);   // reads g.grad_acc, writes every gradient output
@@ -438,29 +437,9 @@ int launch_blend_weights(const GeomState& g, const uint2* pairs, ImageState& img
 // gm_backward_aux: dL/dmean3D += dL/dz (view[2], view[6], view[10]); dL/dz = grad_acc[12 i + 9] (written to dL_dz too when given)
 int launch_depth_grad(int P, const GeomState& g, const float* viewmatrix, float* dL_dmean3D, float* dL_dz, hipStream_t s);
 
-int launch_deform(int N, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
-                  const float* cov, const float* pos, float* pos_out, float* cov_out, float* rot_out, float* cov6_out,
-                  hipStream_t s);
-int launch_sh_colors(int N, int deg, int M, const float* pos, const float* campos, const float* rot,
-                     const float* shs, float* rgb, hipStream_t s);
-int launch_deform_shade(int N, int deg, int M, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
-                        const float* cov, const float* pos, const float* shs, const float* campos, float* pos_out,
-                        float* cov6_out, float* rgb_out, float* cov_out, float* rot_out, hipStream_t s);
 int launch_deform_shade_pre(const RasterArgs& r, GeomState& g, int* radii, int deg, const int* tri, const float* w, const float* packed,
                             const float* cov, const float* pos, const float* shs, float* pos_out, float* cov6_out, float* rgb_out,
                             const struct DepthSlab* slab = nullptr, bool cov6 = false);
-int launch_pack_mesh_state(int Vm, const float* state, const float* verts, float* packed, hipStream_t s);
-int launch_deform_shade_packed(int N, int deg, int M, const int* tri, const float* w, const float* packed, const float* cov,
-                               const float* pos, const float* shs, const float* campos, float* pos_out, float* cov6_out,
-                               float* rgb_out, float* cov_out, float* rot_out, hipStream_t s);
-int launch_cov_to_scale_rot(int N, const float* cov, float* scales, float* rots, hipStream_t s);
-// gm_shrot.hip: SH rows re-expressed in the frame rot turns away from (shs_out == shs allowed)
-int launch_sh_rotate(int N, int deg, int M, const float* shs, const float* rot, float* shs_out, hipStream_t s);
-int launch_mesh_rs(int Vm, const float* V0, const float* V1, const int* faces, const int* adj_offsets, const int* adj_faces, float* R,
-                   float* S, float* state, float* packed, hipStream_t s);
-// the packed gather tables of `frames` deformation frames in one launch (gridDim.z = frame): V1[f] -> packed[f]
-int launch_mesh_rs_batch(int frames, int Vm, const float* V0, const float* const* V1, const int* faces, const int* adj_offsets, const int* adj_faces,
-                         float* const* packed, hipStream_t s);
 // one frame of a batched fused pass (gm_deform.hip): what differs between the frames that share one pass over the static cloud
 struct BatchFrameArgs {
   const float *packed, *viewmatrix, *projmatrix, *cam_pos;
@@ -475,30 +454,6 @@ int launch_deform_shade_pre_batch(int frames, const BatchFrameArgs* fr, int P, i
 int launch_scene_shade_pre_batch(int frames, const BatchFrameArgs* fr, const uint32_t* deformed, int n_obj, const int* object_rows, int P, int deg,
                                  int W, int H, int tile_cull, const float* pos, const float* scales, const float* rots, const float* shs,
                                  const float* opacities, const int* tri, const float* w, const float* cov, int debug, hipStream_t s);
-int launch_ssim_fwd(const float* img1, const float* img2, int planes, int H, int W, float* d_mu1, float* d_e11, float* d_e12,
-                    float* partial, hipStream_t s);
-int launch_loss_combine(const float* partial, long long n, double c_ssim, double c_l1, double offset, float* out, hipStream_t s);
-int launch_ssim_bwd(const float* img1, const float* img2, const float* d_mu1, const float* d_e11, const float* d_e12, int planes,
-                    int H, int W, const float* g_ssim, const float* g_l1, float* dL_dimg1, hipStream_t s);
-// the same two kernels' bodies with an 8-bit target composited on load (three planes; gm_loss.hip U8Target)
-int launch_ssim_fwd_u8(const float* img1, const unsigned char* rgb, const unsigned char* mask, size_t mask_stride, const float* bg, int H,
-                       int W, float* d_mu1, float* d_e11, float* d_e12, float* partial, hipStream_t s);
-int launch_ssim_bwd_u8(const float* img1, const unsigned char* rgb, const unsigned char* mask, size_t mask_stride, const float* bg,
-                       const float* d_mu1, const float* d_e11, const float* d_e12, int H, int W, const float* g_ssim, const float* g_l1,
-                       float* dL_dimg1, hipStream_t s);
-struct ActArgs {                 // mesh-bound parameter -> rasterizer-input map (gm_train.hip)
-  int N;
-  float alpha;
-  const float *bc, *dist, *scaling, *rotation, *opacity, *v1, *v2, *v3, *normal, *r;
-};
-struct AdamTensor {
-  float* p; const float* g; float* m; float* v;
-  unsigned long long n;
-  float step_lo, step_hi;      // lr * sqrt(1-b2^t)/(1-b1^t) for elements with (index % period) < split / the others
-  unsigned period, split;      // period == 0: one rate (step_lo) for the whole tensor
-  unsigned active;             // 0: every element; else only elements with (index % period) < active (rounded up to a 16-byte granule) are touched
-};
-struct AdamTable { AdamTensor t[8]; int count; float b1, b2, eps, omb1, omb2; };   // omb = (float)(1 - beta), formed in double
 // jittor.nn.Adam's rule for one element (jittor/optim.py Adam.step), spelled with explicit fused multiply-adds so that adam_kernel
 // (gm_train.hip, contraction allowed) and the SH step fused into the preprocess backward (gm_preprocess.hip, contraction off) round alike
 __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, float b1, float b2, float c1, float c2, float eps, float st) {
@@ -512,74 +467,6 @@ struct ShAdamArgs {
   int rows;                      // trainable rows (the operand may continue with frozen rows behind them)
   float b1, b2, c1, c2, eps, step_lo, step_hi;   // step_lo: coefficient 0 (the reference's "f_dc" group), step_hi: the others ("f_rest")
 };
-int launch_mesh_activate_fwd(const ActArgs& a, float* xyz, float* scales, float* rots, float* opac, float mr_weight, float* mr_partial,
-                             hipStream_t s);
-int launch_mesh_activate_bwd(const ActArgs& a, const float* d_xyz, const float* d_scales, const float* d_rots, const float* d_opac,
-                             float* d_bc, float* d_dist, float* d_scaling, float* d_rotation, float* d_opacity, float mr_weight,
-                             const float* d_mr, hipStream_t s);
-int launch_plain_activate_fwd(int N, const float* xyz_in, const float* scaling, const float* rotation, const float* opacity, float* xyz,
-                              float* scales, float* rots, float* opac, hipStream_t s);
-int launch_plain_activate_bwd(int N, const float* scaling, const float* rotation, const float* opacity, const float* g_xyz,
-                              const float* g_scales, const float* g_rots, const float* g_opac, float* d_xyz, float* d_scaling,
-                              float* d_rotation, float* d_opacity, hipStream_t s);
-int launch_adam(const AdamTable& tab, hipStream_t s);
-int launch_densify_stats(int N, const int* radii, const float* grad2d, float* max_radii2D, float* grad_accum, float* denom, hipStream_t s);
-int launch_knn(int P, const float* points, float* meanDists, void* ws, size_t ws_bytes, hipStream_t s);
-size_t knn_workspace_bytes(int P);
-int launch_knn_nearest(int Pq, const float* query, int Pr, const float* ref, float* out_d2, int* out_idx, void* ws, size_t ws_bytes,
-                       hipStream_t s);
-size_t knn_nearest_workspace_bytes(int Pq, int Pr);
-int launch_closest_face(int N, const float* points, int Vm, const float* vertices, int F, const int* faces, float* out_d2, int* out_face,
-                        float* out_closest, void* ws, size_t ws_bytes, hipStream_t s);
-size_t closest_face_workspace_bytes(int N, int F);
-int launch_arap_solve(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
-                      const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
-                      size_t ws_bytes, hipStream_t s);
-size_t arap_workspace_bytes(int Vm);
-int launch_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
-                           const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats, void* ws,
-                           size_t ws_bytes, hipStream_t s);
-size_t arap_grid_workspace_bytes(int Vm);
-int launch_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
-                            const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
-                            double* stats, void* ws, size_t ws_bytes, hipStream_t s);
-size_t arap_batch_workspace_bytes(int Vm, int B, int global_step);
-int launch_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const float* vertices, int F, const int* faces, float t_min,
-                    float t_max, float* out_t, int* out_face, float* out_uv, void* ws, size_t ws_bytes, hipStream_t s);
-size_t ray_mesh_workspace_bytes(int R, int F);
-unsigned long long ray_mesh_blocks(int R, int F);
-int launch_mesh_geodesic(int Vm, const int* row_offsets, const int* cols, const float* lengths, int B, const int* source_offsets,
-                         const int* sources, float max_distance, int sweeps, int resume, float* dist, int* unsettled, void* ws,
-                         size_t ws_bytes, hipStream_t s);
-size_t mesh_geodesic_workspace_bytes(int Vm, int B, int sweeps);
-// gm_tsdf.hip: depth / opacity maps -> signed distance volume -> indexed mesh (origin: three floats on the host)
-int launch_tsdf_integrate(int K, int H, int W, const float* depth, const float* alpha, const float* views, const float* tans, int nx, int ny,
-                          int nz, const float* origin, float voxel, float trunc, float alpha_min, int carve, float* tsdf, float* weight,
-                          hipStream_t s);
-int launch_surface_nets(int nx, int ny, int nz, const float* origin, float voxel, const float* tsdf, const float* weight, float min_weight,
-                        int max_vertices, float* out_vertices, int max_faces, int* out_faces, int* out_counts, void* ws, size_t ws_bytes,
-                        hipStream_t s);
-size_t surface_nets_workspace_bytes(int nx, int ny, int nz);
-// gm_tsdf_fill.hip: diffuse the observed distances into the unobserved samples (the inputs are only read)
-int launch_tsdf_fill(int nx, int ny, int nz, const float* tsdf_in, const float* weight_in, float min_weight, int iterations, int boundary_free,
-                     float fill_weight, float* tsdf_out, float* weight_out, int* out_counts, void* ws, size_t ws_bytes, hipStream_t s);
-size_t tsdf_fill_workspace_bytes(int nx, int ny, int nz);
-// gm_simplify.hip: error quadrics, and one round of independent edge collapses (subset placement)
-int launch_mesh_quadrics(int Vm, const float* V, int F, const int* faces, const int* off, const int* adj, float* Q, hipStream_t s);
-int launch_mesh_collapse_round(int Vm, const float* V, const float* Q, int F, const int* faces, const int* off, const int* adj, int E,
-                               const int* edges, const int* uses, float min_cos, float max_error, unsigned char* selected, int* from, int* to,
-                               unsigned long long* key, int* count, void* ws, size_t ws_bytes, hipStream_t s);
-size_t mesh_collapse_round_workspace_bytes(int Vm);
-// gm_mesh_color.hip: vertex normals, the views' renders fused into vertex colours, and their spread over the unseen vertices
-// (fallback: three floats on the host)
-int launch_mesh_vertex_normals(int Vm, int F, const float* vertices, const int* faces, const int* off, const int* adj, float* out, hipStream_t s);
-int launch_mesh_color_integrate(int K, int H, int W, const float* image, const float* depth, const float* alpha, const float* views,
-                                const float* tans, int Vm, const float* vertices, const float* normals, float alpha_min, float depth_tol,
-                                int two_sided, float* csum, float* wsum, hipStream_t s);
-int launch_mesh_color_spread(int Vm, int F, const int* faces, const int* off, const int* adj, const unsigned char* seen, int iterations,
-                             const float* fallback, float* colors, unsigned char* out_has, int* out_counts, void* ws, size_t ws_bytes,
-                             hipStream_t s);
-size_t mesh_color_spread_workspace_bytes(int Vm);
 
 // number of set bits of a wave-wide 64-bit mask (a ballot) at positions BELOW the calling lane: v_mbcnt_lo + v_mbcnt_hi, two
 // vector instructions and no per-lane mask registers (popcount(mask & lanes_lt) costs four and two registers)

@@ -8,6 +8,7 @@
 // One thread per Gaussian; the per-vertex tables (dV, R, S: 84 B x Vm, ~0.6 MB for a 7.5k-vertex proxy mesh)
 // stay L2-resident, the per-Gaussian streams (72 B in, 84-108 B out) are the HBM traffic.
 #include "gm_common.h"
+#include "gm_check.h"
 #pragma clang fp contract(off)
 #include "gm_sh.h"
 #include "gm_stage.h"
@@ -63,17 +64,6 @@ __global__ __launch_bounds__(256) void deform_kernel(int N, const int* __restric
   }
 }
 
-int launch_deform(int N, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
-                  const float* cov, const float* pos, float* pos_out, float* cov_out, float* rot_out, float* cov6_out,
-                  hipStream_t s) {
-  StageScope sc(ST_DEFORM, s);
-  if (N > 0)
-    hipLaunchKernelGGL(deform_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, tri, w, dV, Rv, Sv, cov, pos, pos_out, cov_out,
-                       rot_out, cov6_out);
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
 __global__ __launch_bounds__(256) void sh_colors_kernel(int N, int deg, int M, const float* __restrict__ pos,
                                                         const float* __restrict__ campos, const float* __restrict__ rot,
                                                         const float* __restrict__ shs, float* __restrict__ rgb) {
@@ -96,14 +86,6 @@ __global__ __launch_bounds__(256) void sh_colors_kernel(int N, int deg, int M, c
     const float r = sh_channel(deg, [&](int k) { return sh[3 * k + ch]; }, x, y, z);
     rgb[3 * (size_t)i + ch] = fmaxf(r + 0.5f, 0.0f);
   }
-}
-
-int launch_sh_colors(int N, int deg, int M, const float* pos, const float* campos, const float* rot,
-                     const float* shs, float* rgb, hipStream_t s) {
-  StageScope sc(ST_SH_COLORS, s);
-  if (N > 0) hipLaunchKernelGGL(sh_colors_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, deg, M, pos, campos, rot, shs, rgb);
-  GM_HIP(hipGetLastError());
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -519,30 +501,6 @@ __global__ __launch_bounds__(256) void pack_mesh_state_kernel(int Vm, const floa
   o[5] = make_float4(s[19], s[20], 0.f, 0.f);
 }
 
-int launch_pack_mesh_state(int Vm, const float* state, const float* verts, float* packed, hipStream_t s) {
-  if (Vm <= 0) return 0;
-  StageScope sc(ST_DEFORM, s);
-  hipLaunchKernelGGL(pack_mesh_state_kernel, dim3((Vm + 255) / 256), dim3(256), 0, s, Vm, state, verts, reinterpret_cast<float4*>(packed));
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
-int launch_deform_shade_packed(int N, int deg, int M, const int* tri, const float* w, const float* packed, const float* cov,
-                               const float* pos, const float* shs, const float* campos, float* pos_out, float* cov6_out,
-                               float* rgb_out, float* cov_out, float* rot_out, hipStream_t s) {
-  if (N <= 0) return 0;
-  if (M != 16 || !aligned16(shs) || !aligned16(cov) || !aligned16(pos_out) || !aligned16(cov6_out) || !aligned16(rgb_out) ||
-      !aligned16(packed) || (cov_out && (!aligned16(cov_out) || !aligned16(rot_out)))) {
-    set_error("gm_deform_shade_packed: needs M == 16 and 16-byte aligned buffers"); return 1;
-  }
-  StageScope sc(ST_DEFORM, s);
-  const size_t lds_bytes = sizeof(float) * 64 * 48;
-  hipLaunchKernelGGL((deform_shade_kernel<true, false>), dim3((N + 63) / 64), dim3(64), lds_bytes, s, N, deg, tri, w, packed, nullptr, nullptr,
-                     cov, pos, shs, campos, pos_out, cov6_out, rgb_out, cov_out, rot_out, FusedPre{});
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
 int launch_deform_shade_pre(const RasterArgs& r, GeomState& g, int* radii, int deg, const int* tri, const float* w, const float* packed,
                             const float* cov, const float* pos, const float* shs, float* pos_out, float* cov6_out, float* rgb_out,
                             const DepthSlab* slab, bool cov6) {
@@ -573,25 +531,6 @@ int launch_deform_shade_pre(const RasterArgs& r, GeomState& g, int* radii, int d
   return 0;
 }
 
-int launch_deform_shade(int N, int deg, int M, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
-                        const float* cov, const float* pos, const float* shs, const float* campos, float* pos_out,
-                        float* cov6_out, float* rgb_out, float* cov_out, float* rot_out, hipStream_t s) {
-  if (N <= 0) return 0;
-  if (M != 16 || !aligned16(shs) || !aligned16(cov) || !aligned16(pos_out) || !aligned16(cov6_out) || !aligned16(rgb_out) ||
-      (cov_out && (!aligned16(cov_out) || !aligned16(rot_out)))) {
-    // general layout: run the two unfused kernels (needs the 72 B/Gaussian intermediates from the caller)
-    if (!cov_out || !rot_out) { set_error("gm_deform_shade: M != 16 or unaligned buffers need cov_out/rot_out"); return 1; }
-    if (int rc = launch_deform(N, tri, w, dV, Rv, Sv, cov, pos, pos_out, cov_out, rot_out, cov6_out, s)) return rc;
-    return launch_sh_colors(N, deg, M, pos_out, campos, rot_out, shs, rgb_out, s);
-  }
-  StageScope sc(ST_DEFORM, s);
-  const size_t lds_bytes = sizeof(float) * 64 * 48;
-  hipLaunchKernelGGL((deform_shade_kernel<false, false>), dim3((N + 63) / 64), dim3(64), lds_bytes, s, N, deg, tri, w, dV, Rv, Sv, cov, pos,
-                     shs, campos, pos_out, cov6_out, rgb_out, cov_out, rot_out, FusedPre{});
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Covariance -> (scale, quaternion): replaces SceneVisualTool.render_gaussian's per-frame
 //   eigh(cov) on the device, det sign fixed on the HOST through numpy, sqrt(eigenvalues), matrix -> quaternion
@@ -611,12 +550,6 @@ __global__ __launch_bounds__(256) void cov_to_scale_rot_kernel(int N, const floa
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
 #include "gm_cov_to_scale_rot_body.inc"
-}
-
-int launch_cov_to_scale_rot(int N, const float* cov, float* scales, float* rots, hipStream_t s) {
-  if (N > 0) hipLaunchKernelGGL(cov_to_scale_rot_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, cov, scales, rots);
-  GM_HIP(hipGetLastError());
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -739,3 +672,105 @@ int launch_scene_shade_pre_batch(int frames, const BatchFrameArgs* fr, const uin
 }
 
 }  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points the rasteriser's orchestration (gm_api.hip) does not compose: their refusals, then the launches
+using namespace gm;
+
+extern "C" {
+
+int gm_deform(int N, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
+              const float* cov, const float* pos, float* pos_out, float* cov_out, float* rot_out, float* cov6_out,
+              void* stream) {
+  if (N < 0 || (N > 0 && (!tri || !w || !dV || !Rv || !Sv || !cov || !pos || !pos_out || !cov_out || !rot_out))) {
+    set_error("gm_deform: bad args"); return GM_ERR_INVALID_ARG;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  StageScope sc(ST_DEFORM, s);
+  if (N > 0)
+    hipLaunchKernelGGL(deform_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, tri, w, dV, Rv, Sv, cov, pos, pos_out, cov_out,
+                       rot_out, cov6_out);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_sh_colors(int N, int deg, int M, const float* pos, const float* campos, const float* rot, const float* shs,
+                 float* rgb, void* stream) {
+  if (N < 0 || deg < 0 || deg > 3 || M < (deg + 1) * (deg + 1) || (N > 0 && (!pos || !campos || !shs || !rgb))) {
+    set_error("gm_sh_colors: bad args"); return GM_ERR_INVALID_ARG;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  StageScope sc(ST_SH_COLORS, s);
+  if (N > 0) hipLaunchKernelGGL(sh_colors_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, deg, M, pos, campos, rot, shs, rgb);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_pack_mesh_state(int Vm, const float* state, const float* verts, float* packed, void* stream) {
+  if (Vm < 0 || (Vm > 0 && (!state || !verts || !packed))) { set_error("gm_pack_mesh_state: bad args"); return GM_ERR_INVALID_ARG; }
+  if (Vm == 0) return GM_OK;
+  if (reinterpret_cast<uintptr_t>(packed) & 15) { set_error("gm_pack_mesh_state: packed must be 16-byte aligned"); return GM_ERR_INVALID_ARG; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  StageScope sc(ST_DEFORM, s);
+  hipLaunchKernelGGL(pack_mesh_state_kernel, dim3((Vm + 255) / 256), dim3(256), 0, s, Vm, state, verts, reinterpret_cast<float4*>(packed));
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_deform_shade_packed(int N, int deg, int M, const int* tri, const float* w, const float* packed, const float* cov,
+                           const float* pos, const float* shs, const float* campos, float* pos_out, float* cov6_out,
+                           float* rgb_out, float* cov_out, float* rot_out, void* stream) {
+  if (N < 0 || deg < 0 || deg > 3 || M < (deg + 1) * (deg + 1) ||
+      (N > 0 && (!tri || !w || !packed || !cov || !pos || !shs || !campos || !pos_out || !cov6_out || !rgb_out)) ||
+      ((cov_out == nullptr) != (rot_out == nullptr))) {
+    set_error("gm_deform_shade_packed: bad args"); return GM_ERR_INVALID_ARG;
+  }
+  if (N == 0) return GM_OK;
+  if (M != 16 || !aligned16(shs) || !aligned16(cov) || !aligned16(pos_out) || !aligned16(cov6_out) || !aligned16(rgb_out) ||
+      !aligned16(packed) || (cov_out && (!aligned16(cov_out) || !aligned16(rot_out)))) {
+    set_error("gm_deform_shade_packed: needs M == 16 and 16-byte aligned buffers"); return GM_ERR_INVALID_ARG;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  StageScope sc(ST_DEFORM, s);
+  const size_t lds_bytes = sizeof(float) * 64 * 48;
+  hipLaunchKernelGGL((deform_shade_kernel<true, false>), dim3((N + 63) / 64), dim3(64), lds_bytes, s, N, deg, tri, w, packed, nullptr, nullptr,
+                     cov, pos, shs, campos, pos_out, cov6_out, rgb_out, cov_out, rot_out, FusedPre{});
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_deform_shade(int N, int deg, int M, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
+                    const float* cov, const float* pos, const float* shs, const float* campos, float* pos_out, float* cov6_out,
+                    float* rgb_out, float* cov_out, float* rot_out, void* stream) {
+  if (N < 0 || deg < 0 || deg > 3 || M < (deg + 1) * (deg + 1) ||
+      (N > 0 && (!tri || !w || !dV || !Rv || !Sv || !cov || !pos || !shs || !campos || !pos_out || !cov6_out || !rgb_out)) ||
+      ((cov_out == nullptr) != (rot_out == nullptr))) {
+    set_error("gm_deform_shade: bad args"); return GM_ERR_INVALID_ARG;
+  }
+  if (N == 0) return GM_OK;
+  if (M != 16 || !aligned16(shs) || !aligned16(cov) || !aligned16(pos_out) || !aligned16(cov6_out) || !aligned16(rgb_out) ||
+      (cov_out && (!aligned16(cov_out) || !aligned16(rot_out)))) {
+    // general layout: run the two unfused kernels (needs the 72 B/Gaussian intermediates from the caller)
+    if (!cov_out || !rot_out) { set_error("gm_deform_shade: M != 16 or unaligned buffers need cov_out/rot_out"); return GM_ERR_INVALID_ARG; }
+    if (int rc = gm_deform(N, tri, w, dV, Rv, Sv, cov, pos, pos_out, cov_out, rot_out, cov6_out, stream)) return rc;
+    return gm_sh_colors(N, deg, M, pos_out, campos, rot_out, shs, rgb_out, stream);
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  StageScope sc(ST_DEFORM, s);
+  const size_t lds_bytes = sizeof(float) * 64 * 48;
+  hipLaunchKernelGGL((deform_shade_kernel<false, false>), dim3((N + 63) / 64), dim3(64), lds_bytes, s, N, deg, tri, w, dV, Rv, Sv, cov, pos,
+                     shs, campos, pos_out, cov6_out, rgb_out, cov_out, rot_out, FusedPre{});
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_cov_to_scale_rot(int N, const float* cov, float* scales, float* rots, void* stream) {
+  if (N < 0 || (N > 0 && (!cov || !scales || !rots))) { set_error("gm_cov_to_scale_rot: bad args"); return GM_ERR_INVALID_ARG; }
+  if (N > 0 && (reinterpret_cast<uintptr_t>(rots) & 15)) { set_error("gm_cov_to_scale_rot: rots must be 16-byte aligned"); return GM_ERR_INVALID_ARG; }
+  if (N > 0)
+    hipLaunchKernelGGL(cov_to_scale_rot_kernel, dim3((N + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), N, cov, scales, rots);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+}  // extern "C"

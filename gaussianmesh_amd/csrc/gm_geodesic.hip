@@ -31,14 +31,10 @@
 //
 // Conventions of gm_closest_face: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
+#include "gm_check.h"
 #pragma clang fp contract(off)
 
 namespace gm {
-
-size_t mesh_geodesic_workspace_bytes(int Vm, int B, int sweeps) {
-  (void)Vm; (void)B;                                      // in place: the workspace holds the sweep counters alone
-  return ((size_t)(sweeps > 0 ? sweeps : 0) + 1) * sizeof(int) + 256;
-}
 
 static inline int gd_div_up(int n, int d) { return n > 0 ? (n - 1) / d + 1 : 0; }
 
@@ -92,13 +88,33 @@ __global__ __launch_bounds__(256) void gd_sweep(int Vm, const int* __restrict__ 
 
 __global__ void gd_report(const int* __restrict__ last, int* __restrict__ unsettled) { *unsettled = *last; }
 
-int launch_mesh_geodesic(int Vm, const int* row_offsets, const int* cols, const float* lengths, int B, const int* source_offsets,
-                         const int* sources, float max_distance, int sweeps, int resume, float* dist, int* unsettled, void* ws,
-                         size_t ws_bytes, hipStream_t s) {
-  if (Vm <= 0) return 0;
-  const size_t need = mesh_geodesic_workspace_bytes(Vm, B, sweeps);
-  if (ws_bytes < need) { set_error("gm_mesh_geodesic: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
-  int* counters = reinterpret_cast<int*>(ws);
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+extern "C" {
+
+size_t gm_mesh_geodesic_workspace_bytes(int Vm, int B, int sweeps) {
+  (void)Vm; (void)B;                                      // in place: the workspace holds the sweep counters alone
+  return ((size_t)(sweeps > 0 ? sweeps : 0) + 1) * sizeof(int) + 256;
+}
+
+int gm_mesh_geodesic(int Vm, const int* row_offsets, const int* cols, const float* lengths, int B, const int* source_offsets, const int* sources,
+                     float max_distance, int sweeps, int resume, float* dist, int* unsettled, void* workspace, size_t workspace_bytes, void* stream) {
+  if (Vm < 0 || B < 0) { set_error("gm_mesh_geodesic: negative size Vm=%d B=%d", Vm, B); return GM_ERR_INVALID_ARG; }
+  if (sweeps < 1) { set_error("gm_mesh_geodesic: sweeps must be >= 1; got %d", sweeps); return GM_ERR_INVALID_ARG; }
+  if (!(max_distance >= 0.f)) { set_error("gm_mesh_geodesic: max_distance must be >= 0 and not NaN (+inf: no cutoff)"); return GM_ERR_INVALID_ARG; }
+  if (Vm == 0) return GM_OK;
+  if (B < 1 || B > 65535) { set_error("gm_mesh_geodesic: B must be 1 .. 65535 source sets; got %d", B); return GM_ERR_INVALID_ARG; }
+  if (!row_offsets || !cols || !lengths || !source_offsets || !sources || !dist || !unsettled || !workspace) {
+    set_error("gm_mesh_geodesic: null pointer"); return GM_ERR_INVALID_ARG;
+  }
+  const size_t need = gm_mesh_geodesic_workspace_bytes(Vm, B, sweeps);
+  if (workspace_bytes < need) { set_error("gm_mesh_geodesic: workspace too small (%zu < %zu)", workspace_bytes, need); return GM_ERR_BUFFER; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int* counters = reinterpret_cast<int*>(workspace);
   const int row_blocks = gd_div_up(Vm, 256), arm_blocks = sweeps / 256 + 1;          // counters 0 .. sweeps
   hipLaunchKernelGGL(gd_fill, dim3(resume ? arm_blocks : (row_blocks > arm_blocks ? row_blocks : arm_blocks), resume ? 1 : B), dim3(256), 0, s, Vm,
                      dist, resume ? 0 : 1, sweeps, counters);
@@ -108,7 +124,7 @@ int launch_mesh_geodesic(int Vm, const int* row_offsets, const int* cols, const 
                        counters + k);
   hipLaunchKernelGGL(gd_report, dim3(1), dim3(1), 0, s, counters + sweeps, unsettled);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

@@ -8,6 +8,7 @@
 // Differences by design: no internal allocation (caller workspace), no host readback of the bounding box
 // (it stays on the device), our own radix sort (gm_sort.hip).
 #include "gm_common.h"
+#include "gm_check.h"
 #include "gm_spatial.h"
 #include "gm_wave.h"
 #include <cfloat>
@@ -32,11 +33,6 @@ struct KnnWs {
     return k;
   }
 };
-
-size_t knn_workspace_bytes(int P) {
-  KnnWs k = KnnWs::from(nullptr, (size_t)(P > 0 ? P : 1));
-  return (size_t)k.end + 256;
-}
 
 // one workgroup per box of 1024 Morton-consecutive points (simple_knn.cu:78-117)
 __global__ __launch_bounds__(256) void knn_box_minmax(int P, const float* __restrict__ pts, const uint32_t* __restrict__ idx,
@@ -104,21 +100,6 @@ __global__ __launch_bounds__(256) void knn_box_mean_dist(int P, const float* __r
   dists[self] = (best[0] + best[1] + best[2]) / 3.0f;
 }
 
-int launch_knn(int P, const float* points, float* meanDists, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (P <= 0) return 0;
-  if (ws_bytes < knn_workspace_bytes(P)) { set_error("gm_knn: workspace too small (%zu < %zu)", ws_bytes, knn_workspace_bytes(P)); return 3; }
-  KnnWs k = KnnWs::from(ws, (size_t)P);
-  if (int rc = launch_point_bbox(P, points, k.front.bbox_partial, k.front.bbox, s)) return rc;
-  if (int rc = launch_point_morton(P, points, k.front.bbox, k.set.keys[0], s)) return rc;
-  MortonSorted sorted;
-  if (int rc = morton_sort(k.set, k.front, (size_t)P, &sorted, s)) return rc;
-  const int nboxes = (P + KNN_BOX - 1) / KNN_BOX;
-  hipLaunchKernelGGL(knn_box_minmax, dim3(nboxes), dim3(256), 0, s, P, points, sorted.idx, k.boxes);
-  hipLaunchKernelGGL(knn_box_mean_dist, dim3((P + 255) / 256), dim3(256), 0, s, P, points, sorted.idx, k.boxes, meanDists);
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------
 // knn_nearest: for every query point the nearest reference point (k = 1), squared distance and index.
 //   d2 = (dx*dx + dy*dy) + dz*dz in float32, no contraction (file pragma), ties -> lowest reference index: the result is that of
@@ -149,11 +130,6 @@ struct NnWs {
     return k;
   }
 };
-
-size_t knn_nearest_workspace_bytes(int Pq, int Pr) {
-  NnWs k = NnWs::from(nullptr, (size_t)(Pq > 0 ? Pq : 1), (size_t)(Pr > 0 ? Pr : 1));
-  return (size_t)k.end + 256;
-}
 
 // sorted reference points as float4 (w = original index) and the bounding box of every NN_BOX of them (one workgroup per box)
 __global__ __launch_bounds__(NN_BOX) void nn_gather_boxes(int Pr, const float* __restrict__ ref, const uint32_t* __restrict__ idx,
@@ -215,12 +191,52 @@ __global__ __launch_bounds__(256) void nn_query(int Pq, const float* __restrict_
   out_idx[q] = (int)bid;
 }
 
-int launch_knn_nearest(int Pq, const float* query, int Pr, const float* ref, float* out_d2, int* out_idx, void* ws, size_t ws_bytes,
-                       hipStream_t s) {
-  if (Pq <= 0) return 0;
-  const size_t need = knn_nearest_workspace_bytes(Pq, Pr);
-  if (ws_bytes < need) { set_error("gm_knn_nearest: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
-  NnWs k = NnWs::from(ws, (size_t)Pq, (size_t)Pr);
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+extern "C" {
+
+size_t gm_knn_workspace_bytes(int P) {
+  KnnWs k = KnnWs::from(nullptr, (size_t)(P > 0 ? P : 1));
+  return (size_t)k.end + 256;
+}
+
+int gm_knn(int P, const float* points, float* meanDists, void* workspace, size_t workspace_bytes, void* stream) {
+  if (P < 0 || (P > 0 && (!points || !meanDists || !workspace))) { set_error("gm_knn: bad args"); return GM_ERR_INVALID_ARG; }
+  if (P == 0) return GM_OK;
+  const size_t need = gm_knn_workspace_bytes(P);
+  if (workspace_bytes < need) { set_error("gm_knn: workspace too small (%zu < %zu)", workspace_bytes, need); return GM_ERR_BUFFER; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  KnnWs k = KnnWs::from(workspace, (size_t)P);
+  if (int rc = launch_point_bbox(P, points, k.front.bbox_partial, k.front.bbox, s)) return rc;
+  if (int rc = launch_point_morton(P, points, k.front.bbox, k.set.keys[0], s)) return rc;
+  MortonSorted sorted;
+  if (int rc = morton_sort(k.set, k.front, (size_t)P, &sorted, s)) return rc;
+  const int nboxes = (P + KNN_BOX - 1) / KNN_BOX;
+  hipLaunchKernelGGL(knn_box_minmax, dim3(nboxes), dim3(256), 0, s, P, points, sorted.idx, k.boxes);
+  hipLaunchKernelGGL(knn_box_mean_dist, dim3((P + 255) / 256), dim3(256), 0, s, P, points, sorted.idx, k.boxes, meanDists);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+size_t gm_knn_nearest_workspace_bytes(int Pq, int Pr) {
+  NnWs k = NnWs::from(nullptr, (size_t)(Pq > 0 ? Pq : 1), (size_t)(Pr > 0 ? Pr : 1));
+  return (size_t)k.end + 256;
+}
+
+int gm_knn_nearest(int Pq, const float* query, int Pr, const float* ref, float* out_d2, int* out_idx, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+  if (Pq < 0 || Pr < 0) { set_error("gm_knn_nearest: negative size"); return GM_ERR_INVALID_ARG; }
+  if (Pr == 0) { set_error("gm_knn_nearest: empty reference set (Pr == 0)"); return GM_ERR_INVALID_ARG; }
+  if (Pq == 0) return GM_OK;
+  if (!query || !ref || !out_d2 || !out_idx || !workspace) { set_error("gm_knn_nearest: null pointer"); return GM_ERR_INVALID_ARG; }
+  const size_t need = gm_knn_nearest_workspace_bytes(Pq, Pr);
+  if (workspace_bytes < need) { set_error("gm_knn_nearest: workspace too small (%zu < %zu)", workspace_bytes, need); return GM_ERR_BUFFER; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  NnWs k = NnWs::from(workspace, (size_t)Pq, (size_t)Pr);
   if (int rc = launch_point_bbox(Pr, ref, k.front.bbox_partial, k.front.bbox, s)) return rc;
   if (int rc = launch_point_morton(Pr, ref, k.front.bbox, k.rset.keys[0], s)) return rc;
   if (int rc = launch_point_morton(Pq, query, k.front.bbox, k.qset.keys[0], s)) return rc;
@@ -232,7 +248,7 @@ int launch_knn_nearest(int Pq, const float* query, int Pr, const float* ref, flo
   hipLaunchKernelGGL(nn_query, dim3((Pq + 255) / 256), dim3(256), 0, s, Pq, query, q.idx, Pr, r.keys, k.rsorted, k.boxes, nboxes,
                      k.front.bbox, out_d2, out_idx);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

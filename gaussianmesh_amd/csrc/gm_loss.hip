@@ -16,6 +16,7 @@
 // 8-bit planes of a dataset and composited over a background on load: 2 B (rgb + one mask plane) instead of 4 B of target per
 // pixel-channel, and no composite pass in front of the loss.
 #include "gm_common.h"
+#include "gm_check.h"
 
 namespace gm {
 
@@ -158,58 +159,109 @@ __global__ __launch_bounds__(1024) void loss_combine_kernel(const float* __restr
   }
 }
 
-int launch_loss_combine(const float* partial, long long n, double c_ssim, double c_l1, double offset, float* out, hipStream_t s) {
-  hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(1024), 0, s, partial, n, c_ssim, c_l1, offset, out);
-  GM_HIP(hipGetLastError());
-  return 0;
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+// what the two calls with an 8-bit target refuse about it
+static int check_u8_target(const char* who, const unsigned char* rgb, const unsigned char* mask, int64_t mask_plane_stride, const float* background,
+                           int planes, int H, int W) {
+  if (planes != 3) { set_error("%s: an 8-bit target has 3 planes", who); return GM_ERR_INVALID_ARG; }
+  if (!rgb) { set_error("%s: null rgb", who); return GM_ERR_INVALID_ARG; }
+  if (mask && !background) { set_error("%s: a mask needs the background colour (device float[3])", who); return GM_ERR_INVALID_ARG; }
+  if (mask && mask_plane_stride != 0 && mask_plane_stride < (int64_t)H * W) {
+    set_error("%s: mask_plane_stride is 0 (one shared plane) or at least H*W", who); return GM_ERR_INVALID_ARG;
+  }
+  return GM_OK;
 }
 
-int launch_ssim_fwd(const float* img1, const float* img2, int planes, int H, int W, float* d_mu1, float* d_e11, float* d_e12,
-                    float* partial, hipStream_t s) {
+extern "C" {
+
+int gm_loss_combine(const float* partial, int64_t n_partials, double c_ssim, double c_l1, double offset, float* out, void* stream) {
+  if (n_partials < 0) { set_error("gm_loss_combine: negative count"); return GM_ERR_INVALID_ARG; }
+  if (!out || (n_partials > 0 && !partial)) { set_error("gm_loss_combine: null partial / out"); return GM_ERR_INVALID_ARG; }
+  hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), partial, (long long)n_partials, c_ssim, c_l1,
+                     offset, out);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_ssim_fwd(const float* img1, const float* img2, int planes, int H, int W, float* dS_dmu1, float* dS_dE11, float* dS_dE12,
+                float* partial, void* stream) {
+  if (planes < 0 || H < 0 || W < 0) { set_error("gm_ssim_fwd: negative size"); return GM_ERR_INVALID_ARG; }
+  if (planes == 0 || H == 0 || W == 0) return GM_OK;
+  if (!img1 || !img2 || !partial) { set_error("gm_ssim_fwd: null image or partial buffer"); return GM_ERR_INVALID_ARG; }
+  const int nmaps = (dS_dmu1 != nullptr) + (dS_dE11 != nullptr) + (dS_dE12 != nullptr);
+  if (nmaps != 0 && nmaps != 3) { set_error("gm_ssim_fwd: pass all three derivative maps or none"); return GM_ERR_INVALID_ARG; }
+  if (planes > 65535) { set_error("gm_ssim_fwd: at most 65535 image planes per call"); return GM_ERR_INVALID_ARG; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   StageScope sc(ST_LOSS, s);
   const dim3 grid((W + LS_TILE - 1) / LS_TILE, (H + LS_TILE - 1) / LS_TILE, planes);
   const LossWindow win = make_window();
-  hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(LS_THREADS), 0, s, img1, img2, H, W, win, d_mu1, d_e11, d_e12, partial);
+  hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(LS_THREADS), 0, s, img1, img2, H, W, win, dS_dmu1, dS_dE11, dS_dE12, partial);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-int launch_ssim_bwd(const float* img1, const float* img2, const float* d_mu1, const float* d_e11, const float* d_e12, int planes,
-                    int H, int W, const float* g_ssim, const float* g_l1, float* dL_dimg1, hipStream_t s) {
+int gm_ssim_bwd(const float* img1, const float* img2, const float* dS_dmu1, const float* dS_dE11, const float* dS_dE12, int planes,
+                int H, int W, const float* g_ssim, const float* g_l1, float* dL_dimg1, void* stream) {
+  if (planes < 0 || H < 0 || W < 0) { set_error("gm_ssim_bwd: negative size"); return GM_ERR_INVALID_ARG; }
+  if (planes == 0 || H == 0 || W == 0) return GM_OK;
+  if (!img1 || !img2 || !dS_dmu1 || !dS_dE11 || !dS_dE12 || !g_ssim || !dL_dimg1) { set_error("gm_ssim_bwd: null argument"); return GM_ERR_INVALID_ARG; }
+  if (planes > 65535) { set_error("gm_ssim_bwd: at most 65535 image planes per call"); return GM_ERR_INVALID_ARG; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   StageScope sc(ST_LOSS_BWD, s);
   const dim3 grid((W + LS_TILE - 1) / LS_TILE, (H + LS_TILE - 1) / LS_TILE, planes);
-  hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(LS_THREADS), 0, s, img1, img2, d_mu1, d_e11, d_e12, H, W, make_window(), g_ssim, g_l1,
+  hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(LS_THREADS), 0, s, img1, img2, dS_dmu1, dS_dE11, dS_dE12, H, W, make_window(), g_ssim, g_l1,
                      dL_dimg1);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-int launch_ssim_fwd_u8(const float* img1, const unsigned char* rgb, const unsigned char* mask, size_t mask_stride, const float* bg, int H,
-                       int W, float* d_mu1, float* d_e11, float* d_e12, float* partial, hipStream_t s) {
+// the same two kernels' bodies with an 8-bit target composited on load (three planes; U8Target)
+int gm_ssim_fwd_u8(const float* img1, const uint8_t* rgb, const uint8_t* mask, int64_t mask_plane_stride, const float* background,
+                   int planes, int H, int W, float* dS_dmu1, float* dS_dE11, float* dS_dE12, float* partial, void* stream) {
+  if (planes < 0 || H < 0 || W < 0) { set_error("gm_ssim_fwd_u8: negative size"); return GM_ERR_INVALID_ARG; }
+  if (planes == 0 || H == 0 || W == 0) return GM_OK;
+  if (!img1 || !partial) { set_error("gm_ssim_fwd_u8: null image or partial buffer"); return GM_ERR_INVALID_ARG; }
+  const int nmaps = (dS_dmu1 != nullptr) + (dS_dE11 != nullptr) + (dS_dE12 != nullptr);
+  if (nmaps != 0 && nmaps != 3) { set_error("gm_ssim_fwd_u8: pass all three derivative maps or none"); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_u8_target("gm_ssim_fwd_u8", rgb, mask, mask_plane_stride, background, planes, H, W)) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   StageScope sc(ST_LOSS, s);
   const dim3 grid((W + LS_TILE - 1) / LS_TILE, (H + LS_TILE - 1) / LS_TILE, 3);
   const LossWindow win = make_window();
-#define LS_FWD_U8(MASK) \
-  hipLaunchKernelGGL(ssim_fwd_u8_kernel<MASK>, grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, bg, H, W, win, d_mu1, d_e11, d_e12, partial)
+  const size_t mask_stride = (size_t)mask_plane_stride;
+#define LS_FWD_U8(MASK)                                                                                                                \
+  hipLaunchKernelGGL(ssim_fwd_u8_kernel<MASK>, grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, background, H, W, win, dS_dmu1, \
+                     dS_dE11, dS_dE12, partial)
   if (mask) LS_FWD_U8(true); else LS_FWD_U8(false);
 #undef LS_FWD_U8
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-int launch_ssim_bwd_u8(const float* img1, const unsigned char* rgb, const unsigned char* mask, size_t mask_stride, const float* bg,
-                       const float* d_mu1, const float* d_e11, const float* d_e12, int H, int W, const float* g_ssim, const float* g_l1,
-                       float* dL_dimg1, hipStream_t s) {
+int gm_ssim_bwd_u8(const float* img1, const uint8_t* rgb, const uint8_t* mask, int64_t mask_plane_stride, const float* background,
+                   const float* dS_dmu1, const float* dS_dE11, const float* dS_dE12, int planes, int H, int W, const float* g_ssim,
+                   const float* g_l1, float* dL_dimg1, void* stream) {
+  if (planes < 0 || H < 0 || W < 0) { set_error("gm_ssim_bwd_u8: negative size"); return GM_ERR_INVALID_ARG; }
+  if (planes == 0 || H == 0 || W == 0) return GM_OK;
+  if (!img1 || !dS_dmu1 || !dS_dE11 || !dS_dE12 || !g_ssim || !dL_dimg1) { set_error("gm_ssim_bwd_u8: null argument"); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_u8_target("gm_ssim_bwd_u8", rgb, mask, mask_plane_stride, background, planes, H, W)) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   StageScope sc(ST_LOSS_BWD, s);
   const dim3 grid((W + LS_TILE - 1) / LS_TILE, (H + LS_TILE - 1) / LS_TILE, 3);
+  const size_t mask_stride = (size_t)mask_plane_stride;
   if (mask)
-    hipLaunchKernelGGL(ssim_bwd_u8_kernel<true>, grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, bg, d_mu1, d_e11, d_e12, H, W,
+    hipLaunchKernelGGL(ssim_bwd_u8_kernel<true>, grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, background, dS_dmu1, dS_dE11, dS_dE12, H, W,
                        make_window(), g_ssim, g_l1, dL_dimg1);
   else
-    hipLaunchKernelGGL(ssim_bwd_u8_kernel<false>, grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, bg, d_mu1, d_e11, d_e12, H, W,
+    hipLaunchKernelGGL(ssim_bwd_u8_kernel<false>, grid, dim3(LS_THREADS), 0, s, img1, rgb, mask, mask_stride, background, dS_dmu1, dS_dE11, dS_dE12, H, W,
                        make_window(), g_ssim, g_l1, dL_dimg1);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

@@ -27,6 +27,7 @@
 // One thread per vertex over a CSR vertex -> face adjacency built once per mesh on the host (deterministic, no atomics);
 // double precision (7.5 k vertices: the kernel is a few microseconds either way).
 #include "gm_common.h"
+#include "gm_check.h"
 #include "gm_mat3.h"
 
 namespace gm {
@@ -277,29 +278,65 @@ __global__ __launch_bounds__(GM_MESH_THREADS) void mesh_rs_kernel(int Vm, const 
   }
 }
 
-int launch_mesh_rs(int Vm, const float* V0, const float* V1, const int* faces, const int* adj_offsets, const int* adj_faces, float* R,
-                   float* S, float* state, float* packed, hipStream_t s) {
-  if (Vm <= 0) return 0;
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+// one frame's tables: (R, S, state) or the packed gather table
+static int launch_mesh_rs(int Vm, const float* V0, const float* V1, const int* faces, const int* adj_offsets, const int* adj_faces, float* R,
+                          float* S, float* state, float* packed, void* stream) {
+  if (Vm <= 0) return GM_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   StageScope sc(ST_MESH_RS, s);          // a stage of its own: bench.py's `roofline` names single kernels
   MeshFrames mf{};
   mf.frames = 1;
   hipLaunchKernelGGL(mesh_rs_kernel, dim3((Vm + GM_MESH_THREADS - 1) / GM_MESH_THREADS), dim3(GM_MESH_THREADS), 0, s, Vm, V0, V1, faces, adj_offsets, adj_faces, R, S, state,
                      reinterpret_cast<float4*>(packed), mf);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-int launch_mesh_rs_batch(int frames, int Vm, const float* V0, const float* const* V1, const int* faces, const int* adj_offsets, const int* adj_faces,
-                         float* const* packed, hipStream_t s) {
-  if (Vm <= 0 || frames <= 0) return 0;
-  StageScope sc(ST_MESH_RS, s);
+extern "C" {
+
+int gm_mesh_rs(int Vm, int nfaces, const float* V0, const float* V1, const int* faces, const int* adj_offsets, const int* adj_faces,
+               float* R, float* S, float* state, void* stream) {
+  if (Vm < 0 || nfaces < 0 || (Vm > 0 && (!V0 || !V1 || !adj_offsets || (nfaces > 0 && (!faces || !adj_faces)) || (!R && !S && !state)))) {
+    set_error("gm_mesh_rs: bad args"); return GM_ERR_INVALID_ARG;
+  }
+  if ((R == nullptr) != (S == nullptr)) { set_error("gm_mesh_rs: pass R and S together"); return GM_ERR_INVALID_ARG; }
+  return launch_mesh_rs(Vm, V0, V1, faces, adj_offsets, adj_faces, R, S, state, nullptr, stream);
+}
+
+int gm_mesh_rs_packed(int Vm, int nfaces, const float* V0, const float* V1, const int* faces, const int* adj_offsets, const int* adj_faces,
+                      float* packed, void* stream) {
+  if (Vm < 0 || nfaces < 0 || (Vm > 0 && (!V0 || !V1 || !adj_offsets || !packed || (nfaces > 0 && (!faces || !adj_faces))))) {
+    set_error("gm_mesh_rs_packed: bad args"); return GM_ERR_INVALID_ARG;
+  }
+  if (reinterpret_cast<uintptr_t>(packed) & 15) { set_error("gm_mesh_rs_packed: packed must be 16-byte aligned"); return GM_ERR_INVALID_ARG; }
+  return launch_mesh_rs(Vm, V0, V1, faces, adj_offsets, adj_faces, nullptr, nullptr, nullptr, packed, stream);
+}
+
+// the packed gather tables of K deformation frames in one launch (gridDim.z = frame): V1[k] -> packed[k]
+int gm_mesh_rs_packed_batch(int K, int Vm, int nfaces, const float* V0, const float* const* V1, const int* faces, const int* adj_offsets,
+                            const int* adj_faces, float* const* packed, void* stream) {
+  if (K < 1 || K > GM_BATCH_MAX || Vm < 0 || nfaces < 0 || !V1 || !packed || (Vm > 0 && (!V0 || !adj_offsets || (nfaces > 0 && (!faces || !adj_faces))))) {
+    set_error("gm_mesh_rs_packed_batch: bad args"); return GM_ERR_INVALID_ARG;
+  }
+  if (Vm == 0) return GM_OK;
   MeshFrames mf{};
-  mf.frames = frames;
-  for (int f = 0; f < frames; f++) { mf.V1[f] = V1[f]; mf.packed[f] = reinterpret_cast<float4*>(packed[f]); }
-  hipLaunchKernelGGL(mesh_rs_kernel, dim3((Vm + GM_MESH_THREADS - 1) / GM_MESH_THREADS, 1, (uint32_t)frames), dim3(GM_MESH_THREADS), 0, s, Vm, V0, V1[0], faces, adj_offsets,
+  mf.frames = K;
+  for (int k = 0; k < K; k++) {
+    if (!V1[k] || !packed[k] || (reinterpret_cast<uintptr_t>(packed[k]) & 15)) { set_error("gm_mesh_rs_packed_batch: frame %d: null or unaligned pointer", k); return GM_ERR_INVALID_ARG; }
+    mf.V1[k] = V1[k]; mf.packed[k] = reinterpret_cast<float4*>(packed[k]);
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  StageScope sc(ST_MESH_RS, s);
+  hipLaunchKernelGGL(mesh_rs_kernel, dim3((Vm + GM_MESH_THREADS - 1) / GM_MESH_THREADS, 1, (uint32_t)K), dim3(GM_MESH_THREADS), 0, s, Vm, V0, V1[0], faces, adj_offsets,
                      adj_faces, nullptr, nullptr, nullptr, reinterpret_cast<float4*>(packed[0]), mf);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

@@ -50,6 +50,7 @@
 // Vertex ids read from faces, face ids and offsets read from the CSR are forced into range: no fault, no meaning.
 // Conventions of gm_tsdf.hip: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
+#include "gm_check.h"
 #include "gm_wave.h"
 #pragma clang fp contract(off)   // every product, sum and quotient rounds on its own, as the definition above says
 
@@ -92,14 +93,6 @@ __global__ __launch_bounds__(256) void mc_normals(McMesh m, const float* __restr
     nz = nz + (e1x * e2y - e1y * e2x);
   }
   out[3 * (size_t)i] = nx; out[3 * (size_t)i + 1] = ny; out[3 * (size_t)i + 2] = nz;
-}
-
-int launch_mesh_vertex_normals(int Vm, int F, const float* vertices, const int* faces, const int* off, const int* adj, float* out, hipStream_t s) {
-  if (Vm <= 0) return 0;
-  const McMesh m = {Vm, F, faces, off, adj};
-  hipLaunchKernelGGL(mc_normals, dim3((unsigned)((Vm + 255) / 256)), dim3(256), 0, s, m, vertices, out);
-  GM_HIP(hipGetLastError());
-  return 0;
 }
 
 __global__ __launch_bounds__(256) void mc_integrate(int K, int H, int W, const float* __restrict__ image, const float* __restrict__ depth,
@@ -151,16 +144,6 @@ __global__ __launch_bounds__(256) void mc_integrate(int K, int H, int W, const f
   wsum[i] = w;
 }
 
-int launch_mesh_color_integrate(int K, int H, int W, const float* image, const float* depth, const float* alpha, const float* views,
-                                const float* tans, int Vm, const float* vertices, const float* normals, float alpha_min, float depth_tol,
-                                int two_sided, float* csum, float* wsum, hipStream_t s) {
-  if (K <= 0 || Vm <= 0) return 0;
-  hipLaunchKernelGGL(mc_integrate, dim3((unsigned)((Vm + 255) / 256)), dim3(256), 0, s, K, H, W, image, depth, alpha, views, tans, Vm, vertices,
-                     normals, alpha_min, depth_tol, two_sided ? 1 : 0, csum, wsum);
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
 // ---- spread ----
 struct McWs {
   float* col;              // [Vm,3] the second colour array (the first is the caller's)
@@ -177,11 +160,6 @@ struct McWs {
     return k;
   }
 };
-
-size_t mesh_color_spread_workspace_bytes(int Vm) {
-  const McWs k = McWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 0));
-  return (size_t)k.end + 256;    // (the caller's pointer may sit anywhere inside a 256-byte line)
-}
 
 // (colour_0, has_0) into both pairs
 __global__ __launch_bounds__(256) void mc_spread_init(int Vm, const uint8_t* __restrict__ seen, float* __restrict__ col0, float* __restrict__ col1,
@@ -263,19 +241,88 @@ __global__ __launch_bounds__(256) void mc_spread_counts(int blocks, const uint2*
   }
 }
 
-int launch_mesh_color_spread(int Vm, int F, const int* faces, const int* off, const int* adj, const unsigned char* seen, int iterations,
-                             const float* fallback, float* colors, unsigned char* out_has, int* out_counts, void* ws, size_t ws_bytes,
-                             hipStream_t s) {
-  const size_t need = mesh_color_spread_workspace_bytes(Vm);
-  if (ws_bytes < need) { set_error("gm_mesh_color_spread: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+// the mesh rules the three calls share: sizes that 3 Vm and 3 F index with an int
+static int check_color_mesh(const char* fn, int Vm, int F) {
+  if (Vm < 0 || F < 0) { set_error("%s: negative size Vm=%d F=%d", fn, Vm, F); return GM_ERR_INVALID_ARG; }
+  if (Vm > 0x7FFFFFFF / 3 || F > 0x7FFFFFFF / 3) { set_error("%s: Vm=%d F=%d: 3 Vm and 3 F must fit an int", fn, Vm, F); return GM_ERR_INVALID_ARG; }
+  return GM_OK;
+}
+
+extern "C" {
+
+int gm_mesh_vertex_normals(int Vm, int F, const float* vertices, const int* faces, const int* adj_offsets, const int* adj_faces, float* out_normals,
+                           void* stream) {
+  const char* fn = "gm_mesh_vertex_normals";
+  if (int rc = check_color_mesh(fn, Vm, F)) return rc;
+  if (Vm == 0) return GM_OK;
+  if (!vertices || !out_normals || (F > 0 && (!faces || !adj_offsets || !adj_faces))) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  const ByteRange rg[5] = {{vertices, 12 * (size_t)Vm, "vertices", false}, {faces, 12 * (size_t)F, "faces", false},
+                           {adj_offsets, 4 * ((size_t)Vm + 1), "adj_offsets", false}, {adj_faces, 12 * (size_t)F, "adj_faces", false},
+                           {out_normals, 12 * (size_t)Vm, "out_normals", true}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  const McMesh m = {Vm, F, faces, adj_offsets, adj_faces};
+  hipLaunchKernelGGL(mc_normals, dim3((unsigned)((Vm + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), m, vertices, out_normals);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_mesh_color_integrate(int K, int H, int W, const float* image, const float* depth, const float* alpha, const float* views, const float* tanfov,
+                            int Vm, const float* vertices, const float* normals, float alpha_min, float depth_tol, int two_sided, float* csum,
+                            float* wsum, void* stream) {
+  const char* fn = "gm_mesh_color_integrate";
+  if (K < 0 || H <= 0 || W <= 0 || H > (1 << 24) || W > (1 << 24)) { set_error("%s: invalid sizes K=%d H=%d W=%d", fn, K, H, W); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_color_mesh(fn, Vm, 0)) return rc;
+  if (alpha_min != alpha_min || !(depth_tol >= 0.f)) { set_error("%s: alpha_min must not be NaN, depth_tol >= 0 and not NaN", fn); return GM_ERR_INVALID_ARG; }
+  if (Vm == 0) return GM_OK;
+  if (!vertices || !normals || !csum || !wsum) { set_error("%s: null pointer (vertices / normals / csum / wsum)", fn); return GM_ERR_INVALID_ARG; }
+  if (K > 0 && (!image || !depth || !alpha || !views || !tanfov)) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  const size_t maps = 4 * (size_t)K * H * W;
+  const ByteRange rg[9] = {{image, 3 * maps, "image", false}, {depth, maps, "depth", false}, {alpha, maps, "alpha", false},
+                           {views, 64 * (size_t)K, "views", false}, {tanfov, 8 * (size_t)K, "tanfov", false}, {vertices, 12 * (size_t)Vm, "vertices", false},
+                           {normals, 12 * (size_t)Vm, "normals", false}, {csum, 12 * (size_t)Vm, "csum", true}, {wsum, 4 * (size_t)Vm, "wsum", true}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  if (K == 0) return GM_OK;
+  hipLaunchKernelGGL(mc_integrate, dim3((unsigned)((Vm + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), K, H, W, image, depth, alpha,
+                     views, tanfov, Vm, vertices, normals, alpha_min, depth_tol, two_sided ? 1 : 0, csum, wsum);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+size_t gm_mesh_color_spread_workspace_bytes(int Vm) {
+  const McWs k = McWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 0));
+  return (size_t)k.end + 256;    // (the caller's pointer may sit anywhere inside a 256-byte line)
+}
+
+int gm_mesh_color_spread(int Vm, int F, const int* faces, const int* adj_offsets, const int* adj_faces, const unsigned char* seen, int iterations,
+                         const float* fallback, float* colors, unsigned char* out_has, int* out_counts, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  const char* fn = "gm_mesh_color_spread";
+  if (int rc = check_color_mesh(fn, Vm, F)) return rc;
+  if (iterations < 0) { set_error("%s: iterations = %d (negative)", fn, iterations); return GM_ERR_INVALID_ARG; }
+  if (!fallback || !out_counts || !workspace || (Vm > 0 && (!seen || !colors || !out_has)) || (Vm > 0 && F > 0 && (!faces || !adj_offsets || !adj_faces))) {
+    set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG;
+  }
+  const ByteRange rg[8] = {{faces, 12 * (size_t)F, "faces", false}, {adj_offsets, Vm > 0 ? 4 * ((size_t)Vm + 1) : 0, "adj_offsets", false},
+                           {adj_faces, 12 * (size_t)F, "adj_faces", false}, {seen, (size_t)Vm, "seen", false}, {colors, 12 * (size_t)Vm, "colors", true},
+                           {out_has, (size_t)Vm, "out_has", true}, {out_counts, 8, "out_counts", true}, {workspace, workspace_bytes, "workspace", true}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  const size_t need = gm_mesh_color_spread_workspace_bytes(Vm);
+  if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 one(1), threads(256);
-  if (Vm <= 0) {
+  if (Vm == 0) {
     hipLaunchKernelGGL(mc_spread_counts, one, threads, 0, s, 0, (const uint2*)nullptr, out_counts);
     GM_HIP(hipGetLastError());
-    return 0;
+    return GM_OK;
   }
-  const McWs k = McWs::from(ws, (size_t)Vm);
-  const McMesh m = {Vm, F, faces, off, adj};
+  const McWs k = McWs::from(workspace, (size_t)Vm);
+  const McMesh m = {Vm, F, faces, adj_offsets, adj_faces};
   const int nblocks = (Vm + 255) / 256;
   const dim3 blocks((unsigned)nblocks);
   float* col[2] = {colors, k.col};
@@ -289,7 +336,7 @@ int launch_mesh_color_spread(int Vm, int F, const int* faces, const int* off, co
   hipLaunchKernelGGL(mc_spread_finish, blocks, threads, 0, s, Vm, seen, has[0], fallback[0], fallback[1], fallback[2], col[0], k.sums);
   hipLaunchKernelGGL(mc_spread_counts, one, threads, 0, s, nblocks, k.sums, out_counts);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

@@ -16,6 +16,7 @@
 // ~90 B out per Gaussian at SH degree 3); the camera matrices are wave-uniform and read through
 // the scalar cache.
 #include "gm_common.h"
+#include "gm_check.h"
 #pragma clang fp contract(off)
 #include "gm_sh.h"
 #include "gm_cull.h"
@@ -189,12 +190,6 @@ __global__ __launch_bounds__(256) void mark_visible_kernel(int P, const float* _
   const V3 p = {means[3 * (size_t)idx], means[3 * (size_t)idx + 1], means[3 * (size_t)idx + 2]};
   const V3 pv = xform4x3(p, view);
   present[idx] = (pv.z <= 0.2f) ? 0 : 1;
-}
-
-int launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s) {
-  if (P > 0) hipLaunchKernelGGL(mark_visible_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, means3D, view, present);
-  GM_HIP(hipGetLastError());
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -628,3 +623,20 @@ int launch_depth_grad(int P, const GeomState& g, const float* viewmatrix, float*
 }
 
 }  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry point the rasteriser's orchestration (gm_api.hip) does not compose: its refusals, then the launch
+using namespace gm;
+
+extern "C" {
+
+int gm_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present, void* stream) {
+  (void)projmatrix;
+  if (P < 0 || (P > 0 && (!means3D || !viewmatrix || !present))) { set_error("gm_mark_visible: bad args"); return GM_ERR_INVALID_ARG; }
+  if (P > 0)
+    hipLaunchKernelGGL(mark_visible_kernel, dim3((P + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), P, means3D, viewmatrix, present);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+}  // extern "C"

@@ -23,6 +23,7 @@
 //
 // Conventions of gm_closest_face: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
+#include "gm_check.h"
 #pragma clang fp contract(off)   // every product and sum rounds on its own, as the definition above says
 
 namespace gm {
@@ -44,15 +45,10 @@ struct RcWs {
   }
 };
 
-size_t ray_mesh_workspace_bytes(int R, int F) {
-  RcWs k = RcWs::from(nullptr, (size_t)(R > 0 ? R : 1), (size_t)(F > 0 ? F : 1));
-  return (size_t)k.end + 256;
-}
-
 static inline int rc_div_up(int n, int d) { return n > 0 ? (n - 1) / d + 1 : 0; }      // (no overflow near INT_MAX)
 
 // workgroups of rc_cast; more than a grid holds is refused by gm_ray_mesh
-unsigned long long ray_mesh_blocks(int R, int F) { return (unsigned long long)rc_div_up(R, 256) * (unsigned long long)rc_div_up(F, RC_CHUNK); }
+static inline unsigned long long ray_mesh_blocks(int R, int F) { return (unsigned long long)rc_div_up(R, 256) * (unsigned long long)rc_div_up(F, RC_CHUNK); }
 
 __global__ __launch_bounds__(256) void rc_prepare(int F, int Vm, const float* __restrict__ verts, const int* __restrict__ faces,
                                                   float4* __restrict__ recs, int R, unsigned long long* __restrict__ slots) {
@@ -126,18 +122,39 @@ __global__ __launch_bounds__(256) void rc_finish(int R, const float* __restrict_
   if (out_uv) { out_uv[2 * (size_t)i] = u; out_uv[2 * (size_t)i + 1] = v; }
 }
 
-int launch_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const float* vertices, int F, const int* faces, float t_min,
-                    float t_max, float* out_t, int* out_face, float* out_uv, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (R <= 0) return 0;
-  const size_t need = ray_mesh_workspace_bytes(R, F);
-  if (ws_bytes < need) { set_error("gm_ray_mesh: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
-  RcWs k = RcWs::from(ws, (size_t)R, (size_t)F);
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+extern "C" {
+
+size_t gm_ray_mesh_workspace_bytes(int R, int F) {
+  RcWs k = RcWs::from(nullptr, (size_t)(R > 0 ? R : 1), (size_t)(F > 0 ? F : 1));
+  return (size_t)k.end + 256;
+}
+
+int gm_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const float* vertices, int F, const int* faces, float t_min, float t_max,
+                float* out_t, int* out_face, float* out_uv, void* workspace, size_t workspace_bytes, void* stream) {
+  if (R < 0 || Vm < 0 || F < 0) { set_error("gm_ray_mesh: negative size R=%d Vm=%d F=%d", R, Vm, F); return GM_ERR_INVALID_ARG; }
+  if (!(t_min >= 0.f) || t_max != t_max) { set_error("gm_ray_mesh: t_min must be >= 0 and neither bound NaN"); return GM_ERR_INVALID_ARG; }
+  if (R == 0) return GM_OK;
+  if (F == 0 || Vm == 0) { set_error("gm_ray_mesh: empty mesh (F == %d, Vm == %d)", F, Vm); return GM_ERR_INVALID_ARG; }
+  if (!origins || !dirs || !vertices || !faces || !out_t || !out_face || !workspace) { set_error("gm_ray_mesh: null pointer"); return GM_ERR_INVALID_ARG; }
+  if (ray_mesh_blocks(R, F) > 0x7FFFFFFFull) {
+    set_error("gm_ray_mesh: R x F too large for one launch (%llu workgroups); split the rays", ray_mesh_blocks(R, F)); return GM_ERR_INVALID_ARG;
+  }
+  const size_t need = gm_ray_mesh_workspace_bytes(R, F);
+  if (workspace_bytes < need) { set_error("gm_ray_mesh: workspace too small (%zu < %zu)", workspace_bytes, need); return GM_ERR_BUFFER; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  RcWs k = RcWs::from(workspace, (size_t)R, (size_t)F);
   const int ray_blocks = rc_div_up(R, 256);
   hipLaunchKernelGGL(rc_prepare, dim3(rc_div_up(R > F ? R : F, 256)), dim3(256), 0, s, F, Vm, vertices, faces, k.recs, R, k.slots);
   hipLaunchKernelGGL(rc_cast, dim3((unsigned)ray_mesh_blocks(R, F)), dim3(256), 0, s, R, origins, dirs, F, k.recs, ray_blocks, t_min, t_max, k.slots);
   hipLaunchKernelGGL(rc_finish, dim3(ray_blocks), dim3(256), 0, s, R, origins, dirs, k.recs, k.slots, t_min, t_max, out_t, out_face, out_uv);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

@@ -19,6 +19,7 @@
 // sample was hoisted and 174 VGPRs spilled).  A thread has read its whole row before it writes it, so shs_out == shs is allowed.
 // No workspace, no device allocation, no host wait: stream-ordered.
 #include "gm_common.h"
+#include "gm_check.h"
 #pragma clang fp contract(off)
 #include "gm_sh.h"
 
@@ -148,11 +149,28 @@ __global__ __launch_bounds__(256) void sh_rotate_copy_kernel(size_t n, const flo
   for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) shs_out[k] = shs[k];
 }
 
-int launch_sh_rotate(int N, int deg, int M, const float* shs, const float* rot, float* shs_out, hipStream_t s) {
-  if (N <= 0) return 0;
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+extern "C" {
+
+int gm_sh_rotate(int N, int deg, int M, const float* shs, const float* rot, float* shs_out, void* stream) {
+  const char* fn = "gm_sh_rotate";
+  if (N < 0) { set_error("%s: negative N = %d", fn, N); return GM_ERR_INVALID_ARG; }
+  if (N == 0) return GM_OK;
+  if (deg < 0 || deg > 3) { set_error("%s: degree %d out of range 0..3", fn, deg); return GM_ERR_INVALID_ARG; }
+  if (M < (deg + 1) * (deg + 1)) { set_error("%s: rows of M = %d coefficients hold no degree %d", fn, M, deg); return GM_ERR_INVALID_ARG; }
+  if (!shs || !rot || !shs_out) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  const size_t n = (size_t)N * (size_t)M * 3;
+  // shs_out == shs is the in-place call: shs is then left out; any other meeting of the two is an overlap
+  const ByteRange rg[3] = {{shs_out, 4 * n, "shs_out", true}, {shs_out == shs ? nullptr : shs, 4 * n, "shs", false}, {rot, 36 * (size_t)N, "rot", false}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((N + 255) / 256), block(256);
   if (deg == 0) {
-    const size_t n = (size_t)N * (size_t)M * 3;
     const size_t blocks = (n + 255) / 256;
     if (shs_out != shs) hipLaunchKernelGGL(sh_rotate_copy_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), block, 0, s, n, shs, shs_out);
   } else if (deg == 1) {
@@ -163,7 +181,7 @@ int launch_sh_rotate(int N, int deg, int M, const float* shs, const float* rot, 
     hipLaunchKernelGGL(sh_rotate_kernel<3>, grid, block, 0, s, N, M, shs, rot, shs_out);
   }
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

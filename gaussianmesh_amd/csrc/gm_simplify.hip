@@ -49,7 +49,7 @@
 // Vertex ids read from faces and edges, face ids and offsets read from the CSR are forced into range: no fault, no meaning.
 // Conventions of gm_closest_face: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
-#include "../../include/gmesh_hip.h"
+#include "gm_check.h"
 #pragma clang fp contract(off)   // every product and sum rounds on its own, as the definition above says
 
 namespace gm {
@@ -92,11 +92,6 @@ struct SpWs {
   }
 };
 
-size_t mesh_collapse_round_workspace_bytes(int Vm) {
-  SpWs k = SpWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 0));
-  return (size_t)k.end + 256;
-}
-
 __device__ __forceinline__ float sp_dot(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 __device__ __forceinline__ void sp_normal(const float p0[3], const float p1[3], const float p2[3], float n[3]) {
   const float x[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]}, y[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
@@ -132,14 +127,6 @@ __global__ __launch_bounds__(256) void sp_quadrics(SpMesh m, float* __restrict__
   }
 #pragma unroll
   for (int k = 0; k < 10; k++) Q[10 * (size_t)v + k] = q[k];
-}
-
-int launch_mesh_quadrics(int Vm, const float* V, int F, const int* faces, const int* off, const int* adj, float* Q, hipStream_t s) {
-  if (Vm <= 0) return 0;
-  const SpMesh m = {Vm, F, V, faces, off, adj};
-  hipLaunchKernelGGL(sp_quadrics, dim3((unsigned)((Vm + 255) / 256)), dim3(256), 0, s, m, Q);
-  GM_HIP(hipGetLastError());
-  return 0;
 }
 
 // ---- one round ----
@@ -307,22 +294,70 @@ __global__ __launch_bounds__(256) void sp_select(SpMesh m, int E, const int* __r
   selected[e] = sel;
 }
 
-int launch_mesh_collapse_round(int Vm, const float* V, const float* Q, int F, const int* faces, const int* off, const int* adj, int E,
-                               const int* edges, const int* uses, float min_cos, float max_error, unsigned char* selected, int* from, int* to,
-                               unsigned long long* key, int* count, void* ws, size_t ws_bytes, hipStream_t s) {
-  const size_t need = mesh_collapse_round_workspace_bytes(Vm);
-  if (ws_bytes < need) { set_error("gm_mesh_collapse_round: workspace too small (%zu < %zu)", ws_bytes, need); return GM_ERR_BUFFER; }
-  if (E <= 0) return 0;
-  SpWs k = SpWs::from(ws, (size_t)Vm);
-  const SpMesh m = {Vm, F, V, faces, off, adj};
-  const float mc2 = min_cos * min_cos;
-  const dim3 threads(256), vb((unsigned)((Vm + 255) / 256)), eb((unsigned)((E + 255) / 256));
-  hipLaunchKernelGGL(sp_clear, vb, threads, 0, s, Vm, k.vmin, k.locked, count);
-  hipLaunchKernelGGL(sp_lock, eb, threads, 0, s, Vm, E, edges, uses, k.locked);
-  hipLaunchKernelGGL(sp_candidates, eb, threads, 0, s, m, Q, E, edges, uses, mc2, max_error, k.locked, k.vmin, from, to, key);
-  hipLaunchKernelGGL(sp_select, eb, threads, 0, s, m, E, from, to, key, k.vmin, selected, count);
-  GM_HIP(hipGetLastError());
-  return 0;
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+extern "C" {
+
+size_t gm_mesh_collapse_round_workspace_bytes(int Vm) {
+  SpWs k = SpWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 0));
+  return (size_t)k.end + 256;
 }
 
-}  // namespace gm
+int gm_mesh_quadrics(int Vm, const float* vertices, int F, const int* faces, const int* vf_offsets, const int* vf_faces, float* out_quadrics,
+                     void* stream) {
+  const char* fn = "gm_mesh_quadrics";
+  if (Vm < 0 || F < 0) { set_error("%s: negative size Vm=%d F=%d", fn, Vm, F); return GM_ERR_INVALID_ARG; }
+  if (F > 0x7FFFFFFF / 3) { set_error("%s: F=%d: 3 F must fit an int", fn, F); return GM_ERR_INVALID_ARG; }
+  if (Vm == 0) return GM_OK;
+  if (!vertices || !vf_offsets || !out_quadrics || (F > 0 && (!faces || !vf_faces))) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  const ByteRange rg[5] = {{vertices, 12 * (size_t)Vm, "vertices", false}, {faces, 12 * (size_t)F, "faces", false},
+                           {vf_offsets, 4 * ((size_t)Vm + 1), "vf_offsets", false}, {vf_faces, 12 * (size_t)F, "vf_faces", false},
+                           {out_quadrics, 40 * (size_t)Vm, "out_quadrics", true}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  const SpMesh m = {Vm, F, vertices, faces, vf_offsets, vf_faces};
+  hipLaunchKernelGGL(sp_quadrics, dim3((unsigned)((Vm + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), m, out_quadrics);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_mesh_collapse_round(int Vm, const float* vertices, const float* quadrics, int F, const int* faces, const int* vf_offsets, const int* vf_faces,
+                           int E, const int* edges, const int* edge_faces, float min_cos, float max_error, unsigned char* out_selected, int* out_from,
+                           int* out_to, unsigned long long* out_key, int* out_count, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "gm_mesh_collapse_round";
+  if (Vm < 0 || F < 0 || E < 0) { set_error("%s: negative size Vm=%d F=%d E=%d", fn, Vm, F, E); return GM_ERR_INVALID_ARG; }
+  if (F > 0x7FFFFFFF / 3) { set_error("%s: F=%d: 3 F must fit an int", fn, F); return GM_ERR_INVALID_ARG; }
+  if (!(min_cos >= 0.f) || min_cos > 3.4028234e38f) { set_error("%s: min_cos must be >= 0, finite and not NaN", fn); return GM_ERR_INVALID_ARG; }
+  if (!(max_error >= 0.f)) { set_error("%s: max_error must be >= 0 and not NaN (+inf: no bound)", fn); return GM_ERR_INVALID_ARG; }
+  if (E == 0) return GM_OK;
+  if (Vm == 0 || F == 0) { set_error("%s: %d edges of an empty mesh (Vm == %d, F == %d)", fn, E, Vm, F); return GM_ERR_INVALID_ARG; }
+  if (!vertices || !quadrics || !faces || !vf_offsets || !vf_faces || !edges || !edge_faces || !out_selected || !out_from || !out_to || !out_key ||
+      !out_count || !workspace) {
+    set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG;
+  }
+  if (reinterpret_cast<uintptr_t>(out_key) & 7) { set_error("%s: out_key must be 8-byte aligned", fn); return GM_ERR_INVALID_ARG; }
+  const ByteRange rg[13] = {{vertices, 12 * (size_t)Vm, "vertices", false}, {quadrics, 40 * (size_t)Vm, "quadrics", false}, {faces, 12 * (size_t)F, "faces", false},
+                            {vf_offsets, 4 * ((size_t)Vm + 1), "vf_offsets", false}, {vf_faces, 12 * (size_t)F, "vf_faces", false},
+                            {edges, 8 * (size_t)E, "edges", false}, {edge_faces, 4 * (size_t)E, "edge_faces", false},
+                            {out_selected, (size_t)E, "out_selected", true}, {out_from, 4 * (size_t)E, "out_from", true}, {out_to, 4 * (size_t)E, "out_to", true},
+                            {out_key, 8 * (size_t)E, "out_key", true}, {out_count, 4, "out_count", true}, {workspace, workspace_bytes, "workspace", true}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  const size_t need = gm_mesh_collapse_round_workspace_bytes(Vm);
+  if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  SpWs k = SpWs::from(workspace, (size_t)Vm);
+  const SpMesh m = {Vm, F, vertices, faces, vf_offsets, vf_faces};
+  const float mc2 = min_cos * min_cos;
+  const dim3 threads(256), vb((unsigned)((Vm + 255) / 256)), eb((unsigned)((E + 255) / 256));
+  hipLaunchKernelGGL(sp_clear, vb, threads, 0, s, Vm, k.vmin, k.locked, out_count);
+  hipLaunchKernelGGL(sp_lock, eb, threads, 0, s, Vm, E, edges, edge_faces, k.locked);
+  hipLaunchKernelGGL(sp_candidates, eb, threads, 0, s, m, quadrics, E, edges, edge_faces, mc2, max_error, k.locked, k.vmin, out_from, out_to, out_key);
+  hipLaunchKernelGGL(sp_select, eb, threads, 0, s, m, E, out_from, out_to, out_key, k.vmin, out_selected, out_count);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+}  // extern "C"

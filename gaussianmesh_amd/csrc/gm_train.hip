@@ -17,8 +17,24 @@
 //     and the rule above leaves p, m and v exactly as they are.  The kernel then does not touch them at all - at D = 0 that is
 //     45 of the 60 parameters of a Gaussian, 28 bytes each.
 #include "gm_common.h"
+#include "gm_check.h"
+#include <cmath>
 
 namespace gm {
+
+struct ActArgs {                 // mesh-bound parameter -> rasterizer-input map
+  int N;
+  float alpha;
+  const float *bc, *dist, *scaling, *rotation, *opacity, *v1, *v2, *v3, *normal, *r;
+};
+struct AdamTensor {
+  float* p; const float* g; float* m; float* v;
+  unsigned long long n;
+  float step_lo, step_hi;      // lr * sqrt(1-b2^t)/(1-b1^t) for elements with (index % period) < split / the others
+  unsigned period, split;      // period == 0: one rate (step_lo) for the whole tensor
+  unsigned active;             // 0: every element; else only elements with (index % period) < active (rounded up to a 16-byte granule) are touched
+};
+struct AdamTable { AdamTensor t[8]; int count; float b1, b2, eps, omb1, omb2; };   // omb = (float)(1 - beta), formed in double
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
@@ -128,26 +144,6 @@ __global__ __launch_bounds__(256) void mesh_activate_bwd_kernel(const ActArgs a,
   }
 }
 
-int launch_mesh_activate_fwd(const ActArgs& a, float* xyz, float* scales, float* rots, float* opac, float mr_weight, float* mr_partial,
-                             hipStream_t s) {
-  if (a.N <= 0) return 0;
-  hipLaunchKernelGGL(mesh_activate_fwd_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a, xyz, scales, reinterpret_cast<float4*>(rots), opac,
-                     mr_weight, mr_partial);
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
-int launch_mesh_activate_bwd(const ActArgs& a, const float* d_xyz, const float* d_scales, const float* d_rots, const float* d_opac,
-                             float* d_bc, float* d_dist, float* d_scaling, float* d_rotation, float* d_opacity, float mr_weight,
-                             const float* d_mr, hipStream_t s) {
-  if (a.N <= 0) return 0;
-  hipLaunchKernelGGL(mesh_activate_bwd_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a, d_xyz, d_scales,
-                     reinterpret_cast<const float4*>(d_rots), d_opac, d_bc, d_dist, d_scaling, reinterpret_cast<float4*>(d_rotation), d_opacity,
-                     mr_weight, d_mr);
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------
 // plain_activate_fwd / _bwd : GaussianModel's raw parameters -> rasterizer inputs and the adjoint (scene/gaussian_model.py:26-43,
 // 96-117): xyz copied, scales = exp(_scaling), rots = _rotation / max(|_rotation|, 1e-12), opac = sigmoid(_opacity).  The outputs
@@ -200,26 +196,6 @@ __global__ __launch_bounds__(256) void plain_activate_bwd_kernel(int N, const fl
   d_opacity[i] = g_opac ? (g_opac[i] * (1.0f - o)) * o : 0.f;
 }
 
-int launch_plain_activate_fwd(int N, const float* xyz_in, const float* scaling, const float* rotation, const float* opacity, float* xyz,
-                              float* scales, float* rots, float* opac, hipStream_t s) {
-  if (N <= 0) return 0;
-  hipLaunchKernelGGL(plain_activate_fwd_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, xyz_in, scaling,
-                     reinterpret_cast<const float4*>(rotation), opacity, xyz, scales, reinterpret_cast<float4*>(rots), opac);
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
-int launch_plain_activate_bwd(int N, const float* scaling, const float* rotation, const float* opacity, const float* g_xyz,
-                              const float* g_scales, const float* g_rots, const float* g_opac, float* d_xyz, float* d_scaling,
-                              float* d_rotation, float* d_opacity, hipStream_t s) {
-  if (N <= 0) return 0;
-  hipLaunchKernelGGL(plain_activate_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, scaling, reinterpret_cast<const float4*>(rotation),
-                     opacity, g_xyz, g_scales, reinterpret_cast<const float4*>(g_rots), g_opac, d_xyz, d_scaling,
-                     reinterpret_cast<float4*>(d_rotation), d_opacity);
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void adam_kernel(const AdamTable tab) {
   const AdamTensor t = tab.t[blockIdx.y];
@@ -268,18 +244,6 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTable tab) {
   }
 }
 
-int launch_adam(const AdamTable& tab, hipStream_t s) {
-  if (tab.count <= 0) return 0;
-  unsigned long long mx = 0;
-  for (int i = 0; i < tab.count; i++) mx = tab.t[i].n > mx ? tab.t[i].n : mx;
-  unsigned long long nb = (mx / 4 + 255) / 256;
-  if (nb < 1) nb = 1;
-  if (nb > 16384) nb = 16384;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)nb, (unsigned)tab.count), dim3(256), 0, s, tab);
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Densification statistics of one training iteration (train_mesh_gaussian.py:119-126) in one pass:
 //   max_radii2D[vis] = max(max_radii2D[vis], radii[vis])                                            (:123)
@@ -298,11 +262,151 @@ __global__ __launch_bounds__(256) void densify_stats_kernel(int N, const int* __
   denom[i] += 1.0f;
 }
 
-int launch_densify_stats(int N, const int* radii, const float* grad2d, float* max_radii2D, float* grad_accum, float* denom, hipStream_t s) {
-  if (N <= 0) return 0;
-  hipLaunchKernelGGL(densify_stats_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, radii, grad2d, max_radii2D, grad_accum, denom);
-  GM_HIP(hipGetLastError());
-  return 0;
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+// the operands the mesh-bound activation and its adjoint share
+static int fill_act(ActArgs& a, int N, float alpha, const float* bc, const float* dist, const float* scaling, const float* rotation,
+                    const float* opacity, const float* v1, const float* v2, const float* v3, const float* normal, const float* r) {
+  if (N < 0) { set_error("gm_mesh_activate: negative N"); return GM_ERR_INVALID_ARG; }
+  if (N > 0 && (!bc || !dist || !scaling || !rotation || !opacity || !v1 || !v2 || !v3 || !normal || !r)) {
+    set_error("gm_mesh_activate: null input"); return GM_ERR_INVALID_ARG;
+  }
+  if (N > 0 && (reinterpret_cast<uintptr_t>(rotation) & 15)) { set_error("gm_mesh_activate: rotation must be 16-byte aligned"); return GM_ERR_INVALID_ARG; }
+  a.N = N; a.alpha = alpha; a.bc = bc; a.dist = dist; a.scaling = scaling; a.rotation = rotation; a.opacity = opacity;
+  a.v1 = v1; a.v2 = v2; a.v3 = v3; a.normal = normal; a.r = r;
+  return GM_OK;
 }
 
-}  // namespace gm
+extern "C" {
+
+int gm_mesh_activate_fwd(int N, float alpha, const float* bc, const float* dist, const float* scaling, const float* rotation,
+                         const float* opacity, const float* v1, const float* v2, const float* v3, const float* normal, const float* r,
+                         float* xyz, float* scales, float* rots, float* opac, float mr_weight, float* mr_partial, void* stream) {
+  ActArgs a;
+  if (int rc = fill_act(a, N, alpha, bc, dist, scaling, rotation, opacity, v1, v2, v3, normal, r)) return rc;
+  if (N == 0) return GM_OK;
+  if (!xyz || !scales || !rots || !opac || (reinterpret_cast<uintptr_t>(rots) & 15)) {
+    set_error("gm_mesh_activate_fwd: null output or unaligned rots"); return GM_ERR_INVALID_ARG;
+  }
+  hipLaunchKernelGGL(mesh_activate_fwd_kernel, dim3((N + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, xyz, scales,
+                     reinterpret_cast<float4*>(rots), opac, mr_weight, mr_partial);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_mesh_activate_bwd(int N, float alpha, const float* bc, const float* dist, const float* scaling, const float* rotation,
+                         const float* opacity, const float* v1, const float* v2, const float* v3, const float* normal, const float* r,
+                         const float* d_xyz, const float* d_scales, const float* d_rots, const float* d_opac, float* d_bc, float* d_dist,
+                         float* d_scaling, float* d_rotation, float* d_opacity, float mr_weight, const float* d_mr, void* stream) {
+  ActArgs a;
+  if (int rc = fill_act(a, N, alpha, bc, dist, scaling, rotation, opacity, v1, v2, v3, normal, r)) return rc;
+  if (N == 0) return GM_OK;
+  if (!d_bc || !d_dist || !d_scaling || !d_rotation || !d_opacity || (reinterpret_cast<uintptr_t>(d_rotation) & 15) ||
+      (d_rots && (reinterpret_cast<uintptr_t>(d_rots) & 15))) {
+    set_error("gm_mesh_activate_bwd: null output or unaligned rotation gradient"); return GM_ERR_INVALID_ARG;
+  }
+  hipLaunchKernelGGL(mesh_activate_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, d_xyz, d_scales,
+                     reinterpret_cast<const float4*>(d_rots), d_opac, d_bc, d_dist, d_scaling, reinterpret_cast<float4*>(d_rotation), d_opacity,
+                     mr_weight, d_mr);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_plain_activate_fwd(int N, const float* xyz, const float* scaling, const float* rotation, const float* opacity, float* out_xyz,
+                          float* out_scales, float* out_rots, float* out_opac, int row0, int capacity, void* stream) {
+  if (N < 0 || row0 < 0 || capacity < 0 || (long long)row0 + N > capacity) {
+    set_error("gm_plain_activate_fwd: rows [%d, %d + %d) do not fit a capacity of %d", row0, row0, N, capacity); return GM_ERR_INVALID_ARG;
+  }
+  if (N == 0) return GM_OK;
+  if (!xyz || !scaling || !rotation || !opacity || !out_xyz || !out_scales || !out_rots || !out_opac) {
+    set_error("gm_plain_activate_fwd: null pointer"); return GM_ERR_INVALID_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(rotation) | reinterpret_cast<uintptr_t>(out_rots)) & 15) {
+    set_error("gm_plain_activate_fwd: rotation / out_rots must be 16-byte aligned"); return GM_ERR_INVALID_ARG;
+  }
+  const size_t r = (size_t)row0;
+  hipLaunchKernelGGL(plain_activate_fwd_kernel, dim3((N + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), N, xyz, scaling,
+                     reinterpret_cast<const float4*>(rotation), opacity, out_xyz + 3 * r, out_scales + 3 * r, reinterpret_cast<float4*>(out_rots + 4 * r),
+                     out_opac + r);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_plain_activate_bwd(int N, const float* scaling, const float* rotation, const float* opacity, const float* g_xyz, const float* g_scales,
+                          const float* g_rots, const float* g_opac, int row0, int capacity, float* d_xyz, float* d_scaling, float* d_rotation,
+                          float* d_opacity, void* stream) {
+  if (N < 0 || row0 < 0 || capacity < 0 || (long long)row0 + N > capacity) {
+    set_error("gm_plain_activate_bwd: rows [%d, %d + %d) do not fit a capacity of %d", row0, row0, N, capacity); return GM_ERR_INVALID_ARG;
+  }
+  if (N == 0) return GM_OK;
+  if (!scaling || !rotation || !opacity || !d_xyz || !d_scaling || !d_rotation || !d_opacity) {
+    set_error("gm_plain_activate_bwd: null pointer"); return GM_ERR_INVALID_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(rotation) | reinterpret_cast<uintptr_t>(d_rotation) | reinterpret_cast<uintptr_t>(g_rots)) & 15) {
+    set_error("gm_plain_activate_bwd: rotation / g_rots / d_rotation must be 16-byte aligned"); return GM_ERR_INVALID_ARG;
+  }
+  const size_t r = (size_t)row0;
+  hipLaunchKernelGGL(plain_activate_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), N, scaling,
+                     reinterpret_cast<const float4*>(rotation), opacity, g_xyz ? g_xyz + 3 * r : nullptr, g_scales ? g_scales + 3 * r : nullptr,
+                     reinterpret_cast<const float4*>(g_rots ? g_rots + 4 * r : nullptr), g_opac ? g_opac + r : nullptr, d_xyz, d_scaling,
+                     reinterpret_cast<float4*>(d_rotation), d_opacity);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_adam_step(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                 const uint64_t* sizes, const float* lr, const float* lr_rest, const uint32_t* period, const uint32_t* split,
+                 double beta1, double beta2, double eps, int step, void* stream) {
+  return gm_adam_step_active(count, params, grads, exp_avg, exp_avg_sq, sizes, lr, lr_rest, period, split, nullptr, beta1, beta2, eps, step, stream);
+}
+
+int gm_adam_step_active(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                        const uint64_t* sizes, const float* lr, const float* lr_rest, const uint32_t* period, const uint32_t* split,
+                        const uint32_t* active, double beta1, double beta2, double eps, int step, void* stream) {
+  if (count < 0 || count > 8 || step < 1) { set_error("gm_adam_step: 0..8 tensors per call, step >= 1"); return GM_ERR_INVALID_ARG; }
+  if (count > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !sizes || !lr)) { set_error("gm_adam_step: null table"); return GM_ERR_INVALID_ARG; }
+  AdamTable tab;
+  tab.count = 0; tab.b1 = (float)beta1; tab.b2 = (float)beta2; tab.eps = (float)eps;
+  tab.omb1 = (float)(1.0 - beta1); tab.omb2 = (float)(1.0 - beta2);
+  const double corr = sqrt(1.0 - pow(beta2, (double)step)) / (1.0 - pow(beta1, (double)step));
+  unsigned long long mx = 0;                  // the longest tensor: it sizes the grid
+  for (int i = 0; i < count; i++) {
+    if (sizes[i] == 0) continue;
+    if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]) { set_error("gm_adam_step: null tensor %d", i); return GM_ERR_INVALID_ARG; }
+    if ((reinterpret_cast<uintptr_t>(params[i]) | reinterpret_cast<uintptr_t>(grads[i]) | reinterpret_cast<uintptr_t>(exp_avg[i]) |
+         reinterpret_cast<uintptr_t>(exp_avg_sq[i])) & 15) { set_error("gm_adam_step: tensor %d is not 16-byte aligned", i); return GM_ERR_INVALID_ARG; }
+    AdamTensor& t = tab.t[tab.count++];
+    t.p = params[i]; t.g = grads[i]; t.m = exp_avg[i]; t.v = exp_avg_sq[i]; t.n = sizes[i];
+    t.step_lo = (float)(lr[i] * corr);
+    t.period = period ? period[i] : 0u; t.split = split ? split[i] : 0u;
+    if (t.period & 3u) { set_error("gm_adam_step: period must be a multiple of 4"); return GM_ERR_INVALID_ARG; }
+    t.active = (active && active[i] && t.period && active[i] < t.period) ? active[i] : 0u;
+    if (t.active && (t.n % t.period) != 0) { set_error("gm_adam_step_active: tensor %d is not a whole number of periods", i); return GM_ERR_INVALID_ARG; }
+    t.step_hi = (float)((lr_rest && t.period) ? lr_rest[i] * corr : lr[i] * corr);
+    mx = t.n > mx ? t.n : mx;
+  }
+  if (tab.count == 0) return GM_OK;
+  unsigned long long nb = (mx / 4 + 255) / 256;
+  if (nb < 1) nb = 1;
+  if (nb > 16384) nb = 16384;
+  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)nb, (unsigned)tab.count), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tab);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_densify_stats(int N, const int* radii, const float* viewspace_grad, float* max_radii2D, float* grad_accum, float* denom, void* stream) {
+  if (N < 0 || (N > 0 && (!radii || !viewspace_grad || !max_radii2D || !grad_accum || !denom))) {
+    set_error("gm_densify_stats: bad args"); return GM_ERR_INVALID_ARG;
+  }
+  if (N == 0) return GM_OK;
+  hipLaunchKernelGGL(densify_stats_kernel, dim3((N + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), N, radii, viewspace_grad,
+                     max_radii2D, grad_accum, denom);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+}  // extern "C"

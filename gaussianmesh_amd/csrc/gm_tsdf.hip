@@ -35,6 +35,7 @@
 // boundaries: deterministic, and no workgroup ever waits for another.
 // Conventions of gm_closest_face: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
+#include "gm_check.h"
 #include "gm_wave.h"
 #pragma clang fp contract(off)   // every product and sum rounds on its own, as the definition above says
 
@@ -84,18 +85,6 @@ __global__ __launch_bounds__(256) void ts_integrate(int K, int H, int W, const f
   weight[i] = w;
 }
 
-int launch_tsdf_integrate(int K, int H, int W, const float* depth, const float* alpha, const float* views, const float* tans, int nx, int ny,
-                          int nz, const float* origin, float voxel, float trunc, float alpha_min, int carve, float* tsdf, float* weight,
-                          hipStream_t s) {
-  if (K <= 0) return 0;
-  const TsdfGrid g = {nx, ny, nz, origin[0], origin[1], origin[2], voxel};
-  const size_t n = (size_t)nx * ny * nz;
-  hipLaunchKernelGGL(ts_integrate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, K, H, W, depth, alpha, views, tans, g, trunc, alpha_min,
-                     carve, tsdf, weight);
-  GM_HIP(hipGetLastError());
-  return 0;
-}
-
 // ---- surface nets ----
 struct SnWs {
   uint8_t* act;                  // [n] the cell whose lowest corner is sample g is active (0 where there is no such cell)
@@ -126,11 +115,6 @@ struct SnWs {
 };
 
 static inline size_t sn_samples(int nx, int ny, int nz) { return (size_t)(nx > 2 ? nx : 2) * (size_t)(ny > 2 ? ny : 2) * (size_t)(nz > 2 ? nz : 2); }
-
-size_t surface_nets_workspace_bytes(int nx, int ny, int nz) {
-  SnWs k = SnWs::from(nullptr, sn_samples(nx, ny, nz));
-  return (size_t)k.end + 256;
-}
 
 // exclusive scan of one value per thread over the 256 threads of the workgroup (every thread calls it); total = the sum of all
 __device__ __forceinline__ uint32_t sn_block_scan(uint32_t v, uint32_t* lds, uint32_t& total) {
@@ -286,14 +270,63 @@ __global__ __launch_bounds__(256) void sn_faces(SnDims dm, const float* __restri
   }
 }
 
-int launch_surface_nets(int nx, int ny, int nz, const float* origin, float voxel, const float* tsdf, const float* weight, float min_weight,
-                        int max_vertices, float* out_vertices, int max_faces, int* out_faces, int* out_counts, void* ws, size_t ws_bytes,
-                        hipStream_t s) {
-  const size_t need = surface_nets_workspace_bytes(nx, ny, nz);
-  if (ws_bytes < need) { set_error("gm_surface_nets: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+extern "C" {
+
+int gm_tsdf_integrate(int K, int H, int W, const float* depth, const float* alpha, const float* views, const float* tanfov, int nx, int ny, int nz,
+                      const float* origin, float voxel, float trunc, float alpha_min, int carve, float* tsdf, float* weight, void* stream) {
+  const char* fn = "gm_tsdf_integrate";
+  if (K < 0 || H <= 0 || W <= 0 || H > (1 << 24) || W > (1 << 24)) { set_error("%s: invalid sizes K=%d H=%d W=%d", fn, K, H, W); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_tsdf_grid(fn, nx, ny, nz, 1, origin, voxel)) return rc;
+  if (!(trunc > 0.f) || trunc > 3.4028234e38f || alpha_min != alpha_min) {
+    set_error("%s: trunc must be positive and finite, alpha_min not NaN", fn); return GM_ERR_INVALID_ARG;
+  }
+  if (!tsdf || !weight) { set_error("%s: null pointer (tsdf / weight)", fn); return GM_ERR_INVALID_ARG; }
+  // the volume against itself (also when there is nothing to integrate), then - once the maps are known to be there - against what is read
+  const size_t n = (size_t)nx * ny * nz, maps = 4 * (size_t)K * H * W;
+  const ByteRange rg[6] = {{tsdf, 4 * n, "tsdf", true}, {weight, 4 * n, "weight", true}, {depth, maps, "depth", false}, {alpha, maps, "alpha", false},
+                           {views, 64 * (size_t)K, "views", false}, {tanfov, 8 * (size_t)K, "tanfov", false}};
+  if (int rc = check_ranges(fn, rg, 2)) return rc;
+  if (K == 0) return GM_OK;
+  if (!depth || !alpha || !views || !tanfov) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  if (int rc = check_ranges(fn, rg)) return rc;
+  const TsdfGrid g = {nx, ny, nz, origin[0], origin[1], origin[2], voxel};
+  hipLaunchKernelGGL(ts_integrate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), K, H, W, depth, alpha, views,
+                     tanfov, g, trunc, alpha_min, carve, tsdf, weight);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+size_t gm_surface_nets_workspace_bytes(int nx, int ny, int nz) {
+  SnWs k = SnWs::from(nullptr, sn_samples(nx, ny, nz));
+  return (size_t)k.end + 256;
+}
+
+int gm_surface_nets(int nx, int ny, int nz, const float* origin, float voxel, const float* tsdf, const float* weight, float min_weight,
+                    int max_vertices, float* out_vertices, int max_faces, int* out_faces, int* out_counts, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  const char* fn = "gm_surface_nets";
+  if (int rc = check_tsdf_grid(fn, nx, ny, nz, 2, origin, voxel)) return rc;
+  if (min_weight != min_weight) { set_error("%s: min_weight is NaN", fn); return GM_ERR_INVALID_ARG; }
+  if (max_vertices < 0 || max_faces < 0) { set_error("%s: negative capacity (%d vertices, %d faces)", fn, max_vertices, max_faces); return GM_ERR_INVALID_ARG; }
+  if (!tsdf || !weight || !out_counts || !workspace || (max_vertices > 0 && !out_vertices) || (max_faces > 0 && !out_faces)) {
+    set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG;
+  }
   const SnDims dm = {{nx, ny, nz}};
   const size_t n = dm.total();
-  SnWs k = SnWs::from(ws, n);
+  const ByteRange rg[6] = {{tsdf, 4 * n, "tsdf", false}, {weight, 4 * n, "weight", false},               // (only read: they may be one buffer)
+                           {out_vertices, 12 * (size_t)max_vertices, "out_vertices", true}, {out_faces, 12 * (size_t)max_faces, "out_faces", true},
+                           {out_counts, 8, "out_counts", true}, {workspace, workspace_bytes, "workspace", true}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  const size_t need = gm_surface_nets_workspace_bytes(nx, ny, nz);
+  if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  SnWs k = SnWs::from(workspace, n);
   const TsdfGrid gr = {nx, ny, nz, origin[0], origin[1], origin[2], voxel};
   const dim3 blocks((unsigned)k.len[0]), threads(SN_BLOCK);
   hipLaunchKernelGGL(sn_cells, blocks, threads, 0, s, dm, tsdf, weight, min_weight, k.act);
@@ -306,7 +339,7 @@ int launch_surface_nets(int nx, int ny, int nz, const float* origin, float voxel
   hipLaunchKernelGGL(sn_vertices, blocks, threads, 0, s, dm, tsdf, k.flags, k.lvl[0], gr, max_vertices, k.vid, out_vertices);
   hipLaunchKernelGGL(sn_faces, blocks, threads, 0, s, dm, tsdf, k.flags, k.lvl[0], k.vid, max_faces, out_faces);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

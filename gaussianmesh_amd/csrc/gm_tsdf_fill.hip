@@ -25,6 +25,7 @@
 // counts are integer atomics over per-workgroup sums: the same in every run.
 // Conventions of gm_tsdf.hip: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
+#include "gm_check.h"
 #include "gm_wave.h"
 #pragma clang fp contract(off)   // every sum and quotient rounds on its own, as the definition above says
 
@@ -70,11 +71,6 @@ struct TfWs {
     return k;
   }
 };
-
-size_t tsdf_fill_workspace_bytes(int nx, int ny, int nz) {
-  const TfWs k = TfWs::from(nullptr, TfGrid::of(nx > 2 ? nx : 2, ny > 2 ? ny : 2, nz > 2 ? nz : 2));
-  return (size_t)k.end + 256;    // (the caller's pointer may sit anywhere inside a 256-byte line)
-}
 
 // (val_0, known_0) into both pairs, the brick's byte, and the counters back to zero
 __global__ __launch_bounds__(256) void tf_init(TfGrid g, const float* __restrict__ tsdf_in, const float* __restrict__ weight_in, float min_weight,
@@ -159,13 +155,37 @@ __global__ __launch_bounds__(256) void tf_finish(size_t n, const float* __restri
   }
 }
 
-int launch_tsdf_fill(int nx, int ny, int nz, const float* tsdf_in, const float* weight_in, float min_weight, int iterations, int boundary_free,
-                     float fill_weight, float* tsdf_out, float* weight_out, int* out_counts, void* ws, size_t ws_bytes, hipStream_t s) {
-  const size_t need = tsdf_fill_workspace_bytes(nx, ny, nz);
-  if (ws_bytes < need) { set_error("gm_tsdf_fill: workspace too small (%zu < %zu)", ws_bytes, need); return 3; }
+}  // namespace gm
+
+// ---------------------------------------------------------------------------------------------
+// the entry points (include/gmesh_hip.h): their refusals, then the launches
+using namespace gm;
+
+extern "C" {
+
+size_t gm_tsdf_fill_workspace_bytes(int nx, int ny, int nz) {
+  const TfWs k = TfWs::from(nullptr, TfGrid::of(nx > 2 ? nx : 2, ny > 2 ? ny : 2, nz > 2 ? nz : 2));
+  return (size_t)k.end + 256;    // (the caller's pointer may sit anywhere inside a 256-byte line)
+}
+
+int gm_tsdf_fill(int nx, int ny, int nz, const float* tsdf_in, const float* weight_in, float min_weight, int iterations, int boundary_free,
+                 float fill_weight, float* tsdf_out, float* weight_out, int* out_counts, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "gm_tsdf_fill";
+  static const float no_origin[3] = {0.f, 0.f, 0.f};                  // (the fill knows samples, not where they lie)
+  if (int rc = check_tsdf_grid(fn, nx, ny, nz, 2, no_origin, 1.0f)) return rc;
+  if (iterations < 0) { set_error("%s: iterations = %d (negative)", fn, iterations); return GM_ERR_INVALID_ARG; }
+  if (min_weight != min_weight || fill_weight != fill_weight) { set_error("%s: min_weight or fill_weight is NaN", fn); return GM_ERR_INVALID_ARG; }
+  if (!tsdf_in || !weight_in || !tsdf_out || !weight_out || !workspace) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
   const TfGrid g = TfGrid::of(nx, ny, nz);
-  const TfWs k = TfWs::from(ws, g);
   const size_t n = g.samples();
+  const ByteRange rg[6] = {{tsdf_in, 4 * n, "tsdf_in", false}, {weight_in, 4 * n, "weight_in", false},     // (only read: they may be one buffer)
+                           {tsdf_out, 4 * n, "tsdf_out", true}, {weight_out, 4 * n, "weight_out", true}, {out_counts, 8, "out_counts", true},
+                           {workspace, workspace_bytes, "workspace", true}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  const size_t need = gm_tsdf_fill_workspace_bytes(nx, ny, nz);
+  if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const TfWs k = TfWs::from(workspace, g);
   const dim3 bricks((unsigned)g.bricks()), threads(256);
   float* val[2] = {tsdf_out, k.val};
   hipLaunchKernelGGL(tf_init, bricks, threads, 0, s, g, tsdf_in, weight_in, min_weight, val[0], val[1], k.state[0], k.state[1], k.open, out_counts);
@@ -174,7 +194,7 @@ int launch_tsdf_fill(int nx, int ny, int nz, const float* tsdf_in, const float* 
     hipLaunchKernelGGL(tf_step, bricks, threads, 0, s, g, boundary_free ? 1 : 0, k.open, val[cur], k.state[cur], val[cur ^ 1], k.state[cur ^ 1]);
   hipLaunchKernelGGL(tf_finish, dim3((unsigned)((n + 255) / 256)), threads, 0, s, n, weight_in, k.state[0], fill_weight, weight_out, out_counts);
   GM_HIP(hipGetLastError());
-  return 0;
+  return GM_OK;
 }
 
-}  // namespace gm
+}  // extern "C"

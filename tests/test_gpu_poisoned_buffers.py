@@ -16,20 +16,20 @@ loop bound of four billion):
   rasterizer, geometry buffer   launch_arm_counters (gm_binning.hip:29) zero-fills slots | counters | coarse | acc | chunk_inst in one
                                 memset (arm_words) as the first launch of every first half; the direct placement's arm_direct_kernel
                                 (gm_bucket.hip:871) does the same plus the slab's bucket counters.  The preprocess kernels write radii,
-                                tiles_touched, bin, inst16, depth_key of EVERY row (gm_preprocess.hip:147-153: radius 0, an empty record,
+                                tiles_touched, bin, inst16, depth_key of EVERY row (gm_preprocess.hip:148-154: radius 0, an empty record,
                                 key 0xFFFFFFFF for a culled row).  splat, clamped and cov3D of a culled row stay UNWRITTEN: the kernel
-                                breaks out before those stores (gm_preprocess.hip:96-116, 140-142).  Nothing reads them: the ordering
+                                breaks out before those stores (gm_preprocess.hip:97-117, 141-143).  Nothing reads them: the ordering
                                 and the blend reach a row through order / pairs, which hold visible ids only, and preprocess_bwd
-                                loads splat / cov3D / clamped only under radii > 0 (gm_preprocess.hip:296-324).
+                                loads splat / cov3D / clamped only under radii > 0 (gm_preprocess.hip:291-319).
                                 bk_hist_kernel writes hist, dmap, bmap and counters[VISIBLE / NBUCKETS / RENDERED / CMIN / CMAX],
                                 bk_scan_kernel bucket_start, bk_scatter dpairs, bucket_sort_kernel order[:V] and chunk_inst.  Every loop
                                 bound read from memory is one of those counters or bucket_start, behind their writers.
   rasterizer, binning buffer    duplicate_kernel zeroes acc (gm_binning.hip:83) and writes pairs[0][:num_rendered], refusing when
                                 counters[RENDERED] > capacity; the tile pass writes hist before bk_scan reads it and pairs[1].
-  rasterizer, image buffer      ranges: hipMemsetAsync (gm_api.hip:309, gm_binning.hip:306, gm_bucket.hip:1032) or every entry by bk_scan;
+  rasterizer, image buffer      ranges: hipMemsetAsync (gm_api.hip:259, gm_binning.hip:306, gm_bucket.hip:1032) or every entry by bk_scan;
                                 tile_order / tile_work by tile_order_by before the blend reads them; final_T / n_contrib by the blend for
                                 every pixel inside the image (unless image_only); epoch only read with a work hint, which writes it first.
-  rasterizer, backward          grad_acc: hipMemsetAsync (gm_api.hip:590, "the only zero-fill of a backward"); preprocess_bwd writes
+  rasterizer, backward          grad_acc: hipMemsetAsync (gm_api.hip:518, "the only zero-fill of a backward"); preprocess_bwd writes
                                 every row of every gradient output, zeros for culled rows.
   radix sort (knn, closest)     hist by radix_hist_kernel, digit_total by radix_scan_kernel, both before radix_scatter reads them.
   Morton front end (knn,        bbox_partial[nb] by point_bbox_partial (all nb partials), bbox by point_bbox_final, keys by point_morton /
@@ -78,7 +78,7 @@ def _default_emission_policy():
 SCRATCH_VIEWS = [
     dict(buffer="geom", field="splat", dtype=torch.float32, keep="rows with radii > 0",
          quote='gmesh_hip.h:176 "the record the blend kernels gather": a culled Gaussian has no instance, nothing gathers its row, and the forward '
-               'preprocess kernels leave it unwritten (gm_preprocess.hip:96-116 breaks out before splat_store; no header sentence promises its content)'),
+               'preprocess kernels leave it unwritten (gm_preprocess.hip:97-117 breaks out before splat_store; no header sentence promises its content)'),
     dict(buffer="geom", field="bucket_start", dtype=torch.int32, keep="entry [2048] = V",
          quote='gmesh_hip.h:182 "V = \"bucket_start\"[2048]"'),
     dict(buffer="geom", field="order", dtype=torch.int32, keep="entries [0, V)",
