@@ -6,10 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+from ._op import enqueue, host, on_device, workspace
 
 
 def edge_csr(vertices, faces):
@@ -18,8 +15,8 @@ def edge_csr(vertices, faces):
     float32 vertices: every face corner c opposite edge (a, b) adds max(0.5 cot(angle at c), 1e-3) to w_ab, cot = (u . w) / |u x w| with
     u = a - c, w = b - c; a face with |u x w| <= 1e-30 adds nothing (an edge that only such faces hold does not appear).  Every weight
     is positive.  Host, numpy only; once per mesh, like deform.vertex_face_adjacency."""
-    v = np.asarray(_host(vertices), np.float32).astype(np.float64)
-    f = np.asarray(_host(faces)).astype(np.int64).reshape(-1, 3)
+    v = np.asarray(host(vertices), np.float32).astype(np.float64)
+    f = np.asarray(host(faces)).astype(np.int64).reshape(-1, 3)
     if v.ndim != 2 or v.shape[1] != 3:
         raise ValueError("edge_csr: vertices must be [Vm,3]; got %s" % (tuple(v.shape),))
     Vm = v.shape[0]
@@ -45,7 +42,7 @@ def edge_csr(vertices, faces):
     return offsets.astype(np.int32), cols.astype(np.int32), weights
 
 
-def _components(Vm, rows, cols):
+def components(Vm, rows, cols):
     """Label of the connected component of every vertex (the smallest vertex id in it): min-label propagation with pointer jumping."""
     label = np.arange(Vm, dtype=np.int64)
     while True:
@@ -76,11 +73,11 @@ class ArapSolver:
 
     def __init__(self, rest_vertices, faces, handles, device="cuda"):
         self.device = torch.device(device)
-        v = np.ascontiguousarray(np.asarray(_host(rest_vertices), np.float32))
+        v = np.ascontiguousarray(np.asarray(host(rest_vertices), np.float32))
         if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] == 0:
             raise ValueError("ArapSolver: rest_vertices must be [Vm,3] with Vm > 0; got %s" % (tuple(v.shape),))
         Vm = v.shape[0]
-        h = np.asarray(_host(handles)).reshape(-1)
+        h = np.asarray(host(handles)).reshape(-1)
         if h.size == 0:
             raise ValueError("ArapSolver: the handle set is empty")
         if h.dtype.kind not in "iu":
@@ -95,7 +92,7 @@ class ArapSolver:
         pinned = np.bincount(rows, weights=weights, minlength=Vm) <= 0.0
         fixed = pinned.copy()
         fixed[h] = True
-        label = _components(Vm, rows, cols.astype(np.int64))
+        label = components(Vm, rows, cols.astype(np.int64))
         has_handle = np.zeros(Vm, bool)
         has_handle[label[h]] = True
         loose = np.nonzero(~fixed & ~has_handle[label])[0]
@@ -106,13 +103,12 @@ class ArapSolver:
         self.csr = (off, cols, weights)
         if self.device.type != "cuda":                                 # the set-up above is host work; solve() needs the device
             return
-        t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=self.device)
+        t = lambda a, dt: on_device(a, dt, self.device)
         self.rest = t(v, torch.float32)
         self._off, self._cols, self._w = t(off, torch.int32), t(cols, torch.int32), t(weights, torch.float64)
         self._fixed = t(fixed.astype(np.uint8), torch.uint8)
         self._handle_idx = t(h, torch.int64)
-        self._nbytes = _lib.lib().gm_arap_workspace_bytes(Vm)
-        self._ws = torch.empty((self._nbytes,), dtype=torch.uint8, device=self.device)
+        self._ws = workspace(self.device, "gm_arap_workspace_bytes", Vm)
         self._grid_ws = None                                           # the whole-chip global step's own workspace: made by its first solve
         self._batch_ws = {}                                            # global_step -> solve_batch's workspace, grown to the largest B seen
 
@@ -136,7 +132,6 @@ class ArapSolver:
             raise ValueError('ArapSolver.solve: global_step must be "column" or "grid"; got %r' % (global_step,))
         if self.device.type != "cuda":
             raise _lib.GmeshError("ArapSolver.solve needs a HIP (cuda) device; there is no CPU path")
-        lib = _lib.lib()
         Vm, dev = self.Vm, self.device
         hp = torch.as_tensor(handle_positions, dtype=torch.float32, device=dev) if not torch.is_tensor(handle_positions) else \
             handle_positions.detach().to(device=dev, dtype=torch.float32)
@@ -160,15 +155,12 @@ class ArapSolver:
         stats = torch.zeros((int(outer_iterations), 8), dtype=torch.float64, device=dev) if want_stats and outer_iterations > 0 else None
         if global_step == "grid":
             if self._grid_ws is None:
-                self._grid_ws = torch.empty((lib.gm_arap_grid_workspace_bytes(Vm),), dtype=torch.uint8, device=dev)
-            entry, ws = lib.gm_arap_solve_grid, self._grid_ws
+                self._grid_ws = workspace(dev, "gm_arap_grid_workspace_bytes", Vm)
+            entry, ws = "gm_arap_solve_grid", self._grid_ws
         else:
-            entry, ws = lib.gm_arap_solve, self._ws
-        with torch.cuda.device(dev):
-            _lib.check(entry(Vm, self._off.data_ptr(), self._cols.data_ptr(), self._w.data_ptr(), self.rest.data_ptr(),
-                             self._fixed.data_ptr(), guess.data_ptr(), int(outer_iterations), int(cg_iterations), float(cg_tolerance),
-                             out.data_ptr(), None if stats is None else stats.data_ptr(), ws.data_ptr(), ws.numel(),
-                             torch.cuda.current_stream(dev).cuda_stream))
+            entry, ws = "gm_arap_solve", self._ws
+        enqueue(dev, entry, Vm, self._off, self._cols, self._w, self.rest, self._fixed, guess, int(outer_iterations), int(cg_iterations),
+                float(cg_tolerance), out, stats, workspace=ws)
         if want_stats:
             return out, (stats if stats is not None else torch.zeros((0, 8), dtype=torch.float64, device=dev))
         return out
@@ -190,7 +182,6 @@ class ArapSolver:
             raise ValueError('ArapSolver.solve_batch: global_step must be "column" or "grid"; got %r' % (global_step,))
         if self.device.type != "cuda":
             raise _lib.GmeshError("ArapSolver.solve_batch needs a HIP (cuda) device; there is no CPU path")
-        lib = _lib.lib()
         Vm, dev, H = self.Vm, self.device, len(self.handles)
         hp = torch.as_tensor(np.asarray(handle_positions), dtype=torch.float32, device=dev) if not torch.is_tensor(handle_positions) else \
             handle_positions.detach().to(device=dev, dtype=torch.float32)
@@ -217,15 +208,12 @@ class ArapSolver:
             out = guess
         stats = torch.zeros((B, int(outer_iterations), 8), dtype=torch.float64, device=dev) if want_stats and outer_iterations > 0 else None
         step = 1 if global_step == "grid" else 0
-        need = lib.gm_arap_batch_workspace_bytes(Vm, B, step)
+        need = _lib.lib().gm_arap_batch_workspace_bytes(Vm, B, step)
         ws = self._batch_ws.get(global_step)
         if ws is None or ws.numel() < need:
             ws = self._batch_ws[global_step] = torch.empty((need,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.gm_arap_solve_batch(B, step, Vm, self._off.data_ptr(), self._cols.data_ptr(), self._w.data_ptr(), self.rest.data_ptr(),
-                                               self._fixed.data_ptr(), guess.data_ptr(), int(outer_iterations), int(cg_iterations),
-                                               float(cg_tolerance), out.data_ptr(), None if stats is None else stats.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+        enqueue(dev, "gm_arap_solve_batch", B, step, Vm, self._off, self._cols, self._w, self.rest, self._fixed, guess, int(outer_iterations),
+                int(cg_iterations), float(cg_tolerance), out, stats, workspace=ws)
         if want_stats:
             return out, (stats if stats is not None else torch.zeros((B, 0, 8), dtype=torch.float64, device=dev))
         return out

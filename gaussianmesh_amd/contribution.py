@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import GmeshError
+from ._op import enqueue, need_cuda
 
 WEIGHT_UNIT = 2.0 ** -24          # sums[:, 0] counts weights in this unit, sums[:, 1] in WEIGHT_UNIT / 255 (mask bytes 0..255)
 
@@ -47,8 +48,7 @@ def blend_weights(policy, geom, binning, img, P, width, height, mask=None, sums=
         if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous():
             raise GmeshError("blend_weights: %s must be the contiguous uint8 buffer a forward returned" % name)
     device = geom.device
-    if device.type != "cuda":
-        raise GmeshError("blend_weights needs buffers on a HIP (cuda) device; there is no CPU path")
+    need_cuda(device, "blend_weights", "buffers")
     for name, t in (("binning", binning), ("img", img)):
         if t.device != device:
             raise GmeshError("blend_weights: %s is on %s, geom on %s" % (name, t.device, device))
@@ -65,11 +65,9 @@ def blend_weights(policy, geom, binning, img, P, width, height, mask=None, sums=
         peak = torch.zeros((P,), dtype=torch.int32, device=device)
     _check("sums", sums, torch.int64, (P, 2), device)
     _check("peak", peak, torch.int32, (P,), device)
-    if stream is None:
-        stream = torch._C._cuda_getCurrentRawStream(device.index)
-    ptr = lambda t: None if (t is None or t.numel() == 0) else t.data_ptr()
-    with torch.cuda.device(device):
-        _lib.check(lib.gm_blend_weights(int(policy), ptr(geom), ptr(binning), ptr(img), P, cap, W, H, ptr(mask), ptr(sums), ptr(peak), 0, stream))
+    some = lambda t: None if (t is None or t.numel() == 0) else t                  # (an empty tensor goes as NULL)
+    enqueue(device, "gm_blend_weights", int(policy), some(geom), some(binning), some(img), P, cap, W, H, some(mask), some(sums), some(peak), 0,
+            stream=stream)
     return sums, peak
 
 

@@ -11,6 +11,7 @@ The arithmetic (gather, barycentric blend, RS cov RS^T, x + dx) runs in one HIP 
 import torch
 
 from . import _lib
+from ._op import enqueue, need_cuda
 
 
 def _f(t):
@@ -33,44 +34,34 @@ def barycentric_weights(points, p1, p2, p3):
 
 def deform_tensors(tri, w, dV, Rv, Sv, cov, pos):
     """gm_deform: returns (pos' [N,3], cov' [N,3,3], rot [N,3,3], cov6 [N,6])."""
-    lib = _lib.lib()
     device = pos.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("deform needs tensors on a HIP (cuda) device; there is no CPU path")
+    need_cuda(device, "deform", "tensors")
     tri = tri.detach().contiguous().to(torch.int32)
     w, dV, Rv, Sv, cov, pos = (_f(t) for t in (w, dV, Rv, Sv, cov, pos))
     N = pos.shape[0]
     f = dict(dtype=torch.float32, device=device)
     pos_o = torch.empty((N, 3), **f); cov_o = torch.empty((N, 3, 3), **f); rot_o = torch.empty((N, 3, 3), **f)
     cov6 = torch.empty((N, 6), **f)
-    with torch.cuda.device(device):
-        _lib.check(lib.gm_deform(N, tri.data_ptr(), w.data_ptr(), dV.data_ptr(), Rv.data_ptr(), Sv.data_ptr(), cov.data_ptr(),
-                                 pos.data_ptr(), pos_o.data_ptr(), cov_o.data_ptr(), rot_o.data_ptr(), cov6.data_ptr(),
-                                 torch.cuda.current_stream(device).cuda_stream))
+    enqueue(device, "gm_deform", N, tri, w, dV, Rv, Sv, cov, pos, pos_o, cov_o, rot_o, cov6)
     return pos_o, cov_o, rot_o, cov6
 
 
 def sh_colors(pos, campos, shs, rot=None, deg=3):
     """gm_sh_colors: max(SH_deg(rot^T normalize(pos - campos)) + 0.5, 0)  (edittool/__init__.py:442-448)."""
-    lib = _lib.lib()
     device = pos.device
     pos, campos, shs = _f(pos), _f(campos), _f(shs)
     rot = None if rot is None else _f(rot)
     N, M = shs.shape[0], shs.shape[1]
     rgb = torch.empty((N, 3), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(lib.gm_sh_colors(N, int(deg), M, pos.data_ptr(), campos.data_ptr(), None if rot is None else rot.data_ptr(),
-                                    shs.data_ptr(), rgb.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
+    enqueue(device, "gm_sh_colors", N, int(deg), M, pos, campos, rot, shs, rgb)
     return rgb
 
 
 def deform_shade(tri, w, dV, Rv, Sv, cov, pos, shs, campos, deg=3, want_cov_rot=False):
     """gm_deform_shade: fused deform + rotated-direction SH colour.  Returns (pos' [N,3], cov6 [N,6], rgb [N,3]) and, with
     want_cov_rot, also (cov' [N,3,3], rot [N,3,3])."""
-    lib = _lib.lib()
     device = pos.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("deform_shade needs tensors on a HIP (cuda) device; there is no CPU path")
+    need_cuda(device, "deform_shade", "tensors")
     tri = tri.detach().contiguous().to(torch.int32)
     w, dV, Rv, Sv, cov, pos, shs, campos = (_f(t) for t in (w, dV, Rv, Sv, cov, pos, shs, campos))
     N, M = pos.shape[0], shs.shape[1]
@@ -78,11 +69,7 @@ def deform_shade(tri, w, dV, Rv, Sv, cov, pos, shs, campos, deg=3, want_cov_rot=
     pos_o = torch.empty((N, 3), **f); cov6 = torch.empty((N, 6), **f); rgb = torch.empty((N, 3), **f)
     cov_o = torch.empty((N, 3, 3), **f) if want_cov_rot else None
     rot_o = torch.empty((N, 3, 3), **f) if want_cov_rot else None
-    with torch.cuda.device(device):
-        _lib.check(lib.gm_deform_shade(N, int(deg), M, tri.data_ptr(), w.data_ptr(), dV.data_ptr(), Rv.data_ptr(), Sv.data_ptr(),
-                                       cov.data_ptr(), pos.data_ptr(), shs.data_ptr(), campos.data_ptr(), pos_o.data_ptr(),
-                                       cov6.data_ptr(), rgb.data_ptr(), None if cov_o is None else cov_o.data_ptr(),
-                                       None if rot_o is None else rot_o.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
+    enqueue(device, "gm_deform_shade", N, int(deg), M, tri, w, dV, Rv, Sv, cov, pos, shs, campos, pos_o, cov6, rgb, cov_o, rot_o)
     return (pos_o, cov6, rgb, cov_o, rot_o) if want_cov_rot else (pos_o, cov6, rgb)
 
 
@@ -98,27 +85,21 @@ def pack_cov6(cov):
 
 def pack_mesh_state(state, verts, out=None):
     """gm_pack_mesh_state: [Vm,21] frame state (V1 | R | S) and rest pose verts [Vm,3] -> gather table [Vm,24]."""
-    lib = _lib.lib()
     device = state.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("pack_mesh_state needs tensors on a HIP (cuda) device; there is no CPU path")
+    need_cuda(device, "pack_mesh_state", "tensors")
     state, verts = _f(state), _f(verts)
     Vm = state.shape[0]
     if state.shape[1] != 21 or verts.shape != (Vm, 3):
         raise ValueError("pack_mesh_state: state must be [Vm,21] and verts [Vm,3]")
     packed = out if out is not None else torch.empty((Vm, 24), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(lib.gm_pack_mesh_state(Vm, state.data_ptr(), verts.data_ptr(), packed.data_ptr(),
-                                          torch.cuda.current_stream(device).cuda_stream))
+    enqueue(device, "gm_pack_mesh_state", Vm, state, verts, packed)
     return packed
 
 
 def deform_shade_packed(tri, w, packed, cov, pos, shs, campos, deg=3, want_cov_rot=False):
     """gm_deform_shade_packed: deform_shade with the per-vertex (dV, R, S) read from pack_mesh_state()'s table."""
-    lib = _lib.lib()
     device = pos.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("deform_shade needs tensors on a HIP (cuda) device; there is no CPU path")
+    need_cuda(device, "deform_shade", "tensors")
     tri = tri.detach().contiguous().to(torch.int32)
     w, packed, cov, pos, shs, campos = (_f(t) for t in (w, packed, cov, pos, shs, campos))
     N, M = pos.shape[0], shs.shape[1]
@@ -126,28 +107,20 @@ def deform_shade_packed(tri, w, packed, cov, pos, shs, campos, deg=3, want_cov_r
     pos_o = torch.empty((N, 3), **f); cov6 = torch.empty((N, 6), **f); rgb = torch.empty((N, 3), **f)
     cov_o = torch.empty((N, 3, 3), **f) if want_cov_rot else None
     rot_o = torch.empty((N, 3, 3), **f) if want_cov_rot else None
-    with torch.cuda.device(device):
-        _lib.check(lib.gm_deform_shade_packed(N, int(deg), M, tri.data_ptr(), w.data_ptr(), packed.data_ptr(), cov.data_ptr(),
-                                              pos.data_ptr(), shs.data_ptr(), campos.data_ptr(), pos_o.data_ptr(), cov6.data_ptr(),
-                                              rgb.data_ptr(), None if cov_o is None else cov_o.data_ptr(),
-                                              None if rot_o is None else rot_o.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
+    enqueue(device, "gm_deform_shade_packed", N, int(deg), M, tri, w, packed, cov, pos, shs, campos, pos_o, cov6, rgb, cov_o, rot_o)
     return (pos_o, cov6, rgb, cov_o, rot_o) if want_cov_rot else (pos_o, cov6, rgb)
 
 
 def cov_to_scale_rot(cov):
     """gm_cov_to_scale_rot: (scales [N,3], rotations [N,4]) whose covariance R diag(s^2) R^T equals cov [N,3,3]
     (the SceneVisualTool route: edittool/__init__.py:204-207, rasterised with scales/rotations instead of cov3D_precomp)."""
-    lib = _lib.lib()
     device = cov.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("cov_to_scale_rot needs a tensor on a HIP (cuda) device; there is no CPU path")
+    need_cuda(device, "cov_to_scale_rot", "a tensor")
     cov = _f(cov)
     N = cov.shape[0]
     scales = torch.empty((N, 3), dtype=torch.float32, device=device)
     rots = torch.empty((N, 4), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(lib.gm_cov_to_scale_rot(N, cov.data_ptr(), scales.data_ptr(), rots.data_ptr(),
-                                           torch.cuda.current_stream(device).cuda_stream))
+    enqueue(device, "gm_cov_to_scale_rot", N, cov, scales, rots)
     return scales, rots
 
 
@@ -156,10 +129,8 @@ def rotate_sh(shs, rot, deg=3, out=None):
     SH_deg(d) . c' == SH_deg(rot_i^T d) . c_i for every unit d, so that sh_colors(pos, campos, rotate_sh(shs, rot), rot=None) is
     sh_colors(pos, campos, shs, rot=rot) up to float32 rounding (exact for any 3x3 rot [N,3,3], e.g. deform_tensors' rot_out).
     Coefficients k >= (deg+1)^2 are copied.  out: the result's tensor ([N,M,3] float32, contiguous; may be shs itself: in place)."""
-    lib = _lib.lib()
     device = shs.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("rotate_sh needs tensors on a HIP (cuda) device; there is no CPU path")
+    need_cuda(device, "rotate_sh", "tensors")
     shs, rot = _f(shs), _f(rot)
     if shs.dim() != 3 or shs.shape[2] != 3:
         raise ValueError("rotate_sh: shs must be [N,M,3]")
@@ -170,8 +141,7 @@ def rotate_sh(shs, rot, deg=3, out=None):
         out = torch.empty_like(shs)
     elif out.dtype is not torch.float32 or not out.is_contiguous() or out.shape != shs.shape or out.device != device:
         raise ValueError("rotate_sh: out must be a contiguous float32 tensor of shs' shape on its device")
-    with torch.cuda.device(device):
-        _lib.check(lib.gm_sh_rotate(N, int(deg), M, shs.data_ptr(), rot.data_ptr(), out.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
+    enqueue(device, "gm_sh_rotate", N, int(deg), M, shs, rot, out)
     return out
 
 
@@ -191,20 +161,15 @@ def vertex_face_adjacency(faces, Vm):
 def mesh_rs_packed(rest_vertices, deformed_vertices, faces, adjacency, out=None):
     """gm_mesh_rs_packed: the per-vertex gather table [Vm,24] of the fused deformation kernels, straight from the deformed
     mesh (= pack_mesh_state(mesh_rs(..., want_state=True)[2], rest_vertices), bit for bit, in one launch)."""
-    lib = _lib.lib()
     device = rest_vertices.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("mesh_rs_packed needs tensors on a HIP (cuda) device; there is no CPU path")
+    need_cuda(device, "mesh_rs_packed", "tensors")
     V0, V1 = _f(rest_vertices), _f(deformed_vertices)
     Vm = V0.shape[0]
     if faces.dtype is not torch.int32 or not faces.is_contiguous():
         faces = faces.detach().contiguous().to(torch.int32)
     off, adj = adjacency
     packed = out if out is not None else torch.empty((Vm, 24), dtype=torch.float32, device=device)
-    from .rasterizer import _on, _stream
-    with _on(device):
-        _lib.check(lib.gm_mesh_rs_packed(Vm, faces.shape[0], V0.data_ptr(), V1.data_ptr(), faces.data_ptr(), off.data_ptr(), adj.data_ptr(),
-                                         packed.data_ptr(), _stream(device)))
+    enqueue(device, "gm_mesh_rs_packed", Vm, faces.shape[0], V0, V1, faces, off, adj, packed)
     return packed
 
 
@@ -213,10 +178,8 @@ def mesh_rs_packed_batch(rest_vertices, deformed_vertices_list, faces, adjacency
     rasterizer.forward_deformed_batch); deformed_vertices_list: K tensors [Vm,3]; out: optional [K,Vm,24] tensor, or a list of K
     contiguous [Vm,24] tensors (e.g. one object's rows of combined tables).  Returns the K tables (views of one [K,Vm,24] tensor, or
     the list), each bit for bit what mesh_rs_packed makes of its mesh."""
-    lib = _lib.lib()
     device = rest_vertices.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("mesh_rs_packed_batch needs tensors on a HIP (cuda) device; there is no CPU path")
+    need_cuda(device, "mesh_rs_packed_batch", "tensors")
     K = len(deformed_vertices_list)
     if not 1 <= K <= _lib.GM_BATCH_MAX:
         raise ValueError("mesh_rs_packed_batch: 1..%d frames" % _lib.GM_BATCH_MAX)
@@ -230,12 +193,9 @@ def mesh_rs_packed_batch(rest_vertices, deformed_vertices_list, faces, adjacency
     if isinstance(packed, (list, tuple)) and (len(packed) != K or any(t.shape != (Vm, 24) or not t.is_contiguous() for t in packed)):
         raise ValueError("mesh_rs_packed_batch: out must hold K contiguous [Vm,24] tables")
     import ctypes as C
-    from .rasterizer import _on, _stream
     pv = (C.c_void_p * K)(*[v.data_ptr() for v in V1])
     pp = (C.c_void_p * K)(*[packed[k].data_ptr() for k in range(K)])
-    with _on(device):
-        _lib.check(lib.gm_mesh_rs_packed_batch(K, Vm, faces.shape[0], V0.data_ptr(), pv, faces.data_ptr(), off.data_ptr(), adj.data_ptr(), pp,
-                                               _stream(device)))
+    enqueue(device, "gm_mesh_rs_packed_batch", K, Vm, faces.shape[0], V0, pv, faces, off, adj, pp)
     return [packed[k] for k in range(K)]
 
 
@@ -254,14 +214,14 @@ def plan_sequence(sizes, frames_per_launch=4, emission_policy=None, batchable=Tr
                  resolution ends a batch);
       "single" - a frame whose resolution the batch refuses (more than 2048 list tiles under its emission policy, or batchable False,
                  e.g. an empty cloud): the single-frame path, forward_deformed_begin / finish."""
-    from .rasterizer import _pol
+    from .rasterizer import emission_policy_of
     K = int(frames_per_launch)
     if not 1 <= K <= _lib.GM_BATCH_MAX:
         raise ValueError("frames_per_launch: 1..%d, got %r" % (_lib.GM_BATCH_MAX, frames_per_launch))
     plan, learned, run, run_size = [], set(), [], None
 
     def fits(W, H):                                        # gm_forward_deformed_batch_async: the one-pass tile sort (TileGrid in gm_common.h)
-        s = max(_pol(emission_policy, W, H) - 1, 0)
+        s = max(emission_policy_of(emission_policy, W, H) - 1, 0)
         gx, gy = (W + 15) // 16, (H + 15) // 16
         return ((gx + (1 << s) - 1) >> s) * ((gy + (1 << s) - 1) >> s) <= 2048
 
@@ -288,10 +248,8 @@ def mesh_rs(rest_vertices, deformed_vertices, faces, adjacency=None, want_state=
     of the rotation).
     adjacency: (offsets, face ids) device int32 tensors from vertex_face_adjacency (built here when None).
     want_state: also return the frame record [Vm,21] = V1 | R | S that pack_mesh_state consumes."""
-    lib = _lib.lib()
     device = rest_vertices.device
-    if device.type != "cuda":
-        raise _lib.GmeshError("mesh_rs needs tensors on a HIP (cuda) device; there is no CPU path")
+    need_cuda(device, "mesh_rs", "tensors")
     V0, V1 = _f(rest_vertices), _f(deformed_vertices)
     Vm = V0.shape[0]
     faces = faces.detach().contiguous().to(torch.int32)
@@ -302,10 +260,7 @@ def mesh_rs(rest_vertices, deformed_vertices, faces, adjacency=None, want_state=
     R = torch.empty((Vm, 3, 3), dtype=torch.float32, device=device)
     S = torch.empty((Vm, 3, 3), dtype=torch.float32, device=device)
     state = torch.empty((Vm, 21), dtype=torch.float32, device=device) if want_state else None
-    with torch.cuda.device(device):
-        _lib.check(lib.gm_mesh_rs(Vm, faces.shape[0], V0.data_ptr(), V1.data_ptr(), faces.data_ptr(), off.data_ptr(), adj.data_ptr(),
-                                  R.data_ptr(), S.data_ptr(), None if state is None else state.data_ptr(),
-                                  torch.cuda.current_stream(device).cuda_stream))
+    enqueue(device, "gm_mesh_rs", Vm, faces.shape[0], V0, V1, faces, off, adj, R, S, state)
     return (R, S, state) if want_state else (R, S)
 
 
@@ -380,9 +335,9 @@ class SingleObjectDeform:
         free_radius, every vertex farther than free_radius from all picks is held at rest; the others bend
         (mesh_region.region_handles: its order, its refusals).  Distances are computed up to free_radius (grab_radius without it).
         Builds the ArapSolver through set_handles (faces: as there) and returns it; the region ids are arap.handles."""
-        from .mesh_region import _check_radii, region_handles
+        from .mesh_region import check_radii, region_handles
         import numpy as np
-        grab, free = _check_radii("set_region_handles", grab_radius, free_radius)
+        grab, free = check_radii("set_region_handles", grab_radius, free_radius)
         hv = np.asarray(handle_vertices.detach().cpu() if torch.is_tensor(handle_vertices) else handle_vertices).reshape(-1)
         av = np.asarray(anchor_vertices.detach().cpu() if torch.is_tensor(anchor_vertices) else anchor_vertices).reshape(-1)
         if hv.size == 0:

@@ -17,6 +17,7 @@ the first image (the rendered one); the ground truth gets no gradient, as in the
 import torch
 
 from . import _lib
+from ._op import enqueue, f32, need_cuda
 
 
 def l1_loss(network_output, gt):
@@ -36,37 +37,28 @@ def _planes(img):
 
 
 def _fwd(img1, img2, want_grad):
-    lib = _lib.lib()
-    if img1.device.type != "cuda":
-        raise _lib.GmeshError("ssim needs tensors on a HIP (cuda) device; there is no CPU path")
+    need_cuda(img1, "ssim", "tensors")
     if img1.shape != img2.shape:
         raise ValueError("ssim: image shapes differ: %s vs %s" % (tuple(img1.shape), tuple(img2.shape)))
-    a = img1.detach().contiguous().float()
-    b = img2.detach().contiguous().float()
+    a, b = f32(img1), f32(img2)
     planes, _ = _planes(a)
     H, W = a.shape[-2], a.shape[-1]
     dev = a.device
-    n = int(lib.gm_ssim_partials(planes, H, W))
+    n = int(_lib.lib().gm_ssim_partials(planes, H, W))
     partial = torch.empty((n, 2), dtype=torch.float32, device=dev)
     maps = torch.empty((3,) + tuple(a.shape), dtype=torch.float32, device=dev) if want_grad else None
-    mp = [maps[i].data_ptr() for i in range(3)] if want_grad else [None, None, None]
-    with torch.cuda.device(dev):
-        _lib.check(lib.gm_ssim_fwd(a.data_ptr(), b.data_ptr(), planes, H, W, mp[0], mp[1], mp[2], partial.data_ptr(),
-                                   torch.cuda.current_stream(dev).cuda_stream))
+    mp = maps if want_grad else [None, None, None]
+    enqueue(dev, "gm_ssim_fwd", a, b, planes, H, W, mp[0], mp[1], mp[2], partial)
     return a, b, maps, partial.view(planes, -1, 2)
 
 
 def _bwd(a, b, maps, g_ssim_planes, g_l1):
-    lib = _lib.lib()
     planes, _ = _planes(a)
     H, W = a.shape[-2], a.shape[-1]
     grad = torch.empty_like(a)
     g_ssim_planes = g_ssim_planes.contiguous().float()          # views of one small tensor are contiguous already
     g_l1 = None if g_l1 is None else g_l1.reshape(1).contiguous().float()
-    with torch.cuda.device(a.device):
-        _lib.check(lib.gm_ssim_bwd(a.data_ptr(), b.data_ptr(), maps[0].data_ptr(), maps[1].data_ptr(), maps[2].data_ptr(), planes, H, W,
-                                   g_ssim_planes.data_ptr(), None if g_l1 is None else g_l1.data_ptr(), grad.data_ptr(),
-                                   torch.cuda.current_stream(a.device).cuda_stream))
+    enqueue(a.device, "gm_ssim_bwd", a, b, maps[0], maps[1], maps[2], planes, H, W, g_ssim_planes, g_l1, grad)
     return grad
 
 
@@ -131,9 +123,8 @@ class _Photometric(torch.autograd.Function):
             ctx.save_for_backward(a, b, maps, grad)
         out = torch.empty((), dtype=torch.float32, device=a.device)
         flat = partial.reshape(-1, 2)
-        with torch.cuda.device(a.device):                                      # lam + <(-lam/n, (1-lam)/n), (sum ssim, sum |a-b|)>, one launch
-            _lib.check(_lib.lib().gm_loss_combine(flat.data_ptr(), flat.shape[0], -lam / n, (1.0 - lam) / n, lam, out.data_ptr(),
-                                                  torch.cuda.current_stream(a.device).cuda_stream))
+        # lam + <(-lam/n, (1-lam)/n), (sum ssim, sum |a-b|)>, one launch
+        enqueue(a.device, "gm_loss_combine", flat, flat.shape[0], -lam / n, (1.0 - lam) / n, lam, out)
         return out
 
     @staticmethod
@@ -175,25 +166,21 @@ class _PhotometricU8(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, image, gt, background, lambda_dssim):
-        lib = _lib.lib()
-        if image.device.type != "cuda":
-            raise _lib.GmeshError("photometric_loss_u8 needs tensors on a HIP (cuda) device; there is no CPU path")
-        a = image.detach().contiguous().float()
+        need_cuda(image, "photometric_loss_u8", "tensors")
+        a = f32(image)
         rgb, mask, stride, bg, keep = _u8_args(a, gt, background)
         H, W = a.shape[-2], a.shape[-1]
         dev = a.device
         want_grad = ctx.needs_input_grad[0]
-        n_part = int(lib.gm_ssim_partials(3, H, W))
+        n_part = int(_lib.lib().gm_ssim_partials(3, H, W))
         partial = torch.empty((n_part, 2), dtype=torch.float32, device=dev)
         maps = torch.empty((3,) + tuple(a.shape), dtype=torch.float32, device=dev) if want_grad else None
-        mp = [maps[i].data_ptr() for i in range(3)] if want_grad else [None, None, None]
+        mp = maps if want_grad else [None, None, None]
         lam, n = float(lambda_dssim), a.numel()
         _, grad = _coefs(lam, n, 3, dev)
         out = torch.empty((), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.gm_ssim_fwd_u8(a.data_ptr(), rgb, mask, stride, bg, 3, H, W, mp[0], mp[1], mp[2], partial.data_ptr(), stream))
-            _lib.check(lib.gm_loss_combine(partial.data_ptr(), n_part, -lam / n, (1.0 - lam) / n, lam, out.data_ptr(), stream))
+        enqueue(dev, "gm_ssim_fwd_u8", a, rgb, mask, stride, bg, 3, H, W, mp[0], mp[1], mp[2], partial)
+        enqueue(dev, "gm_loss_combine", partial, n_part, -lam / n, (1.0 - lam) / n, lam, out)
         ctx.shape, ctx.u8 = image.shape, (rgb, mask, stride, bg, keep)
         ctx.partial = partial                    # (tests read the partial sums; a small tensor)
         if maps is not None:
@@ -208,10 +195,7 @@ class _PhotometricU8(torch.autograd.Function):
         g_ssim, g_l1 = gv[:3].contiguous(), gv[3:].contiguous()
         out = torch.empty_like(a)
         H, W = a.shape[-2], a.shape[-1]
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.lib().gm_ssim_bwd_u8(a.data_ptr(), rgb, mask, stride, bg, maps[0].data_ptr(), maps[1].data_ptr(), maps[2].data_ptr(),
-                                                 3, H, W, g_ssim.data_ptr(), g_l1.data_ptr(), out.data_ptr(),
-                                                 torch.cuda.current_stream(a.device).cuda_stream))
+        enqueue(a.device, "gm_ssim_bwd_u8", a, rgb, mask, stride, bg, maps[0], maps[1], maps[2], 3, H, W, g_ssim, g_l1, out)
         return out.view(ctx.shape), None, None, None
 
 

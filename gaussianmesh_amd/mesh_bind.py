@@ -5,13 +5,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._op import enqueue, f32, host, need_cuda, on_device, workspace
 from .deform import barycentric_weights
 
 
-def _mesh_arrays(vertices, faces, who):
+def mesh_arrays(vertices, faces, who):
     """(vertices, faces) as host arrays, shapes and index range checked: the device cannot report an index outside [0, Vm)."""
-    v = vertices.detach().cpu().numpy() if torch.is_tensor(vertices) else np.asarray(vertices)
-    f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+    v, f = host(vertices), host(faces)
     if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
         raise ValueError("%s: vertices must be [Vm,3] and faces [F,3]; got %s and %s" % (who, tuple(v.shape), tuple(f.shape)))
     if f.dtype.kind not in "iu":
@@ -21,6 +21,18 @@ def _mesh_arrays(vertices, faces, who):
     return v, f
 
 
+def device_mesh(vertices, faces, who, dev, check_faces=True):
+    """(vertices float32 [Vm,3], faces int32 [F,3]) on dev.  check_faces: shapes, dtype and the index range on the host
+    (mesh_arrays - a host copy, so it waits for the stream); False: the shapes alone, for a caller that checked this face
+    tensor before and must not wait (SingleObjectDeform.pick)."""
+    if check_faces:
+        mesh_arrays(vertices, faces, who)
+    vd, fd = on_device(vertices, torch.float32, dev), on_device(faces, torch.int32, dev)
+    if vd.dim() != 2 or vd.shape[1] != 3 or fd.dim() != 2 or fd.shape[1] != 3:
+        raise ValueError("%s: vertices must be [Vm,3] and faces [F,3]; got %s and %s" % (who, tuple(vd.shape), tuple(fd.shape)))
+    return vd, fd
+
+
 def closest_faces(points, vertices, faces, want_closest=False):
     """For every row of points [N,3] the closest triangle of the mesh (vertices [Vm,3], faces [F,3] vertex ids):
     (d2 float32 [N], face int64 [N]) and with want_closest also the closest point on that face, float32 [N,3].
@@ -28,29 +40,22 @@ def closest_faces(points, vertices, faces, want_closest=False):
     ties go to the lowest face index, a face whose formula gives NaN (no area) never wins - a float32 brute force gives the same
     bits.  A point for which every face gives NaN gets face -1 and d2 = +inf.  points on a HIP (cuda) device; vertices / faces
     may be host arrays or tensors on any device (the face indices are checked on the host).  No CPU path."""
-    lib = _lib.lib()
     if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("closest_faces: points must be a [N,3] tensor; got %s" % (tuple(getattr(points, "shape", ())),))
-    v, f = _mesh_arrays(vertices, faces, "closest_faces")
+    v, f = mesh_arrays(vertices, faces, "closest_faces")
     if points.shape[0] and (f.shape[0] == 0 or v.shape[0] == 0):
         raise ValueError("closest_faces: the mesh is empty (%d vertices, %d faces)" % (v.shape[0], f.shape[0]))
-    if points.device.type != "cuda":
-        raise _lib.GmeshError("closest_faces needs the points on a HIP (cuda) device; there is no CPU path")
+    need_cuda(points, "closest_faces", "the points")
     dev = points.device
-    p = points.detach().contiguous().float()
-    on_dev = lambda a, dt: (a.detach().to(device=dev, dtype=dt) if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)).contiguous()
-    vd, fd = on_dev(vertices, torch.float32), on_dev(faces, torch.int32)
+    p = f32(points)
+    vd, fd = on_device(vertices, torch.float32, dev), on_device(faces, torch.int32, dev)
     N, Vm, F = p.shape[0], vd.shape[0], fd.shape[0]
     d2 = torch.empty((N,), dtype=torch.float32, device=dev)
     face = torch.empty((N,), dtype=torch.int32, device=dev)
     close = torch.empty((N, 3), dtype=torch.float32, device=dev) if want_closest else None
     if N > 0:
-        with torch.cuda.device(dev):
-            nbytes = lib.gm_closest_face_workspace_bytes(N, F)
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            _lib.check(lib.gm_closest_face(N, p.data_ptr(), Vm, vd.data_ptr(), F, fd.data_ptr(), d2.data_ptr(), face.data_ptr(),
-                                           close.data_ptr() if want_closest else None, ws.data_ptr(), nbytes,
-                                           torch.cuda.current_stream(dev).cuda_stream))
+        ws = workspace(dev, "gm_closest_face_workspace_bytes", N, F)
+        enqueue(dev, "gm_closest_face", N, p, Vm, vd, F, fd, d2, face, close, workspace=ws)
     return (d2, face.long(), close) if want_closest else (d2, face.long())
 
 
@@ -62,11 +67,8 @@ def bind_points(points, vertices, faces, face_id=None):
     Returns dict(face_id int64 [N], tri int32 [N,3] the face's vertex ids, weights float32 [N,3], sqr_distance float32 [N] - the
     squared distance to the closest face; NaN rows when face_id was given).  Host arrays.  A point that no face can claim (every
     face without area) raises ValueError naming the first such row."""
-    v, f = _mesh_arrays(vertices, faces, "bind_points")
-    if torch.is_tensor(points):
-        pts = points.detach().cpu().numpy()
-    else:
-        pts = np.asarray(points)
+    v, f = mesh_arrays(vertices, faces, "bind_points")
+    pts = host(points)
     if pts.ndim != 2 or pts.shape[1] != 3:
         raise ValueError("bind_points: points must be [N,3]; got %s" % (tuple(pts.shape),))
     N = pts.shape[0]
@@ -79,7 +81,7 @@ def bind_points(points, vertices, faces, face_id=None):
         if len(bad):
             raise ValueError("bind_points: point %d has no closest face (every face of the mesh is degenerate for it)" % int(bad[0]))
     else:
-        fid = (face_id.detach().cpu().numpy() if torch.is_tensor(face_id) else np.asarray(face_id)).reshape(-1).astype(np.int64)
+        fid = host(face_id).reshape(-1).astype(np.int64)
         if fid.shape[0] != N:
             raise ValueError("bind_points: face_id must have one entry per point (%d), got %d" % (N, fid.shape[0]))
         if N and (int(fid.min()) < 0 or int(fid.max()) >= f.shape[0]):

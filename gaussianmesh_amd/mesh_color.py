@@ -20,11 +20,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._op import enqueue, need_cuda, workspace
 from .deform import vertex_face_adjacency
-from .mesh_bind import _mesh_arrays
-from .mesh_pick import _camera, _hits, camera_rays
-from .proxy_mesh import _maps, _need_device
-from .rasterizer import _stream
+from .mesh_bind import mesh_arrays
+from .mesh_pick import camera_rays, camera_tuple, first_hits
+from .proxy_mesh import maps_list
 
 SPREAD_MAX = 1024                # spread=True: min(Vm, SPREAD_MAX) steps
 
@@ -49,8 +49,8 @@ def _images(x, who):
 
 def _mesh_on_device(vertices, faces, who):
     """(vertices float32 [Vm,3], faces int32 [F,3]) contiguous on the vertices' device, the face indices checked on the host"""
-    _need_device(vertices, who, "the vertices")
-    _mesh_arrays(vertices, faces, who)
+    need_cuda(vertices, who, "the vertices")
+    mesh_arrays(vertices, faces, who)
     dev = vertices.device
     V = vertices.detach().to(torch.float32).contiguous()
     F = (faces.detach() if torch.is_tensor(faces) else torch.as_tensor(np.ascontiguousarray(faces))).to(device=dev, dtype=torch.int32).contiguous()
@@ -65,9 +65,7 @@ def _adjacency(faces, Vm, dev):
 def _normals(V, F, adjacency):
     off, adj = adjacency
     N = torch.empty_like(V)
-    with torch.cuda.device(V.device):
-        _lib.check(_lib.lib().gm_mesh_vertex_normals(V.shape[0], F.shape[0], V.data_ptr(), F.data_ptr(), off.data_ptr(), adj.data_ptr(), N.data_ptr(),
-                                                     _stream(V.device)))
+    enqueue(V.device, "gm_mesh_vertex_normals", V.shape[0], F.shape[0], V, F, off, adj, N)
     return N
 
 
@@ -79,7 +77,7 @@ def vertex_normals(vertices, faces, adjacency=None):
     if adjacency is None:
         adjacency = _adjacency(F, V.shape[0], V.device)
     for a in adjacency:
-        _need_device(a, "vertex_normals", "the adjacency")
+        need_cuda(a, "vertex_normals", "the adjacency")
     return _normals(V, F, tuple(a.to(torch.int32).contiguous() for a in adjacency))
 
 
@@ -113,17 +111,16 @@ class VertexColors:
         Only enqueues; nothing waits for the device."""
         who = "VertexColors.integrate"
         cameras = list(cameras)
-        images, depth, alpha = _images(images, who), _maps(depth, who, "depth"), _maps(alpha, who, "alpha")
+        images, depth, alpha = _images(images, who), maps_list(depth, who, "depth"), maps_list(alpha, who, "alpha")
         if not (len(cameras) == len(images) == len(depth) == len(alpha)):
             raise ValueError("%s: %d cameras, %d images, %d depth maps, %d alpha maps" % (who, len(cameras), len(images), len(depth), len(alpha)))
         for im, d, a in zip(images, depth, alpha):
-            _need_device(im, who, "the images")
-            _need_device(d, who, "the depth maps")
-            _need_device(a, who, "the alpha maps")
+            need_cuda(im, who, "the images")
+            need_cuda(d, who, "the depth maps")
+            need_cuda(a, who, "the alpha maps")
             if d.shape != a.shape or tuple(im.shape[1:]) != tuple(d.shape):
                 raise ValueError("%s: an image is %s, its depth map %s and its alpha map %s" % (who, tuple(im.shape), tuple(d.shape), tuple(a.shape)))
         tol = self.default_depth_tol if depth_tol is None else float(depth_tol)
-        lib = _lib.lib()
         self._stats = None
         Vm = self.vertices.shape[0]
         k = 0
@@ -134,7 +131,7 @@ class VertexColors:
             H, W = (int(s) for s in depth[k].shape)
             rows, tans = [], []
             for cam in cameras[k:e]:
-                view, _, _, cw, ch, tanx, tany = _camera(cam)
+                view, _, _, cw, ch, tanx, tany = camera_tuple(cam)
                 if (cw, ch) != (W, H):
                     raise ValueError("%s: a %d x %d camera with %d x %d maps" % (who, cw, ch, W, H))
                 rows.append(view.detach().to(self.device, torch.float32).reshape(16))
@@ -143,10 +140,8 @@ class VertexColors:
             tanfov = torch.tensor(tans, dtype=torch.float32).to(self.device, non_blocking=True)
             stack = lambda maps: torch.stack([m.detach().to(self.device, torch.float32) for m in maps]).contiguous()
             ii, dd, aa = stack(images[k:e]), stack(depth[k:e]), stack(alpha[k:e])
-            with torch.cuda.device(self.device):
-                _lib.check(lib.gm_mesh_color_integrate(e - k, H, W, ii.data_ptr(), dd.data_ptr(), aa.data_ptr(), views.data_ptr(), tanfov.data_ptr(), Vm,
-                                                       self.vertices.data_ptr(), self.normals.data_ptr(), float(alpha_min), tol, int(self.two_sided),
-                                                       self.csum.data_ptr(), self.wsum.data_ptr(), _stream(self.device)))
+            enqueue(self.device, "gm_mesh_color_integrate", e - k, H, W, ii, dd, aa, views, tanfov, Vm, self.vertices, self.normals, float(alpha_min),
+                    tol, int(self.two_sided), self.csum, self.wsum)
             self.views += e - k
             k = e
         return self
@@ -168,17 +163,13 @@ class VertexColors:
             n = min(Vm, SPREAD_MAX) if spread is True else int(spread)
             if n < 0:
                 raise ValueError("VertexColors.resolve: spread must not be negative; got %r" % (spread,))
-            lib = _lib.lib()
             off, adj = self.adjacency
             seen8 = seen.to(torch.uint8)
             has = torch.empty((Vm,), dtype=torch.uint8, device=self.device)
             counts = torch.empty((2,), dtype=torch.int32, device=self.device)
-            nbytes = lib.gm_mesh_color_spread_workspace_bytes(Vm)
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
-            with torch.cuda.device(self.device):
-                _lib.check(lib.gm_mesh_color_spread(Vm, self.faces.shape[0], self.faces.data_ptr(), off.data_ptr(), adj.data_ptr(), seen8.data_ptr(), n,
-                                                    (C.c_float * 3)(*fb), colors.data_ptr(), has.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes,
-                                                    _stream(self.device)))
+            ws = workspace(self.device, "gm_mesh_color_spread_workspace_bytes", Vm)
+            enqueue(self.device, "gm_mesh_color_spread", Vm, self.faces.shape[0], self.faces, off, adj, seen8, n, (C.c_float * 3)(*fb), colors, has,
+                    counts, workspace=ws)
         self._stats = [seen.sum(), counts, None]
         return colors
 
@@ -198,7 +189,7 @@ def _color_from_cloud(pc, cameras, vertices, faces, pipe, bg_gaussian, views_per
     """(colors, the VertexColors that made them)"""
     from .bg_model import PlainGaussians
     from .renderer import Camera, bg_render, render
-    _need_device(pc.get_xyz, "color_from_cloud", "the cloud")
+    need_cuda(pc.get_xyz, "color_from_cloud", "the cloud")
     dev = pc.get_xyz.device
     pipe = pipe if pipe is not None else SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False)
     bg_color = torch.zeros(3, device=dev) if bg_color is None else bg_color
@@ -219,6 +210,9 @@ def _color_from_cloud(pc, cameras, vertices, faces, pipe, bg_gaussian, views_per
         return vc.resolve(spread=spread), vc
 
 
+colors_and_state = _color_from_cloud     # (colors, VertexColors): for a caller that also reports vc.stats (the command lines)
+
+
 def color_from_cloud(pc, cameras, vertices, faces, pipe=None, bg_gaussian=None, views_per_call=8, alpha_min=0.5, depth_tol=None, two_sided=False,
                      spread=True, bg_color=None):
     """The vertex colours of a mesh (vertices [Vm,3] on the device, faces [F,3]) from a trained cloud: float32 [Vm,3] on the device.
@@ -232,12 +226,12 @@ def render_preview(camera, vertices, faces, colors, bg_color=None):
     """[3,H,W] float32 on the device: the coloured mesh as the camera sees it, one ray per pixel through gm_ray_mesh (mesh_pick): a pixel
     whose ray hits face (a, b, c) at (u, v) shows (1 - u - v) c_a + u c_b + v c_c, a pixel whose ray misses shows bg_color (black unless
     given).  No shading, no lighting: a preview of where colours, picks and handles lie.  Torch glue; no kernel of its own."""
-    _need_device(vertices, "render_preview", "the vertices")
+    need_cuda(vertices, "render_preview", "the vertices")
     dev = vertices.device
     if isinstance(camera, dict):
         from .renderer import Camera
         camera = Camera(camera, dev)
-    _, _, _, W, H, _, _ = _camera(camera)
+    _, _, _, W, H, _, _ = camera_tuple(camera)
     V, F = _mesh_on_device(vertices, faces, "render_preview")
     col = colors.detach().to(device=dev, dtype=torch.float32) if torch.is_tensor(colors) else torch.as_tensor(np.asarray(colors), dtype=torch.float32, device=dev)
     if col.shape != V.shape:
@@ -245,7 +239,7 @@ def render_preview(camera, vertices, faces, colors, bg_color=None):
     bg = torch.zeros(3, device=dev) if bg_color is None else torch.as_tensor(bg_color, dtype=torch.float32, device=dev).reshape(3)
     y, x = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32), torch.arange(W, device=dev, dtype=torch.float32), indexing="ij")
     origins, dirs = camera_rays(camera, torch.stack([x.reshape(-1), y.reshape(-1)], dim=1))
-    _, face, uv = _hits(origins.to(dev).contiguous(), dirs.to(dev).contiguous(), V, F, 0.0, math.inf)
+    _, face, uv = first_hits(origins.to(dev).contiguous(), dirs.to(dev).contiguous(), V, F, 0.0, math.inf)
     tri = F[face.clamp(min=0)].long()
     u, v = uv[:, 0:1], uv[:, 1:2]
     shade = ((1.0 - u - v) * col[tri[:, 0]] + u * col[tri[:, 1]]) + v * col[tri[:, 2]]
@@ -268,10 +262,10 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("mesh_color needs a HIP (cuda) device; there is no CPU path")
     from . import io as gio
-    from .proxy_mesh import _load_model
+    from .proxy_mesh import load_model
     dev = torch.device("cuda")
     t0 = time.perf_counter()
-    pc = _load_model(a.gaussian, a.mesh_gaussian, dev)
+    pc = load_model(a.gaussian, a.mesh_gaussian, dev)
     cams = gio.load_cameras_json(a.cameras)
     if not cams:
         raise SystemExit("mesh_color: %s holds no camera" % a.cameras)

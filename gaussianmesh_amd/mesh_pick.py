@@ -7,13 +7,13 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
-from .mesh_bind import _mesh_arrays
+from ._op import enqueue, f32, need_cuda, workspace
+from .mesh_bind import device_mesh, mesh_arrays
 
 OCCLUSION_TOLERANCE = 2.0 ** -10     # visible_vertices: a hit at t >= 1 - 2^-10 is the vertex's own neighbourhood (part of the definition)
 
 
-def _camera(camera):
+def camera_tuple(camera):
     """(view [4,4] stored transposed, proj [4,4], centre [3], W, H, tan(FoVx/2), tan(FoVy/2)) of a camera with the reference's attribute
     names (renderer.Camera) or of a scenes.camera_from_RT dict; the tensors where the camera holds them."""
     if isinstance(camera, dict):
@@ -37,7 +37,7 @@ def camera_rays(camera, pixels):
     is a pixel centre: the inverse of ndc2pix, csrc/gm_pre_body.h).  View-space direction (((2x+1)/W - 1) tan(FoVx/2),
     ((2y+1)/H - 1) tan(FoVy/2), 1), world direction d_view @ world_view_transform[:3,:3].T (the matrix is stored transposed), origin
     camera_center.  Directions are NOT normalised: a hit's t is its view depth.  Torch on the camera's device (CPU tensors work)."""
-    view, _, centre, W, H, tanx, tany = _camera(camera)
+    view, _, centre, W, H, tanx, tany = camera_tuple(camera)
     pix = _rows(pixels, 2, view.device, "camera_rays", "pixels")
     dv = torch.stack([((2.0 * pix[:, 0] + 1.0) / W - 1.0) * tanx, ((2.0 * pix[:, 1] + 1.0) / H - 1.0) * tany, torch.ones_like(pix[:, 0])], dim=1)
     dirs = dv @ view[:3, :3].T
@@ -45,7 +45,7 @@ def camera_rays(camera, pixels):
 
 
 def _view_space(camera, points):
-    view, _, _, W, H, tanx, tany = _camera(camera)
+    view, _, _, W, H, tanx, tany = camera_tuple(camera)
     return points @ view[:3, :3] + view[3, :3], W, H, tanx, tany
 
 
@@ -53,7 +53,7 @@ def screen_offset(camera, points, pixel_offsets):
     """World points [P,3] moved parallel to the image plane by pixel_offsets [P,2], each at its own view depth z: the move in view x
     and y is (dx 2 tan(FoVx/2) / W z, dy 2 tan(FoVy/2) / H z), rotated back to world space and added (a zero offset returns the point
     itself).  Torch on the points' device; nothing waits."""
-    view, _, _, W, H, tanx, tany = _camera(camera)
+    view, _, _, W, H, tanx, tany = camera_tuple(camera)
     pts = _rows(points, 3, points.device if torch.is_tensor(points) else view.device, "screen_offset", "points")
     view = view.to(pts.device)
     off = _rows(pixel_offsets, 2, pts.device, "screen_offset", "pixel_offsets")
@@ -64,22 +64,8 @@ def screen_offset(camera, points, pixel_offsets):
     return pts + mv @ view[:3, :3].T
 
 
-def _device_mesh(vertices, faces, who, dev, check_faces=True):
-    """(vertices float32 [Vm,3], faces int32 [F,3]) on dev.  check_faces: shapes, dtype and the index range on the host
-    (mesh_bind._mesh_arrays - a host copy, so it waits for the stream); False: the shapes alone, for a caller that checked this face
-    tensor before and must not wait (SingleObjectDeform.pick)."""
-    if check_faces:
-        _mesh_arrays(vertices, faces, who)
-    on_dev = lambda a, dt: (a.detach().to(device=dev, dtype=dt) if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)).contiguous()
-    vd, fd = on_dev(vertices, torch.float32), on_dev(faces, torch.int32)
-    if vd.dim() != 2 or vd.shape[1] != 3 or fd.dim() != 2 or fd.shape[1] != 3:
-        raise ValueError("%s: vertices must be [Vm,3] and faces [F,3]; got %s and %s" % (who, tuple(vd.shape), tuple(fd.shape)))
-    return vd, fd
-
-
-def _hits(origins, dirs, vd, fd, t_min, t_max, want_uv=True):
+def first_hits(origins, dirs, vd, fd, t_min, t_max, want_uv=True):
     """gm_ray_mesh on device tensors (contiguous float32 / int32, checked by the callers)"""
-    lib = _lib.lib()
     dev = origins.device
     R, Vm, F = origins.shape[0], vd.shape[0], fd.shape[0]
     if R and (F == 0 or Vm == 0):
@@ -88,12 +74,8 @@ def _hits(origins, dirs, vd, fd, t_min, t_max, want_uv=True):
     face = torch.empty((R,), dtype=torch.int32, device=dev)
     uv = torch.empty((R, 2), dtype=torch.float32, device=dev) if want_uv else None
     if R > 0:
-        with torch.cuda.device(dev):
-            nbytes = lib.gm_ray_mesh_workspace_bytes(R, F)
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            _lib.check(lib.gm_ray_mesh(R, origins.data_ptr(), dirs.data_ptr(), Vm, vd.data_ptr(), F, fd.data_ptr(), float(t_min), float(t_max),
-                                       t.data_ptr(), face.data_ptr(), uv.data_ptr() if want_uv else None, ws.data_ptr(), nbytes,
-                                       torch.cuda.current_stream(dev).cuda_stream))
+        ws = workspace(dev, "gm_ray_mesh_workspace_bytes", R, F)
+        enqueue(dev, "gm_ray_mesh", R, origins, dirs, Vm, vd, F, fd, float(t_min), float(t_max), t, face, uv, workspace=ws)
     return t, face.long(), uv
 
 
@@ -112,22 +94,20 @@ def ray_mesh_hits(origins, dirs, vertices, faces, t_min=0.0, t_max=math.inf, che
     if not (t_min >= 0.0) or t_max != t_max:
         raise ValueError("ray_mesh_hits: t_min must be >= 0 and neither bound NaN; got %r, %r" % (t_min, t_max))
     if check_faces:
-        v, f = _mesh_arrays(vertices, faces, "ray_mesh_hits")
+        v, f = mesh_arrays(vertices, faces, "ray_mesh_hits")
         if origins.shape[0] and (f.shape[0] == 0 or v.shape[0] == 0):
             raise ValueError("ray_mesh_hits: the mesh is empty (%d vertices, %d faces)" % (v.shape[0], f.shape[0]))
-    if origins.device.type != "cuda":
-        raise _lib.GmeshError("ray_mesh_hits needs the rays on a HIP (cuda) device; there is no CPU path")
+    need_cuda(origins, "ray_mesh_hits", "the rays")
     dev = origins.device
-    vd, fd = _device_mesh(vertices, faces, "ray_mesh_hits", dev, check_faces=False)
-    o = origins.detach().contiguous().float()
+    vd, fd = device_mesh(vertices, faces, "ray_mesh_hits", dev, check_faces=False)
+    o = f32(origins)
     d = dirs.detach().to(dev).contiguous().float()
-    return _hits(o, d, vd, fd, t_min, t_max)
+    return first_hits(o, d, vd, fd, t_min, t_max)
 
 
 def _camera_device(camera, who):
-    dev = _camera(camera)[0].device
-    if dev.type != "cuda":
-        raise _lib.GmeshError("%s needs the camera on a HIP (cuda) device; there is no CPU path" % who)
+    dev = camera_tuple(camera)[0].device
+    need_cuda(dev, who, "the camera")
     return dev
 
 
@@ -137,8 +117,8 @@ def pick(camera, pixels, vertices, faces, check_faces=True):
     miss), depth float32 [P] = t, the view depth (+inf on a miss)).  Everything stays on the device; nothing waits for it."""
     dev = _camera_device(camera, "pick")
     origins, dirs = camera_rays(camera, pixels)
-    vd, fd = _device_mesh(vertices, faces, "pick", dev, check_faces)
-    t, face, uv = _hits(origins, dirs, vd, fd, 0.0, math.inf)
+    vd, fd = device_mesh(vertices, faces, "pick", dev, check_faces)
+    t, face, uv = first_hits(origins, dirs, vd, fd, 0.0, math.inf)
     hit = face >= 0
     tri = fd[face.clamp(min=0)].long()
     a, b, c = vd[tri[:, 0]], vd[tri[:, 1]], vd[tri[:, 2]]
@@ -156,10 +136,10 @@ def visible_vertices(camera, vertices, faces, rect=None, check_faces=True):
     t >= 1 - 2^-10 (the tolerance is part of the definition).  rect = (x0, y0, x1, y1) in pixels: the vertex must also have a view depth
     > 0 and its projected pixel inside the rectangle, edges included."""
     dev = _camera_device(camera, "visible_vertices")
-    vd, fd = _device_mesh(vertices, faces, "visible_vertices", dev, check_faces)
-    centre = _camera(camera)[2].reshape(1, 3)
+    vd, fd = device_mesh(vertices, faces, "visible_vertices", dev, check_faces)
+    centre = camera_tuple(camera)[2].reshape(1, 3)
     origins = centre.expand(vd.shape[0], 3).contiguous()
-    t, face, _ = _hits(origins, (vd - centre).contiguous(), vd, fd, 0.0, math.inf, want_uv=False)
+    t, face, _ = first_hits(origins, (vd - centre).contiguous(), vd, fd, 0.0, math.inf, want_uv=False)
     own = (fd[face.clamp(min=0)].long() == torch.arange(vd.shape[0], device=dev)[:, None]).any(dim=1)
     visible = (face < 0) | own | (t >= 1.0 - OCCLUSION_TOLERANCE)
     if rect is not None:

@@ -10,10 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+from ._op import enqueue, host
 
 
 def _norm3(d):
@@ -39,8 +36,8 @@ def surface_graph(vertices, faces, unfold=True):
       cell; 1.08 with them).
       Duplicates, a virtual edge that is also a real one included, keep the smallest length.
     ValueError for bad shapes and for face ids out of range."""
-    v = np.asarray(_host(vertices))
-    f = np.asarray(_host(faces))
+    v = np.asarray(host(vertices))
+    f = np.asarray(host(faces))
     if v.ndim != 2 or v.shape[1] != 3:
         raise ValueError("surface_graph: vertices must be [Vm,3]; got %s" % (tuple(v.shape),))
     if f.ndim != 2 or f.shape[1] != 3:
@@ -102,7 +99,7 @@ def _radius(name, r):
     return r
 
 
-def _check_radii(who, grab_radius, free_radius):
+def check_radii(who, grab_radius, free_radius):
     grab = _radius("%s: grab_radius" % who, grab_radius)
     free = None if free_radius is None else _radius("%s: free_radius" % who, free_radius)
     if free is not None and free < grab:
@@ -157,7 +154,7 @@ class SurfaceGraph:
             raise ValueError("SurfaceGraph.distances: sweeps_per_check and max_sweeps must be >= 1; got %r, %r" % (sweeps_per_check, max_sweeps))
         sets = []
         for b, s in enumerate(source_sets):
-            a = np.asarray(_host(s)).reshape(-1)
+            a = np.asarray(host(s)).reshape(-1)
             if a.size and a.dtype.kind not in "iu":
                 raise ValueError("SurfaceGraph.distances: source set %d must hold integer vertex ids, got %s" % (b, a.dtype))
             a = a.astype(np.int64)
@@ -175,21 +172,18 @@ class SurfaceGraph:
         src = np.concatenate(sets + [np.zeros(1, np.int64)])            # (one spare entry: never an empty array)
         d_off = torch.as_tensor(offsets.astype(np.int32), device=dev)
         d_src = torch.as_tensor(src.astype(np.int32), device=dev)
-        lib = _lib.lib()
-        nbytes = lib.gm_mesh_geodesic_workspace_bytes(Vm, B, chunk)
+        nbytes = _lib.lib().gm_mesh_geodesic_workspace_bytes(Vm, B, chunk)
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
         used, resume = 0, 0
-        with torch.cuda.device(dev):
-            while used < budget:
-                n = min(chunk, budget - used)
-                _lib.check(lib.gm_mesh_geodesic(Vm, self._off.data_ptr(), self._cols.data_ptr(), self._lens.data_ptr(), B, d_off.data_ptr(),
-                                                d_src.data_ptr(), cutoff, n, resume, dist.data_ptr(), self._unsettled.data_ptr(),
-                                                self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
-                used, resume = used + n, 1
-                if int(self._unsettled.item()) == 0:                   # the 4-byte read-back
-                    self.sweeps_enqueued = used
-                    return dist
+        while used < budget:
+            n = min(chunk, budget - used)
+            enqueue(dev, "gm_mesh_geodesic", Vm, self._off, self._cols, self._lens, B, d_off, d_src, cutoff, n, resume, dist, self._unsettled,
+                    workspace=self._ws)
+            used, resume = used + n, 1
+            if int(self._unsettled.item()) == 0:                       # the 4-byte read-back
+                self.sweeps_enqueued = used
+                return dist
         raise _lib.GmeshError("SurfaceGraph.distances: %d sweeps did not settle the distances (max_sweeps; Vm = %d always suffices)" % (budget, Vm))
 
 
@@ -202,12 +196,12 @@ def region_handles(d_handles, d_anchors, grab_radius, free_radius=None):
       and a component without a pick no longer trips ArapSolver's singular-system refusal.
     ValueError for two handle regions that overlap (naming both picks and a shared vertex), a handle region that meets an anchor
     region, free_radius < grab_radius, a negative or NaN radius."""
-    grab, free = _check_radii("region_handles", grab_radius, free_radius)
-    dh = np.asarray(_host(d_handles), np.float32)
+    grab, free = check_radii("region_handles", grab_radius, free_radius)
+    dh = np.asarray(host(d_handles), np.float32)
     if dh.ndim != 2 or dh.shape[0] == 0:
         raise ValueError("region_handles: d_handles must be [H,Vm] with H >= 1; got %s" % (tuple(dh.shape),))
     H, Vm = dh.shape
-    da = np.zeros((0, Vm), np.float32) if d_anchors is None else np.asarray(_host(d_anchors), np.float32).reshape(-1, Vm)
+    da = np.zeros((0, Vm), np.float32) if d_anchors is None else np.asarray(host(d_anchors), np.float32).reshape(-1, Vm)
     owner_of = np.full(Vm, -1, np.int64)
     ids, owner = [], []
     for i in range(H):

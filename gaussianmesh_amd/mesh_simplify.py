@@ -21,11 +21,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import _lib
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
+from ._op import enqueue, need_cuda, workspace
 
 
 def _number(name, x):
@@ -80,8 +76,8 @@ def _bookkeeping(F, Vm):
 
 def quadrics(vertices, faces):
     """gm_mesh_quadrics: float32 [Vm,10], the error quadric of every vertex (upper triangle, row order)"""
-    _need_device(vertices, "quadrics", "vertices")
-    _need_device(faces, "quadrics", "faces")
+    need_cuda(vertices, "quadrics", "vertices")
+    need_cuda(faces, "quadrics", "faces")
     V = vertices.detach().to(torch.float32).contiguous()
     F = faces.detach().to(torch.int64).reshape(-1, 3)
     _, _, off, adj = _bookkeeping(F, V.shape[0])
@@ -90,9 +86,7 @@ def quadrics(vertices, faces):
 
 def _quadrics(V, F32, off, adj):
     Q = torch.empty((V.shape[0], 10), dtype=torch.float32, device=V.device)
-    with torch.cuda.device(V.device):
-        _lib.check(_lib.lib().gm_mesh_quadrics(V.shape[0], V.data_ptr(), F32.shape[0], F32.data_ptr(), off.data_ptr(), adj.data_ptr(), Q.data_ptr(),
-                                               _stream(V.device)))
+    enqueue(V.device, "gm_mesh_quadrics", V.shape[0], V, F32.shape[0], F32, off, adj, Q)
     return Q
 
 
@@ -101,24 +95,15 @@ def collapse_round(V, Q, F32, off, adj, edges, uses, min_cos, max_error):
     all on the device; nothing waits"""
     dev = V.device
     E = edges.shape[0]
-    lib = _lib.lib()
     selected = torch.empty((E,), dtype=torch.uint8, device=dev)
     frm = torch.empty((E,), dtype=torch.int32, device=dev)
     to = torch.empty((E,), dtype=torch.int32, device=dev)
     key = torch.empty((E,), dtype=torch.int64, device=dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev)
-    nbytes = lib.gm_mesh_collapse_round_workspace_bytes(V.shape[0])
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.gm_mesh_collapse_round(V.shape[0], V.data_ptr(), Q.data_ptr(), F32.shape[0], F32.data_ptr(), off.data_ptr(), adj.data_ptr(), E,
-                                              edges.data_ptr(), uses.data_ptr(), float(min_cos), float(max_error), selected.data_ptr(), frm.data_ptr(),
-                                              to.data_ptr(), key.data_ptr(), count.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)))
+    ws = workspace(dev, "gm_mesh_collapse_round_workspace_bytes", V.shape[0])
+    enqueue(dev, "gm_mesh_collapse_round", V.shape[0], V, Q, F32.shape[0], F32, off, adj, E, edges, uses, float(min_cos), float(max_error), selected,
+            frm, to, key, count, workspace=ws)
     return selected, frm, to, key, count
-
-
-def _need_device(t, who, what):
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise _lib.GmeshError("%s needs %s on a HIP (cuda) device; there is no CPU path" % (who, what))
 
 
 def simplify(vertices, faces, target_faces=None, ratio=None, max_error=None, min_cos=0.2, max_rounds=1024):
@@ -144,8 +129,8 @@ def simplify(vertices, faces, target_faces=None, ratio=None, max_error=None, min
         raise ValueError("simplify: min_cos must be in [0, 1]; got %r" % (min_cos,))
     max_rounds = _count("max_rounds", max_rounds)
     resolve_target(0, target_faces, ratio, max_error)                  # the parameters alone, before anything touches a tensor
-    _need_device(vertices, "simplify", "vertices")
-    _need_device(faces, "simplify", "faces")
+    need_cuda(vertices, "simplify", "vertices")
+    need_cuda(faces, "simplify", "faces")
     if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError("simplify: vertices must be [V,3] and faces [F,3]; got %s, %s" % (tuple(vertices.shape), tuple(faces.shape)))
     dev = vertices.device

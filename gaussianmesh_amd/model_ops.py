@@ -13,21 +13,15 @@ import ctypes as C
 
 import torch
 
-from . import _lib
-
-
-def _c(t):
-    return t.detach().contiguous().float()
+from ._op import enqueue, f32, need_cuda
 
 
 class _MeshActivate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, bc, distance, scaling, rotation, opacity, v1, v2, v3, normal, r, alpha, mr_weight, joint=None):
-        lib = _lib.lib()
         dev = bc.device
-        if dev.type != "cuda":
-            raise _lib.GmeshError("mesh_activate needs tensors on a HIP (cuda) device; there is no CPU path")
-        ins = [_c(t) for t in (bc, distance, scaling, rotation, opacity, v1, v2, v3, normal, r)]
+        need_cuda(dev, "mesh_activate", "tensors")
+        ins = [f32(t) for t in (bc, distance, scaling, rotation, opacity, v1, v2, v3, normal, r)]
         N = ins[0].shape[0]
         f = dict(dtype=torch.float32, device=dev)
         if joint is None:
@@ -44,10 +38,7 @@ class _MeshActivate(torch.autograd.Function):
                 torch.autograd.graph.increment_version(t)
         want_mr = mr_weight is not None
         part = torch.empty(((N + 255) // 256,), **f) if want_mr else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.gm_mesh_activate_fwd(N, float(alpha), *[t.data_ptr() for t in ins], xyz.data_ptr(), scales.data_ptr(),
-                                                rots.data_ptr(), opac.data_ptr(), float(mr_weight or 0.0),
-                                                None if part is None else part.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        enqueue(dev, "gm_mesh_activate_fwd", N, float(alpha), *ins, xyz, scales, rots, opac, float(mr_weight or 0.0), part)
         ctx.save_for_backward(*ins)
         ctx.alpha, ctx.mr_weight = float(alpha), (float(mr_weight) if want_mr else None)
         mr = part.sum() if want_mr else torch.zeros((), **f)
@@ -55,20 +46,15 @@ class _MeshActivate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_xyz, d_scales, d_rots, d_opac, d_mr):
-        lib = _lib.lib()
         ins = ctx.saved_tensors
         dev = ins[0].device
         N = ins[0].shape[0]
         f = dict(dtype=torch.float32, device=dev)
         d_bc = torch.empty((N, 3), **f); d_dist = torch.empty_like(ins[1]); d_scaling = torch.empty((N, 3), **f)
         d_rot = torch.empty((N, 4), **f); d_op = torch.empty_like(ins[4])
-        g = [None if t is None else _c(t) for t in (d_xyz, d_scales, d_rots, d_opac)]
-        gm = _c(d_mr).reshape(1) if (ctx.mr_weight is not None and d_mr is not None) else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.gm_mesh_activate_bwd(N, ctx.alpha, *[t.data_ptr() for t in ins], *[None if t is None else t.data_ptr() for t in g],
-                                                d_bc.data_ptr(), d_dist.data_ptr(), d_scaling.data_ptr(), d_rot.data_ptr(), d_op.data_ptr(),
-                                                float(ctx.mr_weight or 0.0), None if gm is None else gm.data_ptr(),
-                                                torch.cuda.current_stream(dev).cuda_stream))
+        g = [None if t is None else f32(t) for t in (d_xyz, d_scales, d_rots, d_opac)]
+        gm = f32(d_mr).reshape(1) if (ctx.mr_weight is not None and d_mr is not None) else None
+        enqueue(dev, "gm_mesh_activate_bwd", N, ctx.alpha, *ins, *g, d_bc, d_dist, d_scaling, d_rot, d_op, float(ctx.mr_weight or 0.0), gm)
         return d_bc, d_dist, d_scaling, d_rot, d_op, None, None, None, None, None, None, None, None
 
 
@@ -84,11 +70,9 @@ def mesh_activate(bc, distance, scaling, rotation, opacity, v1, v2, v3, normal, 
 class _PlainActivate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, scaling, rotation, opacity, joint=None):
-        lib = _lib.lib()
         dev = xyz.device
-        if dev.type != "cuda":
-            raise _lib.GmeshError("plain_activate needs tensors on a HIP (cuda) device; there is no CPU path")
-        ins = [_c(t) for t in (xyz, scaling, rotation, opacity)]
+        need_cuda(dev, "plain_activate", "tensors")
+        ins = [f32(t) for t in (xyz, scaling, rotation, opacity)]
         N = ins[0].shape[0]
         f = dict(dtype=torch.float32, device=dev)
         if joint is None:
@@ -100,9 +84,7 @@ class _PlainActivate(torch.autograd.Function):
             for t in outs:
                 torch.autograd.graph.increment_version(t)
         cap = outs[0].shape[0]
-        with torch.cuda.device(dev):
-            _lib.check(lib.gm_plain_activate_fwd(N, *[t.data_ptr() for t in ins], *[t.data_ptr() for t in outs], 0, cap,
-                                                 torch.cuda.current_stream(dev).cuda_stream))
+        enqueue(dev, "gm_plain_activate_fwd", N, *ins, *outs, 0, cap)
         ctx.save_for_backward(ins[1], ins[2], ins[3])
         ctx.N, ctx.cap = N, cap
         ctx.shapes = [tuple(t.shape) for t in (xyz, scaling, rotation, opacity)]
@@ -110,17 +92,13 @@ class _PlainActivate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_xyz, d_scales, d_rots, d_opac):
-        lib = _lib.lib()
         scaling, rotation, opacity = ctx.saved_tensors
         dev = scaling.device
         N = ctx.N
         f = dict(dtype=torch.float32, device=dev)
         outs = (torch.empty((N, 3), **f), torch.empty((N, 3), **f), torch.empty((N, 4), **f), torch.empty((N,), **f))
-        g = [None if t is None else _c(t) for t in (d_xyz, d_scales, d_rots, d_opac)]
-        with torch.cuda.device(dev):
-            _lib.check(lib.gm_plain_activate_bwd(N, scaling.data_ptr(), rotation.data_ptr(), opacity.data_ptr(),
-                                                 *[None if t is None else t.data_ptr() for t in g], 0, ctx.cap, *[t.data_ptr() for t in outs],
-                                                 torch.cuda.current_stream(dev).cuda_stream))
+        g = [None if t is None else f32(t) for t in (d_xyz, d_scales, d_rots, d_opac)]
+        enqueue(dev, "gm_plain_activate_bwd", N, scaling, rotation, opacity, *g, 0, ctx.cap, *outs)
         return tuple(o.reshape(s) for o, s in zip(outs, ctx.shapes)) + (None,)
 
 
@@ -235,7 +213,6 @@ class FusedAdam:
                 p.grad.zero_()
 
     def step(self):
-        lib = _lib.lib()
         live = [g for g in self.param_groups if g["params"][0].grad is not None and g["params"][0].numel() > 0]
         if not live:
             return
@@ -256,15 +233,13 @@ class FusedAdam:
         # "active" (optional, with "period"): only the first `active` elements of every period have ever had a gradient - the SH
         # coefficients of the degrees the model has switched on so far (Trainer keeps it at 3 (D+1)^2); the rest is left alone
         ACT = arr(C.c_uint32, [int(g.get("active", 0)) for g in live])
-        with torch.cuda.device(dev), torch.no_grad():
-            _lib.check(lib.gm_adam_step_active(n, P, G, M, V, S, LR, LR2, PER, SPL, ACT, float(self.betas[0]), float(self.betas[1]),
-                                               float(self.eps), int(self.n_step), torch.cuda.current_stream(dev).cuda_stream))
+        enqueue(dev, "gm_adam_step_active", n, P, G, M, V, S, LR, LR2, PER, SPL, ACT, float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                int(self.n_step))
 
 
 def densify_stats(radii, viewspace_grad, max_radii2D, grad_accum, denom):
     """gm_densify_stats: the per-iteration densification bookkeeping of train_mesh_gaussian.py:119-126 in one kernel, in
     place on max_radii2D [N], grad_accum [N(,1)], denom [N(,1)] (float32); radii int32 [N], viewspace_grad [N,3]."""
-    lib = _lib.lib()
     dev = radii.device
     N = radii.shape[0]
     if N == 0:
@@ -272,7 +247,5 @@ def densify_stats(radii, viewspace_grad, max_radii2D, grad_accum, denom):
     for t in (max_radii2D, grad_accum, denom):
         if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != N:
             raise ValueError("densify_stats: accumulators must be contiguous float32 of N elements")
-    g = viewspace_grad.detach().contiguous().float()
-    with torch.cuda.device(dev), torch.no_grad():
-        _lib.check(lib.gm_densify_stats(N, radii.contiguous().data_ptr(), g.data_ptr(), max_radii2D.data_ptr(), grad_accum.data_ptr(),
-                                        denom.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    g = f32(viewspace_grad)
+    enqueue(dev, "gm_densify_stats", N, radii.contiguous(), g, max_radii2D, grad_accum, denom)

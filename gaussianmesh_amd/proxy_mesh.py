@@ -19,16 +19,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .arap import _components
-from .mesh_pick import _camera
+from ._op import enqueue, need_cuda, on_device, workspace
+from .arap import components
+from .mesh_pick import camera_tuple
 
 
-def _need_device(t, who, what):
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise _lib.GmeshError("%s needs %s on a HIP (cuda) device; there is no CPU path" % (who, what))
-
-
-def _maps(x, who, what):
+def maps_list(x, who, what):
     """a list of [H,W] maps from a list of [H,W] / [1,H,W] tensors or one stacked [K,H,W] / [K,1,H,W] tensor"""
     if torch.is_tensor(x):
         if x.dim() == 4 and x.shape[1] == 1:
@@ -58,7 +54,7 @@ def largest_component(vertices, faces):
         return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), 0
     rows = np.concatenate([f[:, 0], f[:, 1], f[:, 2], f[:, 1], f[:, 2], f[:, 0]])
     cols = np.concatenate([f[:, 1], f[:, 2], f[:, 0], f[:, 0], f[:, 1], f[:, 2]])
-    label = _components(len(v), rows, cols)[f[:, 0]]                   # the smallest vertex id of the face's component
+    label = components(len(v), rows, cols)[f[:, 0]]                   # the smallest vertex id of the face's component
     names, counts = np.unique(label, return_counts=True)
     f = f[label == names[np.argmax(counts)]]                          # argmax: the first of the largest, names ascend
     used = np.unique(f)
@@ -114,15 +110,14 @@ class TsdfVolume:
         resolution go into one call each (in the order given: the volume's bits depend on the order of the views, not on the grouping).
         alpha < alpha_min: free space with carve, ignored without.  Only enqueues; nothing waits for the device."""
         cameras = list(cameras)
-        depth, alpha = _maps(depth, "TsdfVolume.integrate", "depth"), _maps(alpha, "TsdfVolume.integrate", "alpha")
+        depth, alpha = maps_list(depth, "TsdfVolume.integrate", "depth"), maps_list(alpha, "TsdfVolume.integrate", "alpha")
         if not (len(cameras) == len(depth) == len(alpha)):
             raise ValueError("TsdfVolume.integrate: %d cameras, %d depth maps, %d alpha maps" % (len(cameras), len(depth), len(alpha)))
         for d, a in zip(depth, alpha):
-            _need_device(d, "TsdfVolume.integrate", "the depth maps")
-            _need_device(a, "TsdfVolume.integrate", "the alpha maps")
+            need_cuda(d, "TsdfVolume.integrate", "the depth maps")
+            need_cuda(a, "TsdfVolume.integrate", "the alpha maps")
             if d.shape != a.shape:
                 raise ValueError("TsdfVolume.integrate: a depth map is %s and its alpha map %s" % (tuple(d.shape), tuple(a.shape)))
-        lib = _lib.lib()
         self.filled_tsdf = self.filled_weight = self._fill = None      # a fill is of the volume as it was
         k = 0
         while k < len(cameras):                                        # runs of one resolution, in view order
@@ -132,7 +127,7 @@ class TsdfVolume:
             H, W = (int(s) for s in depth[k].shape)
             rows, tans = [], []
             for cam in cameras[k:e]:
-                view, _, _, cw, ch, tanx, tany = _camera(cam)
+                view, _, _, cw, ch, tanx, tany = camera_tuple(cam)
                 if (cw, ch) != (W, H):
                     raise ValueError("TsdfVolume.integrate: a %d x %d camera with %d x %d maps" % (cw, ch, W, H))
                 rows.append(view.detach().to(self.device, torch.float32).reshape(16))
@@ -141,10 +136,8 @@ class TsdfVolume:
             tanfov = torch.tensor(tans, dtype=torch.float32).to(self.device, non_blocking=True)
             dd = torch.stack([m.detach().to(self.device, torch.float32) for m in depth[k:e]]).contiguous()
             aa = torch.stack([m.detach().to(self.device, torch.float32) for m in alpha[k:e]]).contiguous()
-            with torch.cuda.device(self.device):
-                _lib.check(lib.gm_tsdf_integrate(e - k, H, W, dd.data_ptr(), aa.data_ptr(), views.data_ptr(), tanfov.data_ptr(), self.nx, self.ny,
-                                                 self.nz, self._origin_c, self.voxel, self.trunc, float(alpha_min), int(bool(carve)),
-                                                 self.tsdf.data_ptr(), self.weight.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+            enqueue(self.device, "gm_tsdf_integrate", e - k, H, W, dd, aa, views, tanfov, self.nx, self.ny, self.nz, self._origin_c, self.voxel,
+                    self.trunc, float(alpha_min), int(bool(carve)), self.tsdf, self.weight)
             self.views += e - k
             k = e
         return self
@@ -162,20 +155,15 @@ class TsdfVolume:
         filled_voxels, unreached_voxels) reads the counts when it is asked for.  Returns self."""
         if boundary not in ("none", "free"):
             raise ValueError("TsdfVolume.fill_holes: boundary must be 'none' or 'free'; got %r" % (boundary,))
-        _need_device(getattr(self, "tsdf", None), "TsdfVolume.fill_holes", "the volume")
+        need_cuda(getattr(self, "tsdf", None), "TsdfVolume.fill_holes", "the volume")
         n = max(self.nx, self.ny, self.nz) if iterations is None else int(iterations)
         if n < 0:
             raise ValueError("TsdfVolume.fill_holes: iterations must not be negative; got %r" % (iterations,))
-        lib = _lib.lib()
         self.filled_tsdf, self.filled_weight = torch.empty_like(self.tsdf), torch.empty_like(self.weight)
         counts = torch.empty((2,), dtype=torch.int32, device=self.device)
-        nbytes = lib.gm_tsdf_fill_workspace_bytes(self.nx, self.ny, self.nz)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(lib.gm_tsdf_fill(self.nx, self.ny, self.nz, self.tsdf.data_ptr(), self.weight.data_ptr(), float(min_weight), n,
-                                        int(boundary == "free"), float(min_weight if fill_weight is None else fill_weight),
-                                        self.filled_tsdf.data_ptr(), self.filled_weight.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes,
-                                        torch.cuda.current_stream(self.device).cuda_stream))
+        ws = workspace(self.device, "gm_tsdf_fill_workspace_bytes", self.nx, self.ny, self.nz)
+        enqueue(self.device, "gm_tsdf_fill", self.nx, self.ny, self.nz, self.tsdf, self.weight, float(min_weight), n, int(boundary == "free"),
+                float(min_weight if fill_weight is None else fill_weight), self.filled_tsdf, self.filled_weight, counts, workspace=ws)
         self._fill = [n, counts, None]
         return self
 
@@ -193,17 +181,13 @@ class TsdfVolume:
         """gm_surface_nets at the given capacities on (tsdf, weight) = volume, by default the fused pair: (vertex buffer, face buffer,
         device counts); nothing waits"""
         tsdf, weight = (self.tsdf, self.weight) if volume is None else volume
-        lib = _lib.lib()
         f = dict(device=self.device)
         V = torch.empty((max_vertices, 3), dtype=torch.float32, **f)
         F = torch.empty((max_faces, 3), dtype=torch.int32, **f)
         counts = torch.empty((2,), dtype=torch.int32, **f)
-        nbytes = lib.gm_surface_nets_workspace_bytes(self.nx, self.ny, self.nz)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, **f)
-        with torch.cuda.device(self.device):
-            _lib.check(lib.gm_surface_nets(self.nx, self.ny, self.nz, self._origin_c, self.voxel, tsdf.data_ptr(), weight.data_ptr(),
-                                           float(min_weight), max_vertices, V.data_ptr(), max_faces, F.data_ptr(), counts.data_ptr(), ws.data_ptr(),
-                                           nbytes, torch.cuda.current_stream(self.device).cuda_stream))
+        ws = workspace(self.device, "gm_surface_nets_workspace_bytes", self.nx, self.ny, self.nz)
+        enqueue(self.device, "gm_surface_nets", self.nx, self.ny, self.nz, self._origin_c, self.voxel, tsdf, weight, float(min_weight), max_vertices, V,
+                max_faces, F, counts, workspace=ws)
         return V, F, counts
 
     def _surface_nets(self, min_weight, max_vertices, max_faces, volume=None):
@@ -234,7 +218,7 @@ class TsdfVolume:
         if fill_holes is not None and fill_holes is not False:
             if fill_boundary not in ("none", "free"):
                 raise ValueError("TsdfVolume.extract: fill_boundary must be 'none' or 'free'; got %r" % (fill_boundary,))
-            _need_device(getattr(self, "tsdf", None), "TsdfVolume.extract", "the volume")
+            need_cuda(getattr(self, "tsdf", None), "TsdfVolume.extract", "the volume")
             clock = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             clock[0].record(torch.cuda.current_stream(self.device))
             self.fill_holes(None if fill_holes is True else fill_holes, min_weight=min_weight, boundary=fill_boundary)
@@ -294,7 +278,7 @@ def fuse_cloud(pc, cameras, pipe=None, bg_gaussian=None, resolution=96, bounds=N
     are fused, views_per_call views per call.  bounds = (min, max); default: default_bounds()."""
     from .bg_model import PlainGaussians
     from .renderer import Camera, bg_render, render
-    _need_device(pc.get_xyz, "from_cloud", "the cloud")
+    need_cuda(pc.get_xyz, "from_cloud", "the cloud")
     dev = pc.get_xyz.device
     pipe = pipe if pipe is not None else SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False)
     bg_color = torch.zeros(3, device=dev) if bg_color is None else bg_color
@@ -338,9 +322,9 @@ def from_cloud(pc, cameras, pipe=None, bg_gaussian=None, resolution=96, bounds=N
     return V, F, colors
 
 
-def _load_model(path, mesh_gaussian, dev):
+def load_model(path, mesh_gaussian, dev):
     from . import io as gio
-    t = lambda a, dt=torch.float32: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+    t = lambda a: on_device(a, torch.float32, dev)
     if not mesh_gaussian:
         from .bg_model import PlainGaussians
         m = gio.load_plain_gaussians(path)
@@ -378,7 +362,7 @@ def main(argv=None):
     from . import io as gio
     dev = torch.device("cuda")
     t0 = time.perf_counter()
-    pc = _load_model(a.gaussian, a.mesh_gaussian, dev)
+    pc = load_model(a.gaussian, a.mesh_gaussian, dev)
     cams = gio.load_cameras_json(a.cameras)
     if not cams:
         raise SystemExit("proxy_mesh: %s holds no camera" % a.cameras)
@@ -394,8 +378,8 @@ def main(argv=None):
     t3 = time.perf_counter()
     colors = color_stats = None
     if a.vertex_colors:                                                # on the final mesh, from a second rendering of the views
-        from .mesh_color import _color_from_cloud
-        colors, vc = _color_from_cloud(pc, cams, V, F, None, None, 8, a.alpha_min, vol.trunc, False, True if a.color_spread is None else a.color_spread,
+        from .mesh_color import colors_and_state
+        colors, vc = colors_and_state(pc, cams, V, F, None, None, 8, a.alpha_min, vol.trunc, False, True if a.color_spread is None else a.color_spread,
                                        None)
         colors, color_stats = colors.cpu().numpy(), vc.stats           # (the copy waits for the device)
     t_write = time.perf_counter()

@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._op import enqueue, on as _on, ptr as _ptr, raw_stream as _stream
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -34,10 +35,6 @@ class GaussianRasterizationSettings(NamedTuple):
     work_hint: Optional[torch.Tensor] = None     # extension (new_work_hint()): per-tile cost memory of this camera / view stream
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _prep(t, device):
     """contiguous float32 on `device`, or None for an absent / empty optional input."""
     if t is None or t.numel() == 0:
@@ -47,27 +44,6 @@ def _prep(t, device):
     if t.dtype is torch.float32 and t.is_contiguous():      # the usual case: nothing to convert (only the pointer is used; a render
         return t                                            # loop issues a dozen of these per frame, each conversion a dispatcher trip)
     return t.detach().contiguous().float()
-
-
-class _on:
-    """`with torch.cuda.device(d)` for the usual case that d already is the current device: one C call instead of the context
-    manager's four (a pipelined render loop enters it three times per frame)."""
-    __slots__ = ("guard",)
-
-    def __init__(self, device):
-        self.guard = None if torch.cuda.current_device() == device.index else torch.cuda.device(device)
-
-    def __enter__(self):
-        if self.guard is not None:
-            self.guard.__enter__()
-
-    def __exit__(self, *a):
-        if self.guard is not None:
-            return self.guard.__exit__(*a)
-
-
-def _stream(device):
-    return torch._C._cuda_getCurrentRawStream(device.index)
 
 
 _STREAM_OBJECTS = {}
@@ -122,6 +98,9 @@ def _pol(p, width, height):
     if p is None:
         p = _default_policy[0]
     return auto_emission_policy(width, height) if p == "auto" else int(p)
+
+
+emission_policy_of = _pol      # for the other modules (deform.plan_sequence)
 
 
 class RasterWorkspace:
@@ -773,14 +752,12 @@ def current_sh_step():
 
 def mark_visible(means3D, viewmatrix, projmatrix):
     """rasterize_points.py:39-58 mark_visible -> bool [P]."""
-    lib = _lib.lib()
     device = means3D.device
     means3D, viewmatrix, projmatrix = (_prep(t, device) for t in (means3D, viewmatrix, projmatrix))
     P = 0 if means3D is None else means3D.shape[0]
     present = torch.zeros((P,), dtype=torch.uint8, device=device)
     if P:
-        with _on(device):
-            _lib.check(lib.gm_mark_visible(P, _ptr(means3D), _ptr(viewmatrix), _ptr(projmatrix), _ptr(present), _stream(device)))
+        enqueue(device, "gm_mark_visible", P, means3D, viewmatrix, projmatrix, present)
     return present.bool()
 
 
