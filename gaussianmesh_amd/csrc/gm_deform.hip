@@ -90,7 +90,8 @@ __global__ __launch_bounds__(256) void sh_colors_kernel(int N, int deg, int M, c
 
 // ---------------------------------------------------------------------------------------------
 // The row body of the three fused kernels below (deform_shade_kernel, deform_shade_pre_batch_kernel, scene_shade_pre_batch_kernel).
-// Their frames must come out bit for bit equal (tests/test_gpu_batch.py, test_gpu_scene_batch.py, test_gpu_parity.py), so every
+// Their frames must come out bit for bit equal (tests/test_gpu_batch.py, test_gpu_scene_batch.py, test_gpu_parity.py; row by row, at every SH
+// degree and block edge, and per element against float64: test_gpu_deform_rows.py), so every
 // expression they share is written once, here, with its parenthesisation; arrays are plain pointers and stay in registers after inlining.
 constexpr int DS_THREADS = 64;                     // one-wave workgroups of 64 Gaussians
 

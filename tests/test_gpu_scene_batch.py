@@ -73,7 +73,7 @@ def _batch_inputs(tool, nbg, objs, ntail=0):
     return g
 
 
-def _reference(tool, nbg, objs, defs, cam, H, W, bg, ntail=0, policy=None):
+def _reference(tool, nbg, objs, defs, cam, H, W, bg, ntail=0, policy=None, deg=3):
     """The contract: the rows concatenated in render_gaussian's order (deformed objects through mesh_rs + deform), gm_cov_to_scale_rot of
     every row, the rasterizer's forward with scales / rotations / SH rows -> (num_rendered, image, radii, dict(the frame's rows: pos,
     scales, rots; its binning buffer, laid out for num_rendered instances))"""
@@ -92,7 +92,7 @@ def _reference(tool, nbg, objs, defs, cam, H, W, bg, ntail=0, policy=None):
     s, q = cov_to_scale_rot(torch.cat(cov, dim=0))
     pos = torch.cat(pos, dim=0)
     out = Rz.rasterize_forward_begin(bg, pos, None, g["opac"], s, q, 1, None, cam["view"], cam["proj"], cam["tanx"], cam["tany"],
-                                     H, W, g["shs"], 3, cam["campos"], False, False, emission_policy=policy, force_M=16).finish(image_only=True)
+                                     H, W, g["shs"], deg, cam["campos"], False, False, emission_policy=policy, force_M=16).finish(image_only=True)
     return out[0], out[1].clone(), out[2].clone(), dict(pos=pos, scales=s, rots=q, binning=out[4])
 
 
@@ -110,7 +110,7 @@ def _tables(objs, defs_list):
     return out
 
 
-def _run_batch(tool, nbg, objs, defs_list, cams, H, W, bg, cap, ntail=0, policy=None):
+def _run_batch(tool, nbg, objs, defs_list, cams, H, W, bg, cap, ntail=0, policy=None, deg=3):
     from gaussianmesh_amd import rasterizer as Rz
     from gaussianmesh_amd.deform import cov_to_scale_rot
     g = _batch_inputs(tool, nbg, objs, ntail)
@@ -120,7 +120,7 @@ def _run_batch(tool, nbg, objs, defs_list, cams, H, W, bg, cap, ntail=0, policy=
     for w_ in ws:
         w_.capacity = cap
     hs = Rz.forward_scene_batch(bg, g["rows"], masks, g["pos"], s, q, g["shs"], g["opac"], g["tri"], g["w"], g["ocov"], _tables(objs, defs_list),
-                                cams, H, W, 3, ws, image_only=True, emission_policy=policy)
+                                cams, H, W, deg, ws, image_only=True, emission_policy=policy)
     return hs
 
 
@@ -130,6 +130,17 @@ _PATTERN = [(0,), (0, 1), (), (1,), (0, 1), (0,), (), (0, 1)]
 
 @pytest.mark.parametrize("K,layout", [(1, "scene"), (3, "scene"), (8, "scene"), (8, "straddle"), (3, "no_bg"), (3, "bg_only")])
 def test_scene_batch_frames_equal_the_contract(tmp_path, K, layout):
+    _scene_batch_frames_equal_the_contract(tmp_path, K, layout, 3)
+
+
+@pytest.mark.parametrize("D", [0, 1, 2, 3])
+def test_scene_batch_frames_equal_the_contract_at_every_sh_degree(tmp_path, D):
+    """the straddling layout (wave 0 holds background, A and B rows) with the degree a model sends before its SH degree has grown, in the
+    kernel call and in the contract"""
+    _scene_batch_frames_equal_the_contract(tmp_path, 3, "straddle", D)
+
+
+def _scene_batch_frames_equal_the_contract(tmp_path, K, layout, deg):
     from gaussianmesh_amd import rasterizer as Rz
     tool, d1, _ = _tool(tmp_path)
     nbg, objs = _layout(tool, layout)
@@ -140,17 +151,17 @@ def test_scene_batch_frames_equal_the_contract(tmp_path, K, layout):
     for k in range(K):
         defs_list.append({j: _mesh(o, 3 + 2 * k + 5 * j) for j, (o, _) in enumerate(objs) if j in _PATTERN[k]})
     frame_cams = [cams[k % len(cams)] for k in range(K)]
-    ref = [_reference(tool, nbg, objs, defs, c, H, W, bg) for defs, c in zip(defs_list, frame_cams)]
+    ref = [_reference(tool, nbg, objs, defs, c, H, W, bg, deg=deg) for defs, c in zip(defs_list, frame_cams)]
     assert all(r[0] > 0 for r in ref), [r[0] for r in ref]
     cap = int(max(r[0] for r in ref) * 1.25) + 1024
-    hs = _run_batch(tool, nbg, objs, defs_list, frame_cams, H, W, bg, cap)
+    hs = _run_batch(tool, nbg, objs, defs_list, frame_cams, H, W, bg, cap, deg=deg)
     policy = Rz.get_default_emission_policy(W, H)
     for k, h in enumerate(hs):
         ok, nr = h.check()
         assert ok and nr == ref[k][0], (k, ok, nr, ref[k][0])
         assert h.workspace.status()[0].tolist() == [nr, 0, policy, 0], k
-        assert torch.equal(h.radii, ref[k][2]), "frame %d of %d (%s): radii" % (k, K, layout)
-        assert torch.equal(h.color, ref[k][1]), "frame %d of %d (%s): image" % (k, K, layout)
+        assert torch.equal(h.radii, ref[k][2]), "frame %d of %d (%s, degree %d): radii" % (k, K, layout, deg)
+        assert torch.equal(h.color, ref[k][1]), "frame %d of %d (%s, degree %d): image" % (k, K, layout, deg)
 
 
 def test_a_scene_frame_refused_for_capacity_is_rendered_again_exactly(tmp_path):
