@@ -105,6 +105,8 @@ SIGNATURES = {
     "gm_deform_shade_packed": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gm_cov_to_scale_rot": (i32, [i32, vp, vp, vp, vp]),
     "gm_sh_rotate": (i32, [i32, i32, i32, vp, vp, vp, vp]),
+    "gm_deform_shade_bwd_workspace_bytes": (sz, [i32, i32]),
+    "gm_deform_shade_bwd": (i32, [i32, i32, i32, i32] + [vp] * 11 + [vp] * 3 + [vp] * 6 + [vp, sz, vp]),
     "gm_mesh_rs": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gm_mesh_rs_packed": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "gm_mesh_activate_fwd": (i32, [i32, f32] + [vp] * 10 + [vp] * 4 + [f32, vp] + [vp]),

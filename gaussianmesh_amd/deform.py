@@ -11,7 +11,7 @@ The arithmetic (gather, barycentric blend, RS cov RS^T, x + dx) runs in one HIP 
 import torch
 
 from . import _lib
-from ._op import enqueue, need_cuda
+from ._op import enqueue, need_cuda, workspace
 
 
 def _f(t):
@@ -71,6 +71,92 @@ def deform_shade(tri, w, dV, Rv, Sv, cov, pos, shs, campos, deg=3, want_cov_rot=
     rot_o = torch.empty((N, 3, 3), **f) if want_cov_rot else None
     enqueue(device, "gm_deform_shade", N, int(deg), M, tri, w, dV, Rv, Sv, cov, pos, shs, campos, pos_o, cov6, rgb, cov_o, rot_o)
     return (pos_o, cov6, rgb, cov_o, rot_o) if want_cov_rot else (pos_o, cov6, rgb)
+
+
+class DeformBinding:
+    """What ties a cloud to its proxy mesh, as the differentiable pass needs it: tri int32 [N,3], w float32 [N,3], Vm, and the vertex ->
+    (row, corner) incidence list in CSR form that gm_deform_shade_bwd sums over - inc_offsets int32 [Vm+1], inc_entries int32 [3N] with
+    entry 3 * row + corner, ascending within a vertex.  Built once, on the device: a stable sort of tri.reshape(-1), a bincount and its
+    cumsum.  The vertex ids are checked against Vm here (one host wait per binding), since the kernels index the tables with them."""
+
+    def __init__(self, tri, w, Vm):
+        need_cuda(tri, "DeformBinding", "tensors")
+        self.tri = tri.detach().contiguous().to(torch.int32)
+        self.w = _f(w)
+        self.Vm = int(Vm)
+        N = self.tri.shape[0]
+        if self.tri.shape != (N, 3) or self.w.shape != (N, 3):
+            raise ValueError("DeformBinding: tri and w must be [N,3]; got %s and %s" % (tuple(self.tri.shape), tuple(self.w.shape)))
+        if 3 * N >= 2 ** 31:
+            raise ValueError("DeformBinding: 3 N = %d entries do not fit an int32" % (3 * N))
+        flat = self.tri.reshape(-1).to(torch.int64)
+        if N and (self.Vm < 1 or int(flat.min()) < 0 or int(flat.max()) >= self.Vm):
+            raise ValueError("DeformBinding: vertex ids outside 0..%d" % (self.Vm - 1))
+        self.inc_entries = torch.sort(flat, stable=True)[1].to(torch.int32)
+        off = torch.zeros(self.Vm + 1, dtype=torch.int64, device=self.tri.device)
+        if N:
+            off[1:] = torch.cumsum(torch.bincount(flat, minlength=self.Vm), 0)
+        self.inc_offsets = off.to(torch.int32)
+
+
+class _DeformShade(torch.autograd.Function):
+    """forward: gm_deform_shade; backward: one gm_deform_shade_bwd"""
+
+    @staticmethod
+    def forward(ctx, binding, deg, dV, Rv, Sv, cov, pos, shs, campos):
+        device = pos.device
+        args = tuple(_f(t) for t in (dV, Rv, Sv, cov, pos, shs, campos))
+        dV_, Rv_, Sv_, cov_, pos_, shs_, campos_ = args
+        N, M = pos_.shape[0], shs_.shape[1]
+        f = dict(dtype=torch.float32, device=device)
+        pos_o = torch.empty((N, 3), **f); cov6 = torch.empty((N, 6), **f); rgb = torch.empty((N, 3), **f)
+        # (rows of M != 16 coefficients take gm_deform_shade's unfused route, which needs the two [N,3,3] intermediates)
+        cov_o = torch.empty((N, 3, 3), **f) if M != 16 else None
+        rot_o = torch.empty((N, 3, 3), **f) if M != 16 else None
+        enqueue(device, "gm_deform_shade", N, int(deg), M, binding.tri, binding.w, dV_, Rv_, Sv_, cov_, pos_, shs_, campos_, pos_o, cov6, rgb,
+                cov_o, rot_o)
+        ctx.binding, ctx.deg, ctx.shapes = binding, int(deg), (dV.shape, Rv.shape, Sv.shape, cov.shape, pos.shape, shs.shape)
+        ctx.save_for_backward(*args)
+        ctx.set_materialize_grads(False)                         # an output nobody used arrives as None and goes to the call as NULL
+        return pos_o, cov6, rgb
+
+    @staticmethod
+    def backward(ctx, g_pos, g_cov6, g_rgb):
+        dV, Rv, Sv, cov, pos, shs, campos = ctx.saved_tensors
+        b, device = ctx.binding, pos.device
+        N, M, Vm = pos.shape[0], shs.shape[1], b.Vm
+        f = dict(dtype=torch.float32, device=device)
+        need = ctx.needs_input_grad                              # (binding, deg, dV, Rv, Sv, cov, pos, shs, campos)
+        g_pos = torch.zeros((N, 3), **f) if g_pos is None else _f(g_pos)
+        g_cov6 = None if g_cov6 is None else _f(g_cov6)
+        g_rgb = None if g_rgb is None else _f(g_rgb)
+        g_dV = torch.empty((Vm, 3), **f); g_Rv = torch.empty((Vm, 9), **f); g_Sv = torch.empty((Vm, 9), **f)
+        g_cov = torch.empty((N, 9), **f) if need[5] else None
+        g_rest = torch.empty((N, 3), **f) if need[6] else None
+        no_upstream = g_cov6 is None and g_rgb is None           # (the rows' gradient is then zero, and the call refuses to be asked for it)
+        g_shs = None
+        if need[7]:
+            g_shs = torch.zeros((N, M, 3), **f) if no_upstream else torch.empty((N, M, 3), **f)
+        ws = workspace(device, "gm_deform_shade_bwd_workspace_bytes", N, Vm)
+        enqueue(device, "gm_deform_shade_bwd", N, ctx.deg, M, Vm, b.tri, b.w, dV, Rv, Sv, cov, pos, shs, campos, b.inc_offsets, b.inc_entries,
+                g_pos, g_cov6, g_rgb, g_dV, g_Rv, g_Sv, None if no_upstream else g_shs, g_cov, g_rest, workspace=ws)
+        s = ctx.shapes
+        out = (g_dV.reshape(s[0]), g_Rv.reshape(s[1]), g_Sv.reshape(s[2]), None if g_cov is None else g_cov.reshape(s[3]),
+               None if g_rest is None else g_rest.reshape(s[4]), None if g_shs is None else g_shs.reshape(s[5]))
+        return (None, None) + tuple(g if n else None for g, n in zip(out, need[2:8])) + (None,)
+
+
+def deform_shade_differentiable(binding, dV, Rv, Sv, cov, pos, shs, campos, deg=3):
+    """deform_shade with a backward: (pos' [N,3], cov6 [N,6], rgb [N,3]), bit for bit deform_shade's, as an autograd Function whose
+    backward is one gm_deform_shade_bwd (csrc/gm_deform_bwd.hip).  binding: a DeformBinding (its tri and w carry no gradient, nor does
+    campos).  Gradients flow to dV [Vm,3], Rv / Sv [Vm,3,3] or [Vm,9], and - where the tensor requires grad - to cov, pos and shs; None
+    comes back for the rest.  The vertex sums are deterministic: the same inputs give the same bits."""
+    need_cuda(pos.device, "deform_shade_differentiable", "tensors")
+    if not isinstance(binding, DeformBinding):
+        raise TypeError("deform_shade_differentiable: binding must be a DeformBinding")
+    if dV.shape[0] != binding.Vm or Rv.numel() != 9 * binding.Vm or Sv.numel() != 9 * binding.Vm or pos.shape[0] != binding.tri.shape[0]:
+        raise ValueError("deform_shade_differentiable: tables of %d vertices and %d rows expected" % (binding.Vm, binding.tri.shape[0]))
+    return _DeformShade.apply(binding, int(deg), dV, Rv, Sv, cov, pos, shs, campos)
 
 
 def pack_cov6(cov):
@@ -299,6 +385,26 @@ class SingleObjectDeform:
     def mesh_vertex_current(self):
         """The proxy mesh's vertices as last deformed ([Vm,3], the V1 of deform_state); None: the rest pose.  drag() starts from them."""
         return None if self.deform_state is None else self.deform_state[0]
+
+    @property
+    def binding(self):
+        """The DeformBinding of this object's cloud (deform_shade_differentiable's first argument), built the first time it is asked for."""
+        if getattr(self, "_binding", None) is None:
+            self._binding = DeformBinding(self.gaussian_triangles, self.coord, self.vertex.shape[0])
+        return self._binding
+
+    def fit_pose(self, views, iterations, faces=None, background=None, **fitter_options):
+        """Fit the proxy mesh's pose to images: pose_fit.PoseFitter(self, faces, **fitter_options).fit(views, iterations, background) -
+        views a list of (camera, target [3,H,W]) pairs.  Leaves the object deformed to the fitted pose (deform_state) and returns the
+        fitter (its .losses, its .pose)."""
+        from .pose_fit import PoseFitter
+        if faces is not None:
+            self._set_faces(faces)
+        if getattr(self, "faces", None) is None:
+            raise ValueError("fit_pose: this object has no faces; pass faces=[F,3]")
+        fitter = PoseFitter(self, self.faces, **fitter_options)
+        fitter.fit(views, iterations, background=background)
+        return fitter
 
     def _set_faces(self, faces):
         self.faces = torch.as_tensor(faces).detach().to(device=self.vertex.device, dtype=torch.int32).contiguous()

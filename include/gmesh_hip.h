@@ -770,6 +770,28 @@ int gm_cov_to_scale_rot(int N, const float* cov, float* scales, float* rots, voi
  * overlapping shs other than exactly equal, shs_out overlapping rot. */
 int gm_sh_rotate(int N, int deg, int M, const float* shs, const float* rot, float* shs_out, void* stream);
 
+/* Backward of gm_deform_shade (csrc/gm_deform_bwd.hip): from the gradients of its three outputs - g_pos [N,3], g_cov6 [N,6] (may be NULL),
+ * g_rgb [N,3] (may be NULL); a NULL stands for zeros and gives the bits an all-zero tensor gives - to the gradients of the per-vertex
+ * tables, g_dV [Vm,3], g_Rv [Vm,9], g_Sv [Vm,9] (mandatory), and optionally (NULL switches each off) of the SH rows g_shs [N,M,3]
+ * (coefficients k >= (deg+1)^2 are written as 0), the rest covariances g_cov [N,9] and the rest positions g_rest_pos [N,3].  No gradient
+ * to w or campos.  The forward's inputs are the forward's: tri int32 [N,3], w [N,3], dV [Vm,3], Rv / Sv [Vm,9], cov [N,9], pos [N,3],
+ * shs [N,M,3], campos [3]; the forward is recomputed with its own arithmetic, so the clamp gate is the one behind the rgb it wrote.
+ * Vertex sums are deterministic and use no atomics: they run over the vertex -> (row, corner) incidence list in CSR form,
+ * inc_offsets int32 [Vm+1] (inc_offsets[0] = 0, inc_offsets[Vm] = 3 N) and inc_entries int32 [3N] with entry 3 * row + corner, ascending
+ * within a vertex (deform.DeformBinding builds it once per binding).  THE CALLER'S CONTRACT: entry e lies in vertex tri[e]'s list, each
+ * e in [0, 3N) exactly once; the call does not check it (an entry outside [0, 3N) is skipped, nothing else).  A vertex's sum is a fixed
+ * function of its list: the same bits every run.  A vertex with an empty list gets exact zeros; every element of g_dV / g_Rv / g_Sv is
+ * written (no pre-zeroing).  workspace: gm_deform_shade_bwd_workspace_bytes(N, Vm) bytes, fully written before it is read.
+ * Stream-ordered: no device allocation, no host wait.  N == 0 writes zero tables; Vm == 0 with N == 0 does nothing.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: N < 0 or Vm < 0, deg outside 0..3, M < (deg+1)^2, N > 0 with Vm == 0, a NULL
+ * mandatory pointer, g_shs without both g_rgb and g_cov6, a workspace shorter than gm_deform_shade_bwd_workspace_bytes, an output or the
+ * workspace overlapping an input or another output. */
+size_t gm_deform_shade_bwd_workspace_bytes(int N, int Vm);
+int gm_deform_shade_bwd(int N, int deg, int M, int Vm, const int* tri, const float* w, const float* dV, const float* Rv, const float* Sv,
+                        const float* cov, const float* pos, const float* shs, const float* campos, const int* inc_offsets,
+                        const int* inc_entries, const float* g_pos, const float* g_cov6, const float* g_rgb, float* g_dV, float* g_Rv,
+                        float* g_Sv, float* g_shs, float* g_cov, float* g_rest_pos, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Photometric loss of the training loop (train_mesh_gaussian.py:92-94): replaces utils/loss_utils.py:17-18 (l1_loss) and
  * :23-81 (ssim: 11x11 Gaussian window of sigma 1.5, zero padding 5, depthwise) and the autograd pass through them.
  * img1 (rendered) / img2 (ground truth): float [planes,H,W] (planes = channels, or batch x channels).
