@@ -66,6 +66,10 @@ SIGNATURES = {
     "gm_arap_solve_grid": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp, sz, vp]),
     "gm_arap_batch_workspace_bytes": (sz, [i32, i32, i32]),
     "gm_arap_solve_batch": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp, sz, vp]),
+    "gm_arap_energy_workspace_bytes": (sz, [i32]),
+    "gm_arap_energy_grad": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "gm_mesh_smooth_workspace_bytes": (sz, [i32]),
+    "gm_mesh_smooth_rows": (i32, [i32, vp, vp, vp, vp, f64, i32, vp, vp, sz, vp]),
     "gm_ray_mesh_workspace_bytes": (sz, [i32, i32]),
     "gm_ray_mesh": (i32, [i32, vp, vp, i32, vp, i32, vp, f32, f32, vp, vp, vp, vp, sz, vp]),
     "gm_mesh_geodesic_workspace_bytes": (sz, [i32, i32, i32]),

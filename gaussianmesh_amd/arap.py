@@ -1,7 +1,9 @@
 """Deform a proxy mesh from dragged handle vertices: as-rigid-as-possible (Sorkine & Alexa 2007) on the device (gm_arap_solve,
 csrc/gm_arap.hip).  The stage the reference leaves to an external binary: "move these vertices there; the rest of the mesh follows as
 rigidly as it can".  Its output is what deform.mesh_rs / SingleObjectDeform.deform_vertices / render_sequence take, so a handle drag is
-solve -> gm_mesh_rs -> forward on one stream, with no host wait.  Definition, ABI and rules: INTEGRATION.md section Q."""
+solve -> gm_mesh_rs -> forward on one stream, with no host wait.  Definition, ABI and rules: INTEGRATION.md section Q.
+ArapEnergy is the same energy as a function of a pose, with its gradient, and one-ring smoothing of per-vertex rows (gm_arap_energy_grad,
+gm_mesh_smooth_rows): what pose_fit.PoseFitter takes as a rigidity term and for its gradient."""
 import numpy as np
 import torch
 
@@ -61,6 +63,89 @@ def sequence_runs(T, batch):
     if T < 0 or batch < 1:
         raise ValueError("sequence_runs: T >= 0 and batch >= 1; got T = %d, batch = %d" % (T, batch))
     return [(a, min(a + batch, T)) for a in range(0, T, batch)]
+
+
+class _ArapEnergyFunction(torch.autograd.Function):
+    """E(V1) / scale of an ArapEnergy as a node of the graph: forward keeps the device's gradient, backward scales it"""
+
+    @staticmethod
+    def forward(ctx, V1, energy):
+        E, grad = energy.value_and_grad(V1)
+        ctx.save_for_backward(grad)
+        ctx.scale, ctx.dtype = energy.scale, V1.dtype
+        return (E / energy.scale).to(V1.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (grad,) = ctx.saved_tensors
+        return (grad_out.to(torch.float64) * grad / ctx.scale).to(ctx.dtype), None
+
+
+class ArapEnergy:
+    """The ARAP energy of a pose of one mesh as a function of the pose alone, with its gradient (gm_arap_energy_grad), and one-ring
+    smoothing of per-vertex rows over the same edge graph (gm_mesh_smooth_rows): a rigidity term that sees bending, and the Sobolev
+    gradient, for an optimiser of the vertices (pose_fit.PoseFitter).  Built once: the edge CSR (edge_csr), the rest vertices,
+    scale = sum_ij w_ij |p_i - p_j|^2 (the size of E's terms: E / scale does not depend on the mesh's units) and the workspaces.
+        E(x) = sum_i sum_j w_ij |(x_i - x_j) - R_i (p_i - p_j)|^2, R_i the local step's rotation at x;  0 for a rigid motion of the rest pose
+    ValueError for a mesh without an edge (scale = 0).  Definition, ABI and rules: INTEGRATION.md section Y."""
+
+    def __init__(self, rest_vertices, faces, device="cuda"):
+        self.device = torch.device(device)
+        v = np.ascontiguousarray(np.asarray(host(rest_vertices), np.float32))
+        if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] == 0:
+            raise ValueError("ArapEnergy: rest_vertices must be [Vm,3] with Vm > 0; got %s" % (tuple(v.shape),))
+        off, cols, weights = edge_csr(v, faces)
+        rows = np.repeat(np.arange(v.shape[0], dtype=np.int64), np.diff(off.astype(np.int64)))
+        e = v.astype(np.float64)[rows] - v.astype(np.float64)[cols]
+        self.Vm, self.csr = v.shape[0], (off, cols, weights)
+        self.scale = float((weights * (e * e).sum(axis=1)).sum())
+        if not self.scale > 0.0:
+            raise ValueError("ArapEnergy: the mesh has no edge of positive length (scale = %g)" % self.scale)
+        if self.device.type != "cuda":                                 # the set-up above is host work; every call needs the device
+            return
+        t = lambda a, dt: on_device(a, dt, self.device)
+        self.rest = t(v, torch.float32)
+        self._off, self._cols, self._w = t(off, torch.int32), t(cols, torch.int32), t(weights, torch.float64)
+        self._ws = workspace(self.device, "gm_arap_energy_workspace_bytes", self.Vm)
+        self._smooth_ws = None                                         # made by the first smooth_rows
+
+    def _pose(self, V1, who):
+        if self.device.type != "cuda" or not torch.is_tensor(V1) or V1.device.type != "cuda":
+            raise _lib.GmeshError("%s needs the object and V1 on a HIP (cuda) device; there is no CPU path" % who)
+        if V1.shape != (self.Vm, 3) or not V1.dtype.is_floating_point:
+            raise ValueError("%s: V1 must be a floating-point [%d,3] tensor; got %s %s" % (who, self.Vm, V1.dtype, tuple(V1.shape)))
+        return V1.detach().to(device=self.rest.device, dtype=torch.float32).contiguous()
+
+    def value_and_grad(self, V1, want_grad=True):
+        """(E float64 0-dim, dE/dV1 float64 [Vm,3]) of the pose V1 [Vm,3] (read as float32), on the device; want_grad=False: (E, None),
+        the same bits of E.  Stream-ordered, nothing here waits for the device; two identical calls give identical bits."""
+        v1 = self._pose(V1, "ArapEnergy.value_and_grad")
+        E = torch.empty((), dtype=torch.float64, device=v1.device)
+        grad = torch.empty((self.Vm, 3), dtype=torch.float64, device=v1.device) if want_grad else None
+        enqueue(v1.device, "gm_arap_energy_grad", self.Vm, self._off, self._cols, self._w, self.rest, v1, E, grad, workspace=self._ws)
+        return E, grad
+
+    def __call__(self, V1):
+        """E(V1) / scale: a 0-dim tensor of V1's dtype, differentiable in V1 once (a second derivative raises)"""
+        self._pose(V1, "ArapEnergy")
+        return _ArapEnergyFunction.apply(V1, self)
+
+    def smooth_rows(self, rows, lam, sweeps):
+        """`sweeps` Jacobi sweeps of (I + lam L) y = rows from y = rows, L the Laplacian of the edge weights: rows [Vm,3] float32 or
+        float64 on the device, returned in the same dtype (a new tensor), the arithmetic in float64.  sweeps = 0 or lam = 0 return the
+        rows; max |y| never grows and a constant field stays constant.  GmeshError for lam < 0, sweeps < 0 and a CPU tensor."""
+        if self.device.type != "cuda" or not torch.is_tensor(rows) or rows.device.type != "cuda":
+            raise _lib.GmeshError("ArapEnergy.smooth_rows needs the object and rows on a HIP (cuda) device; there is no CPU path")
+        if rows.shape != (self.Vm, 3) or rows.dtype not in (torch.float32, torch.float64):
+            raise ValueError("ArapEnergy.smooth_rows: rows must be float32 or float64 [%d,3]; got %s %s" % (self.Vm, rows.dtype, tuple(rows.shape)))
+        dev = self.rest.device
+        if self._smooth_ws is None:
+            self._smooth_ws = workspace(dev, "gm_mesh_smooth_workspace_bytes", self.Vm)
+        g = rows.detach().to(device=dev, dtype=torch.float64).contiguous()
+        out = torch.empty((self.Vm, 3), dtype=torch.float64, device=dev)
+        enqueue(dev, "gm_mesh_smooth_rows", self.Vm, self._off, self._cols, self._w, g, float(lam), int(sweeps), out, workspace=self._smooth_ws)
+        return out.to(rows.dtype)
 
 
 class ArapSolver:

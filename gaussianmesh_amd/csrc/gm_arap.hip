@@ -33,6 +33,10 @@
 //   rows and workspace slab (state columns, R, slots, carry), `slab` doubles from item b - 1's - on the one mesh: CSR, weights, V0, diag
 //   and free_row are shared (item 0's workgroups write the last two, in arap_init).  The single solves are a batch of one, through the
 //   same kernels: an item's bits do not depend on the batch it rides in.  No workgroup reads what another item's wrote.
+// THE ENERGY OF A POSE (gm_arap_energy_grad) and ONE-RING SMOOTHING of rows (gm_mesh_smooth_rows) are at the end of the namespace: E as a
+//   function of the pose alone with its gradient, over ceil(Vm / 256) workgroups, and Jacobi sweeps of (I + lambda L) y = g - what an
+//   optimiser of the vertices (pose_fit.py) takes as a rigidity term and as a preconditioner of its gradient.  They share arap_rotation,
+//   arap_block_sum and arap_slot_sum with the solver and none of its kernels.
 // Conventions of gm_closest.hip: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
 #include "gm_check.h"
@@ -647,6 +651,208 @@ static void arap_grid_chain(int B, size_t slab, const ArapGridWs& k, int Vm, con
   }
 }
 
+// ---- the energy of a pose and its gradient (gm_arap_energy_grad): E(x) = min_R E(x, R) as a function of the pose alone ----
+//   R_i(x): the local step (arap_rotation of S_i, above), so E(x) = E(x, R(x)); the R_i minimise E, hence the total derivative is the
+//   partial one at fixed R:   dE/dx_i = 4 sum_j w_ij [ (x_i - x_j) - (R_i + R_j)(p_i - p_j) / 2 ]   (w symmetric: the neighbour's share
+//   of the edge is its own term of row i, nothing is scattered) - the residual of the global step's equation, times 4.
+//   A row whose pose edges x_i - x_j equal its rest edges p_i - p_j bit for bit (the rest pose, a translate of it that float32 holds)
+//   takes R_i = I itself and not the eigen-route's I + O(1e-16): the rest pose then has E = 0 and dE/dx = 0 exactly.
+// Three launches, rows over G = ceil(Vm / 256) workgroups that meet only at the kernel boundaries:
+//   arap_pose_local    one thread per vertex: R_i from the float32 pose, into the workspace as [Vm][9] (one gather per neighbour)
+//   arap_energy_grad   one thread per vertex: g_i, the row's energy; the workgroup's energies into its slot (arap_block_sum)
+//   arap_energy_total  one wave adds the G slots in index order (arap_slot_sum)
+// Both row kernels ask for ARAP_POSE_BATCH edges of a row together, as arap_grid_product does: at these sizes (one workgroup per CU
+// or fewer) a row's time is its chain of dependent gathers, not its bytes.  Sums in CSR order, no atomics: two calls give the same bits.
+#define ARAP_POSE_BATCH 8
+
+struct ArapEnergyWs {
+  double* R;       // [Vm][9]: R_i row-major
+  double* slots;   // [G] the workgroups' energies
+  char* end;
+  static ArapEnergyWs from(void* ws, size_t Vm) {
+    char* p = reinterpret_cast<char*>(ws);
+    ArapEnergyWs k;
+    k.R = carve<double>(p, 9 * Vm);
+    k.slots = carve<double>(p, (Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS);
+    k.end = p;
+    return k;
+  }
+};
+
+__global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_pose_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                           const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                           const float* __restrict__ V1, double* __restrict__ R) {
+  const int i = blockIdx.x * ARAP_ROW_THREADS + threadIdx.x;
+  if (i >= Vm) return;
+  const int k0 = row_offsets[i], k1 = row_offsets[i + 1];
+  double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Q[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, pi[3], xi[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) { pi[c] = (double)V0[3 * (size_t)i + c]; xi[c] = (double)V1[3 * (size_t)i + c]; }
+  bool unmoved = true;
+  for (int kb = k0; kb < k1; kb += ARAP_POSE_BATCH) {               // past the row's end the last edge is read again and not added
+    int j[ARAP_POSE_BATCH];
+    double w[ARAP_POSE_BATCH];
+    float pj[ARAP_POSE_BATCH][3], xj[ARAP_POSE_BATCH][3];
+#pragma unroll
+    for (int t = 0; t < ARAP_POSE_BATCH; t++) {
+      const int k = min(kb + t, k1 - 1);
+      j[t] = clamp_index(cols[k], Vm); w[t] = weights[k];
+    }
+#pragma unroll
+    for (int t = 0; t < ARAP_POSE_BATCH; t++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) { pj[t][c] = V0[3 * (size_t)j[t] + c]; xj[t][c] = V1[3 * (size_t)j[t] + c]; }
+#pragma unroll
+    for (int t = 0; t < ARAP_POSE_BATCH; t++)
+      if (kb + t < k1) {
+        double e[3], d[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) { e[c] = pi[c] - (double)pj[t][c]; d[c] = xi[c] - (double)xj[t][c]; unmoved = unmoved && d[c] == e[c]; }
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+          for (int b = 0; b < 3; b++) S[a][b] += w[t] * d[a] * e[b];
+      }
+  }
+  if (!unmoved) arap_rotation(S, Q);
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = 0; b < 3; b++) R[9 * (size_t)i + 3 * a + b] = Q[a][b];
+}
+
+// grad: null when only the energy is wanted (the same arithmetic: the same energy bits)
+__global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_energy_grad_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                            const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                            const float* __restrict__ V1, const double* __restrict__ R,
+                                                                            double* __restrict__ grad, double* __restrict__ slots) {
+  __shared__ double part[1][ARAP_ROW_WAVES];
+  // (a thread past the last row reads the last row, adds nothing and writes nothing: every thread reaches the sum's barrier)
+  const int i = min(blockIdx.x * ARAP_ROW_THREADS + threadIdx.x, Vm - 1);
+  const bool row = blockIdx.x * ARAP_ROW_THREADS + threadIdx.x < Vm;
+  const int k0 = row_offsets[i], k1 = row_offsets[i + 1];
+  double Ri[3][3], pi[3], xi[3], g[3] = {0.0, 0.0, 0.0}, e_i = 0.0, deg = 0.0;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    pi[c] = (double)V0[3 * (size_t)i + c]; xi[c] = (double)V1[3 * (size_t)i + c];
+#pragma unroll
+    for (int a = 0; a < 3; a++) Ri[c][a] = R[9 * (size_t)i + 3 * c + a];
+  }
+  for (int kb = k0; kb < k1; kb += ARAP_POSE_BATCH) {
+    int j[ARAP_POSE_BATCH];
+    double w[ARAP_POSE_BATCH], Rj[ARAP_POSE_BATCH][9];
+    float pj[ARAP_POSE_BATCH][3], xj[ARAP_POSE_BATCH][3];
+#pragma unroll
+    for (int t = 0; t < ARAP_POSE_BATCH; t++) {
+      const int k = min(kb + t, k1 - 1);
+      j[t] = clamp_index(cols[k], Vm); w[t] = weights[k];
+    }
+#pragma unroll
+    for (int t = 0; t < ARAP_POSE_BATCH; t++) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) { pj[t][c] = V0[3 * (size_t)j[t] + c]; xj[t][c] = V1[3 * (size_t)j[t] + c]; }
+#pragma unroll
+      for (int a = 0; a < 9; a++) Rj[t][a] = R[9 * (size_t)j[t] + a];
+    }
+#pragma unroll
+    for (int t = 0; t < ARAP_POSE_BATCH; t++)
+      if (kb + t < k1) {
+        double e[3], s = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) e[c] = pi[c] - (double)pj[t][c];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          const double d = xi[c] - (double)xj[t][c];
+          const double own = Ri[c][0] * e[0] + Ri[c][1] * e[1] + Ri[c][2] * e[2];
+          const double both = (Ri[c][0] + Rj[t][3 * c]) * e[0] + (Ri[c][1] + Rj[t][3 * c + 1]) * e[1] + (Ri[c][2] + Rj[t][3 * c + 2]) * e[2];
+          g[c] += w[t] * (d - 0.5 * both);
+          s += (d - own) * (d - own);
+        }
+        e_i += w[t] * s;
+        deg += w[t];
+      }
+  }
+  double acc[1] = {row && deg > 0.0 ? e_i : 0.0};                  // a pinned row (its weights sum to 0) contributes nothing
+  if (row && grad)
+#pragma unroll
+    for (int c = 0; c < 3; c++) grad[3 * (size_t)i + c] = deg > 0.0 ? 4.0 * g[c] : 0.0;
+  arap_block_sum<1, ARAP_ROW_WAVES>(acc, part);
+  if (threadIdx.x == 0) slots[blockIdx.x] = acc[0];
+}
+
+// one wave: the G slots in the order of arap_slot_sum, into *out
+__global__ __launch_bounds__(64) void arap_energy_total_kernel(const double* __restrict__ slots, int G, double* __restrict__ out) {
+  double v[1];
+  arap_slot_sum<1>(slots, G, v);
+  if (threadIdx.x == 0) *out = v[0];
+}
+
+// ---- one-ring smoothing of per-vertex rows (gm_mesh_smooth_rows): T Jacobi sweeps of (I + lambda L) y = g from y = g ----
+//   y_i <- (g_i + lambda sum_j w_ij y_j) / (1 + lambda d_i): a convex combination of g_i and the neighbours' values, so nothing grows, a
+//   constant field stays, a row with d_i = 0 keeps g_i.  One thread per vertex, one launch per sweep between two copies of the state
+//   (the scheme of gm_tsdf_fill): a sweep reads only what the previous launch wrote.  smooth_init: d_i once (as 1 + lambda d_i), g into
+//   the first copy; the last sweep writes `out`, which may be g itself - a thread reads g_i before it writes row i, and no other row of g.
+__global__ __launch_bounds__(ARAP_ROW_THREADS) void smooth_init_kernel(int Vm, const int* __restrict__ row_offsets, const double* __restrict__ weights,
+                                                                       const double* g, double lambda, double* __restrict__ denom,
+                                                                       double* __restrict__ state, double* out) {
+  const int i = blockIdx.x * ARAP_ROW_THREADS + threadIdx.x;
+  if (i >= Vm) return;
+  const double gi[3] = {g[3 * (size_t)i], g[3 * (size_t)i + 1], g[3 * (size_t)i + 2]};
+  double d = 0.0;
+  for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) d += weights[k];
+  denom[i] = 1.0 + lambda * d;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    state[3 * (size_t)i + c] = gi[c];
+    if (out) out[3 * (size_t)i + c] = gi[c];                         // sweeps == 0: the copy
+  }
+}
+
+__global__ __launch_bounds__(ARAP_ROW_THREADS) void smooth_sweep_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                        const double* __restrict__ weights, const double* g,
+                                                                        const double* __restrict__ denom, double lambda, const double* __restrict__ y,
+                                                                        double* y_next) {
+  const int i = blockIdx.x * ARAP_ROW_THREADS + threadIdx.x;
+  if (i >= Vm) return;
+  const int k0 = row_offsets[i], k1 = row_offsets[i + 1];
+  const double gi[3] = {g[3 * (size_t)i], g[3 * (size_t)i + 1], g[3 * (size_t)i + 2]}, den = denom[i];
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int kb = k0; kb < k1; kb += ARAP_POSE_BATCH) {               // past the row's end the last edge is read again and not added
+    int j[ARAP_POSE_BATCH];
+    double w[ARAP_POSE_BATCH], yj[ARAP_POSE_BATCH][3];
+#pragma unroll
+    for (int t = 0; t < ARAP_POSE_BATCH; t++) {
+      const int k = min(kb + t, k1 - 1);
+      j[t] = clamp_index(cols[k], Vm); w[t] = weights[k];
+    }
+#pragma unroll
+    for (int t = 0; t < ARAP_POSE_BATCH; t++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) yj[t][c] = y[3 * (size_t)j[t] + c];
+#pragma unroll
+    for (int t = 0; t < ARAP_POSE_BATCH; t++)
+      if (kb + t < k1)
+#pragma unroll
+        for (int c = 0; c < 3; c++) acc[c] += w[t] * yj[t][c];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++) y_next[3 * (size_t)i + c] = (gi[c] + lambda * acc[c]) / den;
+}
+
+struct SmoothWs {
+  double* denom;      // [Vm] 1 + lambda d_i
+  double* state[2];   // [Vm][3] each
+  char* end;
+  static SmoothWs from(void* ws, size_t Vm) {
+    char* p = reinterpret_cast<char*>(ws);
+    SmoothWs k;
+    k.denom = carve<double>(p, Vm);
+    k.state[0] = carve<double>(p, 3 * Vm); k.state[1] = carve<double>(p, 3 * Vm);
+    k.end = p;
+    return k;
+  }
+};
+
 }  // namespace gm
 
 // ---------------------------------------------------------------------------------------------
@@ -735,6 +941,62 @@ int gm_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, 
     const ArapWs k = ArapWs::batch(workspace, (size_t)Vm, (size_t)B, &slab);
     arap_column_chain(B, slab, k, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats, s);
   }
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+// ---- E(x) and dE/dx of a pose (gm_arap_energy_grad), one-ring smoothing of rows (gm_mesh_smooth_rows) ----
+size_t gm_arap_energy_workspace_bytes(int Vm) {
+  ArapEnergyWs k = ArapEnergyWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 1));
+  return (size_t)k.end + 256;
+}
+
+int gm_arap_energy_grad(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const float* V1,
+                        double* energy_out, double* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "gm_arap_energy_grad";
+  if (Vm <= 0) { set_error("%s: Vm = %d (must be positive)", fn, Vm); return GM_ERR_INVALID_ARG; }
+  if (!row_offsets || !cols || !weights || !V0 || !V1 || !energy_out || !workspace) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  // V0 and V1 are only read and may be one array (the rest pose); every meeting of an output or the workspace with anything is refused
+  const ByteRange rg[5] = {{V0, 12 * (size_t)Vm, "V0", false}, {V1, 12 * (size_t)Vm, "V1", false}, {energy_out, 8, "energy_out", true},
+                           {grad_out, 24 * (size_t)Vm, "grad_out", true}, {workspace, workspace_bytes, "workspace", true}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  const size_t need = gm_arap_energy_workspace_bytes(Vm);
+  if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
+  const ArapEnergyWs k = ArapEnergyWs::from(workspace, (size_t)Vm);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int G = (Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS;
+  hipLaunchKernelGGL(arap_pose_local_kernel, dim3(G), dim3(ARAP_ROW_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, V1, k.R);
+  hipLaunchKernelGGL(arap_energy_grad_kernel, dim3(G), dim3(ARAP_ROW_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, V1, k.R, grad_out, k.slots);
+  hipLaunchKernelGGL(arap_energy_total_kernel, dim3(1), dim3(64), 0, s, k.slots, G, energy_out);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+size_t gm_mesh_smooth_workspace_bytes(int Vm) {
+  SmoothWs k = SmoothWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 1));
+  return (size_t)k.end + 256;
+}
+
+int gm_mesh_smooth_rows(int Vm, const int* row_offsets, const int* cols, const double* weights, const double* g_in, double lambda, int sweeps,
+                        double* out, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "gm_mesh_smooth_rows";
+  if (Vm <= 0) { set_error("%s: Vm = %d (must be positive)", fn, Vm); return GM_ERR_INVALID_ARG; }
+  if (sweeps < 0) { set_error("%s: sweeps = %d (negative)", fn, sweeps); return GM_ERR_INVALID_ARG; }
+  if (!(lambda >= 0.0) || lambda > 1.7976931348623157e308) { set_error("%s: lambda must be finite and not negative", fn); return GM_ERR_INVALID_ARG; }
+  if (!row_offsets || !cols || !weights || !g_in || !out || !workspace) { set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG; }
+  // out == g_in is the in-place call (g_in stands for both); any other meeting of g_in, out and the workspace is refused
+  const ByteRange rg[3] = {{g_in, 24 * (size_t)Vm, "g_in", true}, {out == g_in ? nullptr : out, 24 * (size_t)Vm, "out", true},
+                           {workspace, workspace_bytes, "workspace", true}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  const size_t need = gm_mesh_smooth_workspace_bytes(Vm);
+  if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
+  const SmoothWs k = SmoothWs::from(workspace, (size_t)Vm);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 rows((Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS), threads(ARAP_ROW_THREADS);
+  hipLaunchKernelGGL(smooth_init_kernel, rows, threads, 0, s, Vm, row_offsets, weights, g_in, lambda, k.denom, k.state[0], sweeps == 0 ? out : nullptr);
+  for (int t = 0; t < sweeps; t++)                                   // sweep t reads copy t & 1; the last one writes out
+    hipLaunchKernelGGL(smooth_sweep_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, g_in, k.denom, lambda, k.state[t & 1],
+                       t == sweeps - 1 ? out : k.state[(t + 1) & 1]);
   GM_HIP(hipGetLastError());
   return GM_OK;
 }

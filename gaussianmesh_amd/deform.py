@@ -395,7 +395,8 @@ class SingleObjectDeform:
 
     def fit_pose(self, views, iterations, faces=None, background=None, **fitter_options):
         """Fit the proxy mesh's pose to images: pose_fit.PoseFitter(self, faces, **fitter_options).fit(views, iterations, background) -
-        views a list of (camera, target [3,H,W]) pairs.  Leaves the object deformed to the fitted pose (deform_state) and returns the
+        views a list of (camera, target [3,H,W]) pairs; fitter_options: PoseFitter's lr, rigidity, deg, lambda_dssim, regularizer,
+        smooth_sweeps, smooth_lambda.  Leaves the object deformed to the fitted pose (deform_state) and returns the
         fitter (its .losses, its .pose)."""
         from .pose_fit import PoseFitter
         if faces is not None:

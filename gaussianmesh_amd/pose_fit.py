@@ -147,11 +147,25 @@ class PoseFitter:
     per step whatever the gradient's size, and the one-ring fit of a nearly flat ring takes its normal direction from the ring's sagitta
     alone: neighbours that drift apart by that much along the normal turn the fitted map into a reflection, which state() refuses
     (measured on the 24 x 16 torus, edges of 0.27-0.7, sagitta 0.05: refused after 0.04 of travel at every lr >= 1e-3 and every
-    rigidity tried, NOTEBOOK.md "Pose fitting"; the edge-length term does not see bending).  Small steps, many of them."""
+    rigidity tried, NOTEBOOK.md "Pose fitting"; the edge-length term does not see bending).  Small steps, many of them.
+    Two options against that, both off by default (the defaults are bit for bit the fitter described above):
+    regularizer: "edge" (the edge-length term) or "arap" - rigidity * arap.ArapEnergy(V1), the ARAP energy over its scale, which is 0
+    for a rigid motion and does see bending (gm_arap_energy_grad); ValueError for any other value.
+    smooth_sweeps > 0: between backward() and the optimizer's step V1.grad is replaced by ArapEnergy.smooth_rows(V1.grad, smooth_lambda,
+    smooth_sweeps) - Jacobi sweeps of (I + smooth_lambda L) y = grad, the Sobolev gradient: neighbours are moved together."""
 
-    def __init__(self, obj, faces, lr=None, rigidity=1.0, deg=3, lambda_dssim=0.2):
+    def __init__(self, obj, faces, lr=None, rigidity=1.0, deg=3, lambda_dssim=0.2, regularizer="edge", smooth_sweeps=0, smooth_lambda=1.0):
+        if regularizer not in ("edge", "arap"):
+            raise ValueError('PoseFitter: regularizer must be "edge" or "arap"; got %r' % (regularizer,))
+        if int(smooth_sweeps) < 0 or not float(smooth_lambda) >= 0.0:
+            raise ValueError("PoseFitter: smooth_sweeps and smooth_lambda must not be negative; got %r, %r" % (smooth_sweeps, smooth_lambda))
         self.obj, self.deg, self.rigidity, self.lambda_dssim = obj, int(deg), float(rigidity), float(lambda_dssim)
+        self.regularizer, self.smooth_sweeps, self.smooth_lambda = regularizer, int(smooth_sweeps), float(smooth_lambda)
         self.faces = torch.as_tensor(faces).detach().to(device=obj.vertex.device, dtype=torch.int32).contiguous()
+        self.arap = None                                                      # the mesh's ArapEnergy: only when an option asks for it
+        if regularizer == "arap" or self.smooth_sweeps > 0:
+            from .arap import ArapEnergy
+            self.arap = ArapEnergy(obj.vertex, self.faces, device=obj.vertex.device)
         self.pose = MeshPose(obj.vertex, self.faces)
         start = obj.mesh_vertex_current
         if start is not None:
@@ -180,8 +194,10 @@ class PoseFitter:
         self.optimizer.zero_grad(set_to_none=True)
         loss = photometric_loss(self.render(camera, background), target, self.lambda_dssim)
         if self.rigidity:
-            loss = loss + self.rigidity * self.pose.edge_length_term()
+            loss = loss + self.rigidity * (self.arap(self.pose.V1) if self.regularizer == "arap" else self.pose.edge_length_term())
         loss.backward()
+        if self.smooth_sweeps > 0:
+            self.pose.V1.grad = self.arap.smooth_rows(self.pose.V1.grad, self.smooth_lambda, self.smooth_sweeps)
         self.optimizer.step()
         self.losses.append(loss.detach())
         return self.losses[-1]

@@ -297,6 +297,39 @@ int gm_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, 
                         const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance,
                         float* V_out, double* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The ARAP energy of a pose as a function of the pose alone, and its gradient: a bending-aware rigidity term for an optimiser of the
+ * vertices (arap.ArapEnergy, pose_fit.PoseFitter(regularizer="arap")).  The CSR and V0 of gm_arap_solve; V1 float [Vm,3] the pose, read
+ * as float64.  With e_ij = p_i - p_j:
+ *   E(x) = sum_i sum_j w_ij |(x_i - x_j) - R_i e_ij|^2,  R_i = the local step's rotation of S_i = sum_j w_ij (x_i - x_j) e_ij^T (rank <= 1: I);
+ *   dE/dx_i = 4 sum_j w_ij [ (x_i - x_j) - (R_i + R_j) e_ij / 2 ]  - the R_i minimise E, so this partial derivative at fixed R is the
+ *   total one (it is 4 times the residual of the global step's equation).
+ * A row whose pose edges equal its rest edges bit for bit takes R_i = I exactly, so the rest pose gives E = 0 and a zero gradient
+ * exactly.  A row whose weights sum to 0 adds nothing to E and gets a zero gradient row.
+ * energy_out: one double.  grad_out: double [Vm,3], or NULL when only E is wanted (the same bits of E either way).
+ * Three launches (rotations; rows of the gradient with one energy partial per workgroup of 256 rows; the partials added in index
+ * order), sums in a fixed order and no atomics: two calls on the same input give the same bits.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: Vm <= 0, a NULL among row_offsets, cols, weights, V0, V1, energy_out, workspace,
+ * any overlap of energy_out, grad_out or the workspace with another buffer of the call (V0 and V1 may coincide); with GM_ERR_BUFFER a
+ * workspace below gm_arap_energy_workspace_bytes(Vm) (O(Vm), monotonic).  Column ids are forced into [0, Vm), as in gm_arap_solve.
+ * Stream-ordered, no device allocation, no host synchronisation. */
+size_t gm_arap_energy_workspace_bytes(int Vm);
+int gm_arap_energy_grad(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const float* V1,
+                        double* energy_out, double* grad_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One-ring smoothing of per-vertex rows over the same CSR: `sweeps` Jacobi sweeps of (I + lambda L) y = g started at y = g,
+ *   y_i <- (g_i + lambda sum_j w_ij y_j) / (1 + lambda d_i),  d_i = sum_j w_ij
+ * (the Sobolev gradient of g: each sweep is a convex combination of g_i and the neighbours' values, so max |y| never grows, a constant
+ * field stays constant and a row with d_i = 0 keeps g_i).  g_in, out double [Vm,3]; out may be g_in itself.  sweeps == 0 copies g_in
+ * to out.  One launch per sweep between two copies of the state in the workspace, plus one that forms d_i; no atomics, the same bits
+ * from call to call.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: Vm <= 0, sweeps < 0, a lambda that is negative or not finite, a NULL among
+ * row_offsets, cols, weights, g_in, out, workspace, any overlap among g_in, out and the workspace other than out == g_in; with
+ * GM_ERR_BUFFER a workspace below gm_mesh_smooth_workspace_bytes(Vm) (O(Vm), monotonic).  Stream-ordered, no device allocation, no
+ * host synchronisation. */
+size_t gm_mesh_smooth_workspace_bytes(int Vm);
+int gm_mesh_smooth_rows(int Vm, const int* row_offsets, const int* cols, const double* weights, const double* g_in, double lambda, int sweeps,
+                        double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* First hit of every ray on a mesh: what takes an editor from a pixel to a vertex of the current, deformed proxy mesh
  * (mesh_pick.ray_mesh_hits / pick / visible_vertices).  The reference has no such stage: the result is defined by arithmetic.
  * origins, dirs float [R,3], vertices float [Vm,3], faces int32 [F,3] vertex ids.  out_t float [R], out_face int32 [R], out_uv float
