@@ -1,0 +1,82 @@
+// gm_arap_shared.h -- the two device primitives gm_arap.hip and gm_pose_interp.hip share: the polar rotation of a 3 x 3 matrix and the
+// workgroup sum that leaves the same bits in every thread.  Device code only; both are inlined where they are used.
+#pragma once
+#include "gm_common.h"
+#include "gm_mat3.h"
+
+namespace gm {
+
+#define ARAP_WAVES 16         // waves of the 1024-thread workgroups (arap_global / arap_energy / pi_solve)
+
+// the proper rotation closest to F (max tr(Q^T F)); identity for rank <= 1
+__device__ __forceinline__ void arap_rotation(const double F[3][3], double Q[3][3]) {
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) Q[i][j] = i == j ? 1.0 : 0.0;
+  double C[3][3], E[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) C[i][j] = F[0][i] * F[0][j] + F[1][i] * F[1][j] + F[2][i] * F[2][j];   // F^T F
+  jacobi3(C, E);
+  double FE[3][3], sig[3];                                        // F E and its column lengths: the singular values (never sqrt(lambda))
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int k = 0; k < 3; k++) FE[i][k] = F[i][0] * E[0][k] + F[i][1] * E[1][k] + F[i][2] * E[2][k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) sig[k] = sqrt(FE[0][k] * FE[0][k] + FE[1][k] * FE[1][k] + FE[2][k] * FE[2][k]);
+#pragma unroll
+  for (int pass = 0; pass < 3; pass++) {                          // sig[0] >= sig[1] >= sig[2]
+    const int a = pass == 1 ? 1 : 0, b = a + 1;
+    if (sig[a] < sig[b]) {
+      double t = sig[a]; sig[a] = sig[b]; sig[b] = t;
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        t = FE[i][a]; FE[i][a] = FE[i][b]; FE[i][b] = t;
+        t = E[i][a]; E[i][a] = E[i][b]; E[i][b] = t;
+      }
+    }
+  }
+  if (!(sig[1] > 1e-12 * sig[0])) return;                         // a line or a point (or F = 0, or not finite): no rotation is singled out
+  const double ep[3] = {E[0][0], E[1][0], E[2][0]}, eq[3] = {E[0][1], E[1][1], E[2][1]};
+  double em[3], up[3], uq[3], um[3];
+  cross3(ep, eq, em);                                        // right-handed (ep, eq, em) and (up, uq, um): det Q = +1
+  double dpq = 0.0, lq = 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; i++) { up[i] = FE[i][0] / sig[0]; dpq += up[i] * FE[i][1]; }
+#pragma unroll
+  for (int i = 0; i < 3; i++) { uq[i] = FE[i][1] - dpq * up[i]; lq += uq[i] * uq[i]; }
+  lq = sqrt(lq);
+#pragma unroll
+  for (int i = 0; i < 3; i++) uq[i] /= lq;
+  cross3(up, uq, um);
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) Q[i][j] = up[i] * ep[j] + uq[i] * eq[j] + um[i] * em[j];
+}
+
+// sum of N values over the workgroup of W waves, the same bits in every thread: wave butterfly, W partials in LDS, fixed-order sum.
+// The barrier inside is reached by all threads; `part` must not be the array of the previous call (a slow thread may still read it).
+template <int N, int W = ARAP_WAVES>
+__device__ __forceinline__ void arap_block_sum(double (&v)[N], double (*part)[W]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d);
+    if (lane == 0) part[k][wave] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    double s = part[k][0];
+#pragma unroll
+    for (int w = 1; w < W; w++) s += part[k][w];
+    v[k] = s;
+  }
+}
+
+}  // namespace gm

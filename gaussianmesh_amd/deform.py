@@ -516,6 +516,28 @@ class SingleObjectDeform:
             self.deform_vertices(meshes[-1])
         return meshes
 
+    def interpolate_to(self, target_vertices, inbetweens, faces=None, anchors=None, ease="linear", **between_options):
+        """The meshes from mesh_vertex_current (the rest pose the first time) to target_vertices [Vm,3] with `inbetweens` frames in
+        between, rotation-aware: exactly pose_interp.PoseInterpolator(rest, faces, anchors).sequence([current, target], inbetweens,
+        ease=ease, **between_options), [inbetweens + 2, Vm, 3], then deform_vertices of the target, which leaves the object there (in the
+        manner of drag_sequence).  The interpolator is built on the first call and kept while faces and anchors stay the same.  faces
+        [F,3]: for an object built from tensors alone.  Returns the meshes; no host wait."""
+        from .pose_interp import PoseInterpolator
+        import numpy as np
+        if faces is not None:
+            self._set_faces(faces)
+        if getattr(self, "faces", None) is None:
+            raise ValueError("interpolate_to: this object has no faces; pass faces=[F,3]")
+        ids = None if anchors is None else tuple(np.asarray(anchors.detach().cpu() if torch.is_tensor(anchors) else anchors).reshape(-1).tolist())
+        cached = getattr(self, "_pose_interp", None)
+        if cached is None or cached[0] is not self.faces or cached[1] != ids:
+            cached = self._pose_interp = (self.faces, ids, PoseInterpolator(self.vertex, self.faces, anchors=None if ids is None else list(ids),
+                                                                            device=self.vertex.device))
+        current = self.mesh_vertex_current
+        meshes = cached[2].sequence([self.vertex if current is None else current, target_vertices], inbetweens, ease=ease, **between_options)
+        self.deform_vertices(meshes[-1])
+        return meshes
+
     def _screen_mesh(self, who):
         """(current vertices, faces, check_faces) for the screen-space methods: the face indices are checked on the host the first
         time this face tensor is seen (mesh_pick), afterwards nothing waits for the device."""

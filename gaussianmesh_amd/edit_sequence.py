@@ -3,7 +3,7 @@
     python -m gaussianmesh_amd.edit_sequence (--object_gaussian fg.ply | --object_plain_gaussian cloud.ply) --object_origin_mesh mesh.obj \
         (--mesh_sequence DIR | --handle_sequence FILE.npz | --pick_sequence FILE.json) --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N]
         [--frames_per_launch 4] [--save_maps] [--save_meshes] [--save_baked PATH] [--background_gaussian BG.ply [--is_exist_bg]]
-        [--arap_global_step {column,grid}] [--arap_batch K]
+        [--arap_global_step {column,grid}] [--arap_batch K] [--inbetweens N [--ease {linear,smoothstep}]]
 
 --object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
 faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of the two.
@@ -30,6 +30,11 @@ one workgroup per coordinate) or grid (rows over the whole chip; the same meshes
 frames go in runs of K, and every frame of a run starts from the last frame of the previous run instead of from its own predecessor, so
 the meshes differ a little from K = 1's.  The default 1 is the chain described above, bit for bit.  What K buys and costs: INTEGRATION.md
 section Q.
+--inbetweens N: the frames of --mesh_sequence / --handle_sequence / --pick_sequence become KEY poses, with the rest pose as key 0, and N
+rotation-aware in-betweens are rendered between consecutive keys (pose_interp.PoseInterpolator.sequence: every face's rotation along its
+geodesic, its stretch linearly, one Poisson solve per frame): K source frames give K (N + 1) + 1 frames, the keys among them bit for bit.
+--ease smoothstep spaces the in-betweens of a segment by 3 t^2 - 2 t^3 instead of evenly.  The default 0 changes nothing: the source's
+frames, no rest pose in front.  A face that turns by nearly half a turn between two keys may turn either way: add a key.
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
@@ -122,6 +127,8 @@ def main(argv=None):
     parser.add_argument("--save_meshes", action="store_true", default=False)
     parser.add_argument("--arap_global_step", choices=("column", "grid"), default="column")
     parser.add_argument("--arap_batch", type=int, default=1)
+    parser.add_argument("--inbetweens", type=int, default=0)
+    parser.add_argument("--ease", choices=("linear", "smoothstep"), default="linear")
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
     parser.add_argument("--save_maps", action="store_true", default=False)
@@ -135,6 +142,8 @@ def main(argv=None):
         parser.error("--save_maps: a scene with a background renders no depth / alpha maps; drop --save_maps or the background")
     if not 1 <= args.arap_batch <= ARAP_BATCH_MAX:
         raise SystemExit("edit_sequence: --arap_batch %d: a launch chain carries 1 .. %d frames' solves" % (args.arap_batch, ARAP_BATCH_MAX))
+    if args.inbetweens < 0:
+        raise SystemExit("edit_sequence: --inbetweens %d: the number of frames between two keys, 0 or more" % args.inbetweens)
     if args.pick_sequence is not None:
         pick = read_pick_sequence(args.pick_sequence)
         (pick_camera, pick_handles, pick_anchors, pick_offsets), pick_radii = pick[:4], (pick[4] if len(pick) > 4 else None)
@@ -190,6 +199,14 @@ def main(argv=None):
             solver = tool.gaussians_list[-1].set_handles(handles)
         # enqueued back to back: no host wait between the solves; --arap_batch frames per launch chain
         meshes = list(solver.solve_sequence(positions, batch=args.arap_batch, global_step=args.arap_global_step))
+    if args.inbetweens > 0:                                                           # the frames so far are keys; the rest pose is key 0
+        from .pose_interp import PoseInterpolator
+        obj = tool.gaussians_list[-1]
+        keys = [obj.vertex] + [torch.as_tensor(read_obj(m)[0], dtype=torch.float32, device=obj.vertex.device) if isinstance(m, str) else m for m in meshes]
+        try:
+            meshes = list(PoseInterpolator(obj.vertex, obj.faces, device=obj.vertex.device).sequence(keys, args.inbetweens, ease=args.ease))
+        except ValueError as e:
+            raise SystemExit("edit_sequence: --inbetweens: %s" % e)
     frames = [(cams[args.camera_id] if args.camera_id is not None else cams[i % len(cams)], {args.object_name: m})
               for i, m in enumerate(meshes)]
     os.makedirs(args.render_path, exist_ok=True)

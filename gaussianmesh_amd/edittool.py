@@ -216,6 +216,16 @@ class ObjectVisualTool:
                     g.set_handles(ids)
                 g.drag(handle_positions, **solve_options)
 
+    def interpolate_one_gaussian(self, name, target, inbetweens, **options):
+        """The in-betweens from the current mesh of the objects called `name` to the mesh `target` [Vm,3]
+        (SingleObjectDeform.interpolate_to: rotation-aware, pose_interp.PoseInterpolator); the objects are left at the target.  Returns
+        the meshes [inbetweens + 2, Vm, 3] of the last such object (None if there is none)."""
+        meshes = None
+        for g in self.gaussians_list:
+            if g.get_name() == name:
+                meshes = g.interpolate_to(target, inbetweens, **options)
+        return meshes
+
     def drag_region_one_gaussian(self, name, handle_vertices, displacements, grab_radius, free_radius=None, anchor_vertices=(), **solve_options):
         """drag_one_gaussian with surface regions for handles: on the objects called `name`, everything within grab_radius (along the
         rest mesh) of handle_vertices[i] moves by displacements[i] ([H,3]), everything within grab_radius of an anchor vertex or, with

@@ -330,6 +330,31 @@ size_t gm_mesh_smooth_workspace_bytes(int Vm);
 int gm_mesh_smooth_rows(int Vm, const int* row_offsets, const int* cols, const double* weights, const double* g_in, double lambda, int sweeps,
                         double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The meshes between two key poses A and B of one proxy mesh (pose_interp.PoseInterpolator): T in-betweens in ONE launch chain.
+ * Every face's deformation gradient is interpolated in polar form - the rotation along its geodesic, the stretch linearly - and the
+ * vertices are recovered from one Poisson solve per coordinate and frame over the cotangent Laplacian of gm_arap_solve's CSR
+ * (definition: csrc/gm_pose_interp.hip).  row_offsets / cols / weights: that CSR (arap.edge_csr); V0, A, B
+ * float [Vm,3] (V0, A and B may be one another: a key may be the rest pose); faces int32 [F,3]; vf_offsets int32 [Vm+1], vf_faces int32
+ * [3F]: the faces at every vertex (deform.vertex_face_adjacency); held unsigned char [Vm]: rows with held[i] != 0, and rows whose
+ * weights sum to 0, stay at (1 - t) A_i + t B_i.  C > 0: the rows of component k are comp_rows[comp_offsets[k] .. comp_offsets[k + 1])
+ * (comp_offsets int32 [C+1]), label int32 [Vm] names each vertex's component (or -1), and every component is translated so that its
+ * mean is (1 - t) mean_A + t mean_B; C == 0: the three may be NULL and nothing is translated.  ts double [T] ON THE DEVICE, each in
+ * [0, 1] (the caller's check: it cannot be made here without a read-back).  V_out float [T,Vm,3].  stats (optional) double [T,6]: CG
+ * steps used for x / y / z, final |r| / |b| for x / y / z.  Frame t of V_out and stats is bit for bit what a call with T = 1 and ts[t]
+ * writes; no atomics, the same bits from call to call.  Ids are forced into range (vertex ids into [0, Vm), face ids into [0, F),
+ * labels outside [0, C) mean none); the offset arrays must ascend within their arrays.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: T < 1 or T > GM_POSE_INTERP_BATCH_MAX, Vm < 1, F < 0, C < 0 or C > Vm,
+ * cg_iterations < 1, a cg_tolerance that is negative or not finite, a NULL among the required pointers (faces and vf_faces only when
+ * F > 0), any overlap of V_out, stats or the workspace with one another or with V0, A, B, ts; with GM_ERR_BUFFER a workspace below
+ * gm_pose_interp_workspace_bytes(Vm, F, T) (O(Vm T + F T), monotonic; 0 for arguments that would be refused).  Stream-ordered, no
+ * device allocation, no host synchronisation. */
+#define GM_POSE_INTERP_BATCH_MAX 64
+size_t gm_pose_interp_workspace_bytes(int Vm, int F, int T);
+int gm_pose_interp(int T, int Vm, int F, const int* row_offsets, const int* cols, const double* weights, const float* V0, const int* faces,
+                   const int* vf_offsets, const int* vf_faces, const unsigned char* held, int C, const int* comp_offsets, const int* comp_rows,
+                   const int* label, const float* A, const float* B, const double* ts, int cg_iterations, double cg_tolerance, float* V_out,
+                   double* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* First hit of every ray on a mesh: what takes an editor from a pixel to a vertex of the current, deformed proxy mesh
  * (mesh_pick.ray_mesh_hits / pick / visible_vertices).  The reference has no such stage: the result is defined by arithmetic.
  * origins, dirs float [R,3], vertices float [Vm,3], faces int32 [F,3] vertex ids.  out_t float [R], out_face int32 [R], out_uv float
