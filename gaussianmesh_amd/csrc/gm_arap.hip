@@ -10,6 +10,12 @@
 //     directions only; the two strongest columns S e_k are normalised (the second orthogonalised against the first), the third column
 //     is their cross product and the third direction the cross product of the first two - so det R = +1 by construction and a planar
 //     one-ring (rank-2 S_i) gets its unique rotation.  Second singular value <= 1e-12 of the first (rank <= 1): R_i = I.
+//     WHAT IS GUARANTEED.  S^T S squares the condition number.  With singular values s0 >= s1 >= s2, d = det(U V^T) and
+//     gap = (s1 + d s2) / s0:  gap >= 1e-2: R_i is the SVD's rotation element by element (to eps / gap^2) and loses at most 64 eps s0 of
+//     tr(R^T S_i).  A one-ring whose second singular value is below about 1e-3 of the first (a needle), or a reflected one with
+//     s1 ~ s2: R_i is a proper rotation that maximises tr(R^T S_i) only to within 8 sqrt(eps) s0 = 1.2e-7 s0 - it is NOT element by
+//     element the SVD's rotation; the difference is a turn about the strongest direction (of any angle for s1 < 1e-8 s0) and costs E
+//     at most twice that bar.  tests/polar_route_cases.py, test_gpu_polar_routes.py.
 //   global step: for every free vertex  sum_j w_ij (p'_i - p'_j) = sum_j (w_ij / 2)(R_i + R_j)(p_i - p_j);  rows with fixed[i] != 0
 //     (handles, pinned vertices) and rows whose weights sum to 0 keep their V_init position.
 //   The three coordinate columns are independent systems with one symmetric positive definite matrix (the Laplacian restricted to

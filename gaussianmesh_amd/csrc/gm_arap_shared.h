@@ -8,7 +8,11 @@ namespace gm {
 
 #define ARAP_WAVES 16         // waves of the 1024-thread workgroups (arap_global / arap_energy / pi_solve)
 
-// the proper rotation closest to F (max tr(Q^T F)); identity for rank <= 1
+// the proper rotation closest to F (max tr(Q^T F)); identity for rank <= 1.  Always a proper rotation (to 1e-14).  With singular values
+// s0 >= s1 >= s2 of F and gap = (s1 + sign(det F) s2) / s0:  gap >= 1e-2: the SVD's U diag(1, 1, det) V^T element by element, tr(Q^T F)
+// within 64 eps s0 of its maximum.  Below (a needle: s1 under about 1e-3 s0; a reflection with s1 ~ s2): F^T F has squared the condition
+// number, and Q maximises tr(Q^T F) only to within 8 sqrt(eps) s0 - it is not element by element the SVD's rotation but differs from it
+// by a turn about the strongest direction, which the trace barely sees (an ARAP row's energy: at most twice that bar).
 __device__ __forceinline__ void arap_rotation(const double F[3][3], double Q[3][3]) {
 #pragma unroll
   for (int i = 0; i < 3; i++)

@@ -249,7 +249,10 @@ int gm_closest_face(int N, const float* points, int Vm, const float* vertices, i
  * V_init float [Vm,3] the starting positions, whose held rows already carry their targets; V_out float [Vm,3].
  *   E(P', R) = sum_i sum_j w_ij |(p'_i - p'_j) - R_i (p_i - p_j)|^2.  Per outer iteration, in float64:
  *   local:  S_i = sum_j w_ij (p'_i - p'_j)(p_i - p_j)^T, R_i = U diag(1, 1, det(U V^T)) V^T (S_i = U Sigma V^T); rank <= 1
- *           (second singular value <= 1e-12 of the first): R_i = I;
+ *           (second singular value <= 1e-12 of the first): R_i = I.  R_i is formed from the eigenvectors of S_i^T S_i, which squares
+ *           the condition number: for a one-ring whose second singular value s1 is below about 1e-3 of the first, s0, R_i is that
+ *           maximiser of tr(R^T S_i) only to within 8 sqrt(eps) s0 = 1.2e-7 s0 (64 eps s0 above 1e-2), and NOT element by element the
+ *           SVD's rotation: it differs by a turn about the strongest direction, which costs E at most twice that bar;
  *   global: for every free row sum_j w_ij (p'_i - p'_j) = sum_j (w_ij / 2)(R_i + R_j)(p_i - p_j), the three coordinates separately by
  *           Jacobi-preconditioned conjugate gradients from the current positions, until |r|_2 <= cg_tolerance |b|_2 or cg_iterations
  *           steps; no number of steps raises E.
