@@ -28,6 +28,7 @@
 //   arap_global  3 workgroups of 1024 threads, one per coordinate; a workgroup forms its column of the right-hand side (it needs
 //                the neighbours' R_j: hence a launch boundary after arap_local) and runs the WHOLE PCG of that column, rows strided
 //                over the threads, x / r / p / q in the workspace (L2-resident: 7.5 k rows x 8 B).  No workgroup waits on another.
+//                The step loop behind the right-hand side is arap_pcg_steps (gm_arap_shared.h), which gm_pose_interp.hip runs too.
 //   Dot products: butterfly inside each wave, 16 wave partials in LDS, then EVERY thread adds the 16 in index order - all threads
 //   hold the same bits, so the loop's exit tests are uniform, and the result is the same from run to run (no atomics anywhere).
 //   With stats, arap_energy (one workgroup, same reduction) runs after the local and after the global step; without, E is never formed.
@@ -38,12 +39,13 @@
 // A BATCH (gm_arap_solve_batch) is the second grid dimension of every kernel: workgroup (., b) runs item b - its own V_init / V_out, stats
 //   rows and workspace slab (state columns, R, slots, carry), `slab` doubles from item b - 1's - on the one mesh: CSR, weights, V0, diag
 //   and free_row are shared (item 0's workgroups write the last two, in arap_init).  The single solves are a batch of one, through the
-//   same kernels: an item's bits do not depend on the batch it rides in.  No workgroup reads what another item's wrote.
+//   same kernels, the same workspace carve and the same host loop (arap_chain, with the column launch or the grid launch sequence as
+//   its global step): an item's bits do not depend on the batch it rides in.  No workgroup reads what another item's wrote.
 // THE ENERGY OF A POSE (gm_arap_energy_grad) and ONE-RING SMOOTHING of rows (gm_mesh_smooth_rows) are at the end of the namespace: E as a
 //   function of the pose alone with its gradient, over ceil(Vm / 256) workgroups, and Jacobi sweeps of (I + lambda L) y = g - what an
 //   optimiser of the vertices (pose_fit.py) takes as a rigidity term and as a preconditioner of its gradient.  They share arap_rotation,
-//   arap_block_sum and arap_slot_sum with the solver and none of its kernels.  (arap_rotation and arap_block_sum live in
-//   gm_arap_shared.h: gm_pose_interp.hip uses them too.)
+//   arap_block_sum and arap_slot_sum with the solver and none of its kernels.  (arap_rotation, arap_row_sum, arap_block_sum,
+//   arap_pcg_steps and arap_rel_residual live in gm_arap_shared.h: gm_pose_interp.hip uses them too.)
 // Conventions of gm_closest.hip: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include "gm_common.h"
 #include "gm_check.h"
@@ -55,35 +57,29 @@ namespace gm {
 #define ARAP_THREADS 1024     // arap_global / arap_energy: one workgroup of 16 waves
 #define ARAP_ROW_THREADS 256  // arap_init / arap_local: one thread per vertex
 
+// B items (the single solve: B = 1): per item a slab of `slab` doubles (x, r, p, q, R), then the mesh's own diag and free_row once.  The
+// pointers are item 0's; slab is a multiple of 256 bytes, so every item's arrays are aligned as item 0's.  The slabs come first so
+// that x lies at the workspace's base whatever B (a single solve's arrays are where they were before there was a batch).
 struct ArapWs {
   double* x;       // [3][Vm] positions, one column per coordinate
   double* r;       // [3][Vm]
   double* p;       // [3][Vm]
   double* q;       // [3][Vm]
   double* R;       // [3][Vm][3]: row c of R_i at (c Vm + i) 3
+  size_t slab;
   double* diag;    // [Vm] sum_j w_ij
   int* free_row;   // [Vm] 1 = a row of the linear system
   char* end;
-  static ArapWs from(void* ws, size_t Vm) {
+  static ArapWs from(void* ws, size_t Vm, size_t B) {
     char* p = reinterpret_cast<char*>(ws);
     ArapWs k;
     k.x = carve<double>(p, 3 * Vm); k.r = carve<double>(p, 3 * Vm); k.p = carve<double>(p, 3 * Vm); k.q = carve<double>(p, 3 * Vm);
     k.R = carve<double>(p, 9 * Vm);
+    k.slab = (size_t)(carve<double>(p, 0) - k.x);
+    p = reinterpret_cast<char*>(k.x + B * k.slab);
     k.diag = carve<double>(p, Vm);
     k.free_row = carve<int>(p, Vm);
     k.end = p;
-    return k;
-  }
-  // B items: diag and free_row once, then per item a slab of *slab doubles (x, r, p, q, R); the pointers are item 0's
-  static ArapWs batch(void* ws, size_t Vm, size_t B, size_t* slab) {
-    char* p = reinterpret_cast<char*>(ws);
-    ArapWs k;
-    k.diag = carve<double>(p, Vm);
-    k.free_row = carve<int>(p, Vm);
-    k.x = carve<double>(p, 3 * Vm); k.r = carve<double>(p, 3 * Vm); k.p = carve<double>(p, 3 * Vm); k.q = carve<double>(p, 3 * Vm);
-    k.R = carve<double>(p, 9 * Vm);
-    *slab = (size_t)(carve<double>(p, 0) - k.x);                   // a multiple of 256 bytes: every item's arrays are aligned as item 0's
-    k.end = reinterpret_cast<char*>(k.x + B * *slab);
     return k;
   }
 };
@@ -105,10 +101,9 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_init_kernel(int Vm, con
 #pragma unroll
   for (int c = 0; c < 3; c++) x[(size_t)c * Vm + i] = (double)v[c];
   if (blockIdx.y) return;                                          // the mesh's own words have one writer: item 0
-  double d = 0.0;
-  for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) d += weights[k];
-  diag[i] = d;
-  free_row[i] = (fixed[i] == 0 && d > 0.0) ? 1 : 0;
+  const ArapRowSum row = arap_row_sum(row_offsets, weights, fixed, i);
+  diag[i] = row.d;
+  free_row[i] = row.free_row;
 }
 
 __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
@@ -172,8 +167,9 @@ __global__ __launch_bounds__(ARAP_THREADS) void arap_energy_kernel(int Vm, const
   if (threadIdx.x == 0) *out = acc[0];
 }
 
-// workgroup (c, b): column c of item b's right-hand side, then the whole PCG of that column.  Every test that leaves a loop holding a
-// barrier is made on sums that arap_block_sum left identical in all threads.
+// workgroup (c, b): column c of item b's right-hand side, r and p with it in the one edge loop, then the whole PCG of that column
+// (arap_pcg_steps)
+static_assert(ARAP_THREADS == ARAP_WAVES * 64, "arap_global_kernel strides its rows as arap_pcg_steps does");
 __global__ __launch_bounds__(ARAP_THREADS) void arap_global_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
                                                                    const double* __restrict__ weights, const float* __restrict__ V0,
                                                                    const double* __restrict__ Rall, const double* __restrict__ diag,
@@ -213,64 +209,12 @@ __global__ __launch_bounds__(ARAP_THREADS) void arap_global_kernel(int Vm, const
     }
     r[i] = ri; p[i] = zi;                                          // held rows: r = p = 0, for the whole solve
   }
-  arap_block_sum<3>(s3, partB);                                    // (its barrier also publishes p)
-  const double bb = s3[0];
-  double rr = s3[1], rz = s3[2];
-  int used = 0;
-  for (int it = 0; it < cg_iterations; it++) {
-    if (!(rr > tol2 * bb)) break;                                  // converged (or not finite): uniform
-    double s1[1] = {0.0};
-    for (int i = threadIdx.x; i < Vm; i += ARAP_THREADS) {
-      if (!free_row[i]) continue;
-      const double pi = p[i];
-      double qi = 0.0;
-      for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) qi += weights[k] * (pi - p[clamp_index(cols[k], Vm)]);
-      q[i] = qi;
-      s1[0] += pi * qi;
-    }
-    arap_block_sum<1>(s1, partA);
-    if (!(s1[0] > 0.0)) break;                                     // p = 0: nothing left to do; uniform
-    const double alpha = rz / s1[0];
-    double s2[2] = {0.0, 0.0};                                     // |r|^2, r . z
-    for (int i = threadIdx.x; i < Vm; i += ARAP_THREADS) {
-      if (!free_row[i]) continue;
-      x[i] += alpha * p[i];
-      const double ri = r[i] - alpha * q[i];
-      r[i] = ri;
-      s2[0] += ri * ri; s2[1] += ri * (ri / diag[i]);
-    }
-    arap_block_sum<2>(s2, partB);
-    rr = s2[0];
-    const double beta = s2[1] / rz;
-    rz = s2[1];
-    for (int i = threadIdx.x; i < Vm; i += ARAP_THREADS)
-      if (free_row[i]) p[i] = r[i] / diag[i] + beta * p[i];
-    used = it + 1;
-    __syncthreads();                                               // p complete before the next product reads the neighbours'
-  }
+  const ArapPcgResult cg = arap_pcg_steps(Vm, row_offsets, cols, weights, diag, free_row, x, r, p, q, cg_iterations, tol2, s3, partA, partB);
   if (V_out)                                                       // the last outer iteration: each thread reads back its own rows
     for (int i = threadIdx.x; i < Vm; i += ARAP_THREADS) V_out[3 * (size_t)i + c] = (float)x[i];
   if (stats_row && threadIdx.x == 0) {
-    stats_row[2 + c] = (double)used;
-    stats_row[5 + c] = bb > 0.0 ? sqrt(rr / bb) : (rr > 0.0 ? (double)INFINITY : 0.0);
-  }
-}
-
-// the launch chain of the column step over B items: B = 1 (slab unused) is the single solve
-static void arap_column_chain(int B, size_t slab, const ArapWs& k, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
-                              const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
-                              double* stats, hipStream_t s) {
-  const dim3 rows((Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS, B);
-  const size_t stride = 8 * (size_t)outer_iterations;              // doubles between two items' stats
-  hipLaunchKernelGGL(arap_init_kernel, rows, dim3(ARAP_ROW_THREADS), 0, s, Vm, row_offsets, weights, fixed, V_init, V_out, k.x, k.diag, k.free_row,
-                     outer_iterations == 0 ? 1 : 0, slab);
-  for (int it = 0; it < outer_iterations; it++) {
-    double* row = stats ? stats + 8 * (size_t)it : nullptr;
-    hipLaunchKernelGGL(arap_local_kernel, rows, dim3(ARAP_ROW_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, slab);
-    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row, slab, stride);
-    hipLaunchKernelGGL(arap_global_kernel, dim3(3, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.diag, k.free_row, k.x, k.r,
-                       k.p, k.q, cg_iterations, cg_tolerance * cg_tolerance, it == outer_iterations - 1 ? V_out : nullptr, row, slab, stride);
-    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row + 1, slab, stride);
+    stats_row[2 + c] = (double)cg.used;
+    stats_row[5 + c] = arap_rel_residual(cg.bb, cg.rr);
   }
 }
 
@@ -293,46 +237,32 @@ static void arap_column_chain(int B, size_t slab, const ArapWs& k, int Vm, const
 #define ARAP_EDGE_BATCH 8     // arap_grid_product: edges of a row in flight together (a closed triangle mesh has 6 per vertex on average)
 #define ARAP_CARRY 6          // per coordinate: alpha and gamma of the previous step, |b|^2, |r|^2, steps used, stopped (0 / 1)
 
+// B items, as ArapWs: per item a slab (the six state columns, R, both slot arrays, the carry pair), then diag and free_row once
 struct ArapGridWs {
   double *x, *r, *u, *w, *p, *s;   // [3][Vm] each
   double* R;                       // [3][Vm][3]
-  double* diag;                    // [Vm]
   double* bb_slots;                // [3][G]
   double* slots;                   // [3 quantities][3][G]
   double* carry;                   // [2][3][ARAP_CARRY]
+  size_t slab;
+  double* diag;                    // [Vm]
   int* free_row;                   // [Vm]
   char* end;
-  static ArapGridWs from(void* ws, size_t Vm) {
+  static ArapGridWs from(void* ws, size_t Vm, size_t B) {
     char* p = reinterpret_cast<char*>(ws);
     const size_t G = (Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS;
     ArapGridWs k;
     k.x = carve<double>(p, 3 * Vm); k.r = carve<double>(p, 3 * Vm); k.u = carve<double>(p, 3 * Vm);
     k.w = carve<double>(p, 3 * Vm); k.p = carve<double>(p, 3 * Vm); k.s = carve<double>(p, 3 * Vm);
     k.R = carve<double>(p, 9 * Vm);
-    k.diag = carve<double>(p, Vm);
     k.bb_slots = carve<double>(p, 3 * G);
     k.slots = carve<double>(p, 9 * G);
     k.carry = carve<double>(p, 2 * 3 * ARAP_CARRY);
+    k.slab = (size_t)(carve<double>(p, 0) - k.x);
+    p = reinterpret_cast<char*>(k.x + B * k.slab);
+    k.diag = carve<double>(p, Vm);
     k.free_row = carve<int>(p, Vm);
     k.end = p;
-    return k;
-  }
-  // B items: diag and free_row once, then per item a slab of *slab doubles (the six state columns, R, both slot arrays, the carry
-  // pair); the pointers are item 0's
-  static ArapGridWs batch(void* ws, size_t Vm, size_t B, size_t* slab) {
-    char* p = reinterpret_cast<char*>(ws);
-    const size_t G = (Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS;
-    ArapGridWs k;
-    k.diag = carve<double>(p, Vm);
-    k.free_row = carve<int>(p, Vm);
-    k.x = carve<double>(p, 3 * Vm); k.r = carve<double>(p, 3 * Vm); k.u = carve<double>(p, 3 * Vm);
-    k.w = carve<double>(p, 3 * Vm); k.p = carve<double>(p, 3 * Vm); k.s = carve<double>(p, 3 * Vm);
-    k.R = carve<double>(p, 9 * Vm);
-    k.bb_slots = carve<double>(p, 3 * G);
-    k.slots = carve<double>(p, 9 * G);
-    k.carry = carve<double>(p, 2 * 3 * ARAP_CARRY);
-    *slab = (size_t)(carve<double>(p, 0) - k.x);
-    k.end = reinterpret_cast<char*>(k.x + B * *slab);
     return k;
   }
 };
@@ -535,7 +465,7 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_update_kernel(int 
       if (stats_row) {
         const double bb = st[c][2], rr = st[c][3];
         stats_row[2 + c] = st[c][4];
-        stats_row[5 + c] = bb > 0.0 ? sqrt(rr / bb) : (rr > 0.0 ? (double)INFINITY : 0.0);
+        stats_row[5 + c] = arap_rel_residual(bb, rr);
       }
     }
   }
@@ -552,38 +482,6 @@ __global__ __launch_bounds__(ARAP_ROW_THREADS) void arap_grid_update_kernel(int 
       p[o] = pc; s[o] = sc; x[o] = xv; r[o] = rv; u[o] = rv / d;
     }
     if (V_out) V_out[3 * (size_t)i + c] = (float)xv;
-  }
-}
-
-// the launch chain of the grid step over B items: B = 1 (slab unused) is the single solve
-static void arap_grid_chain(int B, size_t slab, const ArapGridWs& k, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
-                            const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
-                            double* stats, hipStream_t s) {
-  const dim3 rows((Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS, B), threads(ARAP_ROW_THREADS);
-  const double tol2 = cg_tolerance * cg_tolerance;
-  const size_t stride = 8 * (size_t)outer_iterations;              // doubles between two items' stats
-  hipLaunchKernelGGL(arap_init_kernel, rows, threads, 0, s, Vm, row_offsets, weights, fixed, V_init, V_out, k.x, k.diag, k.free_row,
-                     outer_iterations == 0 ? 1 : 0, slab);
-  for (int it = 0; it < outer_iterations; it++) {
-    double* row = stats ? stats + 8 * (size_t)it : nullptr;
-    float* out = it == outer_iterations - 1 ? V_out : nullptr;
-    hipLaunchKernelGGL(arap_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, slab);
-    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row, slab, stride);
-    hipLaunchKernelGGL(arap_grid_rhs_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.diag, k.free_row, k.x, k.r, k.u, k.bb_slots, slab);
-    // steps 0 .. cg_iterations - 1 update; the pair behind them only forms the final |r|^2, which nothing but stats reads
-    // (Unlike the column step, whose loop leaves on the device, a cap costs 2 * cg_iterations host launches per outer iteration whether
-    // or not the solve stops early: a cap far above the steps needed is paid for.  64-bit, so that cap + 1 cannot overflow.)
-    const long long pairs = (long long)cg_iterations + (row ? 1 : 0);
-    for (long long step = 0; step < pairs; step++) {
-      const double* carry_in = k.carry + (step & 1) * 3 * ARAP_CARRY;
-      double* carry_out = k.carry + ((step + 1) & 1) * 3 * ARAP_CARRY;
-      const int last = step == cg_iterations;
-      hipLaunchKernelGGL(arap_grid_product_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, k.free_row, k.r, k.u, k.w, step ? carry_in : nullptr,
-                         k.slots, slab);
-      hipLaunchKernelGGL(arap_grid_update_kernel, rows, threads, 0, s, Vm, k.diag, k.free_row, k.x, k.r, k.u, k.w, k.p, k.s, k.bb_slots, k.slots, carry_in,
-                         carry_out, step == 0 ? 1 : 0, last, tol2, step == pairs - 1 ? out : nullptr, last ? row : nullptr, slab, stride);
-    }
-    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row + 1, slab, stride);
   }
 }
 
@@ -816,47 +714,94 @@ static int arap_args_checked(const char* fn, int B, int Vm, const int* row_offse
   return GM_OK;
 }
 
+// the launch chain of a solve over B items: init, then per outer iteration local, [energy], the global step, [energy] (the energies
+// only with stats).  global_step(out, row, stride) enqueues one global step on k's state: out is V_out in the last outer iteration and
+// null before, row the iteration's stats row or null, stride the doubles between two items' stats.
+template <class Ws, class GlobalStep>
+static void arap_chain(int B, const Ws& k, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
+                       const float* V_init, int outer_iterations, float* V_out, double* stats, hipStream_t s, GlobalStep global_step) {
+  const dim3 rows((Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS, B), threads(ARAP_ROW_THREADS);
+  const size_t stride = 8 * (size_t)outer_iterations;
+  hipLaunchKernelGGL(arap_init_kernel, rows, threads, 0, s, Vm, row_offsets, weights, fixed, V_init, V_out, k.x, k.diag, k.free_row,
+                     outer_iterations == 0 ? 1 : 0, k.slab);
+  for (int it = 0; it < outer_iterations; it++) {
+    double* row = stats ? stats + 8 * (size_t)it : nullptr;
+    hipLaunchKernelGGL(arap_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, k.slab);
+    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row, k.slab, stride);
+    global_step(it == outer_iterations - 1 ? V_out : nullptr, row, stride);
+    if (row) hipLaunchKernelGGL(arap_energy_kernel, dim3(1, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R, row + 1, k.slab, stride);
+  }
+}
+
+static size_t arap_workspace_bytes(int Vm, int B, int global_step) {
+  if (Vm < 1) Vm = 1;                                              // the public sizes are defined for every Vm; a solve refuses Vm <= 0
+  return (size_t)(global_step ? ArapGridWs::from(nullptr, (size_t)Vm, (size_t)B).end : ArapWs::from(nullptr, (size_t)Vm, (size_t)B).end) + 256;
+}
+
+// gm_arap_solve, gm_arap_solve_grid (B = 1) and gm_arap_solve_batch behind their own refusals: the shared ones, then the chain with the
+// column step (global_step 0) or the grid step (1)
+static int arap_solve(const char* fn, int B, int global_step, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                      const unsigned char* fixed, const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out,
+                      double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = arap_args_checked(fn, B, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats,
+                                 workspace, workspace_bytes, arap_workspace_bytes(Vm, B, global_step)))
+    return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const double tol2 = cg_tolerance * cg_tolerance;
+  if (global_step) {
+    const ArapGridWs k = ArapGridWs::from(workspace, (size_t)Vm, (size_t)B);
+    const dim3 rows((Vm + ARAP_ROW_THREADS - 1) / ARAP_ROW_THREADS, B), threads(ARAP_ROW_THREADS);
+    arap_chain(B, k, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, V_out, stats, s, [&](float* out, double* row, size_t stride) {
+      hipLaunchKernelGGL(arap_grid_rhs_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.diag, k.free_row, k.x, k.r, k.u, k.bb_slots, k.slab);
+      // steps 0 .. cg_iterations - 1 update; the pair behind them only forms the final |r|^2, which nothing but stats reads
+      // (Unlike the column step, whose loop leaves on the device, a cap costs 2 * cg_iterations host launches per outer iteration whether
+      // or not the solve stops early: a cap far above the steps needed is paid for.  64-bit, so that cap + 1 cannot overflow.)
+      const long long pairs = (long long)cg_iterations + (row ? 1 : 0);
+      for (long long step = 0; step < pairs; step++) {
+        const double* carry_in = k.carry + (step & 1) * 3 * ARAP_CARRY;
+        double* carry_out = k.carry + ((step + 1) & 1) * 3 * ARAP_CARRY;
+        const int last = step == cg_iterations;
+        hipLaunchKernelGGL(arap_grid_product_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, k.free_row, k.r, k.u, k.w, step ? carry_in : nullptr,
+                           k.slots, k.slab);
+        hipLaunchKernelGGL(arap_grid_update_kernel, rows, threads, 0, s, Vm, k.diag, k.free_row, k.x, k.r, k.u, k.w, k.p, k.s, k.bb_slots, k.slots, carry_in,
+                           carry_out, step == 0 ? 1 : 0, last, tol2, step == pairs - 1 ? out : nullptr, last ? row : nullptr, k.slab, stride);
+      }
+    });
+  } else {
+    const ArapWs k = ArapWs::from(workspace, (size_t)Vm, (size_t)B);
+    arap_chain(B, k, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, V_out, stats, s, [&](float* out, double* row, size_t stride) {
+      hipLaunchKernelGGL(arap_global_kernel, dim3(3, B), dim3(ARAP_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.diag, k.free_row, k.x, k.r,
+                         k.p, k.q, cg_iterations, tol2, out, row, k.slab, stride);
+    });
+  }
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
 extern "C" {
 
-size_t gm_arap_workspace_bytes(int Vm) {
-  ArapWs k = ArapWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 1));
-  return (size_t)k.end + 256;
-}
+size_t gm_arap_workspace_bytes(int Vm) { return arap_workspace_bytes(Vm, 1, 0); }
 
 int gm_arap_solve(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
                   const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
                   void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = arap_args_checked("gm_arap_solve", 1, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out,
-                                 stats, workspace, workspace_bytes, gm_arap_workspace_bytes(Vm)))
-    return rc;
-  arap_column_chain(1, 0, ArapWs::from(workspace, (size_t)Vm), Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations,
-                    cg_tolerance, V_out, stats, reinterpret_cast<hipStream_t>(stream));
-  GM_HIP(hipGetLastError());
-  return GM_OK;
+  return arap_solve("gm_arap_solve", 1, 0, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats,
+                    workspace, workspace_bytes, stream);
 }
 
-size_t gm_arap_grid_workspace_bytes(int Vm) {
-  ArapGridWs k = ArapGridWs::from(nullptr, (size_t)(Vm > 0 ? Vm : 1));
-  return (size_t)k.end + 256;
-}
+size_t gm_arap_grid_workspace_bytes(int Vm) { return arap_workspace_bytes(Vm, 1, 1); }
 
 int gm_arap_solve_grid(int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const unsigned char* fixed,
                        const float* V_init, int outer_iterations, int cg_iterations, double cg_tolerance, float* V_out, double* stats,
                        void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = arap_args_checked("gm_arap_solve_grid", 1, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance,
-                                 V_out, stats, workspace, workspace_bytes, gm_arap_grid_workspace_bytes(Vm)))
-    return rc;
-  arap_grid_chain(1, 0, ArapGridWs::from(workspace, (size_t)Vm), Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations,
-                  cg_tolerance, V_out, stats, reinterpret_cast<hipStream_t>(stream));
-  GM_HIP(hipGetLastError());
-  return GM_OK;
+  return arap_solve("gm_arap_solve_grid", 1, 1, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out,
+                    stats, workspace, workspace_bytes, stream);
 }
 
-// ---- B solves in one chain (gm_arap_solve_batch): the chains above with the batch as the second grid dimension ----
+// ---- B solves in one chain (gm_arap_solve_batch): the batch is the second grid dimension of every kernel ----
 size_t gm_arap_batch_workspace_bytes(int Vm, int B, int global_step) {
   if (Vm <= 0 || B < 1 || B > GM_ARAP_BATCH_MAX || (global_step != 0 && global_step != 1)) return 0;
-  size_t slab;
-  return (size_t)(global_step ? ArapGridWs::batch(nullptr, (size_t)Vm, (size_t)B, &slab).end : ArapWs::batch(nullptr, (size_t)Vm, (size_t)B, &slab).end) + 256;
+  return arap_workspace_bytes(Vm, B, global_step);
 }
 
 int gm_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
@@ -865,20 +810,8 @@ int gm_arap_solve_batch(int B, int global_step, int Vm, const int* row_offsets, 
   const char* fn = "gm_arap_solve_batch";
   if (B < 1 || B > GM_ARAP_BATCH_MAX) { set_error("%s: B = %d (1 .. %d)", fn, B, GM_ARAP_BATCH_MAX); return GM_ERR_INVALID_ARG; }
   if (global_step != 0 && global_step != 1) { set_error("%s: global_step = %d (0 column, 1 grid)", fn, global_step); return GM_ERR_INVALID_ARG; }
-  if (int rc = arap_args_checked(fn, B, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats,
-                                 workspace, workspace_bytes, gm_arap_batch_workspace_bytes(Vm, B, global_step)))
-    return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  size_t slab;
-  if (global_step) {
-    const ArapGridWs k = ArapGridWs::batch(workspace, (size_t)Vm, (size_t)B, &slab);
-    arap_grid_chain(B, slab, k, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats, s);
-  } else {
-    const ArapWs k = ArapWs::batch(workspace, (size_t)Vm, (size_t)B, &slab);
-    arap_column_chain(B, slab, k, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats, s);
-  }
-  GM_HIP(hipGetLastError());
-  return GM_OK;
+  return arap_solve(fn, B, global_step, Vm, row_offsets, cols, weights, V0, fixed, V_init, outer_iterations, cg_iterations, cg_tolerance, V_out, stats,
+                    workspace, workspace_bytes, stream);
 }
 
 // ---- E(x) and dE/dx of a pose (gm_arap_energy_grad), one-ring smoothing of rows (gm_mesh_smooth_rows) ----

@@ -1,5 +1,6 @@
-// gm_arap_shared.h -- the two device primitives gm_arap.hip and gm_pose_interp.hip share: the polar rotation of a 3 x 3 matrix and the
-// workgroup sum that leaves the same bits in every thread.  Device code only; both are inlined where they are used.
+// gm_arap_shared.h -- the device primitives gm_arap.hip and gm_pose_interp.hip share: the polar rotation of a 3 x 3 matrix, the sum of a
+// CSR row's weights, the workgroup sum that leaves the same bits in every thread, and on top of it the step loop of the one-workgroup
+// column PCG (arap_global_kernel, pi_solve_kernel).  Device code only; all are inlined where they are used.
 #pragma once
 #include "gm_common.h"
 #include "gm_mat3.h"
@@ -62,6 +63,20 @@ __device__ __forceinline__ void arap_rotation(const double F[3][3], double Q[3][
     for (int j = 0; j < 3; j++) Q[i][j] = up[i] * ep[j] + uq[i] * eq[j] + um[i] * em[j];
 }
 
+// d_i = sum_j w_ij of CSR row i, and whether the row is an unknown of the linear systems: not held and d_i > 0
+struct ArapRowSum { double d; int free_row; };
+__device__ __forceinline__ ArapRowSum arap_row_sum(const int* __restrict__ row_offsets, const double* __restrict__ weights,
+                                                   const unsigned char* __restrict__ held, int i) {
+  double d = 0.0;
+  for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) d += weights[k];
+  return {d, (held[i] == 0 && d > 0.0) ? 1 : 0};
+}
+
+// |r| / |b| as the stats rows report it
+__device__ __forceinline__ double arap_rel_residual(double bb, double rr) {
+  return bb > 0.0 ? sqrt(rr / bb) : (rr > 0.0 ? (double)INFINITY : 0.0);
+}
+
 // sum of N values over the workgroup of W waves, the same bits in every thread: wave butterfly, W partials in LDS, fixed-order sum.
 // The barrier inside is reached by all threads; `part` must not be the array of the previous call (a slow thread may still read it).
 template <int N, int W = ARAP_WAVES>
@@ -81,6 +96,56 @@ __device__ __forceinline__ void arap_block_sum(double (&v)[N], double (*part)[W]
     for (int w = 1; w < W; w++) s += part[k][w];
     v[k] = s;
   }
+}
+
+// The Jacobi-preconditioned CG of one column (x, r, p, q: [Vm]) by one workgroup of ARAP_WAVES waves, rows strided over the threads.  The
+// caller has written r = b - L x and p = r / diag (0 in held rows, for the whole solve) and holds this thread's share of |b|^2, |r|^2,
+// r . z in s3; partA and partB are two LDS arrays of its own.  Stops at |r|^2 <= tol2 |b|^2, at p . A p <= 0 or after cg_iterations
+// steps.  Every test that leaves the loop, which holds barriers, is made on sums that arap_block_sum left identical in all threads.
+// Returns bb = |b|^2, rr = the last |r|^2, used = steps taken.
+struct ArapPcgResult { double bb, rr; int used; };
+__device__ __forceinline__ ArapPcgResult arap_pcg_steps(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                        const double* __restrict__ weights, const double* __restrict__ diag,
+                                                        const int* __restrict__ free_row, double* x, double* r, double* p, double* q,
+                                                        int cg_iterations, double tol2, double (&s3)[3], double (*partA)[ARAP_WAVES],
+                                                        double (*partB)[ARAP_WAVES]) {
+  constexpr int THREADS = ARAP_WAVES * 64;
+  arap_block_sum<3>(s3, partB);                                    // (its barrier also publishes p)
+  const double bb = s3[0];
+  double rr = s3[1], rz = s3[2];
+  int used = 0;
+  for (int it = 0; it < cg_iterations; it++) {
+    if (!(rr > tol2 * bb)) break;                                  // converged (or not finite): uniform
+    double s1[1] = {0.0};
+    for (int i = threadIdx.x; i < Vm; i += THREADS) {
+      if (!free_row[i]) continue;
+      const double pi = p[i];
+      double qi = 0.0;
+      for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) qi += weights[k] * (pi - p[clamp_index(cols[k], Vm)]);
+      q[i] = qi;
+      s1[0] += pi * qi;
+    }
+    arap_block_sum<1>(s1, partA);
+    if (!(s1[0] > 0.0)) break;                                     // p = 0: nothing left to do; uniform
+    const double alpha = rz / s1[0];
+    double s2[2] = {0.0, 0.0};                                     // |r|^2, r . z
+    for (int i = threadIdx.x; i < Vm; i += THREADS) {
+      if (!free_row[i]) continue;
+      x[i] += alpha * p[i];
+      const double ri = r[i] - alpha * q[i];
+      r[i] = ri;
+      s2[0] += ri * ri; s2[1] += ri * (ri / diag[i]);
+    }
+    arap_block_sum<2>(s2, partB);
+    rr = s2[0];
+    const double beta = s2[1] / rz;
+    rz = s2[1];
+    for (int i = threadIdx.x; i < Vm; i += THREADS)
+      if (free_row[i]) p[i] = r[i] / diag[i] + beta * p[i];
+    used = it + 1;
+    __syncthreads();                                               // p complete before the next product reads the neighbours'
+  }
+  return {bb, rr, used};
 }
 
 }  // namespace gm

@@ -31,8 +31,8 @@
 //   pi_rhs        one thread per (vertex, frame): gathers the vertex's faces through the vertex -> face CSR (deform.vertex_face_adjacency)
 //                 into the three right-hand-side entries, writes the warm start; frame 0's threads write diag and free_row.
 //   pi_solve      grid (3, T) of 1024 threads: workgroup (c, t) runs the WHOLE PCG of coordinate c of frame t, rows strided over the
-//                 threads, no launch per step; dot products through arap_block_sum, so every exit test is uniform (arap_global_kernel's
-//                 scheme).  No workgroup waits on another.
+//                 threads, no launch per step.  The step loop is arap_pcg_steps (gm_arap_shared.h), the one arap_global_kernel runs:
+//                 dot products through arap_block_sum, so every exit test is uniform.  No workgroup waits on another.
 //   pi_shift      one workgroup per (component, frame): the component's sums of x, A and B in a fixed order, the translation.
 //   pi_finish     one thread per (vertex, frame): adds the translation of the vertex's component, rounds, writes V_out.
 // A frame reads nothing another frame wrote and every sum has one fixed order: a frame's bits do not depend on the batch it rides in,
@@ -283,14 +283,13 @@ __global__ __launch_bounds__(PI_ROW_THREADS) void pi_rhs_kernel(int Vm, int F, c
     bcol[(size_t)c * Vm + i] = rhs[c];
   }
   if (blockIdx.y) return;                                          // the mesh's own words have one writer: frame 0
-  double d = 0.0;
-  for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) d += weights[k];
-  diag[i] = d;
-  free_row[i] = (held[i] == 0 && d > 0.0) ? 1 : 0;
+  const ArapRowSum row = arap_row_sum(row_offsets, weights, held, i);
+  diag[i] = row.d;
+  free_row[i] = row.free_row;
 }
 
-// workgroup (c, t): the whole PCG of coordinate c of frame t.  Every test that leaves a loop holding a barrier is made on sums that
-// arap_block_sum left identical in all threads.
+// workgroup (c, t): the whole PCG of coordinate c of frame t: r, p and the first sums from the stored b, then arap_pcg_steps
+static_assert(PI_THREADS == ARAP_WAVES * 64, "pi_solve_kernel strides its rows as arap_pcg_steps does");
 __global__ __launch_bounds__(PI_THREADS) void pi_solve_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
                                                               const double* __restrict__ weights, const double* __restrict__ diag,
                                                               const int* __restrict__ free_row, double* xall, int cg_iterations, double tol2,
@@ -319,45 +318,11 @@ __global__ __launch_bounds__(PI_THREADS) void pi_solve_kernel(int Vm, const int*
     }
     r[i] = ri; p[i] = zi;                                          // held rows: r = p = 0, for the whole solve
   }
-  arap_block_sum<3>(s3, partB);                                    // (its barrier also publishes p)
-  const double bb = s3[0];
-  double rr = s3[1], rz = s3[2];
-  int used = 0;
-  for (int it = 0; it < cg_iterations; it++) {
-    if (!(rr > tol2 * bb)) break;                                  // converged (or not finite): uniform
-    double s1[1] = {0.0};
-    for (int i = threadIdx.x; i < Vm; i += PI_THREADS) {
-      if (!free_row[i]) continue;
-      const double pi = p[i];
-      double qi = 0.0;
-      for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) qi += weights[k] * (pi - p[clamp_index(cols[k], Vm)]);
-      q[i] = qi;
-      s1[0] += pi * qi;
-    }
-    arap_block_sum<1>(s1, partA);
-    if (!(s1[0] > 0.0)) break;                                     // p = 0: nothing left to do; uniform
-    const double alpha = rz / s1[0];
-    double s2[2] = {0.0, 0.0};                                     // |r|^2, r . z
-    for (int i = threadIdx.x; i < Vm; i += PI_THREADS) {
-      if (!free_row[i]) continue;
-      x[i] += alpha * p[i];
-      const double ri = r[i] - alpha * q[i];
-      r[i] = ri;
-      s2[0] += ri * ri; s2[1] += ri * (ri / diag[i]);
-    }
-    arap_block_sum<2>(s2, partB);
-    rr = s2[0];
-    const double beta = s2[1] / rz;
-    rz = s2[1];
-    for (int i = threadIdx.x; i < Vm; i += PI_THREADS)
-      if (free_row[i]) p[i] = r[i] / diag[i] + beta * p[i];
-    used = it + 1;
-    __syncthreads();                                               // p complete before the next product reads the neighbours'
-  }
+  const ArapPcgResult cg = arap_pcg_steps(Vm, row_offsets, cols, weights, diag, free_row, x, r, p, q, cg_iterations, tol2, s3, partA, partB);
   if (stats && threadIdx.x == 0) {
     double* row = stats + 6 * (size_t)blockIdx.y;
-    row[c] = (double)used;
-    row[3 + c] = bb > 0.0 ? sqrt(rr / bb) : (rr > 0.0 ? (double)INFINITY : 0.0);
+    row[c] = (double)cg.used;
+    row[3 + c] = arap_rel_residual(cg.bb, cg.rr);
   }
 }
 
