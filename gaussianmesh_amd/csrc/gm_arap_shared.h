@@ -1,6 +1,7 @@
-// gm_arap_shared.h -- the device primitives gm_arap.hip and gm_pose_interp.hip share: the polar rotation of a 3 x 3 matrix, the sum of a
-// CSR row's weights, the workgroup sum that leaves the same bits in every thread, and on top of it the step loop of the one-workgroup
-// column PCG (arap_global_kernel, pi_solve_kernel).  Device code only; all are inlined where they are used.
+// gm_arap_shared.h -- the device primitives gm_arap.hip, gm_pose_interp.hip and gm_dynamics.hip share: the polar rotation of a 3 x 3
+// matrix, the sum of a CSR row's weights, the workgroup sum that leaves the same bits in every thread, and on top of it the step loop of
+// the one-workgroup column PCG (arap_global_kernel, pi_solve_kernel, dyn_global_kernel).  Device code only; all are inlined where they are
+// used.
 #pragma once
 #include "gm_common.h"
 #include "gm_mat3.h"
@@ -103,12 +104,15 @@ __device__ __forceinline__ void arap_block_sum(double (&v)[N], double (*part)[W]
 // r . z in s3; partA and partB are two LDS arrays of its own.  Stops at |r|^2 <= tol2 |b|^2, at p . A p <= 0 or after cg_iterations
 // steps.  Every test that leaves the loop, which holds barriers, is made on sums that arap_block_sum left identical in all threads.
 // Returns bb = |b|^2, rr = the last |r|^2, used = steps taken.
+// SHIFTED: the operator is diag(shift) + L (gm_dynamics.hip: the mass term of an implicit step), and diag is then its diagonal,
+// shift_i + d_i; the default is the plain Laplacian, and shift is not read.
 struct ArapPcgResult { double bb, rr; int used; };
+template <bool SHIFTED = false>
 __device__ __forceinline__ ArapPcgResult arap_pcg_steps(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
                                                         const double* __restrict__ weights, const double* __restrict__ diag,
                                                         const int* __restrict__ free_row, double* x, double* r, double* p, double* q,
                                                         int cg_iterations, double tol2, double (&s3)[3], double (*partA)[ARAP_WAVES],
-                                                        double (*partB)[ARAP_WAVES]) {
+                                                        double (*partB)[ARAP_WAVES], const double* __restrict__ shift = nullptr) {
   constexpr int THREADS = ARAP_WAVES * 64;
   arap_block_sum<3>(s3, partB);                                    // (its barrier also publishes p)
   const double bb = s3[0];
@@ -122,6 +126,7 @@ __device__ __forceinline__ ArapPcgResult arap_pcg_steps(int Vm, const int* __res
       const double pi = p[i];
       double qi = 0.0;
       for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) qi += weights[k] * (pi - p[clamp_index(cols[k], Vm)]);
+      if constexpr (SHIFTED) qi += shift[i] * pi;
       q[i] = qi;
       s1[0] += pi * qi;
     }

@@ -538,6 +538,37 @@ class SingleObjectDeform:
         self.deform_vertices(meshes[-1])
         return meshes
 
+    def simulate(self, steps, handle_targets=None, pinned=None, keep_velocity=True, faces=None, **options):
+        """`steps` steps of secondary motion (dynamics.MeshDynamics: implicit Euler with the ARAP energy as the potential) from
+        mesh_vertex_current (the rest pose the first time): the meshes [steps,Vm,3].  The handles are the ones set_handles /
+        set_region_handles chose, scripted to handle_targets [steps,H,3] (in the order of arap.handles); with none chosen the object is
+        a free body and handle_targets stays None.  pinned: vertex ids held where they are.  keep_velocity: start from the velocity the
+        previous simulate() left (zero the first time); False: from zero.  options: MeshDynamics' mass, density, stiffness, damping,
+        gravity, dt, iterations, cg_iterations, cg_tolerance; the object is built on the first call and kept while faces, handles, pins
+        and options stay the same.  Leaves the object at the last frame through deform_vertices, in the manner of drag_sequence.
+        faces [F,3]: for an object built from tensors alone.  Returns the meshes; no host wait."""
+        from .dynamics import MeshDynamics
+        import numpy as np
+        if faces is not None:
+            self._set_faces(faces)
+        if getattr(self, "faces", None) is None:
+            raise ValueError("simulate: this object has no faces; pass faces=[F,3]")
+        ids = lambda a: tuple(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a).reshape(-1).tolist())
+        hid = () if getattr(self, "arap", None) is None else ids(self.arap.handles)
+        pid = () if pinned is None else ids(pinned)
+        opts = tuple(sorted((k, id(v) if torch.is_tensor(v) or isinstance(v, np.ndarray) else (tuple(v) if isinstance(v, (list, tuple)) else v))
+                            for k, v in options.items()))
+        cached = getattr(self, "_dynamics", None)
+        if cached is None or cached[0] is not self.faces or cached[1:4] != (hid, pid, opts):
+            cached = self._dynamics = (self.faces, hid, pid, opts, MeshDynamics(self.vertex, self.faces, pinned=list(pid), handles=list(hid),
+                                                                                device=self.vertex.device, **options))
+        dyn, current = cached[4], self.mesh_vertex_current
+        dyn.reset(positions=self.vertex if current is None else current, velocities=getattr(self, "_sim_velocity", None) if keep_velocity else None)
+        meshes = dyn.run(steps, handle_targets)
+        self._sim_velocity = dyn.velocities
+        self.deform_vertices(meshes[-1])
+        return meshes
+
     def _screen_mesh(self, who):
         """(current vertices, faces, check_faces) for the screen-space methods: the face indices are checked on the host the first
         time this face tensor is seen (mesh_pick), afterwards nothing waits for the device."""

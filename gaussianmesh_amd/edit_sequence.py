@@ -4,6 +4,7 @@
         (--mesh_sequence DIR | --handle_sequence FILE.npz | --pick_sequence FILE.json) --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N]
         [--frames_per_launch 4] [--save_maps] [--save_meshes] [--save_baked PATH] [--background_gaussian BG.ply [--is_exist_bg]]
         [--arap_global_step {column,grid}] [--arap_batch K] [--inbetweens N [--ease {linear,smoothstep}]]
+        [--dynamics [--settle N] [--dt S] [--stiffness K] [--damping G] [--gravity X Y Z]]
 
 --object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
 faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of the two.
@@ -35,6 +36,13 @@ rotation-aware in-betweens are rendered between consecutive keys (pose_interp.Po
 geodesic, its stretch linearly, one Poisson solve per frame): K source frames give K (N + 1) + 1 frames, the keys among them bit for bit.
 --ease smoothstep spaces the in-betweens of a segment by 3 t^2 - 2 t^3 instead of evenly.  The default 0 changes nothing: the source's
 frames, no rest pose in front.  A face that turns by nearly half a turn between two keys may turn either way: add a key.
+--dynamics: the frames of --handle_sequence / --pick_sequence are SIMULATED steps instead of per-frame ARAP solves (SingleObjectDeform.simulate,
+dynamics.MeshDynamics): the mesh has velocity, so a dragged part follows through and swings back.  Every handle row is scripted to its
+position in each frame; anchors and held regions are rows whose scripted position is their rest position in every frame, which pins them.
+--settle N appends N steps with the handles held at their last positions (the mesh comes to rest); --dt (seconds per frame), --stiffness,
+--damping and --gravity X Y Z set the material, by default MeshDynamics' own.  Refused with --mesh_sequence (there is nothing to solve),
+with --arap_batch above 1 and with --inbetweens above 0; --settle and the material flags are refused without --dynamics.  Without these
+flags nothing changes.
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
@@ -129,6 +137,12 @@ def main(argv=None):
     parser.add_argument("--arap_batch", type=int, default=1)
     parser.add_argument("--inbetweens", type=int, default=0)
     parser.add_argument("--ease", choices=("linear", "smoothstep"), default="linear")
+    parser.add_argument("--dynamics", action="store_true", default=False)
+    parser.add_argument("--settle", type=int, default=0)
+    parser.add_argument("--dt", type=float, default=None)
+    parser.add_argument("--stiffness", type=float, default=None)
+    parser.add_argument("--damping", type=float, default=None)
+    parser.add_argument("--gravity", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
     parser.add_argument("--save_maps", action="store_true", default=False)
@@ -144,6 +158,21 @@ def main(argv=None):
         raise SystemExit("edit_sequence: --arap_batch %d: a launch chain carries 1 .. %d frames' solves" % (args.arap_batch, ARAP_BATCH_MAX))
     if args.inbetweens < 0:
         raise SystemExit("edit_sequence: --inbetweens %d: the number of frames between two keys, 0 or more" % args.inbetweens)
+    if args.settle < 0:
+        raise SystemExit("edit_sequence: --settle %d: the number of steps appended with the handles held, 0 or more" % args.settle)
+    if args.settle > 0 and not args.dynamics:
+        raise SystemExit("edit_sequence: --settle needs --dynamics (only a simulated mesh has anything to settle)")
+    if not args.dynamics:
+        for flag, value in (("--dt", args.dt), ("--stiffness", args.stiffness), ("--damping", args.damping), ("--gravity", args.gravity)):
+            if value is not None:
+                raise SystemExit("edit_sequence: %s sets the simulated material and needs --dynamics" % flag)
+    if args.dynamics:
+        if args.mesh_sequence is not None:
+            raise SystemExit("edit_sequence: --dynamics simulates the frames of --handle_sequence / --pick_sequence; --mesh_sequence has ready-made meshes")
+        if args.arap_batch > 1:
+            raise SystemExit("edit_sequence: --dynamics with --arap_batch %d: a simulated step starts from its predecessor; drop --arap_batch" % args.arap_batch)
+        if args.inbetweens > 0:
+            raise SystemExit("edit_sequence: --dynamics with --inbetweens %d: simulated frames are no key poses; drop one of the two" % args.inbetweens)
     if args.pick_sequence is not None:
         pick = read_pick_sequence(args.pick_sequence)
         (pick_camera, pick_handles, pick_anchors, pick_offsets), pick_radii = pick[:4], (pick[4] if len(pick) > 4 else None)
@@ -197,8 +226,20 @@ def main(argv=None):
     if handles is not None:
         if solver is None:
             solver = tool.gaussians_list[-1].set_handles(handles)
-        # enqueued back to back: no host wait between the solves; --arap_batch frames per launch chain
-        meshes = list(solver.solve_sequence(positions, batch=args.arap_batch, global_step=args.arap_global_step))
+        if args.dynamics:                                                             # one launch chain per 64 steps, no host wait
+            obj = tool.gaussians_list[-1]
+            pos = torch.stack([torch.as_tensor(p, dtype=torch.float32, device=obj.vertex.device) for p in positions], 0)
+            if args.settle > 0:
+                pos = torch.cat([pos, pos[-1:].expand(args.settle, -1, -1)], 0)
+            material = {k: v for k, v in (("dt", args.dt), ("stiffness", args.stiffness), ("damping", args.damping),
+                                          ("gravity", None if args.gravity is None else tuple(args.gravity))) if v is not None}
+            try:
+                meshes = list(obj.simulate(len(pos), pos, **material))
+            except ValueError as e:
+                raise SystemExit("edit_sequence: --dynamics: %s" % e)
+        else:
+            # enqueued back to back: no host wait between the solves; --arap_batch frames per launch chain
+            meshes = list(solver.solve_sequence(positions, batch=args.arap_batch, global_step=args.arap_global_step))
     if args.inbetweens > 0:                                                           # the frames so far are keys; the rest pose is key 0
         from .pose_interp import PoseInterpolator
         obj = tool.gaussians_list[-1]

@@ -226,6 +226,16 @@ class ObjectVisualTool:
                 meshes = g.interpolate_to(target, inbetweens, **options)
         return meshes
 
+    def simulate_one_gaussian(self, name, steps, handle_targets=None, **options):
+        """`steps` simulated steps of the objects called `name` from their current mesh (SingleObjectDeform.simulate: secondary motion,
+        dynamics.MeshDynamics) with their handles at handle_targets [steps,H,3]; the objects are left at the last frame.  Returns the
+        meshes [steps, Vm, 3] of the last such object (None if there is none)."""
+        meshes = None
+        for g in self.gaussians_list:
+            if g.get_name() == name:
+                meshes = g.simulate(steps, handle_targets, **options)
+        return meshes
+
     def drag_region_one_gaussian(self, name, handle_vertices, displacements, grab_radius, free_radius=None, anchor_vertices=(), **solve_options):
         """drag_one_gaussian with surface regions for handles: on the objects called `name`, everything within grab_radius (along the
         rest mesh) of handle_vertices[i] moves by displacements[i] ([H,3]), everything within grab_radius of an anchor vertex or, with

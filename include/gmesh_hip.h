@@ -358,6 +358,39 @@ int gm_pose_interp(int T, int Vm, int F, const int* row_offsets, const int* cols
                    const int* label, const float* A, const float* B, const double* ts, int cg_iterations, double cg_tolerance, float* V_out,
                    double* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Secondary motion of a proxy mesh (dynamics.MeshDynamics): T implicit-Euler steps of an elastic mesh whose potential is the ARAP energy,
+ * in ONE launch chain - the local/global iteration of projective dynamics (Bouaziz et al. 2014) over gm_arap_solve's CSR, whose global
+ * step's matrix gains the positive diagonal mu (definition: csrc/gm_dynamics.hip, INTEGRATION.md section AA).  row_offsets / cols /
+ * weights: that CSR (arap.edge_csr); V0 float [Vm,3] the rest vertices; mass double [Vm], positive wherever d_i > 0; held unsigned char [Vm]:
+ * rows with held[i] != 0, and rows whose weights sum to 0, are not unknowns; handle_ids int32 [H]: the held rows whose positions are
+ * scripted, handle_targets float [T,H,3] their position in every step (H == 0: both may be NULL); x_in, v_in float [Vm,3] the state.
+ * With h = dt, k = stiffness, g = damping, a = (gx, gy, gz), step t takes (x, v) to (x', v'):
+ *   y_i = x_i + h v_i + h^2 a;   X_i = y_i on free rows, handle_targets[t] on handle rows, x_i on the other held rows;
+ *   `iterations` times: R_i = the local step's rotation at X (gm_arap_solve's), then for every free row and coordinate
+ *     mu_i X_i + sum_j w_ij (X_i - X_j) = mu_i y_i + sum_j (w_ij / 2)(R_i + R_j)(p_i - p_j),  mu_i = mass_i / (2 k h^2),
+ *     by Jacobi-preconditioned CG (diagonal mu_i + d_i) warm-started from X and stopped at |r| <= cg_tolerance |b|, at p . A p <= 0 or
+ *     after cg_iterations steps;
+ *   x' = float32(X);  v'_i = float32((1 - g)(X_i - x_i) / h) on free rows, float32((X_i - x_i) / h) on held rows.
+ * X_out float [T,Vm,3]: x' of every step; v_out float [Vm,3]: v' of the last step (it may be v_in itself); stats (optional) double [T,6]:
+ * CG steps used for x / y / z and final |r| / |b| for x / y / z in the step's last iteration.  The state is rounded to float32 at every
+ * step boundary, so a call of T steps is bit for bit T calls of one step; no atomics, the same bits from call to call.  With no held
+ * row the system is still positive definite: a free body.  Column and handle ids are forced into [0, Vm).  THE CALLER'S CHECKS (they
+ * cannot be made here without a read-back): every mass positive on a row with an edge, every handle id a held row and given once.
+ * 1 + (H > 0) + 2 T iterations launches: the global step of a step's last iteration also writes the step's result and the next step's
+ * prediction for its own coordinate.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: T < 1 or T > GM_MESH_DYNAMICS_STEPS_MAX, Vm < 1, H < 0 or H > Vm, a dt or
+ * stiffness that is not finite and positive, a damping outside [0, 1), a gravity or cg_tolerance that is not finite, a negative
+ * cg_tolerance, iterations < 1, cg_iterations < 1, a NULL among the required pointers (handle_ids and handle_targets only when H > 0),
+ * any overlap of X_out, v_out, stats or the workspace with one another or with an input, other than v_out == v_in; with GM_ERR_BUFFER a
+ * workspace below gm_mesh_dynamics_workspace_bytes(Vm) (O(Vm), monotonic; 0 for Vm < 1).  Stream-ordered, no device allocation, no
+ * host synchronisation. */
+#define GM_MESH_DYNAMICS_STEPS_MAX 64
+size_t gm_mesh_dynamics_workspace_bytes(int Vm);
+int gm_mesh_dynamics(int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const double* mass,
+                     const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in, const float* v_in,
+                     double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
+                     double cg_tolerance, float* X_out, float* v_out, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* First hit of every ray on a mesh: what takes an editor from a pixel to a vertex of the current, deformed proxy mesh
  * (mesh_pick.ray_mesh_hits / pick / visible_vertices).  The reference has no such stage: the result is defined by arithmetic.
  * origins, dirs float [R,3], vertices float [Vm,3], faces int32 [F,3] vertex ids.  out_t float [R], out_face int32 [R], out_uv float
