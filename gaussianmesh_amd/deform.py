@@ -377,6 +377,7 @@ class SingleObjectDeform:
         self.deform_state = None         # (V1, R, S) of the last deform(); None: the rest pose (edittool render_sequence renders it)
         self.arap = None                 # the ArapSolver of set_handles()
         self.region = None               # set_region_handles(): (picked vertex ids int64 [H], owner int64 [n]) on the device
+        self._operators, self._operator_keys = {}, {}    # _operator(): name -> kept operator, name -> (face tensor, key) it was built for
 
     def get_name(self):
         return self.name
@@ -399,11 +400,7 @@ class SingleObjectDeform:
         smooth_sweeps, smooth_lambda.  Leaves the object deformed to the fitted pose (deform_state) and returns the
         fitter (its .losses, its .pose)."""
         from .pose_fit import PoseFitter
-        if faces is not None:
-            self._set_faces(faces)
-        if getattr(self, "faces", None) is None:
-            raise ValueError("fit_pose: this object has no faces; pass faces=[F,3]")
-        fitter = PoseFitter(self, self.faces, **fitter_options)
+        fitter = PoseFitter(self, self._need_faces("fit_pose", faces), **fitter_options)
         fitter.fit(views, iterations, background=background)
         return fitter
 
@@ -412,15 +409,33 @@ class SingleObjectDeform:
         off, adj = vertex_face_adjacency(self.faces, self.vertex.shape[0])
         self._adjacency = (torch.tensor(off, device=self.vertex.device), torch.tensor(adj, device=self.vertex.device))
 
+    def _need_faces(self, who, faces=None):
+        """the face tensor, after _set_faces(faces) where faces are given; ValueError where the object has none"""
+        if faces is not None:
+            self._set_faces(faces)
+        if getattr(self, "faces", None) is None:
+            raise ValueError("%s: this object has no faces; pass faces=[F,3] here or to set_handles" % who)
+        return self.faces
+
+    def _operator(self, name, key, make):
+        """The kept operator `name` (_operators[name]); make() builds it anew when `key` or the face tensor is not what it was built for."""
+        if name not in self._operators or self._operator_keys[name][0] is not self.faces or self._operator_keys[name][1] != key:
+            self._operators[name], self._operator_keys[name] = make(), (self.faces, key)
+        return self._operators[name]
+
+    @property
+    def mesh_graph(self):
+        """The mesh_graph.MeshGraph of the rest mesh, which every operator of this object shares (ArapSolver, PoseInterpolator,
+        MeshDynamics, PoseFitter's ArapEnergy): built the first time it is asked for and again when the face tensor changes."""
+        from .mesh_graph import MeshGraph
+        return self._operator("mesh_graph", None, lambda: MeshGraph(self.vertex, self._need_faces("mesh_graph"), device=self.vertex.device))
+
     def set_handles(self, vertex_ids, faces=None):
         """Choose the handle vertices of drag(): builds the arap.ArapSolver of this object's rest mesh (its refusals apply).  faces
         [F,3]: the proxy mesh's triangles, for an object built from tensors alone (the file-based object has them)."""
         from .arap import ArapSolver
-        if faces is not None:
-            self._set_faces(faces)
-        if getattr(self, "faces", None) is None:
-            raise ValueError("set_handles: this object has no faces; pass faces=[F,3]")
-        self.arap = ArapSolver(self.vertex, self.faces, vertex_ids, device=self.vertex.device)
+        self._need_faces("set_handles", faces)
+        self.arap = ArapSolver(self.mesh_graph, None, vertex_ids)
         self.region = None
         return self.arap
 
@@ -429,12 +444,9 @@ class SingleObjectDeform:
         lists: float32 [B,Vm] on the device, +inf beyond max_distance (mesh_region.SurfaceGraph.distances; one 4-byte read-back per
         64 sweeps).  The graph is built on the host the first time this face tensor is seen and kept."""
         from .mesh_region import SurfaceGraph
-        if getattr(self, "faces", None) is None:
-            raise ValueError("surface_distances: this object has no faces; set_handles(..., faces=[F,3]) supplies them")
-        cached = getattr(self, "_surface_graph", None)
-        if cached is None or cached[0] is not self.faces:
-            cached = self._surface_graph = (self.faces, SurfaceGraph(self.vertex, self.faces, device=self.vertex.device))
-        return cached[1].distances(vertex_sets, max_distance=max_distance)
+        faces = self._need_faces("surface_distances")
+        graph = self._operator("surface_graph", None, lambda: SurfaceGraph(self.vertex, faces, device=self.vertex.device))
+        return graph.distances(vertex_sets, max_distance=max_distance)
 
     def set_region_handles(self, handle_vertices, grab_radius, free_radius=None, anchor_vertices=(), faces=None):
         """Choose drag_region()'s handles as surface regions around picked vertices: every vertex within grab_radius (along the rest
@@ -487,9 +499,7 @@ class SingleObjectDeform:
 
     def deform_vertices(self, deform_vertex):
         """deform() from the deformed vertices alone: their per-vertex (R, S) by gm_mesh_rs first."""
-        if getattr(self, "faces", None) is None:
-            raise ValueError("deform_vertices: this object has no faces; set_handles(..., faces=[F,3]) supplies them")
-        R, S = mesh_rs(self.vertex, deform_vertex, self.faces, adjacency=getattr(self, "_adjacency", None))
+        R, S = mesh_rs(self.vertex, deform_vertex, self._need_faces("deform_vertices"), adjacency=getattr(self, "_adjacency", None))
         return self.deform(deform_vertex, R, S)
 
     def drag(self, handle_positions, **solve_options):
@@ -524,17 +534,11 @@ class SingleObjectDeform:
         [F,3]: for an object built from tensors alone.  Returns the meshes; no host wait."""
         from .pose_interp import PoseInterpolator
         import numpy as np
-        if faces is not None:
-            self._set_faces(faces)
-        if getattr(self, "faces", None) is None:
-            raise ValueError("interpolate_to: this object has no faces; pass faces=[F,3]")
+        self._need_faces("interpolate_to", faces)
         ids = None if anchors is None else tuple(np.asarray(anchors.detach().cpu() if torch.is_tensor(anchors) else anchors).reshape(-1).tolist())
-        cached = getattr(self, "_pose_interp", None)
-        if cached is None or cached[0] is not self.faces or cached[1] != ids:
-            cached = self._pose_interp = (self.faces, ids, PoseInterpolator(self.vertex, self.faces, anchors=None if ids is None else list(ids),
-                                                                            device=self.vertex.device))
+        interp = self._operator("pose_interp", ids, lambda: PoseInterpolator(self.mesh_graph, None, anchors=None if ids is None else list(ids)))
         current = self.mesh_vertex_current
-        meshes = cached[2].sequence([self.vertex if current is None else current, target_vertices], inbetweens, ease=ease, **between_options)
+        meshes = interp.sequence([self.vertex if current is None else current, target_vertices], inbetweens, ease=ease, **between_options)
         self.deform_vertices(meshes[-1])
         return meshes
 
@@ -549,20 +553,14 @@ class SingleObjectDeform:
         faces [F,3]: for an object built from tensors alone.  Returns the meshes; no host wait."""
         from .dynamics import MeshDynamics
         import numpy as np
-        if faces is not None:
-            self._set_faces(faces)
-        if getattr(self, "faces", None) is None:
-            raise ValueError("simulate: this object has no faces; pass faces=[F,3]")
+        self._need_faces("simulate", faces)
         ids = lambda a: tuple(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a).reshape(-1).tolist())
         hid = () if getattr(self, "arap", None) is None else ids(self.arap.handles)
         pid = () if pinned is None else ids(pinned)
         opts = tuple(sorted((k, id(v) if torch.is_tensor(v) or isinstance(v, np.ndarray) else (tuple(v) if isinstance(v, (list, tuple)) else v))
                             for k, v in options.items()))
-        cached = getattr(self, "_dynamics", None)
-        if cached is None or cached[0] is not self.faces or cached[1:4] != (hid, pid, opts):
-            cached = self._dynamics = (self.faces, hid, pid, opts, MeshDynamics(self.vertex, self.faces, pinned=list(pid), handles=list(hid),
-                                                                                device=self.vertex.device, **options))
-        dyn, current = cached[4], self.mesh_vertex_current
+        dyn = self._operator("dynamics", (hid, pid, opts), lambda: MeshDynamics(self.mesh_graph, None, pinned=list(pid), handles=list(hid), **options))
+        current = self.mesh_vertex_current
         dyn.reset(positions=self.vertex if current is None else current, velocities=getattr(self, "_sim_velocity", None) if keep_velocity else None)
         meshes = dyn.run(steps, handle_targets)
         self._sim_velocity = dyn.velocities
@@ -572,11 +570,10 @@ class SingleObjectDeform:
     def _screen_mesh(self, who):
         """(current vertices, faces, check_faces) for the screen-space methods: the face indices are checked on the host the first
         time this face tensor is seen (mesh_pick), afterwards nothing waits for the device."""
-        if getattr(self, "faces", None) is None:
-            raise ValueError("%s: this object has no faces; set_handles(..., faces=[F,3]) supplies them" % who)
-        check = getattr(self, "_faces_checked", None) is not self.faces
+        faces = self._need_faces(who)
+        check = getattr(self, "_faces_checked", None) is not faces
         current = self.mesh_vertex_current
-        return (self.vertex if current is None else current), self.faces, check
+        return (self.vertex if current is None else current), faces, check
 
     def pick(self, camera, pixels):
         """mesh_pick.pick on this object's mesh as last deformed (mesh_vertex_current; the rest pose if there is none): what lies under

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._op import enqueue, host, on_device
-from .arap import edge_csr
+from .mesh_graph import MeshGraph
 
 
 def vertex_masses(vertices, faces, density=1.0):
@@ -33,21 +33,9 @@ def vertex_masses(vertices, faces, density=1.0):
     return m * float(density)
 
 
-def _ids(a, Vm, who, what):
-    h = np.asarray(host(a)).reshape(-1)
-    if h.size == 0:
-        return np.zeros(0, np.int64)
-    if h.dtype.kind not in "iu":
-        raise ValueError("%s: %s must be integer vertex ids, got %s" % (who, what, h.dtype))
-    h = h.astype(np.int64)
-    if int(h.min()) < 0 or int(h.max()) >= Vm:
-        raise ValueError("%s: %s id outside [0, %d) (min %d, max %d)" % (who, what, Vm, int(h.min()), int(h.max())))
-    return h
-
-
 class MeshDynamics:
-    """The motion of one mesh under scripted handles, pins, gravity and its own elasticity.  Built once: the edge CSR (arap.edge_csr),
-    the masses, the masks, and on a device the state (positions, velocities: float32 [Vm,3]) and the workspace.
+    """The motion of one mesh under scripted handles, pins, gravity and its own elasticity.  Built once: the mesh's MeshGraph (given as
+    rest_vertices with faces=None, it is shared), the masses, the masks, and on a device the state (float32 [Vm,3] each) and the workspace.
     rest_vertices [Vm,3], faces [F,3] vertex ids.  pinned: vertex ids held where they are; handles: H distinct vertex ids whose
     positions every step scripts (run's handle_targets); neither: a free body.  Vertices whose weights sum to 0 (unreferenced, or every
     face at them degenerate) are held too.  mass: "area" (vertex_masses(rest_vertices, faces, density)) or [Vm] numbers, positive on
@@ -64,24 +52,17 @@ class MeshDynamics:
     def __init__(self, rest_vertices, faces, pinned=(), handles=(), mass="area", density=1.0, stiffness=10.0, damping=0.02, gravity=(0.0, 0.0, 0.0),
                  dt=1.0 / 30.0, iterations=3, cg_iterations=64, cg_tolerance=1e-6, device="cuda"):
         who = "MeshDynamics"
-        self.device = torch.device(device)
-        v = np.ascontiguousarray(np.asarray(host(rest_vertices), np.float32))
-        if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] == 0:
-            raise ValueError("%s: rest_vertices must be [Vm,3] with Vm > 0; got %s" % (who, tuple(v.shape)))
-        Vm = v.shape[0]
-        f = np.ascontiguousarray(np.asarray(host(faces)).astype(np.int64).reshape(-1, 3))
-        off, cols, weights = edge_csr(v, f)                            # (refuses a face id out of range)
-        rows = np.repeat(np.arange(Vm, dtype=np.int64), np.diff(off.astype(np.int64)))
-        self._edgeless = np.bincount(rows, weights=weights, minlength=Vm) <= 0.0
+        mesh = self.mesh = MeshGraph.of(rest_vertices, faces, device, who)
+        self.device, Vm = mesh.device, mesh.Vm
         if isinstance(mass, str):
             if mass != "area":
                 raise ValueError('%s: mass must be "area" or [Vm] numbers; got %r' % (who, mass))
-            m = vertex_masses(v, f, density)
+            m = vertex_masses(mesh.rest_host, mesh.faces_host, density)
         else:
             m = np.asarray(host(mass), np.float64).reshape(-1)
             if m.shape != (Vm,):
                 raise ValueError("%s: mass must hold %d numbers; got %d" % (who, Vm, m.size))
-        if not np.isfinite(m).all() or bool((m[~self._edgeless] <= 0.0).any()) or bool((m < 0.0).any()):
+        if not np.isfinite(m).all() or bool((m[~mesh.edgeless] <= 0.0).any()) or bool((m < 0.0).any()):
             raise ValueError("%s: every mass must be finite and positive (negative nowhere, zero only at a vertex without an edge)" % who)
         g = np.asarray(host(gravity), np.float64).reshape(-1)
         if g.shape != (3,) or not np.isfinite(g).all():
@@ -93,17 +74,13 @@ class MeshDynamics:
         for name, val in (("iterations", iterations), ("cg_iterations", cg_iterations)):
             if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or val < 1:
                 raise ValueError("%s: %s = %r; an integer >= 1" % (who, name, val))
-        self.Vm, self.F, self.csr, self.mass = Vm, f.shape[0], (off, cols, weights), m
+        self.Vm, self.F, self.csr, self.mass = Vm, mesh.F, mesh.csr, m
         self.dt, self.stiffness, self.damping, self.gravity = float(dt), float(stiffness), float(damping), tuple(float(x) for x in g)
         self.iterations, self.cg_iterations, self.cg_tolerance = int(iterations), int(cg_iterations), float(cg_tolerance)
-        self._rest_host = v
         self._x = self._v = self._ws = None
         if self.device.type == "cuda":
-            t = lambda a, dtype: on_device(a, dtype, self.device)
-            self.rest = t(v, torch.float32)
-            if len(cols) == 0:                                         # a mesh without an edge: no row reads them, but the entry point wants pointers
-                cols, weights = np.zeros(1, np.int32), np.zeros(1, np.float64)
-            self._off, self._cols, self._w, self._mass = t(off, torch.int32), t(cols, torch.int32), t(weights, torch.float64), t(m, torch.float64)
+            self.rest, self._off, self._cols, self._w = mesh.device_csr
+            self._mass = on_device(m, torch.float64, self.device)
         self.set_constraints(pinned, handles)
         if self.device.type == "cuda":
             self.reset()
@@ -112,30 +89,18 @@ class MeshDynamics:
         """Replace the pins and the handles; the state (positions, velocities) stays, so dropping a handle RELEASES it with the velocity
         its drag gave it.  ValueError for an id out of range or given twice among the handles, and for a handle that is also pinned."""
         who = "MeshDynamics.set_constraints"
-        p, h = _ids(pinned, self.Vm, who, "pinned"), _ids(handles, self.Vm, who, "handles")
-        if len(np.unique(h)) != len(h):
-            raise ValueError("%s: a handle id is given twice" % who)
+        p = self.mesh.vertex_ids(pinned, who, "pinned", allow_empty=True, distinct=False)
+        h = self.mesh.vertex_ids(handles, who, "handle", allow_empty=True)
         both = np.intersect1d(p, h)
         if len(both):
             raise ValueError("%s: vertex %d is both a handle and pinned" % (who, int(both[0])))
-        held = self._edgeless.copy()
+        held = self.mesh.edgeless.copy()
         held[p] = True
         held[h] = True
         self.pinned, self.handles, self.held = np.unique(p), h, held
         if self.device.type == "cuda":
             self._held = on_device(held.astype(np.uint8), torch.uint8, self.device)
             self._handle_ids = on_device(h.astype(np.int32), torch.int32, self.device) if len(h) else None
-
-    def _need_device(self, who):
-        if self.device.type != "cuda":
-            raise _lib.GmeshError("%s needs a HIP (cuda) device; there is no CPU path" % who)
-
-    def _rows(self, a, who, name):
-        if not torch.is_tensor(a):
-            a = torch.as_tensor(np.asarray(a), dtype=torch.float32)
-        if a.shape != (self.Vm, 3) or not a.dtype.is_floating_point:
-            raise ValueError("%s: %s must be a floating-point [%d,3] tensor; got %s %s" % (who, name, self.Vm, a.dtype, tuple(a.shape)))
-        return a.detach().to(device=self.rest.device, dtype=torch.float32).clone(memory_format=torch.contiguous_format)
 
     def reset(self, positions=None, velocities=None):
         """Set the state: positions [Vm,3] (None: the rest pose), velocities [Vm,3] (None: zero); both are copied."""
@@ -144,20 +109,20 @@ class MeshDynamics:
             raise ValueError("%s: positions must be [%d,3]; got %s" % (who, self.Vm, tuple(getattr(positions, "shape", ()))))
         if velocities is not None and (not hasattr(velocities, "shape") or tuple(velocities.shape) != (self.Vm, 3)):
             raise ValueError("%s: velocities must be [%d,3]; got %s" % (who, self.Vm, tuple(getattr(velocities, "shape", ()))))
-        self._need_device(who)
-        self._x = self.rest.clone() if positions is None else self._rows(positions, who, "positions")
-        self._v = torch.zeros_like(self.rest) if velocities is None else self._rows(velocities, who, "velocities")
+        self.mesh.need_device(who)
+        self._x = self.rest.clone() if positions is None else self.mesh.rows_f32(positions, who, "positions", copy=True)
+        self._v = torch.zeros_like(self.rest) if velocities is None else self.mesh.rows_f32(velocities, who, "velocities", copy=True)
 
     @property
     def positions(self):
         """the state's positions, float32 [Vm,3] on the device (a copy)"""
-        self._need_device("MeshDynamics.positions")
+        self.mesh.need_device("MeshDynamics.positions")
         return self._x.clone()
 
     @property
     def velocities(self):
         """the state's velocities, float32 [Vm,3] on the device (a copy)"""
-        self._need_device("MeshDynamics.velocities")
+        self.mesh.need_device("MeshDynamics.velocities")
         return self._v.clone()
 
     def step(self, handle_targets=None):
@@ -192,16 +157,12 @@ class MeshDynamics:
                 handle_targets = np.asarray(handle_targets, np.float32)
             if tuple(handle_targets.shape) != (T, H, 3):
                 raise ValueError("%s: handle_targets must be [%d,%d,3]; got %s" % (who, T, H, tuple(handle_targets.shape)))
-        self._need_device(who)
+        self.mesh.need_device(who)
         dev = self.rest.device
         hp = None
         if handle_targets is not None:
             hp = on_device(handle_targets, torch.float32, dev)
-        if out is not None:
-            if not torch.is_tensor(out) or out.shape != (T, Vm, 3) or out.dtype is not torch.float32 or not out.is_contiguous() or out.device != dev:
-                raise ValueError("%s: out must be a contiguous float32 [%d,%d,3] tensor on the object's device" % (who, T, Vm))
-        else:
-            out = torch.empty((T, Vm, 3), dtype=torch.float32, device=dev)
+        out = self.mesh.out_f32(out, (T, Vm, 3), who)
         stats = torch.zeros((T, 6), dtype=torch.float64, device=dev) if want_stats else None
         if self._ws is None:
             need = _lib.lib().gm_mesh_dynamics_workspace_bytes(Vm)

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from ._op import enqueue, host
+from .mesh_graph import vertex_ids
 
 
 def _norm3(d):
@@ -152,15 +153,7 @@ class SurfaceGraph:
         budget = max(Vm, 1) if max_sweeps is None else int(max_sweeps)
         if chunk < 1 or budget < 1:
             raise ValueError("SurfaceGraph.distances: sweeps_per_check and max_sweeps must be >= 1; got %r, %r" % (sweeps_per_check, max_sweeps))
-        sets = []
-        for b, s in enumerate(source_sets):
-            a = np.asarray(host(s)).reshape(-1)
-            if a.size and a.dtype.kind not in "iu":
-                raise ValueError("SurfaceGraph.distances: source set %d must hold integer vertex ids, got %s" % (b, a.dtype))
-            a = a.astype(np.int64)
-            if a.size and (int(a.min()) < 0 or int(a.max()) >= Vm):
-                raise ValueError("SurfaceGraph.distances: source set %d has an id outside [0, %d) (min %d, max %d)" % (b, Vm, int(a.min()), int(a.max())))
-            sets.append(a)
+        sets = [vertex_ids(s, Vm, "SurfaceGraph.distances", "source set %d" % b, allow_empty=True, distinct=False) for b, s in enumerate(source_sets)]
         B = len(sets)
         if B > 65535:
             raise ValueError("SurfaceGraph.distances: at most 65535 source sets a call; got %d" % B)

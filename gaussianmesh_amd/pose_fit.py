@@ -165,7 +165,8 @@ class PoseFitter:
         self.arap = None                                                      # the mesh's ArapEnergy: only when an option asks for it
         if regularizer == "arap" or self.smooth_sweeps > 0:
             from .arap import ArapEnergy
-            self.arap = ArapEnergy(obj.vertex, self.faces, device=obj.vertex.device)
+            own = faces is getattr(obj, "faces", None)                        # the object's own faces: its graph is shared, not rebuilt
+            self.arap = ArapEnergy(obj.mesh_graph, None) if own else ArapEnergy(obj.vertex, self.faces, device=obj.vertex.device)
         self.pose = MeshPose(obj.vertex, self.faces)
         start = obj.mesh_vertex_current
         if start is not None:

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._op import enqueue, host, on_device
-from .arap import components, edge_csr
+from .mesh_graph import MeshGraph
 
 EASES = ("linear", "smoothstep")
 
@@ -40,8 +40,8 @@ def component_rows(label):
 
 
 class PoseInterpolator:
-    """In-betweens of key poses of one mesh.  Built once: the edge CSR (arap.edge_csr), the faces at every vertex
-    (deform.vertex_face_adjacency), the connected components of the weighted edge graph (arap.components), the mask of held rows, and
+    """In-betweens of key poses of one mesh.  Built once: the mesh's MeshGraph (rest_vertices may be one, with faces=None: it is shared, not
+    rebuilt) - the edge CSR, the faces at every vertex, the connected components of the weighted edge graph -, the mask of held rows, and
     on a device the workspace, grown to the largest batch seen.
     rest_vertices [Vm,3], faces [F,3] vertex ids.  anchors=None: the vertex of least id of every component is held on its linear path
     and every component is then translated so that its mean is (1 - t) mean_A + t mean_B - a spin about the centroid comes out as a
@@ -51,64 +51,30 @@ class PoseInterpolator:
     (the system would be singular)."""
 
     def __init__(self, rest_vertices, faces, anchors=None, device="cuda"):
-        from .deform import vertex_face_adjacency
-        self.device = torch.device(device)
-        v = np.ascontiguousarray(np.asarray(host(rest_vertices), np.float32))
-        if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] == 0:
-            raise ValueError("PoseInterpolator: rest_vertices must be [Vm,3] with Vm > 0; got %s" % (tuple(v.shape),))
-        Vm = v.shape[0]
-        f = np.ascontiguousarray(np.asarray(host(faces)).astype(np.int64).reshape(-1, 3))
-        off, cols, weights = edge_csr(v, f)                            # (refuses a face id out of range)
-        rows = np.repeat(np.arange(Vm, dtype=np.int64), np.diff(off.astype(np.int64)))
-        pinned = np.bincount(rows, weights=weights, minlength=Vm) <= 0.0
-        label = components(Vm, rows, cols.astype(np.int64))
-        held = pinned.copy()
+        who = "PoseInterpolator"
+        g = self.mesh = MeshGraph.of(rest_vertices, faces, device, who)
+        held = g.edgeless.copy()
         if anchors is None:
-            held[np.unique(label)] = True
+            held[np.unique(g.label)] = True
             h = None
         else:
-            h = np.asarray(host(anchors)).reshape(-1)
-            if h.size == 0:
-                raise ValueError("PoseInterpolator: the anchor list is empty (anchors=None holds one vertex per component)")
-            if h.dtype.kind not in "iu":
-                raise ValueError("PoseInterpolator: anchors must be integer vertex ids, got %s" % h.dtype)
-            h = h.astype(np.int64)
-            if int(h.min()) < 0 or int(h.max()) >= Vm:
-                raise ValueError("PoseInterpolator: anchor id outside [0, %d) (min %d, max %d)" % (Vm, int(h.min()), int(h.max())))
-            if len(np.unique(h)) != len(h):
-                raise ValueError("PoseInterpolator: an anchor id is given twice")
+            h = g.vertex_ids(anchors, who, "anchor")
             held[h] = True
-            has_anchor = np.zeros(Vm, bool)
-            has_anchor[label[h]] = True
-            loose = np.nonzero(~held & ~has_anchor[label])[0]
-            if len(loose):
-                raise ValueError("PoseInterpolator: vertex %d lies in a connected component without an anchor (%d such vertices): the system "
-                                 "is singular" % (int(loose[0]), len(loose)))
-        self.Vm, self.F, self.anchors, self.pinned = Vm, f.shape[0], h, np.nonzero(pinned)[0]
-        self.csr, self.label, self.held = (off, cols, weights), label, held
+            g.require_anchored(held, h, who, "anchor")
+        self.device, self.Vm, self.F, self.csr, self.label = g.device, g.Vm, g.F, g.csr, g.label
+        self.anchors, self.pinned, self.held = h, np.nonzero(g.edgeless)[0], held
         if self.device.type != "cuda":                                 # the set-up above is host work; between() needs the device
             return
-        t = lambda a, dt: on_device(a, dt, self.device)
-        self.rest = t(v, torch.float32)
-        if len(cols) == 0:                                             # a mesh without an edge: no row reads them, but the entry point wants pointers
-            cols, weights = np.zeros(1, np.int32), np.zeros(1, np.float64)
-        self._off, self._cols, self._w = t(off, torch.int32), t(cols, torch.int32), t(weights, torch.float64)
-        vf_off, vf_faces = vertex_face_adjacency(f, Vm)
-        self._faces, self._vf_off, self._vf_faces = t(f, torch.int32), t(vf_off, torch.int32), t(vf_faces, torch.int32)
-        self._held = t(held.astype(np.uint8), torch.uint8)
+        t = lambda a: on_device(a, torch.int32, self.device)
+        self.rest, self._off, self._cols, self._w = g.device_csr
+        self._faces, self._vf_off, self._vf_faces = g.device_faces
+        self._held = on_device(held.astype(np.uint8), torch.uint8, self.device)
         if anchors is None:
-            index, c_off, c_rows = component_rows(label)
-            self.C, self._label, self._comp_off, self._comp_rows = len(c_off) - 1, t(index, torch.int32), t(c_off, torch.int32), t(c_rows, torch.int32)
+            index, c_off, c_rows = component_rows(g.label)
+            self.C, self._label, self._comp_off, self._comp_rows = len(c_off) - 1, t(index), t(c_off), t(c_rows)
         else:
             self.C, self._label, self._comp_off, self._comp_rows = 0, None, None, None
         self._ws = None                                                # made by the first between(), grown to the largest T seen
-
-    def _key(self, K, who, name):
-        if not torch.is_tensor(K):
-            K = torch.as_tensor(np.asarray(K), dtype=torch.float32, device=self.device)
-        if K.shape != (self.Vm, 3) or not K.dtype.is_floating_point:
-            raise ValueError("%s: %s must be a floating-point [%d,3] tensor; got %s %s" % (who, name, self.Vm, K.dtype, tuple(K.shape)))
-        return K.detach().to(device=self.rest.device, dtype=torch.float32).contiguous()
 
     def between(self, A, B, ts, cg_iterations=512, cg_tolerance=1e-6, out=None, want_stats=False):
         """The meshes [T,Vm,3] float32 on the device at parameters ts (T numbers, each in [0, 1]) between the key poses A and B ([Vm,3],
@@ -124,22 +90,17 @@ class PoseInterpolator:
         short at |r| / |b| = 8e-4; 512 lies above the largest count seen.  A step costs about 31 us at 7.5 k vertices, whatever T up
         to 8: 64 in-betweens take 0.2 ms each."""
         who = "PoseInterpolator.between"
-        if self.device.type != "cuda":
-            raise _lib.GmeshError("%s needs a HIP (cuda) device; there is no CPU path" % who)
+        self.mesh.need_device(who)
         tv = np.asarray(host(ts), np.float64).reshape(-1)
         if tv.size == 0 or not np.all(np.isfinite(tv)) or float(tv.min()) < 0.0 or float(tv.max()) > 1.0:
             raise ValueError("%s: ts must be at least one finite number in [0, 1]; got %s" % (who, tv.tolist() if tv.size <= 8 else "%d values" % tv.size))
-        a, b = self._key(A, who, "A"), self._key(B, who, "B")
+        a, b = self.mesh.rows_f32(A, who, "A"), self.mesh.rows_f32(B, who, "B")
         T, Vm, dev = tv.size, self.Vm, self.rest.device
-        if out is not None:
-            if not torch.is_tensor(out) or out.shape != (T, Vm, 3) or out.dtype is not torch.float32 or not out.is_contiguous() or out.device != dev:
-                raise ValueError("%s: out must be a contiguous float32 [%d,%d,3] tensor on the interpolator's device" % (who, T, Vm))
-            lo, hi = out.data_ptr(), out.data_ptr() + 12 * T * Vm
-            for k in (a, b):
-                if k.data_ptr() < hi and lo < k.data_ptr() + 12 * Vm:
-                    raise ValueError("%s: out shares memory with a key pose" % who)
-        else:
-            out = torch.empty((T, Vm, 3), dtype=torch.float32, device=dev)
+        given, out = out is not None, self.mesh.out_f32(out, (T, Vm, 3), who)
+        lo, hi = out.data_ptr(), out.data_ptr() + 12 * T * Vm
+        for k in (a, b) if given else ():
+            if k.data_ptr() < hi and lo < k.data_ptr() + 12 * Vm:
+                raise ValueError("%s: out shares memory with a key pose" % who)
         stats = torch.zeros((T, 6), dtype=torch.float64, device=dev) if want_stats else None
         t_dev = torch.as_tensor(tv, dtype=torch.float64, device=dev)
         top = _lib.GM_POSE_INTERP_BATCH_MAX
@@ -159,8 +120,7 @@ class PoseInterpolator:
         copied; only the frames strictly between are solved, at segment_ts(inbetweens, ease).  inbetweens = 0 returns the keys.
         between_options: cg_iterations, cg_tolerance."""
         who = "PoseInterpolator.sequence"
-        if self.device.type != "cuda":
-            raise _lib.GmeshError("%s needs a HIP (cuda) device; there is no CPU path" % who)
+        self.mesh.need_device(who)
         if "out" in between_options or "want_stats" in between_options:
             raise ValueError("%s: out and want_stats are between()'s; the result is allocated here" % who)
         ts = segment_ts(inbetweens, ease)
@@ -168,7 +128,7 @@ class PoseInterpolator:
             if keys.ndim != 3:
                 raise ValueError("%s: keys must be [K,%d,3]; got %s" % (who, self.Vm, tuple(keys.shape)))
             keys = list(keys)
-        keys = [self._key(k, who, "every key") for k in keys]
+        keys = [self.mesh.rows_f32(k, who, "every key") for k in keys]
         if len(keys) < 2:
             raise ValueError("%s: at least two keys; got %d" % (who, len(keys)))
         n = len(ts)

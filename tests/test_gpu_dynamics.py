@@ -305,15 +305,15 @@ def test_simulate_is_run_and_leaves_the_object_at_the_last_frame(tmp_path):
     assert torch.equal(o.mesh_vertex_current, want[-1])
     exp = q.deform_vertices(want[-1])
     assert all(torch.equal(g, e) for g, e in zip(o.deform_vertices(o.mesh_vertex_current), exp))
-    kept = o._dynamics[4]
+    kept = o._operators["dynamics"]
     again = o.simulate(2, pos[3:], stiffness=20.0)                     # from the current mesh with the velocity the first call left
-    assert o._dynamics[4] is kept and same_bits(again, m.run(2, pos[3:]))
+    assert o._operators["dynamics"] is kept and same_bits(again, m.run(2, pos[3:]))
     m.reset(positions=again[-1])
     cold = o.simulate(2, pos[3:], keep_velocity=False, stiffness=20.0)
     assert same_bits(cold, m.run(2, pos[3:])) and not same_bits(cold, again)
     pins = np.setdiff1d(np.arange(o.vertex.shape[0]), ids)[:2]
     pinned = o.simulate(1, pos[4:], pinned=pins, stiffness=20.0)
-    assert o._dynamics[4] is not kept and bool((pinned[0, _dev(pins, torch.int64)] == cold[-1, _dev(pins, torch.int64)]).all())
+    assert o._operators["dynamics"] is not kept and bool((pinned[0, _dev(pins, torch.int64)] == cold[-1, _dev(pins, torch.int64)]).all())
     # the tool's wrapper, and a free body: no handles chosen, gravity on
     third = _tool(d)
     fall = third.simulate_one_gaussian("Object", 4, gravity=dc.GRAVITY)

@@ -268,12 +268,12 @@ def test_interpolate_to_is_sequence_and_leaves_the_object_at_the_target(tmp_path
     assert torch.equal(o.mesh_vertex_current, first)
     exp = q.deform_vertices(first)
     assert all(torch.equal(g, e) for g, e in zip(o.deform_vertices(o.mesh_vertex_current), exp))
-    kept = o._pose_interp[2]
+    kept = o._operators["pose_interp"]
     again = o.interpolate_to(second, 2, ease="smoothstep", cg_tolerance=1e-8)      # from the current mesh, with the kept interpolator
-    assert o._pose_interp[2] is kept and same_bits(again, p.sequence([first, second], 2, ease="smoothstep", cg_tolerance=1e-8))
+    assert o._operators["pose_interp"] is kept and same_bits(again, p.sequence([first, second], 2, ease="smoothstep", cg_tolerance=1e-8))
     assert torch.equal(o.mesh_vertex_current, second)
     anchored = o.interpolate_to(first, 1, anchors=[0, 5])
-    assert o._pose_interp[2] is not kept
+    assert o._operators["pose_interp"] is not kept
     assert same_bits(anchored, PoseInterpolator(o.vertex, o.faces, anchors=[0, 5]).sequence([second, first], 1))
     # the tool's wrapper, and an object built from tensors alone
     third = _tool(d)
