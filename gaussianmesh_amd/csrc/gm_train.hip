@@ -75,7 +75,8 @@ __global__ __launch_bounds__(256) void mesh_activate_fwd_kernel(const ActArgs a,
 #pragma unroll
   for (int c = 0; c < 3; c++) { const float sc = __expf(a.scaling[i3 + c]); scales[i3 + c] = sc; smax = fmaxf(smax, sc); }
   const float4 q = reinterpret_cast<const float4*>(a.rotation)[i];
-  const float qn = 1.0f / fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-12f);   // F.normalize eps
+  const float qlen = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+  const float qn = 1.0f / (qlen < 1e-12f ? 1e-12f : qlen);   // F.normalize eps; not fmaxf: a NaN |q| stays NaN, as torch's clamp_min keeps it (Jittor's maximum on a NaN: not checked)
   rots[i] = make_float4(q.x * qn, q.y * qn, q.z * qn, q.w * qn);
   opac[i] = sigmoidf(a.opacity[i]);
   if (mr_partial) term = fmaxf(smax - mr_weight * face_radius(a, i3), 0.f);
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(256) void mesh_activate_bwd_kernel(const ActArgs a,
   {
     const float4 q = reinterpret_cast<const float4*>(a.rotation)[i];
     const float len = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-    const float qn = 1.0f / fmaxf(len, 1e-12f);
+    const float qn = 1.0f / (len < 1e-12f ? 1e-12f : len);   // (a NaN |q| stays NaN, as in the forward)
     const float4 g = d_rots ? d_rots[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     if (len > 1e-12f) {                          // d(q/|q|) = (g - y (y.g)) / |q|
       const float4 y = make_float4(q.x * qn, q.y * qn, q.z * qn, q.w * qn);
@@ -162,7 +163,8 @@ __global__ __launch_bounds__(256) void plain_activate_fwd_kernel(int N, const fl
 #pragma unroll
   for (int c = 0; c < 3; c++) { xyz[i3 + c] = xyz_in[i3 + c]; scales[i3 + c] = expf(scaling[i3 + c]); }
   const float4 q = rotation[i];
-  const float n = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-12f);   // F.normalize eps
+  const float len = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+  const float n = len < 1e-12f ? 1e-12f : len;   // F.normalize eps; not fmaxf: a NaN |q| stays NaN, as torch's clamp_min keeps it
   rots[i] = make_float4(q.x / n, q.y / n, q.z / n, q.w / n);
   opac[i] = 1.0f / (1.0f + expf(-opacity[i]));
 }
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(256) void plain_activate_bwd_kernel(int N, const fl
   const float4 q = rotation[i];
   const float4 g = g_rots ? g_rots[i] : make_float4(0.f, 0.f, 0.f, 0.f);
   const float len = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-  const float qn = 1.0f / fmaxf(len, 1e-12f);
+  const float qn = 1.0f / (len < 1e-12f ? 1e-12f : len);   // (a NaN |q| stays NaN, as in the forward)
   if (len > 1e-12f) {                            // d(q/|q|) = (g - y (y.g)) / |q|
     const float4 y = make_float4(q.x * qn, q.y * qn, q.z * qn, q.w * qn);
     const float yd = y.x * g.x + y.y * g.y + y.z * g.z + y.w * g.w;

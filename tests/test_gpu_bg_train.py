@@ -21,20 +21,14 @@ def _rel(a, b):
 @pytest.mark.parametrize("joint", [False, True])
 def test_plain_activate_matches_float64_autograd(joint):
     from gaussianmesh_amd.model_ops import plain_activate
-    g = torch.Generator().manual_seed(1)
-    n = 5000
-    xyz = torch.randn(n, 3, generator=g)
-    scaling = torch.randn(n, 3, generator=g) * 2 - 3
-    rot = torch.randn(n, 4, generator=g)
-    rot[:7] *= 1e-7                                               # near-zero quaternions (above the clamp) ...
-    rot[7] = 0.0                                                  # ... and one at it
-    rot[8] = torch.tensor([1e-14, 0.0, -1e-14, 0.0])
-    opac = torch.randn(n, 1, generator=g) * 10
-    opac[:20, 0] = torch.linspace(-30, 30, 20)                    # |opacity| > 20
+    import plain_activate_ref as P
+    n, extra = 5000, 37
+    # near-zero quaternions above the clamp (rows 0-6), one at it and one below it (7, 8), |opacity| > 20 (rows 0-19): drawn by
+    # plain_activate_ref.present_test_inputs, which test_plain_activate_ref_host.py reads too
+    xyz, scaling, rot, opac, ups = P.present_test_inputs(extra if joint else 0)
     leaves = [t.cuda().requires_grad_(True) for t in (xyz, scaling, rot, opac)]
     ref = [t.detach().double().requires_grad_(True) for t in (xyz, scaling, rot, opac)]
     jb = None
-    extra = 37
     if joint:
         f = dict(dtype=torch.float32, device="cuda")
         jb = {"xyz": torch.full((n + extra, 3), 7.0, **f), "scales": torch.full((n + extra, 3), 7.0, **f),
@@ -48,7 +42,8 @@ def test_plain_activate_matches_float64_autograd(joint):
             assert torch.equal(o[n:], torch.full_like(o[n:], 7.0))   # the tail is never written
     # element-wise too, for the opacities at |x| > 20 (a normwise error would hide them)
     assert (((out[3][:n] if joint else out[3]).detach().cpu().double() - want[3].detach()).abs() / want[3].detach()).max() <= 1e-6
-    ups = [torch.randn(o.shape, generator=g).cuda() for o in out]
+    assert [tuple(u.shape) for u in ups] == [tuple(o.shape) for o in out]
+    ups = [u.cuda() for u in ups]
     sum(((o * u).sum() for o, u in zip(out, ups))).backward()
     sum(((w * u[:n].cpu().double()).sum() for w, u in zip(want, ups))).backward()
     for lf, rf in zip(leaves, ref):
@@ -63,6 +58,16 @@ def test_plain_activate_matches_float64_autograd(joint):
     want_lo = g64[lo] * e / (1 + e) ** 2
     assert ((got[lo] - want_lo).abs() <= 1e-5 * want_lo.abs()).all()
     assert (got[hi].abs() <= 1.2e-7 * g64[hi].abs()).all()
+    # every element of every tensor against float64 (plain_activate_ref.py): the rotation gradient's max-norm is 1.2e12 (row 8, under the
+    # clamp), so the norm-wise figures above hold the ordinary rows to ~1e7 absolute - test_plain_activate_ref_host.py shows what passes them
+    a = [t.numpy() for t in (xyz, scaling, rot, opac)]
+    u = [t[:n].cpu().numpy() for t in ups]
+    ref64, s_abs = P.reference(*a, *u)
+    dev = {t: (o[:n] if joint else o).detach().cpu().numpy() for t, o in zip(P.FWD, out)}
+    dev.update({t: lf.grad.cpu().numpy().reshape(n, -1) for t, lf in zip(P.BWD, leaves)})
+    fig = P.check(dev, ref64, s_abs, a[3], u[3])
+    print("plain_activate, the 5000 rows of this test, worst ratio / bar: " + P.table(fig))
+    assert not P.failures(fig), P.failures(fig)
 
 
 def test_plain_activate_null_gradients_are_zero():

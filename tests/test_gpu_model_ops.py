@@ -215,6 +215,27 @@ def test_mesh_activate_clamp_active_quaternion_gradient():
     assert not msg, msg
 
 
+def test_mesh_activate_nan_rotation_component_makes_its_row_nan():
+    """one NaN component: |q| is NaN, and torch's F.normalize (clamp_min keeps a NaN) makes the whole row NaN, forward and backward - what
+    Jittor's maximum(|x|, eps) returns for a NaN was not checked.  fmaxf(|q|, eps) returned eps instead: three finite rots of ~1e12 beside the NaN and a finite gradient g / eps - found on plain_activate by
+    test_gpu_plain_activate.py::test_the_rows_kept_out_of_the_gate.  No other row and no other tensor of the row is touched."""
+    N = 300
+    ins, labels = R.mesh_edge_inputs(N, seed=9)
+    clean, clean_grads, _ = _mesh_run(ins, R.upstream(N, 9))
+    ins["rot"][5, 2] = np.nan
+    ins["rot"][256, 0] = np.nan
+    got, grads, _ = _mesh_run(ins, R.upstream(N, 9))
+    rows = np.zeros(N, bool)
+    rows[[5, 256]] = True
+    assert np.isnan(got["rots"][rows]).all() and np.isnan(grads["rot"][rows]).all()
+    for k in got:
+        keep = slice(None) if k != "rots" else ~rows
+        assert np.array_equal(got[k][keep].view(np.int32), clean[k][keep].view(np.int32)), k
+    for k in grads:
+        keep = slice(None) if k != "rot" else ~rows
+        assert np.array_equal(grads[k][keep].view(np.int32), clean_grads[k][keep].view(np.int32)), k
+
+
 def _abi_bwd(ins, ups, mr_weight=None, g_mr=None):
     """gm_mesh_activate_bwd at the C ABI: a missing upstream gradient is a NULL pointer (autograd materialises zeros instead, so the
     kernel's null branches are only reached from here).  The outputs start as NaN."""
