@@ -21,6 +21,7 @@ GM_SCENE_OBJECTS_MAX = 32
 GM_ARAP_BATCH_MAX = 64
 GM_POSE_INTERP_BATCH_MAX = 64
 GM_MESH_DYNAMICS_STEPS_MAX = 64
+GM_MESH_CONTACT_COLLIDERS_MAX = 16
 
 
 class BatchFrame(C.Structure):
@@ -76,6 +77,9 @@ SIGNATURES = {
     "gm_pose_interp": (i32, [i32, i32, i32] + [vp] * 8 + [i32] + [vp] * 6 + [i32, f64, vp, vp, vp, sz, vp]),
     "gm_mesh_dynamics_workspace_bytes": (sz, [i32]),
     "gm_mesh_dynamics": (i32, [i32, i32] + [vp] * 6 + [i32] + [vp] * 4 + [f64] * 6 + [i32, i32, f64, vp, vp, vp, vp, sz, vp]),
+    "gm_mesh_dynamics_contact_workspace_bytes": (sz, [i32]),
+    "gm_mesh_dynamics_contact": (i32, [i32, i32] + [vp] * 6 + [i32] + [vp] * 4 + [f64] * 6 + [i32, i32, f64] + [i32, vp, vp, vp, f64]
+                                 + [vp, vp, vp, vp, vp, sz, vp]),
     "gm_ray_mesh_workspace_bytes": (sz, [i32, i32]),
     "gm_ray_mesh": (i32, [i32, vp, vp, i32, vp, i32, vp, f32, f32, vp, vp, vp, vp, sz, vp]),
     "gm_mesh_geodesic_workspace_bytes": (sz, [i32, i32, i32]),

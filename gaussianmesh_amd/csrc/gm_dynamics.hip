@@ -151,15 +151,19 @@ struct DynStepEnd {
 };
 
 // workgroup c: column c of the right-hand side, r and p with it in the one edge loop, the whole PCG of that column (arap_pcg_steps with
-// the diagonal mu), and in a step's last iteration the step's end for this coordinate
+// the diagonal mu), and in a step's last iteration the step's end for this coordinate.  CONTACT (dyn_contact_global_kernel, below): the
+// operator's diagonal part is shift = mu + kappa instead of mu, diag is its Jacobi diagonal, and the right-hand side gains kappa_i c_i;
+// without it kappa, shift and ctall are not read, and dyn_global_kernel is the code it was before the body became a template.
 static_assert(DYN_THREADS == ARAP_WAVES * 64, "dyn_global_kernel strides its rows as arap_pcg_steps does");
-__global__ __launch_bounds__(DYN_THREADS) void dyn_global_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
-                                                                 const double* __restrict__ weights, const float* __restrict__ V0,
-                                                                 const double* __restrict__ Rall, const double* __restrict__ mu,
-                                                                 const double* __restrict__ diag, const int* __restrict__ free_row, double* xall,
-                                                                 double* rall, double* pall, double* qall, double* yall, double* xsall,
-                                                                 double* vsall, int cg_iterations, double tol2, DynStepEnd end) {
-  __shared__ double partA[1][ARAP_WAVES], partB[3][ARAP_WAVES];
+template <bool CONTACT>
+__device__ __forceinline__ void dyn_global_body(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                const double* __restrict__ weights, const float* __restrict__ V0,
+                                                const double* __restrict__ Rall, const double* __restrict__ mu,
+                                                const double* __restrict__ kappa, const double* __restrict__ shift,
+                                                const double* __restrict__ diag, const double* __restrict__ ctall,
+                                                const int* __restrict__ free_row, double* xall, double* rall, double* pall, double* qall,
+                                                double* yall, double* xsall, double* vsall, int cg_iterations, double tol2,
+                                                const DynStepEnd& end, double (*partA)[ARAP_WAVES], double (*partB)[ARAP_WAVES]) {
   const int c = blockIdx.x;
   const double* R = Rall + (size_t)c * Vm * 3;
   double* x = xall + (size_t)c * Vm;
@@ -185,13 +189,17 @@ __global__ __launch_bounds__(DYN_THREADS) void dyn_global_kernel(int Vm, const i
         if (!free_row[j]) bc += w * xj;                            // a held neighbour moves to the right-hand side
       }
       b += mi * y[i];
+      if constexpr (CONTACT) b += kappa[i] * ctall[(size_t)c * Vm + i];
       bc += b;
-      ri = b - (mi * xi + Lx); zi = ri / diag[i];
+      if constexpr (CONTACT) ri = b - (shift[i] * xi + Lx);
+      else ri = b - (mi * xi + Lx);
+      zi = ri / diag[i];
       s3[0] += bc * bc; s3[1] += ri * ri; s3[2] += ri * zi;
     }
     r[i] = ri; p[i] = zi;                                          // held rows: r = p = 0, for the whole solve
   }
-  const ArapPcgResult cg = arap_pcg_steps<true>(Vm, row_offsets, cols, weights, diag, free_row, x, r, p, q, cg_iterations, tol2, s3, partA, partB, mu);
+  const ArapPcgResult cg = arap_pcg_steps<true>(Vm, row_offsets, cols, weights, diag, free_row, x, r, p, q, cg_iterations, tol2, s3, partA, partB,
+                                                CONTACT ? shift : mu);
   if (!end.X_out) return;
   // the step's end: each thread reads back its own rows of x
   double* xs = xsall + (size_t)c * Vm;
@@ -215,6 +223,146 @@ __global__ __launch_bounds__(DYN_THREADS) void dyn_global_kernel(int Vm, const i
   for (int k = threadIdx.x; k < end.H; k += DYN_THREADS) x[clamp_index(end.handle_ids[k], Vm)] = (double)end.next_targets[3 * (size_t)k + c];
 }
 
+__global__ __launch_bounds__(DYN_THREADS) void dyn_global_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                 const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                 const double* __restrict__ Rall, const double* __restrict__ mu,
+                                                                 const double* __restrict__ diag, const int* __restrict__ free_row, double* xall,
+                                                                 double* rall, double* pall, double* qall, double* yall, double* xsall,
+                                                                 double* vsall, int cg_iterations, double tol2, DynStepEnd end) {
+  __shared__ double partA[1][ARAP_WAVES], partB[3][ARAP_WAVES];
+  dyn_global_body<false>(Vm, row_offsets, cols, weights, V0, Rall, mu, nullptr, nullptr, diag, nullptr, free_row, xall, rall, pall, qall, yall, xsall, vsall,
+                         cg_iterations, tol2, end, partA, partB);
+}
+
+// ---------------------------------------------------------------------------------------------
+// CONTACT (gm_mesh_dynamics_contact; INTEGRATION.md section AB): unilateral contact of the free rows with K analytic colliders, as a
+// penalty in projective-dynamics form.  Collider k of step t is row (t K + k) of collider_rows: kind 0 a half-space (nx, ny, nz, d),
+// phi = n . x - d, normal n as given; kind 1 a sphere (cx, cy, cz, r), phi = |x - c| - r, normal (x - c) / |x - c|, (0, 1, 0) at the
+// centre; any other kind is never chosen.  In every iteration, at the iterate X the local step read, free row i takes the collider k* of
+// the smallest phi (`phi < best` from best = +inf: ties to the lowest k, a NaN never), is ACTIVE iff phi* < 0, and then adds
+// kappa_i = mu_i (kc h^2) to its diagonal and kappa_i c_i to its right-hand side, c_i = X_i - phi* n - scale t, with u = X_i - xs_i,
+// t = u - (n . u) n, lim = friction_k* |phi*|, scale = |t| <= lim ? 1 : lim / |t|: the normal part of c_i is the surface point, the
+// tangential part pulls back to where the row was at the step's start, capped by Coulomb's cone.  Inactive, held and handle rows:
+// kappa_i = 0.  The rounding order is dyn_contact_phi's and dyn_contact_row's, spelled out there.
+// KERNELS.  dyn_contact_local (dyn_local_row, then the row's contact: kappa, mu + kappa, mu + kappa + d, c into the workspace, and
+// contact_out in a step's last iteration) and dyn_contact_global (dyn_global_body<true>: dyn_global_kernel's source with the effective
+// diagonal and shift and kappa_i c_i on the right-hand side; dyn_global_kernel, the <false> instantiation, kept its code).  A step
+// stays 2 * iterations launches; no workgroup reads what another wrote in the same launch; no atomics.
+
+struct DynContactWs {
+  double* kappa;   // [Vm] mu_i kc h^2 on active rows, 0 elsewhere
+  double* shift;   // [Vm] mu_i + kappa_i
+  double* diag;    // [Vm] (mu_i + kappa_i) + d_i
+  double* c;       // [3][Vm] the contact targets, 0 on inactive rows
+  char* end;
+  static DynContactWs from(char* p, size_t Vm) {
+    DynContactWs k;
+    k.kappa = carve<double>(p, Vm); k.shift = carve<double>(p, Vm); k.diag = carve<double>(p, Vm); k.c = carve<double>(p, 3 * Vm);
+    k.end = p;
+    return k;
+  }
+};
+
+struct DynColliders {
+  int K;
+  const int* kind;          // [K]
+  const float* rows;        // [K][4] this step's
+  const double* friction;   // [K]
+  double kch2;              // contact_stiffness h^2
+  int* contact_out;         // [Vm] this step's row of contact_out; null: not wanted, or not the step's last iteration
+};
+
+// phi of collider (kind, row) at X, in this order: half-space  fma(nz, X2, fma(ny, X1, nx X0)) - d;  sphere  e = X - c per coordinate,
+// s = sqrt(fma(e2, e2, fma(e1, e1, e0 e0))), s - r.  NaN for a kind that is neither.
+__device__ __forceinline__ double dyn_contact_phi(int kind, const float* __restrict__ row, const double (&X)[3]) {
+  const double a = (double)row[0], b = (double)row[1], c = (double)row[2], d = (double)row[3];
+  if (kind == 0) return fma(c, X[2], fma(b, X[1], a * X[0])) - d;
+  if (kind == 1) {
+    const double e0 = X[0] - a, e1 = X[1] - b, e2 = X[2] - c;
+    return sqrt(fma(e2, e2, fma(e1, e1, e0 * e0))) - d;
+  }
+  return (double)NAN;
+}
+
+// The contact of one free row at the iterate X with the step's start xs: returns 1 + k* if the row is active (0 if not) and then its
+// target in c.  The order of every rounding:
+//   phi_k      dyn_contact_phi, k ascending, kept iff phi_k < best
+//   n          the half-space's row as given; the sphere's e / s per coordinate with e, s as in dyn_contact_phi ((0, 1, 0) at s == 0)
+//   u = X - xs per coordinate;  nu = fma(n2, u2, fma(n1, u1, n0 u0));  t = fma(-nu, n, u) per coordinate
+//   s = sqrt(fma(t2, t2, fma(t1, t1, t0 t0)));  lim = friction fabs(phi);  scale = s <= lim ? 1 : lim / s
+//   c = fma(-scale, t, fma(-phi, n, X)) per coordinate
+__device__ __forceinline__ int dyn_contact_row(const DynColliders& col, const double (&X)[3], const double (&xs)[3], double (&c)[3]) {
+  double best = (double)INFINITY;
+  int which = -1;
+  for (int k = 0; k < col.K; k++) {                                  // uniform addresses: every thread reads collider k
+    const double phi = dyn_contact_phi(col.kind[k], col.rows + 4 * k, X);
+    if (phi < best) { best = phi; which = k; }
+  }
+  if (!(best < 0.0)) return 0;                                       // (which >= 0 here: best left +inf)
+  const float* row = col.rows + 4 * which;
+  double n[3] = {(double)row[0], (double)row[1], (double)row[2]};
+  if (col.kind[which] == 1) {
+    const double e[3] = {X[0] - n[0], X[1] - n[1], X[2] - n[2]};
+    const double s = sqrt(fma(e[2], e[2], fma(e[1], e[1], e[0] * e[0])));
+    if (s == 0.0) { n[0] = 0.0; n[1] = 1.0; n[2] = 0.0; }
+    else { n[0] = e[0] / s; n[1] = e[1] / s; n[2] = e[2] / s; }
+  }
+  const double u[3] = {X[0] - xs[0], X[1] - xs[1], X[2] - xs[2]};
+  const double nu = fma(n[2], u[2], fma(n[1], u[1], n[0] * u[0]));
+  const double t[3] = {fma(-nu, n[0], u[0]), fma(-nu, n[1], u[1]), fma(-nu, n[2], u[2])};
+  const double s = sqrt(fma(t[2], t[2], fma(t[1], t[1], t[0] * t[0])));
+  const double lim = col.friction[which] * fabs(best);
+  const double scale = s <= lim ? 1.0 : lim / s;
+#pragma unroll
+  for (int a = 0; a < 3; a++) c[a] = fma(-scale, t[a], fma(-best, n[a], X[a]));
+  return 1 + which;
+}
+
+__global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_contact_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                            const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                            const double* __restrict__ x, const double* __restrict__ xs,
+                                                                            const double* __restrict__ mu, const int* __restrict__ free_row,
+                                                                            double* __restrict__ R, DynColliders col, double* __restrict__ kappa,
+                                                                            double* __restrict__ shift, double* __restrict__ diag,
+                                                                            double* __restrict__ ct) {
+  const int i = blockIdx.x * DYN_ROW_THREADS + threadIdx.x;
+  if (i >= Vm) return;
+  dyn_local_row(Vm, row_offsets, cols, weights, V0, x, R, i);
+  double d = 0.0;                                                    // arap_row_sum's order: with kappa = 0 the diagonal is dyn_init's
+  for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) d += weights[k];
+  const double m = mu[i];
+  double c[3] = {0.0, 0.0, 0.0}, kap = 0.0;
+  int hit = 0;
+  if (free_row[i]) {
+    const double X[3] = {x[i], x[(size_t)Vm + i], x[2 * (size_t)Vm + i]};
+    const double s[3] = {xs[i], xs[(size_t)Vm + i], xs[2 * (size_t)Vm + i]};
+    hit = dyn_contact_row(col, X, s, c);
+    if (hit) kap = m * col.kch2;
+    else c[0] = c[1] = c[2] = 0.0;
+  }
+  kappa[i] = kap;
+  shift[i] = m + kap;
+  diag[i] = (m + kap) + d;
+#pragma unroll
+  for (int a = 0; a < 3; a++) ct[(size_t)a * Vm + i] = c[a];
+  if (col.contact_out) col.contact_out[i] = hit;
+}
+
+// dyn_global_body with the contact terms: shift = mu + kappa is the operator's diagonal part (diag its Jacobi diagonal), the right-hand
+// side gains kappa_i c_i
+__global__ __launch_bounds__(DYN_THREADS) void dyn_contact_global_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                         const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                         const double* __restrict__ Rall, const double* __restrict__ mu,
+                                                                         const double* __restrict__ kappa, const double* __restrict__ shift,
+                                                                         const double* __restrict__ diag, const double* __restrict__ ctall,
+                                                                         const int* __restrict__ free_row, double* xall, double* rall, double* pall,
+                                                                         double* qall, double* yall, double* xsall, double* vsall,
+                                                                         int cg_iterations, double tol2, DynStepEnd end) {
+  __shared__ double partA[1][ARAP_WAVES], partB[3][ARAP_WAVES];
+  dyn_global_body<true>(Vm, row_offsets, cols, weights, V0, Rall, mu, kappa, shift, diag, ctall, free_row, xall, rall, pall, qall, yall, xsall, vsall,
+                        cg_iterations, tol2, end, partA, partB);
+}
+
 }  // namespace gm
 
 // ---------------------------------------------------------------------------------------------
@@ -230,11 +378,13 @@ size_t gm_mesh_dynamics_workspace_bytes(int Vm) {
   return (size_t)DynWs::from(nullptr, (size_t)Vm).end + 256;
 }
 
-int gm_mesh_dynamics(int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const double* mass,
-                     const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in, const float* v_in,
-                     double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
-                     double cg_tolerance, float* X_out, float* v_out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* fn = "gm_mesh_dynamics";
+// the checks and launches of both entries.  col == null: gm_mesh_dynamics; with col->K == 0 the same launches, so the same bits.
+struct DynContactArgs { int K; const int* kind; const float* rows; const double* friction; double kc; int* contact_out; };
+
+static int dyn_run(const char* fn, const DynContactArgs* col, int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+                   const double* mass, const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in,
+                   const float* v_in, double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
+                   double cg_tolerance, float* X_out, float* v_out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
   if (T < 1 || T > GM_MESH_DYNAMICS_STEPS_MAX) { set_error("%s: T = %d (1 .. %d)", fn, T, GM_MESH_DYNAMICS_STEPS_MAX); return GM_ERR_INVALID_ARG; }
   if (Vm < 1) { set_error("%s: Vm = %d (must be positive)", fn, Vm); return GM_ERR_INVALID_ARG; }
   if (H < 0 || H > Vm) { set_error("%s: H = %d (0 .. Vm = %d)", fn, H, Vm); return GM_ERR_INVALID_ARG; }
@@ -247,6 +397,12 @@ int gm_mesh_dynamics(int T, int Vm, const int* row_offsets, const int* cols, con
   if (iterations < 1) { set_error("%s: iterations = %d (at least 1)", fn, iterations); return GM_ERR_INVALID_ARG; }
   if (cg_iterations < 1) { set_error("%s: cg_iterations = %d (at least 1)", fn, cg_iterations); return GM_ERR_INVALID_ARG; }
   if (!(cg_tolerance >= 0.0) || !dyn_finite(cg_tolerance)) { set_error("%s: cg_tolerance must be finite and not negative", fn); return GM_ERR_INVALID_ARG; }
+  const int K = col ? col->K : 0;
+  if (col) {
+    if (K < 0 || K > GM_MESH_CONTACT_COLLIDERS_MAX) { set_error("%s: K = %d (0 .. %d)", fn, K, GM_MESH_CONTACT_COLLIDERS_MAX); return GM_ERR_INVALID_ARG; }
+    if (!dyn_finite(col->kc) || !(col->kc > 0.0)) { set_error("%s: contact_stiffness must be finite and positive", fn); return GM_ERR_INVALID_ARG; }
+    if (K > 0 && (!col->kind || !col->rows || !col->friction)) { set_error("%s: null pointer (K = %d colliders)", fn, K); return GM_ERR_INVALID_ARG; }
+  }
   if (!row_offsets || !cols || !weights || !V0 || !mass || !held || !x_in || !v_in || !X_out || !v_out || !workspace ||
       (H > 0 && (!handle_ids || !handle_targets))) {
     set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG;
@@ -254,37 +410,77 @@ int gm_mesh_dynamics(int T, int Vm, const int* row_offsets, const int* cols, con
   // the inputs are only read and may alias one another; an output or the workspace meets nothing, except that v_out may be v_in (v_in
   // stands for both: it is read once, by the first launch)
   const size_t row = 12 * (size_t)Vm;
-  const ByteRange rg[11] = {{V0, row, "V0", false}, {mass, 8 * (size_t)Vm, "mass", false}, {held, (size_t)Vm, "held", false},
+  const ByteRange rg[15] = {{V0, row, "V0", false}, {mass, 8 * (size_t)Vm, "mass", false}, {held, (size_t)Vm, "held", false},
                             {H > 0 ? handle_ids : nullptr, 4 * (size_t)H, "handle_ids", false},
                             {H > 0 ? handle_targets : nullptr, 12 * (size_t)H * T, "handle_targets", false}, {x_in, row, "x_in", false},
                             {v_in, row, "v_in", v_out == v_in}, {X_out, row * T, "X_out", true}, {v_out == v_in ? nullptr : v_out, row, "v_out", true},
-                            {stats, 48 * (size_t)T, "stats", true}, {workspace, workspace_bytes, "workspace", true}};
+                            {stats, 48 * (size_t)T, "stats", true}, {workspace, workspace_bytes, "workspace", true},
+                            {K > 0 ? col->kind : nullptr, 4 * (size_t)K, "collider_kind", false},
+                            {K > 0 ? col->rows : nullptr, 16 * (size_t)K * T, "collider_rows", false},
+                            {K > 0 ? col->friction : nullptr, 8 * (size_t)K, "collider_friction", false},
+                            {col ? col->contact_out : nullptr, 4 * (size_t)Vm * T, "contact_out", true}};
   if (int rc = check_ranges(fn, rg)) return rc;
-  const size_t need = gm_mesh_dynamics_workspace_bytes(Vm);
+  const size_t need = col ? gm_mesh_dynamics_contact_workspace_bytes(Vm) : gm_mesh_dynamics_workspace_bytes(Vm);
   if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
   const DynWs k = DynWs::from(workspace, (size_t)Vm);
+  const DynContactWs kc = DynContactWs::from(k.end, (size_t)Vm);   // (pointers only: not touched when K == 0)
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 rows((Vm + DYN_ROW_THREADS - 1) / DYN_ROW_THREADS), threads(DYN_ROW_THREADS);
   const DynGravity grav = {{dt * dt * gx, dt * dt * gy, dt * dt * gz}};
   hipLaunchKernelGGL(dyn_init_kernel, rows, threads, 0, s, Vm, row_offsets, weights, mass, held, x_in, v_in, two_k_h2, dt, grav, k.x, k.y, k.xs, k.vs, k.mu,
                      k.diag, k.free_row);
   if (H > 0) hipLaunchKernelGGL(dyn_handles_kernel, dim3((H + DYN_ROW_THREADS - 1) / DYN_ROW_THREADS), threads, 0, s, Vm, H, handle_ids, handle_targets, k.x);
+  if (K == 0 && col && col->contact_out) GM_HIP(hipMemsetAsync(col->contact_out, 0, 4 * (size_t)Vm * T, s));
   const double tol2 = cg_tolerance * cg_tolerance;
   for (int t = 0; t < T; t++)
     for (int it = 0; it < iterations; it++) {
       DynStepEnd end = {nullptr, nullptr, nullptr, nullptr, handle_ids, H, dt, 1.0 - damping, grav};
-      if (it == iterations - 1) {
+      const bool last = it == iterations - 1;
+      if (last) {
         end.X_out = X_out + 3 * (size_t)Vm * t;
         end.v_out = t == T - 1 ? v_out : nullptr;
         end.stats_row = stats ? stats + 6 * (size_t)t : nullptr;
         end.next_targets = (H > 0 && t + 1 < T) ? handle_targets + 3 * (size_t)H * (t + 1) : nullptr;
       }
-      hipLaunchKernelGGL(dyn_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R);
-      hipLaunchKernelGGL(dyn_global_kernel, dim3(3), dim3(DYN_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.mu, k.diag, k.free_row, k.x, k.r,
-                         k.p, k.q, k.y, k.xs, k.vs, cg_iterations, tol2, end);
+      if (K == 0) {
+        hipLaunchKernelGGL(dyn_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R);
+        hipLaunchKernelGGL(dyn_global_kernel, dim3(3), dim3(DYN_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.mu, k.diag, k.free_row, k.x, k.r,
+                           k.p, k.q, k.y, k.xs, k.vs, cg_iterations, tol2, end);
+        continue;
+      }
+      const DynColliders dc = {K, col->kind, col->rows + 4 * (size_t)K * t, col->friction, col->kc * dt * dt,
+                               (last && col->contact_out) ? col->contact_out + (size_t)Vm * t : nullptr};
+      hipLaunchKernelGGL(dyn_contact_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.xs, k.mu, k.free_row, k.R, dc, kc.kappa,
+                         kc.shift, kc.diag, kc.c);
+      hipLaunchKernelGGL(dyn_contact_global_kernel, dim3(3), dim3(DYN_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.mu, kc.kappa, kc.shift,
+                         kc.diag, kc.c, k.free_row, k.x, k.r, k.p, k.q, k.y, k.xs, k.vs, cg_iterations, tol2, end);
     }
   GM_HIP(hipGetLastError());
   return GM_OK;
+}
+
+int gm_mesh_dynamics(int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const double* mass,
+                     const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in, const float* v_in,
+                     double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
+                     double cg_tolerance, float* X_out, float* v_out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  return dyn_run("gm_mesh_dynamics", nullptr, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt, stiffness,
+                 damping, gx, gy, gz, iterations, cg_iterations, cg_tolerance, X_out, v_out, stats, workspace, workspace_bytes, stream);
+}
+
+size_t gm_mesh_dynamics_contact_workspace_bytes(int Vm) {
+  if (Vm < 1) return 0;
+  return (size_t)DynContactWs::from(DynWs::from(nullptr, (size_t)Vm).end, (size_t)Vm).end + 256;
+}
+
+int gm_mesh_dynamics_contact(int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const double* mass,
+                             const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in,
+                             const float* v_in, double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations,
+                             int cg_iterations, double cg_tolerance, int K, const int* collider_kind, const float* collider_rows,
+                             const double* collider_friction, double contact_stiffness, float* X_out, float* v_out, int* contact_out,
+                             double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  const DynContactArgs col = {K, collider_kind, collider_rows, collider_friction, contact_stiffness, contact_out};
+  return dyn_run("gm_mesh_dynamics_contact", &col, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt,
+                 stiffness, damping, gx, gy, gz, iterations, cg_iterations, cg_tolerance, X_out, v_out, stats, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

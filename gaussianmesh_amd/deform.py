@@ -542,14 +542,15 @@ class SingleObjectDeform:
         self.deform_vertices(meshes[-1])
         return meshes
 
-    def simulate(self, steps, handle_targets=None, pinned=None, keep_velocity=True, faces=None, **options):
+    def simulate(self, steps, handle_targets=None, pinned=None, keep_velocity=True, faces=None, collider_rows=None, **options):
         """`steps` steps of secondary motion (dynamics.MeshDynamics: implicit Euler with the ARAP energy as the potential) from
         mesh_vertex_current (the rest pose the first time): the meshes [steps,Vm,3].  The handles are the ones set_handles /
         set_region_handles chose, scripted to handle_targets [steps,H,3] (in the order of arap.handles); with none chosen the object is
         a free body and handle_targets stays None.  pinned: vertex ids held where they are.  keep_velocity: start from the velocity the
         previous simulate() left (zero the first time); False: from zero.  options: MeshDynamics' mass, density, stiffness, damping,
-        gravity, dt, iterations, cg_iterations, cg_tolerance; the object is built on the first call and kept while faces, handles, pins
-        and options stay the same.  Leaves the object at the last frame through deform_vertices, in the manner of drag_sequence.
+        gravity, dt, iterations, cg_iterations, cg_tolerance, colliders (dynamics.floor / half_space / sphere, or their tuples, lists or
+        dicts) and contact_stiffness; the object is built on the first call and kept while faces, handles, pins and options stay the same
+        (colliders are compared by value).  collider_rows [steps,K,4]: MeshDynamics.run's, for colliders that move.  Leaves the object at the last frame through deform_vertices, in the manner of drag_sequence.
         faces [F,3]: for an object built from tensors alone.  Returns the meshes; no host wait."""
         from .dynamics import MeshDynamics
         import numpy as np
@@ -557,12 +558,19 @@ class SingleObjectDeform:
         ids = lambda a: tuple(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a).reshape(-1).tolist())
         hid = () if getattr(self, "arap", None) is None else ids(self.arap.handles)
         pid = () if pinned is None else ids(pinned)
-        opts = tuple(sorted((k, id(v) if torch.is_tensor(v) or isinstance(v, np.ndarray) else (tuple(v) if isinstance(v, (list, tuple)) else v))
-                            for k, v in options.items()))
+        def frozen(v):                                                 # nested lists, tuples and dicts (colliders) by value
+            if isinstance(v, (list, tuple)):
+                return tuple(frozen(e) for e in v)
+            if isinstance(v, dict):
+                return tuple(sorted((k, frozen(e)) for k, e in v.items()))
+            if torch.is_tensor(v) or isinstance(v, np.ndarray):
+                return tuple(np.asarray(v.detach().cpu() if torch.is_tensor(v) else v).reshape(-1).tolist())
+            return v
+        opts = tuple(sorted((k, id(v) if torch.is_tensor(v) or isinstance(v, np.ndarray) else frozen(v)) for k, v in options.items()))
         dyn = self._operator("dynamics", (hid, pid, opts), lambda: MeshDynamics(self.mesh_graph, None, pinned=list(pid), handles=list(hid), **options))
         current = self.mesh_vertex_current
         dyn.reset(positions=self.vertex if current is None else current, velocities=getattr(self, "_sim_velocity", None) if keep_velocity else None)
-        meshes = dyn.run(steps, handle_targets)
+        meshes = dyn.run(steps, handle_targets, collider_rows=collider_rows)
         self._sim_velocity = dyn.velocities
         self.deform_vertices(meshes[-1])
         return meshes

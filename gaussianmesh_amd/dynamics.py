@@ -5,7 +5,8 @@ local/global iteration of projective dynamics (Bouaziz et al. 2014) with Sorkine
 local step is ArapSolver's, the global step's matrix gains the positive diagonal mass_i / (2 stiffness dt^2), so the system is positive
 definite with no held row at all - a free body is a valid input, which ArapSolver cannot express.  The result is a [steps,Vm,3] stack of
 meshes: what render_sequence, SingleObjectDeform.deform_vertices and edit_sequence --save_meshes take.  Definition, ABI and rules:
-INTEGRATION.md section AA."""
+INTEGRATION.md section AA.  With colliders (floor / half_space / sphere) the free rows cannot enter them: unilateral contact with
+Coulomb-limited friction (gm_mesh_dynamics_contact), INTEGRATION.md section AB."""
 import numpy as np
 import torch
 
@@ -33,6 +34,93 @@ def vertex_masses(vertices, faces, density=1.0):
     return m * float(density)
 
 
+HALF_SPACE, SPHERE = 0, 1          # collider_kind of gm_mesh_dynamics_contact
+
+
+def _friction(who, friction):
+    if isinstance(friction, bool) or not isinstance(friction, (int, float, np.integer, np.floating)) or not np.isfinite(friction) or friction < 0.0:
+        raise ValueError("%s: friction = %r; a finite number >= 0" % (who, friction))
+    return float(friction)
+
+
+def half_space(normal, offset=None, point=None, friction=0.0):
+    """A collider that fills the half-space n . x < d: ("half_space", (nx, ny, nz, d), friction) with the normal normalised.  Give the
+    plane by offset (d itself, for the normalised normal) or by a point on it; neither: through the origin.  ValueError for a zero or
+    non-finite normal, a non-finite plane, both offset and point, a negative friction."""
+    who = "half_space"
+    n = np.asarray(host(normal), np.float64).reshape(-1)
+    if n.shape != (3,) or not np.isfinite(n).all() or not float(np.linalg.norm(n)) > 0.0 or not np.isfinite(np.linalg.norm(n)):
+        raise ValueError("%s: normal must be three finite numbers, not all zero; got %r" % (who, normal))
+    n = n / np.linalg.norm(n)
+    if offset is not None and point is not None:
+        raise ValueError("%s: give the plane by offset or by point, not both" % who)
+    if point is not None:
+        q = np.asarray(host(point), np.float64).reshape(-1)
+        if q.shape != (3,):
+            raise ValueError("%s: point must be three numbers; got %r" % (who, point))
+        d = float(n @ q)
+    else:
+        d = 0.0 if offset is None else float(offset)
+    if not np.isfinite(d):
+        raise ValueError("%s: the plane must be finite; got offset %r, point %r" % (who, offset, point))
+    return ("half_space", (float(n[0]), float(n[1]), float(n[2]), d), _friction(who, friction))
+
+
+def floor(height=0.0, up=(0.0, 1.0, 0.0), friction=0.0):
+    """half_space(up, offset=height): the ground at `height` along `up`"""
+    return half_space(up, offset=height, friction=friction)
+
+
+def sphere(center, radius, friction=0.0):
+    """A solid ball: ("sphere", (cx, cy, cz, r), friction).  ValueError for a non-finite centre, a radius that is not finite and
+    positive, a negative friction."""
+    who = "sphere"
+    c = np.asarray(host(center), np.float64).reshape(-1)
+    if c.shape != (3,) or not np.isfinite(c).all():
+        raise ValueError("%s: center must be three finite numbers; got %r" % (who, center))
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not np.isfinite(radius) or not radius > 0.0:
+        raise ValueError("%s: radius = %r; finite and positive" % (who, radius))
+    return ("sphere", (float(c[0]), float(c[1]), float(c[2]), float(radius)), _friction(who, friction))
+
+
+def _collider(who, c):
+    """one collider, given as half_space / floor / sphere make it (a tuple or list (kind, row, friction), nested lists welcome) or as a
+    dict(kind=, friction=, and normal= with offset= or point= / center=, radius=), checked again: (kind id, row [4], friction)"""
+    if isinstance(c, dict):
+        kind = c.get("kind")
+        extra = set(c) - {"kind", "friction", "normal", "offset", "point", "center", "radius"}
+        if extra:
+            raise ValueError("%s: a collider has no %r" % (who, sorted(extra)[0]))
+        if kind == "half_space":
+            c = half_space(c.get("normal", ()), c.get("offset"), c.get("point"), c.get("friction", 0.0))
+        elif kind == "sphere":
+            c = sphere(c.get("center", ()), c.get("radius"), c.get("friction", 0.0))
+        else:
+            raise ValueError('%s: a collider\'s kind is "half_space" or "sphere"; got %r' % (who, kind))
+    if not isinstance(c, (tuple, list)) or len(c) != 3 or c[0] not in ("half_space", "sphere"):
+        raise ValueError('%s: a collider is ("half_space" | "sphere", (four numbers), friction), as half_space(), floor() and sphere() make it; got %r' % (who, c))
+    row = np.asarray(c[1], np.float64).reshape(-1)
+    if row.shape != (4,):
+        raise ValueError("%s: a collider's row holds four numbers; got %r" % (who, c[1]))
+    if c[0] == "half_space":
+        _, r, mu = half_space(row[:3], offset=row[3], friction=c[2])
+        return HALF_SPACE, r, mu
+    _, r, mu = sphere(row[:3], float(row[3]), friction=c[2])
+    return SPHERE, r, mu
+
+
+def collider_table(colliders, who="collider_table"):
+    """The colliders of MeshDynamics(colliders=...) as the arrays gm_mesh_dynamics_contact reads: (kinds int32 [K], rows float32 [K,4],
+    friction float64 [K]), every collider checked.  rows is what run's collider_rows repeats or replaces per step."""
+    if isinstance(colliders, dict) or not isinstance(colliders, (tuple, list)):
+        raise ValueError("%s: colliders must be a sequence of half_space() / floor() / sphere(); got %r" % (who, colliders))
+    if len(colliders) > _lib.GM_MESH_CONTACT_COLLIDERS_MAX:
+        raise ValueError("%s: %d colliders; at most %d" % (who, len(colliders), _lib.GM_MESH_CONTACT_COLLIDERS_MAX))
+    parsed = [_collider(who, c) for c in colliders]
+    return (np.array([c[0] for c in parsed], np.int32), np.array([c[1] for c in parsed], np.float32).reshape(len(parsed), 4),
+            np.array([c[2] for c in parsed], np.float64))
+
+
 class MeshDynamics:
     """The motion of one mesh under scripted handles, pins, gravity and its own elasticity.  Built once: the mesh's MeshGraph (given as
     rest_vertices with faces=None, it is shared), the masses, the masks, and on a device the state (float32 [Vm,3] each) and the workspace.
@@ -47,11 +135,23 @@ class MeshDynamics:
     within a few seconds at dt = 1 / 30); cg_iterations = 64 and cg_tolerance = 1e-6 are ArapSolver.solve's.
     ValueError for shapes, ids out of range or given twice, a handle that is also pinned, a mass that is not finite or not positive
     where it counts, and parameters outside their ranges (dt, stiffness > 0, damping in [0, 1), iterations, cg_iterations >= 1,
-    cg_tolerance >= 0, all finite)."""
+    cg_tolerance >= 0, all finite).
+    colliders: up to GM_MESH_CONTACT_COLLIDERS_MAX (16) of half_space() / floor() / sphere() (or their tuples, lists or dicts): what the
+    free rows cannot enter (gm_mesh_dynamics_contact, INTEGRATION.md section AB).  A free row that is inside a collider at an iterate is
+    pushed to its surface with the stiffness contact_stiffness x mass_i and held back tangentially, towards where it was at the step's
+    start, by at most the collider's friction times the normal push; a body at rest on a floor sinks in by about |gravity| /
+    contact_stiffness.  Handle and pinned rows never take part.  Friction is measured in the world frame: give a moving pusher
+    friction 0.  The default contact_stiffness = 1e4 is an unmeasured starting value (a unit-size object under |g| = 9.8 rests about 1e-3
+    deep).  With no colliders every call goes through gm_mesh_dynamics, exactly as without these two arguments.  ValueError for a zero or
+    non-finite normal, a radius <= 0, a negative friction, more than 16 colliders, a contact_stiffness that is not finite and positive."""
 
     def __init__(self, rest_vertices, faces, pinned=(), handles=(), mass="area", density=1.0, stiffness=10.0, damping=0.02, gravity=(0.0, 0.0, 0.0),
-                 dt=1.0 / 30.0, iterations=3, cg_iterations=64, cg_tolerance=1e-6, device="cuda"):
+                 dt=1.0 / 30.0, iterations=3, cg_iterations=64, cg_tolerance=1e-6, device="cuda", colliders=(), contact_stiffness=1.0e4):
         who = "MeshDynamics"
+        table = collider_table(colliders, who)
+        kc = contact_stiffness
+        if isinstance(kc, bool) or not isinstance(kc, (int, float, np.integer, np.floating)) or not np.isfinite(kc) or not kc > 0.0:
+            raise ValueError("%s: contact_stiffness = %r; finite and positive" % (who, kc))
         mesh = self.mesh = MeshGraph.of(rest_vertices, faces, device, who)
         self.device, Vm = mesh.device, mesh.Vm
         if isinstance(mass, str):
@@ -77,10 +177,16 @@ class MeshDynamics:
         self.Vm, self.F, self.csr, self.mass = Vm, mesh.F, mesh.csr, m
         self.dt, self.stiffness, self.damping, self.gravity = float(dt), float(stiffness), float(damping), tuple(float(x) for x in g)
         self.iterations, self.cg_iterations, self.cg_tolerance = int(iterations), int(cg_iterations), float(cg_tolerance)
+        self.K, self.contact_stiffness = len(table[0]), float(kc)
+        self.collider_kinds, self.collider_rows, self.collider_friction = table
         self._x = self._v = self._ws = None
         if self.device.type == "cuda":
             self.rest, self._off, self._cols, self._w = mesh.device_csr
             self._mass = on_device(m, torch.float64, self.device)
+            if self.K:
+                self._kinds = on_device(self.collider_kinds, torch.int32, self.device)
+                self._rows = on_device(self.collider_rows, torch.float32, self.device)
+                self._mus = on_device(self.collider_friction, torch.float64, self.device)
         self.set_constraints(pinned, handles)
         if self.device.type == "cuda":
             self.reset()
@@ -125,25 +231,36 @@ class MeshDynamics:
         self.mesh.need_device("MeshDynamics.velocities")
         return self._v.clone()
 
-    def step(self, handle_targets=None):
-        """One step: the new positions [Vm,3]; handle_targets [H,3] (in the order of `handles`) exactly when there are handles.
-        run(1, handle_targets[None])[0]."""
+    def step(self, handle_targets=None, collider_rows=None):
+        """One step: the new positions [Vm,3]; handle_targets [H,3] (in the order of `handles`) exactly when there are handles;
+        collider_rows [K,4]: where the colliders are in this step (None: where they were built).
+        run(1, handle_targets[None], collider_rows[None])[0]."""
+        if collider_rows is not None:
+            if not hasattr(collider_rows, "shape"):
+                collider_rows = np.asarray(collider_rows, np.float32)
+            if len(collider_rows.shape) != 2:
+                raise ValueError("MeshDynamics.step: collider_rows must be [%d,4]; got %s" % (self.K, tuple(collider_rows.shape)))
+            collider_rows = collider_rows[None]
         if handle_targets is not None:
             if not hasattr(handle_targets, "shape"):
                 handle_targets = np.asarray(handle_targets, np.float32)
             if len(handle_targets.shape) != 2:
                 raise ValueError("MeshDynamics.step: handle_targets must be [%d,3]; got %s" % (len(self.handles), tuple(handle_targets.shape)))
             handle_targets = handle_targets[None]
-        return self.run(1, handle_targets)[0]
+        return self.run(1, handle_targets, collider_rows=collider_rows)[0]
 
-    def run(self, steps, handle_targets=None, out=None, want_stats=False):
+    def run(self, steps, handle_targets=None, out=None, want_stats=False, collider_rows=None, want_contacts=False):
         """`steps` steps from the state, which they advance: the positions after every step, [steps,Vm,3] float32 on the device.
         handle_targets [steps,H,3]: where the handles are in every step - required exactly when there are handles.  Cut into launch
         chains of at most GM_MESH_DYNAMICS_STEPS_MAX (64) steps; the state is rounded to float32 at every step boundary, so run(n) is
         bit for bit n calls of step().  out: a contiguous float32 [steps,Vm,3] tensor on the device.  With want_stats returns (meshes,
         stats float64 [steps,6]): CG steps used for x / y / z and final |r| / |b| for x / y / z in each step's last iteration.
+        collider_rows [steps,K,4] float32: the colliders' rows in every step ((nx, ny, nz, d) with a unit normal / (cx, cy, cz, r)), which
+        is how they move; a tensor on the device is taken as it is, a host array is checked (finite, normals of unit length within 1e-4,
+        radii positive); None: the rows they were built with, in every step.  want_contacts: also int32 [steps,Vm], 1 + the index of the
+        collider every row was in contact with in the step's last iteration, 0 elsewhere; returned after the meshes (and before stats).
         Stream-ordered; nothing here waits for the device (reading stats does).  ValueError for steps < 1, shapes, handle_targets without
-        handles and handles without handle_targets; GmeshError without a device."""
+        handles and handles without handle_targets, collider_rows without colliders; GmeshError without a device."""
         who = "MeshDynamics.run"
         if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
             raise ValueError("%s: steps = %r; an integer >= 1" % (who, steps))
@@ -157,6 +274,19 @@ class MeshDynamics:
                 handle_targets = np.asarray(handle_targets, np.float32)
             if tuple(handle_targets.shape) != (T, H, 3):
                 raise ValueError("%s: handle_targets must be [%d,%d,3]; got %s" % (who, T, H, tuple(handle_targets.shape)))
+        K = self.K
+        if collider_rows is not None:
+            if K == 0:
+                raise ValueError("%s: collider_rows given, but there are no colliders" % who)
+            if not hasattr(collider_rows, "shape"):
+                collider_rows = np.asarray(collider_rows, np.float32)
+            if tuple(collider_rows.shape) != (T, K, 4):
+                raise ValueError("%s: collider_rows must be [%d,%d,4]; got %s" % (who, T, K, tuple(collider_rows.shape)))
+            if not torch.is_tensor(collider_rows):
+                r = np.asarray(collider_rows, np.float64)
+                flat = self.collider_kinds == HALF_SPACE
+                if not np.isfinite(r).all() or bool((np.abs(np.linalg.norm(r[:, flat, :3], axis=2) - 1.0) > 1e-4).any()) or bool((r[:, ~flat, 3] <= 0.0).any()):
+                    raise ValueError("%s: collider_rows must be finite, a half-space's normal of unit length, a sphere's radius positive" % who)
         self.mesh.need_device(who)
         dev = self.rest.device
         hp = None
@@ -164,16 +294,28 @@ class MeshDynamics:
             hp = on_device(handle_targets, torch.float32, dev)
         out = self.mesh.out_f32(out, (T, Vm, 3), who)
         stats = torch.zeros((T, 6), dtype=torch.float64, device=dev) if want_stats else None
+        contacts = None
+        if want_contacts:
+            contacts = torch.zeros((T, Vm), dtype=torch.int32, device=dev) if K == 0 else torch.empty((T, Vm), dtype=torch.int32, device=dev)
+        entry = "gm_mesh_dynamics" if K == 0 else "gm_mesh_dynamics_contact"
         if self._ws is None:
-            need = _lib.lib().gm_mesh_dynamics_workspace_bytes(Vm)
+            need = getattr(_lib.lib(), entry + "_workspace_bytes")(Vm)
             self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+        if K > 0:
+            cp = self._rows.unsqueeze(0).expand(min(T, _lib.GM_MESH_DYNAMICS_STEPS_MAX), K, 4).contiguous() if collider_rows is None \
+                else on_device(collider_rows, torch.float32, dev)
         top = _lib.GM_MESH_DYNAMICS_STEPS_MAX
         g = self.gravity
         for s in range(0, T, top):
             e = min(s + top, T)
-            enqueue(dev, "gm_mesh_dynamics", e - s, Vm, self._off, self._cols, self._w, self.rest, self._mass, self._held, H, self._handle_ids,
-                    None if hp is None else hp[s:e], self._x if s == 0 else out[s - 1], self._v, self.dt, self.stiffness, self.damping, g[0], g[1], g[2],
-                    self.iterations, self.cg_iterations, self.cg_tolerance, out[s:e], self._v, None if stats is None else stats[s:e],
-                    workspace=self._ws)
+            state = (e - s, Vm, self._off, self._cols, self._w, self.rest, self._mass, self._held, H, self._handle_ids, None if hp is None else hp[s:e],
+                     self._x if s == 0 else out[s - 1], self._v, self.dt, self.stiffness, self.damping, g[0], g[1], g[2], self.iterations,
+                     self.cg_iterations, self.cg_tolerance)
+            if K == 0:                                                 # exactly the call there was before there were colliders
+                enqueue(dev, entry, *state, out[s:e], self._v, None if stats is None else stats[s:e], workspace=self._ws)
+            else:
+                enqueue(dev, entry, *state, K, self._kinds, cp[:e - s] if collider_rows is None else cp[s:e], self._mus, self.contact_stiffness,
+                        out[s:e], self._v, None if contacts is None else contacts[s:e], None if stats is None else stats[s:e], workspace=self._ws)
         self._x.copy_(out[T - 1])
-        return (out, stats) if want_stats else out
+        got = (out,) + ((contacts,) if want_contacts else ()) + ((stats,) if want_stats else ())
+        return got if len(got) > 1 else out

@@ -4,7 +4,8 @@
         (--mesh_sequence DIR | --handle_sequence FILE.npz | --pick_sequence FILE.json) --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N]
         [--frames_per_launch 4] [--save_maps] [--save_meshes] [--save_baked PATH] [--background_gaussian BG.ply [--is_exist_bg]]
         [--arap_global_step {column,grid}] [--arap_batch K] [--inbetweens N [--ease {linear,smoothstep}]]
-        [--dynamics [--settle N] [--dt S] [--stiffness K] [--damping G] [--gravity X Y Z]]
+        [--dynamics [--settle N] [--dt S] [--stiffness K] [--damping G] [--gravity X Y Z]
+                    [--floor H] [--friction MU] [--contact_stiffness KC] [--colliders FILE.json]]
 
 --object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
 faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of the two.
@@ -43,6 +44,13 @@ position in each frame; anchors and held regions are rows whose scripted positio
 --damping and --gravity X Y Z set the material, by default MeshDynamics' own.  Refused with --mesh_sequence (there is nothing to solve),
 with --arap_batch above 1 and with --inbetweens above 0; --settle and the material flags are refused without --dynamics.  Without these
 flags nothing changes.
+--floor H (with --dynamics and a non-zero --gravity): the ground, a half-space whose normal is opposite to gravity and whose surface lies at
+height H along that normal (dynamics.floor); the simulated mesh cannot sink through it.  --friction MU: the floor's Coulomb friction, and
+the default of the colliders of --colliders (0 without it).  --contact_stiffness KC: MeshDynamics' contact_stiffness (a body rests about
+|gravity| / KC deep).  --colliders FILE.json: a list of {"kind": "half_space", "normal": [x, y, z], "offset": d or "point": [x, y, z],
+"friction": mu} and {"kind": "sphere", "radius": r, "center": [x, y, z] or "centers": [[x, y, z], ...], "friction": mu}; "centers" gives a
+moving ball its centre in every frame (the last one is kept for frames beyond the list, --settle's included).  At most 16 colliders with
+the floor.  All four are refused without --dynamics; without them nothing changes.
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
@@ -119,6 +127,33 @@ def read_pick_sequence(path):
     return cam, handles, anchors, offsets, (grab, free)
 
 
+def read_colliders(path, friction):
+    """A --colliders file -> (colliders: a list of dicts for MeshDynamics, moving: {index: centres [[x, y, z], ...]}); SystemExit naming
+    what is wrong with it.  Host work only, no numpy; the numbers themselves are MeshDynamics' to check."""
+    import json
+    bad = lambda what: SystemExit("edit_sequence: %s: %s" % (path, what))
+    try:
+        with open(path) as fh:
+            doc = json.load(fh)
+    except (OSError, ValueError) as e:
+        raise bad("cannot read it as JSON (%s)" % e)
+    if not isinstance(doc, list) or not all(isinstance(c, dict) for c in doc):
+        raise bad('must hold a JSON list of {"kind": "sphere" | "half_space", ...} objects')
+    colliders, moving = [], {}
+    for i, c in enumerate(doc):
+        c = dict(c)
+        c.setdefault("friction", friction)
+        if c.get("kind") == "sphere" and "centers" in c:
+            cs = c.pop("centers")
+            if "center" in c or not isinstance(cs, list) or not cs or not all(isinstance(q, list) and len(q) == 3 for q in cs):
+                raise bad('collider %d: "centers" must be a list of [x, y, z], at least one, and stands instead of "center"' % i)
+            moving[i], c["center"] = cs, cs[0]
+        elif c.get("kind") not in ("sphere", "half_space"):
+            raise bad('collider %d: "kind" must be "sphere" or "half_space"; got %r' % (i, c.get("kind")))
+        colliders.append(c)
+    return colliders, moving
+
+
 def main(argv=None):
     parser = ArgumentParser(description="Render a mesh-driven animation of a mesh-bound Gaussian object")
     which = parser.add_mutually_exclusive_group(required=True)
@@ -143,6 +178,10 @@ def main(argv=None):
     parser.add_argument("--stiffness", type=float, default=None)
     parser.add_argument("--damping", type=float, default=None)
     parser.add_argument("--gravity", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
+    parser.add_argument("--floor", type=float, default=None, metavar="H")
+    parser.add_argument("--friction", type=float, default=None, metavar="MU")
+    parser.add_argument("--contact_stiffness", type=float, default=None, metavar="KC")
+    parser.add_argument("--colliders", type=str, default=None, metavar="FILE.json")
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
     parser.add_argument("--save_maps", action="store_true", default=False)
@@ -166,6 +205,10 @@ def main(argv=None):
         for flag, value in (("--dt", args.dt), ("--stiffness", args.stiffness), ("--damping", args.damping), ("--gravity", args.gravity)):
             if value is not None:
                 raise SystemExit("edit_sequence: %s sets the simulated material and needs --dynamics" % flag)
+        for flag, value in (("--floor", args.floor), ("--friction", args.friction), ("--contact_stiffness", args.contact_stiffness),
+                            ("--colliders", args.colliders)):
+            if value is not None:
+                raise SystemExit("edit_sequence: %s sets what the simulated mesh collides with and needs --dynamics" % flag)
     if args.dynamics:
         if args.mesh_sequence is not None:
             raise SystemExit("edit_sequence: --dynamics simulates the frames of --handle_sequence / --pick_sequence; --mesh_sequence has ready-made meshes")
@@ -173,6 +216,15 @@ def main(argv=None):
             raise SystemExit("edit_sequence: --dynamics with --arap_batch %d: a simulated step starts from its predecessor; drop --arap_batch" % args.arap_batch)
         if args.inbetweens > 0:
             raise SystemExit("edit_sequence: --dynamics with --inbetweens %d: simulated frames are no key poses; drop one of the two" % args.inbetweens)
+        if args.floor is not None and (args.gravity is None or not any(args.gravity)):
+            raise SystemExit("edit_sequence: --floor lies opposite to gravity and needs a non-zero --gravity X Y Z")
+        if args.friction is not None and args.floor is None and args.colliders is None:
+            raise SystemExit("edit_sequence: --friction is the friction of --floor and --colliders; give one of them")
+        if args.contact_stiffness is not None and args.floor is None and args.colliders is None:
+            raise SystemExit("edit_sequence: --contact_stiffness needs something to collide with: --floor or --colliders")
+        colliders, moving = ([], {}) if args.colliders is None else read_colliders(args.colliders, args.friction or 0.0)
+        if args.floor is not None:
+            colliders.append(dict(kind="half_space", normal=[0.0 - g for g in args.gravity], offset=args.floor, friction=args.friction or 0.0))
     if args.pick_sequence is not None:
         pick = read_pick_sequence(args.pick_sequence)
         (pick_camera, pick_handles, pick_anchors, pick_offsets), pick_radii = pick[:4], (pick[4] if len(pick) > 4 else None)
@@ -233,8 +285,22 @@ def main(argv=None):
                 pos = torch.cat([pos, pos[-1:].expand(args.settle, -1, -1)], 0)
             material = {k: v for k, v in (("dt", args.dt), ("stiffness", args.stiffness), ("damping", args.damping),
                                           ("gravity", None if args.gravity is None else tuple(args.gravity))) if v is not None}
+            rows = None
+            if colliders:
+                material["colliders"] = colliders
+                if args.contact_stiffness is not None:
+                    material["contact_stiffness"] = args.contact_stiffness
+            if moving:                                                                # the centres of the moving balls, frame by frame
+                from .dynamics import collider_table
+                try:
+                    rows = np.tile(collider_table(colliders, "--colliders")[1], (len(pos), 1, 1))
+                    for i, cs in moving.items():
+                        c = np.asarray(cs, np.float32)
+                        rows[:, i, :3] = c[np.minimum(np.arange(len(pos)), len(c) - 1)]
+                except ValueError as e:
+                    raise SystemExit("edit_sequence: --colliders: %s" % e)
             try:
-                meshes = list(obj.simulate(len(pos), pos, **material))
+                meshes = list(obj.simulate(len(pos), pos, collider_rows=rows, **material))
             except ValueError as e:
                 raise SystemExit("edit_sequence: --dynamics: %s" % e)
         else:

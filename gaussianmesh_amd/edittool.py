@@ -226,14 +226,15 @@ class ObjectVisualTool:
                 meshes = g.interpolate_to(target, inbetweens, **options)
         return meshes
 
-    def simulate_one_gaussian(self, name, steps, handle_targets=None, **options):
+    def simulate_one_gaussian(self, name, steps, handle_targets=None, collider_rows=None, **options):
         """`steps` simulated steps of the objects called `name` from their current mesh (SingleObjectDeform.simulate: secondary motion,
-        dynamics.MeshDynamics) with their handles at handle_targets [steps,H,3]; the objects are left at the last frame.  Returns the
+        dynamics.MeshDynamics) with their handles at handle_targets [steps,H,3] and, with colliders= among the options, those at
+        collider_rows [steps,K,4] (None: where they were built); the objects are left at the last frame.  Returns the
         meshes [steps, Vm, 3] of the last such object (None if there is none)."""
         meshes = None
         for g in self.gaussians_list:
             if g.get_name() == name:
-                meshes = g.simulate(steps, handle_targets, **options)
+                meshes = g.simulate(steps, handle_targets, collider_rows=collider_rows, **options)
         return meshes
 
     def drag_region_one_gaussian(self, name, handle_vertices, displacements, grab_radius, free_radius=None, anchor_vertices=(), **solve_options):

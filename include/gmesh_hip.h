@@ -391,6 +391,37 @@ int gm_mesh_dynamics(int T, int Vm, const int* row_offsets, const int* cols, con
                      double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
                      double cg_tolerance, float* X_out, float* v_out, double* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* gm_mesh_dynamics with unilateral contact against K analytic colliders (dynamics.MeshDynamics(colliders=...); definition:
+ * csrc/gm_dynamics.hip, INTEGRATION.md section AB).  Every argument of gm_mesh_dynamics means what it means there.  K in
+ * 0 .. GM_MESH_CONTACT_COLLIDERS_MAX; collider_kind int32 [K]: 0 a half-space, 1 a sphere; collider_rows float [T,K,4]: step t reads rows
+ * [t]: (nx, ny, nz, d) of a half-space, whose solid is n . x < d: phi = n . x - d and the normal is n AS GIVEN (the caller normalises
+ * it; the kernel does not), or (cx, cy, cz, r) of a sphere: phi = |x - c| - r, normal (x - c) / |x - c|, (0, 1, 0) at the centre;
+ * collider_friction double [K], each >= 0; contact_stiffness kc > 0.  All float64 on the float32 rows.  In each of a step's iterations,
+ * at the iterate X the local step reads and before its right-hand side is used, every free row i (held and handle rows never):
+ *   k* = the collider of the smallest phi_k(X_i): compared as phi < best from +inf, so ties go to the lowest k and a NaN is never chosen;
+ *   the row is active iff phi* < 0;  kappa_i = mu_i (kc h^2) if active, else 0;
+ *   c_i = X_i - phi* n - scale t,  u = X_i - xs_i (xs: the state at the step's start), t = u - (n . u) n, lim = friction_k* |phi*|,
+ *   scale = |t| <= lim ? 1 : lim / |t|;
+ *   the global step solves (mu_i + kappa_i) X_i + sum_j w_ij (X_i - X_j) = mu_i y_i + kappa_i c_i + (the rotations' term) with the Jacobi
+ *   diagonal (mu_i + kappa_i) + d_i, warm start and stopping rules unchanged.
+ * - the contact energy sum_i (kc mass_i / 2) min(phi(X_i), 0)^2 with Coulomb-limited friction against the world frame; restitution 0.  The
+ * step's end is gm_mesh_dynamics's.  contact_out (optional) int32 [T,Vm]: 1 + k* of every row active in the step's LAST iteration, 0
+ * elsewhere, held rows included.  A step stays 2 * iterations launches.  With K == 0 the launches are gm_mesh_dynamics's own and so are
+ * the bits (contact_out, if given, is zeroed).  THE CALLER'S CHECKS, beyond gm_mesh_dynamics's: every kind 0 or 1 (in the kernel a
+ * collider of any other kind has phi = NaN and is never chosen), every friction >= 0, half-space normals of unit length.
+ * Refused as gm_mesh_dynamics refuses, and with GM_ERR_INVALID_ARG: K < 0 or K > GM_MESH_CONTACT_COLLIDERS_MAX, a contact_stiffness that is
+ * not finite and positive, a NULL among collider_kind / collider_rows / collider_friction when K > 0, any overlap of contact_out with
+ * another buffer or of an output or the workspace with a collider array; with GM_ERR_BUFFER a workspace below
+ * gm_mesh_dynamics_contact_workspace_bytes(Vm) (gm_mesh_dynamics's plus six doubles per vertex; required for every K). */
+#define GM_MESH_CONTACT_COLLIDERS_MAX 16
+size_t gm_mesh_dynamics_contact_workspace_bytes(int Vm);
+int gm_mesh_dynamics_contact(int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const double* mass,
+                             const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in,
+                             const float* v_in, double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations,
+                             int cg_iterations, double cg_tolerance, int K, const int* collider_kind, const float* collider_rows,
+                             const double* collider_friction, double contact_stiffness, float* X_out, float* v_out, int* contact_out,
+                             double* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* First hit of every ray on a mesh: what takes an editor from a pixel to a vertex of the current, deformed proxy mesh
  * (mesh_pick.ray_mesh_hits / pick / visible_vertices).  The reference has no such stage: the result is defined by arithmetic.
  * origins, dirs float [R,3], vertices float [Vm,3], faces int32 [F,3] vertex ids.  out_t float [R], out_face int32 [R], out_uv float
