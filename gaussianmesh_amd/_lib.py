@@ -80,6 +80,10 @@ SIGNATURES = {
     "gm_mesh_dynamics_contact_workspace_bytes": (sz, [i32]),
     "gm_mesh_dynamics_contact": (i32, [i32, i32] + [vp] * 6 + [i32] + [vp] * 4 + [f64] * 6 + [i32, i32, f64] + [i32, vp, vp, vp, f64]
                                  + [vp, vp, vp, vp, vp, sz, vp]),
+    "gm_sdf_grid_prepare": (i32, [i32, i32, i32, vp, vp, f32, f32, f32, vp, vp]),
+    "gm_sdf_grid_sample": (i32, [i32, vp, i32, i32, i32, C.POINTER(f32), f32, vp, vp, vp, vp]),
+    "gm_mesh_dynamics_field": (i32, [i32, i32] + [vp] * 6 + [i32] + [vp] * 4 + [f64] * 6 + [i32, i32, f64] + [i32, vp, vp, vp, f64]
+                               + [i32, i32, i32, C.POINTER(f32), f32, vp, f64] + [vp, vp, vp, vp, vp, sz, vp]),
     "gm_ray_mesh_workspace_bytes": (sz, [i32, i32]),
     "gm_ray_mesh": (i32, [i32, vp, vp, i32, vp, i32, vp, f32, f32, vp, vp, vp, vp, sz, vp]),
     "gm_mesh_geodesic_workspace_bytes": (sz, [i32, i32, i32]),

@@ -33,6 +33,7 @@
 #include "gm_check.h"
 #include "gm_mat3.h"
 #include "gm_arap_shared.h"
+#include "gm_sdf.h"
 
 namespace gm {
 
@@ -363,6 +364,85 @@ __global__ __launch_bounds__(DYN_THREADS) void dyn_contact_global_kernel(int Vm,
                         cg_iterations, tol2, end, partA, partB);
 }
 
+// ---------------------------------------------------------------------------------------------
+// FIELD CONTACT (gm_mesh_dynamics_field; INTEGRATION.md section AC): the K analytic colliders and, as candidate K, a prepared
+// signed-distance grid (gm_sdf.hip) that is static over the call.  A free row evaluates the analytic colliders exactly as
+// dyn_contact_row does (k ascending, phi < best), then the field's (phi, n) = sdf_sample(grid, X) with the same phi < best: ties go to
+// the analytic collider, and a NaN - a row outside the grid, next to an unknown sample, on a gradient without a direction - is never
+// chosen.  An active row takes dyn_contact_row's kappa, c and Coulomb cap, in its rounding order, with the winner's (phi, n, friction);
+// contact_out is 1 + K for the field.  This stands BESIDE dyn_contact_row and dyn_contact_local_kernel, which keep their code; the
+// global launch is dyn_contact_global_kernel itself.
+
+struct DynField {
+  SdfGrid grid;
+  double friction;
+};
+
+__device__ __forceinline__ int dyn_field_row(const DynColliders& col, const DynField& fld, const double (&X)[3], const double (&xs)[3], double (&c)[3]) {
+  double best = (double)INFINITY;
+  int which = -1;
+  for (int k = 0; k < col.K; k++) {
+    const double phi = dyn_contact_phi(col.kind[k], col.rows + 4 * k, X);
+    if (phi < best) { best = phi; which = k; }
+  }
+  double n[3] = {0.0, 0.0, 0.0};
+  const double fphi = sdf_sample(fld.grid, X, n);
+  if (fphi < best) { best = fphi; which = col.K; }
+  if (!(best < 0.0)) return 0;
+  double friction = fld.friction;
+  if (which < col.K) {                                               // an analytic collider won: dyn_contact_row's normal
+    const float* row = col.rows + 4 * which;
+    n[0] = (double)row[0]; n[1] = (double)row[1]; n[2] = (double)row[2];
+    if (col.kind[which] == 1) {
+      const double e[3] = {X[0] - n[0], X[1] - n[1], X[2] - n[2]};
+      const double s = sqrt(fma(e[2], e[2], fma(e[1], e[1], e[0] * e[0])));
+      if (s == 0.0) { n[0] = 0.0; n[1] = 1.0; n[2] = 0.0; }
+      else { n[0] = e[0] / s; n[1] = e[1] / s; n[2] = e[2] / s; }
+    }
+    friction = col.friction[which];
+  }
+  const double u[3] = {X[0] - xs[0], X[1] - xs[1], X[2] - xs[2]};
+  const double nu = fma(n[2], u[2], fma(n[1], u[1], n[0] * u[0]));
+  const double t[3] = {fma(-nu, n[0], u[0]), fma(-nu, n[1], u[1]), fma(-nu, n[2], u[2])};
+  const double s = sqrt(fma(t[2], t[2], fma(t[1], t[1], t[0] * t[0])));
+  const double lim = friction * fabs(best);
+  const double scale = s <= lim ? 1.0 : lim / s;
+#pragma unroll
+  for (int a = 0; a < 3; a++) c[a] = fma(-scale, t[a], fma(-best, n[a], X[a]));
+  return 1 + which;
+}
+
+// dyn_contact_local_kernel with dyn_field_row as the row's contact
+__global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_field_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                          const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                          const double* __restrict__ x, const double* __restrict__ xs,
+                                                                          const double* __restrict__ mu, const int* __restrict__ free_row,
+                                                                          double* __restrict__ R, DynColliders col, DynField fld,
+                                                                          double* __restrict__ kappa, double* __restrict__ shift,
+                                                                          double* __restrict__ diag, double* __restrict__ ct) {
+  const int i = blockIdx.x * DYN_ROW_THREADS + threadIdx.x;
+  if (i >= Vm) return;
+  dyn_local_row(Vm, row_offsets, cols, weights, V0, x, R, i);
+  double d = 0.0;
+  for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) d += weights[k];
+  const double m = mu[i];
+  double c[3] = {0.0, 0.0, 0.0}, kap = 0.0;
+  int hit = 0;
+  if (free_row[i]) {
+    const double X[3] = {x[i], x[(size_t)Vm + i], x[2 * (size_t)Vm + i]};
+    const double s[3] = {xs[i], xs[(size_t)Vm + i], xs[2 * (size_t)Vm + i]};
+    hit = dyn_field_row(col, fld, X, s, c);
+    if (hit) kap = m * col.kch2;
+    else c[0] = c[1] = c[2] = 0.0;
+  }
+  kappa[i] = kap;
+  shift[i] = m + kap;
+  diag[i] = (m + kap) + d;
+#pragma unroll
+  for (int a = 0; a < 3; a++) ct[(size_t)a * Vm + i] = c[a];
+  if (col.contact_out) col.contact_out[i] = hit;
+}
+
 }  // namespace gm
 
 // ---------------------------------------------------------------------------------------------
@@ -378,10 +458,12 @@ size_t gm_mesh_dynamics_workspace_bytes(int Vm) {
   return (size_t)DynWs::from(nullptr, (size_t)Vm).end + 256;
 }
 
-// the checks and launches of both entries.  col == null: gm_mesh_dynamics; with col->K == 0 the same launches, so the same bits.
+// the checks and launches of the three entries.  col == null: gm_mesh_dynamics; with col->K == 0 and no field the same launches, so the
+// same bits.  fld != null (gm_mesh_dynamics_field; col is there too): the field's local kernel in every iteration, for every K.
 struct DynContactArgs { int K; const int* kind; const float* rows; const double* friction; double kc; int* contact_out; };
+struct DynFieldArgs { int nx, ny, nz; const float* origin; float voxel; const float* grid; double friction; };
 
-static int dyn_run(const char* fn, const DynContactArgs* col, int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+static int dyn_run(const char* fn, const DynContactArgs* col, const DynFieldArgs* fld, int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
                    const double* mass, const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in,
                    const float* v_in, double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
                    double cg_tolerance, float* X_out, float* v_out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
@@ -403,6 +485,10 @@ static int dyn_run(const char* fn, const DynContactArgs* col, int T, int Vm, con
     if (!dyn_finite(col->kc) || !(col->kc > 0.0)) { set_error("%s: contact_stiffness must be finite and positive", fn); return GM_ERR_INVALID_ARG; }
     if (K > 0 && (!col->kind || !col->rows || !col->friction)) { set_error("%s: null pointer (K = %d colliders)", fn, K); return GM_ERR_INVALID_ARG; }
   }
+  if (fld) {
+    if (int rc = check_sdf_grid(fn, fld->nx, fld->ny, fld->nz, fld->origin, fld->voxel, fld->grid)) return rc;
+    if (!(fld->friction >= 0.0)) { set_error("%s: field_friction must not be negative", fn); return GM_ERR_INVALID_ARG; }
+  }
   if (!row_offsets || !cols || !weights || !V0 || !mass || !held || !x_in || !v_in || !X_out || !v_out || !workspace ||
       (H > 0 && (!handle_ids || !handle_targets))) {
     set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG;
@@ -410,7 +496,7 @@ static int dyn_run(const char* fn, const DynContactArgs* col, int T, int Vm, con
   // the inputs are only read and may alias one another; an output or the workspace meets nothing, except that v_out may be v_in (v_in
   // stands for both: it is read once, by the first launch)
   const size_t row = 12 * (size_t)Vm;
-  const ByteRange rg[15] = {{V0, row, "V0", false}, {mass, 8 * (size_t)Vm, "mass", false}, {held, (size_t)Vm, "held", false},
+  const ByteRange rg[16] = {{V0, row, "V0", false}, {mass, 8 * (size_t)Vm, "mass", false}, {held, (size_t)Vm, "held", false},
                             {H > 0 ? handle_ids : nullptr, 4 * (size_t)H, "handle_ids", false},
                             {H > 0 ? handle_targets : nullptr, 12 * (size_t)H * T, "handle_targets", false}, {x_in, row, "x_in", false},
                             {v_in, row, "v_in", v_out == v_in}, {X_out, row * T, "X_out", true}, {v_out == v_in ? nullptr : v_out, row, "v_out", true},
@@ -418,7 +504,8 @@ static int dyn_run(const char* fn, const DynContactArgs* col, int T, int Vm, con
                             {K > 0 ? col->kind : nullptr, 4 * (size_t)K, "collider_kind", false},
                             {K > 0 ? col->rows : nullptr, 16 * (size_t)K * T, "collider_rows", false},
                             {K > 0 ? col->friction : nullptr, 8 * (size_t)K, "collider_friction", false},
-                            {col ? col->contact_out : nullptr, 4 * (size_t)Vm * T, "contact_out", true}};
+                            {col ? col->contact_out : nullptr, 4 * (size_t)Vm * T, "contact_out", true},
+                            {fld ? fld->grid : nullptr, fld ? 16 * (size_t)fld->nx * fld->ny * fld->nz : 0, "field_grid", false}};
   if (int rc = check_ranges(fn, rg)) return rc;
   const size_t need = col ? gm_mesh_dynamics_contact_workspace_bytes(Vm) : gm_mesh_dynamics_workspace_bytes(Vm);
   if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
@@ -430,7 +517,7 @@ static int dyn_run(const char* fn, const DynContactArgs* col, int T, int Vm, con
   hipLaunchKernelGGL(dyn_init_kernel, rows, threads, 0, s, Vm, row_offsets, weights, mass, held, x_in, v_in, two_k_h2, dt, grav, k.x, k.y, k.xs, k.vs, k.mu,
                      k.diag, k.free_row);
   if (H > 0) hipLaunchKernelGGL(dyn_handles_kernel, dim3((H + DYN_ROW_THREADS - 1) / DYN_ROW_THREADS), threads, 0, s, Vm, H, handle_ids, handle_targets, k.x);
-  if (K == 0 && col && col->contact_out) GM_HIP(hipMemsetAsync(col->contact_out, 0, 4 * (size_t)Vm * T, s));
+  if (K == 0 && !fld && col && col->contact_out) GM_HIP(hipMemsetAsync(col->contact_out, 0, 4 * (size_t)Vm * T, s));
   const double tol2 = cg_tolerance * cg_tolerance;
   for (int t = 0; t < T; t++)
     for (int it = 0; it < iterations; it++) {
@@ -442,7 +529,7 @@ static int dyn_run(const char* fn, const DynContactArgs* col, int T, int Vm, con
         end.stats_row = stats ? stats + 6 * (size_t)t : nullptr;
         end.next_targets = (H > 0 && t + 1 < T) ? handle_targets + 3 * (size_t)H * (t + 1) : nullptr;
       }
-      if (K == 0) {
+      if (K == 0 && !fld) {
         hipLaunchKernelGGL(dyn_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R);
         hipLaunchKernelGGL(dyn_global_kernel, dim3(3), dim3(DYN_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.mu, k.diag, k.free_row, k.x, k.r,
                            k.p, k.q, k.y, k.xs, k.vs, cg_iterations, tol2, end);
@@ -450,8 +537,15 @@ static int dyn_run(const char* fn, const DynContactArgs* col, int T, int Vm, con
       }
       const DynColliders dc = {K, col->kind, col->rows + 4 * (size_t)K * t, col->friction, col->kc * dt * dt,
                                (last && col->contact_out) ? col->contact_out + (size_t)Vm * t : nullptr};
-      hipLaunchKernelGGL(dyn_contact_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.xs, k.mu, k.free_row, k.R, dc, kc.kappa,
-                         kc.shift, kc.diag, kc.c);
+      if (fld) {
+        const DynField df = {{reinterpret_cast<const float4*>(fld->grid), fld->nx, fld->ny, fld->nz, {fld->origin[0], fld->origin[1], fld->origin[2]}, fld->voxel},
+                             fld->friction};
+        hipLaunchKernelGGL(dyn_field_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.xs, k.mu, k.free_row, k.R, dc, df,
+                           kc.kappa, kc.shift, kc.diag, kc.c);
+      } else {
+        hipLaunchKernelGGL(dyn_contact_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.xs, k.mu, k.free_row, k.R, dc, kc.kappa,
+                           kc.shift, kc.diag, kc.c);
+      }
       hipLaunchKernelGGL(dyn_contact_global_kernel, dim3(3), dim3(DYN_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.mu, kc.kappa, kc.shift,
                          kc.diag, kc.c, k.free_row, k.x, k.r, k.p, k.q, k.y, k.xs, k.vs, cg_iterations, tol2, end);
     }
@@ -463,7 +557,7 @@ int gm_mesh_dynamics(int T, int Vm, const int* row_offsets, const int* cols, con
                      const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in, const float* v_in,
                      double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
                      double cg_tolerance, float* X_out, float* v_out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
-  return dyn_run("gm_mesh_dynamics", nullptr, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt, stiffness,
+  return dyn_run("gm_mesh_dynamics", nullptr, nullptr, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt, stiffness,
                  damping, gx, gy, gz, iterations, cg_iterations, cg_tolerance, X_out, v_out, stats, workspace, workspace_bytes, stream);
 }
 
@@ -479,7 +573,20 @@ int gm_mesh_dynamics_contact(int T, int Vm, const int* row_offsets, const int* c
                              const double* collider_friction, double contact_stiffness, float* X_out, float* v_out, int* contact_out,
                              double* stats, void* workspace, size_t workspace_bytes, void* stream) {
   const DynContactArgs col = {K, collider_kind, collider_rows, collider_friction, contact_stiffness, contact_out};
-  return dyn_run("gm_mesh_dynamics_contact", &col, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt,
+  return dyn_run("gm_mesh_dynamics_contact", &col, nullptr, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt,
+                 stiffness, damping, gx, gy, gz, iterations, cg_iterations, cg_tolerance, X_out, v_out, stats, workspace, workspace_bytes, stream);
+}
+
+int gm_mesh_dynamics_field(int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const double* mass,
+                           const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in, const float* v_in,
+                           double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
+                           double cg_tolerance, int K, const int* collider_kind, const float* collider_rows, const double* collider_friction,
+                           double contact_stiffness, int nx, int ny, int nz, const float* origin, float voxel, const float* field_grid,
+                           double field_friction, float* X_out, float* v_out, int* contact_out, double* stats, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  const DynContactArgs col = {K, collider_kind, collider_rows, collider_friction, contact_stiffness, contact_out};
+  const DynFieldArgs fld = {nx, ny, nz, origin, voxel, field_grid, field_friction};
+  return dyn_run("gm_mesh_dynamics_field", &col, &fld, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt,
                  stiffness, damping, gx, gy, gz, iterations, cg_iterations, cg_tolerance, X_out, v_out, stats, workspace, workspace_bytes, stream);
 }
 

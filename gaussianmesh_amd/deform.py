@@ -550,7 +550,8 @@ class SingleObjectDeform:
         previous simulate() left (zero the first time); False: from zero.  options: MeshDynamics' mass, density, stiffness, damping,
         gravity, dt, iterations, cg_iterations, cg_tolerance, colliders (dynamics.floor / half_space / sphere, or their tuples, lists or
         dicts) and contact_stiffness; the object is built on the first call and kept while faces, handles, pins and options stay the same
-        (colliders are compared by value).  collider_rows [steps,K,4]: MeshDynamics.run's, for colliders that move.  Leaves the object at the last frame through deform_vertices, in the manner of drag_sequence.
+        (colliders are compared by value; field=, a dynamics.SdfGrid, by identity: the operator is reused while the SAME grid object is
+        passed; field_friction goes with it).  collider_rows [steps,K,4]: MeshDynamics.run's, for colliders that move.  Leaves the object at the last frame through deform_vertices, in the manner of drag_sequence.
         faces [F,3]: for an object built from tensors alone.  Returns the meshes; no host wait."""
         from .dynamics import MeshDynamics
         import numpy as np

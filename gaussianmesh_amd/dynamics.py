@@ -6,12 +6,15 @@ local step is ArapSolver's, the global step's matrix gains the positive diagonal
 definite with no held row at all - a free body is a valid input, which ArapSolver cannot express.  The result is a [steps,Vm,3] stack of
 meshes: what render_sequence, SingleObjectDeform.deform_vertices and edit_sequence --save_meshes take.  Definition, ABI and rules:
 INTEGRATION.md section AA.  With colliders (floor / half_space / sphere) the free rows cannot enter them: unilateral contact with
-Coulomb-limited friction (gm_mesh_dynamics_contact), INTEGRATION.md section AB."""
+Coulomb-limited friction (gm_mesh_dynamics_contact), INTEGRATION.md section AB.  With field=SdfGrid(...) they cannot enter a sampled
+signed-distance volume either - the fused volume of the scene's background cloud, say (gm_mesh_dynamics_field), section AC."""
+import ctypes
+
 import numpy as np
 import torch
 
 from . import _lib
-from ._op import enqueue, host, on_device
+from ._op import enqueue, host, need_cuda, on_device
 from .mesh_graph import MeshGraph
 
 
@@ -121,6 +124,67 @@ def collider_table(colliders, who="collider_table"):
             np.array([c[2] for c in parsed], np.float64))
 
 
+class SdfGrid:
+    """A signed-distance volume prepared for contact (gm_sdf_grid_prepare, INTEGRATION.md section AC).  values: any float32 [nz,ny,nx]
+    tensor of signed distances, sample (ix, iy, iz) at origin + (i + 0.5) voxel, negative inside the solid, NaN where nothing is known;
+    weight (optional, the same shape): samples with weight < min_weight are unknown too; scale multiplies every value (a TSDF stores
+    distance / trunc).  .grid is the prepared float32 [nz,ny,nx,4] tensor (phi, gx, gy, gz) - the gradient over every sample's known
+    neighbours - with four NaNs on unknown samples; values and weight are not kept.  Only enqueues; nothing waits for the device.
+    ValueError for shapes, fewer than 2 or more than 2^28 samples, a non-finite origin, voxel or scale, a voxel <= 0, a weight of
+    another shape; GmeshError without a device."""
+
+    def __init__(self, values, origin, voxel, weight=None, min_weight=1, scale=1.0, device="cuda"):
+        who = "SdfGrid"
+        if not hasattr(values, "shape") or len(values.shape) != 3:
+            raise ValueError("%s: values must be [nz,ny,nx]; got %s" % (who, tuple(getattr(values, "shape", ()))))
+        nz, ny, nx = (int(n) for n in values.shape)
+        if min(nx, ny, nz) < 2 or nx * ny * nz > 1 << 28:
+            raise ValueError("%s: a grid of %d x %d x %d samples (every side at least 2, at most 2^28 in all)" % (who, nx, ny, nz))
+        if weight is not None and (not hasattr(weight, "shape") or tuple(weight.shape) != (nz, ny, nx)):
+            raise ValueError("%s: weight must be [%d,%d,%d] as values are; got %s" % (who, nz, ny, nx, tuple(getattr(weight, "shape", ()))))
+        o = np.asarray(host(origin), np.float64).reshape(-1)
+        if o.shape != (3,) or not np.isfinite(o.astype(np.float32)).all():
+            raise ValueError("%s: origin must be three finite numbers; got %r" % (who, origin))
+        for name, val in (("voxel", voxel), ("scale", scale), ("min_weight", min_weight)):
+            if isinstance(val, bool) or not isinstance(val, (int, float, np.integer, np.floating)) or not np.isfinite(np.float32(val)):
+                raise ValueError("%s: %s = %r; a finite number" % (who, name, val))
+        if not float(np.float32(voxel)) > 0.0:
+            raise ValueError("%s: voxel = %r; positive" % (who, voxel))
+        self.device = torch.device(device)
+        need_cuda(self.device, who, "a grid")
+        self.nx, self.ny, self.nz = nx, ny, nz
+        self.origin = o.astype(np.float32)
+        self.voxel, self.scale, self.min_weight = float(np.float32(voxel)), float(np.float32(scale)), float(np.float32(min_weight))
+        self._origin_c = (ctypes.c_float * 3)(*self.origin.tolist())
+        v = on_device(values, torch.float32, self.device)
+        w = None if weight is None else on_device(weight, torch.float32, self.device)
+        self.device = v.device
+        self.grid = torch.empty((nz, ny, nx, 4), dtype=torch.float32, device=self.device)
+        enqueue(self.device, "gm_sdf_grid_prepare", nx, ny, nz, v, w, self.min_weight, self.scale, self.voxel, self.grid)
+
+    @classmethod
+    def from_tsdf(cls, volume, min_weight=1, use_fill=True):
+        """The grid of a proxy_mesh.TsdfVolume: its filled pair (fill_holes) when it has one and use_fill, else tsdf / weight; samples
+        fewer than min_weight views observed are unknown; the scale is the volume's truncation distance."""
+        filled = use_fill and getattr(volume, "filled_tsdf", None) is not None
+        values, weight = (volume.filled_tsdf, volume.filled_weight) if filled else (volume.tsdf, volume.weight)
+        return cls(values, volume.origin, volume.voxel, weight=weight, min_weight=min_weight, scale=volume.trunc, device=values.device)
+
+    def sample(self, points):
+        """(phi float64 [N], normal float64 [N,3]) of points [N,3] (read as float32), on the device: the distance and unit normal the
+        contact step sees (gm_sdf_grid_sample); NaN outside the grid, next to an unknown sample and where the gradient has no direction"""
+        who = "SdfGrid.sample"
+        if not hasattr(points, "shape") or len(points.shape) != 2 or points.shape[1] != 3:
+            raise ValueError("%s: points must be [N,3]; got %s" % (who, tuple(getattr(points, "shape", ()))))
+        p = on_device(points, torch.float32, self.device)
+        N = int(p.shape[0])
+        phi = torch.empty((N,), dtype=torch.float64, device=self.device)
+        normal = torch.empty((N, 3), dtype=torch.float64, device=self.device)
+        if N:
+            enqueue(self.device, "gm_sdf_grid_sample", N, p, self.nx, self.ny, self.nz, self._origin_c, self.voxel, self.grid, phi, normal)
+        return phi, normal
+
+
 class MeshDynamics:
     """The motion of one mesh under scripted handles, pins, gravity and its own elasticity.  Built once: the mesh's MeshGraph (given as
     rest_vertices with faces=None, it is shared), the masses, the masks, and on a device the state (float32 [Vm,3] each) and the workspace.
@@ -143,17 +207,30 @@ class MeshDynamics:
     contact_stiffness.  Handle and pinned rows never take part.  Friction is measured in the world frame: give a moving pusher
     friction 0.  The default contact_stiffness = 1e4 is an unmeasured starting value (a unit-size object under |g| = 9.8 rests about 1e-3
     deep).  With no colliders every call goes through gm_mesh_dynamics, exactly as without these two arguments.  ValueError for a zero or
-    non-finite normal, a radius <= 0, a negative friction, more than 16 colliders, a contact_stiffness that is not finite and positive."""
+    non-finite normal, a radius <= 0, a negative friction, more than 16 colliders, a contact_stiffness that is not finite and positive.
+    field: an SdfGrid on this object's device, or None: one more collider, static, the sampled volume (gm_mesh_dynamics_field,
+    INTEGRATION.md section AC) with the friction field_friction.  It is candidate K behind the K analytic colliders: a tie goes to the
+    analytic one, want_contacts reports 1 + K, and a row outside the grid, next to an unknown sample or on a zero gradient is not in
+    contact with it.  With field=None every call goes where it went without the argument.  ValueError for a field that is no SdfGrid or
+    lives on another device, a field_friction that is negative or not finite."""
 
     def __init__(self, rest_vertices, faces, pinned=(), handles=(), mass="area", density=1.0, stiffness=10.0, damping=0.02, gravity=(0.0, 0.0, 0.0),
-                 dt=1.0 / 30.0, iterations=3, cg_iterations=64, cg_tolerance=1e-6, device="cuda", colliders=(), contact_stiffness=1.0e4):
+                 dt=1.0 / 30.0, iterations=3, cg_iterations=64, cg_tolerance=1e-6, device="cuda", colliders=(), contact_stiffness=1.0e4, field=None,
+                 field_friction=0.0):
         who = "MeshDynamics"
         table = collider_table(colliders, who)
+        if field is not None and not isinstance(field, SdfGrid):
+            raise ValueError("%s: field must be an SdfGrid or None; got %r" % (who, type(field).__name__))
+        field_friction = _friction(who, field_friction)
         kc = contact_stiffness
         if isinstance(kc, bool) or not isinstance(kc, (int, float, np.integer, np.floating)) or not np.isfinite(kc) or not kc > 0.0:
             raise ValueError("%s: contact_stiffness = %r; finite and positive" % (who, kc))
         mesh = self.mesh = MeshGraph.of(rest_vertices, faces, device, who)
         self.device, Vm = mesh.device, mesh.Vm
+        if field is not None and (self.device.type != "cuda" or field.device != (self.device if self.device.index is not None
+                                                                                 else torch.device("cuda", torch.cuda.current_device()))):
+            raise ValueError("%s: the field is on %s, the mesh on %s" % (who, field.device, self.device))
+        self.field, self.field_friction = field, field_friction
         if isinstance(mass, str):
             if mass != "area":
                 raise ValueError('%s: mass must be "area" or [Vm] numbers; got %r' % (who, mass))
@@ -274,7 +351,7 @@ class MeshDynamics:
                 handle_targets = np.asarray(handle_targets, np.float32)
             if tuple(handle_targets.shape) != (T, H, 3):
                 raise ValueError("%s: handle_targets must be [%d,%d,3]; got %s" % (who, T, H, tuple(handle_targets.shape)))
-        K = self.K
+        K, field = self.K, self.field
         if collider_rows is not None:
             if K == 0:
                 raise ValueError("%s: collider_rows given, but there are no colliders" % who)
@@ -296,10 +373,10 @@ class MeshDynamics:
         stats = torch.zeros((T, 6), dtype=torch.float64, device=dev) if want_stats else None
         contacts = None
         if want_contacts:
-            contacts = torch.zeros((T, Vm), dtype=torch.int32, device=dev) if K == 0 else torch.empty((T, Vm), dtype=torch.int32, device=dev)
-        entry = "gm_mesh_dynamics" if K == 0 else "gm_mesh_dynamics_contact"
+            contacts = torch.zeros((T, Vm), dtype=torch.int32, device=dev) if K == 0 and field is None else torch.empty((T, Vm), dtype=torch.int32, device=dev)
+        entry = "gm_mesh_dynamics_field" if field is not None else "gm_mesh_dynamics" if K == 0 else "gm_mesh_dynamics_contact"
         if self._ws is None:
-            need = getattr(_lib.lib(), entry + "_workspace_bytes")(Vm)
+            need = getattr(_lib.lib(), ("gm_mesh_dynamics_contact" if field is not None else entry) + "_workspace_bytes")(Vm)
             self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)
         if K > 0:
             cp = self._rows.unsqueeze(0).expand(min(T, _lib.GM_MESH_DYNAMICS_STEPS_MAX), K, 4).contiguous() if collider_rows is None \
@@ -311,7 +388,12 @@ class MeshDynamics:
             state = (e - s, Vm, self._off, self._cols, self._w, self.rest, self._mass, self._held, H, self._handle_ids, None if hp is None else hp[s:e],
                      self._x if s == 0 else out[s - 1], self._v, self.dt, self.stiffness, self.damping, g[0], g[1], g[2], self.iterations,
                      self.cg_iterations, self.cg_tolerance)
-            if K == 0:                                                 # exactly the call there was before there were colliders
+            if field is not None:
+                table = (0, None, None, None) if K == 0 else (K, self._kinds, cp[:e - s] if collider_rows is None else cp[s:e], self._mus)
+                enqueue(dev, entry, *state, *table, self.contact_stiffness, field.nx, field.ny, field.nz, field._origin_c, field.voxel, field.grid,
+                        self.field_friction, out[s:e], self._v, None if contacts is None else contacts[s:e], None if stats is None else stats[s:e],
+                        workspace=self._ws)
+            elif K == 0:                                               # exactly the call there was before there were colliders
                 enqueue(dev, entry, *state, out[s:e], self._v, None if stats is None else stats[s:e], workspace=self._ws)
             else:
                 enqueue(dev, entry, *state, K, self._kinds, cp[:e - s] if collider_rows is None else cp[s:e], self._mus, self.contact_stiffness,

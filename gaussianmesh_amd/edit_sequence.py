@@ -5,7 +5,8 @@
         [--frames_per_launch 4] [--save_maps] [--save_meshes] [--save_baked PATH] [--background_gaussian BG.ply [--is_exist_bg]]
         [--arap_global_step {column,grid}] [--arap_batch K] [--inbetweens N [--ease {linear,smoothstep}]]
         [--dynamics [--settle N] [--dt S] [--stiffness K] [--damping G] [--gravity X Y Z]
-                    [--floor H] [--friction MU] [--contact_stiffness KC] [--colliders FILE.json]]
+                    [--floor H] [--friction MU] [--contact_stiffness KC] [--colliders FILE.json]
+                    [--background_contact [RES] [--contact_margin M]]]
 
 --object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
 faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of the two.
@@ -51,6 +52,12 @@ the default of the colliders of --colliders (0 without it).  --contact_stiffness
 "friction": mu} and {"kind": "sphere", "radius": r, "center": [x, y, z] or "centers": [[x, y, z], ...], "friction": mu}; "centers" gives a
 moving ball its centre in every frame (the last one is kept for frames beyond the list, --settle's included).  At most 16 colliders with
 the floor.  All four are refused without --dynamics; without them nothing changes.
+--background_contact [RES] (with --dynamics and --background_gaussian): the simulated mesh also collides with the background cloud itself.
+The cloud's depth and opacity maps from ALL cameras of MODEL_DIR/cameras.json are fused into a signed-distance volume of RES (default 128)
+voxels along the longest side of the object's rest box grown by --contact_margin M (default 0.5) times that side
+(SceneVisualTool.background_field, dynamics.SdfGrid); the volume is one more collider, behind --floor and --colliders, with --friction as
+its friction and --contact_stiffness as everyone's.  Where no view saw the background the volume knows nothing and nothing is in contact
+with it.  Refused without --dynamics or without --background_gaussian; --contact_margin is refused without it.
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
@@ -182,6 +189,8 @@ def main(argv=None):
     parser.add_argument("--friction", type=float, default=None, metavar="MU")
     parser.add_argument("--contact_stiffness", type=float, default=None, metavar="KC")
     parser.add_argument("--colliders", type=str, default=None, metavar="FILE.json")
+    parser.add_argument("--background_contact", type=int, nargs="?", const=128, default=None, metavar="RES")
+    parser.add_argument("--contact_margin", type=float, default=None, metavar="M")
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
     parser.add_argument("--save_maps", action="store_true", default=False)
@@ -206,9 +215,19 @@ def main(argv=None):
             if value is not None:
                 raise SystemExit("edit_sequence: %s sets the simulated material and needs --dynamics" % flag)
         for flag, value in (("--floor", args.floor), ("--friction", args.friction), ("--contact_stiffness", args.contact_stiffness),
-                            ("--colliders", args.colliders)):
+                            ("--colliders", args.colliders), ("--background_contact", args.background_contact)):
             if value is not None:
                 raise SystemExit("edit_sequence: %s sets what the simulated mesh collides with and needs --dynamics" % flag)
+    if args.background_contact is not None:
+        if args.background_gaussian is None:
+            raise SystemExit("edit_sequence: --background_contact collides with the background cloud and needs --background_gaussian")
+        if args.background_contact < 2:
+            raise SystemExit("edit_sequence: --background_contact %d: the volume's resolution, 2 or more voxels along its longest side" % args.background_contact)
+    if args.contact_margin is not None:
+        if args.background_contact is None:
+            raise SystemExit("edit_sequence: --contact_margin grows the volume of --background_contact and needs it")
+        if not 0.0 <= args.contact_margin < float("inf"):
+            raise SystemExit("edit_sequence: --contact_margin %r: a finite number >= 0" % args.contact_margin)
     if args.dynamics:
         if args.mesh_sequence is not None:
             raise SystemExit("edit_sequence: --dynamics simulates the frames of --handle_sequence / --pick_sequence; --mesh_sequence has ready-made meshes")
@@ -218,9 +237,9 @@ def main(argv=None):
             raise SystemExit("edit_sequence: --dynamics with --inbetweens %d: simulated frames are no key poses; drop one of the two" % args.inbetweens)
         if args.floor is not None and (args.gravity is None or not any(args.gravity)):
             raise SystemExit("edit_sequence: --floor lies opposite to gravity and needs a non-zero --gravity X Y Z")
-        if args.friction is not None and args.floor is None and args.colliders is None:
+        if args.friction is not None and args.floor is None and args.colliders is None and args.background_contact is None:
             raise SystemExit("edit_sequence: --friction is the friction of --floor and --colliders; give one of them")
-        if args.contact_stiffness is not None and args.floor is None and args.colliders is None:
+        if args.contact_stiffness is not None and args.floor is None and args.colliders is None and args.background_contact is None:
             raise SystemExit("edit_sequence: --contact_stiffness needs something to collide with: --floor or --colliders")
         colliders, moving = ([], {}) if args.colliders is None else read_colliders(args.colliders, args.friction or 0.0)
         if args.floor is not None:
@@ -288,8 +307,12 @@ def main(argv=None):
             rows = None
             if colliders:
                 material["colliders"] = colliders
-                if args.contact_stiffness is not None:
-                    material["contact_stiffness"] = args.contact_stiffness
+            if args.background_contact is not None:                                   # the background cloud itself, fused from every camera
+                material["field"] = tool.background_field(cams, resolution=args.background_contact,
+                                                          margin=0.5 if args.contact_margin is None else args.contact_margin)
+                material["field_friction"] = args.friction or 0.0
+            if (colliders or args.background_contact is not None) and args.contact_stiffness is not None:
+                material["contact_stiffness"] = args.contact_stiffness
             if moving:                                                                # the centres of the moving balls, frame by frame
                 from .dynamics import collider_table
                 try:

@@ -229,7 +229,8 @@ class ObjectVisualTool:
     def simulate_one_gaussian(self, name, steps, handle_targets=None, collider_rows=None, **options):
         """`steps` simulated steps of the objects called `name` from their current mesh (SingleObjectDeform.simulate: secondary motion,
         dynamics.MeshDynamics) with their handles at handle_targets [steps,H,3] and, with colliders= among the options, those at
-        collider_rows [steps,K,4] (None: where they were built); the objects are left at the last frame.  Returns the
+        collider_rows [steps,K,4] (None: where they were built), with field= (a dynamics.SdfGrid, SceneVisualTool.background_field's for
+        one) and field_friction= the sampled volume as one more collider; the objects are left at the last frame.  Returns the
         meshes [steps, Vm, 3] of the last such object (None if there is none)."""
         meshes = None
         for g in self.gaussians_list:
@@ -478,6 +479,39 @@ class SceneVisualTool(ObjectVisualTool):
         self.bg_opacity = torch.sigmoid(t(m["opacity"]))
         self.bg_deform_rot = torch.eye(3, device=self.device).repeat(self.bg_scale.shape[0], 1, 1)
         self._scene_seq = None                       # the static scene cloud of render_sequence: rebuilt from the new background
+
+    def background_field(self, cameras, resolution=128, bounds=None, margin=0.5, fill_holes=None):
+        """The background cloud as something the objects can stand on: a dynamics.SdfGrid for MeshDynamics(field=) / simulate(field=)
+        (INTEGRATION.md section AC).  The cloud's own depth and opacity maps from `cameras` are fused into a TsdfVolume
+        (proxy_mesh.fuse_cloud) of `resolution` voxels along the longest side of bounds = (min, max); by default the box of the objects'
+        rest meshes grown on every side by margin times its longest side - contact only matters where the objects can get to.
+        fill_holes: True or an iteration count closes what no view saw (TsdfVolume.fill_holes) and the grid is that of the filled pair;
+        None: the fused volume as it is, unobserved samples unknown.  The volume is kept as self.background_volume.  Reads the objects'
+        boxes (a host wait) when bounds is None.  ValueError with neither bounds nor an object."""
+        from .bg_model import PlainGaussians
+        from .dynamics import SdfGrid
+        from .proxy_mesh import fuse_cloud
+        if bounds is None:
+            if not self.gaussians_list:
+                raise ValueError("SceneVisualTool.background_field: no object to take the bounds from; give bounds=(min, max)")
+            if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not 0.0 <= margin < float("inf"):
+                raise ValueError("SceneVisualTool.background_field: margin = %r; a finite number >= 0" % (margin,))
+            lo = torch.stack([o.vertex.min(dim=0).values for o in self.gaussians_list]).min(dim=0).values.cpu().numpy().astype(np.float64)
+            hi = torch.stack([o.vertex.max(dim=0).values for o in self.gaussians_list]).max(dim=0).values.cpu().numpy().astype(np.float64)
+            grow = float(margin) * max(float((hi - lo).max()), 1e-6)
+            bounds = (lo - grow, hi + grow)
+        m = self._bg_loaded
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32)
+        feats = torch.cat([t(m["features_dc"]), t(m["features_rest"])], dim=1)
+        degree = int(round(feats.shape[1] ** 0.5)) - 1
+        pc = PlainGaussians(sh_degree=degree, device=self.device)
+        pc._set_params(t(m["xyz"]), feats, t(m["scaling"]), t(m["rotation"]), t(m["opacity"]).reshape(-1, 1))
+        pc.active_sh_degree = degree
+        vol = fuse_cloud(pc, cameras, resolution=int(resolution), bounds=bounds)
+        if fill_holes is not None and fill_holes is not False:
+            vol.fill_holes(None if fill_holes is True else int(fill_holes))
+        self.background_volume = vol
+        return SdfGrid.from_tsdf(vol)
 
     def save_baked(self, path, name=None, deg=3, include_background=False):
         """ObjectVisualTool.save_baked for a scene; with include_background the background's raw rows come first, bit for bit as loaded:

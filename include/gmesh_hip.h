@@ -422,6 +422,55 @@ int gm_mesh_dynamics_contact(int T, int Vm, const int* row_offsets, const int* c
                              const double* collider_friction, double contact_stiffness, float* X_out, float* v_out, int* contact_out,
                              double* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* A sampled signed-distance field for contact (dynamics.SdfGrid; definition: csrc/gm_sdf.hip and csrc/gm_sdf.h, INTEGRATION.md section AC).
+ * The reference has no such stage: the results are defined by arithmetic.
+ * gm_sdf_grid_prepare: values float [nz,ny,nx], sample (ix, iy, iz) at origin + (i + 0.5) voxel (TsdfVolume's layout); weight (optional)
+ * float of the same shape.  A sample is VALID iff its value is not NaN and (weight == NULL or weight >= min_weight).  grid_out float
+ * [nz,ny,nx,4], 16-byte aligned: an invalid sample gets four NaNs, a valid one (phi, gx, gy, gz), in float32, no contraction, correctly
+ * rounded division, with phi- / phi+ the phi of the VALID neighbour inside the grid one sample down / up the axis:
+ *   phi = value * scale;   per axis  (phi+ - phi-) / (2.f * voxel) with both neighbours,  (phi+ - phi) / voxel with only the upper,
+ *   (phi - phi-) / voxel with only the lower,  0 with neither.
+ * One thread per sample, no atomics: the same bits from call to call, and those of the restatement in numpy float32.  For a TSDF scale
+ * is the truncation distance (the volume stores distance / trunc).
+ * gm_sdf_grid_sample: points float [N,3]; phi_out double [N], n_out double [N,3].  Per row, in float64 and in this order:
+ *   g_a = (X_a - origin_a) / voxel - 0.5 per axis; OUTSIDE unless 0 <= g_a < n_a - 1 on all three (a NaN is outside): phi = NaN;
+ *   i_a = floor(g_a), f_a = g_a - i_a; the eight corners (ix + dx, iy + dy, iz + dz) as eight 16-byte loads; a corner whose phi is NaN:
+ *   phi = NaN; each of the four channels, widened to double, interpolated along x, then y, then z, every interpolation
+ *   fma(f, q1 - q0, q0); s = sqrt(fma(g2, g2, fma(g1, g1, g0 g0))); !(s > 0) or s not finite: phi = NaN; else n = g / s per coordinate.
+ * Where phi_out is NaN, n_out is three NaNs.  The normal interpolates the prepared gradients, so it is continuous across cell faces.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: a side below 2, more than 2^28 samples, a voxel that is not finite and positive,
+ * an origin that is not finite, a scale that is not finite, N < 1, a NULL among the required pointers, a grid that is not 16-byte
+ * aligned, any overlap of an output with another buffer.  Stream-ordered, no device allocation, no host synchronisation. */
+int gm_sdf_grid_prepare(int nx, int ny, int nz, const float* values, const float* weight, float min_weight, float scale, float voxel,
+                        float* grid_out, void* stream);
+int gm_sdf_grid_sample(int N, const float* points, int nx, int ny, int nz, const float* origin, float voxel, const float* grid, double* phi_out,
+                       double* n_out, void* stream);
+
+/* gm_mesh_dynamics_contact with one more collider: a prepared signed-distance grid (dynamics.MeshDynamics(field=...); INTEGRATION.md
+ * section AC).  Every argument of gm_mesh_dynamics_contact means what it means there; nx, ny, nz, origin (three floats on the HOST),
+ * voxel and field_grid describe the grid gm_sdf_grid_prepare wrote, static over the call; field_friction >= 0.  In every iteration a free
+ * row evaluates the K analytic colliders exactly as gm_mesh_dynamics_contact does (k ascending, phi < best from +inf) and then the field,
+ * (phi, n) = gm_sdf_grid_sample's at the iterate X_i, as candidate K with the same phi < best: ties go to the analytic collider, and a
+ * NaN field value - a row outside the grid, next to an unknown sample, on a gradient without a direction - is never chosen, so such a
+ * row is simply not in contact with the field.  An active row takes gm_mesh_dynamics_contact's kappa_i, c_i and Coulomb cap, in its
+ * rounding order:
+ *   u = X - xs per coordinate;  nu = fma(n2, u2, fma(n1, u1, n0 u0));  t = fma(-nu, n, u) per coordinate;
+ *   s = sqrt(fma(t2, t2, fma(t1, t1, t0 t0)));  lim = friction fabs(phi);  scale = s <= lim ? 1 : lim / s;
+ *   c = fma(-scale, t, fma(-phi, n, X)) per coordinate
+ * with the winner's (phi, n, friction): the field's and field_friction when k* == K.  contact_out reports 1 + K for the field.  K may
+ * be 0; the launches are the field's for every K (one local kernel of its own; the global kernel is gm_mesh_dynamics_contact's), a step
+ * stays 2 * iterations launches, and the workspace is gm_mesh_dynamics_contact_workspace_bytes(Vm).
+ * Refused as gm_mesh_dynamics_contact refuses, and with GM_ERR_INVALID_ARG: a side of the grid below 2, more than 2^28 samples, a voxel
+ * that is not finite and positive, an origin that is NULL or not finite, a NULL or not 16-byte aligned field_grid (it is not routed to
+ * gm_mesh_dynamics_contact), a field_friction that is negative or NaN, any overlap of the grid with an output or the workspace. */
+int gm_mesh_dynamics_field(int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const double* mass,
+                           const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in, const float* v_in,
+                           double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
+                           double cg_tolerance, int K, const int* collider_kind, const float* collider_rows, const double* collider_friction,
+                           double contact_stiffness, int nx, int ny, int nz, const float* origin, float voxel, const float* field_grid,
+                           double field_friction, float* X_out, float* v_out, int* contact_out, double* stats, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* First hit of every ray on a mesh: what takes an editor from a pixel to a vertex of the current, deformed proxy mesh
  * (mesh_pick.ray_mesh_hits / pick / visible_vertices).  The reference has no such stage: the result is defined by arithmetic.
  * origins, dirs float [R,3], vertices float [Vm,3], faces int32 [F,3] vertex ids.  out_t float [R], out_face int32 [R], out_uv float
