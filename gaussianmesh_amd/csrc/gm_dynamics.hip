@@ -27,6 +27,10 @@
 //                step's handle targets.  No workgroup reads what another wrote in the same launch.
 // Sums in a fixed order (arap_block_sum), no atomics: the same bits from call to call.  One workgroup per column keeps the nine state
 // columns of a proxy mesh (7.5 k vertices: 60 KB each) in L2; a whole-chip global step for meshes far above that is not built.
+// CONTACT (gm_mesh_dynamics_contact, gm_mesh_dynamics_field; the block further down) is the same step with other kernels in the same two
+// slots, each pair of kernels one templated source: dyn_contact_local / dyn_field_local are dyn_contact_local_body<FIELD> over the one
+// contact row dyn_contact_row<FIELD>, and dyn_global / dyn_contact_global are dyn_global_body<CONTACT>.  Every kernel symbol is a one-line
+// wrapper with a name and signature of its own, so two builds compare symbol by symbol (tools/kernel_disasm.sh).
 // Conventions of gm_closest.hip: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include <math.h>
 #include "gm_common.h"
@@ -245,10 +249,15 @@ __global__ __launch_bounds__(DYN_THREADS) void dyn_global_kernel(int Vm, const i
 // t = u - (n . u) n, lim = friction_k* |phi*|, scale = |t| <= lim ? 1 : lim / |t|: the normal part of c_i is the surface point, the
 // tangential part pulls back to where the row was at the step's start, capped by Coulomb's cone.  Inactive, held and handle rows:
 // kappa_i = 0.  The rounding order is dyn_contact_phi's and dyn_contact_row's, spelled out there.
-// KERNELS.  dyn_contact_local (dyn_local_row, then the row's contact: kappa, mu + kappa, mu + kappa + d, c into the workspace, and
-// contact_out in a step's last iteration) and dyn_contact_global (dyn_global_body<true>: dyn_global_kernel's source with the effective
-// diagonal and shift and kappa_i c_i on the right-hand side; dyn_global_kernel, the <false> instantiation, kept its code).  A step
-// stays 2 * iterations launches; no workgroup reads what another wrote in the same launch; no atomics.
+// FIELD CONTACT (gm_mesh_dynamics_field; INTEGRATION.md section AC): the same, with a prepared signed-distance grid (gm_sdf.hip), static
+// over the call, as candidate K behind the K analytic colliders: (phi, n) = sdf_sample(grid, X), taken with the same phi < best, so a tie
+// goes to the analytic collider and a NaN - a row outside the grid, next to an unknown sample, on a gradient without a direction - is
+// never chosen.  The winner's (phi, n, friction) go through the one tail of dyn_contact_row; contact_out is 1 + K for the field.
+// KERNELS.  dyn_contact_local / dyn_field_local (dyn_contact_local_body<FIELD>: dyn_local_row, then the row's contact
+// dyn_contact_row<FIELD>: kappa, mu + kappa, mu + kappa + d, c into the workspace, and contact_out in a step's last iteration) and, for
+// both, dyn_contact_global (dyn_global_body<true>: dyn_global_kernel's source with the effective diagonal and shift and kappa_i c_i on
+// the right-hand side; dyn_global_kernel, the <false> instantiation, kept its code).  A step stays 2 * iterations launches; no workgroup
+// reads what another wrote in the same launch; no atomics.
 
 struct DynContactWs {
   double* kappa;   // [Vm] mu_i kc h^2 on active rows, 0 elsewhere
@@ -285,112 +294,36 @@ __device__ __forceinline__ double dyn_contact_phi(int kind, const float* __restr
   return (double)NAN;
 }
 
+struct DynField {
+  SdfGrid grid;
+  double friction;
+};
+
 // The contact of one free row at the iterate X with the step's start xs: returns 1 + k* if the row is active (0 if not) and then its
-// target in c.  The order of every rounding:
+// target in c.  FIELD: fld's grid is candidate K; without it fld is not read.  The order of every rounding:
 //   phi_k      dyn_contact_phi, k ascending, kept iff phi_k < best
-//   n          the half-space's row as given; the sphere's e / s per coordinate with e, s as in dyn_contact_phi ((0, 1, 0) at s == 0)
+//   phi_K      FIELD only: sdf_sample (gm_sdf.h), behind the colliders, kept iff phi_K < best
+//   n          the half-space's row as given; the sphere's e / s per coordinate with e, s as in dyn_contact_phi ((0, 1, 0) at s == 0);
+//              the field's as sdf_sample gives it
 //   u = X - xs per coordinate;  nu = fma(n2, u2, fma(n1, u1, n0 u0));  t = fma(-nu, n, u) per coordinate
 //   s = sqrt(fma(t2, t2, fma(t1, t1, t0 t0)));  lim = friction fabs(phi);  scale = s <= lim ? 1 : lim / s
-//   c = fma(-scale, t, fma(-phi, n, X)) per coordinate
-__device__ __forceinline__ int dyn_contact_row(const DynColliders& col, const double (&X)[3], const double (&xs)[3], double (&c)[3]) {
+//   c = (X - phi n) - scale t per coordinate: two fused multiply-adds, the inner one first
+template <bool FIELD>
+__device__ __forceinline__ int dyn_contact_row(const DynColliders& col, const DynField& fld, const double (&X)[3], const double (&xs)[3], double (&c)[3]) {
   double best = (double)INFINITY;
   int which = -1;
   for (int k = 0; k < col.K; k++) {                                  // uniform addresses: every thread reads collider k
     const double phi = dyn_contact_phi(col.kind[k], col.rows + 4 * k, X);
     if (phi < best) { best = phi; which = k; }
   }
+  double n[3] = {0.0, 0.0, 0.0}, friction = 0.0;
+  if constexpr (FIELD) {
+    const double fphi = sdf_sample(fld.grid, X, n);
+    if (fphi < best) { best = fphi; which = col.K; }
+    friction = fld.friction;
+  }
   if (!(best < 0.0)) return 0;                                       // (which >= 0 here: best left +inf)
-  const float* row = col.rows + 4 * which;
-  double n[3] = {(double)row[0], (double)row[1], (double)row[2]};
-  if (col.kind[which] == 1) {
-    const double e[3] = {X[0] - n[0], X[1] - n[1], X[2] - n[2]};
-    const double s = sqrt(fma(e[2], e[2], fma(e[1], e[1], e[0] * e[0])));
-    if (s == 0.0) { n[0] = 0.0; n[1] = 1.0; n[2] = 0.0; }
-    else { n[0] = e[0] / s; n[1] = e[1] / s; n[2] = e[2] / s; }
-  }
-  const double u[3] = {X[0] - xs[0], X[1] - xs[1], X[2] - xs[2]};
-  const double nu = fma(n[2], u[2], fma(n[1], u[1], n[0] * u[0]));
-  const double t[3] = {fma(-nu, n[0], u[0]), fma(-nu, n[1], u[1]), fma(-nu, n[2], u[2])};
-  const double s = sqrt(fma(t[2], t[2], fma(t[1], t[1], t[0] * t[0])));
-  const double lim = col.friction[which] * fabs(best);
-  const double scale = s <= lim ? 1.0 : lim / s;
-#pragma unroll
-  for (int a = 0; a < 3; a++) c[a] = fma(-scale, t[a], fma(-best, n[a], X[a]));
-  return 1 + which;
-}
-
-__global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_contact_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
-                                                                            const double* __restrict__ weights, const float* __restrict__ V0,
-                                                                            const double* __restrict__ x, const double* __restrict__ xs,
-                                                                            const double* __restrict__ mu, const int* __restrict__ free_row,
-                                                                            double* __restrict__ R, DynColliders col, double* __restrict__ kappa,
-                                                                            double* __restrict__ shift, double* __restrict__ diag,
-                                                                            double* __restrict__ ct) {
-  const int i = blockIdx.x * DYN_ROW_THREADS + threadIdx.x;
-  if (i >= Vm) return;
-  dyn_local_row(Vm, row_offsets, cols, weights, V0, x, R, i);
-  double d = 0.0;                                                    // arap_row_sum's order: with kappa = 0 the diagonal is dyn_init's
-  for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) d += weights[k];
-  const double m = mu[i];
-  double c[3] = {0.0, 0.0, 0.0}, kap = 0.0;
-  int hit = 0;
-  if (free_row[i]) {
-    const double X[3] = {x[i], x[(size_t)Vm + i], x[2 * (size_t)Vm + i]};
-    const double s[3] = {xs[i], xs[(size_t)Vm + i], xs[2 * (size_t)Vm + i]};
-    hit = dyn_contact_row(col, X, s, c);
-    if (hit) kap = m * col.kch2;
-    else c[0] = c[1] = c[2] = 0.0;
-  }
-  kappa[i] = kap;
-  shift[i] = m + kap;
-  diag[i] = (m + kap) + d;
-#pragma unroll
-  for (int a = 0; a < 3; a++) ct[(size_t)a * Vm + i] = c[a];
-  if (col.contact_out) col.contact_out[i] = hit;
-}
-
-// dyn_global_body with the contact terms: shift = mu + kappa is the operator's diagonal part (diag its Jacobi diagonal), the right-hand
-// side gains kappa_i c_i
-__global__ __launch_bounds__(DYN_THREADS) void dyn_contact_global_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
-                                                                         const double* __restrict__ weights, const float* __restrict__ V0,
-                                                                         const double* __restrict__ Rall, const double* __restrict__ mu,
-                                                                         const double* __restrict__ kappa, const double* __restrict__ shift,
-                                                                         const double* __restrict__ diag, const double* __restrict__ ctall,
-                                                                         const int* __restrict__ free_row, double* xall, double* rall, double* pall,
-                                                                         double* qall, double* yall, double* xsall, double* vsall,
-                                                                         int cg_iterations, double tol2, DynStepEnd end) {
-  __shared__ double partA[1][ARAP_WAVES], partB[3][ARAP_WAVES];
-  dyn_global_body<true>(Vm, row_offsets, cols, weights, V0, Rall, mu, kappa, shift, diag, ctall, free_row, xall, rall, pall, qall, yall, xsall, vsall,
-                        cg_iterations, tol2, end, partA, partB);
-}
-
-// ---------------------------------------------------------------------------------------------
-// FIELD CONTACT (gm_mesh_dynamics_field; INTEGRATION.md section AC): the K analytic colliders and, as candidate K, a prepared
-// signed-distance grid (gm_sdf.hip) that is static over the call.  A free row evaluates the analytic colliders exactly as
-// dyn_contact_row does (k ascending, phi < best), then the field's (phi, n) = sdf_sample(grid, X) with the same phi < best: ties go to
-// the analytic collider, and a NaN - a row outside the grid, next to an unknown sample, on a gradient without a direction - is never
-// chosen.  An active row takes dyn_contact_row's kappa, c and Coulomb cap, in its rounding order, with the winner's (phi, n, friction);
-// contact_out is 1 + K for the field.  This stands BESIDE dyn_contact_row and dyn_contact_local_kernel, which keep their code; the
-// global launch is dyn_contact_global_kernel itself.
-
-struct DynField {
-  SdfGrid grid;
-  double friction;
-};
-
-__device__ __forceinline__ int dyn_field_row(const DynColliders& col, const DynField& fld, const double (&X)[3], const double (&xs)[3], double (&c)[3]) {
-  double best = (double)INFINITY;
-  int which = -1;
-  for (int k = 0; k < col.K; k++) {
-    const double phi = dyn_contact_phi(col.kind[k], col.rows + 4 * k, X);
-    if (phi < best) { best = phi; which = k; }
-  }
-  double n[3] = {0.0, 0.0, 0.0};
-  const double fphi = sdf_sample(fld.grid, X, n);
-  if (fphi < best) { best = fphi; which = col.K; }
-  if (!(best < 0.0)) return 0;
-  double friction = fld.friction;
-  if (which < col.K) {                                               // an analytic collider won: dyn_contact_row's normal
+  if (!FIELD || which < col.K) {                                     // an analytic collider won
     const float* row = col.rows + 4 * which;
     n[0] = (double)row[0]; n[1] = (double)row[1]; n[2] = (double)row[2];
     if (col.kind[which] == 1) {
@@ -412,18 +345,19 @@ __device__ __forceinline__ int dyn_field_row(const DynColliders& col, const DynF
   return 1 + which;
 }
 
-// dyn_contact_local_kernel with dyn_field_row as the row's contact
-__global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_field_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
-                                                                          const double* __restrict__ weights, const float* __restrict__ V0,
-                                                                          const double* __restrict__ x, const double* __restrict__ xs,
-                                                                          const double* __restrict__ mu, const int* __restrict__ free_row,
-                                                                          double* __restrict__ R, DynColliders col, DynField fld,
-                                                                          double* __restrict__ kappa, double* __restrict__ shift,
-                                                                          double* __restrict__ diag, double* __restrict__ ct) {
+// dyn_local_row, then row i's contact into the workspace
+template <bool FIELD>
+__device__ __forceinline__ void dyn_contact_local_body(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                        const double* __restrict__ weights, const float* __restrict__ V0,
+                                                        const double* __restrict__ x, const double* __restrict__ xs,
+                                                        const double* __restrict__ mu, const int* __restrict__ free_row,
+                                                        double* __restrict__ R, const DynColliders& col, const DynField& fld,
+                                                        double* __restrict__ kappa, double* __restrict__ shift, double* __restrict__ diag,
+                                                        double* __restrict__ ct) {
   const int i = blockIdx.x * DYN_ROW_THREADS + threadIdx.x;
   if (i >= Vm) return;
   dyn_local_row(Vm, row_offsets, cols, weights, V0, x, R, i);
-  double d = 0.0;
+  double d = 0.0;                                                    // arap_row_sum's order: with kappa = 0 the diagonal is dyn_init's
   for (int k = row_offsets[i]; k < row_offsets[i + 1]; k++) d += weights[k];
   const double m = mu[i];
   double c[3] = {0.0, 0.0, 0.0}, kap = 0.0;
@@ -431,7 +365,7 @@ __global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_field_local_kernel(int Vm
   if (free_row[i]) {
     const double X[3] = {x[i], x[(size_t)Vm + i], x[2 * (size_t)Vm + i]};
     const double s[3] = {xs[i], xs[(size_t)Vm + i], xs[2 * (size_t)Vm + i]};
-    hit = dyn_field_row(col, fld, X, s, c);
+    hit = dyn_contact_row<FIELD>(col, fld, X, s, c);
     if (hit) kap = m * col.kch2;
     else c[0] = c[1] = c[2] = 0.0;
   }
@@ -441,6 +375,41 @@ __global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_field_local_kernel(int Vm
 #pragma unroll
   for (int a = 0; a < 3; a++) ct[(size_t)a * Vm + i] = c[a];
   if (col.contact_out) col.contact_out[i] = hit;
+}
+
+__global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_contact_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                            const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                            const double* __restrict__ x, const double* __restrict__ xs,
+                                                                            const double* __restrict__ mu, const int* __restrict__ free_row,
+                                                                            double* __restrict__ R, DynColliders col, double* __restrict__ kappa,
+                                                                            double* __restrict__ shift, double* __restrict__ diag,
+                                                                            double* __restrict__ ct) {
+  dyn_contact_local_body<false>(Vm, row_offsets, cols, weights, V0, x, xs, mu, free_row, R, col, DynField(), kappa, shift, diag, ct);
+}
+
+// dyn_global_body with the contact terms: shift = mu + kappa is the operator's diagonal part (diag its Jacobi diagonal), the right-hand
+// side gains kappa_i c_i
+__global__ __launch_bounds__(DYN_THREADS) void dyn_contact_global_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                         const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                         const double* __restrict__ Rall, const double* __restrict__ mu,
+                                                                         const double* __restrict__ kappa, const double* __restrict__ shift,
+                                                                         const double* __restrict__ diag, const double* __restrict__ ctall,
+                                                                         const int* __restrict__ free_row, double* xall, double* rall, double* pall,
+                                                                         double* qall, double* yall, double* xsall, double* vsall,
+                                                                         int cg_iterations, double tol2, DynStepEnd end) {
+  __shared__ double partA[1][ARAP_WAVES], partB[3][ARAP_WAVES];
+  dyn_global_body<true>(Vm, row_offsets, cols, weights, V0, Rall, mu, kappa, shift, diag, ctall, free_row, xall, rall, pall, qall, yall, xsall, vsall,
+                        cg_iterations, tol2, end, partA, partB);
+}
+
+__global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_field_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                          const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                          const double* __restrict__ x, const double* __restrict__ xs,
+                                                                          const double* __restrict__ mu, const int* __restrict__ free_row,
+                                                                          double* __restrict__ R, DynColliders col, DynField fld,
+                                                                          double* __restrict__ kappa, double* __restrict__ shift,
+                                                                          double* __restrict__ diag, double* __restrict__ ct) {
+  dyn_contact_local_body<true>(Vm, row_offsets, cols, weights, V0, x, xs, mu, free_row, R, col, fld, kappa, shift, diag, ct);
 }
 
 }  // namespace gm

@@ -40,10 +40,20 @@ def vertex_masses(vertices, faces, density=1.0):
 HALF_SPACE, SPHERE = 0, 1          # collider_kind of gm_mesh_dynamics_contact
 
 
+def _number(who, name, val, ok, rule):
+    """val as a float: a real number (no bool), finite, with ok(val); else ValueError('<who>: <name> = <val><rule>')"""
+    if isinstance(val, bool) or not isinstance(val, (int, float, np.integer, np.floating)) or not np.isfinite(val) or not ok(float(val)):
+        raise ValueError("%s: %s = %r%s" % (who, name, val, rule))
+    return float(val)
+
+
 def _friction(who, friction):
-    if isinstance(friction, bool) or not isinstance(friction, (int, float, np.integer, np.floating)) or not np.isfinite(friction) or friction < 0.0:
-        raise ValueError("%s: friction = %r; a finite number >= 0" % (who, friction))
-    return float(friction)
+    return _number(who, "friction", friction, lambda x: x >= 0.0, "; a finite number >= 0")
+
+
+def _shaped(a):
+    """an array-like as something that has a .shape: a tensor or an array as it is, anything else as a float32 array"""
+    return a if hasattr(a, "shape") else np.asarray(a, np.float32)
 
 
 def half_space(normal, offset=None, point=None, friction=0.0):
@@ -81,9 +91,8 @@ def sphere(center, radius, friction=0.0):
     c = np.asarray(host(center), np.float64).reshape(-1)
     if c.shape != (3,) or not np.isfinite(c).all():
         raise ValueError("%s: center must be three finite numbers; got %r" % (who, center))
-    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not np.isfinite(radius) or not radius > 0.0:
-        raise ValueError("%s: radius = %r; finite and positive" % (who, radius))
-    return ("sphere", (float(c[0]), float(c[1]), float(c[2]), float(radius)), _friction(who, friction))
+    radius = _number(who, "radius", radius, lambda x: x > 0.0, "; finite and positive")
+    return ("sphere", (float(c[0]), float(c[1]), float(c[2]), radius), _friction(who, friction))
 
 
 def _collider(who, c):
@@ -146,8 +155,7 @@ class SdfGrid:
         if o.shape != (3,) or not np.isfinite(o.astype(np.float32)).all():
             raise ValueError("%s: origin must be three finite numbers; got %r" % (who, origin))
         for name, val in (("voxel", voxel), ("scale", scale), ("min_weight", min_weight)):
-            if isinstance(val, bool) or not isinstance(val, (int, float, np.integer, np.floating)) or not np.isfinite(np.float32(val)):
-                raise ValueError("%s: %s = %r; a finite number" % (who, name, val))
+            _number(who, name, val, lambda x: np.isfinite(np.float32(x)), "; a finite number")      # finite as the float32 it is stored as
         if not float(np.float32(voxel)) > 0.0:
             raise ValueError("%s: voxel = %r; positive" % (who, voxel))
         self.device = torch.device(device)
@@ -222,9 +230,7 @@ class MeshDynamics:
         if field is not None and not isinstance(field, SdfGrid):
             raise ValueError("%s: field must be an SdfGrid or None; got %r" % (who, type(field).__name__))
         field_friction = _friction(who, field_friction)
-        kc = contact_stiffness
-        if isinstance(kc, bool) or not isinstance(kc, (int, float, np.integer, np.floating)) or not np.isfinite(kc) or not kc > 0.0:
-            raise ValueError("%s: contact_stiffness = %r; finite and positive" % (who, kc))
+        kc = _number(who, "contact_stiffness", contact_stiffness, lambda x: x > 0.0, "; finite and positive")
         mesh = self.mesh = MeshGraph.of(rest_vertices, faces, device, who)
         self.device, Vm = mesh.device, mesh.Vm
         if field is not None and (self.device.type != "cuda" or field.device != (self.device if self.device.index is not None
@@ -246,15 +252,14 @@ class MeshDynamics:
             raise ValueError("%s: gravity must be three finite numbers; got %r" % (who, gravity))
         for name, val, ok in (("dt", dt, lambda x: x > 0.0), ("stiffness", stiffness, lambda x: x > 0.0), ("damping", damping, lambda x: 0.0 <= x < 1.0),
                               ("cg_tolerance", cg_tolerance, lambda x: x >= 0.0)):
-            if isinstance(val, bool) or not isinstance(val, (int, float, np.integer, np.floating)) or not np.isfinite(val) or not ok(float(val)):
-                raise ValueError("%s: %s = %r (dt and stiffness positive, damping in [0, 1), cg_tolerance not negative, all finite)" % (who, name, val))
+            _number(who, name, val, ok, " (dt and stiffness positive, damping in [0, 1), cg_tolerance not negative, all finite)")
         for name, val in (("iterations", iterations), ("cg_iterations", cg_iterations)):
             if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or val < 1:
                 raise ValueError("%s: %s = %r; an integer >= 1" % (who, name, val))
         self.Vm, self.F, self.csr, self.mass = Vm, mesh.F, mesh.csr, m
         self.dt, self.stiffness, self.damping, self.gravity = float(dt), float(stiffness), float(damping), tuple(float(x) for x in g)
         self.iterations, self.cg_iterations, self.cg_tolerance = int(iterations), int(cg_iterations), float(cg_tolerance)
-        self.K, self.contact_stiffness = len(table[0]), float(kc)
+        self.K, self.contact_stiffness = len(table[0]), kc
         self.collider_kinds, self.collider_rows, self.collider_friction = table
         self._x = self._v = self._ws = None
         if self.device.type == "cuda":
@@ -312,19 +317,15 @@ class MeshDynamics:
         """One step: the new positions [Vm,3]; handle_targets [H,3] (in the order of `handles`) exactly when there are handles;
         collider_rows [K,4]: where the colliders are in this step (None: where they were built).
         run(1, handle_targets[None], collider_rows[None])[0]."""
-        if collider_rows is not None:
-            if not hasattr(collider_rows, "shape"):
-                collider_rows = np.asarray(collider_rows, np.float32)
-            if len(collider_rows.shape) != 2:
-                raise ValueError("MeshDynamics.step: collider_rows must be [%d,4]; got %s" % (self.K, tuple(collider_rows.shape)))
-            collider_rows = collider_rows[None]
-        if handle_targets is not None:
-            if not hasattr(handle_targets, "shape"):
-                handle_targets = np.asarray(handle_targets, np.float32)
-            if len(handle_targets.shape) != 2:
-                raise ValueError("MeshDynamics.step: handle_targets must be [%d,3]; got %s" % (len(self.handles), tuple(handle_targets.shape)))
-            handle_targets = handle_targets[None]
-        return self.run(1, handle_targets, collider_rows=collider_rows)[0]
+        def one_step(a, name, n, width):
+            if a is None:
+                return None
+            a = _shaped(a)
+            if len(a.shape) != 2:
+                raise ValueError("MeshDynamics.step: %s must be [%d,%d]; got %s" % (name, n, width, tuple(a.shape)))
+            return a[None]
+        collider_rows = one_step(collider_rows, "collider_rows", self.K, 4)
+        return self.run(1, one_step(handle_targets, "handle_targets", len(self.handles), 3), collider_rows=collider_rows)[0]
 
     def run(self, steps, handle_targets=None, out=None, want_stats=False, collider_rows=None, want_contacts=False):
         """`steps` steps from the state, which they advance: the positions after every step, [steps,Vm,3] float32 on the device.
@@ -347,16 +348,14 @@ class MeshDynamics:
         if H > 0 and handle_targets is None:
             raise ValueError("%s: there are %d handles; handle_targets [%d,%d,3] says where they are in every step" % (who, H, T, H))
         if handle_targets is not None:
-            if not hasattr(handle_targets, "shape"):
-                handle_targets = np.asarray(handle_targets, np.float32)
+            handle_targets = _shaped(handle_targets)
             if tuple(handle_targets.shape) != (T, H, 3):
                 raise ValueError("%s: handle_targets must be [%d,%d,3]; got %s" % (who, T, H, tuple(handle_targets.shape)))
         K, field = self.K, self.field
         if collider_rows is not None:
             if K == 0:
                 raise ValueError("%s: collider_rows given, but there are no colliders" % who)
-            if not hasattr(collider_rows, "shape"):
-                collider_rows = np.asarray(collider_rows, np.float32)
+            collider_rows = _shaped(collider_rows)
             if tuple(collider_rows.shape) != (T, K, 4):
                 raise ValueError("%s: collider_rows must be [%d,%d,4]; got %s" % (who, T, K, tuple(collider_rows.shape)))
             if not torch.is_tensor(collider_rows):
@@ -366,38 +365,36 @@ class MeshDynamics:
                     raise ValueError("%s: collider_rows must be finite, a half-space's normal of unit length, a sphere's radius positive" % who)
         self.mesh.need_device(who)
         dev = self.rest.device
-        hp = None
-        if handle_targets is not None:
-            hp = on_device(handle_targets, torch.float32, dev)
+        hp = None if handle_targets is None else on_device(handle_targets, torch.float32, dev)
         out = self.mesh.out_f32(out, (T, Vm, 3), who)
         stats = torch.zeros((T, 6), dtype=torch.float64, device=dev) if want_stats else None
+        plain = K == 0 and field is None                               # exactly the call there was before there were colliders
         contacts = None
         if want_contacts:
-            contacts = torch.zeros((T, Vm), dtype=torch.int32, device=dev) if K == 0 and field is None else torch.empty((T, Vm), dtype=torch.int32, device=dev)
+            contacts = (torch.zeros if plain else torch.empty)((T, Vm), dtype=torch.int32, device=dev)
         entry = "gm_mesh_dynamics_field" if field is not None else "gm_mesh_dynamics" if K == 0 else "gm_mesh_dynamics_contact"
         if self._ws is None:
-            need = getattr(_lib.lib(), ("gm_mesh_dynamics_contact" if field is not None else entry) + "_workspace_bytes")(Vm)
+            need = getattr(_lib.lib(), ("gm_mesh_dynamics" if plain else "gm_mesh_dynamics_contact") + "_workspace_bytes")(Vm)
             self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        if K > 0:
-            cp = self._rows.unsqueeze(0).expand(min(T, _lib.GM_MESH_DYNAMICS_STEPS_MAX), K, 4).contiguous() if collider_rows is None \
-                else on_device(collider_rows, torch.float32, dev)
         top = _lib.GM_MESH_DYNAMICS_STEPS_MAX
+        if K > 0:
+            cp = self._rows.unsqueeze(0).expand(min(T, top), K, 4).contiguous() if collider_rows is None else on_device(collider_rows, torch.float32, dev)
         g = self.gravity
+        fld = () if field is None else (field.nx, field.ny, field.nz, field._origin_c, field.voxel, field.grid, self.field_friction)
         for s in range(0, T, top):
             e = min(s + top, T)
-            state = (e - s, Vm, self._off, self._cols, self._w, self.rest, self._mass, self._held, H, self._handle_ids, None if hp is None else hp[s:e],
+            part = lambda a: None if a is None else a[s:e]              # this chain's steps of a per-step array
+            state = (e - s, Vm, self._off, self._cols, self._w, self.rest, self._mass, self._held, H, self._handle_ids, part(hp),
                      self._x if s == 0 else out[s - 1], self._v, self.dt, self.stiffness, self.damping, g[0], g[1], g[2], self.iterations,
                      self.cg_iterations, self.cg_tolerance)
-            if field is not None:
-                table = (0, None, None, None) if K == 0 else (K, self._kinds, cp[:e - s] if collider_rows is None else cp[s:e], self._mus)
-                enqueue(dev, entry, *state, *table, self.contact_stiffness, field.nx, field.ny, field.nz, field._origin_c, field.voxel, field.grid,
-                        self.field_friction, out[s:e], self._v, None if contacts is None else contacts[s:e], None if stats is None else stats[s:e],
-                        workspace=self._ws)
-            elif K == 0:                                               # exactly the call there was before there were colliders
-                enqueue(dev, entry, *state, out[s:e], self._v, None if stats is None else stats[s:e], workspace=self._ws)
+            if plain:
+                col = ()
+            elif K == 0:
+                col = (0, None, None, None, self.contact_stiffness)
             else:
-                enqueue(dev, entry, *state, K, self._kinds, cp[:e - s] if collider_rows is None else cp[s:e], self._mus, self.contact_stiffness,
-                        out[s:e], self._v, None if contacts is None else contacts[s:e], None if stats is None else stats[s:e], workspace=self._ws)
+                col = (K, self._kinds, cp[:e - s] if collider_rows is None else cp[s:e], self._mus, self.contact_stiffness)
+            outs = (out[s:e], self._v) + (() if plain else (part(contacts),)) + (part(stats),)
+            enqueue(dev, entry, *state, *col, *fld, *outs, workspace=self._ws)
         self._x.copy_(out[T - 1])
         got = (out,) + ((contacts,) if want_contacts else ()) + ((stats,) if want_stats else ())
         return got if len(got) > 1 else out

@@ -45,8 +45,8 @@ class ContactDynamics(dr.Dynamics):
     """colliders: a sequence of (kind, row [4], friction) as half_space / floor / sphere make them; contact_stiffness kc.  run / step /
     solve_step take collider_rows ([steps,K,4] / [K,4]) for colliders that move; without it the colliders' own rows in every step.
     After run: contact [steps,Vm] int (1 + k* of the rows active in each step's last iteration, 0 elsewhere), phi_star [steps,Vm] (the
-    smallest phi at that iterate; +inf on held rows and with no collider) and gap [steps,Vm] (the second smallest phi minus the smallest;
-    +inf with fewer than two)."""
+    smallest phi at that iterate; +inf on held rows and with no candidate) and gap [steps,Vm] (the second smallest phi minus the smallest;
+    +inf with fewer than two).  What a row can touch is candidates(): a subclass adds to it."""
 
     def __init__(self, *args, colliders=(), contact_stiffness=1.0e4, **kw):
         super().__init__(*args, **kw)
@@ -56,37 +56,39 @@ class ContactDynamics(dr.Dynamics):
         self.kc = float(contact_stiffness)
         self.contact = self.phi_star = self.gap = None
 
+    def candidates(self, X, rows):
+        """(phi [Vm,K'], friction [K'], normal(i, k) of candidate k at row i, per-row arrays run is to keep as well, by name)"""
+        def normal(i, k):
+            if self.kinds[k] == HALF_SPACE:
+                return rows[k, :3]
+            e = X[i] - rows[k, :3]
+            s = np.linalg.norm(e)
+            return e / s if s > 0.0 else np.array([0.0, 1.0, 0.0])
+        return phis(self.kinds, rows, X), self.friction, normal, {}
+
     def contact_terms(self, X, xs, rows):
         """(kappa [Vm], c [Vm,3], which [Vm] int: 1 + k* or 0, phi_star [Vm], gap [Vm]) at the iterate X with the step's start xs"""
-        Vm, K = len(X), len(self.kinds)
+        Vm = len(X)
         kappa, c, which = np.zeros(Vm), np.zeros((Vm, 3)), np.zeros(Vm, np.int64)
-        best, gap = np.full(Vm, np.inf), np.full(Vm, np.inf)
-        if K == 0:
-            return kappa, c, which, best, gap
-        rows = np.asarray(rows, np.float32).astype(np.float64)
-        phi = phis(self.kinds, rows, X)
-        kstar = np.full(Vm, -1)
-        for k in range(K):                                             # phi < best: ties to the lowest k, a NaN never
+        best, gap, kstar = np.full(Vm, np.inf), np.full(Vm, np.inf), np.full(Vm, -1)
+        rows = np.asarray(rows, np.float32).astype(np.float64).reshape(len(self.kinds), 4)
+        phi, friction, normal, also = self.candidates(X, rows)
+        for k in range(phi.shape[1]):                                  # phi < best: ties to the lowest k, a NaN never
             take = phi[:, k] < best
             best[take], kstar[take] = phi[take, k], k
-        if K > 1:
+        if phi.shape[1] > 1:
             s = np.sort(np.where(np.isnan(phi), np.inf, phi), axis=1)
             with np.errstate(invalid="ignore"):
                 gap = np.where(np.isfinite(s[:, 1]), s[:, 1] - s[:, 0], np.inf)
         best[self.held], gap[self.held] = np.inf, np.inf
         for i in np.flatnonzero(self.free & (best < 0.0)):
-            k, p = kstar[i], best[i]
-            if self.kinds[k] == HALF_SPACE:
-                n = rows[k, :3]
-            else:
-                e = X[i] - rows[k, :3]
-                s = np.linalg.norm(e)
-                n = e / s if s > 0.0 else np.array([0.0, 1.0, 0.0])
+            k, p, n = kstar[i], best[i], normal(i, kstar[i])
             u = X[i] - xs[i]
             t = u - (n @ u) * n
-            s, lim = np.linalg.norm(t), self.friction[k] * abs(p)
+            s, lim = np.linalg.norm(t), friction[k] * abs(p)
             scale = 1.0 if s <= lim else lim / s
             kappa[i], c[i], which[i] = self.mu[i] * (self.kc * self.h * self.h), X[i] - p * n - scale * t, 1 + k
+        self.last = dict(also, contact=which, phi_star=best, gap=gap)
         return kappa, c, which, best, gap
 
     def _global_contact_exact(self, X, y, R, kappa, c):
@@ -132,7 +134,7 @@ class ContactDynamics(dr.Dynamics):
 
     def solve_step(self, x, v, targets=None, pcg=None, collider_rows=None):
         """the float64 iterate X of one step from the float32 state, with (y, R of the last iteration, stats [6]); the contact of the
-        last iteration is left in self.last = (which, phi_star, gap)"""
+        last iteration is left in self.last (contact_terms)"""
         rows = self.rows if collider_rows is None else np.asarray(collider_rows, np.float32).reshape(len(self.kinds), 4)
         x, v = np.asarray(x, np.float32).astype(np.float64), np.asarray(v, np.float32).astype(np.float64)
         y = self.prediction(x, v)
@@ -141,8 +143,7 @@ class ContactDynamics(dr.Dynamics):
             X[self.handles] = np.asarray(targets, np.float32).astype(np.float64)
         for _ in range(self.iterations):
             R = self.ref.rotations(X)
-            kappa, c, which, best, gap = self.contact_terms(X, x, rows)
-            self.last = (which, best, gap)
+            kappa, c, which, _, _ = self.contact_terms(X, x, rows)
             if not which.any():
                 X, used, res = self._global_exact(X, y, R) if pcg is None else self._global_pcg(X, y, R, *pcg)
             elif pcg is None:
@@ -154,8 +155,7 @@ class ContactDynamics(dr.Dynamics):
     def step(self, x, v, targets=None, pcg=None, collider_rows=None):
         """(x', v', stats [6]): the state after one step, float32"""
         X, _, _, stats = self.solve_step(x, v, targets, pcg, collider_rows)
-        x64 = np.asarray(x, np.float32).astype(np.float64)
-        vel = (X - x64) / self.h
+        vel = (X - np.asarray(x, np.float32).astype(np.float64)) / self.h
         vel[self.free] *= 1.0 - self.g
         return X.astype(np.float32), vel.astype(np.float32), stats
 
@@ -167,7 +167,6 @@ class ContactDynamics(dr.Dynamics):
             xs.append(x)
             stats.append(s)
             trace.append(self.last)
-        self.contact = np.array([a[0] for a in trace]).reshape(steps, -1)
-        self.phi_star = np.array([a[1] for a in trace]).reshape(steps, -1)
-        self.gap = np.array([a[2] for a in trace]).reshape(steps, -1)
+        for name in trace[0]:                                          # contact, phi_star, gap, and what candidates() named
+            setattr(self, name, np.array([a[name] for a in trace]).reshape(steps, -1))
         return np.array(xs, np.float32).reshape(steps, -1, 3), v, np.array(stats).reshape(steps, 6)
