@@ -4,6 +4,8 @@
   simple_knn.distCUDA2
   deform.SingleObjectDeform (tensor-in deform + the reference attribute names)
   mesh_bind.closest_faces / bind_points (a plain cloud bound to a proxy mesh)
+  mesh_sdf.winding_numbers / inside / signed_distances / grid_values (a triangle mesh as a solid: point-in-mesh tests and the
+    signed-distance grid behind dynamics.SdfGrid.from_mesh)
   arap.ArapSolver (the proxy mesh deformed from dragged handle vertices, as rigidly as possible)
   mesh_pick.ray_mesh_hits / pick / visible_vertices / screen_offset (from a pixel to a vertex of the current mesh and back)
   mesh_region.surface_graph / SurfaceGraph / region_handles (distances along the mesh: a picked vertex grown into a surface region)

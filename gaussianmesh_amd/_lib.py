@@ -86,6 +86,10 @@ SIGNATURES = {
                                + [i32, i32, i32, C.POINTER(f32), f32, vp, f64] + [vp, vp, vp, vp, vp, sz, vp]),
     "gm_ray_mesh_workspace_bytes": (sz, [i32, i32]),
     "gm_ray_mesh": (i32, [i32, vp, vp, i32, vp, i32, vp, f32, f32, vp, vp, vp, vp, sz, vp]),
+    "gm_mesh_winding_workspace_bytes": (sz, [i32, i32]),
+    "gm_mesh_winding": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, sz, vp]),
+    "gm_mesh_signed_distance_workspace_bytes": (sz, [i32, i32]),
+    "gm_mesh_signed_distance": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "gm_mesh_geodesic_workspace_bytes": (sz, [i32, i32, i32]),
     "gm_mesh_geodesic": (i32, [i32, vp, vp, vp, i32, vp, vp, f32, i32, i32, vp, vp, vp, sz, vp]),
     "gm_tsdf_integrate": (i32, [i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), f32, f32, f32, i32, vp, vp, vp]),

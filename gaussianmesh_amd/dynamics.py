@@ -178,6 +178,26 @@ class SdfGrid:
         values, weight = (volume.filled_tsdf, volume.filled_weight) if filled else (volume.tsdf, volume.weight)
         return cls(values, volume.origin, volume.voxel, weight=weight, min_weight=min_weight, scale=volume.trunc, device=values.device)
 
+    @classmethod
+    def from_mesh(cls, vertices, faces, resolution=128, bounds=None, margin=0.5, device="cuda"):
+        """The grid of a triangle mesh as a solid obstacle (mesh_sdf.grid_values: the distance to the closest face, negative where the
+        generalized winding number says inside - open and inward-wound meshes welcome; INTEGRATION.md section AD).  bounds = (min, max),
+        by default the mesh's box grown on every side by margin times its longest side; `resolution` voxels along the bounds' longest
+        side (SceneVisualTool.background_field's rules).  Every sample is known.  Reads the mesh on the host (its box, its face
+        indices).  ValueError for what mesh_sdf.grid_values and mesh_sdf.box_lattice refuse; GmeshError without a device."""
+        from .mesh_bind import mesh_arrays
+        from .mesh_sdf import box_lattice, grid_values
+        who = "SdfGrid.from_mesh"
+        v, f = mesh_arrays(vertices, faces, who)
+        if f.shape[0] == 0 or v.shape[0] == 0:
+            raise ValueError("%s: the mesh is empty (%d vertices, %d faces)" % (who, v.shape[0], f.shape[0]))
+        v = np.asarray(v, np.float32)
+        if not np.isfinite(v).all():
+            raise ValueError("%s: the vertices must be finite" % who)
+        origin, voxel, shape = box_lattice(who, v.min(axis=0), v.max(axis=0), resolution, bounds, margin)
+        need_cuda(torch.device(device), who, "a grid")
+        return cls(grid_values(v, f, origin, voxel, shape, device=device), origin, voxel, device=device)
+
     def sample(self, points):
         """(phi float64 [N], normal float64 [N,3]) of points [N,3] (read as float32), on the device: the distance and unit normal the
         contact step sees (gm_sdf_grid_sample); NaN outside the grid, next to an unknown sample and where the gradient has no direction"""

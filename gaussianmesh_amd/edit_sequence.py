@@ -6,7 +6,8 @@
         [--arap_global_step {column,grid}] [--arap_batch K] [--inbetweens N [--ease {linear,smoothstep}]]
         [--dynamics [--settle N] [--dt S] [--stiffness K] [--damping G] [--gravity X Y Z]
                     [--floor H] [--friction MU] [--contact_stiffness KC] [--colliders FILE.json]
-                    [--background_contact [RES] [--contact_margin M]]]
+                    [--background_contact [RES] [--contact_margin M]]
+                    [--obstacle_mesh FILE.obj [--obstacle_resolution RES] [--obstacle_margin M]]]
 
 --object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
 faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of the two.
@@ -58,6 +59,12 @@ voxels along the longest side of the object's rest box grown by --contact_margin
 (SceneVisualTool.background_field, dynamics.SdfGrid); the volume is one more collider, behind --floor and --colliders, with --friction as
 its friction and --contact_stiffness as everyone's.  Where no view saw the background the volume knows nothing and nothing is in contact
 with it.  Refused without --dynamics or without --background_gaussian; --contact_margin is refused without it.
+--obstacle_mesh FILE.obj (with --dynamics): the simulated mesh also collides with the triangle mesh of FILE.obj, a static solid - a
+table, a bowl, a neighbour's proxy mesh; it may be open or wound inwards (mesh_sdf, the generalized winding number).  Its signed distances
+are sampled on a volume of --obstacle_resolution RES (default 128) voxels along the longest side of the OBSTACLE's box grown by
+--obstacle_margin M (default 0.5) times that side (dynamics.SdfGrid.from_mesh); the volume is one more collider, behind --floor and
+--colliders, with --friction as its friction and --contact_stiffness as everyone's.  Refused without --dynamics and together with
+--background_contact (a simulation takes one volume); --obstacle_resolution and --obstacle_margin are refused without it.
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
@@ -191,6 +198,9 @@ def main(argv=None):
     parser.add_argument("--colliders", type=str, default=None, metavar="FILE.json")
     parser.add_argument("--background_contact", type=int, nargs="?", const=128, default=None, metavar="RES")
     parser.add_argument("--contact_margin", type=float, default=None, metavar="M")
+    parser.add_argument("--obstacle_mesh", type=str, default=None, metavar="FILE.obj")
+    parser.add_argument("--obstacle_resolution", type=int, default=None, metavar="RES")
+    parser.add_argument("--obstacle_margin", type=float, default=None, metavar="M")
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
     parser.add_argument("--save_maps", action="store_true", default=False)
@@ -215,7 +225,8 @@ def main(argv=None):
             if value is not None:
                 raise SystemExit("edit_sequence: %s sets the simulated material and needs --dynamics" % flag)
         for flag, value in (("--floor", args.floor), ("--friction", args.friction), ("--contact_stiffness", args.contact_stiffness),
-                            ("--colliders", args.colliders), ("--background_contact", args.background_contact)):
+                            ("--colliders", args.colliders), ("--background_contact", args.background_contact),
+                            ("--obstacle_mesh", args.obstacle_mesh)):
             if value is not None:
                 raise SystemExit("edit_sequence: %s sets what the simulated mesh collides with and needs --dynamics" % flag)
     if args.background_contact is not None:
@@ -228,6 +239,17 @@ def main(argv=None):
             raise SystemExit("edit_sequence: --contact_margin grows the volume of --background_contact and needs it")
         if not 0.0 <= args.contact_margin < float("inf"):
             raise SystemExit("edit_sequence: --contact_margin %r: a finite number >= 0" % args.contact_margin)
+    if args.obstacle_mesh is not None and args.background_contact is not None:
+        raise SystemExit("edit_sequence: --obstacle_mesh with --background_contact: a simulation takes one volume; drop one of the two")
+    for flag, value in (("--obstacle_resolution", args.obstacle_resolution), ("--obstacle_margin", args.obstacle_margin)):
+        if value is not None and args.obstacle_mesh is None:
+            raise SystemExit("edit_sequence: %s shapes the volume of --obstacle_mesh and needs it" % flag)
+    if args.obstacle_mesh is not None and args.dynamics and not os.path.isfile(args.obstacle_mesh):
+        raise SystemExit("edit_sequence: --obstacle_mesh %s: no such file" % args.obstacle_mesh)
+    if args.obstacle_resolution is not None and args.obstacle_resolution < 2:
+        raise SystemExit("edit_sequence: --obstacle_resolution %d: the volume's resolution, 2 or more voxels along its longest side" % args.obstacle_resolution)
+    if args.obstacle_margin is not None and not 0.0 <= args.obstacle_margin < float("inf"):
+        raise SystemExit("edit_sequence: --obstacle_margin %r: a finite number >= 0" % args.obstacle_margin)
     if args.dynamics:
         if args.mesh_sequence is not None:
             raise SystemExit("edit_sequence: --dynamics simulates the frames of --handle_sequence / --pick_sequence; --mesh_sequence has ready-made meshes")
@@ -237,9 +259,9 @@ def main(argv=None):
             raise SystemExit("edit_sequence: --dynamics with --inbetweens %d: simulated frames are no key poses; drop one of the two" % args.inbetweens)
         if args.floor is not None and (args.gravity is None or not any(args.gravity)):
             raise SystemExit("edit_sequence: --floor lies opposite to gravity and needs a non-zero --gravity X Y Z")
-        if args.friction is not None and args.floor is None and args.colliders is None and args.background_contact is None:
+        if args.friction is not None and args.floor is None and args.colliders is None and args.background_contact is None and args.obstacle_mesh is None:
             raise SystemExit("edit_sequence: --friction is the friction of --floor and --colliders; give one of them")
-        if args.contact_stiffness is not None and args.floor is None and args.colliders is None and args.background_contact is None:
+        if args.contact_stiffness is not None and args.floor is None and args.colliders is None and args.background_contact is None and args.obstacle_mesh is None:
             raise SystemExit("edit_sequence: --contact_stiffness needs something to collide with: --floor or --colliders")
         colliders, moving = ([], {}) if args.colliders is None else read_colliders(args.colliders, args.friction or 0.0)
         if args.floor is not None:
@@ -311,7 +333,16 @@ def main(argv=None):
                 material["field"] = tool.background_field(cams, resolution=args.background_contact,
                                                           margin=0.5 if args.contact_margin is None else args.contact_margin)
                 material["field_friction"] = args.friction or 0.0
-            if (colliders or args.background_contact is not None) and args.contact_stiffness is not None:
+            if args.obstacle_mesh is not None:                                        # a triangle mesh as a static solid
+                from .dynamics import SdfGrid
+                try:
+                    ov, of = read_obj(args.obstacle_mesh)
+                    material["field"] = SdfGrid.from_mesh(ov, of, resolution=128 if args.obstacle_resolution is None else args.obstacle_resolution,
+                                                          margin=0.5 if args.obstacle_margin is None else args.obstacle_margin, device=obj.vertex.device)
+                except ValueError as e:
+                    raise SystemExit("edit_sequence: --obstacle_mesh %s: %s" % (args.obstacle_mesh, e))
+                material["field_friction"] = args.friction or 0.0
+            if (colliders or args.background_contact is not None or args.obstacle_mesh is not None) and args.contact_stiffness is not None:
                 material["contact_stiffness"] = args.contact_stiffness
             if moving:                                                                # the centres of the moving balls, frame by frame
                 from .dynamics import collider_table

@@ -513,6 +513,37 @@ class SceneVisualTool(ObjectVisualTool):
         self.background_volume = vol
         return SdfGrid.from_tsdf(vol)
 
+    def object_field(self, names, resolution=128, bounds=None, margin=0.5):
+        """Objects of the scene as obstacles of another: one dynamics.SdfGrid for simulate(field=) of an object that is not among
+        `names` (INTEGRATION.md section AD).  The source is the CURRENT, deformed proxy mesh of every object called one of `names` (a
+        name or a sequence of names); each becomes signed distances on one shared lattice (mesh_sdf.grid_values) and the grid is their
+        minimum: the union of the solids.  bounds = (min, max), by default the box of those meshes grown on every side by margin times
+        its longest side; `resolution` voxels along the bounds' longest side (background_field's rules).  The grid is static: it shows
+        the obstacles as they are now.  Reads the meshes on the host.  ValueError for no names, a name no object has, and what
+        mesh_sdf.box_lattice refuses."""
+        from .dynamics import SdfGrid
+        from .mesh_sdf import box_lattice, grid_values
+        who = "SceneVisualTool.object_field"
+        names = [names] if isinstance(names, str) else list(names)
+        if not names:
+            raise ValueError("%s: no object named" % who)
+        meshes = []
+        for n in names:
+            found = [o for o in self.gaussians_list if o.get_name() == n]
+            if not found:
+                raise ValueError("%s: no object named %r" % (who, n))
+            for o in found:
+                current = o.mesh_vertex_current
+                meshes.append(((o.vertex if current is None else current).detach().cpu().numpy().astype(np.float32), o.faces.cpu().numpy()))
+        lo = np.min([v.min(axis=0) for v, _ in meshes], axis=0)
+        hi = np.max([v.max(axis=0) for v, _ in meshes], axis=0)
+        origin, voxel, shape = box_lattice(who, lo, hi, resolution, bounds, margin)
+        values = None
+        for v, f in meshes:
+            phi = grid_values(v, f, origin, voxel, shape, device=self.device)
+            values = phi if values is None else torch.minimum(values, phi)
+        return SdfGrid(values, origin, voxel, device=values.device)
+
     def save_baked(self, path, name=None, deg=3, include_background=False):
         """ObjectVisualTool.save_baked for a scene; with include_background the background's raw rows come first, bit for bit as loaded:
         the whole edited scene as one plain Gaussian PLY."""

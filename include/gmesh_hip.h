@@ -493,6 +493,39 @@ size_t gm_ray_mesh_workspace_bytes(int R, int F);
 int gm_ray_mesh(int R, const float* origins, const float* dirs, int Vm, const float* vertices, int F, const int* faces, float t_min, float t_max,
                 float* out_t, int* out_face, float* out_uv, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The generalized winding number of a mesh at every point of a set, and the signed distance composed from it and gm_closest_face: what
+ * turns a triangle mesh into an obstacle of gm_mesh_dynamics_field (mesh_sdf.winding_numbers / inside / signed_distances / grid_values,
+ * dynamics.SdfGrid.from_mesh; INTEGRATION.md section AD).  The reference has no such stage: the result is defined by arithmetic.
+ * points float [N,3], vertices float [Vm,3], faces int32 [F,3] vertex ids; out_w double [N].
+ * Per (point p, face (v0, v1, v2)) the float32 inputs are widened to float64 and every operation after that is float64, no contraction,
+ * dot(x, y) = (x.x*y.x + x.y*y.y) + x.z*y.z, cross products per component as x.y*y.z - x.z*y.y (Van Oosterom & Strackee 1983):
+ *   a = v0 - p, b = v1 - p, c = v2 - p;  la = sqrt(dot(a, a)), lb, lc likewise;  det = dot(a, b x c)
+ *   den = (((la*lb)*lc + dot(a, b)*lc) + dot(b, c)*la) + dot(c, a)*lb;   omega = 2 atan2(det, den)
+ * atan2(0, 0) = 0: a point on a vertex of the face and a face with two equal corners contribute nothing.  The order of summation is
+ * part of the definition: the faces in chunks of 1024 (chunk k = faces [1024 k, 1024 (k + 1))), within a chunk in face order from 0.0,
+ * the chunk sums in chunk order from 0.0, and w = that total / (4 pi), 4 pi = 4 * 0x1.921fb54442d18p+1.  The chunking depends on F
+ * alone, and there are no float atomics: a point's w has the same bits in every run, however its points are batched.  sqrt and the
+ * division are correctly rounded; atan2 is the device library's (about 1 ulp), so a float64 restatement on the host agrees to about
+ * F * 1e-16, not bit for bit.  w is 1 inside a closed mesh wound outwards, -1 inside one wound inwards, 0 outside, and degrades
+ * gracefully where a mesh is open or non-manifold (Jacobson et al. 2013).  Every (point, face) pair is evaluated: O(N F).
+ * gm_mesh_signed_distance: out_phi float [N]; out_face int32 [N], out_closest float [N,3], out_w double [N] may each be NULL.
+ * (d2, out_face, out_closest) are gm_closest_face's, bit for bit; out_w is gm_mesh_winding's; and
+ *   out_phi = NaN if w is NaN or the point has no closest face (face -1);  +0 if d2 == 0;  otherwise s * sqrtf(d2) with the float32
+ *   square root correctly rounded, s = -1 iff fabs(w) > 0.5 and +1 else - fabs: a mesh wound inwards is solid inside all the same.
+ * Both refuse with GM_ERR_INVALID_ARG before any GPU work (every refusal, the workspace's too): a negative size, and with N > 0: F == 0
+ * or Vm == 0, more than 2^31 - 1 workgroups (ceil(N / 256) * ceil(F / 1024): split the points), a NULL among points, vertices, faces,
+ * out_w (gm_mesh_winding) / out_phi (gm_mesh_signed_distance), workspace, a workspace below gm_mesh_winding_workspace_bytes(N, F) /
+ * gm_mesh_signed_distance_workspace_bytes(N, F) (48 F + 8 N ceil(F / 1024) bytes, plus gm_closest_face's and 16 N for the signed
+ * distance; monotonic in both, positive at (0, 0)), an output or the workspace overlapping another buffer of the call.  N == 0
+ * succeeds and launches nothing.  Face indices outside [0, Vm) are forced into range, as in gm_closest_face; mesh_sdf checks them on
+ * the host.  Stream-ordered, no device allocation, no host synchronisation. */
+size_t gm_mesh_winding_workspace_bytes(int N, int F);
+int gm_mesh_winding(int N, const float* points, int Vm, const float* vertices, int F, const int* faces, double* out_w, void* workspace,
+                    size_t workspace_bytes, void* stream);
+size_t gm_mesh_signed_distance_workspace_bytes(int N, int F);
+int gm_mesh_signed_distance(int N, const float* points, int Vm, const float* vertices, int F, const int* faces, float* out_phi, int* out_face,
+                            float* out_closest, double* out_w, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Shortest-path distances along a proxy mesh from B independent source sets: what grows a picked vertex into a surface region
  * (mesh_region.SurfaceGraph.distances / region_handles).  The reference has no such stage: the result is defined by arithmetic.
  * (row_offsets int32 [Vm+1], cols int32 [nnz], lengths float [nnz]): a symmetric CSR with lengths >= 0 (mesh_region.surface_graph: the
