@@ -20,6 +20,7 @@ GM_BATCH_MAX = 8
 GM_SCENE_OBJECTS_MAX = 32
 GM_ARAP_BATCH_MAX = 64
 GM_POSE_INTERP_BATCH_MAX = 64
+GM_SKIN_BONES_MAX = 256
 GM_MESH_DYNAMICS_STEPS_MAX = 64
 GM_MESH_CONTACT_COLLIDERS_MAX = 16
 
@@ -75,6 +76,9 @@ SIGNATURES = {
     "gm_mesh_smooth_rows": (i32, [i32, vp, vp, vp, vp, f64, i32, vp, vp, sz, vp]),
     "gm_pose_interp_workspace_bytes": (sz, [i32, i32, i32]),
     "gm_pose_interp": (i32, [i32, i32, i32] + [vp] * 8 + [i32] + [vp] * 6 + [i32, f64, vp, vp, vp, sz, vp]),
+    "gm_skin_weights_workspace_bytes": (sz, [i32, i32]),
+    "gm_skin_weights": (i32, [i32, i32] + [vp] * 7 + [f64, i32, f64, i32] + [vp] * 5 + [sz, vp]),
+    "gm_skin_pose": (i32, [i32, i32, i32] + [vp] * 4 + [i32, vp, vp]),
     "gm_mesh_dynamics_workspace_bytes": (sz, [i32]),
     "gm_mesh_dynamics": (i32, [i32, i32] + [vp] * 6 + [i32] + [vp] * 4 + [f64] * 6 + [i32, i32, f64, vp, vp, vp, vp, sz, vp]),
     "gm_mesh_dynamics_contact_workspace_bytes": (sz, [i32]),

@@ -542,6 +542,38 @@ class SingleObjectDeform:
         self.deform_vertices(meshes[-1])
         return meshes
 
+    def attach_skeleton(self, skeleton, faces=None, **weight_options):
+        """Bind this object's rest mesh to a skinning.Skeleton: builds the skinning.SkinBinding (bone-heat weights, one PCG per bone on
+        the device; its refusals apply) over the shared mesh_graph and returns it.  weight_options: SkinBinding's heat,
+        max_influences, cg_iterations, cg_tolerance, want_full.  The binding is kept while faces, skeleton and options stay the same.
+        faces [F,3]: for an object built from tensors alone."""
+        from .skinning import SkinBinding
+        self._need_faces("attach_skeleton", faces)
+        key = (id(skeleton), tuple(sorted(weight_options.items())))
+        self.skin = self._operator("skin", key, lambda: SkinBinding(self.mesh_graph, None, skeleton, **weight_options))
+        return self.skin
+
+    def pose_sequence(self, rotations, root_translation=None, blend="dqs"):
+        """The meshes [T,Vm,3] of the attached skeleton's poses: exactly skin.pose_skeleton(rotations, root_translation, blend) -
+        rotations [T,Nj,3,3] matrices or [T,Nj,3] axis-angle vectors, root_translation [T,3] or None -, then deform_vertices of the
+        last one, which leaves the object there (in the manner of simulate and interpolate_to).  Returns the meshes; no host wait."""
+        if getattr(self, "skin", None) is None:
+            raise ValueError("pose_sequence: call attach_skeleton(skeleton) first")
+        meshes = self.skin.pose_skeleton(rotations, root_translation, blend=blend)
+        self.deform_vertices(meshes[-1])
+        return meshes
+
+    def pose(self, rotations, root_translation=None, blend="dqs"):
+        """One pose of the attached skeleton - rotations [Nj,3,3] or [Nj,3], root_translation [3] or None -: leaves the object deformed
+        to it and returns what deform_vertices returns."""
+        import numpy as np
+        if getattr(self, "skin", None) is None:
+            raise ValueError("pose: call attach_skeleton(skeleton) first")
+        rot = np.asarray(rotations.detach().cpu() if torch.is_tensor(rotations) else rotations, np.float64)[None]
+        tr = None if root_translation is None else np.asarray(root_translation.detach().cpu() if torch.is_tensor(root_translation) else root_translation,
+                                                              np.float64).reshape(1, 3)
+        return self.deform_vertices(self.skin.pose_skeleton(rot, tr, blend=blend)[0])
+
     def simulate(self, steps, handle_targets=None, pinned=None, keep_velocity=True, faces=None, collider_rows=None, **options):
         """`steps` steps of secondary motion (dynamics.MeshDynamics: implicit Euler with the ARAP energy as the potential) from
         mesh_vertex_current (the rest pose the first time): the meshes [steps,Vm,3].  The handles are the ones set_handles /

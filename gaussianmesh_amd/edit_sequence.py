@@ -1,9 +1,11 @@
 """Animate an edited object: the animation loop of the reference's edit.py (its commented-out part, edit.py:46-54), batched.
 
     python -m gaussianmesh_amd.edit_sequence (--object_gaussian fg.ply | --object_plain_gaussian cloud.ply) --object_origin_mesh mesh.obj \
-        (--mesh_sequence DIR | --handle_sequence FILE.npz | --pick_sequence FILE.json) --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N]
+        (--mesh_sequence DIR | --handle_sequence FILE.npz | --pick_sequence FILE.json | --pose_sequence FILE.json --skeleton FILE.json)
+        --camera_path MODEL_DIR --render_path OUT [--object_name Object] [--camera_id N]
         [--frames_per_launch 4] [--save_maps] [--save_meshes] [--save_baked PATH] [--background_gaussian BG.ply [--is_exist_bg]]
         [--arap_global_step {column,grid}] [--arap_batch K] [--inbetweens N [--ease {linear,smoothstep}]]
+        [--skin_blend {dqs,linear}] [--skin_heat C] [--skin_influences K]
         [--dynamics [--settle N] [--dt S] [--stiffness K] [--damping G] [--gravity X Y Z]
                     [--floor H] [--friction MU] [--contact_stiffness KC] [--colliders FILE.json]
                     [--background_contact [RES] [--contact_margin M]]
@@ -27,7 +29,16 @@ along the rest mesh, moves with that handle as one rigid patch; every vertex wit
 every vertex farther than free_radius from all handles stays at its rest position; the band in between bends
 (SingleObjectDeform.set_region_handles / drag_region).  Two handle regions that overlap, or a handle region that meets an anchor's, end
 the run with a message naming the picks.  With neither key nothing changes: single-vertex handles as above.
-Exactly one of --mesh_sequence / --handle_sequence / --pick_sequence.  --save_meshes also writes every frame's mesh as {i:05d}.obj.
+--pose_sequence: the mesh posed from a skeleton (skinning.SkinBinding: bone-heat weights solved once on the device, then one skinning launch
+for all frames).  --skeleton FILE.json (required with it) holds {"joints": [[x, y, z], ...], "parents": [...], "names": [...] (optional)}:
+joint 0 is the root (parent -1), a parent comes before its child, bone b runs from joint parents[b + 1] to joint b + 1.  The pose file
+holds {"rotations": [T][Nj][3], "root_translation": [T][3] (optional)}: per frame one axis-angle vector (radians) per joint, about that
+joint's rest position, children following their parents, and a translation of the root.  --skin_blend dqs (the default: dual quaternions,
+a twisted limb keeps its volume) or linear; --skin_heat C (default 1: larger pins a vertex harder to its nearest bone);
+--skin_influences K (default 4: bones kept per vertex, 1 .. 4).  The four are refused without --pose_sequence; --pose_sequence is refused
+with --dynamics and with --arap_batch above 1, and composes with --inbetweens, --save_meshes, --save_baked and --background_gaussian as
+--mesh_sequence does.
+Exactly one of --mesh_sequence / --handle_sequence / --pick_sequence / --pose_sequence.  --save_meshes also writes every frame's mesh as {i:05d}.obj.
 --arap_global_step: the solver's global step for --handle_sequence / --pick_sequence, ArapSolver.solve's global_step: column (the default:
 one workgroup per coordinate) or grid (rows over the whole chip; the same meshes to within the last bits).
 --arap_batch K: for --handle_sequence / --pick_sequence, K frames' solves per launch chain (ArapSolver.solve_sequence, K in 1 .. 64): the
@@ -141,6 +152,37 @@ def read_pick_sequence(path):
     return cam, handles, anchors, offsets, (grab, free)
 
 
+def read_pose_sequence(path, joints=None):
+    """A --pose_sequence file -> (rotations float64 [T,Nj,3] axis-angle, root_translation float64 [T,3] or None); SystemExit naming what
+    is wrong with it.  joints: the skeleton's joint count, where it is known.  Host work only."""
+    import json
+    import numpy as np
+    bad = lambda what: SystemExit("edit_sequence: %s: %s" % (path, what))
+    try:
+        with open(path) as fh:
+            doc = json.load(fh)
+    except (OSError, ValueError) as e:
+        raise bad("cannot read it as JSON (%s)" % e)
+    if not isinstance(doc, dict):
+        raise bad("must hold a JSON object")
+    try:
+        rot = np.asarray(doc.get("rotations"), np.float64)
+    except (TypeError, ValueError):
+        rot = None
+    if rot is None or rot.ndim != 3 or rot.shape[0] == 0 or rot.shape[2] != 3 or (joints is not None and rot.shape[1] != joints) or not np.isfinite(rot).all():
+        raise bad('"rotations" must be [T][%s][3] finite axis-angle vectors, one per joint, T >= 1; got shape %s'
+                  % ("Nj" if joints is None else joints, None if rot is None else rot.shape))
+    if "root_translation" not in doc:
+        return rot, None
+    try:
+        tr = np.asarray(doc.get("root_translation"), np.float64)
+    except (TypeError, ValueError):
+        tr = None
+    if tr is None or tr.shape != (rot.shape[0], 3) or not np.isfinite(tr).all():
+        raise bad('"root_translation" must be [%d][3] finite numbers, one row per frame; got shape %s' % (rot.shape[0], None if tr is None else tr.shape))
+    return rot, tr
+
+
 def read_colliders(path, friction):
     """A --colliders file -> (colliders: a list of dicts for MeshDynamics, moving: {index: centres [[x, y, z], ...]}); SystemExit naming
     what is wrong with it.  Host work only, no numpy; the numbers themselves are MeshDynamics' to check."""
@@ -181,6 +223,11 @@ def main(argv=None):
     source.add_argument("--mesh_sequence", type=str, default=None)
     source.add_argument("--handle_sequence", type=str, default=None)
     source.add_argument("--pick_sequence", type=str, default=None)
+    source.add_argument("--pose_sequence", type=str, default=None, metavar="FILE.json")
+    parser.add_argument("--skeleton", type=str, default=None, metavar="FILE.json")
+    parser.add_argument("--skin_blend", choices=("dqs", "linear"), default=None)
+    parser.add_argument("--skin_heat", type=float, default=None, metavar="C")
+    parser.add_argument("--skin_influences", type=int, default=None, metavar="K")
     parser.add_argument("--save_meshes", action="store_true", default=False)
     parser.add_argument("--arap_global_step", choices=("column", "grid"), default="column")
     parser.add_argument("--arap_batch", type=int, default=1)
@@ -218,6 +265,23 @@ def main(argv=None):
         raise SystemExit("edit_sequence: --inbetweens %d: the number of frames between two keys, 0 or more" % args.inbetweens)
     if args.settle < 0:
         raise SystemExit("edit_sequence: --settle %d: the number of steps appended with the handles held, 0 or more" % args.settle)
+    if args.pose_sequence is None:
+        for flag, value in (("--skeleton", args.skeleton), ("--skin_blend", args.skin_blend), ("--skin_heat", args.skin_heat),
+                            ("--skin_influences", args.skin_influences)):
+            if value is not None:
+                raise SystemExit("edit_sequence: %s belongs to --pose_sequence (a mesh posed from a skeleton) and needs it" % flag)
+    else:
+        if args.skeleton is None:
+            raise SystemExit("edit_sequence: --pose_sequence poses a skeleton and needs --skeleton FILE.json")
+        if args.dynamics:
+            raise SystemExit("edit_sequence: --dynamics simulates the frames of --handle_sequence / --pick_sequence; --pose_sequence has posed meshes")
+        if args.arap_batch > 1:
+            raise SystemExit("edit_sequence: --pose_sequence with --arap_batch %d: there is no ARAP solve to batch; drop --arap_batch" % args.arap_batch)
+        if args.skin_heat is not None and not 0.0 < args.skin_heat < float("inf"):
+            raise SystemExit("edit_sequence: --skin_heat %r: a finite number > 0" % args.skin_heat)
+        if args.skin_influences is not None and not 1 <= args.skin_influences <= 4:
+            raise SystemExit("edit_sequence: --skin_influences %d: the bones kept per vertex, 1 .. 4" % args.skin_influences)
+        pose_rotations, pose_translation = read_pose_sequence(args.pose_sequence)
     if args.settle > 0 and not args.dynamics:
         raise SystemExit("edit_sequence: --settle needs --dynamics (only a simulated mesh has anything to settle)")
     if not args.dynamics:
@@ -360,6 +424,21 @@ def main(argv=None):
         else:
             # enqueued back to back: no host wait between the solves; --arap_batch frames per launch chain
             meshes = list(solver.solve_sequence(positions, batch=args.arap_batch, global_step=args.arap_global_step))
+    if args.pose_sequence is not None:                                                # weights once, then all frames in one skinning launch
+        from .skinning import Skeleton
+        obj = tool.gaussians_list[-1]
+        try:
+            skeleton = Skeleton.read(args.skeleton)
+        except ValueError as e:
+            raise SystemExit("edit_sequence: --skeleton: %s" % e)
+        if pose_rotations.shape[1] != skeleton.Nj:
+            read_pose_sequence(args.pose_sequence, joints=skeleton.Nj)
+        try:
+            obj.attach_skeleton(skeleton, heat=1.0 if args.skin_heat is None else args.skin_heat,
+                                max_influences=4 if args.skin_influences is None else args.skin_influences)
+            meshes = list(obj.pose_sequence(pose_rotations, pose_translation, blend=args.skin_blend or "dqs"))
+        except ValueError as e:
+            raise SystemExit("edit_sequence: --pose_sequence: %s" % e)
     if args.inbetweens > 0:                                                           # the frames so far are keys; the rest pose is key 0
         from .pose_interp import PoseInterpolator
         obj = tool.gaussians_list[-1]

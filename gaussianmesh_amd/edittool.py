@@ -226,6 +226,19 @@ class ObjectVisualTool:
                 meshes = g.interpolate_to(target, inbetweens, **options)
         return meshes
 
+    def pose_one_gaussian(self, name, rotations, root_translation=None, blend="dqs", skeleton=None, **weight_options):
+        """The objects called `name` posed from a skeleton (SingleObjectDeform.pose_sequence: skinning.SkinBinding): rotations
+        [T,Nj,3,3] or [T,Nj,3] axis-angle, root_translation [T,3] or None.  skeleton: a skinning.Skeleton to attach first
+        (attach_skeleton, with weight_options); None: the one attached before.  The objects are left at the last pose.  Returns the
+        meshes [T,Vm,3] of the last such object (None if there is none)."""
+        meshes = None
+        for g in self.gaussians_list:
+            if g.get_name() == name:
+                if skeleton is not None:
+                    g.attach_skeleton(skeleton, **weight_options)
+                meshes = g.pose_sequence(rotations, root_translation, blend=blend)
+        return meshes
+
     def simulate_one_gaussian(self, name, steps, handle_targets=None, collider_rows=None, **options):
         """`steps` simulated steps of the objects called `name` from their current mesh (SingleObjectDeform.simulate: secondary motion,
         dynamics.MeshDynamics) with their handles at handle_targets [steps,H,3] and, with colliders= among the options, those at

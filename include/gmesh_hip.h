@@ -358,6 +358,35 @@ int gm_pose_interp(int T, int Vm, int F, const int* row_offsets, const int* cols
                    const int* label, const float* A, const float* B, const double* ts, int cg_iterations, double cg_tolerance, float* V_out,
                    double* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The proxy mesh posed from a skeleton (skinning.SkinBinding; definition: csrc/gm_skin.hip, INTEGRATION.md section AE).
+ * gm_skin_weights: the bone-heat weights (Baran & Popovic 2007) of J bones - rest segments bone_a[j] -> bone_b[j], float [J,3] - over the
+ * mesh of gm_arap_solve's CSR (row_offsets / cols / weights, arap.edge_csr); V0 float [Vm,3], area double [Vm] (dynamics.vertex_masses at
+ * density 1).  One workgroup per bone solves (diag(h) + L) w_j = h o p_j by the Jacobi-preconditioned CG of gm_arap_solve's global step,
+ * h_i = heat area_i / d2min_i, stopped at |r| <= cg_tolerance |b| or after cg_iterations steps.  Of a vertex's J weights the
+ * max_influences (1 .. 4) largest are kept, negatives clamped to 0, renormalised: out_ids int32 [Vm,4], out_w float [Vm,4], by falling
+ * weight; an unused slot repeats slot 0's id with weight 0.  out_full (or NULL): the columns before compaction, double [J,Vm].  out_stats
+ * (or NULL) double [J,2]: CG steps used, final |r| / |b| per bone.  No atomics: the same bits from call to call.  Column ids of the CSR
+ * are forced into [0, Vm); row_offsets must ascend.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: Vm < 1, J < 1 or J > GM_SKIN_BONES_MAX, a heat that is not positive and finite,
+ * cg_iterations < 1, a cg_tolerance that is negative or not finite, max_influences outside 1 .. 4, a NULL among the required pointers,
+ * any overlap of an output or the workspace with one another or with V0, area, bone_a, bone_b; with GM_ERR_BUFFER a workspace below
+ * gm_skin_weights_workspace_bytes(Vm, J) (O(J Vm), monotonic; 0 for arguments that would be refused).
+ * gm_skin_pose: T frames of the rest mesh skinned by transforms float [T,J,3,4] (rest-to-posed [A | t] per frame and bone), ids int32
+ * [Vm,4] (forced into [0, J)) and w float [Vm,4] from gm_skin_weights or from anywhere; out float [T,Vm,3].  blend GM_SKIN_BLEND_LINEAR:
+ * x' = (sum_k w_k (A_k x + t_k)) / (sum_k w_k); GM_SKIN_BLEND_DQS: dual-quaternion blending (Kavan et al. 2008), for which every A must be
+ * a rotation (the caller's to check; anything else gives numbers, never a fault).  float64 arithmetic, rounded once; frame t is bit for
+ * bit what a call with T = 1 and its transforms writes.  Refused with GM_ERR_INVALID_ARG: T < 1, Vm < 1, J outside 1 .. GM_SKIN_BONES_MAX,
+ * another blend, a NULL pointer, out overlapping an input.  Both are stream-ordered, without device allocation or host synchronisation. */
+#define GM_SKIN_BONES_MAX 256
+#define GM_SKIN_BLEND_LINEAR 0
+#define GM_SKIN_BLEND_DQS 1
+size_t gm_skin_weights_workspace_bytes(int Vm, int J);
+int gm_skin_weights(int Vm, int J, const int* row_offsets, const int* cols, const double* weights, const float* V0, const double* area,
+                    const float* bone_a, const float* bone_b, double heat, int cg_iterations, double cg_tolerance, int max_influences,
+                    int* out_ids, float* out_w, double* out_full, double* out_stats, void* workspace, size_t workspace_bytes, void* stream);
+int gm_skin_pose(int T, int Vm, int J, const float* V0, const int* ids, const float* w, const float* transforms, int blend, float* out,
+                 void* stream);
+
 /* Secondary motion of a proxy mesh (dynamics.MeshDynamics): T implicit-Euler steps of an elastic mesh whose potential is the ARAP energy,
  * in ONE launch chain - the local/global iteration of projective dynamics (Bouaziz et al. 2014) over gm_arap_solve's CSR, whose global
  * step's matrix gains the positive diagonal mu (definition: csrc/gm_dynamics.hip, INTEGRATION.md section AA).  row_offsets / cols /
