@@ -79,6 +79,8 @@ SIGNATURES = {
     "gm_skin_weights_workspace_bytes": (sz, [i32, i32]),
     "gm_skin_weights": (i32, [i32, i32] + [vp] * 7 + [f64, i32, f64, i32] + [vp] * 5 + [sz, vp]),
     "gm_skin_pose": (i32, [i32, i32, i32] + [vp] * 4 + [i32, vp, vp]),
+    "gm_skin_pose_bwd_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "gm_skin_pose_bwd": (i32, [i32, i32, i32] + [vp] * 4 + [i32] + [vp] * 5 + [sz, vp]),
     "gm_mesh_dynamics_workspace_bytes": (sz, [i32]),
     "gm_mesh_dynamics": (i32, [i32, i32] + [vp] * 6 + [i32] + [vp] * 4 + [f64] * 6 + [i32, i32, f64, vp, vp, vp, vp, sz, vp]),
     "gm_mesh_dynamics_contact_workspace_bytes": (sz, [i32]),

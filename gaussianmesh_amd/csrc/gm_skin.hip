@@ -323,6 +323,223 @@ __global__ __launch_bounds__(SKIN_ROW_THREADS) void skin_pose_kernel(int Vm, int
   o[0] = (float)y[0]; o[1] = (float)y[1]; o[2] = (float)y[2];
 }
 
+// ---------------------------------------------------------------------------------------------
+// gm_skin_pose_bwd: the vector-Jacobian product of DEFINITION, POSE with respect to the transforms, float64 throughout from the float32
+// inputs (g_out float32, read as float64).  The forward's decisions are constants: the Shepperd branch and the sign that makes q_w >= 0
+// of each (frame, bone), the slots' signs s_k, the |b_r| < 1e-12 fallback, the sum == 0 row.
+//   Linear (and the rows of dqs that fell back):  g_M[k][a][:] += w_k (g[a] / sum) (x, 1) for every (vertex, slot) of bone k; nothing from
+//   a row whose weights sum to 0.
+//   Dual quaternion, per vertex with G = 2 g, u = b_v x x + b_w x (b normalised):
+//     g_bv = u x G + x x (G x b_v) - d_w G + d_v x G;  g_bw = (G x b_v) . x + G . d_v;  g_dv = b_w G + G x b_v;  g_dw = -G . b_v;
+//     g_b[f] = g_bh[f] / n - [f < 4] bh_f (sum_e g_bh[e] bh_e) / n;  g_q_k = sum over the bone's (vertex, slot) of s_k w_k g_b.
+//   Per (frame, bone), back through skin_dual_quaternion: q_d = (-(t . v) / 2, (w t + t x v) / 2) gives g_t and adds to g_q_r; the
+//   normalisation q = sg raw / |raw|: g_raw = sg (g_q - q (q . g_q)) / |raw|; the branch: its pivot is s / 4, the others N_i / s with
+//   s = 2 sqrt(D), D = 1 +- A00 +- A11 +- A22, N_i = A_ab +- A_ba: g_s = g_pivot / 4 - sum_i raw_i g_raw_i / s, g_D = 2 g_s / s.
+//   Off the rotation manifold the gradient is what this arithmetic's extension gives (tests/skin_bwd_ref.py states it through autograd).
+// Two launches per 32768 frames, no atomics (the shape of gm_deform_bwd.hip):
+//   rows   grid (ceil(Vm / 256), T), one thread per (frame, vertex): workspace row [T][Vm][ROW] float64 - linear ROW = 3: g / sum (zeros
+//          where sum == 0); dqs ROW = 12: g_b [8] (zeros on a fallback row) | g / sum [3] (fallback rows only, else zeros) | the slots'
+//          signs as bits 0 .. 3 of an integer kept in the 12th double.  Every element of a row is written.
+//   bones  grid (ceil(J / 4), T), one wave per (frame, bone) over its incidence list (CSR: bone_offsets [J+1], bone_entries = 4 vertex +
+//          slot, ascending): lane l takes entries l, l + 64, .. in that order, then a fixed xor butterfly; lane 0 turns g_dq into g_M and
+//          writes the bone's 12 doubles.  An empty list gives exact zeros; an entry outside [0, 4 Vm) is skipped; offsets are forced
+//          into [0, 4 Vm] (the list's consistency with ids is the caller's contract; this only keeps the reads in bounds).
+// A frame reads its own transforms, g_out and workspace rows only: its bits depend on neither T nor its place.
+// Contraction is off from here on: the restated forward decides s_k and the fallback by plain IEEE products and sums.
+#pragma clang fp contract(off)
+
+constexpr int SKIN_BWD_ROW_LINEAR = 3;
+constexpr int SKIN_BWD_ROW_DQS = 12;
+
+template <int BLEND>
+__global__ __launch_bounds__(SKIN_ROW_THREADS) void skin_pose_bwd_rows_kernel(int Vm, int J, const float* __restrict__ V0,
+                                                                              const int* __restrict__ ids, const float* __restrict__ w,
+                                                                              const float* __restrict__ transforms,
+                                                                              const float* __restrict__ g_out, double* __restrict__ rows) {
+  constexpr int ROW = BLEND ? SKIN_BWD_ROW_DQS : SKIN_BWD_ROW_LINEAR;
+  __shared__ double dq[BLEND ? GM_SKIN_BONES_MAX : 1][8];
+  if constexpr (BLEND) {
+    const float* M = transforms + (size_t)blockIdx.y * J * 12;
+    for (int j = threadIdx.x; j < J; j += SKIN_ROW_THREADS) skin_dual_quaternion(M + 12 * (size_t)j, dq[j]);
+    __syncthreads();
+  }
+  const int i = blockIdx.x * SKIN_ROW_THREADS + threadIdx.x;
+  if (i >= Vm) return;
+  const size_t at = (size_t)blockIdx.y * Vm + i;
+  double* o = rows + at * ROW;
+  double x[3], g[3], wk[4];
+  skin_load3(V0, (size_t)i, x);
+  skin_load3(g_out, at, g);
+#pragma unroll
+  for (int k = 0; k < 4; k++) wk[k] = (double)w[4 * (size_t)i + k];
+  if constexpr (BLEND) {
+    int id[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) id[k] = clamp_index(ids[4 * (size_t)i + k], J);
+    double b[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    long long bits = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const double* qk = dq[id[k]];
+      const double* q0 = dq[id[0]];
+      const double dot = qk[0] * q0[0] + qk[1] * q0[1] + qk[2] * q0[2] + qk[3] * q0[3];
+      const double s = dot < 0.0 ? -wk[k] : wk[k];
+      if (dot < 0.0) bits |= 1ll << k;
+#pragma unroll
+      for (int e = 0; e < 8; e++) b[e] += s * qk[e];
+    }
+    o[11] = __longlong_as_double(bits);
+    const double n = sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2] + b[3] * b[3]);
+    if (!(n < 1e-12)) {
+#pragma unroll
+      for (int e = 0; e < 8; e++) b[e] /= n;
+      const double bw = b[0], bv[3] = {b[1], b[2], b[3]}, dw = b[4], dv[3] = {b[5], b[6], b[7]};
+      const double G[3] = {2.0 * g[0], 2.0 * g[1], 2.0 * g[2]};
+      double c1[3], u[3], gu[3], t1[3], t2[3], t3[3], gh[8];
+      cross3(bv, x, c1);
+#pragma unroll
+      for (int a = 0; a < 3; a++) u[a] = c1[a] + bw * x[a];
+      cross3(G, bv, gu);                           // g_u: also the gradient the cross product b_v x d_v hands to d_v
+      cross3(u, G, t1);
+      cross3(x, gu, t2);
+      cross3(dv, G, t3);
+      gh[0] = (gu[0] * x[0] + gu[1] * x[1] + gu[2] * x[2]) + (G[0] * dv[0] + G[1] * dv[1] + G[2] * dv[2]);
+      gh[4] = -(G[0] * bv[0] + G[1] * bv[1] + G[2] * bv[2]);
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        gh[1 + a] = ((t1[a] + t2[a]) - dw * G[a]) + t3[a];
+        gh[5 + a] = bw * G[a] + gu[a];
+      }
+      double S = 0.0;
+#pragma unroll
+      for (int e = 0; e < 8; e++) S += gh[e] * b[e];
+      S /= n;
+#pragma unroll
+      for (int e = 0; e < 8; e++) o[e] = e < 4 ? gh[e] / n - b[e] * S : gh[e] / n;
+      o[8] = 0.0; o[9] = 0.0; o[10] = 0.0;
+      return;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; e++) o[e] = 0.0;
+  }
+  double sum = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) sum += wk[k];
+  double* l = o + (BLEND ? 8 : 0);
+#pragma unroll
+  for (int a = 0; a < 3; a++) l[a] = sum != 0.0 ? g[a] / sum : 0.0;
+}
+
+// gM [12] += the gradient of M = [A | t] (row-major 3 x 4) from G = g_dq [8]: skin_dual_quaternion restated with what its backward needs.
+// Branch P: raw[P] = s / 4, raw[i] = (A[IA][IB] + SG A[IB][IA]) / s for the others, s = 2 sqrt(1 + DD . diag A).
+template <int P>
+__device__ __forceinline__ void skin_dual_quaternion_bwd_branch(const double A[9], const double t[3], const double G[8], double gM[12]) {
+  constexpr int IA[4][4] = {{0, 2, 0, 1}, {2, 0, 0, 0}, {0, 0, 0, 1}, {1, 0, 1, 0}};
+  constexpr int IB[4][4] = {{0, 1, 2, 0}, {1, 0, 1, 2}, {2, 1, 0, 2}, {0, 2, 2, 0}};
+  constexpr double SG[4][4] = {{0.0, -1.0, -1.0, -1.0}, {-1.0, 0.0, 1.0, 1.0}, {-1.0, 1.0, 0.0, 1.0}, {-1.0, 1.0, 1.0, 0.0}};
+  constexpr double DD[4][3] = {{1.0, 1.0, 1.0}, {1.0, -1.0, -1.0}, {-1.0, 1.0, -1.0}, {-1.0, -1.0, 1.0}};
+  const double s = 2.0 * sqrt(((1.0 + DD[P][0] * A[0]) + DD[P][1] * A[4]) + DD[P][2] * A[8]);
+  double raw[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) raw[i] = i == P ? 0.25 * s : (A[3 * IA[P][i] + IB[P][i]] + SG[P][i] * A[3 * IB[P][i] + IA[P][i]]) / s;
+  const double nn = sqrt(raw[0] * raw[0] + raw[1] * raw[1] + raw[2] * raw[2] + raw[3] * raw[3]);
+  const double f = (raw[0] < 0.0 ? -1.0 : 1.0) / nn;
+  const double q[4] = {raw[0] * f, raw[1] * f, raw[2] * f, raw[3] * f};
+  // q_d = (-(t . v) / 2, (q_w t + t x v) / 2)
+  const double Gd[3] = {G[5], G[6], G[7]};
+  double vG[3], Gt[3], gq[4];
+  cross3(q + 1, Gd, vG);
+  cross3(Gd, t, Gt);
+  gq[0] = G[0] + 0.5 * (Gd[0] * t[0] + Gd[1] * t[1] + Gd[2] * t[2]);
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    gM[4 * a + 3] += (0.5 * q[0] * Gd[a] - 0.5 * G[4] * q[1 + a]) + 0.5 * vG[a];
+    gq[1 + a] = (G[1 + a] - 0.5 * G[4] * t[a]) + 0.5 * Gt[a];
+  }
+  // q = f raw, f = sign / |raw|
+  const double qg = q[0] * gq[0] + q[1] * gq[1] + q[2] * gq[2] + q[3] * gq[3];
+  double gs = 0.0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const double graw = f * (gq[i] - q[i] * qg);
+    if (i == P) { gs += 0.25 * graw; continue; }
+    gs -= raw[i] * graw / s;
+    gM[4 * IA[P][i] + IB[P][i]] += graw / s;
+    gM[4 * IB[P][i] + IA[P][i]] += SG[P][i] * (graw / s);
+  }
+  const double gD = 2.0 * gs / s;
+#pragma unroll
+  for (int a = 0; a < 3; a++) gM[5 * a] += DD[P][a] * gD;
+}
+
+__device__ __forceinline__ void skin_dual_quaternion_bwd(const float* __restrict__ M, const double G[8], double gM[12]) {
+  double A[9], t[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+#pragma unroll
+    for (int b = 0; b < 3; b++) A[3 * a + b] = (double)M[4 * a + b];
+    t[a] = (double)M[4 * a + 3];
+  }
+  const double tr = A[0] + A[4] + A[8];
+  if (tr >= A[0] && tr >= A[4] && tr >= A[8]) skin_dual_quaternion_bwd_branch<0>(A, t, G, gM);
+  else if (A[0] >= A[4] && A[0] >= A[8]) skin_dual_quaternion_bwd_branch<1>(A, t, G, gM);
+  else if (A[4] >= A[8]) skin_dual_quaternion_bwd_branch<2>(A, t, G, gM);
+  else skin_dual_quaternion_bwd_branch<3>(A, t, G, gM);
+}
+
+// one wave per (frame, bone), four bones per workgroup
+template <int BLEND>
+__global__ __launch_bounds__(256) void skin_pose_bwd_bones_kernel(int Vm, int J, const float* __restrict__ V0, const float* __restrict__ w,
+                                                                  const float* __restrict__ transforms, const int* __restrict__ bone_offsets,
+                                                                  const int* __restrict__ bone_entries, const double* __restrict__ rows,
+                                                                  double* __restrict__ g_transforms) {
+  constexpr int ROW = BLEND ? SKIN_BWD_ROW_DQS : SKIN_BWD_ROW_LINEAR;
+  constexpr int NACC = BLEND ? 20 : 12;              // g_M [12] | g_dq [8]
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= J) return;                              // (wave-uniform)
+  const int lane = threadIdx.x & 63;
+  const long long n4 = 4ll * Vm;
+  long long lo = bone_offsets[j], hi = bone_offsets[j + 1];
+  lo = lo < 0 ? 0 : lo; hi = hi > n4 ? n4 : hi;
+  const double* frame_rows = rows + (size_t)blockIdx.y * Vm * ROW;
+  double acc[NACC];
+#pragma unroll
+  for (int k = 0; k < NACC; k++) acc[k] = 0.0;
+  for (long long jj = lo + lane; jj < hi; jj += 64) {
+    const int e = bone_entries[jj];
+    if (e < 0 || e >= n4) continue;
+    const size_t v = (size_t)(e >> 2);
+    const double we = (double)w[e];
+    const double* r = frame_rows + v * ROW;
+    const double* l = r + (BLEND ? 8 : 0);
+    double x[3];
+    skin_load3(V0, v, x);
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      const double c = we * l[a];
+#pragma unroll
+      for (int b = 0; b < 3; b++) acc[4 * a + b] = acc[4 * a + b] + c * x[b];
+      acc[4 * a + 3] = acc[4 * a + 3] + c;
+    }
+    if constexpr (BLEND) {
+      const double s = ((__double_as_longlong(r[11]) >> (e & 3)) & 1) ? -we : we;
+#pragma unroll
+      for (int k = 0; k < 8; k++) acc[12 + k] = acc[12 + k] + s * r[k];
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int k = 0; k < NACC; k++) acc[k] = acc[k] + __shfl_xor(acc[k], off);
+  if (lane == 0) {
+    const size_t at = (size_t)blockIdx.y * J + j;
+    if constexpr (BLEND) skin_dual_quaternion_bwd(transforms + at * 12, acc + 12, acc);
+    double* o = g_transforms + at * 12;
+#pragma unroll
+    for (int k = 0; k < 12; k++) o[k] = acc[k];
+  }
+}
+
 }  // namespace gm
 
 // ---------------------------------------------------------------------------------------------
@@ -391,6 +608,53 @@ int gm_skin_pose(int T, int Vm, int J, const float* V0, const int* ids, const fl
     float* o = out + (size_t)t0 * Vm * 3;
     if (blend == GM_SKIN_BLEND_DQS) hipLaunchKernelGGL(skin_pose_kernel<1>, dim3(G, n), dim3(SKIN_ROW_THREADS), 0, s, Vm, J, V0, ids, w, M, o);
     else hipLaunchKernelGGL(skin_pose_kernel<0>, dim3(G, n), dim3(SKIN_ROW_THREADS), 0, s, Vm, J, V0, ids, w, M, o);
+  }
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+size_t gm_skin_pose_bwd_workspace_bytes(int T, int Vm, int J, int blend) {
+  if (T < 1 || Vm < 1 || J < 1 || J > GM_SKIN_BONES_MAX || (blend != GM_SKIN_BLEND_LINEAR && blend != GM_SKIN_BLEND_DQS)) return 0;
+  const size_t row = blend == GM_SKIN_BLEND_DQS ? SKIN_BWD_ROW_DQS : SKIN_BWD_ROW_LINEAR;
+  return ((size_t)T * Vm * row * sizeof(double) + 255) & ~(size_t)255;
+}
+
+int gm_skin_pose_bwd(int T, int Vm, int J, const float* V0, const int* ids, const float* w, const float* transforms, int blend,
+                     const float* g_out, const int* bone_offsets, const int* bone_entries, double* g_transforms, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  const char* fn = "gm_skin_pose_bwd";
+  if (T < 1) { set_error("%s: T = %d (must be positive)", fn, T); return GM_ERR_INVALID_ARG; }
+  if (Vm < 1) { set_error("%s: Vm = %d (must be positive)", fn, Vm); return GM_ERR_INVALID_ARG; }
+  if (J < 1 || J > GM_SKIN_BONES_MAX) { set_error("%s: J = %d bones (1 .. %d)", fn, J, GM_SKIN_BONES_MAX); return GM_ERR_INVALID_ARG; }
+  if (blend != GM_SKIN_BLEND_LINEAR && blend != GM_SKIN_BLEND_DQS) { set_error("%s: blend = %d (0 linear, 1 dual quaternion)", fn, blend); return GM_ERR_INVALID_ARG; }
+  if (!V0 || !ids || !w || !transforms || !g_out || !bone_offsets || !bone_entries || !g_transforms || !workspace) {
+    set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG;
+  }
+  const size_t need = gm_skin_pose_bwd_workspace_bytes(T, Vm, J, blend);
+  // (bone_entries holds bone_offsets[J] ints, a number on the device: its first element stands for it)
+  const ByteRange rg[9] = {{g_transforms, 96 * (size_t)T * J, "g_transforms", true}, {workspace, workspace_bytes, "workspace", true},
+                           {V0, 12 * (size_t)Vm, "V0", false}, {ids, 16 * (size_t)Vm, "ids", false}, {w, 16 * (size_t)Vm, "w", false},
+                           {transforms, 48 * (size_t)T * J, "transforms", false}, {g_out, 12 * (size_t)Vm * T, "g_out", false},
+                           {bone_offsets, 4 * ((size_t)J + 1), "bone_offsets", false}, {bone_entries, 4, "bone_entries", false}};
+  if (int rc = check_ranges(fn, rg)) return rc;
+  if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int G = (Vm + SKIN_ROW_THREADS - 1) / SKIN_ROW_THREADS, B = (J + 3) / 4;
+  const bool dqs = blend == GM_SKIN_BLEND_DQS;
+  const size_t row = dqs ? SKIN_BWD_ROW_DQS : SKIN_BWD_ROW_LINEAR;
+  for (int t0 = 0; t0 < T; t0 += SKIN_POSE_FRAMES) {
+    const int n = T - t0 < SKIN_POSE_FRAMES ? T - t0 : SKIN_POSE_FRAMES;
+    const float* M = transforms + (size_t)t0 * J * 12;
+    const float* g = g_out + (size_t)t0 * Vm * 3;
+    double* rows = reinterpret_cast<double*>(workspace) + (size_t)t0 * Vm * row;
+    double* o = g_transforms + (size_t)t0 * J * 12;
+    if (dqs) {
+      hipLaunchKernelGGL(skin_pose_bwd_rows_kernel<1>, dim3(G, n), dim3(SKIN_ROW_THREADS), 0, s, Vm, J, V0, ids, w, M, g, rows);
+      hipLaunchKernelGGL(skin_pose_bwd_bones_kernel<1>, dim3(B, n), dim3(256), 0, s, Vm, J, V0, w, M, bone_offsets, bone_entries, rows, o);
+    } else {
+      hipLaunchKernelGGL(skin_pose_bwd_rows_kernel<0>, dim3(G, n), dim3(SKIN_ROW_THREADS), 0, s, Vm, J, V0, ids, w, M, g, rows);
+      hipLaunchKernelGGL(skin_pose_bwd_bones_kernel<0>, dim3(B, n), dim3(256), 0, s, Vm, J, V0, w, M, bone_offsets, bone_entries, rows, o);
+    }
   }
   GM_HIP(hipGetLastError());
   return GM_OK;

@@ -561,7 +561,17 @@ class SingleObjectDeform:
             raise ValueError("pose_sequence: call attach_skeleton(skeleton) first")
         meshes = self.skin.pose_skeleton(rotations, root_translation, blend=blend)
         self.deform_vertices(meshes[-1])
+        self._remember_pose(rotations, root_translation)
         return meshes
+
+    def _remember_pose(self, rotations, root_translation):
+        """keeps the last frame's axis-angle parameters for drag_skeleton to start from (matrices are not kept: it starts at rest)"""
+        import numpy as np
+        host = lambda a: np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, np.float64)
+        rot = host(rotations)
+        self.skeleton_pose = None
+        if rot.ndim == 3 and rot.shape[2] == 3:
+            self.skeleton_pose = (rot[-1].copy(), np.zeros(3) if root_translation is None else host(root_translation).reshape(-1, 3)[-1].copy())
 
     def pose(self, rotations, root_translation=None, blend="dqs"):
         """One pose of the attached skeleton - rotations [Nj,3,3] or [Nj,3], root_translation [3] or None -: leaves the object deformed
@@ -572,7 +582,35 @@ class SingleObjectDeform:
         rot = np.asarray(rotations.detach().cpu() if torch.is_tensor(rotations) else rotations, np.float64)[None]
         tr = None if root_translation is None else np.asarray(root_translation.detach().cpu() if torch.is_tensor(root_translation) else root_translation,
                                                               np.float64).reshape(1, 3)
-        return self.deform_vertices(self.skin.pose_skeleton(rot, tr, blend=blend)[0])
+        state = self.deform_vertices(self.skin.pose_skeleton(rot, tr, blend=blend)[0])
+        self._remember_pose(rot, tr)
+        return state
+
+    def drag_skeleton(self, vertex_ids, targets, iterations=40, damping=0.0, blend="dqs", fit_translation=True):
+        """Drag picked vertices and let the attached skeleton follow: skin.solve_ik(vertex_ids, targets, ...) from the current pose
+        (the axis-angle parameters of the last pose / pose_sequence / drag_skeleton / fit_skeleton_pose; the rest pose before any), then
+        pose(rotations, root_translation, blend), which leaves the object there.  vertex_ids [H] (mesh_pick's, for one), targets [H,3].
+        Returns (rotations [Nj,3], root_translation [3], the objective's history) as solve_ik does."""
+        if getattr(self, "skin", None) is None:
+            raise ValueError("drag_skeleton: call attach_skeleton(skeleton) first")
+        start = getattr(self, "skeleton_pose", None) or (None, None)
+        rot, tr, history = self.skin.solve_ik(vertex_ids, targets, start[0], start[1], iterations=iterations, damping=damping, blend=blend,
+                                              fit_translation=fit_translation)
+        self.pose(rot, tr, blend=blend)
+        return rot, tr, history
+
+    def fit_skeleton_pose(self, views, iterations, background=None, from_current=True, **fitter_options):
+        """Fit the attached skeleton's pose to photographs: pose_fit.SkeletonPoseFitter(self, **fitter_options).fit(views, iterations,
+        background) - views: (camera, target [3,H,W]) pairs; fitter_options: lr, blend, deg, lambda_dssim, prior.  from_current: start at
+        the current pose (as drag_skeleton does) instead of the rest pose.  Leaves the object at pose(fitted) and returns the fitter
+        (its pose, losses and write_pose)."""
+        from .pose_fit import SkeletonPoseFitter
+        if getattr(self, "skin", None) is None:
+            raise ValueError("fit_skeleton_pose: call attach_skeleton(skeleton) first")
+        start = (getattr(self, "skeleton_pose", None) if from_current else None) or (None, None)
+        fitter = SkeletonPoseFitter(self, rotations=start[0], root_translation=start[1], **fitter_options)
+        fitter.fit(views, iterations, background)
+        return fitter
 
     def simulate(self, steps, handle_targets=None, pinned=None, keep_velocity=True, faces=None, collider_rows=None, **options):
         """`steps` steps of secondary motion (dynamics.MeshDynamics: implicit Euler with the ARAP energy as the potential) from

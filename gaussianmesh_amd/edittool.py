@@ -239,6 +239,19 @@ class ObjectVisualTool:
                 meshes = g.pose_sequence(rotations, root_translation, blend=blend)
         return meshes
 
+    def drag_skeleton_one_gaussian(self, name, vertex_ids, targets, skeleton=None, weight_options=None, **ik_options):
+        """The objects called `name` with their picked vertices vertex_ids [H] dragged to targets [H,3] and the skeleton following
+        (SingleObjectDeform.drag_skeleton: inverse kinematics through gm_skin_pose_bwd).  skeleton: a skinning.Skeleton to attach first
+        (attach_skeleton, with the dict weight_options); None: the one attached before.  ik_options: iterations, damping, blend,
+        fit_translation.  Returns (rotations, root_translation, history) of the last such object (None if there is none)."""
+        result = None
+        for g in self.gaussians_list:
+            if g.get_name() == name:
+                if skeleton is not None:
+                    g.attach_skeleton(skeleton, **(weight_options or {}))
+                result = g.drag_skeleton(vertex_ids, targets, **ik_options)
+        return result
+
     def simulate_one_gaussian(self, name, steps, handle_targets=None, collider_rows=None, **options):
         """`steps` simulated steps of the objects called `name` from their current mesh (SingleObjectDeform.simulate: secondary motion,
         dynamics.MeshDynamics) with their handles at handle_targets [steps,H,3] and, with colliders= among the options, those at

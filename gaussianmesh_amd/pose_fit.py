@@ -2,6 +2,8 @@
 
     MeshPose(rest_vertices, faces)      the parameter V1 [Vm,3]; state() -> differentiable (dV, R, S), the tables of the fused deform pass
     PoseFitter(obj, faces, ...)         step(camera, target, background) -> loss;  fit(views, iterations)
+    SkeletonPose(binding, ...)          the parameters of an attached skeleton: rotations [Nj,3], root_translation [3]; vertices() -> V1
+    SkeletonPoseFitter(obj, ...)        the same fit over those 3 Nj + 3 numbers: every point of the search space is a skinned mesh
 
 The chain of one step: MeshPose.state() -> deform.deform_shade_differentiable (HIP, csrc/gm_deform_bwd.hip on the way back) ->
 GaussianRasterizer(colors_precomp, cov3D_precomp) -> loss.photometric_loss, plus a cotangent-weighted edge-length term, Adam on V1.
@@ -137,6 +139,20 @@ class MeshPose(torch.nn.Module):
         return ((self.e_w * (length - self.e_len) ** 2).sum() / self.e_w.sum()).to(torch.float32)
 
 
+def _render_state(o, state, camera, background, deg):
+    """the differentiable frame of the object o under the tables state = (dV, R, S): image [3,H,W]"""
+    from .deform import deform_shade_differentiable
+    from .rasterizer import GaussianRasterizer
+    from .renderer import _settings
+    dV, R, S = state
+    pos, cov6, rgb = deform_shade_differentiable(o.binding, dV, R, S, o.gaussian_cov, o.gaussian_pos, o.gaussian_feature, camera.camera_center,
+                                                 deg=deg)
+    bg = torch.ones(3, device=pos.device) if background is None else background
+    image, _ = GaussianRasterizer(_settings(camera, bg, 1.0, deg, False))(pos, torch.zeros_like(pos), o.gaussian_o, colors_precomp=rgb,
+                                                                          cov3D_precomp=cov6)
+    return image
+
+
 class PoseFitter:
     """Adam on a MeshPose's V1 against rendered targets.  obj: a deform.SingleObjectDeform (its cloud, its binding); faces [F,3].
     step(camera, target, background=None) -> the loss (a 0-dim tensor; no host wait here - MeshPose.state()'s refusals wait once per
@@ -178,17 +194,7 @@ class PoseFitter:
 
     def render(self, camera, background=None):
         """the differentiable frame of the current pose: image [3,H,W]"""
-        from .deform import deform_shade_differentiable
-        from .rasterizer import GaussianRasterizer
-        from .renderer import _settings
-        o = self.obj
-        dV, R, S = self.pose.state()
-        pos, cov6, rgb = deform_shade_differentiable(o.binding, dV, R, S, o.gaussian_cov, o.gaussian_pos, o.gaussian_feature, camera.camera_center,
-                                                     deg=self.deg)
-        bg = torch.ones(3, device=pos.device) if background is None else background
-        image, _ = GaussianRasterizer(_settings(camera, bg, 1.0, self.deg, False))(pos, torch.zeros_like(pos), o.gaussian_o, colors_precomp=rgb,
-                                                                                   cov3D_precomp=cov6)
-        return image
+        return _render_state(self.obj, self.pose.state(), camera, background, self.deg)
 
     def step(self, camera, target, background=None):
         from .loss import photometric_loss
@@ -215,3 +221,89 @@ class PoseFitter:
             self.obj._set_faces(self.faces)
         self.obj.deform_vertices(V1)
         return V1
+
+
+class SkeletonPose(torch.nn.Module):
+    """The pose of a skinned mesh as parameters: rotations [Nj,3] (axis-angle, one per joint) and root_translation [3], float64 on the
+    binding's device, zero or given.  binding: a skinning.SkinBinding.  vertices() -> V1 [Vm,3] float32, differentiable in both:
+    Skeleton.bone_transforms_torch, then SkinBinding.pose_differentiable (gm_skin_pose, gm_skin_pose_bwd on the way back)."""
+
+    def __init__(self, binding, rotations=None, root_translation=None, blend="dqs"):
+        super().__init__()
+        from .skinning import BLENDS
+        if blend not in BLENDS:
+            raise ValueError('SkeletonPose: blend must be "dqs" or "linear"; got %r' % (blend,))
+        self.binding, self.blend = binding, blend
+        dev, Nj = binding.rest.device, binding.skeleton.Nj
+        given = lambda a, shape: torch.zeros(shape, dtype=torch.float64, device=dev) if a is None else \
+            torch.as_tensor(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, np.float64), device=dev).reshape(shape).clone()
+        try:
+            self.rotations = torch.nn.Parameter(given(rotations, (Nj, 3)))
+            self.root_translation = torch.nn.Parameter(given(root_translation, (3,)))
+        except RuntimeError:
+            raise ValueError("SkeletonPose: rotations must be [%d,3] axis-angle vectors and root_translation [3]" % Nj)
+
+    def vertices(self):
+        M = self.binding.skeleton.bone_transforms_torch(self.rotations[None], self.root_translation[None])
+        return self.binding.pose_differentiable(M, self.blend)[0]
+
+
+class SkeletonPoseFitter:
+    """Adam on a SkeletonPose against rendered targets, for an object with an attached skeleton (obj.attach_skeleton; ValueError
+    without one).  One step: forward kinematics -> SkinBinding.pose_differentiable -> MeshPose.state(V1) -> deform_shade_differentiable
+    -> GaussianRasterizer -> photometric_loss, plus prior * |rotations|^2; step, fit(views, iterations) and losses as PoseFitter has
+    them.  fit leaves the object posed by obj.pose(rotations, root_translation, blend) - the ordinary forward path, so its state is
+    exactly what pose gives - and returns (rotations [Nj,3], root_translation [3]), float64.  write_pose(path) writes the one-frame
+    {"rotations": ..., "root_translation": ...} JSON that edit_sequence --pose_sequence reads.  rotations / root_translation: where the
+    fit starts (None: the rest pose).
+    lr: Adam's step in radians (and in the mesh's units for the root), 0.002 by default.  Adam moves every one of the 3 Nj + 3 numbers
+    by about lr per step whatever the gradient's size, and a chain's rotations compound along it.  A skinned mesh cannot fold the way
+    free vertices do, but it can tear where two bones with very different transforms meet: on the fit test's scene (an open chain of
+    five bones round the closed 24 x 16 torus) the one-ring maps at the seam between the first and the last bone turn into
+    reflections, which MeshPose.state refuses, once the parameters have travelled about 0.25 rad from rest - after 49 steps at
+    lr = 0.005, 25 at 0.01, 14 at 0.02 (tools/skin_bwd_time.py, INTEGRATION.md section AF).  The first default, 0.02, was written down
+    unmeasured and did not survive that run; 0.003 was the largest lr whose 60 steps converged there (loss ratios 0.42 to 0.65, vertex
+    RMS ratio 0.48), and the default 0.002 (0.65 to 0.78, 0.67) keeps a margin below it."""
+
+    def __init__(self, obj, lr=0.002, blend="dqs", deg=3, lambda_dssim=0.2, prior=0.0, rotations=None, root_translation=None):
+        if getattr(obj, "skin", None) is None:
+            raise ValueError("SkeletonPoseFitter: call attach_skeleton(skeleton) first")
+        if not float(lr) > 0.0 or not float(prior) >= 0.0:
+            raise ValueError("SkeletonPoseFitter: lr must be positive and prior not negative; got %r, %r" % (lr, prior))
+        self.obj, self.deg, self.lambda_dssim, self.prior, self.lr = obj, int(deg), float(lambda_dssim), float(prior), float(lr)
+        self.pose = SkeletonPose(obj.skin, rotations, root_translation, blend)
+        self.mesh = MeshPose(obj.vertex, obj.faces)
+        self.optimizer = torch.optim.Adam([self.pose.rotations, self.pose.root_translation], lr=self.lr)
+        self.losses = []
+
+    def render(self, camera, background=None):
+        """the differentiable frame of the current pose: image [3,H,W]"""
+        return _render_state(self.obj, self.mesh.state(self.pose.vertices()), camera, background, self.deg)
+
+    def step(self, camera, target, background=None):
+        from .loss import photometric_loss
+        self.optimizer.zero_grad(set_to_none=True)
+        loss = photometric_loss(self.render(camera, background), target, self.lambda_dssim)
+        if self.prior:
+            loss = loss + self.prior * (self.pose.rotations ** 2).sum().to(loss.dtype)
+        loss.backward()
+        self.optimizer.step()
+        self.losses.append(loss.detach())
+        return self.losses[-1]
+
+    def fit(self, views, iterations, background=None):
+        views = list(views)
+        if not views:
+            raise ValueError("SkeletonPoseFitter.fit: no views")
+        for it in range(int(iterations)):
+            camera, target = views[it % len(views)]
+            self.step(camera, target, background)
+        rotations, root = self.pose.rotations.detach().clone(), self.pose.root_translation.detach().clone()
+        self.obj.pose(rotations, root, blend=self.pose.blend)
+        return rotations, root
+
+    def write_pose(self, path):
+        import json
+        doc = {"rotations": [self.pose.rotations.detach().cpu().tolist()], "root_translation": [self.pose.root_translation.detach().cpu().tolist()]}
+        with open(path, "w") as fh:
+            json.dump(doc, fh)

@@ -386,6 +386,22 @@ int gm_skin_weights(int Vm, int J, const int* row_offsets, const int* cols, cons
                     int* out_ids, float* out_w, double* out_full, double* out_stats, void* workspace, size_t workspace_bytes, void* stream);
 int gm_skin_pose(int T, int Vm, int J, const float* V0, const int* ids, const float* w, const float* transforms, int blend, float* out,
                  void* stream);
+/* gm_skin_pose_bwd: the gradient of gm_skin_pose with respect to its transforms (skinning.skin_pose_differentiable; definition:
+ * csrc/gm_skin.hip, INTEGRATION.md section AF).  g_out float [T,Vm,3] is dL/d out; g_transforms double [T,J,3,4] receives the
+ * vector-Jacobian product of the forward's own float64 arithmetic, the forward's decisions (Shepperd branch, quaternion signs, the
+ * |b_r| < 1e-12 fallback, the sum == 0 row) held constant.  bone_offsets int32 [J+1] / bone_entries int32 [bone_offsets[J]]: per bone
+ * the (vertex, slot) pairs that name it with a nonzero weight, as 4 vertex + slot, ascending (skinning.bone_incidence); offsets are
+ * forced into [0, 4 Vm] and an entry outside [0, 4 Vm) is skipped, the list's consistency with ids being the caller's.  Every element of
+ * g_transforms is written; a bone with an empty list gets exact zeros.  Two launches per 32768 frames, no atomics, float64 sums in one
+ * fixed order: the same bits from call to call, and frame t is bit for bit what a call with T = 1 and its transforms and g_out writes.
+ * Refused with GM_ERR_INVALID_ARG before any GPU work: T < 1, Vm < 1, J outside 1 .. GM_SKIN_BONES_MAX, another blend, a NULL pointer,
+ * g_transforms or the workspace overlapping one another or an input; with GM_ERR_BUFFER a workspace below
+ * gm_skin_pose_bwd_workspace_bytes(T, Vm, J, blend) (O(T Vm), monotonic; 0 for arguments that would be refused).  Stream-ordered, without
+ * device allocation or host synchronisation. */
+size_t gm_skin_pose_bwd_workspace_bytes(int T, int Vm, int J, int blend);
+int gm_skin_pose_bwd(int T, int Vm, int J, const float* V0, const int* ids, const float* w, const float* transforms, int blend,
+                     const float* g_out, const int* bone_offsets, const int* bone_entries, double* g_transforms, void* workspace,
+                     size_t workspace_bytes, void* stream);
 
 /* Secondary motion of a proxy mesh (dynamics.MeshDynamics): T implicit-Euler steps of an elastic mesh whose potential is the ARAP energy,
  * in ONE launch chain - the local/global iteration of projective dynamics (Bouaziz et al. 2014) over gm_arap_solve's CSR, whose global
