@@ -23,12 +23,18 @@ GM_POSE_INTERP_BATCH_MAX = 64
 GM_SKIN_BONES_MAX = 256
 GM_MESH_DYNAMICS_STEPS_MAX = 64
 GM_MESH_CONTACT_COLLIDERS_MAX = 16
+GM_MESH_FIELDS_MAX = 4
 
 
 class BatchFrame(C.Structure):
     """gm_batch_frame (include/gmesh_hip.h): one frame of gm_forward_deformed_batch_async."""
     _fields_ = [("packed", vp), ("viewmatrix", vp), ("projmatrix", vp), ("cam_pos", vp), ("tan_fovx", f32), ("tan_fovy", f32),
                 ("geom_buffer", vp), ("binning_buffer", vp), ("image_buffer", vp), ("out_color", vp), ("radii", vp), ("status_host", vp)]
+
+
+class DynamicsField(C.Structure):
+    """gm_dynamics_field (include/gmesh_hip.h): one prepared grid of gm_mesh_dynamics_fields' table."""
+    _fields_ = [("nx", i32), ("ny", i32), ("nz", i32), ("origin", f32 * 3), ("voxel", f32), ("grid", vp), ("friction", f64)]
 
 
 # name -> (restype, argtypes); mirrors include/gmesh_hip.h one to one
@@ -90,6 +96,8 @@ SIGNATURES = {
     "gm_sdf_grid_sample": (i32, [i32, vp, i32, i32, i32, C.POINTER(f32), f32, vp, vp, vp, vp]),
     "gm_mesh_dynamics_field": (i32, [i32, i32] + [vp] * 6 + [i32] + [vp] * 4 + [f64] * 6 + [i32, i32, f64] + [i32, vp, vp, vp, f64]
                                + [i32, i32, i32, C.POINTER(f32), f32, vp, f64] + [vp, vp, vp, vp, vp, sz, vp]),
+    "gm_mesh_dynamics_fields": (i32, [i32, i32] + [vp] * 6 + [i32] + [vp] * 4 + [f64] * 6 + [i32, i32, f64] + [i32, vp, vp, vp, f64]
+                                + [i32, C.POINTER(DynamicsField), vp] + [vp, vp, vp, vp, vp, sz, vp]),
     "gm_ray_mesh_workspace_bytes": (sz, [i32, i32]),
     "gm_ray_mesh": (i32, [i32, vp, vp, i32, vp, i32, vp, f32, f32, vp, vp, vp, vp, sz, vp]),
     "gm_mesh_winding_workspace_bytes": (sz, [i32, i32]),

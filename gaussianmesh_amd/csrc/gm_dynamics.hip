@@ -31,6 +31,9 @@
 // slots, each pair of kernels one templated source: dyn_contact_local / dyn_field_local are dyn_contact_local_body<FIELD> over the one
 // contact row dyn_contact_row<FIELD>, and dyn_global / dyn_contact_global are dyn_global_body<CONTACT>.  Every kernel symbol is a one-line
 // wrapper with a name and signature of its own, so two builds compare symbol by symbol (tools/kernel_disasm.sh).
+// MOVING FIELDS (gm_mesh_dynamics_fields; the last block of kernels) add a third local kernel, dyn_fields_local: the same local body
+// (dyn_contact_local_rows) over dyn_fields_contact_row, which samples up to four grids, each in its own posed frame, and carries the
+// friction anchor with the obstacle; the row's tail (dyn_contact_target) is shared with dyn_contact_row.
 // Conventions of gm_closest.hip: caller workspace, stream-ordered, no device allocation, no host wait anywhere in this file.
 #include <math.h>
 #include "gm_common.h"
@@ -299,6 +302,20 @@ struct DynField {
   double friction;
 };
 
+// the tail of a contact row: the target c of an active row from the winner's (phi, n, friction) and the friction anchor xs (the u .. c
+// lines of dyn_contact_row's comment), shared with dyn_fields_contact_row
+__device__ __forceinline__ void dyn_contact_target(const double (&X)[3], const double (&xs)[3], const double (&n)[3], double phi, double friction,
+                                                   double (&c)[3]) {
+  const double u[3] = {X[0] - xs[0], X[1] - xs[1], X[2] - xs[2]};
+  const double nu = fma(n[2], u[2], fma(n[1], u[1], n[0] * u[0]));
+  const double t[3] = {fma(-nu, n[0], u[0]), fma(-nu, n[1], u[1]), fma(-nu, n[2], u[2])};
+  const double s = sqrt(fma(t[2], t[2], fma(t[1], t[1], t[0] * t[0])));
+  const double lim = friction * fabs(phi);
+  const double scale = s <= lim ? 1.0 : lim / s;
+#pragma unroll
+  for (int a = 0; a < 3; a++) c[a] = fma(-scale, t[a], fma(-phi, n[a], X[a]));
+}
+
 // The contact of one free row at the iterate X with the step's start xs: returns 1 + k* if the row is active (0 if not) and then its
 // target in c.  FIELD: fld's grid is candidate K; without it fld is not read.  The order of every rounding:
 //   phi_k      dyn_contact_phi, k ascending, kept iff phi_k < best
@@ -334,24 +351,17 @@ __device__ __forceinline__ int dyn_contact_row(const DynColliders& col, const Dy
     }
     friction = col.friction[which];
   }
-  const double u[3] = {X[0] - xs[0], X[1] - xs[1], X[2] - xs[2]};
-  const double nu = fma(n[2], u[2], fma(n[1], u[1], n[0] * u[0]));
-  const double t[3] = {fma(-nu, n[0], u[0]), fma(-nu, n[1], u[1]), fma(-nu, n[2], u[2])};
-  const double s = sqrt(fma(t[2], t[2], fma(t[1], t[1], t[0] * t[0])));
-  const double lim = friction * fabs(best);
-  const double scale = s <= lim ? 1.0 : lim / s;
-#pragma unroll
-  for (int a = 0; a < 3; a++) c[a] = fma(-scale, t[a], fma(-best, n[a], X[a]));
+  dyn_contact_target(X, xs, n, best, friction, c);
   return 1 + which;
 }
 
-// dyn_local_row, then row i's contact into the workspace
-template <bool FIELD>
-__device__ __forceinline__ void dyn_contact_local_body(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+// dyn_local_row, then row i's contact - contact_row(X, xs, c), one of the row functions - into the workspace
+template <class ContactRow>
+__device__ __forceinline__ void dyn_contact_local_rows(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
                                                         const double* __restrict__ weights, const float* __restrict__ V0,
                                                         const double* __restrict__ x, const double* __restrict__ xs,
                                                         const double* __restrict__ mu, const int* __restrict__ free_row,
-                                                        double* __restrict__ R, const DynColliders& col, const DynField& fld,
+                                                        double* __restrict__ R, const DynColliders& col, ContactRow contact_row,
                                                         double* __restrict__ kappa, double* __restrict__ shift, double* __restrict__ diag,
                                                         double* __restrict__ ct) {
   const int i = blockIdx.x * DYN_ROW_THREADS + threadIdx.x;
@@ -365,7 +375,7 @@ __device__ __forceinline__ void dyn_contact_local_body(int Vm, const int* __rest
   if (free_row[i]) {
     const double X[3] = {x[i], x[(size_t)Vm + i], x[2 * (size_t)Vm + i]};
     const double s[3] = {xs[i], xs[(size_t)Vm + i], xs[2 * (size_t)Vm + i]};
-    hit = dyn_contact_row<FIELD>(col, fld, X, s, c);
+    hit = contact_row(X, s, c);
     if (hit) kap = m * col.kch2;
     else c[0] = c[1] = c[2] = 0.0;
   }
@@ -375,6 +385,19 @@ __device__ __forceinline__ void dyn_contact_local_body(int Vm, const int* __rest
 #pragma unroll
   for (int a = 0; a < 3; a++) ct[(size_t)a * Vm + i] = c[a];
   if (col.contact_out) col.contact_out[i] = hit;
+}
+
+template <bool FIELD>
+__device__ __forceinline__ void dyn_contact_local_body(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                        const double* __restrict__ weights, const float* __restrict__ V0,
+                                                        const double* __restrict__ x, const double* __restrict__ xs,
+                                                        const double* __restrict__ mu, const int* __restrict__ free_row,
+                                                        double* __restrict__ R, const DynColliders& col, const DynField& fld,
+                                                        double* __restrict__ kappa, double* __restrict__ shift, double* __restrict__ diag,
+                                                        double* __restrict__ ct) {
+  dyn_contact_local_rows(Vm, row_offsets, cols, weights, V0, x, xs, mu, free_row, R, col,
+                         [&](const double (&X)[3], const double (&s)[3], double (&c)[3]) { return dyn_contact_row<FIELD>(col, fld, X, s, c); },
+                         kappa, shift, diag, ct);
 }
 
 __global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_contact_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
@@ -412,6 +435,109 @@ __global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_field_local_kernel(int Vm
   dyn_contact_local_body<true>(Vm, row_offsets, cols, weights, V0, x, xs, mu, free_row, R, col, fld, kappa, shift, diag, ct);
 }
 
+// ---------------------------------------------------------------------------------------------
+// MOVING FIELDS (gm_mesh_dynamics_fields; INTEGRATION.md section AG): up to GM_MESH_FIELDS_MAX prepared grids, each under a rigid pose
+// (R | t), world = R local + t, of its own per step: `now` is the pose during this step (row t + 1 of field_poses), `before` the one of
+// the step before (row t; row 0: at the state's time).  Field f is candidate K + f behind the analytic colliders.  One more local kernel,
+// dyn_fields_local (dyn_contact_local_rows over dyn_fields_contact_row); the global kernel is dyn_contact_global itself.  The poses are
+// read at addresses the whole wave shares; the grids' descriptions travel in the kernel's arguments and are indexed by unrolled loops,
+// so nothing goes through scratch.
+struct DynFields {
+  int F;
+  SdfGrid grid[GM_MESH_FIELDS_MAX];
+  double friction[GM_MESH_FIELDS_MAX];
+  const double* before;   // [F][3][4]
+  const double* now;      // [F][3][4]
+};
+
+// the normal of analytic collider `which` at X into n (the n lines of dyn_contact_row's comment, and a copy of its code: called from
+// there, dyn_contact_local_kernel compiled to other code - loads and moves changed places); returns its friction
+__device__ __forceinline__ double dyn_collider_normal(const DynColliders& col, int which, const double (&X)[3], double (&n)[3]) {
+  const float* row = col.rows + 4 * which;
+  n[0] = (double)row[0]; n[1] = (double)row[1]; n[2] = (double)row[2];
+  if (col.kind[which] == 1) {
+    const double e[3] = {X[0] - n[0], X[1] - n[1], X[2] - n[2]};
+    const double s = sqrt(fma(e[2], e[2], fma(e[1], e[1], e[0] * e[0])));
+    if (s == 0.0) { n[0] = 0.0; n[1] = 1.0; n[2] = 0.0; }
+    else { n[0] = e[0] / s; n[1] = e[1] / s; n[2] = e[2] / s; }
+  }
+  return col.friction[which];
+}
+
+// dyn_contact_row with the fields as candidates K .. K + F - 1.  The order of every rounding, beyond dyn_contact_row's (float64, no
+// contraction; P = (R | t) = now[f], R_ab = P[4 a + b], t_a = P[4 a + 3]):
+//   phi_k      dyn_contact_phi, k ascending, kept iff phi_k < best
+//   d = X - t per coordinate: one subtraction;  Xl_a = fma(R_2a, d_2, fma(R_1a, d_1, R_0a d_0))                  (R^T d)
+//   phi_K+f    sdf_sample(grid[f], Xl) with its normal nl, f ascending, kept iff phi_K+f < best
+//   n          an analytic winner's: dyn_collider_normal;  field f's: n_a = fma(R_a2, nl_2, fma(R_a1, nl_1, R_a0 nl_0))    (R nl)
+//   the anchor an analytic winner's: xs.  Field f's: xs itself if before[f] and now[f] compare equal in all twelve numbers; else, with
+//              (Rb | tb) = before[f]:  e = xs - tb per coordinate;  q_a = fma(Rb_2a, e_2, fma(Rb_1a, e_1, Rb_0a e_0));
+//              xs'_a = fma(R_a2, q_2, fma(R_a1, q_1, fma(R_a0, q_0, t_a)))
+//   the rest   dyn_contact_target with the anchor in the place of xs
+// Returns 1 + K + f for field f.  With an identity pose Xl = X and n = nl (products with 0 and 1 are exact), so the bits are
+// dyn_contact_row<true>'s.
+__device__ __forceinline__ int dyn_fields_contact_row(const DynColliders& col, const DynFields& fl, const double (&X)[3], const double (&xs)[3],
+                                                      double (&c)[3]) {
+#pragma clang fp contract(off)
+  double best = (double)INFINITY;
+  int which = -1;
+  for (int k = 0; k < col.K; k++) {                                  // uniform addresses: every thread reads collider k
+    const double phi = dyn_contact_phi(col.kind[k], col.rows + 4 * k, X);
+    if (phi < best) { best = phi; which = k; }
+  }
+  double nl[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int f = 0; f < GM_MESH_FIELDS_MAX; f++) {
+    if (f < fl.F) {                                                  // uniform
+      const double* P = fl.now + 12 * f;
+      const double d[3] = {X[0] - P[3], X[1] - P[7], X[2] - P[11]};
+      double Xl[3], m[3];
+#pragma unroll
+      for (int a = 0; a < 3; a++) Xl[a] = fma(P[8 + a], d[2], fma(P[4 + a], d[1], P[a] * d[0]));
+      const double phi = sdf_sample(fl.grid[f], Xl, m);
+      if (phi < best) { best = phi; which = col.K + f; nl[0] = m[0]; nl[1] = m[1]; nl[2] = m[2]; }
+    }
+  }
+  if (!(best < 0.0)) return 0;
+  double n[3] = {0.0, 0.0, 0.0}, anchor[3] = {xs[0], xs[1], xs[2]}, friction = 0.0;
+  if (which < col.K) friction = dyn_collider_normal(col, which, X, n);
+#pragma unroll
+  for (int f = 0; f < GM_MESH_FIELDS_MAX; f++) {
+    if (which == col.K + f) {                                        // (which < K + F: only a field below F was a candidate)
+      const double* P = fl.now + 12 * f;
+      const double* B = fl.before + 12 * f;
+#pragma unroll
+      for (int a = 0; a < 3; a++) n[a] = fma(P[4 * a + 2], nl[2], fma(P[4 * a + 1], nl[1], P[4 * a] * nl[0]));
+      friction = fl.friction[f];
+      bool same = true;
+#pragma unroll
+      for (int j = 0; j < 12; j++) same = same && P[j] == B[j];
+      if (!same) {                                                   // uniform
+        const double e[3] = {xs[0] - B[3], xs[1] - B[7], xs[2] - B[11]};
+        double q[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++) q[a] = fma(B[8 + a], e[2], fma(B[4 + a], e[1], B[a] * e[0]));
+#pragma unroll
+        for (int a = 0; a < 3; a++) anchor[a] = fma(P[4 * a + 2], q[2], fma(P[4 * a + 1], q[1], fma(P[4 * a], q[0], P[4 * a + 3])));
+      }
+    }
+  }
+  dyn_contact_target(X, anchor, n, best, friction, c);
+  return 1 + which;
+}
+
+__global__ __launch_bounds__(DYN_ROW_THREADS) void dyn_fields_local_kernel(int Vm, const int* __restrict__ row_offsets, const int* __restrict__ cols,
+                                                                           const double* __restrict__ weights, const float* __restrict__ V0,
+                                                                           const double* __restrict__ x, const double* __restrict__ xs,
+                                                                           const double* __restrict__ mu, const int* __restrict__ free_row,
+                                                                           double* __restrict__ R, DynColliders col, DynFields fl,
+                                                                           double* __restrict__ kappa, double* __restrict__ shift,
+                                                                           double* __restrict__ diag, double* __restrict__ ct) {
+  dyn_contact_local_rows(Vm, row_offsets, cols, weights, V0, x, xs, mu, free_row, R, col,
+                         [&](const double (&X)[3], const double (&s)[3], double (&c)[3]) { return dyn_fields_contact_row(col, fl, X, s, c); },
+                         kappa, shift, diag, ct);
+}
+
 }  // namespace gm
 
 // ---------------------------------------------------------------------------------------------
@@ -429,10 +555,13 @@ size_t gm_mesh_dynamics_workspace_bytes(int Vm) {
 
 // the checks and launches of the three entries.  col == null: gm_mesh_dynamics; with col->K == 0 and no field the same launches, so the
 // same bits.  fld != null (gm_mesh_dynamics_field; col is there too): the field's local kernel in every iteration, for every K.
+// fls != null with fls->F > 0 (gm_mesh_dynamics_fields; col is there too, fld is not): the moving fields' local kernel, for every K; with
+// F == 0 the launches of col alone.
 struct DynContactArgs { int K; const int* kind; const float* rows; const double* friction; double kc; int* contact_out; };
 struct DynFieldArgs { int nx, ny, nz; const float* origin; float voxel; const float* grid; double friction; };
+struct DynFieldsArgs { int F; const gm_dynamics_field* fields; const double* poses; };
 
-static int dyn_run(const char* fn, const DynContactArgs* col, const DynFieldArgs* fld, int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
+static int dyn_run(const char* fn, const DynContactArgs* col, const DynFieldArgs* fld, const DynFieldsArgs* fls, int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0,
                    const double* mass, const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in,
                    const float* v_in, double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
                    double cg_tolerance, float* X_out, float* v_out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
@@ -458,6 +587,17 @@ static int dyn_run(const char* fn, const DynContactArgs* col, const DynFieldArgs
     if (int rc = check_sdf_grid(fn, fld->nx, fld->ny, fld->nz, fld->origin, fld->voxel, fld->grid)) return rc;
     if (!(fld->friction >= 0.0)) { set_error("%s: field_friction must not be negative", fn); return GM_ERR_INVALID_ARG; }
   }
+  const int F = fls ? fls->F : 0;
+  if (fls) {
+    if (F < 0 || F > GM_MESH_FIELDS_MAX) { set_error("%s: F = %d (0 .. %d)", fn, F, GM_MESH_FIELDS_MAX); return GM_ERR_INVALID_ARG; }
+    if (F > 0 && !fls->fields) { set_error("%s: null pointer (fields, F = %d)", fn, F); return GM_ERR_INVALID_ARG; }
+    for (int f = 0; f < F; f++) {
+      const gm_dynamics_field& g = fls->fields[f];
+      if (int rc = check_sdf_grid(fn, g.nx, g.ny, g.nz, g.origin, g.voxel, g.grid)) return rc;
+      if (!(g.friction >= 0.0)) { set_error("%s: the friction of field %d must not be negative", fn, f); return GM_ERR_INVALID_ARG; }
+    }
+    if (F > 0 && !fls->poses) { set_error("%s: null pointer (field_poses, F = %d)", fn, F); return GM_ERR_INVALID_ARG; }
+  }
   if (!row_offsets || !cols || !weights || !V0 || !mass || !held || !x_in || !v_in || !X_out || !v_out || !workspace ||
       (H > 0 && (!handle_ids || !handle_targets))) {
     set_error("%s: null pointer", fn); return GM_ERR_INVALID_ARG;
@@ -465,7 +605,7 @@ static int dyn_run(const char* fn, const DynContactArgs* col, const DynFieldArgs
   // the inputs are only read and may alias one another; an output or the workspace meets nothing, except that v_out may be v_in (v_in
   // stands for both: it is read once, by the first launch)
   const size_t row = 12 * (size_t)Vm;
-  const ByteRange rg[16] = {{V0, row, "V0", false}, {mass, 8 * (size_t)Vm, "mass", false}, {held, (size_t)Vm, "held", false},
+  ByteRange rg[17 + GM_MESH_FIELDS_MAX] = {{V0, row, "V0", false}, {mass, 8 * (size_t)Vm, "mass", false}, {held, (size_t)Vm, "held", false},
                             {H > 0 ? handle_ids : nullptr, 4 * (size_t)H, "handle_ids", false},
                             {H > 0 ? handle_targets : nullptr, 12 * (size_t)H * T, "handle_targets", false}, {x_in, row, "x_in", false},
                             {v_in, row, "v_in", v_out == v_in}, {X_out, row * T, "X_out", true}, {v_out == v_in ? nullptr : v_out, row, "v_out", true},
@@ -474,7 +614,13 @@ static int dyn_run(const char* fn, const DynContactArgs* col, const DynFieldArgs
                             {K > 0 ? col->rows : nullptr, 16 * (size_t)K * T, "collider_rows", false},
                             {K > 0 ? col->friction : nullptr, 8 * (size_t)K, "collider_friction", false},
                             {col ? col->contact_out : nullptr, 4 * (size_t)Vm * T, "contact_out", true},
-                            {fld ? fld->grid : nullptr, fld ? 16 * (size_t)fld->nx * fld->ny * fld->nz : 0, "field_grid", false}};
+                            {fld ? fld->grid : nullptr, fld ? 16 * (size_t)fld->nx * fld->ny * fld->nz : 0, "field_grid", false},
+                            {F > 0 ? fls->poses : nullptr, 96 * (size_t)F * ((size_t)T + 1), "field_poses", false}};
+  static const char* const grid_names[GM_MESH_FIELDS_MAX] = {"the grid of field 0", "the grid of field 1", "the grid of field 2", "the grid of field 3"};
+  for (int f = 0; f < F; f++) {                                       // (the entries past F stay empty: they overlap nothing)
+    const gm_dynamics_field& g = fls->fields[f];
+    rg[17 + f] = {g.grid, 16 * (size_t)g.nx * g.ny * g.nz, grid_names[f], false};
+  }
   if (int rc = check_ranges(fn, rg)) return rc;
   const size_t need = col ? gm_mesh_dynamics_contact_workspace_bytes(Vm) : gm_mesh_dynamics_workspace_bytes(Vm);
   if (workspace_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need); return GM_ERR_BUFFER; }
@@ -486,7 +632,7 @@ static int dyn_run(const char* fn, const DynContactArgs* col, const DynFieldArgs
   hipLaunchKernelGGL(dyn_init_kernel, rows, threads, 0, s, Vm, row_offsets, weights, mass, held, x_in, v_in, two_k_h2, dt, grav, k.x, k.y, k.xs, k.vs, k.mu,
                      k.diag, k.free_row);
   if (H > 0) hipLaunchKernelGGL(dyn_handles_kernel, dim3((H + DYN_ROW_THREADS - 1) / DYN_ROW_THREADS), threads, 0, s, Vm, H, handle_ids, handle_targets, k.x);
-  if (K == 0 && !fld && col && col->contact_out) GM_HIP(hipMemsetAsync(col->contact_out, 0, 4 * (size_t)Vm * T, s));
+  if (K == 0 && !fld && F == 0 && col && col->contact_out) GM_HIP(hipMemsetAsync(col->contact_out, 0, 4 * (size_t)Vm * T, s));
   const double tol2 = cg_tolerance * cg_tolerance;
   for (int t = 0; t < T; t++)
     for (int it = 0; it < iterations; it++) {
@@ -498,7 +644,7 @@ static int dyn_run(const char* fn, const DynContactArgs* col, const DynFieldArgs
         end.stats_row = stats ? stats + 6 * (size_t)t : nullptr;
         end.next_targets = (H > 0 && t + 1 < T) ? handle_targets + 3 * (size_t)H * (t + 1) : nullptr;
       }
-      if (K == 0 && !fld) {
+      if (K == 0 && !fld && F == 0) {
         hipLaunchKernelGGL(dyn_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.R);
         hipLaunchKernelGGL(dyn_global_kernel, dim3(3), dim3(DYN_THREADS), 0, s, Vm, row_offsets, cols, weights, V0, k.R, k.mu, k.diag, k.free_row, k.x, k.r,
                            k.p, k.q, k.y, k.xs, k.vs, cg_iterations, tol2, end);
@@ -510,6 +656,18 @@ static int dyn_run(const char* fn, const DynContactArgs* col, const DynFieldArgs
         const DynField df = {{reinterpret_cast<const float4*>(fld->grid), fld->nx, fld->ny, fld->nz, {fld->origin[0], fld->origin[1], fld->origin[2]}, fld->voxel},
                              fld->friction};
         hipLaunchKernelGGL(dyn_field_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.xs, k.mu, k.free_row, k.R, dc, df,
+                           kc.kappa, kc.shift, kc.diag, kc.c);
+      } else if (F > 0) {
+        DynFields df = {};
+        df.F = F;
+        for (int f = 0; f < F; f++) {
+          const gm_dynamics_field& g = fls->fields[f];
+          df.grid[f] = {reinterpret_cast<const float4*>(g.grid), g.nx, g.ny, g.nz, {g.origin[0], g.origin[1], g.origin[2]}, g.voxel};
+          df.friction[f] = g.friction;
+        }
+        df.before = fls->poses + 12 * (size_t)F * t;
+        df.now = df.before + 12 * (size_t)F;
+        hipLaunchKernelGGL(dyn_fields_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.xs, k.mu, k.free_row, k.R, dc, df,
                            kc.kappa, kc.shift, kc.diag, kc.c);
       } else {
         hipLaunchKernelGGL(dyn_contact_local_kernel, rows, threads, 0, s, Vm, row_offsets, cols, weights, V0, k.x, k.xs, k.mu, k.free_row, k.R, dc, kc.kappa,
@@ -526,7 +684,7 @@ int gm_mesh_dynamics(int T, int Vm, const int* row_offsets, const int* cols, con
                      const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in, const float* v_in,
                      double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
                      double cg_tolerance, float* X_out, float* v_out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
-  return dyn_run("gm_mesh_dynamics", nullptr, nullptr, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt, stiffness,
+  return dyn_run("gm_mesh_dynamics", nullptr, nullptr, nullptr, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt, stiffness,
                  damping, gx, gy, gz, iterations, cg_iterations, cg_tolerance, X_out, v_out, stats, workspace, workspace_bytes, stream);
 }
 
@@ -542,7 +700,7 @@ int gm_mesh_dynamics_contact(int T, int Vm, const int* row_offsets, const int* c
                              const double* collider_friction, double contact_stiffness, float* X_out, float* v_out, int* contact_out,
                              double* stats, void* workspace, size_t workspace_bytes, void* stream) {
   const DynContactArgs col = {K, collider_kind, collider_rows, collider_friction, contact_stiffness, contact_out};
-  return dyn_run("gm_mesh_dynamics_contact", &col, nullptr, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt,
+  return dyn_run("gm_mesh_dynamics_contact", &col, nullptr, nullptr, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt,
                  stiffness, damping, gx, gy, gz, iterations, cg_iterations, cg_tolerance, X_out, v_out, stats, workspace, workspace_bytes, stream);
 }
 
@@ -555,7 +713,19 @@ int gm_mesh_dynamics_field(int T, int Vm, const int* row_offsets, const int* col
                            void* stream) {
   const DynContactArgs col = {K, collider_kind, collider_rows, collider_friction, contact_stiffness, contact_out};
   const DynFieldArgs fld = {nx, ny, nz, origin, voxel, field_grid, field_friction};
-  return dyn_run("gm_mesh_dynamics_field", &col, &fld, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt,
+  return dyn_run("gm_mesh_dynamics_field", &col, &fld, nullptr, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt,
+                 stiffness, damping, gx, gy, gz, iterations, cg_iterations, cg_tolerance, X_out, v_out, stats, workspace, workspace_bytes, stream);
+}
+
+int gm_mesh_dynamics_fields(int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const double* mass,
+                            const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in, const float* v_in,
+                            double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
+                            double cg_tolerance, int K, const int* collider_kind, const float* collider_rows, const double* collider_friction,
+                            double contact_stiffness, int F, const gm_dynamics_field* fields, const double* field_poses, float* X_out, float* v_out,
+                            int* contact_out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  const DynContactArgs col = {K, collider_kind, collider_rows, collider_friction, contact_stiffness, contact_out};
+  const DynFieldsArgs fls = {F, fields, field_poses};
+  return dyn_run("gm_mesh_dynamics_fields", &col, nullptr, &fls, T, Vm, row_offsets, cols, weights, V0, mass, held, H, handle_ids, handle_targets, x_in, v_in, dt,
                  stiffness, damping, gx, gy, gz, iterations, cg_iterations, cg_tolerance, X_out, v_out, stats, workspace, workspace_bytes, stream);
 }
 

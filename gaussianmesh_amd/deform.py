@@ -612,7 +612,7 @@ class SingleObjectDeform:
         fitter.fit(views, iterations, background)
         return fitter
 
-    def simulate(self, steps, handle_targets=None, pinned=None, keep_velocity=True, faces=None, collider_rows=None, **options):
+    def simulate(self, steps, handle_targets=None, pinned=None, keep_velocity=True, faces=None, collider_rows=None, field_poses=None, **options):
         """`steps` steps of secondary motion (dynamics.MeshDynamics: implicit Euler with the ARAP energy as the potential) from
         mesh_vertex_current (the rest pose the first time): the meshes [steps,Vm,3].  The handles are the ones set_handles /
         set_region_handles chose, scripted to handle_targets [steps,H,3] (in the order of arap.handles); with none chosen the object is
@@ -621,7 +621,10 @@ class SingleObjectDeform:
         gravity, dt, iterations, cg_iterations, cg_tolerance, colliders (dynamics.floor / half_space / sphere, or their tuples, lists or
         dicts) and contact_stiffness; the object is built on the first call and kept while faces, handles, pins and options stay the same
         (colliders are compared by value; field=, a dynamics.SdfGrid, by identity: the operator is reused while the SAME grid object is
-        passed; field_friction goes with it).  collider_rows [steps,K,4]: MeshDynamics.run's, for colliders that move.  Leaves the object at the last frame through deform_vertices, in the manner of drag_sequence.
+        passed; field_friction goes with it; fields=, a list of SdfGrids that move, grid by grid by identity too, field_frictions= by
+        value).  collider_rows [steps,K,4]: MeshDynamics.run's, for colliders that move; field_poses [steps,F,3,4]: MeshDynamics.run's,
+        the poses of fields= during every step - the fields start every call where the previous call's last pose left them, at the
+        identity the first time.  Leaves the object at the last frame through deform_vertices, in the manner of drag_sequence.
         faces [F,3]: for an object built from tensors alone.  Returns the meshes; no host wait."""
         from .dynamics import MeshDynamics
         import numpy as np
@@ -640,8 +643,9 @@ class SingleObjectDeform:
         opts = tuple(sorted((k, id(v) if torch.is_tensor(v) or isinstance(v, np.ndarray) else frozen(v)) for k, v in options.items()))
         dyn = self._operator("dynamics", (hid, pid, opts), lambda: MeshDynamics(self.mesh_graph, None, pinned=list(pid), handles=list(hid), **options))
         current = self.mesh_vertex_current
-        dyn.reset(positions=self.vertex if current is None else current, velocities=getattr(self, "_sim_velocity", None) if keep_velocity else None)
-        meshes = dyn.run(steps, handle_targets, collider_rows=collider_rows)
+        dyn.reset(positions=self.vertex if current is None else current, velocities=getattr(self, "_sim_velocity", None) if keep_velocity else None,
+                  field_poses=dyn.field_poses if dyn.NF else None)
+        meshes = dyn.run(steps, handle_targets, collider_rows=collider_rows, field_poses=field_poses)
         self._sim_velocity = dyn.velocities
         self.deform_vertices(meshes[-1])
         return meshes

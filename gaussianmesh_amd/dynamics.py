@@ -7,7 +7,10 @@ definite with no held row at all - a free body is a valid input, which ArapSolve
 meshes: what render_sequence, SingleObjectDeform.deform_vertices and edit_sequence --save_meshes take.  Definition, ABI and rules:
 INTEGRATION.md section AA.  With colliders (floor / half_space / sphere) the free rows cannot enter them: unilateral contact with
 Coulomb-limited friction (gm_mesh_dynamics_contact), INTEGRATION.md section AB.  With field=SdfGrid(...) they cannot enter a sampled
-signed-distance volume either - the fused volume of the scene's background cloud, say (gm_mesh_dynamics_field), section AC."""
+signed-distance volume either - the fused volume of the scene's background cloud, say (gm_mesh_dynamics_field), section AC.  With
+fields=[SdfGrid, ...] and run(field_poses=) up to four such volumes move rigidly, each on its own, while the mesh is simulated against
+them, with friction in each obstacle's own frame (gm_mesh_dynamics_fields), section AG; rigid_pose / rigid_poses recover those poses
+from a rigidly moved mesh."""
 import ctypes
 
 import numpy as np
@@ -133,6 +136,55 @@ def collider_table(colliders, who="collider_table"):
             np.array([c[2] for c in parsed], np.float64))
 
 
+def _check_poses(who, poses):
+    """host poses [..., 3, 4] as float64, each (R | t) finite with |R^T R - I| <= 1e-6 and det R > 0; else ValueError"""
+    p = np.asarray(poses, np.float64)
+    if not np.isfinite(p).all():
+        raise ValueError("%s: field_poses must be finite" % who)
+    R = p[..., :3]
+    if p.size and (float(np.abs(np.swapaxes(R, -1, -2) @ R - np.eye(3)).max()) > 1e-6 or not bool((np.linalg.det(R) > 0.0).all())):
+        raise ValueError("%s: every pose of field_poses must be (R | t) with R a rotation: |R^T R - I| <= 1e-6 and det R > 0" % who)
+    return p
+
+
+def rigid_pose(rest_vertices, moved_vertices, tolerance=1e-5):
+    """The rigid motion (R | t), float64 [3,4] on the host, that carries rest_vertices [Vm,3] onto moved_vertices [Vm,3]:
+    moved = R rest + t, by Kabsch's method in float64 (the rotation of the SVD of the centred covariance, det R = +1).  What
+    run(field_poses=) wants of an obstacle whose SdfGrid was sampled at its rest mesh.  ValueError for shapes, fewer than three
+    vertices, non-finite vertices, and where the largest distance |R rest_i + t - moved_i| exceeds `tolerance` (in the mesh's own
+    units; the default suits float32 vertices of unit size): a mesh that deforms is refused, not approximated."""
+    who = "rigid_pose"
+    a, b = np.asarray(host(rest_vertices), np.float64), np.asarray(host(moved_vertices), np.float64)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape != b.shape or a.shape[0] < 3:
+        raise ValueError("%s: rest_vertices and moved_vertices must both be [Vm,3] with Vm >= 3; got %s and %s" % (who, tuple(a.shape), tuple(b.shape)))
+    tolerance = _number(who, "tolerance", tolerance, lambda x: x >= 0.0, "; a finite number >= 0")
+    if not np.isfinite(a).all() or not np.isfinite(b).all():
+        raise ValueError("%s: the vertices must be finite" % who)
+    ca, cb = a.mean(axis=0), b.mean(axis=0)
+    U, _, Vt = np.linalg.svd((b - cb).T @ (a - ca))
+    D = np.diag([1.0, 1.0, 1.0 if np.linalg.det(U @ Vt) > 0.0 else -1.0])
+    R = U @ D @ Vt
+    t = cb - R @ ca
+    residual = float(np.linalg.norm(a @ R.T + t - b, axis=1).max())
+    if not residual <= tolerance:
+        raise ValueError("%s: the meshes differ by more than a rigid motion: residual %.3g > tolerance %.3g" % (who, residual, tolerance))
+    return np.concatenate([R, t[:, None]], axis=1)
+
+
+def rigid_poses(rest_vertices, moved_vertices, tolerance=1e-5):
+    """rigid_pose for every mesh of a sequence: moved_vertices [T,Vm,3] -> float64 [T,3,4]; ValueError names the first frame refused"""
+    m = host(moved_vertices)
+    if m.ndim != 3:
+        raise ValueError("rigid_poses: moved_vertices must be [T,Vm,3]; got %s" % (tuple(m.shape),))
+    out = np.zeros((m.shape[0], 3, 4))
+    for k in range(m.shape[0]):
+        try:
+            out[k] = rigid_pose(rest_vertices, m[k], tolerance)
+        except ValueError as e:
+            raise ValueError("rigid_poses: frame %d: %s" % (k, e)) from None
+    return out
+
+
 class SdfGrid:
     """A signed-distance volume prepared for contact (gm_sdf_grid_prepare, INTEGRATION.md section AC).  values: any float32 [nz,ny,nx]
     tensor of signed distances, sample (ix, iy, iz) at origin + (i + 0.5) voxel, negative inside the solid, NaN where nothing is known;
@@ -240,11 +292,18 @@ class MeshDynamics:
     INTEGRATION.md section AC) with the friction field_friction.  It is candidate K behind the K analytic colliders: a tie goes to the
     analytic one, want_contacts reports 1 + K, and a row outside the grid, next to an unknown sample or on a zero gradient is not in
     contact with it.  With field=None every call goes where it went without the argument.  ValueError for a field that is no SdfGrid or
-    lives on another device, a field_friction that is negative or not finite."""
+    lives on another device, a field_friction that is negative or not finite.
+    fields: up to GM_MESH_FIELDS_MAX (4) SdfGrids on this object's device, each an obstacle that MOVES rigidly on its own
+    (gm_mesh_dynamics_fields, INTEGRATION.md section AG), with field_frictions (one number each; None: all 0).  Field f is candidate
+    K + f, want_contacts reports 1 + K + f, and every field has a pose (R | t), world = R local + t, that run's and step's field_poses
+    move; the object keeps each field's last pose (the identity at first, reset(field_poses=) sets it).  Friction acts in the
+    obstacle's frame: a row is held back towards the point of the obstacle it touched at the step's start, so a rough plate carries
+    what lies on it.  Not together with field=, which keeps its own entry; an empty list is no fields at all.  ValueError for what
+    field= refuses of each grid, more than 4, field_frictions of another length, both field= and fields=."""
 
     def __init__(self, rest_vertices, faces, pinned=(), handles=(), mass="area", density=1.0, stiffness=10.0, damping=0.02, gravity=(0.0, 0.0, 0.0),
                  dt=1.0 / 30.0, iterations=3, cg_iterations=64, cg_tolerance=1e-6, device="cuda", colliders=(), contact_stiffness=1.0e4, field=None,
-                 field_friction=0.0):
+                 field_friction=0.0, fields=None, field_frictions=None):
         who = "MeshDynamics"
         table = collider_table(colliders, who)
         if field is not None and not isinstance(field, SdfGrid):
@@ -257,6 +316,28 @@ class MeshDynamics:
                                                                                  else torch.device("cuda", torch.cuda.current_device()))):
             raise ValueError("%s: the field is on %s, the mesh on %s" % (who, field.device, self.device))
         self.field, self.field_friction = field, field_friction
+        if fields is not None and (isinstance(fields, SdfGrid) or not isinstance(fields, (tuple, list))):
+            raise ValueError("%s: fields must be a sequence of SdfGrids; got %r" % (who, type(fields).__name__))
+        fields = () if fields is None else tuple(fields)
+        if fields and field is not None:
+            raise ValueError("%s: give field= or fields=, not both" % who)
+        if len(fields) > _lib.GM_MESH_FIELDS_MAX:
+            raise ValueError("%s: %d fields; at most %d" % (who, len(fields), _lib.GM_MESH_FIELDS_MAX))
+        if field_frictions is None:
+            field_frictions = (0.0,) * len(fields)
+        if not isinstance(field_frictions, (tuple, list, np.ndarray)) or len(field_frictions) != len(fields):
+            raise ValueError("%s: field_frictions must hold one number per field (%d); got %r" % (who, len(fields), field_frictions))
+        field_frictions = tuple(_friction(who, mu) for mu in field_frictions)
+        here = self.device if self.device.index is not None or self.device.type != "cuda" else torch.device("cuda", torch.cuda.current_device())
+        for f in fields:
+            if not isinstance(f, SdfGrid):
+                raise ValueError("%s: fields must hold SdfGrids; got %r" % (who, type(f).__name__))
+            if self.device.type != "cuda" or f.device != here:
+                raise ValueError("%s: a field is on %s, the mesh on %s" % (who, f.device, self.device))
+        self.fields, self.field_frictions, self.NF = fields, field_frictions, len(fields)
+        self._table = (_lib.DynamicsField * max(self.NF, 1))(*[
+            _lib.DynamicsField(f.nx, f.ny, f.nz, (ctypes.c_float * 3)(*f.origin.tolist()), f.voxel, f.grid.data_ptr(), mu) for f, mu in zip(fields, field_frictions)])
+        self._poses = None
         if isinstance(mass, str):
             if mass != "area":
                 raise ValueError('%s: mass must be "area" or [Vm] numbers; got %r' % (who, mass))
@@ -310,9 +391,23 @@ class MeshDynamics:
             self._held = on_device(held.astype(np.uint8), torch.uint8, self.device)
             self._handle_ids = on_device(h.astype(np.int32), torch.int32, self.device) if len(h) else None
 
-    def reset(self, positions=None, velocities=None):
-        """Set the state: positions [Vm,3] (None: the rest pose), velocities [Vm,3] (None: zero); both are copied."""
+    def _poses_arg(self, who, poses, lead):
+        """field_poses of shape lead + [F,3,4] as a float64 tensor on the device: a device tensor as it is, a host array checked"""
+        if self.NF == 0:
+            raise ValueError("%s: field_poses given, but there are no fields" % who)
+        poses = poses if hasattr(poses, "shape") else np.asarray(poses, np.float64)
+        if tuple(poses.shape) != tuple(lead) + (self.NF, 3, 4):
+            raise ValueError("%s: field_poses must be [%s]; got %s" % (who, ",".join(str(n) for n in tuple(lead) + (self.NF, 3, 4)), tuple(poses.shape)))
+        if not (torch.is_tensor(poses) and poses.device.type == "cuda"):
+            poses = _check_poses(who, host(poses))
+        return poses
+
+    def reset(self, positions=None, velocities=None, field_poses=None):
+        """Set the state: positions [Vm,3] (None: the rest pose), velocities [Vm,3] (None: zero), field_poses [F,3,4] (None: every
+        field at the identity - where its grid was sampled); all are copied."""
         who = "MeshDynamics.reset"
+        if field_poses is not None:
+            field_poses = self._poses_arg(who, field_poses, ())
         if positions is not None and (not hasattr(positions, "shape") or tuple(positions.shape) != (self.Vm, 3)):
             raise ValueError("%s: positions must be [%d,3]; got %s" % (who, self.Vm, tuple(getattr(positions, "shape", ()))))
         if velocities is not None and (not hasattr(velocities, "shape") or tuple(velocities.shape) != (self.Vm, 3)):
@@ -320,6 +415,15 @@ class MeshDynamics:
         self.mesh.need_device(who)
         self._x = self.rest.clone() if positions is None else self.mesh.rows_f32(positions, who, "positions", copy=True)
         self._v = torch.zeros_like(self.rest) if velocities is None else self.mesh.rows_f32(velocities, who, "velocities", copy=True)
+        if self.NF:
+            eye = np.tile(np.eye(3, 4), (self.NF, 1, 1)) if field_poses is None else field_poses
+            self._poses = on_device(eye, torch.float64, self.rest.device).clone()
+
+    @property
+    def field_poses(self):
+        """every field's pose at the state's time, float64 [F,3,4] on the device (a copy)"""
+        self.mesh.need_device("MeshDynamics.field_poses")
+        return None if self._poses is None else self._poses.clone()
 
     @property
     def positions(self):
@@ -333,10 +437,11 @@ class MeshDynamics:
         self.mesh.need_device("MeshDynamics.velocities")
         return self._v.clone()
 
-    def step(self, handle_targets=None, collider_rows=None):
+    def step(self, handle_targets=None, collider_rows=None, field_poses=None):
         """One step: the new positions [Vm,3]; handle_targets [H,3] (in the order of `handles`) exactly when there are handles;
-        collider_rows [K,4]: where the colliders are in this step (None: where they were built).
-        run(1, handle_targets[None], collider_rows[None])[0]."""
+        collider_rows [K,4]: where the colliders are in this step (None: where they were built); field_poses [F,3,4]: where the
+        fields are during this step (None: where they were).
+        run(1, handle_targets[None], collider_rows[None], field_poses=field_poses[None])[0]."""
         def one_step(a, name, n, width):
             if a is None:
                 return None
@@ -345,9 +450,14 @@ class MeshDynamics:
                 raise ValueError("MeshDynamics.step: %s must be [%d,%d]; got %s" % (name, n, width, tuple(a.shape)))
             return a[None]
         collider_rows = one_step(collider_rows, "collider_rows", self.K, 4)
-        return self.run(1, one_step(handle_targets, "handle_targets", len(self.handles), 3), collider_rows=collider_rows)[0]
+        if field_poses is not None:
+            field_poses = field_poses if hasattr(field_poses, "shape") else np.asarray(field_poses, np.float64)
+            if len(field_poses.shape) != 3:
+                raise ValueError("MeshDynamics.step: field_poses must be [%d,3,4]; got %s" % (self.NF, tuple(field_poses.shape)))
+            field_poses = field_poses[None]
+        return self.run(1, one_step(handle_targets, "handle_targets", len(self.handles), 3), collider_rows=collider_rows, field_poses=field_poses)[0]
 
-    def run(self, steps, handle_targets=None, out=None, want_stats=False, collider_rows=None, want_contacts=False):
+    def run(self, steps, handle_targets=None, out=None, want_stats=False, collider_rows=None, want_contacts=False, field_poses=None):
         """`steps` steps from the state, which they advance: the positions after every step, [steps,Vm,3] float32 on the device.
         handle_targets [steps,H,3]: where the handles are in every step - required exactly when there are handles.  Cut into launch
         chains of at most GM_MESH_DYNAMICS_STEPS_MAX (64) steps; the state is rounded to float32 at every step boundary, so run(n) is
@@ -357,8 +467,13 @@ class MeshDynamics:
         is how they move; a tensor on the device is taken as it is, a host array is checked (finite, normals of unit length within 1e-4,
         radii positive); None: the rows they were built with, in every step.  want_contacts: also int32 [steps,Vm], 1 + the index of the
         collider every row was in contact with in the step's last iteration, 0 elsewhere; returned after the meshes (and before stats).
+        field_poses [steps,F,3,4] float64: every field's pose (R | t) DURING each step, world = R local + t, which is how the obstacles
+        move; the pose before the first step is the one the object kept (the last step's of the call before, the identity at first,
+        reset's), and the last one given is kept for the next call, so run(n) stays n calls of step().  A tensor on the device is taken
+        as it is, a host array is checked (finite, |R^T R - I| <= 1e-6, det R > 0); None: every field stays where it is.
         Stream-ordered; nothing here waits for the device (reading stats does).  ValueError for steps < 1, shapes, handle_targets without
-        handles and handles without handle_targets, collider_rows without colliders; GmeshError without a device."""
+        handles and handles without handle_targets, collider_rows without colliders, field_poses without fields; GmeshError without a
+        device."""
         who = "MeshDynamics.run"
         if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
             raise ValueError("%s: steps = %r; an integer >= 1" % (who, steps))
@@ -383,16 +498,22 @@ class MeshDynamics:
                 flat = self.collider_kinds == HALF_SPACE
                 if not np.isfinite(r).all() or bool((np.abs(np.linalg.norm(r[:, flat, :3], axis=2) - 1.0) > 1e-4).any()) or bool((r[:, ~flat, 3] <= 0.0).any()):
                     raise ValueError("%s: collider_rows must be finite, a half-space's normal of unit length, a sphere's radius positive" % who)
+        F = self.NF
+        if field_poses is not None:
+            field_poses = self._poses_arg(who, field_poses, (T,))
         self.mesh.need_device(who)
         dev = self.rest.device
+        if F:                                                          # row 0: the poses kept; row t + 1: step t's
+            moving = field_poses is not None
+            table = torch.cat([self._poses[None], on_device(field_poses, torch.float64, dev) if moving else self._poses[None].expand(T, F, 3, 4)], 0)
         hp = None if handle_targets is None else on_device(handle_targets, torch.float32, dev)
         out = self.mesh.out_f32(out, (T, Vm, 3), who)
         stats = torch.zeros((T, 6), dtype=torch.float64, device=dev) if want_stats else None
-        plain = K == 0 and field is None                               # exactly the call there was before there were colliders
+        plain = K == 0 and field is None and F == 0                               # exactly the call there was before there were colliders
         contacts = None
         if want_contacts:
             contacts = (torch.zeros if plain else torch.empty)((T, Vm), dtype=torch.int32, device=dev)
-        entry = "gm_mesh_dynamics_field" if field is not None else "gm_mesh_dynamics" if K == 0 else "gm_mesh_dynamics_contact"
+        entry = "gm_mesh_dynamics_fields" if F else "gm_mesh_dynamics_field" if field is not None else "gm_mesh_dynamics" if K == 0 else "gm_mesh_dynamics_contact"
         if self._ws is None:
             need = getattr(_lib.lib(), ("gm_mesh_dynamics" if plain else "gm_mesh_dynamics_contact") + "_workspace_bytes")(Vm)
             self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)
@@ -414,7 +535,11 @@ class MeshDynamics:
             else:
                 col = (K, self._kinds, cp[:e - s] if collider_rows is None else cp[s:e], self._mus, self.contact_stiffness)
             outs = (out[s:e], self._v) + (() if plain else (part(contacts),)) + (part(stats),)
+            if F:
+                fld = (F, self._table, table[s:e + 1])
             enqueue(dev, entry, *state, *col, *fld, *outs, workspace=self._ws)
         self._x.copy_(out[T - 1])
+        if F and moving:
+            self._poses.copy_(table[T])
         got = (out,) + ((contacts,) if want_contacts else ()) + ((stats,) if want_stats else ())
         return got if len(got) > 1 else out

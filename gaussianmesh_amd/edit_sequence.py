@@ -9,7 +9,7 @@
         [--dynamics [--settle N] [--dt S] [--stiffness K] [--damping G] [--gravity X Y Z]
                     [--floor H] [--friction MU] [--contact_stiffness KC] [--colliders FILE.json]
                     [--background_contact [RES] [--contact_margin M]]
-                    [--obstacle_mesh FILE.obj [--obstacle_resolution RES] [--obstacle_margin M]]]
+                    [--obstacle_mesh FILE.obj [--obstacle_resolution RES] [--obstacle_margin M] [--obstacle_motion FILE.json]]]
 
 --object_gaussian: the mesh-bound Gaussian PLY of the training code; --object_plain_gaussian: a plain 3DGS PLY instead, bound to the closest
 faces of the mesh on load (ObjectVisualTool.add_plain_gaussian).  Exactly one of the two.
@@ -76,6 +76,10 @@ are sampled on a volume of --obstacle_resolution RES (default 128) voxels along 
 --obstacle_margin M (default 0.5) times that side (dynamics.SdfGrid.from_mesh); the volume is one more collider, behind --floor and
 --colliders, with --friction as its friction and --contact_stiffness as everyone's.  Refused without --dynamics and together with
 --background_contact (a simulation takes one volume); --obstacle_resolution and --obstacle_margin are refused without it.
+--obstacle_motion FILE.json (with --obstacle_mesh): the obstacle MOVES rigidly - a JSON list with one 3x4 or 4x4 matrix (R | t) per
+simulated frame (--settle's frames included), world = R p + t for a point p of FILE.obj; the mesh is pushed and carried by it, with
+--friction acting in the obstacle's own frame (MeshDynamics(fields=), run(field_poses=)).  Refused without --obstacle_mesh, with another
+number of frames than the simulation has, and with a matrix that is not finite or whose R is no rotation (|R^T R - I| <= 1e-6, det R > 0).
 --camera_id N: every frame from camera N of MODEL_DIR/cameras.json, as in the reference loop; without it the frames step through the
 cameras, one per frame, cycling.  Frames go through ObjectVisualTool.render_sequence (K frames per launch chain); each is written as
 {i:05d}.png, and with --save_maps also {i:05d}_depth.npy / {i:05d}_alpha.npy ([H,W] float32, gm_forward_1_aux's definitions).  The
@@ -183,6 +187,32 @@ def read_pose_sequence(path, joints=None):
     return rot, tr
 
 
+def read_obstacle_motion(path):
+    """An --obstacle_motion file -> poses float64 [T,3,4]; SystemExit naming what is wrong with it.  Host work only."""
+    import json
+    import numpy as np
+    bad = lambda what: SystemExit("edit_sequence: %s: %s" % (path, what))
+    try:
+        with open(path) as fh:
+            doc = json.load(fh)
+    except (OSError, ValueError) as e:
+        raise bad("cannot read it as JSON (%s)" % e)
+    try:
+        m = np.asarray(doc, np.float64)
+    except (TypeError, ValueError):
+        m = None
+    if m is None or m.ndim != 3 or m.shape[0] == 0 or tuple(m.shape[1:]) not in ((3, 4), (4, 4)):
+        raise bad("must hold a JSON list of 3x4 or 4x4 matrices, one per frame, at least one; got shape %s" % (None if m is None else m.shape,))
+    if m.shape[1] == 4 and not (np.isfinite(m).all() and np.array_equal(m[:, 3], np.tile([0.0, 0.0, 0.0, 1.0], (len(m), 1)))):
+        raise bad("the last row of a 4x4 matrix must be 0 0 0 1")
+    m = m[:, :3]
+    R = m[:, :, :3]
+    for k in range(len(m)):                                            # MeshDynamics' host check, frame by frame
+        if not np.isfinite(m[k]).all() or float(np.abs(R[k].T @ R[k] - np.eye(3)).max()) > 1e-6 or not np.linalg.det(R[k]) > 0.0:
+            raise bad("frame %d: the matrix must be finite, (R | t) with R a rotation (|R^T R - I| <= 1e-6, det R > 0)" % k)
+    return np.ascontiguousarray(m)
+
+
 def read_colliders(path, friction):
     """A --colliders file -> (colliders: a list of dicts for MeshDynamics, moving: {index: centres [[x, y, z], ...]}); SystemExit naming
     what is wrong with it.  Host work only, no numpy; the numbers themselves are MeshDynamics' to check."""
@@ -248,6 +278,7 @@ def main(argv=None):
     parser.add_argument("--obstacle_mesh", type=str, default=None, metavar="FILE.obj")
     parser.add_argument("--obstacle_resolution", type=int, default=None, metavar="RES")
     parser.add_argument("--obstacle_margin", type=float, default=None, metavar="M")
+    parser.add_argument("--obstacle_motion", type=str, default=None, metavar="FILE.json")
     parser.add_argument("--camera_id", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=4)
     parser.add_argument("--save_maps", action="store_true", default=False)
@@ -308,6 +339,9 @@ def main(argv=None):
     for flag, value in (("--obstacle_resolution", args.obstacle_resolution), ("--obstacle_margin", args.obstacle_margin)):
         if value is not None and args.obstacle_mesh is None:
             raise SystemExit("edit_sequence: %s shapes the volume of --obstacle_mesh and needs it" % flag)
+    if args.obstacle_motion is not None and args.obstacle_mesh is None:
+        raise SystemExit("edit_sequence: --obstacle_motion moves the solid of --obstacle_mesh and needs it")
+    obstacle_poses = None if args.obstacle_motion is None or not args.dynamics else read_obstacle_motion(args.obstacle_motion)
     if args.obstacle_mesh is not None and args.dynamics and not os.path.isfile(args.obstacle_mesh):
         raise SystemExit("edit_sequence: --obstacle_mesh %s: no such file" % args.obstacle_mesh)
     if args.obstacle_resolution is not None and args.obstacle_resolution < 2:
@@ -390,7 +424,7 @@ def main(argv=None):
                 pos = torch.cat([pos, pos[-1:].expand(args.settle, -1, -1)], 0)
             material = {k: v for k, v in (("dt", args.dt), ("stiffness", args.stiffness), ("damping", args.damping),
                                           ("gravity", None if args.gravity is None else tuple(args.gravity))) if v is not None}
-            rows = None
+            rows = poses = None
             if colliders:
                 material["colliders"] = colliders
             if args.background_contact is not None:                                   # the background cloud itself, fused from every camera
@@ -399,13 +433,19 @@ def main(argv=None):
                 material["field_friction"] = args.friction or 0.0
             if args.obstacle_mesh is not None:                                        # a triangle mesh as a static solid
                 from .dynamics import SdfGrid
+                if obstacle_poses is not None and len(obstacle_poses) != len(pos):
+                    raise SystemExit("edit_sequence: --obstacle_motion %s: %d matrices, but the simulation has %d frames"
+                                     % (args.obstacle_motion, len(obstacle_poses), len(pos)))
                 try:
                     ov, of = read_obj(args.obstacle_mesh)
-                    material["field"] = SdfGrid.from_mesh(ov, of, resolution=128 if args.obstacle_resolution is None else args.obstacle_resolution,
-                                                          margin=0.5 if args.obstacle_margin is None else args.obstacle_margin, device=obj.vertex.device)
+                    grid = SdfGrid.from_mesh(ov, of, resolution=128 if args.obstacle_resolution is None else args.obstacle_resolution,
+                                             margin=0.5 if args.obstacle_margin is None else args.obstacle_margin, device=obj.vertex.device)
                 except ValueError as e:
                     raise SystemExit("edit_sequence: --obstacle_mesh %s: %s" % (args.obstacle_mesh, e))
-                material["field_friction"] = args.friction or 0.0
+                if obstacle_poses is None:
+                    material["field"], material["field_friction"] = grid, args.friction or 0.0
+                else:                                                                 # the solid moves: a field with a pose per frame
+                    material["fields"], material["field_frictions"], poses = [grid], [args.friction or 0.0], obstacle_poses[:, None]
             if (colliders or args.background_contact is not None or args.obstacle_mesh is not None) and args.contact_stiffness is not None:
                 material["contact_stiffness"] = args.contact_stiffness
             if moving:                                                                # the centres of the moving balls, frame by frame
@@ -418,7 +458,7 @@ def main(argv=None):
                 except ValueError as e:
                     raise SystemExit("edit_sequence: --colliders: %s" % e)
             try:
-                meshes = list(obj.simulate(len(pos), pos, collider_rows=rows, **material))
+                meshes = list(obj.simulate(len(pos), pos, collider_rows=rows, field_poses=poses, **material))
             except ValueError as e:
                 raise SystemExit("edit_sequence: --dynamics: %s" % e)
         else:

@@ -252,16 +252,17 @@ class ObjectVisualTool:
                 result = g.drag_skeleton(vertex_ids, targets, **ik_options)
         return result
 
-    def simulate_one_gaussian(self, name, steps, handle_targets=None, collider_rows=None, **options):
+    def simulate_one_gaussian(self, name, steps, handle_targets=None, collider_rows=None, field_poses=None, **options):
         """`steps` simulated steps of the objects called `name` from their current mesh (SingleObjectDeform.simulate: secondary motion,
         dynamics.MeshDynamics) with their handles at handle_targets [steps,H,3] and, with colliders= among the options, those at
         collider_rows [steps,K,4] (None: where they were built), with field= (a dynamics.SdfGrid, SceneVisualTool.background_field's for
-        one) and field_friction= the sampled volume as one more collider; the objects are left at the last frame.  Returns the
+        one) and field_friction= the sampled volume as one more collider, with fields= (object_fields' for one), field_frictions= and
+        field_poses [steps,F,3,4] up to four volumes that move rigidly; the objects are left at the last frame.  Returns the
         meshes [steps, Vm, 3] of the last such object (None if there is none)."""
         meshes = None
         for g in self.gaussians_list:
             if g.get_name() == name:
-                meshes = g.simulate(steps, handle_targets, collider_rows=collider_rows, **options)
+                meshes = g.simulate(steps, handle_targets, collider_rows=collider_rows, field_poses=field_poses, **options)
         return meshes
 
     def drag_region_one_gaussian(self, name, handle_vertices, displacements, grab_radius, free_radius=None, anchor_vertices=(), **solve_options):
@@ -569,6 +570,36 @@ class SceneVisualTool(ObjectVisualTool):
             phi = grid_values(v, f, origin, voxel, shape, device=self.device)
             values = phi if values is None else torch.minimum(values, phi)
         return SdfGrid(values, origin, voxel, device=values.device)
+
+    def object_fields(self, names, resolution=128, margin=0.5):
+        """Objects of the scene as obstacles that MOVE: one dynamics.SdfGrid per name, in the order of `names`, for simulate(fields=)
+        of an object that is not among them (INTEGRATION.md section AG).  Each grid is sampled at the REST mesh of the objects called
+        that name, on a lattice of its own (that mesh's box grown by margin times its longest side, `resolution` voxels along the
+        longest side), so the pose (R | t) that field_poses gives it is the one that carries the rest mesh to where the object is:
+        dynamics.rigid_poses(rest, frames).  Reads the meshes on the host.  ValueError for no names, more than
+        GM_MESH_FIELDS_MAX, a name no object has, and what mesh_sdf.box_lattice refuses."""
+        from . import _lib
+        from .dynamics import SdfGrid
+        from .mesh_sdf import box_lattice, grid_values
+        who = "SceneVisualTool.object_fields"
+        names = [names] if isinstance(names, str) else list(names)
+        if not names or len(names) > _lib.GM_MESH_FIELDS_MAX:
+            raise ValueError("%s: %d objects named (1 .. %d)" % (who, len(names), _lib.GM_MESH_FIELDS_MAX))
+        grids = []
+        for n in names:
+            found = [o for o in self.gaussians_list if o.get_name() == n]
+            if not found:
+                raise ValueError("%s: no object named %r" % (who, n))
+            meshes = [(o.vertex.detach().cpu().numpy().astype(np.float32), o.faces.cpu().numpy()) for o in found]
+            lo = np.min([v.min(axis=0) for v, _ in meshes], axis=0)
+            hi = np.max([v.max(axis=0) for v, _ in meshes], axis=0)
+            origin, voxel, shape = box_lattice(who, lo, hi, resolution, None, margin)
+            values = None
+            for v, f in meshes:
+                phi = grid_values(v, f, origin, voxel, shape, device=self.device)
+                values = phi if values is None else torch.minimum(values, phi)
+            grids.append(SdfGrid(values, origin, voxel, device=values.device))
+        return grids
 
     def save_baked(self, path, name=None, deg=3, include_background=False):
         """ObjectVisualTool.save_baked for a scene; with include_background the background's raw rows come first, bit for bit as loaded:

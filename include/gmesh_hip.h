@@ -516,6 +516,46 @@ int gm_mesh_dynamics_field(int T, int Vm, const int* row_offsets, const int* col
                            double field_friction, float* X_out, float* v_out, int* contact_out, double* stats, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* gm_mesh_dynamics_field with a TABLE of F prepared grids, each under a rigid pose of its own per step: obstacles that move
+ * (dynamics.MeshDynamics(fields=[...]), run(field_poses=); INTEGRATION.md section AG).  Every argument of gm_mesh_dynamics_contact means
+ * what it means there.  fields: F entries on the HOST, 0 <= F <= GM_MESH_FIELDS_MAX, each the (nx, ny, nz, origin, voxel, grid, friction)
+ * of gm_mesh_dynamics_field; the grids themselves are on the device and static over the call.  field_poses: double [T + 1,F,3,4] on the
+ * device, row-major (R | t) with world = R local + t; R is to be a rotation (THE CALLER'S CHECK: dynamics.MeshDynamics checks host
+ * arrays; another matrix gives the arithmetic below, no fault).  Row 0 is every field's pose at the state's time, before the call's first
+ * step; row t + 1 is its pose during step t, in all its iterations - as step t reads row t of collider_rows.
+ * Field f is candidate K + f behind the K analytic colliders, f ascending, each taken with the same phi < best: a tie goes to the lower
+ * index, a NaN is never chosen.  At the iterate X, with P = (R | t) of row t + 1, in float64 without contraction:
+ *   d = X - t per coordinate;  Xl_a = fma(R_2a, d_2, fma(R_1a, d_1, R_0a d_0))        (R^T d: column a of R)
+ *   (phi, nl) = gm_sdf_grid_sample's at Xl;  kept iff phi < best
+ *   the winner's normal  n_a = fma(R_a2, nl_2, fma(R_a1, nl_1, R_a0 nl_0))              (R nl: row a of R)
+ * FRICTION IN THE OBSTACLE'S FRAME.  The tangential pull of gm_mesh_dynamics_contact goes back towards xs, the row's position at the
+ * step's start.  When field f wins, the anchor is the point of the obstacle that was at xs, carried to where the obstacle is now:
+ * with Pb = row t, Pn = row t + 1 of field f,
+ *   e = xs - tb per coordinate;  q_a = fma(Rb_2a, e_2, fma(Rb_1a, e_1, Rb_0a e_0));  xs'_a = fma(Rn_a2, q_2, fma(Rn_a1, q_1, fma(Rn_a0, q_0, tn_a)))
+ * and where the twelve numbers of Pb and Pn compare equal xs' = xs itself, with no arithmetic.  Then u = X - xs' and the rest is
+ * gm_mesh_dynamics_field's, with field f's friction.  An analytic collider that wins keeps the world-frame anchor xs.  contact_out
+ * reports 1 + K + f.  With identity poses the bits are gm_mesh_dynamics_field's (Xl = X - 0 and n = nl exactly: every product with 0 or
+ * 1 is exact); with F == 0 the launches are gm_mesh_dynamics_contact's (field_poses is not read and may be NULL).  A step stays
+ * 2 * iterations launches (a local kernel of its own, gm_mesh_dynamics_contact's global kernel); the workspace is
+ * gm_mesh_dynamics_contact_workspace_bytes(Vm); no atomics, nothing waits for the device.
+ * Refused as gm_mesh_dynamics_contact refuses, and with GM_ERR_INVALID_ARG: F < 0 or F > GM_MESH_FIELDS_MAX, a NULL table with F > 0,
+ * per field what gm_mesh_dynamics_field refuses of its grid (sides, samples, voxel, origin, a NULL or misaligned grid) and a friction that
+ * is negative or NaN, a NULL field_poses with F > 0, any overlap of a grid or of the poses with an output or the workspace. */
+#define GM_MESH_FIELDS_MAX 4
+typedef struct gm_dynamics_field {
+  int nx, ny, nz;
+  float origin[3];
+  float voxel;
+  const float* grid;   /* device, float [nz,ny,nx,4], 16-byte aligned */
+  double friction;
+} gm_dynamics_field;
+int gm_mesh_dynamics_fields(int T, int Vm, const int* row_offsets, const int* cols, const double* weights, const float* V0, const double* mass,
+                            const unsigned char* held, int H, const int* handle_ids, const float* handle_targets, const float* x_in, const float* v_in,
+                            double dt, double stiffness, double damping, double gx, double gy, double gz, int iterations, int cg_iterations,
+                            double cg_tolerance, int K, const int* collider_kind, const float* collider_rows, const double* collider_friction,
+                            double contact_stiffness, int F, const gm_dynamics_field* fields, const double* field_poses, float* X_out, float* v_out,
+                            int* contact_out, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* First hit of every ray on a mesh: what takes an editor from a pixel to a vertex of the current, deformed proxy mesh
  * (mesh_pick.ray_mesh_hits / pick / visible_vertices).  The reference has no such stage: the result is defined by arithmetic.
  * origins, dirs float [R,3], vertices float [Vm,3], faces int32 [F,3] vertex ids.  out_t float [R], out_face int32 [R], out_uv float
